@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- forward attention TFLOP/s on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg2nc|cfg1|cfg1c|cfg3|cfg4|anchor]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg2nc|cfg1|cfg1c|cfg3|cfg4|anchor] [--full]
+                    [--dump-outputs DIR]
+
+A plain run (no `--full`) does only what the headline figure needs: inputs, priming, W warm-up steps, the K timed steps, the
+on-device sanity check of the output (`output_ok`: finite; under the mask row 0 equals V's), the line.  `--full` adds everything else this file measures or checks: the unprimed figure,
+the power-limited ceiling microbenchmark, the CPU baseline and `parity`, and the `bf16_out` and `cfg4` sub-records (the
+`--no-*` options switch single parts of that off again).
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the timed call computed in its last step as DIR/O.npy (float32,
+[heads, S, d] over the flattened batch x head index): every head if that fits DUMP_BYTES, else a fixed seeded sample of whole
+heads (dump_heads).  The inputs are seeded, so the same arguments give the same inputs on every run and every build.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process (which has not touched the GPU) starts the N ranks
 itself -- a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same
@@ -12,18 +21,18 @@ A "step" is one pass of the hot path (one flash_attention call) over one batch o
 resident in HBM.  Default workload = BASELINE.json configs[2], the configuration the metric is quoted on: bf16, B=8, H=16,
 S=4096, d=128, causal, with fp32 output (the reference's O is float*, kernels/FlashAttention.cuh:61).  With N > 1 every rank
 runs that same per-GPU batch on its own heads (weak scaling: the path shards over batch x head with no data-path collective;
-RCCL carries only the MAX of elapsed times, outside the timed region).  Every line also carries a `cfg4` sub-record: BASELINE
-configs[4] (B=64, H=32, S=8192, d=128) with its 2048 heads split over the N ranks (strong scaling; N = 1 is its anchor), a
-few steps, and a `bf16_out` sub-record: the same workload with bf16 output.
+RCCL carries only the MAX of elapsed times, outside the timed region).  With --full the line also carries a `cfg4` sub-record:
+BASELINE configs[4] (B=64, H=32, S=8192, d=128) with its 2048 heads split over the N ranks (strong scaling; N = 1 is its anchor),
+a few steps, and a `bf16_out` sub-record: the same workload with bf16 output.
 FLOPs: 4*B*H*S^2*d non-causal, 2*B*H*S^2*d causal (only unmasked work counts) -- SURVEY.md 8(d).
 
 Rank 0 prints ONE JSON line with
   `value`         whole-job TFLOP/s from the host clock around exactly K steps between barriers, on a PRIMED device (~100 ms of
-                  the same launches first; `value_unprimed` is the same K steps from a device just out of idle);
-                  `ms_median` / `ms_min`: per-step HIP-event times of those K steps,
+                  the same launches first; with --full, `value_unprimed` is the same K steps from a device just out of idle);
+                  `ms_per_step`: that host-clock time over K; `ms_median` / `ms_min`: per-step HIP-event times of those K steps,
   `roofline`      HIP-event kernel time against the dense MFMA peak of the workload's arithmetic, the HBM traffic measured by
                   the committed PMC run IF it was taken on the same kernel sources (provenance hash), and
-  `cpu_baseline`  (N=1) the oracle's naive fp32 attention timed on the host cores over a bounded sample of THIS run's own
+  `cpu_baseline`  (--full, N=1) the oracle's naive fp32 attention timed on the host cores over a bounded sample of THIS run's own
                   tensors, whose result is also the checker for `parity`: max-abs / max-rel error and the fraction of
                   elements inside the stated tolerance |O-ref| <= 1e-3 + 1e-3|ref|.  A pass fraction
                   under the floor (1.0 with fp32 output) sets `output_ok` false and the exit status 3.
@@ -65,10 +74,41 @@ ANCHOR_GUIDE_TFLOPS = 1250.0   # cdna_hip_programming.md, Appendix B "Fused atte
 # parity.pass_frac_at_1e-3 below this fails the run: every sampled element with fp32 output (the stated tolerance, met by the
 # default weight precisions: include/flash_attention.h); 2-byte outputs add their own rounding (2^-9 relative for bf16)
 PARITY_FLOOR = {"f32": 1.0, "bf16": 0.998}
+# --dump-outputs: at most this many bytes of float32 output; a larger O is dumped as a fixed seeded sample of whole heads
+DUMP_BYTES = 32 << 20
+DUMP_SEED = 20240613
 
 
 def flops_of(BH, S, d, causal):
     return (2.0 if causal else 4.0) * BH * float(S) * S * d
+
+
+def make_inputs(torch, workload, heads_local, S, d, dev, rank):
+    """The rank's Q, K, V: its slab as dense [heads, 1, S, d] tensors of N(0,1) values from a device generator seeded with
+    1234 + rank, rounded to the workload's input type -- the same tensors for the same arguments on every run."""
+    g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    in_dtype = torch.float8_e4m3fn if workload == "cfg3" else torch.bfloat16
+    return tuple(torch.randn((heads_local, 1, S, d), generator=g, device=dev, dtype=torch.float32).to(in_dtype) for _ in range(3))
+
+
+def dump_heads(heads, S, d):
+    """Flattened head indices whose float32 output --dump-outputs writes: all of them when they fit DUMP_BYTES, else a sorted
+    sample of whole heads drawn with a fixed seed -- the same heads for the same arguments on every run and every build."""
+    import numpy as np
+    n = max(1, min(heads, DUMP_BYTES // (S * d * 4)))
+    if n == heads:
+        return np.arange(heads)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(heads, size=n, replace=False))
+
+
+def dump_outputs(out_dir, O, torch):
+    """Write the output O ([heads, 1, S, d] on the device) as out_dir/O.npy, float32 [n, S, d] over the heads dump_heads picks."""
+    import numpy as np
+    heads, _, S, d = O.shape
+    idx = dump_heads(heads, S, d)
+    sample = O.index_select(0, torch.as_tensor(idx, device=O.device)).reshape(len(idx), S, d)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "O.npy"), sample.float().cpu().numpy())
 
 
 def bound_for(workload):
@@ -209,8 +249,9 @@ def cpu_baseline_and_parity(Q, K, V, O, S, d, causal, budget_s=12.0, heads_at=No
     return base, par
 
 
-def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps, warmup, dry, want_parity, out_dtype, prime=True, parity_heads=None):
-    """One workload on this rank; returns the rank-0 record (None elsewhere)."""
+def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps, warmup, dry, want_parity, out_dtype, prime=True, parity_heads=None,
+                 dump_dir=None):
+    """One workload on this rank; returns the rank-0 record (None elsewhere).  dump_dir: rank 0 writes the timed call's output there."""
     B, H, S, d, causal, desc = WORKLOADS[workload]
     if workload == "cfg4":           # fixed total problem, B*H split over the ranks (strong scaling)
         lo, hi = shard.shard_heads(B * H, rank, world)
@@ -221,11 +262,8 @@ def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps
     osz = 2 if out_dtype == "bf16" else 4
     Q = K = V = O = None
     if not dry:
-        g = torch.Generator(device=dev).manual_seed(1234 + rank)
-        shape = (heads_local, 1, S, d)   # the rank's slab as a dense [heads,1,S,d] tensor
-        in_dtype = torch.float8_e4m3fn if workload == "cfg3" else torch.bfloat16
-        Q, K, V = (torch.randn(shape, generator=g, device=dev, dtype=torch.float32).to(in_dtype) for _ in range(3))
-        O = torch.empty(shape, device=dev, dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32)
+        Q, K, V = make_inputs(torch, workload, heads_local, S, d, dev, rank)
+        O = torch.empty(Q.shape, device=dev, dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32)
     scale = 1.0 / d ** 0.5
     wdt = None if (dry or esz != 2) else {"default": None, "bf16": torch.bfloat16, "f16": torch.float16}[args.weights]
 
@@ -266,10 +304,11 @@ def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps
             per = [ev[i].elapsed_time(ev[i + 1]) for i in range(n)]
         return el, per
 
-    # first touch (LDS limit raised, code object loaded), then the UNPRIMED figure: the same K steps from a device that has
+    # first touch (LDS limit raised, code object loaded), then (--full) the UNPRIMED figure: the same K steps from a device that has
     # just come out of idle -- what a caller sees on its first few calls (clock ramp; reported beside `value`, never as it)
     step(); sync()
-    el_cold, _ = timed(steps)
+    if args.full:
+        el_cold, _ = timed(steps)
     # Device priming (setup, untimed, before the W warmup steps): a GPU coming out of idle needs tens of milliseconds of
     # work before its power state and clocks settle.  ~100 ms of the same launches, at most 3000.
     if prime:
@@ -281,8 +320,11 @@ def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps
     for _ in range(warmup):
         step()
     elapsed, per_step = timed(steps)
+    if dump_dir is not None and rank == 0 and not dry:
+        dump_outputs(dump_dir, O, torch)      # O holds what the last timed step computed
     elapsed = shard.reduce_max(elapsed)
-    el_cold = shard.reduce_max(el_cold)
+    if args.full:
+        el_cold = shard.reduce_max(el_cold)
     kernel_ms = sum(per_step) / len(per_step)
     kernel_ms_max = shard.reduce_max(kernel_ms)
     ms_median = shard.reduce_max(statistics.median(per_step))
@@ -333,8 +375,6 @@ def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps
         "ms_median": round(ms_median, 5), "ms_min": round(ms_min, 5),
         "value_at_ms_median": round(flops_of(total_heads, S, d, causal) / (ms_median * 1e-3) / 1e12, 2),
         "device_primed": bool(prime),
-        # the same K steps timed BEFORE the ~100 ms priming loop (device just out of idle): not the metric, the caveat
-        "value_unprimed": round(flops_of(total_heads, S, d, causal) / (el_cold / steps) / 1e12, 2),
         # causal FLOPs count only the unmasked half; the full-count figure alongside, labelled
         "value_if_masked_half_counted_too": round(value * (2.0 if causal else 1.0), 2),
         "output_ok": ok_all,
@@ -349,6 +389,9 @@ def run_workload(fa, shard, torch, dist, args, workload, world, rank, dev, steps
                      "algorithmic_hbm_bytes": algo_bytes,
                      "algorithmic_hbm_GBps": round(algo_bytes / (kernel_ms_max * 1e-3) / 1e9, 1)},
     }
+    if args.full:
+        # the same K steps timed BEFORE the ~100 ms priming loop (device just out of idle): not the metric, the caveat
+        rec["value_unprimed"] = round(flops_of(total_heads, S, d, causal) / (el_cold / steps) / 1e12, 2)
     if dry:
         rec["dry_run"] = True
     if workload == "anchor":
@@ -397,9 +440,17 @@ def main():
     ap.add_argument("--weights", default="default", choices=["default", "bf16", "f16"],
                     help="softmax-weight precision (bf16 inputs): the library default, or one precision on every row (FA_FLAG_*_WEIGHTS)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo: no launches, no measurements -- the line's structure only")
+    ap.add_argument("--full", action="store_true",
+                    help="also the unprimed figure, the power-limited ceiling, the CPU baseline and parity, the bf16_out and cfg4 sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/O.npy (float32; a fixed seeded sample of whole heads if large)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs is not None and args.dry_run:
+        raise SystemExit("--dump-outputs: a --dry-run computes nothing")
     if args.out_dtype is None:
         args.out_dtype = DEFAULT_OUT_DTYPE.get(args.workload, "f32")
 
@@ -424,7 +475,7 @@ def main():
     # The ceiling microbenchmark is a separate GPU program: run it as a child BEFORE this process touches the GPU
     # (no exec from a process that has initialised HIP).  Single-GPU runs only.
     ceil = None
-    if world == 1 and not args.no_ceiling and not args.dry_run and args.workload != "cfg3":
+    if args.full and world == 1 and not args.no_ceiling and not args.dry_run and args.workload != "cfg3":
         ceil = power_limited_ceiling()
 
     import torch
@@ -467,7 +518,8 @@ def main():
     ranks = dist.get_world_size() if dist.is_initialized() else 1
 
     line = run_workload(fa, shard, torch, dist, args, args.workload, world, rank, dev, args.steps, args.warmup, args.dry_run,
-                        want_parity=world == 1 and not args.no_cpu_baseline, out_dtype=args.out_dtype)
+                        want_parity=args.full and world == 1 and not args.no_cpu_baseline, out_dtype=args.out_dtype,
+                        dump_dir=args.dump_outputs)
     if rank == 0:
         line["rccl_ranks"] = ranks
         if ceil:
@@ -477,13 +529,13 @@ def main():
                 frac_of_attention_mix=round(a / ceil["attention_mix_random_bf16_tflops"], 4))
     few = max(2, min(5, args.steps))
     # the same workload with bf16 output (half the output bytes; its rounding alone exceeds the stated tolerance for |O| > 1)
-    if not args.no_bf16_out and args.out_dtype != "bf16" and args.workload != "cfg4":
+    if args.full and not args.no_bf16_out and args.out_dtype != "bf16" and args.workload != "cfg4":
         sub = run_workload(fa, shard, torch, dist, args, args.workload, world, rank, dev, args.steps, args.warmup, args.dry_run, False, "bf16", prime=False)
         if rank == 0:
             line["bf16_out"] = {k: sub[k] for k in ("value", "unit", "ms_per_step", "ms_median", "ms_min", "output_ok")}
             line["bf16_out"]["roofline"] = {k: sub["roofline"][k] for k in ("achieved", "peak", "frac", "kernel_ms")}
     # BASELINE configs[4] itself, its 2048 heads split over the ranks (the driver never passes --workload cfg4); N = 1: the anchor
-    if not args.no_cfg4 and args.workload != "cfg4":
+    if args.full and not args.no_cfg4 and args.workload != "cfg4":
         # parity of cfg4 at the stated tolerance on whole heads of rank 0's slab: the first, the two either side of the 2^31-byte
         # line of the whole problem (heads 1023 | 1024; on a shard: its middle), and the last
         n_loc = shard.shard_heads(64 * 32, rank, world)

@@ -1,7 +1,9 @@
 set -e
-mkdir -p gpurun_out/profiles_r03
+# usage: profiles/bench_lines.sh OUTDIR -- the full bench.py line (sub-records, parity) of every single-GPU workload, one file each
+OUT=${1:?usage: profiles/bench_lines.sh OUTDIR}
+mkdir -p "$OUT"
 for wl in cfg2 cfg2nc cfg1 cfg1c cfg3; do
-  python3 bench.py --workload $wl > gpurun_out/profiles_r03/r03_bench_$wl.json 2> gpurun_out/profiles_r03/r03_bench_$wl.err
-  tail -c 300 gpurun_out/profiles_r03/r03_bench_$wl.json
+  python3 bench.py --full --workload $wl > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err"
+  tail -c 300 "$OUT/bench_$wl.json"
 done
-python3 bench.py --weights bf16 > gpurun_out/profiles_r03/r03_bench_cfg2_weights_bf16.json 2>/dev/null
+python3 bench.py --full --weights bf16 > "$OUT/bench_cfg2_weights_bf16.json" 2>/dev/null

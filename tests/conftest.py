@@ -56,9 +56,19 @@ def pytest_sessionstart(session):
     clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE",
                                                               "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
     bench = [sys.executable, os.path.join(ROOT, "bench.py")]
-    _run_child("bench_rccl_single", bench + ["--steps", "5", "--warmup", "2", "--no-ceiling", "--no-cfg4", "--no-bf16-out", "--cpu-budget-s", "3"], 600,
-               env=dict(clean, FA_BENCH_RCCL_SINGLE="1"))
+    _run_child("bench_rccl_single", bench + ["--steps", "5", "--warmup", "2", "--full", "--no-ceiling", "--no-cfg4", "--no-bf16-out", "--cpu-budget-s", "3"],
+               600, env=dict(clean, FA_BENCH_RCCL_SINGLE="1"))
     _run_child("bench_gpus2", bench + ["--gpus", "2", "--steps", "2", "--warmup", "1"], 300, env=clean)
+    # a plain run (no --full) that dumps its output: tests/test_bench_gpu.py checks the line and the dump against the oracle
+    import tempfile
+    DRIVER_RUNS["bench_dump_dir"] = tempfile.mkdtemp(prefix="fa_bench_dump_")
+    _run_child("bench_dump", bench + ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", DRIVER_RUNS["bench_dump_dir"]], 300, env=clean)
+
+
+def pytest_sessionfinish(session, exitstatus):
+    if "bench_dump_dir" in DRIVER_RUNS:
+        import shutil
+        shutil.rmtree(DRIVER_RUNS["bench_dump_dir"], ignore_errors=True)
 
 
 @pytest.fixture(scope="session")

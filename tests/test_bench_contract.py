@@ -80,7 +80,7 @@ def _bench_rank(rank, world, port, q):
     import contextlib
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     import sys
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main()
@@ -129,7 +129,7 @@ def test_gpus_n_starts_n_ranks_itself():
     (torch.distributed.run, 127.0.0.1), relays rank 0's ONE JSON line and exits 0.  CPU / gloo dry run: structure only."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -143,7 +143,7 @@ def test_single_rank_line_carries_the_cfg4_anchor():
     """N = 1 (dry run): the line still carries BASELINE cfg4 -- all 2048 heads on the one rank: the strong-scaling anchor."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dry-run", "--no-ceiling", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -177,7 +177,7 @@ def test_roofline_kernel_name_comes_from_the_plan():
     # and the dry-run line carries it, with the traffic ratio's slot, for the headline and the cfg4 sub-record
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dry-run", "--no-ceiling"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dry-run", "--no-ceiling", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -220,3 +220,50 @@ def test_more_ranks_than_visible_gpus_is_refused_before_any_rendezvous():
     r = subprocess.run(exe + ["--gpus", "1", "--steps", "2", "--warmup", "1", "--dry-run", "--no-ceiling", "--no-cfg4", "--no-bf16-out"],
                        env=dict(_clean_env(), FA_BENCH_VISIBLE_DEVICES="1"), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-1000:]
+
+
+def test_plain_run_line_is_the_headline_only():
+    """Without --full the run times the headline workload and nothing else: the line carries the headline fields, `steps` is
+    --steps, and none of what --full adds (unprimed figure, ceiling, CPU baseline / parity, bf16_out and cfg4 sub-records)."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dry-run"],
+                       env=_clean_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["unit"] == "TFLOP/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"cfg4", "bf16_out", "value_unprimed", "parity", "cpu_baseline"} & set(line)
+    assert "power_limited" not in line["roofline"]
+
+
+def test_dump_heads_is_a_fixed_sample_within_the_budget():
+    """--dump-outputs: every head when the float32 output fits DUMP_BYTES, else the same seeded sample of whole heads every time."""
+    import numpy as np
+    assert bench.DUMP_BYTES <= 64 << 20
+    assert np.array_equal(bench.dump_heads(32, 2048, 64), np.arange(32))           # cfg1: 16 MiB, all of it
+    a = bench.dump_heads(128, 4096, 128)                                            # cfg2: 256 MiB, a sample
+    assert np.array_equal(a, bench.dump_heads(128, 4096, 128)) and len(set(a.tolist())) == len(a)
+    assert 1 <= len(a) < 128 and len(a) * 4096 * 128 * 4 <= bench.DUMP_BYTES and list(a) == sorted(a) and 0 <= a.min() and a.max() < 128
+    assert len(bench.dump_heads(2048, 8192, 128)) * 8192 * 128 * 4 <= bench.DUMP_BYTES    # cfg4
+
+
+def test_dump_outputs_writes_float32_heads(tmp_path):
+    import numpy as np
+    import torch
+    O = torch.randn(200, 1, 512, 128, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "out"), O, torch)
+    got = np.load(tmp_path / "out" / "O.npy")
+    idx = bench.dump_heads(200, 512, 128)
+    assert got.dtype == np.float32 and got.shape == (len(idx), 512, 128) and len(idx) < 200
+    assert np.array_equal(got, O.float().numpy()[idx, 0])
+
+
+def test_dump_outputs_is_refused_on_a_dry_run(tmp_path):
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--dump-outputs", str(tmp_path / "out")],
+                       env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "out").exists()
