@@ -64,7 +64,7 @@ tests/micro/%: tests/micro/%.hip
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++20 -o $@ $<
 
 # Host-side sanitizers (there is no GPU ASan on this pool): the oracle under gcc's ASan + UBSan, and the library's
-# HOST code -- argument validation, make_plan, snake_imbalance, plan_ex, shard_range: everything callable without a GPU -- under clang's
+# HOST code -- argument validation, the launch routing, plan, plan_ex, shard_range: everything callable without a GPU -- under clang's
 # (FlashAttention.hip rebuilt with -fsanitize=address,undefined; the kernel translation units are linked as built).  Each test file
 # runs in a process of its own with the matching runtime preloaded; tests/main.cpp (the C++ harness) is compiled and linked under the
 # same flags as a build check (running it needs a GPU).

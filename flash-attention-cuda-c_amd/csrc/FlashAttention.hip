@@ -112,85 +112,124 @@ static bool pair_kernel_applies(int B, int H, int S, int d, bool causal, int dty
     return ((heads + 7) / 8) * getNumCta(S, 128) <= rounds * jpx;
 }
 
-static int make_plan(int B, int H, int S, int d, bool causal, int dtype, int o_dtype, float scale,
-                     fa_launch_plan* plan) {
-    // bf16: d in {64,128} natively; any other multiple of 8 up to 128 runs the next larger instantiation with its
-    // rows zero-padded on the fly (d/64 or d/128 of the MFMA work is useful -- still ~1000x the VALU kernel)
-    const bool mfma_bf16 = dtype == FA_DTYPE_BF16 && d % 8 == 0 && d <= 128 && scale > 0.f;
-    const bool mfma_fp8 = dtype == FA_DTYPE_FP8_E4M3 && d % 16 == 0 && d <= 128 && scale > 0.f;   // d < 128: zero-padded
-    // fp32: d in {64,128} natively, other multiples of 4 up to 128 zero-padded onto the next larger instantiation
-    const bool mfma_f32 = dtype == FA_DTYPE_F32 && d % 4 == 0 && d <= 128 && scale > 0.f;
-    if (mfma_f32) {
-        plan->kernel_id = 3;
-        plan->q_block_rows = calculateSizeBlockQ(d, dtype);
-        plan->kv_block_rows = calculateSizeBlockKV(d, dtype);
-        plan->threads = 256;
-        plan->lds_bytes = f32_lds_bytes(d > 64 ? 128 : 64);
-        const int nQ = getNumCta(S, plan->q_block_rows);
-        const int64_t units = (int64_t)B * H * nQ;
-        plan->grid = (int)(8 * ((units + 7) / 8));
-    } else if (mfma_bf16 || mfma_fp8) {
-        plan->kernel_id = mfma_fp8 ? 2 : 1;
-        plan->q_block_rows = calculateSizeBlockQ(d, dtype);
-        plan->kv_block_rows = calculateSizeBlockKV(d, dtype);
-        plan->threads = 512;
-        // 3-slot ring of [K image (input type) | V image (bf16)] at the instantiated head dimension, or ring slot 0 + the
-        // epilogue's staging regions where those are larger -- as carved up by the instantiation this problem launches (the
-        // engine depends on the mask, the staging form on padding: kernel_bf16.hip.h, KernelCfg::LDS_BYTES)
-        const int dk = mfma_fp8 ? 128 : paddedDHead(d);
-        const bool pad = d != dk;
-        plan->lds_bytes = mfma_fp8 ? fp8_d128_lds_bytes(causal, pad, o_dtype)
-                                   : (dk == 128 ? bf16_d128_lds_bytes(causal, pad, o_dtype) : bf16_d64_lds_bytes(causal, pad, o_dtype));
-        // persistent grid: one workgroup per CU (8 XCD groups x CUs/8), each walking ceil(units/grid) units;
-        // with fewer units than CUs, one workgroup per unit
-        const int nQ = getNumCta(S, plan->q_block_rows);
-        const int64_t units = (int64_t)B * H * nQ;
-        plan->grid = (int)(8 * std::min<int64_t>((units + 7) / 8, device_cus() / 8));
-        if (mfma_bf16 && pair_kernel_applies(B, H, S, d, causal, dtype, scale)) {
-            // 128-row units, one per workgroup of four waves, two workgroups per CU (grid = 16 per XCD-group workgroup slot pair)
-            plan->q_block_rows = 128;
-            plan->threads = 256;
-            plan->lds_bytes = d == 64 ? bf16_pair_d64_lds_bytes(causal, o_dtype) : bf16_pair_d128_lds_bytes(causal, o_dtype);
-            // grid: 8 XCD groups x (the largest group's units, or -- more units than CUs in a group -- two workgroups per CU)
-            const int jpx = device_cus() / 8;
-            const int64_t per_group = (((int64_t)B * H + 7) / 8) * getNumCta(S, 128);
-            plan->grid = 8 * (int)(per_group <= jpx ? per_group : 2 * jpx);   // (d = 128: per_group <= jpx always)
-        }
-    } else {
-        plan->kernel_id = 0;
-        plan->q_block_rows = GenericCfg::BQ;
-        plan->kv_block_rows = GenericCfg::BK;
-        plan->threads = GenericCfg::THREADS;
-        plan->lds_bytes = generic_lds_bytes(d);
-        const int nQ = getNumCta(S, plan->q_block_rows);
-        const int64_t units = (int64_t)B * H * nQ;
-        plan->grid = (int)(8 * ((units + 7) / 8));
-    }
+// Option flags: known, not contradictory, and applicable (the fp16-weights kernels exist for bf16 inputs at the natively
+// instantiated head dimensions; run() also wants a positive scale for them)
+static int check_flags(unsigned flags, int dtype, int d) {
+    if (flags & ~(unsigned)(FA_FLAG_F16_WEIGHTS | FA_FLAG_BF16_WEIGHTS)) return FA_ERR_BAD_FLAGS;
+    if ((flags & FA_FLAG_F16_WEIGHTS) && ((flags & FA_FLAG_BF16_WEIGHTS) || !(dtype == FA_DTYPE_BF16 && (d == 64 || d == 128))))
+        return FA_ERR_BAD_FLAGS;
+    if ((flags & FA_FLAG_BF16_WEIGHTS) && dtype != FA_DTYPE_BF16) return FA_ERR_BAD_FLAGS;
     return FA_OK;
 }
 
-template <typename InT, typename OutT>
-static hipError_t launch_generic_io(const Params& p, const fa_launch_plan& plan, int d, bool causal, hipStream_t st) {
-    dim3 grid(plan.grid), block(plan.threads);
-    static std::atomic<bool> done_c[64], done_n[64];
-    const int lds_max = generic_lds_bytes(256);   // 100 KiB at the largest supported head dimension
-    if (causal) {
-        const hipError_t attr = raise_lds_limit(fwd_generic_kernel<InT, OutT, true>, lds_max, done_c);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL((fwd_generic_kernel<InT, OutT, true>), grid, block, plan.lds_bytes, st, p, d);
-    } else {
-        const hipError_t attr = raise_lds_limit(fwd_generic_kernel<InT, OutT, false>, lds_max, done_n);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL((fwd_generic_kernel<InT, OutT, false>), grid, block, plan.lds_bytes, st, p, d);
-    }
-    return hipGetLastError();
+// The generic VALU kernel (fp32 or bf16 inputs); its LDS limit is raised to what the largest head dimension takes (100 KiB at d = 256)
+static Kernel generic_kernel(int dtype, bool causal, int o_dtype) {
+    return by_out(o_dtype, [&]<class OutT>() {
+        return by_bool(causal, [&]<bool CAUSAL>() {
+            return dtype == FA_DTYPE_F32 ? kernel_of<fwd_generic_kernel<float, OutT, CAUSAL>>(generic_lds_bytes(256))
+                                         : kernel_of<fwd_generic_kernel<__bf16, OutT, CAUSAL>>(generic_lds_bytes(256));
+        });
+    });
 }
 
-template <typename InT>
-static hipError_t launch_generic(const Params& p, const fa_launch_plan& plan, int d, bool causal, int o_dtype, hipStream_t st) {
-    if (o_dtype == FA_DTYPE_F32) return launch_generic_io<InT, float>(p, plan, d, causal, st);
-    if (o_dtype == FA_DTYPE_BF16) return launch_generic_io<InT, __bf16>(p, plan, d, causal, st);
-    return launch_generic_io<InT, _Float16>(p, plan, d, causal, st);
+enum class Family { generic, f32, bf16, fp8, causal_mix, p16, pair };
+
+// What a call launches: ONE kernel over all query blocks [0, nQ) of every head.  run() launches it, flash_attention_plan and
+// flash_attention_plan_ex report it.
+struct Route {
+    Family family;
+    int kernel_id;                 // fa_launch_plan::kernel_id
+    int D;                         // the instantiated head dimension (generic: the call's)
+    bool pad;                      // the call's rows are zero-padded to D
+    int q_block_rows, kv_block_rows, threads;
+    int nQ;                        // query blocks per head
+    int hp;                        // how many leading query blocks of every head take fp16 weights (Params::hp)
+    int64_t units, cpx;            // (head, query block) units; per XCD group
+    int jpx;                       // Params::jpx: workgroups per XCD group (pair kernel: of one dispatch round)
+    int grid;
+    int lds_bytes;                 // the launch's dynamic LDS: kernel.lds_bytes but for the generic kernel
+    int unit_lists;                // fa_launch_plan_ex::unit_lists: both precisions in one launch of the mixed-precision kernel
+    Kernel kernel;
+
+    fa_launch_plan plan() const { return {q_block_rows, kv_block_rows, threads, grid, lds_bytes, kernel_id}; }
+};
+
+// The one launch decision.  Arguments validated by the caller; lse: the call wants the LSE.
+static Route route(int B, int H, int S, int Sk, int d, bool causal, int dtype, int o_dtype, float scale, unsigned flags, bool lse) {
+    // bf16: d in {64,128} natively; any other multiple of 8 up to 128 runs the next larger instantiation with its rows zero-padded on
+    // the fly (d/64 or d/128 of the MFMA work is useful -- still ~1000x the VALU kernel).  fp8: the D = 128 instantiation, d < 128
+    // zero-padded.  fp32: the exact-fp32 MFMA kernel, d in {64,128} natively, other multiples of 4 up to 128 zero-padded.
+    const bool mfma_bf16 = dtype == FA_DTYPE_BF16 && d % 8 == 0 && d <= 128 && scale > 0.f;
+    const bool mfma_fp8 = dtype == FA_DTYPE_FP8_E4M3 && d % 16 == 0 && d <= 128 && scale > 0.f;
+    const bool mfma_f32 = dtype == FA_DTYPE_F32 && d % 4 == 0 && d <= 128 && scale > 0.f;
+    Route r{};
+    if (mfma_bf16 || mfma_fp8 || mfma_f32) {
+        r.family = mfma_f32 ? Family::f32 : mfma_fp8 ? Family::fp8 : Family::bf16;
+        r.kernel_id = mfma_f32 ? 3 : mfma_fp8 ? 2 : 1;
+        r.D = mfma_fp8 ? 128 : paddedDHead(d);
+        r.q_block_rows = calculateSizeBlockQ(d, dtype);
+        r.kv_block_rows = calculateSizeBlockKV(d, dtype);
+        r.threads = mfma_f32 ? 256 : 512;
+    } else {
+        r.family = Family::generic;
+        r.D = d;
+        r.q_block_rows = GenericCfg::BQ;
+        r.kv_block_rows = GenericCfg::BK;
+        r.threads = GenericCfg::THREADS;
+    }
+    r.pad = d != r.D;
+    if (r.family == Family::bf16) {
+        if (pair_kernel_applies(B, H, S, d, causal, dtype, scale)) {
+            r.family = Family::pair;
+            r.q_block_rows = 128;
+            r.threads = 256;
+        }
+        // Which query blocks take fp16 softmax weights (early_q_blocks): all with FA_FLAG_F16_WEIGHTS, none with
+        // FA_FLAG_BF16_WEIGHTS, by default the rows that see few keys.  Both kinds present (a causal problem longer than
+        // FA_EARLY_KEYS): ONE launch of ONE kernel over the list of all query blocks, in the single kernel's head-aligned order (all of
+        // a head's blocks start in one round of one XCD group, so its K/V is streamed from that XCD's L2); every unit runs in the
+        // precision of its block (kernel_bf16.hip.h: KernelCfg::MIX).  The pair kernel does the same in its own form.
+        r.hp = early_q_blocks(S, Sk, d, causal, flags, r.q_block_rows);
+        // hp = nQ (FA_FLAG_F16_WEIGHTS, or every row sees fewer than FA_EARLY_KEYS keys) makes the mixed-precision kernel the
+        // fp16-weights kernel of the 32x32x16 engine, K by LDS-DMA: faster under the mask than the 16x16x32 one with both tiles through
+        // registers (+2.4 % at S = 4096 d = 128, +8 % at S = 2048 d = 64: profiles/r04_tune_f_fp16_everywhere_*.log).  Without the mask
+        // early_q_blocks is all or nothing: hp = nQ, every unit runs with fp16 weights.
+        if (r.family == Family::bf16 && r.hp > 0) r.family = causal ? Family::causal_mix : Family::p16;
+    }
+    r.nQ = getNumCta(S, r.q_block_rows);
+    r.units = (int64_t)B * H * r.nQ;
+    r.cpx = (r.units + 7) / 8;
+    const int cus_per_xcd = device_cus() / 8;
+    switch (r.family) {
+        case Family::generic:
+        case Family::f32:   // one workgroup per unit
+            r.grid = (int)(8 * r.cpx);
+            r.jpx = r.grid / 8;
+            break;
+        case Family::pair: {
+            // 128-row units, one per workgroup of four waves; grid: 8 XCD groups x (the largest group's units, or -- more units than
+            // CUs in a group -- two workgroups per CU: d = 64 only, at d = 128 per_group <= cus_per_xcd always)
+            const int64_t per_group = (((int64_t)B * H + 7) / 8) * r.nQ;
+            r.grid = 8 * (int)(per_group <= cus_per_xcd ? per_group : 2 * cus_per_xcd);
+            r.jpx = cus_per_xcd;   // (workgroups of one dispatch round per XCD group: what the pairing counts in)
+            break;
+        }
+        default:   // persistent grid: one workgroup per CU (8 XCD groups x CUs/8), or per unit when there are fewer units
+            r.grid = (int)(8 * std::min<int64_t>(r.cpx, cus_per_xcd));
+            r.jpx = r.grid / 8;
+    }
+    switch (r.family) {
+        case Family::generic: r.kernel = generic_kernel(dtype, causal, o_dtype); break;
+        case Family::f32: r.kernel = (r.D == 128 ? f32_d128_kernel : f32_d64_kernel)(causal, r.pad, o_dtype); break;
+        case Family::bf16: r.kernel = (r.D == 128 ? bf16_d128_kernel : bf16_d64_kernel)(causal, r.pad, lse, o_dtype); break;
+        case Family::fp8: r.kernel = fp8_d128_kernel(causal, r.pad, o_dtype); break;
+        case Family::causal_mix: r.kernel = bf16_causal_mix_kernel(d, o_dtype); break;
+        case Family::p16: r.kernel = bf16_p16_kernel(d, o_dtype); break;
+        case Family::pair: r.kernel = (d == 64 ? bf16_pair_d64_kernel : bf16_pair_d128_kernel)(causal, o_dtype); break;
+    }
+    r.lds_bytes = r.family == Family::generic ? generic_lds_bytes(d) : r.kernel.lds_bytes;
+    r.unit_lists = r.family == Family::causal_mix && r.hp < r.nQ;
+    return r;
 }
 
 static int run(const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H, int S, int Sk, int d,
@@ -198,85 +237,35 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
                const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream, unsigned flags = 0) {
     int rc = validate(Q, K, V, O, B, H, S, d, scale, dtype, o_dtype);
     if (rc != FA_OK) return rc;
-    if (flags & ~(unsigned)(FA_FLAG_F16_WEIGHTS | FA_FLAG_BF16_WEIGHTS)) return FA_ERR_BAD_FLAGS;
-    if ((flags & FA_FLAG_F16_WEIGHTS) && (flags & FA_FLAG_BF16_WEIGHTS)) return FA_ERR_BAD_FLAGS;
-    // the fp16-weights kernels exist for bf16 inputs at the natively instantiated head dimensions
-    if ((flags & FA_FLAG_F16_WEIGHTS) && !(dtype == FA_DTYPE_BF16 && (d == 64 || d == 128) && scale > 0.f)) return FA_ERR_BAD_FLAGS;
-    if ((flags & FA_FLAG_BF16_WEIGHTS) && dtype != FA_DTYPE_BF16) return FA_ERR_BAD_FLAGS;
+    if ((rc = check_flags(flags, dtype, d)) != FA_OK) return rc;
+    if ((flags & FA_FLAG_F16_WEIGHTS) && !(scale > 0.f)) return FA_ERR_BAD_FLAGS;
     if (Sk <= 0 || Sk > (1 << 24)) return FA_ERR_BAD_SHAPE;
     if (lse && !aligned16(lse)) return FA_ERR_MISALIGNED;
     const int esz = elem_size(dtype), osz = elem_size(o_dtype);
     if (!strides_ok(sQ, esz, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d))
         return FA_ERR_BAD_STRIDE;
-    fa_launch_plan plan;
-    make_plan(B, H, S, d, causal, dtype, o_dtype, scale, &plan);
-    if (plan.kernel_id != 0) {
+    const Route r = route(B, H, S, Sk, d, causal, dtype, o_dtype, scale, flags, lse != nullptr);
+    if (r.kernel_id != 0) {
         // K/V are fetched through buffer descriptors with 32-bit byte offsets: one head's extent
         // (seqLen x row stride) must stay below 2^31 bytes (two prefetch tiles of slack included)
         const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
         if (((int64_t)Sk + 192) * ks * esz >= (1ll << 31) || ((int64_t)Sk + 192) * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
     }
+    if (r.units > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;   // unit indices are 32-bit
     Params p;
     fill_params(p, Q, K, V, O, lse, B, H, S, Sk, d, scale, sQ, sK, sV, sO);
-    const int nQ_total = getNumCta(S, plan.q_block_rows);
-    if ((int64_t)B * H * nQ_total > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;   // unit indices are 32-bit
     p.dbg = nullptr;
-    p.hp = 0;
+    p.qb0 = 0;
+    p.nQ = r.nQ;
+    p.units = (int)r.units;
+    p.cpx = (int)r.cpx;
+    p.jpx = r.jpx;
+    p.hp = r.hp;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // One launch covers the query blocks [qb0, qb0 + nq) of every head.
-    auto set_range = [&](int qb0, int nq, bool persistent) {
-        p.qb0 = qb0;
-        p.nQ = nq;
-        p.units = B * H * nq;
-        p.cpx = (p.units + 7) / 8;
-        if (persistent) plan.grid = 8 * std::min(p.cpx, device_cus() / 8);   // one workgroup per CU, or per unit when there are fewer
-        else plan.grid = 8 * p.cpx;
-        p.jpx = plan.grid / 8;
-    };
-    hipError_t e = hipSuccess;
-    if (plan.kernel_id == 3) {          // fp32 inputs: exact-fp32 MFMA kernel at D = 128 / 64 (narrower rows zero-padded)
-        set_range(0, nQ_total, false);
-        e = d > 64 ? launch_f32_d128(p, plan, causal, d != 128, o_dtype, st) : launch_f32_d64(p, plan, causal, d != 64, o_dtype, st);
-    } else if (plan.kernel_id == 2) {   // fp8 e4m3fn inputs
-        set_range(0, nQ_total, true);
-        e = launch_fp8_d128(p, plan, causal, d != 128, o_dtype, st);
-    } else if (plan.kernel_id == 1) {   // bf16 inputs
-        // Which query blocks take fp16 softmax weights (early_q_blocks): all with FA_FLAG_F16_WEIGHTS, none with
-        // FA_FLAG_BF16_WEIGHTS, by default the rows that see few keys.  Both kinds present (a causal problem longer than
-        // FA_EARLY_KEYS): ONE launch of ONE kernel over the list of all query blocks, in the single kernel's head-aligned order (all of a
-        // head's blocks start in one round of one XCD group, so its K/V is streamed from that XCD's L2); every unit runs in the
-        // precision of its block (kernel_bf16.hip.h: KernelCfg::MIX).
-        const int hp = early_q_blocks(S, Sk, d, causal, flags, plan.q_block_rows);
-        if (pair_kernel_applies(B, H, S, d, causal, dtype, scale)) {   // (make_plan chose 128-row blocks, 256 threads, its grid)
-            p.qb0 = 0;
-            p.nQ = nQ_total;
-            p.units = B * H * nQ_total;
-            p.cpx = (p.units + 7) / 8;
-            p.jpx = device_cus() / 8;   // (workgroups of one dispatch round per XCD group: what the pairing counts in)
-            p.hp = hp;                  // (d = 128: one mixed-precision configuration, the unit's block says which precision)
-            e = d == 64 ? launch_bf16_pair_d64(p, hp, p.jpx, plan, causal, o_dtype, st) : launch_bf16_pair_d128(p, hp, p.jpx, plan, causal, o_dtype, st);
-        } else if (hp > 0 && causal) {
-            // the mixed-precision kernel; hp = nQ_total (FA_FLAG_F16_WEIGHTS, or every row sees fewer than FA_EARLY_KEYS keys) makes it the
-            // fp16-weights kernel of the 32x32x16 engine, K by LDS-DMA: faster under the mask than the 16x16x32 one with both tiles through
-            // registers (+2.4 % at S = 4096 d = 128, +8 % at S = 2048 d = 64: profiles/r04_tune_f_fp16_everywhere_*.log)
-            set_range(0, nQ_total, true);
-            p.hp = hp;
-            e = launch_bf16_causal_mix(p, plan, d, o_dtype, st);
-        } else if (hp > 0) {   // (without the mask early_q_blocks is all or nothing: hp = nQ_total, every unit runs with fp16 weights)
-            set_range(0, hp, true);
-            p.hp = hp;
-            e = launch_bf16_p16(p, plan, causal, d, o_dtype, st);
-        } else {
-            set_range(0, nQ_total, true);
-            e = d > 64 ? launch_bf16_d128(p, plan, causal, d != 128, o_dtype, st) : launch_bf16_d64(p, plan, causal, d != 64, o_dtype, st);
-        }
-    } else {
-        set_range(0, nQ_total, false);
-        e = dtype == FA_DTYPE_F32 ? launch_generic<float>(p, plan, d, causal, o_dtype, st) : launch_generic<__bf16>(p, plan, d, causal, o_dtype, st);
-    }
-    return (int)e;
+    if (r.family == Family::pair) return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p, r.hp, r.jpx);
+    if (r.family == Family::generic) return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p, d);
+    return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p);
 }
-
 }  // namespace fa
 
 extern "C" {
@@ -341,21 +330,11 @@ int flash_attention_weights(const void* Q, const void* K, const float* LSE, floa
     p.scale = scale; p.causal = is_causal;
     const int64_t blocks = (int64_t)batchSize * numHeads * p.nQ * p.nK;
     if (blocks > INT32_MAX) return FA_ERR_BAD_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int lds = weights_lds_bytes(dHead), lds_max = weights_lds_bytes(256);   // 80 KiB at dHead = 256
-    static std::atomic<bool> done[3][64];
-    hipError_t attr;
-    if (dtype == FA_DTYPE_F32) {
-        if ((attr = raise_lds_limit(attn_weights_kernel<float>, lds_max, done[0])) != hipSuccess) return (int)attr;
-        hipLaunchKernelGGL((attn_weights_kernel<float>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    } else if (dtype == FA_DTYPE_BF16) {
-        if ((attr = raise_lds_limit(attn_weights_kernel<__bf16>, lds_max, done[1])) != hipSuccess) return (int)attr;
-        hipLaunchKernelGGL((attn_weights_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    } else {
-        if ((attr = raise_lds_limit(attn_weights_kernel<fp8_t>, lds_max, done[2])) != hipSuccess) return (int)attr;
-        hipLaunchKernelGGL((attn_weights_kernel<fp8_t>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    }
-    return (int)hipGetLastError();
+    // (the LDS limit is raised to what dHead = 256 takes: 80 KiB)
+    const Kernel k = dtype == FA_DTYPE_F32    ? kernel_of<attn_weights_kernel<float>>(weights_lds_bytes(256))
+                     : dtype == FA_DTYPE_BF16 ? kernel_of<attn_weights_kernel<__bf16>>(weights_lds_bytes(256))
+                                              : kernel_of<attn_weights_kernel<fp8_t>>(weights_lds_bytes(256));
+    return (int)launch(k, (unsigned)blocks, 256, weights_lds_bytes(dHead), reinterpret_cast<hipStream_t>(stream), p);
 }
 
 int flash_attention_shard_range(int totalHeads, int rank, int nRanks, int* lo, int* hi) {
@@ -395,44 +374,30 @@ int flash_attention_plan(int batchSize, int numHeads, int seqLen, int dHead, boo
     if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (dtype == FA_DTYPE_FP8_E4M3 && dHead > 128) return FA_ERR_UNSUPPORTED_DHEAD;
     if (dHead > 256 || (dHead * fa::elem_size(dtype)) % 16 != 0) return FA_ERR_UNSUPPORTED_DHEAD;
-    return fa::make_plan(batchSize, numHeads, seqLen, dHead, is_causal, dtype, o_dtype, 1.0f, plan);
+    // (flash_attention_plan_ex with seqLenK = seqLen and bf16 weights: one range)
+    *plan = fa::route(batchSize, numHeads, seqLen, seqLen, dHead, is_causal, dtype, o_dtype, 1.0f, FA_FLAG_BF16_WEIGHTS, false).plan();
+    return FA_OK;
 }
 
 int flash_attention_plan_ex(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead, bool is_causal, int dtype,
                             int o_dtype, unsigned flags, fa_launch_plan_ex* early, fa_launch_plan_ex* main_) {
     fa_launch_plan base;
-    const int rc = flash_attention_plan(batchSize, numHeads, seqLenQ, dHead, is_causal, dtype, o_dtype, &base);
+    int rc = flash_attention_plan(batchSize, numHeads, seqLenQ, dHead, is_causal, dtype, o_dtype, &base);
     if (rc != FA_OK) return rc;
     if (seqLenK <= 0) return FA_ERR_BAD_SHAPE;
-    if (flags & ~(unsigned)(FA_FLAG_F16_WEIGHTS | FA_FLAG_BF16_WEIGHTS)) return FA_ERR_BAD_FLAGS;
-    if ((flags & FA_FLAG_F16_WEIGHTS) && ((flags & FA_FLAG_BF16_WEIGHTS) || !(dtype == FA_DTYPE_BF16 && (dHead == 64 || dHead == 128)))) return FA_ERR_BAD_FLAGS;
-    if ((flags & FA_FLAG_BF16_WEIGHTS) && dtype != FA_DTYPE_BF16) return FA_ERR_BAD_FLAGS;
-    const int nQ = getNumCta(seqLenQ, base.q_block_rows);
-    const int hp = base.kernel_id == 1 ? fa::early_q_blocks(seqLenQ, seqLenK, dHead, is_causal, flags, base.q_block_rows) : 0;
-    auto fill = [&](fa_launch_plan_ex* out, int qb0, int nq, bool p16) {
+    if ((rc = fa::check_flags(flags, dtype, dHead)) != FA_OK) return rc;
+    const fa::Route r = fa::route(batchSize, numHeads, seqLenQ, seqLenK, dHead, is_causal, dtype, o_dtype, 1.0f, flags, false);
+    // early: query blocks [0, hp), main: [hp, nQ).  A range that exists describes the launch; one that does not has grid 0 and the
+    // bf16-weights plan's other figures (the early one: the LDS size of the fp16-weights kernel at this d, mask and output type)
+    auto fill = [&](fa_launch_plan_ex* out, int qb0, int nq, int empty_lds) {
         if (!out) return;
-        out->launch = base;
+        out->launch = nq > 0 ? r.plan() : fa_launch_plan{base.q_block_rows, base.kv_block_rows, base.threads, 0, empty_lds, base.kernel_id};
         out->first_q_block = qb0;
         out->q_blocks = nq;
-        out->unit_lists = 0;
-        const int64_t units = (int64_t)batchSize * numHeads * nq;
-        if (nq == 0) out->launch.grid = 0;
-        else if (base.kernel_id == 1 || base.kernel_id == 2) out->launch.grid = (int)(8 * std::min<int64_t>((units + 7) / 8, fa::device_cus() / 8));
-        else out->launch.grid = (int)(8 * ((units + 7) / 8));
-        if (p16) out->launch.lds_bytes = is_causal ? fa::bf16_causal_mix_lds_bytes(dHead, o_dtype) : fa::bf16_p16_lds_bytes(false, dHead, o_dtype);
+        out->unit_lists = r.unit_lists;
     };
-    fill(early, 0, hp, true);
-    fill(main_, hp, nQ - hp, false);
-    if (base.kernel_id == 1 && base.threads == 256) {   // the pair kernel: one launch whatever the ranges, its own grid and LDS size
-        if (early && hp > 0) early->launch = base;
-        if (main_ && nQ - hp > 0) main_->launch = base;
-    } else if (hp > 0 && hp < nQ) {   // both kinds: ONE launch of the mixed-precision kernel over the list of all query blocks
-        const int64_t units = (int64_t)batchSize * numHeads * nQ;
-        const int grid = (int)(8 * std::min<int64_t>((units + 7) / 8, fa::device_cus() / 8));
-        const int lds = fa::bf16_causal_mix_lds_bytes(dHead, o_dtype);
-        if (early) { early->launch.grid = grid; early->launch.lds_bytes = lds; early->unit_lists = 1; }
-        if (main_) { main_->launch.grid = grid; main_->launch.lds_bytes = lds; main_->unit_lists = 1; }
-    }
+    fill(early, 0, r.hp, (is_causal ? fa::bf16_causal_mix_kernel : fa::bf16_p16_kernel)(dHead, o_dtype).lds_bytes);
+    fill(main_, r.hp, r.nQ - r.hp, base.lds_bytes);
     return FA_OK;
 }
 

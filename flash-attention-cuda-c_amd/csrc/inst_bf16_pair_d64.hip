@@ -1,11 +1,12 @@
 // inst_bf16_pair_d64.hip -- bf16 inputs, D = 64, small problems, with or without the causal mask (at most one 256-row unit per CU): 128-row units, one per
 // workgroup of four waves, two workgroups per CU paired heaviest + lightest (kernel_bf16.hip.h: fwd_mfma_pair_kernel; one translation
 // unit of libflash_attention.so: see launchers.hip.h).  D = 128 (one workgroup per CU): inst_bf16_pair_d128.hip.
+#include <algorithm>
+
 #include "kernel_bf16.hip.h"
 #include "launchers.hip.h"
 
 namespace fa {
-namespace {
 
 // bf16 weights: the engine of the persistent kernels (32x32x16 under the mask, 16x16x32 without; LDS-DMA staging).  Without the mask the row
 // sums are the exact fp32 ones (the persistent kernels' LSE instantiation) whether or not the call asks for the LSE: one instantiation
@@ -15,41 +16,16 @@ template <bool CAUSAL, typename OutT>
 using PairB = KernelCfg<64, CAUSAL, OutT, 2, Opt{.sum_mfma = 0, .waves = 4, .p_f16 = true}>;      // fp16 weights
 
 template <bool CAUSAL, typename OutT>
-constexpr int pair_lds() {
-    return PairA<CAUSAL, OutT>::LDS_BYTES > PairB<CAUSAL, OutT>::LDS_BYTES ? PairA<CAUSAL, OutT>::LDS_BYTES : PairB<CAUSAL, OutT>::LDS_BYTES;
-}
-static_assert(pair_lds<true, float>() <= 80 * 1024 - 256 && pair_lds<true, __bf16>() <= 80 * 1024 - 256, "two workgroups per CU");
+constexpr int pair_lds = std::max(PairA<CAUSAL, OutT>::LDS_BYTES, PairB<CAUSAL, OutT>::LDS_BYTES);
+static_assert(pair_lds<true, float> <= 80 * 1024 - 256 && pair_lds<true, __bf16> <= 80 * 1024 - 256, "two workgroups per CU");
 
-template <bool CAUSAL, typename OutT>
-hipError_t launch_pair(const Params& p, int hp, int jpx, const fa_launch_plan& plan, hipStream_t st) {
-    constexpr int lds = pair_lds<CAUSAL, OutT>();
-    static std::atomic<bool> done[64];
-    const hipError_t attr = raise_lds_limit(fwd_mfma_pair_kernel<PairA<CAUSAL, OutT>, PairB<CAUSAL, OutT>>, lds, done);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((fwd_mfma_pair_kernel<PairA<CAUSAL, OutT>, PairB<CAUSAL, OutT>>), dim3(plan.grid), dim3(plan.threads), lds, st, p, hp, jpx);
-    return hipGetLastError();
+// launched with (Params, hp, jpx): p.nQ = 128-row query blocks per head, the first hp of them take fp16 weights
+Kernel bf16_pair_d64_kernel(bool causal, int o_dtype) {
+    return by_out(o_dtype, [&]<class OutT>() {
+        return by_bool(causal, [&]<bool CAUSAL>() {
+            return kernel_of<fwd_mfma_pair_kernel<PairA<CAUSAL, OutT>, PairB<CAUSAL, OutT>>>(pair_lds<CAUSAL, OutT>);
+        });
+    });
 }
-template <bool CAUSAL>
-hipError_t by_out(const Params& p, int hp, int jpx, const fa_launch_plan& plan, int o_dtype, hipStream_t st) {
-    if (o_dtype == FA_DTYPE_F32) return launch_pair<CAUSAL, float>(p, hp, jpx, plan, st);
-    if (o_dtype == FA_DTYPE_BF16) return launch_pair<CAUSAL, __bf16>(p, hp, jpx, plan, st);
-    return launch_pair<CAUSAL, _Float16>(p, hp, jpx, plan, st);
-}
-template <bool CAUSAL>
-int lds_by_out(int o_dtype) {
-    if (o_dtype == FA_DTYPE_F32) return pair_lds<CAUSAL, float>();
-    if (o_dtype == FA_DTYPE_BF16) return pair_lds<CAUSAL, __bf16>();
-    return pair_lds<CAUSAL, _Float16>();
-}
-
-}  // namespace
-
-// p.nQ = 128-row query blocks per head; hp of them (the first ones) take fp16 weights; plan.grid = 8 x (a group's units, at most 2 jpx)
-// workgroups of 256 threads
-hipError_t launch_bf16_pair_d64(const Params& p, int hp, int jpx, const fa_launch_plan& plan, bool causal, int o_dtype, hipStream_t st) {
-    return causal ? by_out<true>(p, hp, jpx, plan, o_dtype, st) : by_out<false>(p, hp, jpx, plan, o_dtype, st);
-}
-
-int bf16_pair_d64_lds_bytes(bool causal, int o_dtype) { return causal ? lds_by_out<true>(o_dtype) : lds_by_out<false>(o_dtype); }
 
 }  // namespace fa

@@ -114,11 +114,6 @@ struct KernelCfg {
 template <int D, bool CAUSAL, typename OutT, int ESZ = 2, bool STAMP = false, bool PAD = false, bool LSE = false>
 using ProdCfg = KernelCfg<D, CAUSAL, OutT, ESZ, Opt{.stamp = STAMP, .pad = PAD, .m16 = CAUSAL ? 0 : -1, .sum_mfma = LSE ? 0 : -1}>;
 
-// The fp16-weights kernels (FA_FLAG_F16_WEIGHTS, and the early query blocks of the default precision): weights rounded to fp16, V
-// staged as fp16, fp32 sum of the unrounded weights (so the LSE is exact too)
-template <int D, bool CAUSAL, typename OutT>
-using P16Cfg = KernelCfg<D, CAUSAL, OutT, 2, Opt{.sum_mfma = 0, .p_f16 = true}>;
-
 // Workgroup-wide OR of a per-lane predicate through one LDS word per wave and ONE barrier.  (__syncthreads_or takes two barriers, 256
 // bytes of static LDS and -- it linearises threadIdx.y / .z -- two registers that hipcc spills to scratch in the largest kernels.)
 // A wave rewrites its word only a pass later, with at least two workgroup barriers in between: every wave has read by then.
