@@ -7,6 +7,8 @@ entry points for that path:
 * ``flash_attention(Q, K, V, O, ...)`` -- the launch signature of
   ``twoLoaderMhaFlashAttentionKernel`` (reference ``kernels/FlashAttention.cuh:59-63``; launched at
   ``tests/main.cu:60-61``): dense ``[B, H, S, d]`` device tensors, ``scale``, ``is_causal``.
+* ``flash_attention_backward(Q, K, V, O, dO, lse)`` -- dQ, dK, dV of that forward (bf16 inputs, d = 64 / 128), and
+  ``attention(Q, K, V)``, the forward as a differentiable ``torch.autograd.Function``.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -32,7 +34,7 @@ FA_EARLY_KEYS = 1024
 
 # every symbol include/flash_attention.h declares
 EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", "flash_attention_cross", "flash_attention_ex", "flash_attention_weights", "flash_attention_shard_range", "flash_attention_sharded",
-           "flash_attention_plan", "flash_attention_plan_ex",
+           "flash_attention_plan", "flash_attention_plan_ex", "flash_attention_backward", "flash_attention_backward_workspace_size",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -91,6 +93,10 @@ def lib() -> ctypes.CDLL:
         px = ctypes.POINTER(FaLaunchPlanEx)
         L.flash_attention_plan_ex.argtypes = [i, i, i, i, i, b, i, i, ctypes.c_uint, px, px]
         L.flash_attention_plan_ex.restype = i
+        L.flash_attention_backward.argtypes = [vp] * 10 + [i, i, i, i, i, f, b, i, i, i] + [sp] * 8 + [vp]
+        L.flash_attention_backward.restype = i
+        L.flash_attention_backward_workspace_size.argtypes = [i, i, i, i]
+        L.flash_attention_backward_workspace_size.restype = ctypes.c_size_t
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -297,3 +303,97 @@ def multi_head_attention(Q, K, V, num_heads, is_causal=False, return_attn=False,
         return out, None
     _, lse = flash_attention(view(Q), view(K), view(V), view(out), scale=scale, is_causal=is_causal, return_lse=True)
     return out, attention_weights(view(Q), view(K), lse, scale=scale, is_causal=is_causal)
+
+
+def _strides(t):
+    if t.stride(3) != 1:
+        raise ValueError("last dimension must be contiguous")
+    return FaStrides(t.stride(0), t.stride(1), t.stride(2))
+
+
+def backward_workspace_size(B, H, Sq, d):
+    """Bytes of device scratch flash_attention_backward needs."""
+    return int(lib().flash_attention_backward_workspace_size(B, H, Sq, d))
+
+
+def flash_attention_backward(Q, K, V, O, dO, lse, scale=None, is_causal=False, grad_dtype=None, dQ=None, dK=None, dV=None,
+                             stream=None):
+    """(dQ, dK, dV) of O = softmax(scale * Q K^T [+ causal mask]) V, recomputing the softmax from ``lse`` -- the LSE a
+    ``flash_attention(..., return_lse=True)`` call returned with the same Q, K, scale and mask.
+
+    Q, K, V: bf16 [B, H, Sq, d] / [B, H, Sk, d] device tensors, d = 64 or 128; O and dO: [B, H, Sq, d] in fp32 or bf16 (one type
+    for both); lse: dense fp32 [B, H, Sq].  Strided views are accepted (last dimension contiguous).  ``grad_dtype`` (fp32 or
+    bf16) defaults to the type of O; dQ / dK / dV may be given (shaped like Q / K / V).  The workspace is allocated with torch on
+    the tensors' device, on ``stream``, like gradients this call allocates.  Asynchronous on ``stream`` (default: torch's current
+    stream); the caller orders its other streams after it, as for any torch kernel.  No CPU fallback."""
+    import torch
+    if not all(t.is_cuda for t in (Q, K, V, O, dO, lse)):
+        raise RuntimeError("flash_attention_backward needs device tensors (no CPU fallback)")
+    if Q.dim() != 4 or K.shape != V.shape or Q.shape[:2] != K.shape[:2] or Q.shape[3] != K.shape[3] or O.shape != Q.shape \
+            or dO.shape != Q.shape:
+        raise ValueError("Q, O, dO must be [B, H, Sq, d] and K, V [B, H, Sk, d]")
+    if O.dtype != dO.dtype:
+        raise TypeError("O and dO must share a dtype")
+    B, H, S, d = Q.shape
+    Sk = K.shape[2]
+    if lse.shape != (B, H, S) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse must be dense fp32 [B, H, Sq]")
+    if scale is None:
+        scale = 1.0 / float(d) ** 0.5
+    gd = grad_dtype or O.dtype
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # the workspace (and any gradient allocated here) belongs to the stream the kernels run on: the caching allocator hands a
+        # block freed on stream s only to later work on s, which runs after these kernels -- allocated on another stream, the
+        # workspace released at return could be reused by that stream while the kernels still read and add into it
+        with torch.cuda.stream(s):
+            dQ = torch.empty((B, H, S, d), dtype=gd, device=Q.device) if dQ is None else dQ
+            dK = torch.empty((B, H, Sk, d), dtype=gd, device=Q.device) if dK is None else dK
+            dV = torch.empty((B, H, Sk, d), dtype=gd, device=Q.device) if dV is None else dV
+            if dQ.shape != Q.shape or dK.shape != K.shape or dV.shape != K.shape or not (dQ.dtype == dK.dtype == dV.dtype):
+                raise ValueError("dQ must be shaped like Q, dK and dV like K, all three of one dtype")
+            ws = torch.empty(backward_workspace_size(B, H, S, d), dtype=torch.uint8, device=Q.device)
+        st = [_strides(t) for t in (Q, K, V, O, dO, dQ, dK, dV)]
+        rc = lib().flash_attention_backward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), lse.data_ptr(),
+                                            dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), ws.data_ptr(), B, H, S, Sk, d,
+                                            float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(O.dtype),
+                                            _dtype_code(dQ.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(s))
+    _check(rc)
+    return dQ, dK, dV
+
+
+def _attention_function():
+    import torch
+
+    class _Attention(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, Q, K, V, is_causal, scale, out_dtype):
+            O, lse = flash_attention(Q, K, V, scale=scale, is_causal=is_causal, out_dtype=out_dtype, return_lse=True)
+            ctx.save_for_backward(Q, K, V, O, lse)
+            ctx.is_causal, ctx.scale = is_causal, scale
+            return O
+
+        @staticmethod
+        def backward(ctx, dO):
+            Q, K, V, O, lse = ctx.saved_tensors
+            dO = dO.to(O.dtype)
+            if dO.stride(-1) != 1:
+                dO = dO.contiguous()
+            dQ, dK, dV = flash_attention_backward(Q, K, V, O, dO, lse, scale=ctx.scale, is_causal=ctx.is_causal)
+            return dQ.to(Q.dtype), dK.to(K.dtype), dV.to(V.dtype), None, None, None
+
+    return _Attention
+
+
+_AttentionFn = None
+
+
+def attention(Q, K, V, is_causal=False, scale=None, out_dtype=None):
+    """Differentiable O = softmax(scale * Q K^T [+ causal mask]) V: the forward is ``flash_attention(..., return_lse=True)``, the
+    backward ``flash_attention_backward`` (bf16 inputs, d = 64 / 128 for the backward; gradients in the inputs' type)."""
+    global _AttentionFn
+    if _AttentionFn is None:
+        _AttentionFn = _attention_function()
+    if scale is None:
+        scale = 1.0 / float(Q.shape[-1]) ** 0.5
+    return _AttentionFn.apply(Q, K, V, bool(is_causal), float(scale), out_dtype)

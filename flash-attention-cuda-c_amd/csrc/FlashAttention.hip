@@ -16,6 +16,7 @@
 #include "launchers.hip.h"
 #include "generic.hip.h"
 #include "weights.hip.h"
+#include "bwd_bf16.hip.h"
 
 namespace fa {
 
@@ -399,6 +400,70 @@ int flash_attention_plan_ex(int batchSize, int numHeads, int seqLenQ, int seqLen
     fill(early, 0, r.hp, (is_causal ? fa::bf16_causal_mix_kernel : fa::bf16_p16_kernel)(dHead, o_dtype).lds_bytes);
     fill(main_, r.hp, r.nQ - r.hp, base.lds_bytes);
     return FA_OK;
+}
+
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+size_t flash_attention_backward_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead) {
+    if (batchSize <= 0 || numHeads <= 0 || seqLenQ <= 0 || dHead <= 0) return 0;
+    const size_t rows = (size_t)batchSize * numHeads * seqLenQ;
+    return round256(rows * sizeof(float)) + round256(rows * dHead * sizeof(float));   // delta, then the fp32 dQ accumulator
+}
+
+int flash_attention_backward(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
+                             void* dQ, void* dK, void* dV, void* workspace, int batchSize, int numHeads, int seqLenQ,
+                             int seqLenK, int dHead, float scale, bool is_causal, int dtype, int o_dtype, int grad_dtype,
+                             const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                             const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
+                             void* stream) {
+    using namespace fa;
+    const void* ptrs[] = {Q, K, V, O, dO, LSE, dQ, dK, dV, workspace};
+    for (const void* q : ptrs)
+        if (!q) return FA_ERR_NULL_POINTER;
+    for (const void* q : ptrs)
+        if (!aligned16(q)) return FA_ERR_MISALIGNED;
+    const int B = batchSize, H = numHeads, Sq = seqLenQ, Sk = seqLenK, d = dHead;
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
+    if ((int64_t)B * H > INT32_MAX / 2 || Sq > (1 << 24) || Sk > (1 << 24)) return FA_ERR_BAD_SHAPE;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
+    if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (grad_dtype != FA_DTYPE_F32 && grad_dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
+    const int esz = elem_size(dtype), osz = elem_size(o_dtype), gsz = elem_size(grad_dtype);
+    if (!strides_ok(sQ, esz, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d) ||
+        !strides_ok(sdO, osz, d) || !strides_ok(sdQ, gsz, d) || !strides_ok(sdK, gsz, d) || !strides_ok(sdV, gsz, d))
+        return FA_ERR_BAD_STRIDE;
+    // the forward's MFMA-path limit on one head's K / V extent
+    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
+    if (((int64_t)Sk + 192) * ks * esz >= (1ll << 31) || ((int64_t)Sk + 192) * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    const int64_t heads = (int64_t)B * H, nK = (Sk + 255) / 256, rows = heads * Sq;
+    if (heads * nK > INT32_MAX || rows * d / 4 / 256 + 1 > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    BwdParams p;
+    p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.dO = dO; p.lse = LSE;
+    p.dQ = dQ; p.dK = dK; p.dV = dV;
+    p.delta = (float*)workspace;
+    p.dq_acc = (float*)((char*)workspace + round256((size_t)rows * sizeof(float)));
+    auto st3 = [](const fa_strides* s, int64_t S, int64_t& sb, int64_t& sh, int64_t& ss, int64_t Hn, int64_t dd) {
+        sb = s ? s->strideB : Hn * S * dd; sh = s ? s->strideH : S * dd; ss = s ? s->strideS : dd;
+    };
+    st3(sQ, Sq, p.qB, p.qH, p.qS, H, d);    st3(sK, Sk, p.kB, p.kH, p.kS, H, d);    st3(sV, Sk, p.vB, p.vH, p.vS, H, d);
+    st3(sO, Sq, p.oB, p.oH, p.oS, H, d);    st3(sdO, Sq, p.doB, p.doH, p.doS, H, d);
+    st3(sdQ, Sq, p.dqB, p.dqH, p.dqS, H, d); st3(sdK, Sk, p.dkB, p.dkH, p.dkS, H, d); st3(sdV, Sk, p.dvB, p.dvH, p.dvS, H, d);
+    p.H = H; p.Sq = Sq; p.Sk = Sk;
+    p.heads = (int)heads;
+    p.nK = (int)nK;
+    p.scale = scale;
+    p.inv_scale = 1.0f / scale;
+    p.c = scale * 1.4426950408889634f;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int rpb = 256 / (d / 8);
+    hipError_t e = launch(bwd_pre_kernel_of(d, o_dtype), (unsigned)((rows + rpb - 1) / rpb), 256, 0, st, p);
+    if (e != hipSuccess) return (int)e;
+    const Kernel mk = bwd_main_kernel_of(d, is_causal, o_dtype, grad_dtype);
+    if ((e = launch(mk, (unsigned)(heads * nK), 256, mk.lds_bytes, st, p)) != hipSuccess) return (int)e;
+    return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
 }
 
 const char* flash_attention_error_string(int code) {

@@ -1,5 +1,5 @@
 /*
- * flash_attention.h -- C ABI of the MI355X-native FlashAttention forward path.
+ * flash_attention.h -- C ABI of the MI355X-native FlashAttention forward path (and its backward pass: flash_attention_backward).
  *
  * Drop-in boundary for the ONE hot path of GMichailov/Flash-Attention-CUDA-C: the fused
  * QK^T -> online softmax -> PV forward kernel
@@ -271,6 +271,46 @@ typedef struct fa_launch_plan_ex {
 
 int flash_attention_plan_ex(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead, bool is_causal,
                             int dtype, int o_dtype, unsigned flags, fa_launch_plan_ex* early, fa_launch_plan_ex* main);
+
+/*
+ * flash_attention_backward -- the gradients of O = softmax(scale * Q K^T [+ causal mask]) V with respect to Q, K and V, P recomputed
+ * from Q, K and the forward's LSE (no N x N matrix is stored):
+ *     P  = exp(scale * Q K^T - LSE)          delta = rowsum(dO * O)
+ *     dV = P^T dO                            dS    = P * (dO V^T - delta)
+ *     dQ = scale * dS K                      dK    = scale * dS^T Q
+ *   Q, O, dO, dQ   [batchSize, numHeads, seqLenQ, dHead]      K, V, dK, dV   [batchSize, numHeads, seqLenK, dHead]
+ *   LSE            dense fp32 [batchSize, numHeads, seqLenQ], as flash_attention_lse / _cross / _ex return it
+ *   workspace      caller-owned device scratch of flash_attention_backward_workspace_size(batchSize, numHeads, seqLenQ, dHead)
+ *                  bytes, 16-byte aligned; its contents on entry are ignored (fp32 delta, then the fp32 dQ accumulator)
+ *   sQ .. sdV      element strides as for flash_attention_cross, or NULL (dense)
+ * The conventions are the forward's: arguments are validated before any launch, nothing is allocated, the host is never
+ * synchronised, the work is enqueued on `stream` (three kernels in one chain: graph-capturable).
+ *
+ * Mask.  is_causal is the forward's top-left mask on absolute indices (key k hidden when k > q); any seqLenQ, seqLenK >= 1.
+ * Every element of dQ, dK and dV is written; keys that no query sees (under the mask: k >= seqLenQ) get dK = dV = 0.
+ *
+ * Supported: dtype = FA_DTYPE_BF16 (Q, K, V); o_dtype in {F32, BF16}, the type of both O and dO; grad_dtype in {F32, BF16}, the type
+ * of dQ, dK and dV; dHead 64 or 128; scale finite and > 0.  One head's K / V extent (seqLenK x row stride) below 2^31 bytes, as on
+ * the forward's MFMA paths.  Other inputs are rejected before any launch with the forward's codes: fp32 / fp8 inputs and F16 O or
+ * gradients FA_ERR_UNSUPPORTED_DTYPE, any other dHead FA_ERR_UNSUPPORTED_DHEAD, a non-finite or non-positive scale FA_ERR_BAD_SCALE,
+ * null pointers, misalignment, bad strides and shapes FA_ERR_NULL_POINTER / _MISALIGNED / _BAD_STRIDE / _BAD_SHAPE.
+ *
+ * Precision.  P is recomputed in fp32 and rounded to bf16 before dV^T += dO^T P; dS is rounded to bf16 before dK^T += Q^T dS and
+ * dQ += dS K; an fp32 dO is rounded to bf16 for the MFMA products (delta is summed from the given O and dO in fp32); every product
+ * is accumulated in fp32, and gradients are rounded once, to grad_dtype, when they are written.
+ *
+ * Determinism.  dK and dV are summed by one workgroup each, in a fixed order: bitwise reproducible from run to run.  dQ is summed
+ * across the key blocks of a head with fp32 atomics, so its last bits may vary from run to run.
+ */
+size_t flash_attention_backward_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead);
+
+int flash_attention_backward(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
+                             void* dQ, void* dK, void* dV, void* workspace,
+                             int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead,
+                             float scale, bool is_causal, int dtype, int o_dtype, int grad_dtype,
+                             const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                             const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
+                             void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
