@@ -9,6 +9,8 @@ entry points for that path:
   ``tests/main.cu:60-61``): dense ``[B, H, S, d]`` device tensors, ``scale``, ``is_causal``.
 * ``flash_attention_backward(Q, K, V, O, dO, lse)`` -- dQ, dK, dV of that forward (bf16 inputs, d = 64 / 128), and
   ``attention(Q, K, V)``, the forward as a differentiable ``torch.autograd.Function``.
+  All three accept grouped-query attention: K, V ``[B, Hkv, Sk, d]`` with Hkv dividing H; query head h attends K/V head
+  ``h // (H // Hkv)`` (``repeat_interleave(H // Hkv, dim=1)`` without the copy), and dK, dV come back shaped like K, V.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -35,6 +37,7 @@ FA_EARLY_KEYS = 1024
 # every symbol include/flash_attention.h declares
 EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", "flash_attention_cross", "flash_attention_ex", "flash_attention_weights", "flash_attention_shard_range", "flash_attention_sharded",
            "flash_attention_plan", "flash_attention_plan_ex", "flash_attention_backward", "flash_attention_backward_workspace_size",
+           "flash_attention_gqa", "flash_attention_backward_gqa",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -81,6 +84,8 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_cross.restype = i
         L.flash_attention_ex.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, b, i, i, sp, sp, sp, sp, ctypes.c_uint, vp]
         L.flash_attention_ex.restype = i
+        L.flash_attention_gqa.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, f, b, i, i, sp, sp, sp, sp, ctypes.c_uint, vp]
+        L.flash_attention_gqa.restype = i
         L.flash_attention_weights.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, b, i, sp, sp, vp]
         L.flash_attention_weights.restype = i
         ip, pp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)
@@ -95,6 +100,8 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_plan_ex.restype = i
         L.flash_attention_backward.argtypes = [vp] * 10 + [i, i, i, i, i, f, b, i, i, i] + [sp] * 8 + [vp]
         L.flash_attention_backward.restype = i
+        L.flash_attention_backward_gqa.argtypes = [vp] * 10 + [i, i, i, i, i, i, f, b, i, i, i] + [sp] * 8 + [vp]
+        L.flash_attention_backward_gqa.restype = i
         L.flash_attention_backward_workspace_size.argtypes = [i, i, i, i]
         L.flash_attention_backward_workspace_size.restype = ctypes.c_size_t
         L.flash_attention_error_string.argtypes = [i]
@@ -169,6 +176,8 @@ def flash_attention(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None
     are read from Q.shape, ``scale`` defaults to 1/sqrt(d) (tests/main.cu:27).  K and V may hold a
     different number of rows than Q (``[B, H, Sk, d]``: the seqLenQ / seqLenK of the reference's first
     API, kernels/FlashAttention.cuh:23); the causal mask stays ``k > q`` on absolute indices.
+    Grouped-query attention: K and V may hold fewer heads, ``[B, Hkv, Sk, d]`` with Hkv dividing H; query head h then attends
+    K/V head ``h // (H // Hkv)`` (flash_attention_gqa; the result equals the call on ``K.repeat_interleave(H // Hkv, 1)``).
     Asynchronous on ``stream`` (default: torch's current stream).  Returns O, or ``(O, LSE)`` with
     ``return_lse=True`` (LSE: fp32 [B, H, S], natural-log sum of exp(scale * scores) over the visible keys).
     ``weights_dtype`` (bf16 inputs): None = the library default (fp16 softmax weights on the rows that see fewer than
@@ -179,12 +188,13 @@ def flash_attention(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None
     import torch
     if not (Q.is_cuda and K.is_cuda and V.is_cuda):
         raise RuntimeError("flash_attention needs device tensors (no CPU fallback)")
-    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[:2] != K.shape[:2] or Q.shape[3] != K.shape[3]:
-        raise ValueError("Q must be [B, H, S, d] and K, V [B, H, Sk, d]")
+    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] or Q.shape[3] != K.shape[3] \
+            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
+        raise ValueError("Q must be [B, H, S, d] and K, V [B, Hkv, Sk, d] with Hkv dividing H")
     if not (Q.dtype == K.dtype == V.dtype):
         raise TypeError("Q, K, V must share a dtype")
     B, H, S, d = Q.shape
-    Sk = K.shape[2]
+    Hkv, Sk = K.shape[1:3]
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     if O is None:
@@ -207,7 +217,11 @@ def flash_attention(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None
         else:
             raise TypeError("weights_dtype must be torch.float16 or torch.bfloat16")
     with torch.cuda.device(Q.device):
-        if flags:
+        if Hkv != H:
+            refs = [ctypes.byref(_strides(t)) for t in (Q, K, V, O)]
+            rc = lib().flash_attention_gqa(*ptrs, lse.data_ptr() if lse is not None else None, B, H, Hkv, S, Sk, d, *common, *refs,
+                                           flags, _stream_ptr(stream))
+        elif flags:
             st = []
             for t in (Q, K, V, O):
                 if t.stride(3) != 1:
@@ -321,21 +335,22 @@ def flash_attention_backward(Q, K, V, O, dO, lse, scale=None, is_causal=False, g
     """(dQ, dK, dV) of O = softmax(scale * Q K^T [+ causal mask]) V, recomputing the softmax from ``lse`` -- the LSE a
     ``flash_attention(..., return_lse=True)`` call returned with the same Q, K, scale and mask.
 
-    Q, K, V: bf16 [B, H, Sq, d] / [B, H, Sk, d] device tensors, d = 64 or 128; O and dO: [B, H, Sq, d] in fp32 or bf16 (one type
-    for both); lse: dense fp32 [B, H, Sq].  Strided views are accepted (last dimension contiguous).  ``grad_dtype`` (fp32 or
+    Q, K, V: bf16 [B, H, Sq, d] / [B, Hkv, Sk, d] device tensors, d = 64 or 128, Hkv dividing H (grouped-query attention as in
+    ``flash_attention``: dK, dV are shaped like K, V, each the sum over the query heads that share the head); O and dO:
+    [B, H, Sq, d] in fp32 or bf16 (one type for both); lse: dense fp32 [B, H, Sq].  Strided views are accepted (last dimension contiguous).  ``grad_dtype`` (fp32 or
     bf16) defaults to the type of O; dQ / dK / dV may be given (shaped like Q / K / V).  The workspace is allocated with torch on
     the tensors' device, on ``stream``, like gradients this call allocates.  Asynchronous on ``stream`` (default: torch's current
     stream); the caller orders its other streams after it, as for any torch kernel.  No CPU fallback."""
     import torch
     if not all(t.is_cuda for t in (Q, K, V, O, dO, lse)):
         raise RuntimeError("flash_attention_backward needs device tensors (no CPU fallback)")
-    if Q.dim() != 4 or K.shape != V.shape or Q.shape[:2] != K.shape[:2] or Q.shape[3] != K.shape[3] or O.shape != Q.shape \
-            or dO.shape != Q.shape:
-        raise ValueError("Q, O, dO must be [B, H, Sq, d] and K, V [B, H, Sk, d]")
+    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] or Q.shape[3] != K.shape[3] \
+            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0 or O.shape != Q.shape or dO.shape != Q.shape:
+        raise ValueError("Q, O, dO must be [B, H, Sq, d] and K, V [B, Hkv, Sk, d] with Hkv dividing H")
     if O.dtype != dO.dtype:
         raise TypeError("O and dO must share a dtype")
     B, H, S, d = Q.shape
-    Sk = K.shape[2]
+    Hkv, Sk = K.shape[1:3]
     if lse.shape != (B, H, S) or lse.dtype != torch.float32 or not lse.is_contiguous():
         raise ValueError("lse must be dense fp32 [B, H, Sq]")
     if scale is None:
@@ -348,16 +363,20 @@ def flash_attention_backward(Q, K, V, O, dO, lse, scale=None, is_causal=False, g
         # workspace released at return could be reused by that stream while the kernels still read and add into it
         with torch.cuda.stream(s):
             dQ = torch.empty((B, H, S, d), dtype=gd, device=Q.device) if dQ is None else dQ
-            dK = torch.empty((B, H, Sk, d), dtype=gd, device=Q.device) if dK is None else dK
-            dV = torch.empty((B, H, Sk, d), dtype=gd, device=Q.device) if dV is None else dV
+            dK = torch.empty((B, Hkv, Sk, d), dtype=gd, device=Q.device) if dK is None else dK
+            dV = torch.empty((B, Hkv, Sk, d), dtype=gd, device=Q.device) if dV is None else dV
             if dQ.shape != Q.shape or dK.shape != K.shape or dV.shape != K.shape or not (dQ.dtype == dK.dtype == dV.dtype):
                 raise ValueError("dQ must be shaped like Q, dK and dV like K, all three of one dtype")
             ws = torch.empty(backward_workspace_size(B, H, S, d), dtype=torch.uint8, device=Q.device)
         st = [_strides(t) for t in (Q, K, V, O, dO, dQ, dK, dV)]
-        rc = lib().flash_attention_backward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), lse.data_ptr(),
-                                            dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), ws.data_ptr(), B, H, S, Sk, d,
-                                            float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(O.dtype),
-                                            _dtype_code(dQ.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), lse.data_ptr(),
+                dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), ws.data_ptr())
+        tail = (S, Sk, d, float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(O.dtype), _dtype_code(dQ.dtype),
+                *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        if Hkv != H:
+            rc = lib().flash_attention_backward_gqa(*ptrs, B, H, Hkv, *tail)
+        else:
+            rc = lib().flash_attention_backward(*ptrs, B, H, *tail)
     _check(rc)
     return dQ, dK, dV
 
@@ -390,7 +409,8 @@ _AttentionFn = None
 
 def attention(Q, K, V, is_causal=False, scale=None, out_dtype=None):
     """Differentiable O = softmax(scale * Q K^T [+ causal mask]) V: the forward is ``flash_attention(..., return_lse=True)``, the
-    backward ``flash_attention_backward`` (bf16 inputs, d = 64 / 128 for the backward; gradients in the inputs' type)."""
+    backward ``flash_attention_backward`` (bf16 inputs, d = 64 / 128 for the backward; gradients in the inputs' type).  K and V
+    may hold fewer heads than Q (grouped-query attention, see ``flash_attention``); their gradients are shaped like them."""
     global _AttentionFn
     if _AttentionFn is None:
         _AttentionFn = _attention_function()

@@ -25,12 +25,12 @@ namespace fa {
 // ------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-static int fill_params(Params& p, const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H,
+static int fill_params(Params& p, const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H, int Hkv,
                        int S, int Sk, int d, float scale, const fa_strides* sQ, const fa_strides* sK,
                        const fa_strides* sV, const fa_strides* sO) {
     p.Q = Q; p.K = K; p.V = V; p.O = O; p.lse = lse;
     const int64_t dS = d, dH = (int64_t)S * d, dB = (int64_t)H * S * d;      // dense Q / O
-    const int64_t kH = (int64_t)Sk * d, kB = (int64_t)H * Sk * d;            // dense K / V
+    const int64_t kH = (int64_t)Sk * d, kB = (int64_t)Hkv * Sk * d;          // dense K / V
     p.qB = sQ ? sQ->strideB : dB; p.qH = sQ ? sQ->strideH : dH; p.qS = sQ ? sQ->strideS : dS;
     p.kB = sK ? sK->strideB : kB; p.kH = sK ? sK->strideH : kH; p.kS = sK ? sK->strideS : dS;
     p.vB = sV ? sV->strideB : kB; p.vH = sV ? sV->strideH : kH; p.vS = sV ? sV->strideS : dS;
@@ -38,6 +38,8 @@ static int fill_params(Params& p, const void* Q, const void* K, const void* V, v
     p.B = B; p.H = H; p.S = S; p.Sk = Sk; p.d = d;
     p.scale = scale;
     p.scale_log2 = scale * 1.4426950408889634f;
+    const int64_t G = H / Hkv;
+    p.kv_mul = (unsigned)(((1ll << 31) + G - 1) / G);   // loaders.hip.h: kv_head
     return FA_OK;
 }
 
@@ -48,6 +50,12 @@ static int elem_size(int dtype) {
         case FA_DTYPE_FP8_E4M3: return 1;
         default: return 0;
     }
+}
+
+// Grouped-query attention: Hkv K/V heads, each shared by the G = H / Hkv consecutive query heads h with h / G equal (Hkv = H: one
+// each).  (H * G < 2^31: what the kernels' multiply-and-shift form of h / G is exact for -- loaders.hip.h: kv_head.)
+static bool kv_heads_ok(int H, int Hkv) {
+    return H > 0 && Hkv > 0 && H % Hkv == 0 && (int64_t)H * (H / Hkv) < (1ll << 31);
 }
 
 static bool strides_ok(const fa_strides* s, int esz, int d) {
@@ -233,11 +241,14 @@ static Route route(int B, int H, int S, int Sk, int d, bool causal, int dtype, i
     return r;
 }
 
-static int run(const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H, int S, int Sk, int d,
+// Every forward entry point ends here.  Hkv: K/V heads (flash_attention_gqa; every other entry point: Hkv = H).  The route -- the
+// kernel, its units (query head, query block) and grid -- does not depend on Hkv: only the K/V head a unit reads does.
+static int run(const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H, int Hkv, int S, int Sk, int d,
                float scale, bool causal, int dtype, int o_dtype, const fa_strides* sQ,
                const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream, unsigned flags = 0) {
     int rc = validate(Q, K, V, O, B, H, S, d, scale, dtype, o_dtype);
     if (rc != FA_OK) return rc;
+    if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
     if ((rc = check_flags(flags, dtype, d)) != FA_OK) return rc;
     if ((flags & FA_FLAG_F16_WEIGHTS) && !(scale > 0.f)) return FA_ERR_BAD_FLAGS;
     if (Sk <= 0 || Sk > (1 << 24)) return FA_ERR_BAD_SHAPE;
@@ -254,7 +265,7 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
     }
     if (r.units > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;   // unit indices are 32-bit
     Params p;
-    fill_params(p, Q, K, V, O, lse, B, H, S, Sk, d, scale, sQ, sK, sV, sO);
+    fill_params(p, Q, K, V, O, lse, B, H, Hkv, S, Sk, d, scale, sQ, sK, sV, sO);
     p.dbg = nullptr;
     p.qb0 = 0;
     p.nQ = r.nQ;
@@ -274,13 +285,13 @@ extern "C" {
 int flash_attention(const void* Q, const void* K, const void* V, void* O, int batchSize, int numHeads,
                     int seqLen, int dHead, float scale, bool is_causal, int dtype, int o_dtype,
                     void* stream) {
-    return fa::run(Q, K, V, O, nullptr, batchSize, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
+    return fa::run(Q, K, V, O, nullptr, batchSize, numHeads, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
                    nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int flash_attention_lse(const void* Q, const void* K, const void* V, void* O, float* LSE, int batchSize, int numHeads,
                         int seqLen, int dHead, float scale, bool is_causal, int dtype, int o_dtype, void* stream) {
-    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
+    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
                    nullptr, nullptr, nullptr, nullptr, stream);
 }
 
@@ -288,7 +299,7 @@ int flash_attention_strided(const void* Q, const void* K, const void* V, void* O
                             int numHeads, int seqLen, int dHead, float scale, bool is_causal, int dtype,
                             int o_dtype, const fa_strides* sQ, const fa_strides* sK,
                             const fa_strides* sV, const fa_strides* sO, void* stream) {
-    return fa::run(Q, K, V, O, nullptr, batchSize, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype, sQ,
+    return fa::run(Q, K, V, O, nullptr, batchSize, numHeads, numHeads, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype, sQ,
                    sK, sV, sO, stream);
 }
 
@@ -296,7 +307,7 @@ int flash_attention_cross(const void* Q, const void* K, const void* V, void* O, 
                           int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int o_dtype,
                           const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                           void* stream) {
-    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, seqLenQ, seqLenK, dHead, scale, is_causal, dtype, o_dtype, sQ,
+    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, numHeads, seqLenQ, seqLenK, dHead, scale, is_causal, dtype, o_dtype, sQ,
                    sK, sV, sO, stream);
 }
 
@@ -304,8 +315,16 @@ int flash_attention_ex(const void* Q, const void* K, const void* V, void* O, flo
                        int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int o_dtype,
                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                        unsigned flags, void* stream) {
-    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, seqLenQ, seqLenK, dHead, scale, is_causal, dtype, o_dtype, sQ,
-                   sK, sV, sO, stream, flags);
+    return flash_attention_gqa(Q, K, V, O, LSE, batchSize, numHeads, numHeads, seqLenQ, seqLenK, dHead, scale, is_causal, dtype,
+                               o_dtype, sQ, sK, sV, sO, flags, stream);
+}
+
+int flash_attention_gqa(const void* Q, const void* K, const void* V, void* O, float* LSE, int batchSize, int numHeads,
+                        int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int o_dtype,
+                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                        unsigned flags, void* stream) {
+    return fa::run(Q, K, V, O, LSE, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, scale, is_causal, dtype, o_dtype,
+                   sQ, sK, sV, sO, stream, flags);
 }
 
 int flash_attention_weights(const void* Q, const void* K, const float* LSE, float* P, int batchSize, int numHeads,
@@ -361,7 +380,7 @@ int flash_attention_sharded(int nDevices, const int* deviceIds, const void* cons
         if (hi == lo) continue;                       // more devices than heads: nothing for this one
         if ((e = hipSetDevice(deviceIds[r])) != hipSuccess) { rc = (int)e; break; }
         // the slab is a [hi-lo, 1, seqLen, dHead] problem of its own
-        rc = fa::run(Q[r], K[r], V[r], O[r], nullptr, hi - lo, 1, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
+        rc = fa::run(Q[r], K[r], V[r], O[r], nullptr, hi - lo, 1, 1, seqLen, seqLen, dHead, scale, is_causal, dtype, o_dtype,
                      nullptr, nullptr, nullptr, nullptr, streams ? streams[r] : nullptr);
     }
     (void)hipSetDevice(home);
@@ -416,6 +435,16 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
                              const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                              const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
                              void* stream) {
+    return flash_attention_backward_gqa(Q, K, V, O, dO, LSE, dQ, dK, dV, workspace, batchSize, numHeads, numHeads, seqLenQ, seqLenK,
+                                        dHead, scale, is_causal, dtype, o_dtype, grad_dtype, sQ, sK, sV, sO, sdO, sdQ, sdK, sdV, stream);
+}
+
+int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
+                                 void* dQ, void* dK, void* dV, void* workspace, int batchSize, int numHeads, int numHeadsKV,
+                                 int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int o_dtype,
+                                 int grad_dtype, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                                 const fa_strides* sO, const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK,
+                                 const fa_strides* sdV, void* stream) {
     using namespace fa;
     const void* ptrs[] = {Q, K, V, O, dO, LSE, dQ, dK, dV, workspace};
     for (const void* q : ptrs)
@@ -425,6 +454,8 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
     const int B = batchSize, H = numHeads, Sq = seqLenQ, Sk = seqLenK, d = dHead;
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
     if ((int64_t)B * H > INT32_MAX / 2 || Sq > (1 << 24) || Sk > (1 << 24)) return FA_ERR_BAD_SHAPE;
+    if (!kv_heads_ok(H, numHeadsKV)) return FA_ERR_BAD_SHAPE;
+    const int Hkv = numHeadsKV;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
@@ -437,8 +468,9 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
     // the forward's MFMA-path limit on one head's K / V extent
     const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
     if (((int64_t)Sk + 192) * ks * esz >= (1ll << 31) || ((int64_t)Sk + 192) * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
-    const int64_t heads = (int64_t)B * H, nK = (Sk + 255) / 256, rows = heads * Sq;
-    if (heads * nK > INT32_MAX || rows * d / 4 / 256 + 1 > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    // the main kernel's grid: one workgroup per 256-key block of every (batch, K/V head)
+    const int64_t heads = (int64_t)B * H, kv_heads = (int64_t)B * Hkv, nK = (Sk + 255) / 256, rows = heads * Sq;
+    if (kv_heads * nK > INT32_MAX || rows * d / 4 / 256 + 1 > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
     BwdParams p;
     p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.dO = dO; p.lse = LSE;
@@ -448,11 +480,13 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
     auto st3 = [](const fa_strides* s, int64_t S, int64_t& sb, int64_t& sh, int64_t& ss, int64_t Hn, int64_t dd) {
         sb = s ? s->strideB : Hn * S * dd; sh = s ? s->strideH : S * dd; ss = s ? s->strideS : dd;
     };
-    st3(sQ, Sq, p.qB, p.qH, p.qS, H, d);    st3(sK, Sk, p.kB, p.kH, p.kS, H, d);    st3(sV, Sk, p.vB, p.vH, p.vS, H, d);
+    st3(sQ, Sq, p.qB, p.qH, p.qS, H, d);    st3(sK, Sk, p.kB, p.kH, p.kS, Hkv, d);  st3(sV, Sk, p.vB, p.vH, p.vS, Hkv, d);
     st3(sO, Sq, p.oB, p.oH, p.oS, H, d);    st3(sdO, Sq, p.doB, p.doH, p.doS, H, d);
-    st3(sdQ, Sq, p.dqB, p.dqH, p.dqS, H, d); st3(sdK, Sk, p.dkB, p.dkH, p.dkS, H, d); st3(sdV, Sk, p.dvB, p.dvH, p.dvS, H, d);
+    st3(sdQ, Sq, p.dqB, p.dqH, p.dqS, H, d); st3(sdK, Sk, p.dkB, p.dkH, p.dkS, Hkv, d); st3(sdV, Sk, p.dvB, p.dvH, p.dvS, Hkv, d);
     p.H = H; p.Sq = Sq; p.Sk = Sk;
     p.heads = (int)heads;
+    p.Hkv = Hkv; p.group = H / Hkv;
+    p.kv_heads = (int)kv_heads;
     p.nK = (int)nK;
     p.scale = scale;
     p.inv_scale = 1.0f / scale;
@@ -461,8 +495,8 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
     const int rpb = 256 / (d / 8);
     hipError_t e = launch(bwd_pre_kernel_of(d, o_dtype), (unsigned)((rows + rpb - 1) / rpb), 256, 0, st, p);
     if (e != hipSuccess) return (int)e;
-    const Kernel mk = bwd_main_kernel_of(d, is_causal, o_dtype, grad_dtype);
-    if ((e = launch(mk, (unsigned)(heads * nK), 256, mk.lds_bytes, st, p)) != hipSuccess) return (int)e;
+    const Kernel mk = bwd_main_kernel_of(d, is_causal, o_dtype, grad_dtype, p.group > 1);
+    if ((e = launch(mk, (unsigned)(kv_heads * nK), 256, mk.lds_bytes, st, p)) != hipSuccess) return (int)e;
     return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
 }
 

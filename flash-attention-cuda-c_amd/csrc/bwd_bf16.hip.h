@@ -3,10 +3,12 @@
 //
 //   1. bwd_pre_kernel   one pass over the query rows: delta = rowsum(dO * O) (fp32, workspace) and the fp32 dQ accumulator
 //                       (workspace) zeroed -- it stands where a memset node would, so a captured graph stays one chain of kernels.
-//   2. bwd_main_kernel  one workgroup = 4 waves = one block of 256 keys of one (b, h); wave w owns keys 64w .. 64w+63 of the block
-//                       and keeps dV^T and dK^T of those keys in registers for the whole sweep over the head's query rows in 32-row
-//                       slices (under the causal mask from the first slice that sees the block), so dK and dV are written once, by
-//                       one workgroup: no cross-workgroup sum, bitwise reproducible.  Per slice, five 32x32x16 MFMA products:
+//   2. bwd_main_kernel  one workgroup = 4 waves = one block of 256 keys of one (b, K/V head); wave w owns keys 64w .. 64w+63 of the
+//                       block and keeps dV^T and dK^T of those keys in registers for the whole sweep over the query rows, in 32-row
+//                       slices (under the causal mask from the first slice that sees the block), of the G query heads that share the
+//                       K/V head, one head after the other (grouped-query attention; G = 1: the head itself) -- so dK and dV are
+//                       the group's sum, written once, by one workgroup: no cross-workgroup sum, bitwise reproducible.  Per slice,
+//                       five 32x32x16 MFMA products:
 //                         S'  = Q K^T  - LSE/scale     (accumulator seeded with the row constant: p = exp2(c S'), c = scale log2 e,
 //                         dP' = dO V^T - delta          needs no subtraction and no row maximum)
 //                         dV^T += dO^T P,   dK^T += Q^T dS   (dS = P * dP')
@@ -42,15 +44,17 @@ struct BwdParams {
     float* dq_acc;        // workspace: [B*H*Sq][D]
     int64_t qB, qH, qS, kB, kH, kS, vB, vH, vS, oB, oH, oS, doB, doH, doS;
     int64_t dqB, dqH, dqS, dkB, dkH, dkS, dvB, dvH, dvS;
-    int H, Sq, Sk;
+    int H, Sq, Sk;        // H: query heads
     int heads;            // B * H
+    int Hkv, group;       // K/V heads; group = H / Hkv query heads share each: query head h reads K/V head h / group
+    int kv_heads;         // B * Hkv
     int nK;               // 256-key blocks per head
     float scale;
     float inv_scale;      // 1 / scale: the S accumulator is seeded with -LSE / scale
     float c;              // scale * log2(e)
 };
 
-// Under the causal mask the key blocks are launched heaviest first (block 0 of every head, then block 1, ...): 3.53 ms against 5.9 ms
+// Under the causal mask the key blocks are launched heaviest first (block 0 of every K/V head, then block 1, ...): 3.53 ms against 5.9 ms
 // with a head's blocks adjacent at B 8 H 16 S 4096 d 128 (profiles/r05_backward_causal_order_ab.log; head-major ends on the heavy
 // blocks of the last heads).  Without the mask a head's blocks are adjacent, so they share the head's Q and dO in L2.
 #ifndef FA_BWD_HEAVY_FIRST
@@ -145,7 +149,9 @@ __device__ __forceinline__ f32x4 lds_read_f32x4(lds_ptr base, int byte_off) {
     return *reinterpret_cast<FA_LDS const f32x4*>(base + byte_off);
 }
 
-template <int D, bool CAUSAL, class OT, class GT>
+// GROUPED: more than one query head per K/V head (p.group > 1).  The instantiation without it is the sweep over ONE head: the
+// head switch below costs the d = 128 kernel, which has no register to spare, ~1 % when it is compiled in.
+template <int D, bool CAUSAL, class OT, class GT, bool GROUPED>
 __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
     using C = BwdCfg<D>;
     constexpr int ROW = C::ROW, SROW = C::SROW;
@@ -164,18 +170,22 @@ __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = lane & 31, hh = lane >> 5, G = lane >> 4;
-    int bh, kb;
-    if (CAUSAL && FA_BWD_HEAVY_FIRST) { kb = blockIdx.x / p.heads; bh = blockIdx.x - kb * p.heads; }
+    int bh, kb;   // bh: (batch, K/V head)
+    if (CAUSAL && FA_BWD_HEAVY_FIRST) { kb = blockIdx.x / p.kv_heads; bh = blockIdx.x - kb * p.kv_heads; }
     else { bh = blockIdx.x / p.nK; kb = blockIdx.x - bh * p.nK; }
-    const int b = bh / p.H, h = bh - b * p.H;
+    const int b = bh / p.Hkv, h = bh - b * p.Hkv;
     const int k0 = kb * 256;
-    const __bf16* Qh = p.Q + b * p.qB + h * p.qH;
     const __bf16* Kh = p.K + b * p.kB + h * p.kH;
     const __bf16* Vh = p.V + b * p.vB + h * p.vH;
-    const OT* dOh = (const OT*)p.dO + b * p.doB + h * p.doH;
-    const float* lse_h = p.lse + (int64_t)bh * p.Sq;
-    const float* delta_h = p.delta + (int64_t)bh * p.Sq;
-    float* acc_h = p.dq_acc + (int64_t)bh * p.Sq * D;
+    // the group's query heads h * group .. h * group + group - 1 are swept in turn: the head the NEXT slice is loaded from ...
+    const int group = GROUPED ? p.group : 1;
+    const int hq0 = h * group;
+    const int64_t bhq0 = (int64_t)b * p.H + hq0;
+    const __bf16* Qh = p.Q + b * p.qB + hq0 * p.qH;
+    const OT* dOh = (const OT*)p.dO + b * p.doB + hq0 * p.doH;
+    const float* lse_h = p.lse + bhq0 * p.Sq;
+    const float* delta_h = p.delta + bhq0 * p.Sq;
+    float* acc_h = p.dq_acc + bhq0 * p.Sq * D;   // ... and the dQ accumulator of the head being swept
 
     // K block -> LDS (rows past Sk are zeros)
     for (int c = tid; c < 256 * CPR; c += 256) {
@@ -247,7 +257,8 @@ __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
     };
 
     if (sl0 < nsl) load_slice(sl0 * 32);
-    for (int sl = sl0; sl < nsl; ++sl) {
+    // ONE loop over the slices of all the group's heads (sl wraps from the last slice of a head to the first of the next)
+    for (int sl = sl0, left = (nsl - sl0) * group; left > 0; --left) {
         const int q0 = sl * 32;
         __syncthreads();                     // every wave is done with the previous slice's images
         write_slice();
@@ -335,7 +346,15 @@ __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
             }
         }
         __syncthreads();                     // dS^T of all 256 keys is in LDS
-        if (sl + 1 < nsl) load_slice(q0 + 32);   // (issued here, where the S / dP / P / dS registers are dead)
+        // (issued here, where the S / dP / P / dS registers are dead)
+        if (left > 1) {
+            int qn = q0 + 32;
+            if (GROUPED && sl + 1 == nsl) {      // the group's next head, from its first slice
+                Qh += p.qH; dOh += p.doH; lse_h += p.Sq; delta_h += p.Sq;
+                qn = sl0 * 32;
+            }
+            load_slice(qn);
+        }
 
         // ---- dQ += dS K over the block's keys: wave w takes head columns [D/4 w, D/4 (w+1)) ----
         int kend = 256;                      // keys past this are hidden from every row of the slice (their dS is 0)
@@ -377,6 +396,7 @@ __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
                     if (q < p.Sq) unsafeAtomicAdd(acc_h + (int64_t)q * D + 16 * w + (lane & 15), dq[qt][i]);
                 }
         }
+        if (++sl == nsl && GROUPED) { sl = sl0; acc_h += (int64_t)p.Sq * D; }
     }
 
     // ---- dK = scale dS^T Q, dV = P^T dO: lane holds key kw + 32t + r, registers 4g .. 4g+3 = d rows 32n + 8g + 4hh .. +3 ----
@@ -403,7 +423,7 @@ __global__ __launch_bounds__(256, 1) void bwd_main_kernel(const BwdParams p) {
 // ---- selectors (inst_bwd_bf16.hip) ----
 struct Kernel;
 Kernel bwd_pre_kernel_of(int d, int o_dtype);
-Kernel bwd_main_kernel_of(int d, bool causal, int o_dtype, int grad_dtype);
+Kernel bwd_main_kernel_of(int d, bool causal, int o_dtype, int grad_dtype, bool grouped);
 Kernel bwd_post_kernel_of(int d, int grad_dtype);
 
 }  // namespace fa

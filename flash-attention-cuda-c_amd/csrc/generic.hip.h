@@ -37,11 +37,11 @@ __global__ __launch_bounds__(256) void fwd_generic_kernel(const Params p, const 
 
     int g, qb;
     if (!unit_of_block(p, CAUSAL, g, qb)) return;
-    const int b = g / p.H, h = g - b * p.H;
+    const int b = g / p.H, h = g - b * p.H, hk = kv_head(p, h);
     const int S = p.S, Sk = p.Sk;
     const InT* Qh = (const InT*)p.Q + b * p.qB + h * p.qH;
-    const InT* Kh = (const InT*)p.K + b * p.kB + h * p.kH;
-    const InT* Vh = (const InT*)p.V + b * p.vB + h * p.vH;
+    const InT* Kh = (const InT*)p.K + b * p.kB + hk * p.kH;
+    const InT* Vh = (const InT*)p.V + b * p.vB + hk * p.vH;
     OutT* Oh = (OutT*)p.O + b * p.oB + h * p.oH;
 
     const int tid = threadIdx.x;

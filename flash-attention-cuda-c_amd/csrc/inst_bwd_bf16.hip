@@ -17,12 +17,14 @@ Kernel bwd_pre_kernel_of(int d, int o_dtype) {
     });
 }
 
-Kernel bwd_main_kernel_of(int d, bool causal, int o_dtype, int grad_dtype) {
+Kernel bwd_main_kernel_of(int d, bool causal, int o_dtype, int grad_dtype, bool grouped) {
     return by_io(o_dtype, [&]<class OT>() {
         return by_io(grad_dtype, [&]<class GT>() {
             return by_bool(causal, [&]<bool CAUSAL>() {
-                return d == 128 ? kernel_of<bwd_main_kernel<128, CAUSAL, OT, GT>>(BwdCfg<128>::LDS_BYTES)
-                                : kernel_of<bwd_main_kernel<64, CAUSAL, OT, GT>>(BwdCfg<64>::LDS_BYTES);
+                return by_bool(grouped, [&]<bool GROUPED>() {
+                    return d == 128 ? kernel_of<bwd_main_kernel<128, CAUSAL, OT, GT, GROUPED>>(BwdCfg<128>::LDS_BYTES)
+                                    : kernel_of<bwd_main_kernel<64, CAUSAL, OT, GT, GROUPED>>(BwdCfg<64>::LDS_BYTES);
+                });
             });
         });
     });

@@ -281,10 +281,10 @@ struct UnitCtx {
     __device__ __forceinline__ void set(const Params& p, int g, int qb, int wave) {
         early = C::MIX && qb < p.hp;
         constexpr int ESZ = C::ESZ, KVBLK = 64, QBLK = C::QBLK, WROWS = 32;
-        const int b = g / p.H, h = g - b * p.H;
+        const int b = g / p.H, h = g - b * p.H, hk = kv_head(p, h);
         Qh = (const char*)p.Q + (b * p.qB + h * p.qH) * ESZ;
-        Kh = (const char*)p.K + (b * p.kB + h * p.kH) * ESZ;
-        Vh = (const char*)p.V + (b * p.vB + h * p.vH) * ESZ;
+        Kh = (const char*)p.K + (b * p.kB + hk * p.kH) * ESZ;
+        Vh = (const char*)p.V + (b * p.vB + hk * p.vH) * ESZ;
         Oh = (char*)p.O + (b * p.oB + h * p.oH) * (int64_t)sizeof(typename C::OutT);
         lse_head = p.lse ? p.lse + (int64_t)g * p.S : nullptr;
         q_row0 = qb * QBLK + wave * WROWS;              // first query row of this wave

@@ -53,13 +53,13 @@ __global__ __launch_bounds__(256, 2) void fwd_f32_mfma_kernel(const Params p) {
     if (!unit_of_block(p, CAUSAL, g, qb)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = g / p.H, hd = g - b * p.H;
+    const int b = g / p.H, hd = g - b * p.H, hk = kv_head(p, hd);
     const int S = p.S, Sk = p.Sk;
     const int h = lane >> 5, r31 = lane & 31;
 
     const char* Qh = (const char*)p.Q + (b * p.qB + hd * p.qH) * 4;
-    const char* Kh = (const char*)p.K + (b * p.kB + hd * p.kH) * 4;
-    const char* Vh = (const char*)p.V + (b * p.vB + hd * p.vH) * 4;
+    const char* Kh = (const char*)p.K + (b * p.kB + hk * p.kH) * 4;
+    const char* Vh = (const char*)p.V + (b * p.vB + hk * p.vH) * 4;
     char* Oh = (char*)p.O + (b * p.oB + hd * p.oH) * (int64_t)sizeof(OutT);
     const int64_t qSb = p.qS * 4, kSb = p.kS * 4, vSb = p.vS * 4, oSb = p.oS * (int64_t)sizeof(OutT);
 

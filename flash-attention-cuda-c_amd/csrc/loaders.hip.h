@@ -49,8 +49,14 @@ struct Params {
     int hp;           // mixed-precision kernels (KernelCfg::MIX): the query blocks qb < hp of every head take fp16 softmax weights
     float scale_log2; // scale * log2(e)
     float scale;
+    unsigned kv_mul = 1u << 31;  // grouped-query attention: ceil(2^31 / G), G = query heads per K/V head (kv_head below); 2^31 = one each
     unsigned long long* dbg;  // diagnostic builds only (tests/fa_tune): per-wave segment cycle sums
 };
+
+// Grouped-query attention: query head h reads K/V head h / G.  The host passes kv_mul = ceil(2^31 / G), and (h * kv_mul) >> 31 is
+// h / G exactly for every h with h * G < 2^31 (run() checks numHeads * G): one scalar multiply and shift per unit instead of a
+// division, and with G = 1 (kv_mul = 2^31) the head itself.
+__device__ __forceinline__ int kv_head(const Params& p, int h) { return (int)(((uint64_t)(uint32_t)h * p.kv_mul) >> 31); }
 
 // The unit list a workgroup walks (kernel_bf16.hip.h: work_unit): the query blocks qb0 .. qb0 + nQ - 1 of every head.  The single
 // kernels take it from Params; the launch that mixes two configurations takes two of them beside ONE Params.

@@ -192,7 +192,8 @@ int flash_attention_cross(const void* Q, const void* K, const void* V, void* O, 
 
 /*
  * flash_attention_ex -- flash_attention_cross() plus option flags (FA_FLAG_*); flags = 0 is flash_attention_cross().
- * flash_attention(), _lse(), _strided(), _cross() and _sharded() all run with flags = 0.
+ * flash_attention(), _lse(), _strided(), _cross() and _sharded() all run with flags = 0.  It is flash_attention_gqa() with
+ * numHeadsKV = numHeads.
  */
 int flash_attention_ex(const void* Q, const void* K, const void* V, void* O, float* LSE,
                        int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead,
@@ -201,12 +202,35 @@ int flash_attention_ex(const void* Q, const void* K, const void* V, void* O, flo
                        const fa_strides* sO, unsigned flags, void* stream);
 
 /*
+ * flash_attention_gqa -- flash_attention_ex() for grouped-query attention: K and V hold numHeadsKV heads, each shared by a group of
+ * G = numHeads / numHeadsKV CONSECUTIVE query heads: query head h attends K/V head h / G (integer division), the convention of
+ * repeat_interleave(G, dim 1) on K and V.  numHeadsKV = 1 is multi-query attention; numHeadsKV = numHeads is flash_attention_ex()
+ * itself: the same route, the same launch, the same bits.
+ *   Q, O   [batchSize, numHeads, seqLenQ, dHead]      K, V   [batchSize, numHeadsKV, seqLenK, dHead]
+ *   LSE    fp32 [batchSize, numHeads, seqLenQ] or NULL;   sK, sV = NULL: dense with numHeadsKV heads
+ * The result is what flash_attention_ex() returns on K and V expanded G times, bit for bit (the same kernels run the same
+ * arithmetic; only the K/V head a work unit reads differs), without the copy: K/V memory and traffic are 1/G of the expanded form,
+ * and since the query heads of a group are neighbours in the kernels' unit list, they stream the shared head through one XCD's L2.
+ * Every dtype, dHead, mask, flag and stride flash_attention_ex() accepts is accepted, with the same error codes; in addition
+ * numHeadsKV <= 0, numHeads % numHeadsKV != 0 or numHeads * G >= 2^31 give FA_ERR_BAD_SHAPE (before any launch).
+ * flash_attention_plan() / _plan_ex() describe a grouped-query call when given numHeads = the QUERY heads: the work units are
+ * (query head, query block), which numHeadsKV does not alter.
+ * flash_attention_weights() and flash_attention_sharded() take one K/V head per query head only.
+ */
+int flash_attention_gqa(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                        int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                        float scale, bool is_causal, int dtype, int o_dtype,
+                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                        const fa_strides* sO, unsigned flags, void* stream);
+
+/*
  * flash_attention_weights -- the attention matrix the reference's oracle returns next to its output
  * (check.py:20,25 `attn`, printed by its demo at :42).  The fused kernel never stores it; this call
  * rebuilds it from Q, K and the LSE a flash_attention_lse / flash_attention_cross call produced:
  *     P[b,h,q,k] = exp(scale * <Q[b,h,q], K[b,h,k]> - LSE[b,h,q]),   0 where is_causal hides k > q
  * P is a dense fp32 [batchSize, numHeads, seqLenQ, seqLenK] device buffer (mind its size: this is an
  * inspection path for small seqLen).  Any dHead <= 256 with 16-byte rows; sQ / sK as above or NULL.
+ * One K head per query head (not grouped-query: for such a model pass K expanded to numHeads heads).
  */
 int flash_attention_weights(const void* Q, const void* K, const float* LSE, float* P,
                             int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead,
@@ -224,6 +248,7 @@ int flash_attention_weights(const void* Q, const void* K, const float* LSE, floa
  * dense [hi-lo, seqLen, dHead] slabs Q[r], K[r], V[r], O[r], the head range of rank r, and gets the same
  * kernel enqueued on streams[r] (NULL array or NULL entry = that device's default stream).  Asynchronous
  * like flash_attention(); the caller's current device is restored.  Returns the first error, else 0.
+ * One K/V head per query head (a grouped-query model shards over its K/V heads with flash_attention_gqa on each rank's slab).
  * (One process per GPU -- bench.py under torchrun -- just calls flash_attention() on its own slab.)
  */
 int flash_attention_shard_range(int totalHeads, int rank, int nRanks, int* lo, int* hi);
@@ -301,6 +326,18 @@ int flash_attention_plan_ex(int batchSize, int numHeads, int seqLenQ, int seqLen
  *
  * Determinism.  dK and dV are summed by one workgroup each, in a fixed order: bitwise reproducible from run to run.  dQ is summed
  * across the key blocks of a head with fp32 atomics, so its last bits may vary from run to run.
+ *
+ * flash_attention_backward_gqa -- the same for grouped-query attention (flash_attention_gqa: query head h attends K/V head h / G,
+ * G = numHeads / numHeadsKV):
+ *   Q, O, dO, dQ   [batchSize, numHeads, seqLenQ, dHead]      K, V, dK, dV   [batchSize, numHeadsKV, seqLenK, dHead]
+ *   LSE            dense fp32 [batchSize, numHeads, seqLenQ];   sK, sV, sdK, sdV = NULL: dense with numHeadsKV heads
+ *   workspace      flash_attention_backward_workspace_size(batchSize, numHeads, seqLenQ, dHead) bytes: it depends on the QUERY heads only
+ * dK and dV of a K/V head are the sums over its G query heads.  One workgroup owns 256 keys of one (batch, K/V head) and sweeps
+ * the query rows of the group's heads one head after the other with the same accumulators, so the determinism paragraph above
+ * holds for any G: dK and dV are summed by one workgroup each, in a fixed order; dQ with atomics.  (The grid is
+ * batchSize * numHeadsKV * ceil(seqLenK / 256) workgroups: few K/V heads on short sequences leave compute units idle.)
+ * Arguments are checked as flash_attention_backward checks them, and numHeadsKV as flash_attention_gqa does (FA_ERR_BAD_SHAPE).
+ * flash_attention_backward() is this call with numHeadsKV = numHeads: the same launches, the same bits.
  */
 size_t flash_attention_backward_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead);
 
@@ -311,6 +348,14 @@ int flash_attention_backward(const void* Q, const void* K, const void* V, const 
                              const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                              const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
                              void* stream);
+
+int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
+                                 void* dQ, void* dK, void* dV, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                 float scale, bool is_causal, int dtype, int o_dtype, int grad_dtype,
+                                 const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                 const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
+                                 void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
