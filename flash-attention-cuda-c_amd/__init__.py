@@ -11,6 +11,8 @@ entry points for that path:
   ``attention(Q, K, V)``, the forward as a differentiable ``torch.autograd.Function``.
   All three accept grouped-query attention: K, V ``[B, Hkv, Sk, d]`` with Hkv dividing H; query head h attends K/V head
   ``h // (H // Hkv)`` (``repeat_interleave(H // Hkv, dim=1)`` without the copy), and dK, dV come back shaped like K, V.
+* ``flash_attention_decode(Q, K, V, kv_lens)`` -- split-KV decode: 1 .. 16 new query rows per sequence against a long bf16 K/V
+  cache, per-sequence lengths in a device tensor, bottom-right-aligned causal mask (``decode_plan``, ``decode_workspace_size``).
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -33,11 +35,14 @@ FA_DTYPE_F32, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3, FA_DTYPE_F16 = 0, 1, 2, 3
 FA_FLAG_F16_WEIGHTS = 1     # flash_attention_ex: softmax weights rounded to fp16 on every row (bf16 inputs, d = 64 / 128)
 FA_FLAG_BF16_WEIGHTS = 2    # ... to bf16 on every row; flags = 0: fp16 on the rows that see fewer than FA_EARLY_KEYS keys, bf16 elsewhere
 FA_EARLY_KEYS = 1024
+FA_DECODE_MAX_Q = 16        # flash_attention_decode: most new query rows per sequence
+FA_DECODE_MAX_SPLITS = 64   # ... and the cap of num_splits
 
 # every symbol include/flash_attention.h declares
 EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", "flash_attention_cross", "flash_attention_ex", "flash_attention_weights", "flash_attention_shard_range", "flash_attention_sharded",
            "flash_attention_plan", "flash_attention_plan_ex", "flash_attention_backward", "flash_attention_backward_workspace_size",
            "flash_attention_gqa", "flash_attention_backward_gqa",
+           "flash_attention_decode", "flash_attention_decode_plan", "flash_attention_decode_workspace_size",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -53,6 +58,11 @@ class FaLaunchPlan(ctypes.Structure):
 
 class FaLaunchPlanEx(ctypes.Structure):
     _fields_ = [("launch", FaLaunchPlan), ("q_blocks", ctypes.c_int), ("first_q_block", ctypes.c_int), ("unit_lists", ctypes.c_int)]
+
+
+class FaDecodePlan(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("num_splits", "row_blocks", "rows_per_block", "kv_block_rows", "threads", "grid",
+                                            "lds_bytes", "combine_grid", "combine_threads")]
 
 
 class FlashAttentionError(RuntimeError):
@@ -104,6 +114,12 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_backward_gqa.restype = i
         L.flash_attention_backward_workspace_size.argtypes = [i, i, i, i]
         L.flash_attention_backward_workspace_size.restype = ctypes.c_size_t
+        L.flash_attention_decode.argtypes = [vp] * 7 + [i, i, i, i, i, i, f, b, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode.restype = i
+        L.flash_attention_decode_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_decode_plan.restype = i
+        L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
+        L.flash_attention_decode_workspace_size.restype = ctypes.c_size_t
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -379,6 +395,72 @@ def flash_attention_backward(Q, K, V, O, dO, lse, scale=None, is_causal=False, g
             rc = lib().flash_attention_backward(*ptrs, B, H, *tail)
     _check(rc)
     return dQ, dK, dV
+
+
+def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
+    """What a flash_attention_decode call launches (fa_decode_plan as a dict); ``num_splits`` 0 = the library's choice."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+
+
+def decode_workspace_size(B, H, Sq, d, num_splits):
+    """Bytes of device scratch flash_attention_decode needs for ``num_splits`` splits as planned (0 for one split)."""
+    return int(lib().flash_attention_decode_workspace_size(B, H, Sq, d, num_splits))
+
+
+def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
+                           O=None, workspace=None, stream=None):
+    """Split-KV decode: Q ``[B, H, Sq, d]`` with 1 <= Sq <= FA_DECODE_MAX_Q new rows per sequence against a K/V cache
+    ``[B, Hkv, capacity, d]`` (bf16, d = 64 or 128, Hkv dividing H; query head h reads K/V head ``h // (H // Hkv)``).
+
+    ``kv_lens``: int32 device tensor ``[B]``, the valid keys of each sequence, read by the kernel (the call never synchronises; a
+    captured graph sees the lengths of the moment), or None = the capacity.  Keys at and beyond the length may hold anything.
+    ``is_causal`` is BOTTOM-RIGHT aligned: the Sq rows are the last rows of the sequence, row i sees keys
+    ``k <= kv_lens[b] - Sq + i`` (and at least key 0) -- unlike ``flash_attention``, whose mask is top-left aligned.
+    ``num_splits``: 0 = the library's choice (``decode_plan``), > 0 forced.  ``workspace`` (uint8 device tensor of
+    ``decode_workspace_size`` bytes), when not given, is allocated with torch on the call's stream, like an ``O`` allocated here.
+    Strided views are accepted (last dimension contiguous).  Returns O, or ``(O, LSE)`` with ``return_lse=True`` (fp32 [B, H, Sq],
+    natural log).  Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
+    import torch
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError("flash_attention_decode needs device tensors (no CPU fallback)")
+    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] or Q.shape[3] != K.shape[3] \
+            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
+        raise ValueError("Q must be [B, H, Sq, d] and K, V [B, Hkv, capacity, d] with Hkv dividing H")
+    if not (Q.dtype == K.dtype == V.dtype):
+        raise TypeError("Q, K, V must share a dtype")
+    B, H, Sq, d = Q.shape
+    Hkv, Sk = K.shape[1:3]
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    if scale is None:
+        scale = 1.0 / float(d) ** 0.5
+    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
+    ns = decode_plan(B, H, Hkv, Sq, Sk, d, odt, num_splits)["num_splits"]
+    need = decode_workspace_size(B, H, Sq, d, ns)
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif O.shape != Q.shape or not O.is_cuda:
+                raise ValueError("O must be a device tensor shaped like Q")
+            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            if workspace is None and need:
+                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
+            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
+        st = [_strides(t) for t in (Q, K, V, O)]
+        rc = lib().flash_attention_decode(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(),
+                                          lse.data_ptr() if lse is not None else None,
+                                          kv_lens.data_ptr() if kv_lens is not None else None,
+                                          workspace.data_ptr() if need else None, B, H, Hkv, Sq, Sk, d, float(scale), bool(is_causal),
+                                          _dtype_code(Q.dtype), _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
 
 
 def _attention_function():

@@ -17,6 +17,7 @@
 #include "generic.hip.h"
 #include "weights.hip.h"
 #include "bwd_bf16.hip.h"
+#include "decode_bf16.hip.h"
 
 namespace fa {
 
@@ -278,6 +279,49 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
     if (r.family == Family::generic) return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p, d);
     return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p);
 }
+
+// ---- split-KV decode (decode_bf16.hip.h) ----
+// The launch decision of flash_attention_decode, from shapes only (seqLenK is the cache CAPACITY; the lengths live in device memory).
+// Work units are (batch, K/V head, row block, split).  Library's choice of the split count: enough units for DECODE_WGS_PER_CU
+// workgroups on every CU, no split shorter than DECODE_MIN_TILES key tiles of the capacity, at most FA_DECODE_MAX_SPLITS.
+// Measured (profiles/decode_split_sweep.log): the time is flat within 5 % from one to two workgroups per CU
+// on uniform batches -- two or three are resident per CU, so either is one resident round -- and a batch of unequal lengths, which
+// the host cannot see, balances 11 % better at two; a split of a single tile has nothing to prefetch behind and gains nothing.
+constexpr int DECODE_WGS_PER_CU = 2, DECODE_MIN_TILES = 2;
+
+struct DecodeRoute {
+    int ns, row_blocks, tiles;
+    int64_t grid;
+};
+
+static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits) {
+    DecodeRoute r{};
+    const int rows = (H / Hkv) * Sq;                     // packed rows per K/V head
+    r.row_blocks = (rows + DecodeCfg<128>::ROWS - 1) / DecodeCfg<128>::ROWS;
+    r.tiles = (Sk + DecodeCfg<128>::TILE - 1) / DecodeCfg<128>::TILE;
+    const int64_t units = (int64_t)B * Hkv * r.row_blocks;
+    if (numSplits > 0) r.ns = numSplits;
+    else {
+        const int64_t want = ((int64_t)DECODE_WGS_PER_CU * device_cus() + units - 1) / units;
+        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / DECODE_MIN_TILES, (int64_t)FA_DECODE_MAX_SPLITS}));
+    }
+    r.grid = units * r.ns;
+    return r;
+}
+
+static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits) {
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
+    if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
+    if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16 && o_dtype != FA_DTYPE_F16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (decode_route(B, H, Hkv, Sq, Sk, numSplits).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    return FA_OK;
+}
+
+static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 }  // namespace fa
 
 extern "C" {
@@ -498,6 +542,75 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     const Kernel mk = bwd_main_kernel_of(d, is_causal, o_dtype, grad_dtype, p.group > 1);
     if ((e = launch(mk, (unsigned)(kv_heads * nK), 256, mk.lds_bytes, st, p)) != hipSuccess) return (int)e;
     return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
+}
+
+int flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                int numSplits, fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits);
+    if (rc != FA_OK) return rc;
+    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits);
+    plan->num_splits = r.ns;
+    plan->row_blocks = r.row_blocks;
+    plan->rows_per_block = DecodeCfg<128>::ROWS;
+    plan->kv_block_rows = DecodeCfg<128>::TILE;
+    plan->threads = DecodeCfg<128>::THREADS;
+    plan->grid = (int)r.grid;
+    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
+    const int64_t rows = (int64_t)batchSize * numHeads * seqLenQ;
+    plan->combine_grid = r.ns > 1 ? (int)rows : 0;   // one workgroup per (batch, head, query row)
+    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    return FA_OK;
+}
+
+size_t flash_attention_decode_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead, int numSplits) {
+    if (batchSize <= 0 || numHeads <= 0 || seqLenQ <= 0 || dHead <= 0 || numSplits <= 1) return 0;
+    const size_t rows = (size_t)batchSize * numHeads * seqLenQ;
+    return fa::round16(rows * numSplits * dHead * sizeof(float)) + fa::round16(rows * numSplits * sizeof(float));   // partial O, then partial LSE
+}
+
+int flash_attention_decode(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, void* workspace,
+                           int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
+                           bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                           const fa_strides* sV, const fa_strides* sO, void* stream) {
+    using namespace fa;
+    if (!Q || !K || !V || !O) return FA_ERR_NULL_POINTER;
+    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
+    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
+    const int B = batchSize, H = numHeads, Hkv = numHeadsKV, Sq = seqLenQ, Sk = seqLenK, d = dHead;
+    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits);
+    if (rc != FA_OK) return rc;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
+    const int osz = elem_size(o_dtype);
+    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, 2, d) || !strides_ok(sV, 2, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
+    // K / V go through buffer descriptors with 32-bit byte offsets: the prefill paths' limit on one head's extent
+    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
+    if (((int64_t)Sk + 192) * ks * 2 >= (1ll << 31) || ((int64_t)Sk + 192) * vs * 2 >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
+    if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
+    const int64_t rows = (int64_t)B * H * Sq;
+    if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    DecodeParams p;
+    p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
+    p.part_o = (float*)workspace;
+    p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
+    p.qB = sQ ? sQ->strideB : (int64_t)H * Sq * d;   p.qH = sQ ? sQ->strideH : (int64_t)Sq * d;  p.qS = sQ ? sQ->strideS : d;
+    p.kB = sK ? sK->strideB : (int64_t)Hkv * Sk * d; p.kH = sK ? sK->strideH : (int64_t)Sk * d;  p.kS = ks;
+    p.vB = sV ? sV->strideB : (int64_t)Hkv * Sk * d; p.vH = sV ? sV->strideH : (int64_t)Sk * d;  p.vS = vs;
+    p.oB = sO ? sO->strideB : (int64_t)H * Sq * d;   p.oH = sO ? sO->strideH : (int64_t)Sq * d;  p.oS = sO ? sO->strideS : d;
+    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = Sk;
+    p.row_blocks = r.row_blocks; p.ns = r.ns;
+    p.rows = (int)rows;
+    p.o_dtype = o_dtype;
+    p.causal = is_causal;
+    p.scale_log2 = scale * 1.4426950408889634f;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Kernel sk = decode_split_kernel_of(d);
+    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
+    if (e != hipSuccess || r.ns == 1) return (int)e;
+    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
 }
 
 const char* flash_attention_error_string(int code) {

@@ -1,0 +1,305 @@
+// decode_bf16.hip.h -- split-KV decode: 1 .. FA_DECODE_MAX_Q new query rows per sequence against a long K/V cache, every sequence
+// of the batch at its own length (flash_attention_decode).
+//
+// The prefill kernels (kernel_bf16.hip.h) are built around 256 query rows per workgroup and one workgroup per (head, query block)
+// walking all keys.  Decode is the opposite shape: a handful of rows, and the K/V read IS the cost.  So here
+//   * the work unit is (batch, K/V head, row block, key split): the G * seqLenQ rows that share a K/V head are PACKED into the
+//     16-row M dimension of one MFMA tile (packed row = g * seqLenQ + i: query head g of the group, query row i), so a K/V tile
+//     is fetched once for the whole group, and the key range of every sequence is divided over `ns` splits in whole 128-key tiles;
+//   * a workgroup is four waves; per 128-key tile each wave takes 32 keys of its own, and the waves' (m, l, O) are merged
+//     through LDS once, at the end;
+//   * the products are swapped (S^T = K Q^T, O^T = V^T P^T; 16x16x32 MFMA): a softmax row then lives in the four lanes
+//     l, l^16, l^32, l^48, and the score registers ARE the B operand of the P.V product -- the MFMA's k index is free to stand
+//     for any key as long as both operands agree, and V^T is read with that same key order;
+//   * K goes straight from global memory to the registers of its A fragment (16 keys x 64 contiguous bytes per wave instruction),
+//     one tile ahead; V needs a k-major fragment: it is loaded in whole 256-byte rows one tile ahead, written row-major into a
+//     wave-private LDS image (row stride +32 bytes: the eight rows of a half-wave's transposed read fall on different banks) and
+//     read back with ds_read_b64_tr_b16.  Wave-private: no barrier in the loop;
+//   * K and V are fetched through buffer descriptors whose record count is THIS SEQUENCE's length: rows at and beyond kvLens[b]
+//     arrive as 0 whatever the memory holds, their scores are masked to -inf by key index, P = 0 there;
+//   * the kernel is bandwidth-bound with MFMA to spare, which is spent on precision: the softmax weights enter the P.V product
+//     as a bf16 hi + lo pair (two MFMAs against the bf16 V as it lies in memory), ~16 significant bits, so the stated tolerance
+//     holds for short caches too (where plain bf16 weights miss it: flash_attention.h, FA_EARLY_KEYS) with no fp16 range caveat;
+//   * ns = 1: the split kernel normalises and writes O (and the LSE) itself.  ns > 1: it writes normalised fp32 partial outputs
+//     and partial log-sum-exps into slabs, and decode_combine_kernel -- a second launch on the same stream -- sums them in a fixed
+//     order: no atomics, the same bits run to run.  An empty split (a short sequence under many splits) writes O = 0, LSE = -inf
+//     and gets weight 0.
+#pragma once
+
+#include "../../include/flash_attention.h"
+#include "utils.hip.h"
+
+namespace fa {
+
+struct DecodeParams {
+    const __bf16* Q;
+    const __bf16* K;
+    const __bf16* V;
+    void* O;
+    float* lse;              // optional [B, H, Sq]
+    const int32_t* kv_lens;  // optional [B] (device memory)
+    float* part_o;           // ns > 1: [ns][B*H*Sq][D] normalised partial outputs
+    float* part_lse;         // ns > 1: [ns][B*H*Sq] partial log-sum-exps (natural log; -inf: empty split)
+    int64_t qB, qH, qS, kB, kH, kS, vB, vH, vS, oB, oH, oS;   // element strides
+    int H, Hkv, G, Sq, Sk;
+    int row_blocks, ns;
+    int rows;                // B * H * Sq
+    int o_dtype;
+    int causal;
+    float scale_log2;        // scale * log2(e)
+};
+
+template <int D>
+struct DecodeCfg {
+    static constexpr int WAVES = 4, THREADS = 256;
+    static constexpr int ROWS = 16;                    // packed rows per workgroup: M of the 16x16x32 MFMA
+    static constexpr int WKEYS = 32;                   // keys per wave per tile: K of the P.V MFMA
+    static constexpr int TILE = WAVES * WKEYS;         // keys per workgroup per inner-loop tile
+    static constexpr int KS = D / 32;                  // 32-wide k-steps of the Q K^T product
+    static constexpr int DG = D / 16;                  // 16-wide d groups of O^T
+    static constexpr int CPR = D / 8;                  // 16-byte chunks per K / V row
+    static constexpr int KPI = 64 / CPR;               // V rows one wave instruction loads
+    static constexpr int NV = WKEYS / KPI;             // V loads per lane per tile
+    static constexpr int VROW = D * 2 + 32;            // LDS bytes per V row
+    static constexpr int VIMG = WKEYS * VROW;          // a wave's V image; later its (O^T) merge buffer
+    static constexpr int OROW = (D + 4) * 4;           // merge buffer: bytes per packed row of fp32 O
+    static constexpr int ML_OFF = WAVES * VIMG;        // [wave][row] m, then l
+    static constexpr int LDS_BYTES = ML_OFF + 2 * WAVES * ROWS * 4;
+    static_assert(ROWS * OROW <= VIMG, "the merge buffer reuses the V image");
+};
+
+__device__ __forceinline__ void store_out(void* O, int o_dtype, int64_t idx, float v) {
+    if (o_dtype == FA_DTYPE_F32) ((float*)O)[idx] = v;
+    else if (o_dtype == FA_DTYPE_BF16) ((__bf16*)O)[idx] = (__bf16)v;
+    else ((_Float16*)O)[idx] = (_Float16)v;
+}
+
+template <int D>
+__global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams p) {
+    using C = DecodeCfg<D>;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const lds_ptr smem = (lds_ptr)smem_raw;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int r = lane & 15, h4 = lane >> 4;
+
+    // blockIdx -> (batch, K/V head, row block, split); the split index runs fastest
+    int u = blockIdx.x;
+    const int split = u % p.ns; u /= p.ns;
+    const int rb = u % p.row_blocks; u /= p.row_blocks;
+    const int kvh = u % p.Hkv;
+    const int b = u / p.Hkv;
+
+    int len = p.Sk;
+    if (p.kv_lens) len = min(max(p.kv_lens[b], 1), p.Sk);
+    len = __builtin_amdgcn_readfirstlane(len);
+    // this sequence's tiles, divided over the splits in whole tiles
+    const int nt = (len + C::TILE - 1) / C::TILE;
+    const int t0 = (int)(((int64_t)nt * split) / p.ns), t1 = (int)(((int64_t)nt * (split + 1)) / p.ns);
+
+    // this lane's packed row (column r of the swapped products): query head g of the group, query row i
+    const int pr = rb * C::ROWS + r;
+    const bool row_ok = pr < p.G * p.Sq;
+    const int g = row_ok ? pr / p.Sq : 0, qi = row_ok ? pr - g * p.Sq : 0;
+    const int h = kvh * p.G + g;
+    // keys this row sees: [0, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0
+    const int lim = p.causal ? max(len - p.Sq + qi + 1, 1) : len;
+
+    bf16x8 qf[C::KS];   // B fragment of Q^T: Q[row r][32 ks + 8 h4 .. + 7]
+    {
+        const __bf16* q = p.Q + b * p.qB + h * p.qH + qi * p.qS + 8 * h4;
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) {
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(bf16x8, row_ok ? *reinterpret_cast<const u32x4*>(q + 32 * ks) : z);
+        }
+    }
+
+    // descriptors over the VISIBLE part of this (batch, K/V head): rows >= len read as 0
+    const char* Kh = (const char*)(p.K + b * p.kB + kvh * p.kH);
+    const char* Vh = (const char*)(p.V + b * p.vB + kvh * p.vH);
+    const int ksb = (int)(p.kS * 2), vsb = (int)(p.vS * 2);
+    const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, (len - 1) * ksb + D * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t vrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, (len - 1) * vsb + D * 2, 0x00020000);
+    // K A fragment (kg, ks): key 16 kg + r of the wave's 32, 16-byte chunk 4 ks + h4
+    const int koff = (wave * C::WKEYS + r) * ksb + h4 * 16;
+    // V load n: key KPI n + lane / CPR of the wave's 32, chunk lane % CPR
+    const int vkey = lane / C::CPR, vch = lane % C::CPR;
+    const int voff = (wave * C::WKEYS + vkey) * vsb + vch * 16;
+    const lds_ptr vimg = smem + wave * C::VIMG;
+    const int vwr = vkey * C::VROW + vch * 16;
+    // transposed read (dg, jj): lane 4q + pp of quarter h4 supplies row 16 jj + 4 h4 + q, columns 16 dg + 4 pp .. + 3
+    const int vrd = (4 * h4 + ((lane & 15) >> 2)) * C::VROW + (lane & 3) * 8;
+
+    u32x4 kn[2][C::KS], vn[C::NV];
+    auto load_tile = [&](int t) {
+        const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
+#pragma unroll
+        for (int kg = 0; kg < 2; ++kg)
+#pragma unroll
+            for (int ks = 0; ks < C::KS; ++ks)
+                kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + kt + kg * 16 * ksb + ks * 64, 0, 0));
+#pragma unroll
+        for (int n = 0; n < C::NV; ++n)
+            vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + vt + n * C::KPI * vsb, 0, 0));
+    };
+
+    const float NEG_INF = -__builtin_inff();
+    float m = NEG_INF, l = 0.f;   // running max (log2 domain, shared by the row's four lanes) and this lane's share of the sum
+    f32x4 o[C::DG];               // O^T: d = 16 dg + 4 h4 + reg, packed row r
+#pragma unroll
+    for (int dg = 0; dg < C::DG; ++dg) o[dg] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    if (t0 < t1) load_tile(t0);
+    for (int t = t0; t < t1; ++t) {
+        // V of this tile: registers -> the wave's LDS image (the previous tile's reads are done: same wave, program order)
+#pragma unroll
+        for (int n = 0; n < C::NV; ++n) lds_write_b128(vimg, vwr + n * C::KPI * C::VROW, vn[n]);
+        f32x4 s[2];
+#pragma unroll
+        for (int kg = 0; kg < 2; ++kg) {
+            s[kg] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < C::KS; ++ks) s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, kn[kg][ks]), qf[ks], s[kg]);
+        }
+        if (t + 1 < t1) load_tile(t + 1);   // (wave-uniform) next tile's K and V: in flight under the softmax and the P.V product
+
+        // s[kg][reg]: key kb + 16 kg + 4 h4 + reg, packed row r
+        const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4;
+        float x[8];
+        float mx = NEG_INF;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int key = kb + 16 * (j >> 2) + (j & 3);
+            x[j] = key < lim ? s[j >> 2][j & 3] * p.scale_log2 : NEG_INF;
+            mx = fmaxf(mx, x[j]);
+        }
+        mx = max_all_quarters(mx);
+        const float m_new = fmaxf(m, mx);
+        const float m_use = m_new == NEG_INF ? 0.f : m_new;   // nothing visible yet: exp2(-inf - 0) = 0, never inf - inf
+        const float alpha = fast_exp2(m - m_use);
+        m = m_new;
+        float sum = 0.f;
+        uint32_t hi[4], lo[4];
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const float p0 = fast_exp2(x[j] - m_use), p1 = fast_exp2(x[j + 1] - m_use);
+            sum += p0 + p1;
+            // weights as a bf16 pair: hi = bf16(p), lo = bf16(p - hi) -- 16 significant bits between them
+            hi[j >> 1] = pack_bf16(p0, p1);
+            lo[j >> 1] = pack_bf16(p0 - bf16_lo(hi[j >> 1]), p1 - bf16_hi(hi[j >> 1]));
+        }
+        l = l * alpha + sum;
+        // B fragment of P^T: element j of quarter h4 = the MFMA's k index 8 h4 + j = key 16 (j >> 2) + 4 h4 + (j & 3)
+        const bf16x8 phi = __builtin_bit_cast(bf16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+        const bf16x8 plo = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
+#pragma unroll
+        for (int dg = 0; dg < C::DG; ++dg) {
+            // A fragment of V^T in that key order: rows 4 h4 .. + 3 (j < 4), rows 16 + 4 h4 .. + 3 (j >= 4)
+            const s16x4 a0 = lds_read_tr16_b64(vimg, vrd + dg * 32);
+            const s16x4 a1 = lds_read_tr16_b64(vimg, vrd + 16 * C::VROW + dg * 32);
+            typedef __attribute__((ext_vector_type(8))) short s16x8;
+            const bf16x8 a = __builtin_bit_cast(bf16x8, s16x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]});
+            o[dg] *= alpha;
+            o[dg] = mfma_16x16x32(a, phi, o[dg]);
+            o[dg] = mfma_16x16x32(a, plo, o[dg]);
+        }
+    }
+
+    // ---- merge the four waves' (m, l, O^T) through LDS: each wave writes into its own V image, one barrier ----
+    l = sum_all_quarters(l);
+    FA_LDS float* ml = reinterpret_cast<FA_LDS float*>(smem + C::ML_OFF);
+    if (h4 == 0) {
+        ml[wave * C::ROWS + r] = m;
+        ml[(C::WAVES + wave) * C::ROWS + r] = l;
+    }
+#pragma unroll
+    for (int dg = 0; dg < C::DG; ++dg)
+        *reinterpret_cast<FA_LDS f32x4*>(vimg + r * C::OROW + (16 * dg + 4 * h4) * 4) = o[dg];
+    __syncthreads();
+
+    // thread -> packed row tid / 16, DPT consecutive d
+    constexpr int DPT = D / 16;
+    const int orow = tid >> 4, d0 = (tid & 15) * DPT;
+    float M = NEG_INF;
+#pragma unroll
+    for (int w = 0; w < C::WAVES; ++w) M = fmaxf(M, ml[w * C::ROWS + orow]);
+    float L = 0.f, acc[DPT];
+#pragma unroll
+    for (int j = 0; j < DPT; ++j) acc[j] = 0.f;
+    if (M != NEG_INF) {
+#pragma unroll
+        for (int w = 0; w < C::WAVES; ++w) {
+            const float wgt = fast_exp2(ml[w * C::ROWS + orow] - M);   // a wave that saw nothing: exp2(-inf) = 0
+            L += wgt * ml[(C::WAVES + w) * C::ROWS + orow];
+            FA_LDS const float* src = reinterpret_cast<FA_LDS const float*>(smem + w * C::VIMG + orow * C::OROW) + d0;
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) acc[j] += wgt * src[j];
+        }
+    }
+    const int opr = rb * C::ROWS + orow;
+    if (opr >= p.G * p.Sq) return;
+    const int og = opr / p.Sq, oi = opr - og * p.Sq, oh = kvh * p.G + og;
+    const float inv = M != NEG_INF ? 1.0f / L : 0.f;                                   // empty split: O = 0
+    const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
+    const int64_t row = ((int64_t)b * p.H + oh) * p.Sq + oi;
+    if (p.ns == 1) {
+        const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + d0;
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) store_out(p.O, p.o_dtype, base + j, acc[j] * inv);
+        if (p.lse && (tid & 15) == 0) p.lse[row] = lse;
+    } else {
+        float* dst = p.part_o + ((int64_t)split * p.rows + row) * D + d0;
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) dst[j] = acc[j] * inv;
+        if ((tid & 15) == 0) p.part_lse[(int64_t)split * p.rows + row] = lse;
+    }
+}
+
+// Sum of the splits' partial results, in a fixed order: per (b, h, row)
+//     m = max_s lse_s,   O = sum_s exp(lse_s - m) O_s / sum_s exp(lse_s - m),   LSE = m + ln sum_s exp(lse_s - m)
+// rounded once, to the output type.  One workgroup per row, so that the reads of the up to 64 slabs are in flight together (a thread
+// that walks the splits one after the other pays one memory latency per split: 30 us at 64 splits): every wave loads the row's
+// partial LSEs, one split per lane, and reduces max and sum across its lanes; thread t then sums four consecutive d over the splits
+// t / (D/4), + 256 / (D/4), ..., and the 256 / (D/4) partial sums are added through LDS in slot order.  At least one split of a row is
+// not empty (every sequence has a key), so m is finite and an empty split's weight is exp(-inf) = 0.
+template <int D>
+__global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams p) {
+    static_assert(FA_DECODE_MAX_SPLITS <= WAVE, "one split per lane");
+    constexpr int TPR = D / 4, SLOTS = 256 / TPR;
+    __shared__ float wgt[WAVE];
+    __shared__ f32x4 part[SLOTS][TPR];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float mine = lane < p.ns ? p.part_lse[(int64_t)lane * p.rows + row] : -__builtin_inff();
+    float M = mine;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    const float w = __expf(mine - M);
+    float W = w;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) W += __shfl_xor(W, o);   // (a butterfly: the same sum, bit for bit, in every lane and wave)
+    if (tid < WAVE) wgt[tid] = w;
+    __syncthreads();
+    const int c = tid % TPR, slot = tid / TPR;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = slot; s < p.ns; s += SLOTS)
+        acc += wgt[s] * *reinterpret_cast<const f32x4*>(p.part_o + ((int64_t)s * p.rows + row) * D + 4 * c);
+    part[slot][c] = acc;
+    __syncthreads();
+    if (tid >= TPR) return;
+    f32x4 sum = part[0][c];
+#pragma unroll
+    for (int j = 1; j < SLOTS; ++j) sum += part[j][c];
+    const float inv = 1.0f / W;
+    const int oi = row % p.Sq, bh = row / p.Sq, oh = bh % p.H, b = bh / p.H;
+    const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + 4 * c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) store_out(p.O, p.o_dtype, base + j, sum[j] * inv);
+    if (p.lse && c == 0) p.lse[row] = M + __logf(W);
+}
+
+// ---- selectors (inst_decode_bf16.hip) ----
+struct Kernel;
+Kernel decode_split_kernel_of(int d);
+Kernel decode_combine_kernel_of(int d);
+
+}  // namespace fa

@@ -1,5 +1,6 @@
 /*
- * flash_attention.h -- C ABI of the MI355X-native FlashAttention forward path (and its backward pass: flash_attention_backward).
+ * flash_attention.h -- C ABI of the MI355X-native FlashAttention forward path (its backward pass: flash_attention_backward; its
+ * split-KV decode path: flash_attention_decode).
  *
  * Drop-in boundary for the ONE hot path of GMichailov/Flash-Attention-CUDA-C: the fused
  * QK^T -> online softmax -> PV forward kernel
@@ -183,6 +184,9 @@ int flash_attention_lse(const void* Q, const void* K, const void* V, void* O, fl
  * when k > q (kernels/utils.cuh:43) -- i.e. the mask is top-left aligned; query q sees keys
  * 0..min(q, seqLenK-1).  (A caller that wants the last query aligned with the last key offsets its K/V
  * view or runs non-causal over the prefix it may see.)
+ * flash_attention_decode() below has the OTHER alignment: its is_causal is bottom-right aligned (the query rows are the LAST rows
+ * of the sequence).  Top-left is right when the queries are the FIRST rows of the keys (self-attention, prefill from position 0);
+ * bottom-right when new tokens are appended to a cache (decode, speculative decoding).  The two agree when seqLenQ = seqLenK.
  */
 int flash_attention_cross(const void* Q, const void* K, const void* V, void* O, float* LSE,
                           int batchSize, int numHeads, int seqLenQ, int seqLenK, int dHead,
@@ -356,6 +360,72 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                  const fa_strides* sdO, const fa_strides* sdQ, const fa_strides* sdK, const fa_strides* sdV,
                                  void* stream);
+
+/*
+ * flash_attention_decode -- split-KV decode: 1 .. FA_DECODE_MAX_Q new query rows per sequence against a long K/V cache, each sequence
+ * of the batch at its own length.  The G = numHeads / numHeadsKV query heads of a group times the seqLenQ rows are packed into one
+ * MFMA tile, so the K/V cache -- whose read IS the cost of decode -- is read once per group; and the key range of every sequence is
+ * divided over `numSplits` workgroups, whose partial results a second small kernel combines, so that a single sequence fills the chip.
+ *   Q, O     [batchSize, numHeads, seqLenQ, dHead]      K, V   [batchSize, numHeadsKV, seqLenK, dHead]; seqLenK is the cache CAPACITY
+ *   sQ .. sO element strides as for flash_attention_cross, or NULL (dense): a [B, S, Hkv, d] cache is a view.  Query head h reads
+ *            K/V head h / G (flash_attention_gqa's convention)
+ *   kvLens   DEVICE pointer to int32[batchSize], the number of valid keys of each sequence, read BY THE KERNEL -- never by the host: the
+ *            call stays asynchronous and graph-capturable, and a replayed graph sees the lengths of the moment.  NULL = seqLenK for
+ *            every sequence.  A value is clamped on the device into [1, seqLenK].  Keys at and beyond kvLens[b] never enter the result:
+ *            they may hold NaN, inf or stale data
+ *   LSE      optional dense fp32 [batchSize, numHeads, seqLenQ], natural log, over the visible keys (as flash_attention_lse returns it:
+ *            decode results of several devices or cache pages can be merged with it); NULL = not wanted.  O is the same bits either way
+ *   workspace caller-owned device scratch of flash_attention_decode_workspace_size(batchSize, numHeads, seqLenQ, dHead, num_splits)
+ *            bytes, 16-byte aligned; contents on entry ignored (fp32 partial outputs, then partial log-sum-exps, one slab per split).
+ *            Not needed (may be NULL) when the plan says num_splits == 1
+ *   numSplits 0 = the library chooses, on the HOST and from the shapes only (seqLenK, not kvLens); > 0 = forced (tests, tuning);
+ *            < 0 or > FA_DECODE_MAX_SPLITS: FA_ERR_BAD_SHAPE.  flash_attention_decode_plan() reports the choice and the launches
+ * The conventions are the forward's: arguments are validated before any launch, nothing is allocated, the host is never synchronised,
+ * no global state, nothing printed; the work is enqueued on `stream` (one kernel, or two in a chain when num_splits > 1).
+ *
+ * Mask.  is_causal here is BOTTOM-RIGHT aligned: the seqLenQ rows are the LAST rows of the sequence; row i of batch b sees the keys
+ * k <= kvLens[b] - seqLenQ + i and -- the library's rule -- at least key 0.  is_causal = false: every row sees keys [0, kvLens[b]).
+ * (flash_attention_cross's mask is top-left aligned: see there which applies where.  The prefill kernels have no bottom-right mask.)
+ *
+ * Supported: dtype = FA_DTYPE_BF16; dHead 64 or 128; o_dtype F32, BF16 or F16; 1 <= seqLenQ <= FA_DECODE_MAX_Q (more new rows is chunked
+ * prefill: flash_attention_gqa); any numHeadsKV dividing numHeads; scale finite and > 0; one head's K / V extent (seqLenK x row stride)
+ * below 2^31 bytes, as on the prefill MFMA paths.  Everything else is rejected before any launch with the forward's codes: other
+ * inputs or outputs FA_ERR_UNSUPPORTED_DTYPE, other dHead FA_ERR_UNSUPPORTED_DHEAD, a non-finite or non-positive scale FA_ERR_BAD_SCALE,
+ * seqLenQ out of range, bad head counts, shapes and split counts FA_ERR_BAD_SHAPE, null pointers (a NULL workspace the plan needs
+ * included), misalignment (kvLens: 4 bytes) and bad strides FA_ERR_NULL_POINTER / _MISALIGNED / _BAD_STRIDE.
+ *
+ * Precision.  Scores and the softmax are fp32; the weights enter the P.V product as a bf16 hi + lo pair (two MFMAs against the bf16 V
+ * as it lies in memory: ~16 significant bits), accumulated in fp32.  The stated tolerance 1e-3 + 1e-3 |ref| holds on every element for
+ * short caches as for long ones, and any finite bf16 V is valid (nothing is converted to fp16: no "Range of V" caveat).
+ *
+ * Determinism.  Partial results are combined from slabs in a fixed order, without atomics: the same call gives the same bits from run
+ * to run.  With o_dtype BF16 / F16 the result is the F32 result of the same call rounded once, at the store.
+ *
+ * flash_attention_decode_plan -- what a flash_attention_decode() call with these arguments (and this numSplits) launches.
+ * flash_attention_decode_workspace_size -- bytes for `numSplits` splits AS PLANNED (pass plan.num_splits, not 0); 0 for one split.
+ */
+#define FA_DECODE_MAX_Q 16          /* more new rows than this: that is chunked prefill, use flash_attention_gqa */
+#define FA_DECODE_MAX_SPLITS 64     /* cap of numSplits */
+
+typedef struct fa_decode_plan {
+    int num_splits;      /* key-range splits per (batch, K/V head, row block) the call will use */
+    int row_blocks;      /* blocks of packed (query head of the group, query row) rows per K/V head; 1 = K/V read once per group */
+    int rows_per_block;  /* packed rows one workgroup holds */
+    int kv_block_rows;   /* keys per inner-loop tile */
+    int threads, grid, lds_bytes;          /* of the split kernel */
+    int combine_grid, combine_threads;     /* 0 when num_splits == 1: the split kernel writes O itself, one launch */
+} fa_decode_plan;
+
+int    flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                   int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
+size_t flash_attention_decode_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead, int numSplits /* as planned */);
+
+int flash_attention_decode(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                           const int32_t* kvLens, void* workspace,
+                           int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                           float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                           const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                           void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);

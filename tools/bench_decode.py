@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Time flash_attention_decode (split-KV decode): one JSON line per shape.
+
+  python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
+
+Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
+  single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
+  batch64_4k B64 H64 Hkv8 Sq1 Sk4096      mha_16k B4 H32 Hkv32 Sq1 Sk16384        spec4_32k B8 H32 Hkv8 Sq4 Sk32768
+  d64_16k B8 H32 Hkv8 Sq1 Sk16384 d64     ragged B16 H32 Hkv8 Sq1 capacity 32768, lengths spread 1 k ... 32 k
+Each line:
+  ms          one flash_attention_decode call (its launches and the Python binding; O and the workspace given), hipEvents around
+              --steps calls after --warmup calls; the median of --repeats such windows, ms_min / ms_max their spread.  The device
+              is primed first with >= 1 s of calls
+  kv_TBps     unique K/V bytes actually visible (sum over the batch of kv_lens x Hkv x d x 2 tensors x 2 bytes) / ms
+  kv_MB       those bytes: above the 256 MiB Infinity Cache the figure shows HBM, below it the cache
+  splits, grid  what the library planned (or --splits forced)
+  cross_ms    the same problem through flash_attention() (no mask, uniform length = capacity, grouped-query tensors): what a caller
+              had to issue before this path existed; speedup = cross_ms / ms
+--splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [  # name, B, H, Hkv, Sq, Sk, d, ragged
+    ("single_32k", 1, 32, 8, 1, 32768, 128, False),
+    ("single_128k", 1, 32, 8, 1, 131072, 128, False),
+    ("batch8_8k", 8, 32, 8, 1, 8192, 128, False),
+    ("batch64_4k", 64, 64, 8, 1, 4096, 128, False),
+    ("mha_16k", 4, 32, 32, 1, 16384, 128, False),
+    ("spec4_32k", 8, 32, 8, 4, 32768, 128, False),
+    ("d64_16k", 8, 32, 8, 1, 16384, 64, False),
+    ("ragged", 16, 32, 8, 1, 32768, 128, True),
+]
+# run only when named: a short cache under a single sequence (how short a split may usefully be)
+EXTRA = [("single_2k", 1, 32, 8, 1, 2048, 128, False), ("single_4k", 1, 32, 8, 1, 4096, 128, False)]
+
+
+def timed(fn, steps, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--shape", action="append", default=None)
+    ap.add_argument("--splits", default=None, help="comma-separated forced split counts: the sweep")
+    ap.add_argument("--no-cross", action="store_true")
+    args = ap.parse_args()
+    import torch
+    import __graft_entry__ as entry
+    fa = entry.load_package()
+    dev = torch.device("cuda:0")
+    shapes = SHAPES
+    if args.shape:
+        unknown = set(args.shape) - {x[0] for x in SHAPES + EXTRA}
+        if unknown:
+            ap.error(f"unknown shape(s): {sorted(unknown)}")
+        shapes = [x for x in SHAPES + EXTRA if x[0] in args.shape]
+    primed = False
+    for name, B, H, Hkv, Sq, Sk, d, ragged in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        Q = torch.randn(B, H, Sq, d, device=dev, generator=g).to(torch.bfloat16)
+        K, V = (torch.randn(B, Hkv, Sk, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        lens = [1024 + (Sk - 1024) * b // (B - 1) for b in range(B)] if ragged else [Sk] * B
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        O = torch.empty(B, H, Sq, d, device=dev, dtype=torch.bfloat16)
+        kv_bytes = sum(lens) * Hkv * d * 2 * 2
+
+        def measure(ns):
+            plan = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, ns)
+            n = fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"])
+            ws = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+            call = lambda: fa.flash_attention_decode(Q, K, V, lens_d, O=O, workspace=ws, num_splits=ns)
+            nonlocal primed
+            if not primed:   # >= 1 s of calls before the first timed window
+                t = 0.0
+                while t < 1000.0:
+                    t += timed(call, 500, 0) * 500
+                primed = True
+            ms = sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
+            return plan, ms
+
+        if args.splits:
+            for ns in [int(x) for x in args.splits.split(",")]:
+                if ns > -(-Sk // 128):
+                    continue
+                plan, ms = measure(ns)
+                print(json.dumps({"shape": name, "forced_splits": ns, "grid": plan["grid"], "ms": round(statistics.median(ms), 5),
+                                  "ms_min": round(ms[0], 5), "ms_max": round(ms[-1], 5),
+                                  "kv_TBps": round(kv_bytes / statistics.median(ms) / 1e9, 3)}), flush=True)
+            del Q, K, V, O
+            torch.cuda.empty_cache()
+            continue
+        plan, ms = measure(0)
+        med = statistics.median(ms)
+        line = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "Sq": Sq, "Sk": Sk, "d": d, "ragged": ragged, "io": "bfloat16",
+                "ms": round(med, 5), "ms_min": round(ms[0], 5), "ms_max": round(ms[-1], 5), "repeats": args.repeats, "steps": args.steps,
+                "kv_MB": round(kv_bytes / 1e6, 1), "kv_TBps": round(kv_bytes / med / 1e9, 3),
+                "splits": plan["num_splits"], "row_blocks": plan["row_blocks"], "grid": plan["grid"]}
+        if not args.no_cross:
+            cross = lambda: fa.flash_attention(Q, K, V, O)
+            steps = max(10, args.steps // 10)
+            cs = sorted(timed(cross, steps, 3) for _ in range(args.repeats))
+            line.update(cross_ms=round(statistics.median(cs), 5), cross_ms_min=round(cs[0], 5), cross_ms_max=round(cs[-1], 5),
+                        cross_grid=fa.plan_ex(B, H, Sq, Sk, d, False, fa.FA_DTYPE_BF16, fa.FA_DTYPE_BF16, 0)[1]["grid"],
+                        speedup=round(statistics.median(cs) / med, 2))
+        print(json.dumps(line), flush=True)
+        del Q, K, V, O
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
