@@ -463,6 +463,15 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     return (O, lse) if return_lse else O
 
 
+def _library_accepts(t):
+    """What the C ABI asks of a [B, H, S, d] view (csrc/FlashAttention.hip: strides_ok, aligned16): last dimension contiguous, rows
+    that do not overlap, every stride a multiple of 16 bytes, a 16-byte aligned base."""
+    esz = t.element_size()
+    sB, sH, sS, sD = t.stride()
+    return (sD == 1 and sS >= t.shape[3] and sB >= 0 and sH >= 0 and all((s * esz) % 16 == 0 for s in (sB, sH, sS))
+            and t.data_ptr() % 16 == 0)
+
+
 def _attention_function():
     import torch
 
@@ -478,7 +487,9 @@ def _attention_function():
         def backward(ctx, dO):
             Q, K, V, O, lse = ctx.saved_tensors
             dO = dO.to(O.dtype)
-            if dO.stride(-1) != 1:
+            # autograd hands back whatever view the loss produced (expanded: strideS = 0; narrowed: any row stride): copy exactly when
+            # the library would refuse it, pass every other view (a model-layout dO) through
+            if not _library_accepts(dO):
                 dO = dO.contiguous()
             dQ, dK, dV = flash_attention_backward(Q, K, V, O, dO, lse, scale=ctx.scale, is_causal=ctx.is_causal)
             return dQ.to(Q.dtype), dK.to(K.dtype), dV.to(V.dtype), None, None, None
