@@ -13,6 +13,8 @@ entry points for that path:
   ``h // (H // Hkv)`` (``repeat_interleave(H // Hkv, dim=1)`` without the copy), and dK, dV come back shaped like K, V.
 * ``flash_attention_decode(Q, K, V, kv_lens)`` -- split-KV decode: 1 .. 16 new query rows per sequence against a long bf16 K/V
   cache, per-sequence lengths in a device tensor, bottom-right-aligned causal mask (``decode_plan``, ``decode_workspace_size``).
+* ``flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens)`` -- the same against paged caches: pools of fixed-size
+  pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -43,6 +45,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_plan", "flash_attention_plan_ex", "flash_attention_backward", "flash_attention_backward_workspace_size",
            "flash_attention_gqa", "flash_attention_backward_gqa",
            "flash_attention_decode", "flash_attention_decode_plan", "flash_attention_decode_workspace_size",
+           "flash_attention_decode_paged",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -116,6 +119,8 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_backward_workspace_size.restype = ctypes.c_size_t
         L.flash_attention_decode.argtypes = [vp] * 7 + [i, i, i, i, i, i, f, b, i, i, i] + [sp] * 4 + [vp]
         L.flash_attention_decode.restype = i
+        L.flash_attention_decode_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode_paged.restype = i
         L.flash_attention_decode_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_decode_plan.restype = i
         L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
@@ -459,6 +464,67 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
                                           kv_lens.data_ptr() if kv_lens is not None else None,
                                           workspace.data_ptr() if need else None, B, H, Hkv, Sq, Sk, d, float(scale), bool(is_causal),
                                           _dtype_code(Q.dtype), _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
+
+
+def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None):
+    """``flash_attention_decode`` against PAGED K/V caches: Q ``[B, H, Sq, d]``, pools ``[P, Hkv, page, d]`` (bf16, d = 64 or 128,
+    page a power of two >= 16; strided views accepted, so a ``[P, page, Hkv, d]`` pool is ``pool.transpose(1, 2)``) and
+    ``block_table``: int32 device tensor ``[B, max_pages]`` with a contiguous last dimension (a row slice of a wider table is
+    fine).  Key k of sequence b is row ``k % page`` of page ``block_table[b, k // page]``; sequences may share pages.
+
+    The capacity ``max_pages * page`` plays the part of ``flash_attention_decode``'s cache capacity: ``kv_lens`` (int32 device
+    tensor ``[B]``, or None = the capacity) is clamped into [1, capacity], and ``decode_plan`` / ``decode_workspace_size`` called
+    with ``Sk = max_pages * page`` describe this call.  Table entries and lengths are read by the kernel (the call never
+    synchronises; a captured graph sees the table of the moment): only the entries of pages that hold a key below the length,
+    each clamped into [0, P).  Rows beyond the length and pages not named may hold anything.  Mask, ``num_splits``, ``workspace``,
+    ``O``, ``return_lse`` and ``stream`` as for ``flash_attention_decode``; the result is that call's on a contiguous copy of the
+    same pages, bit for bit.  No CPU fallback."""
+    import torch
+    if not (Q.is_cuda and K_pool.is_cuda and V_pool.is_cuda and block_table.is_cuda):
+        raise RuntimeError("flash_attention_decode_paged needs device tensors (no CPU fallback)")
+    if Q.dim() != 4 or K_pool.dim() != 4 or K_pool.shape != V_pool.shape or Q.shape[3] != K_pool.shape[3] \
+            or K_pool.shape[1] < 1 or Q.shape[1] % K_pool.shape[1] != 0:
+        raise ValueError("Q must be [B, H, Sq, d] and K_pool, V_pool [P, Hkv, page, d] with Hkv dividing H")
+    if not (Q.dtype == K_pool.dtype == V_pool.dtype):
+        raise TypeError("Q, K_pool, V_pool must share a dtype")
+    B, H, Sq, d = Q.shape
+    P, Hkv, page = K_pool.shape[:3]
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
+            or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    max_pages = block_table.shape[1]
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    if scale is None:
+        scale = 1.0 / float(d) ** 0.5
+    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
+    ns = decode_plan(B, H, Hkv, Sq, max_pages * page, d, odt, num_splits)["num_splits"]
+    need = decode_workspace_size(B, H, Sq, d, ns)
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif O.shape != Q.shape or not O.is_cuda:
+                raise ValueError("O must be a device tensor shaped like Q")
+            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            if workspace is None and need:
+                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
+            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
+        st = [_strides(t) for t in (Q, K_pool, V_pool, O)]
+        rc = lib().flash_attention_decode_paged(Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(), O.data_ptr(),
+                                                lse.data_ptr() if lse is not None else None,
+                                                kv_lens.data_ptr() if kv_lens is not None else None, block_table.data_ptr(),
+                                                workspace.data_ptr() if need else None, B, H, Hkv, Sq, P, page, max_pages,
+                                                table_stride, d, float(scale), bool(is_causal), _dtype_code(Q.dtype),
+                                                _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
     return (O, lse) if return_lse else O
 

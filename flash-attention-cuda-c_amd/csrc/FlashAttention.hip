@@ -322,6 +322,69 @@ static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int 
 }
 
 static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// flash_attention_decode and flash_attention_decode_paged: one validation and launch sequence.  Contiguous: K / V are
+// [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
+// Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.
+struct DecodePaging {
+    const int32_t* table;
+    int64_t table_stride;
+    int num_pages, page_size, max_pages;
+};
+
+static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, void* workspace,
+                      int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                      const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg,
+                      void* stream) {
+    if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
+    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
+    if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
+    if (pg) {
+        if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
+        if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
+        Sk = pg->max_pages * pg->page_size;
+    }
+    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits);
+    if (rc != FA_OK) return rc;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
+    const int osz = elem_size(o_dtype);
+    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, 2, d) || !strides_ok(sV, 2, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
+    // K / V go through buffer descriptors with 32-bit byte offsets: the prefill paths' limit on one head's extent -- of the whole
+    // cache, or of one page (page bases are 64-bit: the pool as a whole may be larger)
+    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
+    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + 192;
+    if (extent * ks * 2 >= (1ll << 31) || extent * vs * 2 >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
+    if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
+    const int64_t rows = (int64_t)B * H * Sq;
+    if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    const int rowsK = pg ? pg->page_size : Sk;   // rows of one head of one batch entry / page
+    DecodeParams p;
+    p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
+    p.part_o = (float*)workspace;
+    p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
+    p.qB = sQ ? sQ->strideB : (int64_t)H * Sq * d;      p.qH = sQ ? sQ->strideH : (int64_t)Sq * d;     p.qS = sQ ? sQ->strideS : d;
+    p.kB = sK ? sK->strideB : (int64_t)Hkv * rowsK * d; p.kH = sK ? sK->strideH : (int64_t)rowsK * d;  p.kS = ks;
+    p.vB = sV ? sV->strideB : (int64_t)Hkv * rowsK * d; p.vH = sV ? sV->strideH : (int64_t)rowsK * d;  p.vS = vs;
+    p.oB = sO ? sO->strideB : (int64_t)H * Sq * d;      p.oH = sO ? sO->strideH : (int64_t)Sq * d;     p.oS = sO ? sO->strideS : d;
+    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = Sk;
+    p.row_blocks = r.row_blocks; p.ns = r.ns;
+    p.rows = (int)rows;
+    p.o_dtype = o_dtype;
+    p.causal = is_causal;
+    p.scale_log2 = scale * 1.4426950408889634f;
+    p.block_table = pg ? pg->table : nullptr;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Kernel sk = pg ? decode_paged_split_kernel_of(d) : decode_split_kernel_of(d);
+    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
+    if (e != hipSuccess || r.ns == 1) return (int)e;
+    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
+}
 }  // namespace fa
 
 extern "C" {
@@ -574,43 +637,18 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
-    using namespace fa;
-    if (!Q || !K || !V || !O) return FA_ERR_NULL_POINTER;
-    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
-    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
-    const int B = batchSize, H = numHeads, Hkv = numHeadsKV, Sq = seqLenQ, Sk = seqLenK, d = dHead;
-    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits);
-    if (rc != FA_OK) return rc;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
-    const int osz = elem_size(o_dtype);
-    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, 2, d) || !strides_ok(sV, 2, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
-    // K / V go through buffer descriptors with 32-bit byte offsets: the prefill paths' limit on one head's extent
-    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
-    if (((int64_t)Sk + 192) * ks * 2 >= (1ll << 31) || ((int64_t)Sk + 192) * vs * 2 >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
-    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
-    if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
-    const int64_t rows = (int64_t)B * H * Sq;
-    if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    return fa::decode_run(Q, K, V, O, LSE, kvLens, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, scale, is_causal,
+                          dtype, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
+}
 
-    DecodeParams p;
-    p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
-    p.part_o = (float*)workspace;
-    p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
-    p.qB = sQ ? sQ->strideB : (int64_t)H * Sq * d;   p.qH = sQ ? sQ->strideH : (int64_t)Sq * d;  p.qS = sQ ? sQ->strideS : d;
-    p.kB = sK ? sK->strideB : (int64_t)Hkv * Sk * d; p.kH = sK ? sK->strideH : (int64_t)Sk * d;  p.kS = ks;
-    p.vB = sV ? sV->strideB : (int64_t)Hkv * Sk * d; p.vH = sV ? sV->strideH : (int64_t)Sk * d;  p.vS = vs;
-    p.oB = sO ? sO->strideB : (int64_t)H * Sq * d;   p.oH = sO ? sO->strideH : (int64_t)Sq * d;  p.oS = sO ? sO->strideS : d;
-    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = Sk;
-    p.row_blocks = r.row_blocks; p.ns = r.ns;
-    p.rows = (int)rows;
-    p.o_dtype = o_dtype;
-    p.causal = is_causal;
-    p.scale_log2 = scale * 1.4426950408889634f;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const Kernel sk = decode_split_kernel_of(d);
-    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
-    if (e != hipSuccess || r.ns == 1) return (int)e;
-    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
+int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                 const int32_t* blockTable, void* workspace, int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                 int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, float scale,
+                                 bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                                 const fa_strides* sV, const fa_strides* sO, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead, scale, is_causal,
+                          dtype, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
 }
 
 const char* flash_attention_error_string(int code) {

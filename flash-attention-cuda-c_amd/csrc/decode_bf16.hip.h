@@ -23,7 +23,15 @@
 //   * ns = 1: the split kernel normalises and writes O (and the LSE) itself.  ns > 1: it writes normalised fp32 partial outputs
 //     and partial log-sum-exps into slabs, and decode_combine_kernel -- a second launch on the same stream -- sums them in a fixed
 //     order: no atomics, the same bits run to run.  An empty split (a short sequence under many splits) writes O = 0, LSE = -inf
-//     and gets weight 0.
+//     and gets weight 0;
+//   * PAGED (flash_attention_decode_paged): K and V are pools of fixed-size pages [page][K/V head][row][d] and
+//     key k of sequence b is row k % page_size of page block_table[b][k / page_size].  Same loop body; the one difference is where a
+//     16-key group comes from.  A page holds a whole number of 16-key groups, so each of a wave's two groups per tile lies in one
+//     page: the wave builds one descriptor per group and tensor, based AT the group's first row (64-bit: the pool may exceed 4 GiB)
+//     and holding the group's rows below the length (none: zero bytes, everything reads as 0), and the per-lane offsets stay within
+//     16 rows.  The two table entries a wave needs per tile are fetched by one vector load (lane parity = group) two tiles ahead --
+//     in program order BEFORE the K/V loads of the tile in between, whose wait covers it -- so the table is never in the latency
+//     chain of the K/V prefetch; the index is clamped to the last page that holds a visible key and the entry into [0, num_pages).
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -47,6 +55,10 @@ struct DecodeParams {
     int o_dtype;
     int causal;
     float scale_log2;        // scale * log2(e)
+    // paged form only: K / V are the pools, kB / vB the page strides, Sk the capacity max_pages * page size
+    const int32_t* block_table;   // [B][table_stride] page numbers (device memory)
+    int64_t table_stride;
+    int num_pages, page_shift;    // page size = 1 << page_shift, >= 16
 };
 
 template <int D>
@@ -74,7 +86,7 @@ __device__ __forceinline__ void store_out(void* O, int o_dtype, int64_t idx, flo
     else ((_Float16*)O)[idx] = (_Float16)v;
 }
 
-template <int D>
+template <int D, bool PAGED>
 __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams p) {
     using C = DecodeCfg<D>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -114,7 +126,8 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
         }
     }
 
-    // descriptors over the VISIBLE part of this (batch, K/V head): rows >= len read as 0
+    // descriptors over the VISIBLE part of this (batch, K/V head): rows >= len read as 0 (contiguous form; the paged form builds
+    // its descriptors per tile, below)
     const char* Kh = (const char*)(p.K + b * p.kB + kvh * p.kH);
     const char* Vh = (const char*)(p.V + b * p.vB + kvh * p.vH);
     const int ksb = (int)(p.kS * 2), vsb = (int)(p.vS * 2);
@@ -130,17 +143,66 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     // transposed read (dg, jj): lane 4q + pp of quarter h4 supplies row 16 jj + 4 h4 + q, columns 16 dg + 4 pp .. + 3
     const int vrd = (4 * h4 + ((lane & 15) >> 2)) * C::VROW + (lane & 3) * 8;
 
+    // paged form: the wave index as the scalar it is (everything the descriptors are built from is then provably wave-uniform), this
+    // sequence's row of the table, the last page that holds a visible key, the lane's offsets within a 16-key group, and the table
+    // entries of the wave's two 16-key groups: e0, e1 for the tile whose loads are issued next, ev (lane parity = group) in flight
+    // for the tile after it
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int32_t* tb = p.block_table + b * p.table_stride;
+    const int last_page = (len - 1) >> p.page_shift;
+    const int gkoff = r * ksb + h4 * 16, gvoff = vkey * vsb + vch * 16;
+    int ev = 0, e0 = 0, e1 = 0;
+    // the table entries of tile t: only pages that hold a key < len are looked up (a tile past the end repeats the last one)
+    auto table_entries = [&](int t) {
+        const int key = t * C::TILE + wv * C::WKEYS + 16 * (lane & 1);
+        return tb[min(key >> p.page_shift, last_page)];
+    };
+    // take the entries that have arrived into scalars for the next load_tile, THEN fetch tile t's into the register they leave
+    auto next_entries = [&](int t) {
+        e0 = __builtin_amdgcn_readlane(ev, 0);
+        e1 = __builtin_amdgcn_readlane(ev, 1);
+        ev = table_entries(t);
+    };
+    // one 16-key group of one pool: a descriptor at its first row, holding its rows below len
+    auto group_rsrc = [&](const __bf16* pool, int64_t page_stride, int64_t head_stride, int64_t row_stride, int entry, int key) {
+        const int page = min(max(entry, 0), p.num_pages - 1);
+        const __bf16* base = pool + page * page_stride + kvh * head_stride + (key & ((1 << p.page_shift) - 1)) * row_stride;
+        const int rows = min(len - key, 16);
+        const int bytes = rows > 0 ? (rows - 1) * (int)(row_stride * 2) + D * 2 : 0;
+        const uint64_t a = (uint64_t)base;
+        const uint64_t au = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)au, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+    };
     u32x4 kn[2][C::KS], vn[C::NV];
     auto load_tile = [&](int t) {
-        const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
+        if constexpr (!PAGED) {
+            const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
 #pragma unroll
-        for (int kg = 0; kg < 2; ++kg)
+            for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks)
-                kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + kt + kg * 16 * ksb + ks * 64, 0, 0));
+                for (int ks = 0; ks < C::KS; ++ks)
+                    kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + kt + kg * 16 * ksb + ks * 64, 0, 0));
 #pragma unroll
-        for (int n = 0; n < C::NV; ++n)
-            vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + vt + n * C::KPI * vsb, 0, 0));
+            for (int n = 0; n < C::NV; ++n)
+                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + vt + n * C::KPI * vsb, 0, 0));
+        } else {
+            __amdgpu_buffer_rsrc_t kr[2], vr[2];
+#pragma unroll
+            for (int kg = 0; kg < 2; ++kg) {
+                const int entry = kg ? e1 : e0, key = t * C::TILE + wv * C::WKEYS + 16 * kg;
+                kr[kg] = group_rsrc(p.K, p.kB, p.kH, p.kS, entry, key);
+                vr[kg] = group_rsrc(p.V, p.vB, p.vH, p.vS, entry, key);
+            }
+#pragma unroll
+            for (int kg = 0; kg < 2; ++kg)
+#pragma unroll
+                for (int ks = 0; ks < C::KS; ++ks)
+                    kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(kr[kg], gkoff + ks * 64, 0, 0));
+#pragma unroll
+            for (int n = 0; n < C::NV; ++n)   // (V load n covers the keys KPI n .. KPI n + KPI - 1 of the wave's 32: one group)
+                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vr[n * C::KPI / 16], gvoff + (n * C::KPI % 16) * vsb, 0, 0));
+        }
     };
 
     const float NEG_INF = -__builtin_inff();
@@ -149,7 +211,13 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
     for (int dg = 0; dg < C::DG; ++dg) o[dg] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if (t0 < t1) load_tile(t0);
+    if (t0 < t1) {
+        if constexpr (PAGED) {
+            ev = table_entries(t0);
+            next_entries(t0 + 1);
+        }
+        load_tile(t0);
+    }
     for (int t = t0; t < t1; ++t) {
         // V of this tile: registers -> the wave's LDS image (the previous tile's reads are done: same wave, program order)
 #pragma unroll
@@ -161,7 +229,10 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
             for (int ks = 0; ks < C::KS; ++ks) s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, kn[kg][ks]), qf[ks], s[kg]);
         }
-        if (t + 1 < t1) load_tile(t + 1);   // (wave-uniform) next tile's K and V: in flight under the softmax and the P.V product
+        if (t + 1 < t1) {   // (wave-uniform) next tile's K and V: in flight under the softmax and the P.V product
+            if constexpr (PAGED) next_entries(t + 2);   // tile t + 1's entries arrived with the K/V of tile t: issued before them
+            load_tile(t + 1);
+        }
 
         // s[kg][reg]: key kb + 16 kg + 4 h4 + reg, packed row r
         const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4;
@@ -297,9 +368,10 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams 
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (inst_decode_bf16.hip) ----
+// ---- selectors (inst_decode_bf16.hip, inst_decode_paged_bf16.hip) ----
 struct Kernel;
 Kernel decode_split_kernel_of(int d);
+Kernel decode_paged_split_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 
 }  // namespace fa

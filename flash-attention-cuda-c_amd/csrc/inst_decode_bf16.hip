@@ -6,7 +6,7 @@
 namespace fa {
 
 Kernel decode_split_kernel_of(int d) {
-    return d == 128 ? kernel_of<decode_split_kernel<128>>(DecodeCfg<128>::LDS_BYTES) : kernel_of<decode_split_kernel<64>>(DecodeCfg<64>::LDS_BYTES);
+    return d == 128 ? kernel_of<decode_split_kernel<128, false>>(DecodeCfg<128>::LDS_BYTES) : kernel_of<decode_split_kernel<64, false>>(DecodeCfg<64>::LDS_BYTES);
 }
 
 Kernel decode_combine_kernel_of(int d) {

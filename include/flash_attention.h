@@ -427,6 +427,40 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                            void* stream);
 
+/*
+ * flash_attention_decode_paged -- flash_attention_decode against PAGED K/V caches: K and V live in pools of fixed-size pages and every
+ * sequence names its pages in a block table, as serving engines store them (no gather into a contiguous copy before the call).
+ *   Kpool, Vpool [numPages, numHeadsKV, pageSize, dHead] bf16.  In sK / sV strideB is the PAGE stride (strideH the head stride, strideS
+ *            the row stride); NULL = dense.  A [numPages, pageSize, numHeadsKV, dHead] pool is therefore a view
+ *   blockTable DEVICE pointer to int32, 4-byte aligned: key k of sequence b is row k % pageSize of page
+ *            blockTable[b * tableStride + k / pageSize].  tableStride is in elements, >= maxPagesPerSeq (a row slice of a wider table
+ *            is fine).  Entries are read BY THE KERNEL, like kvLens -- the host never synchronises, a replayed graph sees the table of
+ *            the moment -- and only the entries of pages that hold at least one key < kvLens[b]; each entry read is clamped on the
+ *            device into [0, numPages - 1]: a stale entry can give a wrong answer, never an unmapped address.  Several sequences may
+ *            name the same page (a shared prefix); the call only reads the pools
+ *   capacity maxPagesPerSeq * pageSize plays the part of flash_attention_decode's seqLenK: kvLens[b] is clamped on the device into
+ *            [1, capacity], NULL = the capacity, and the split count is chosen on the host from the capacity.
+ *            flash_attention_decode_plan(..., seqLenK = maxPagesPerSeq * pageSize, ...) and flash_attention_decode_workspace_size
+ *            describe a paged call as well (there is no second plan function)
+ *   Rows at and beyond kvLens[b] in the last page, and every page not read, may hold NaN, inf or stale data: they never enter the result.
+ *   pageSize a power of two >= 16 (16 keys are one K fragment load: no load straddles pages); one page's head extent (pageSize x row
+ *            stride) below 2^31 bytes.  The pool as a whole may exceed 2^32 bytes: page bases are 64-bit.
+ * Q, O, LSE, workspace, numSplits, the bottom-right mask, the precision (hi + lo bf16 weights), the supported types, dHead 64 / 128,
+ * seqLenQ <= FA_DECODE_MAX_Q, determinism and the conventions (validated before any launch; never allocates, synchronises or prints)
+ * are flash_attention_decode's.  Tiles and splits are divided as there, so the result equals, bit for bit, flash_attention_decode on a
+ * contiguous copy of the same pages with seqLenK = the capacity and the same numSplits.
+ * Rejected before any launch: everything flash_attention_decode rejects, with the same codes; numPages <= 0, maxPagesPerSeq <= 0,
+ * pageSize < 16 or not a power of two, a capacity above 2^24, tableStride < maxPagesPerSeq, a page extent >= 2^31 bytes
+ * FA_ERR_BAD_SHAPE; a NULL blockTable FA_ERR_NULL_POINTER; a blockTable not aligned to 4 bytes FA_ERR_MISALIGNED.
+ */
+int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                 const int32_t* kvLens, const int32_t* blockTable, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                 int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                 float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                                 const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                 void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 

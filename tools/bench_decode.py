@@ -2,6 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
+                                [--paged 16,128,256]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -16,6 +17,9 @@ Each line:
   splits, grid  what the library planned (or --splits forced)
   cross_ms    the same problem through flash_attention() (no mask, uniform length = capacity, grouped-query tensors): what a caller
               had to issue before this path existed; speedup = cross_ms / ms
+--paged a,b,c   page sizes: per shape, the same K/V data scattered into pools of such pages behind a SHUFFLED block table, through
+              flash_attention_decode_paged (same lengths, O, workspace and plan as `ms`): paged_ms[page] with its min / max and
+              paged_ratio[page] = paged_ms / ms (profiles/decode_paged_bench.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
 """
 import argparse
@@ -63,6 +67,7 @@ def main():
     ap.add_argument("--shape", action="append", default=None)
     ap.add_argument("--splits", default=None, help="comma-separated forced split counts: the sweep")
     ap.add_argument("--no-cross", action="store_true")
+    ap.add_argument("--paged", default=None, help="comma-separated page sizes: add paged_ms per page size to every shape's line")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
@@ -98,6 +103,22 @@ def main():
             ms = sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
             return plan, ms
 
+        def measure_paged(page):
+            # the same data in pages: page j of sequence b is rows [j page, (j + 1) page) of every K/V head, stored wherever a
+            # shuffle of all B * n page numbers puts it
+            n = Sk // page
+            perm = torch.randperm(B * n, device=dev, generator=g)
+            table = perm.reshape(B, n).to(torch.int32)
+            pools = []
+            for T in (K, V):
+                pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=torch.bfloat16)
+                pool[perm] = T.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
+                pools.append(pool)
+            ns = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0)["num_splits"]
+            ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, ns), 16), dtype=torch.uint8, device=dev)
+            call = lambda: fa.flash_attention_decode_paged(Q, pools[0], pools[1], table, lens_d, O=O, workspace=ws)
+            return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
+
         if args.splits:
             for ns in [int(x) for x in args.splits.split(",")]:
                 if ns > -(-Sk // 128):
@@ -122,6 +143,12 @@ def main():
             line.update(cross_ms=round(statistics.median(cs), 5), cross_ms_min=round(cs[0], 5), cross_ms_max=round(cs[-1], 5),
                         cross_grid=fa.plan_ex(B, H, Sq, Sk, d, False, fa.FA_DTYPE_BF16, fa.FA_DTYPE_BF16, 0)[1]["grid"],
                         speedup=round(statistics.median(cs) / med, 2))
+        if args.paged:
+            pm = {page: measure_paged(page) for page in (int(x) for x in args.paged.split(",")) if Sk % page == 0}
+            line.update(paged_ms={str(k): round(statistics.median(v), 5) for k, v in pm.items()},
+                        paged_ms_min={str(k): round(v[0], 5) for k, v in pm.items()},
+                        paged_ms_max={str(k): round(v[-1], 5) for k, v in pm.items()},
+                        paged_ratio={str(k): round(statistics.median(v) / med, 4) for k, v in pm.items()})
         print(json.dumps(line), flush=True)
         del Q, K, V, O
         torch.cuda.empty_cache()
