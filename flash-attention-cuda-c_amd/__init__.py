@@ -14,7 +14,8 @@ entry points for that path:
 * ``flash_attention_decode(Q, K, V, kv_lens)`` -- split-KV decode: 1 .. 16 new query rows per sequence against a long bf16 K/V
   cache, per-sequence lengths in a device tensor, bottom-right-aligned causal mask (``decode_plan``, ``decode_workspace_size``).
 * ``flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens)`` -- the same against paged caches: pools of fixed-size
-  pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.
+  pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.  Both also take fp8
+  (``torch.float8_e4m3fn``) K/V caches under a bf16 Q, with per-K/V-head ``k_descale`` / ``v_descale``: half the bytes per token.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -45,7 +46,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_plan", "flash_attention_plan_ex", "flash_attention_backward", "flash_attention_backward_workspace_size",
            "flash_attention_gqa", "flash_attention_backward_gqa",
            "flash_attention_decode", "flash_attention_decode_plan", "flash_attention_decode_workspace_size",
-           "flash_attention_decode_paged",
+           "flash_attention_decode_paged", "flash_attention_decode_fp8", "flash_attention_decode_paged_fp8",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -121,6 +122,10 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_decode.restype = i
         L.flash_attention_decode_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i] + [sp] * 4 + [vp]
         L.flash_attention_decode_paged.restype = i
+        L.flash_attention_decode_fp8.argtypes = [vp] * 9 + [i, i, i, i, i, i, f, b, i, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode_fp8.restype = i
+        L.flash_attention_decode_paged_fp8.argtypes = [vp] * 10 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode_paged_fp8.restype = i
         L.flash_attention_decode_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_decode_plan.restype = i
         L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
@@ -414,8 +419,26 @@ def decode_workspace_size(B, H, Sq, d, num_splits):
     return int(lib().flash_attention_decode_workspace_size(B, H, Sq, d, num_splits))
 
 
+def _decode_kv_fp8(Q, K, V, k_descale, v_descale, what):
+    """True when the call is the fp8-cache form (bf16 Q, e4m3fn K and V); checks the dtypes and the descales either way."""
+    import torch
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    fp8 = f8 is not None and Q.dtype == torch.bfloat16 and K.dtype == f8 and V.dtype == f8
+    if not fp8 and not (Q.dtype == K.dtype == V.dtype):
+        raise TypeError(f"{what} must share a dtype")
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is None:
+            continue
+        if not fp8:
+            raise ValueError(f"{name} belongs to an fp8 (float8_e4m3fn) K/V cache under a bf16 Q")
+        if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != Q.device or tuple(t.shape) != (K.shape[1],) \
+                or not t.is_contiguous():
+            raise ValueError(f"{name} must be a dense fp32 tensor [Hkv] on the device of Q")
+    return fp8
+
+
 def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-                           O=None, workspace=None, stream=None):
+                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
     """Split-KV decode: Q ``[B, H, Sq, d]`` with 1 <= Sq <= FA_DECODE_MAX_Q new rows per sequence against a K/V cache
     ``[B, Hkv, capacity, d]`` (bf16, d = 64 or 128, Hkv dividing H; query head h reads K/V head ``h // (H // Hkv)``).
 
@@ -426,15 +449,18 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     ``num_splits``: 0 = the library's choice (``decode_plan``), > 0 forced.  ``workspace`` (uint8 device tensor of
     ``decode_workspace_size`` bytes), when not given, is allocated with torch on the call's stream, like an ``O`` allocated here.
     Strided views are accepted (last dimension contiguous).  Returns O, or ``(O, LSE)`` with ``return_lse=True`` (fp32 [B, H, Sq],
-    natural log).  Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
+    natural log).  Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback.
+
+    fp8 cache: K and V of ``torch.float8_e4m3fn`` under a bf16 Q, with ``k_descale`` / ``v_descale``: fp32 device tensors ``[Hkv]``
+    (None = 1), read by the kernel like ``kv_lens``.  The logical cache is ``K.float() * k_descale[kvh]``, ``V.float() *
+    v_descale[kvh]``; the conversion is exact and everything else is as for bf16 (``decode_plan`` does not depend on the cache type)."""
     import torch
     if not (Q.is_cuda and K.is_cuda and V.is_cuda):
         raise RuntimeError("flash_attention_decode needs device tensors (no CPU fallback)")
     if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] or Q.shape[3] != K.shape[3] \
             or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
         raise ValueError("Q must be [B, H, Sq, d] and K, V [B, Hkv, capacity, d] with Hkv dividing H")
-    if not (Q.dtype == K.dtype == V.dtype):
-        raise TypeError("Q, K, V must share a dtype")
+    fp8 = _decode_kv_fp8(Q, K, V, k_descale, v_descale, "Q, K, V")
     B, H, Sq, d = Q.shape
     Hkv, Sk = K.shape[1:3]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -459,17 +485,23 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
         if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
             raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
         st = [_strides(t) for t in (Q, K, V, O)]
-        rc = lib().flash_attention_decode(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(),
-                                          lse.data_ptr() if lse is not None else None,
-                                          kv_lens.data_ptr() if kv_lens is not None else None,
-                                          workspace.data_ptr() if need else None, B, H, Hkv, Sq, Sk, d, float(scale), bool(is_causal),
-                                          _dtype_code(Q.dtype), _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        head = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), lse.data_ptr() if lse is not None else None,
+                kv_lens.data_ptr() if kv_lens is not None else None)
+        ws = workspace.data_ptr() if need else None
+        tail = (_dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        if fp8:
+            rc = lib().flash_attention_decode_fp8(*head, k_descale.data_ptr() if k_descale is not None else None,
+                                                  v_descale.data_ptr() if v_descale is not None else None, ws, B, H, Hkv, Sq, Sk, d,
+                                                  float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(K.dtype), *tail)
+        else:
+            rc = lib().flash_attention_decode(*head, ws, B, H, Hkv, Sq, Sk, d, float(scale), bool(is_causal), _dtype_code(Q.dtype), *tail)
     _check(rc)
     return (O, lse) if return_lse else O
 
 
 def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
-                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None):
+                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
+                                 v_descale=None):
     """``flash_attention_decode`` against PAGED K/V caches: Q ``[B, H, Sq, d]``, pools ``[P, Hkv, page, d]`` (bf16, d = 64 or 128,
     page a power of two >= 16; strided views accepted, so a ``[P, page, Hkv, d]`` pool is ``pool.transpose(1, 2)``) and
     ``block_table``: int32 device tensor ``[B, max_pages]`` with a contiguous last dimension (a row slice of a wider table is
@@ -481,15 +513,15 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     synchronises; a captured graph sees the table of the moment): only the entries of pages that hold a key below the length,
     each clamped into [0, P).  Rows beyond the length and pages not named may hold anything.  Mask, ``num_splits``, ``workspace``,
     ``O``, ``return_lse`` and ``stream`` as for ``flash_attention_decode``; the result is that call's on a contiguous copy of the
-    same pages, bit for bit.  No CPU fallback."""
+    same pages, bit for bit.  fp8 pools (``torch.float8_e4m3fn`` under a bf16 Q) with ``k_descale`` / ``v_descale`` as for
+    ``flash_attention_decode``.  No CPU fallback."""
     import torch
     if not (Q.is_cuda and K_pool.is_cuda and V_pool.is_cuda and block_table.is_cuda):
         raise RuntimeError("flash_attention_decode_paged needs device tensors (no CPU fallback)")
     if Q.dim() != 4 or K_pool.dim() != 4 or K_pool.shape != V_pool.shape or Q.shape[3] != K_pool.shape[3] \
             or K_pool.shape[1] < 1 or Q.shape[1] % K_pool.shape[1] != 0:
         raise ValueError("Q must be [B, H, Sq, d] and K_pool, V_pool [P, Hkv, page, d] with Hkv dividing H")
-    if not (Q.dtype == K_pool.dtype == V_pool.dtype):
-        raise TypeError("Q, K_pool, V_pool must share a dtype")
+    fp8 = _decode_kv_fp8(Q, K_pool, V_pool, k_descale, v_descale, "Q, K_pool, V_pool")
     B, H, Sq, d = Q.shape
     P, Hkv, page = K_pool.shape[:3]
     if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
@@ -519,12 +551,17 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
         if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
             raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
         st = [_strides(t) for t in (Q, K_pool, V_pool, O)]
-        rc = lib().flash_attention_decode_paged(Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(), O.data_ptr(),
-                                                lse.data_ptr() if lse is not None else None,
-                                                kv_lens.data_ptr() if kv_lens is not None else None, block_table.data_ptr(),
-                                                workspace.data_ptr() if need else None, B, H, Hkv, Sq, P, page, max_pages,
-                                                table_stride, d, float(scale), bool(is_causal), _dtype_code(Q.dtype),
-                                                _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        head = (Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(), O.data_ptr(), lse.data_ptr() if lse is not None else None,
+                kv_lens.data_ptr() if kv_lens is not None else None, block_table.data_ptr())
+        ws = workspace.data_ptr() if need else None
+        shape = (B, H, Hkv, Sq, P, page, max_pages, table_stride, d, float(scale), bool(is_causal), _dtype_code(Q.dtype))
+        tail = (_dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+        if fp8:
+            rc = lib().flash_attention_decode_paged_fp8(*head, k_descale.data_ptr() if k_descale is not None else None,
+                                                        v_descale.data_ptr() if v_descale is not None else None, ws, *shape,
+                                                        _dtype_code(K_pool.dtype), *tail)
+        else:
+            rc = lib().flash_attention_decode_paged(*head, ws, *shape, *tail)
     _check(rc)
     return (O, lse) if return_lse else O
 

@@ -325,21 +325,23 @@ static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // flash_attention_decode and flash_attention_decode_paged: one validation and launch sequence.  Contiguous: K / V are
 // [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
-// Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.
+// Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.  kv_dtype is the element type of
+// K / V: FA_DTYPE_BF16 (the type of Q), or FA_DTYPE_FP8_E4M3 with the two optional per-head descale arrays (the _fp8 entry points).
 struct DecodePaging {
     const int32_t* table;
     int64_t table_stride;
     int num_pages, page_size, max_pages;
 };
 
-static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, void* workspace,
-                      int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
-                      const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg,
-                      void* stream) {
+static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, const float* kDescale,
+                      const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal,
+                      int dtype, int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                      const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
     if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
     if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
     if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
+    if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
     if (pg) {
         if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
@@ -347,14 +349,15 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     }
     int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits);
     if (rc != FA_OK) return rc;
+    if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
-    const int osz = elem_size(o_dtype);
-    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, 2, d) || !strides_ok(sV, 2, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
+    const int osz = elem_size(o_dtype), esz = elem_size(kv_dtype);          // K / V: 16-byte row starts = strides in multiples of 16 / esz
+    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
     // K / V go through buffer descriptors with 32-bit byte offsets: the prefill paths' limit on one head's extent -- of the whole
     // cache, or of one page (page bases are 64-bit: the pool as a whole may be larger)
     const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
     const int64_t extent = pg ? pg->page_size : (int64_t)Sk + 192;
-    if (extent * ks * 2 >= (1ll << 31) || extent * vs * 2 >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    if (extent * ks * esz >= (1ll << 31) || extent * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
     const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)B * H * Sq;
@@ -379,8 +382,12 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     p.table_stride = pg ? pg->table_stride : 0;
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.k_descale = kDescale;
+    p.v_descale = vDescale;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const Kernel sk = pg ? decode_paged_split_kernel_of(d) : decode_split_kernel_of(d);
+    const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
+    const Kernel sk = pg ? (kv8 ? decode_paged_fp8_split_kernel_of(d) : decode_paged_split_kernel_of(d))
+                         : (kv8 ? decode_fp8_split_kernel_of(d) : decode_split_kernel_of(d));
     hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
     if (e != hipSuccess || r.ns == 1) return (int)e;
     return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
@@ -637,8 +644,8 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
-    return fa::decode_run(Q, K, V, O, LSE, kvLens, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, scale, is_causal,
-                          dtype, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
+    return fa::decode_run(Q, K, V, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
+                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
 }
 
 int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -647,8 +654,30 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead, scale, is_causal,
-                          dtype, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
+    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
+                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
+}
+
+int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                               const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                               int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
+                               int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                               const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
+}
+
+int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                     const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
+                                     int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                     int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                     int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                                     const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
 }
 
 const char* flash_attention_error_string(int code) {

@@ -32,6 +32,13 @@
 //     16 rows.  The two table entries a wave needs per tile are fetched by one vector load (lane parity = group) two tiles ahead --
 //     in program order BEFORE the K/V loads of the tile in between, whose wait covers it -- so the table is never in the latency
 //     chain of the K/V prefetch; the index is clamped to the last page that holds a visible key and the entry into [0, num_pages).
+//   * KV8 (flash_attention_decode_fp8, flash_attention_decode_paged_fp8): the K/V elements are one byte, OCP
+//     e4m3fn, with an fp32 descale per K/V head: K = K8 * k_descale[kvh], V = V8 * v_descale[kvh].  Only the K/V stream changes: a
+//     lane's 16 bytes of K are 16 consecutive d of one key -- TWO 8-wide MFMA k-groups -- so the Q fragments are loaded in that d
+//     order (the MFMA's k index may stand for any d as long as both operands agree) and K needs no cross-lane move; a lane's 16
+//     bytes of V become 32 bytes of the same bf16 LDS image.  fp8 -> bf16 is exact (3 mantissa bits), in registers; from there
+//     on the MFMAs, the softmax and the P.V product are the bf16 kernel's.  k_descale is folded into the score scale, v_descale
+//     into the final 1 / l: the loop body carries neither.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -59,9 +66,13 @@ struct DecodeParams {
     const int32_t* block_table;   // [B][table_stride] page numbers (device memory)
     int64_t table_stride;
     int num_pages, page_shift;    // page size = 1 << page_shift, >= 16
+    // fp8 (KV8) form only: K / V hold e4m3fn bytes (strides in elements = bytes); the logical cache is K8 * k_descale[K/V head],
+    // V8 * v_descale[K/V head]
+    const float* k_descale;       // optional [Hkv] (device memory); NULL = 1
+    const float* v_descale;       // optional [Hkv] (device memory); NULL = 1
 };
 
-template <int D>
+template <int D, int ES = 2>   // ES: bytes per K/V element in memory (2: bf16, 1: e4m3fn); the LDS image of V is bf16 either way
 struct DecodeCfg {
     static constexpr int WAVES = 4, THREADS = 256;
     static constexpr int ROWS = 16;                    // packed rows per workgroup: M of the 16x16x32 MFMA
@@ -69,7 +80,8 @@ struct DecodeCfg {
     static constexpr int TILE = WAVES * WKEYS;         // keys per workgroup per inner-loop tile
     static constexpr int KS = D / 32;                  // 32-wide k-steps of the Q K^T product
     static constexpr int DG = D / 16;                  // 16-wide d groups of O^T
-    static constexpr int CPR = D / 8;                  // 16-byte chunks per K / V row
+    static constexpr int KL = KS * ES / 2;             // 16-byte K loads per lane and 16-key group: 64 bytes of a row per wave load
+    static constexpr int CPR = D * ES / 16;            // 16-byte chunks per K / V row
     static constexpr int KPI = 64 / CPR;               // V rows one wave instruction loads
     static constexpr int NV = WKEYS / KPI;             // V loads per lane per tile
     static constexpr int VROW = D * 2 + 32;            // LDS bytes per V row
@@ -86,9 +98,11 @@ __device__ __forceinline__ void store_out(void* O, int o_dtype, int64_t idx, flo
     else ((_Float16*)O)[idx] = (_Float16)v;
 }
 
-template <int D, bool PAGED>
+template <int D, bool PAGED, bool KV8 = false>
 __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams p) {
-    using C = DecodeCfg<D>;
+    constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
+    using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
+    using C = DecodeCfg<D, ES>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const lds_ptr smem = (lds_ptr)smem_raw;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -116,30 +130,35 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     // keys this row sees: [0, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0
     const int lim = p.causal ? max(len - p.Sq + qi + 1, 1) : len;
 
-    bf16x8 qf[C::KS];   // B fragment of Q^T: Q[row r][32 ks + 8 h4 .. + 7]
+    // B fragment of Q^T: Q[row r][32 ks + 8 h4 .. + 7].  KV8: Q[row r][64 (ks / 2) + 16 h4 + 8 (ks % 2) .. + 7] -- the d order in
+    // which a lane's 16-byte K loads hold two k-groups each
+    bf16x8 qf[C::KS];
     {
-        const __bf16* q = p.Q + b * p.qB + h * p.qH + qi * p.qS + 8 * h4;
+        const __bf16* q = p.Q + b * p.qB + h * p.qH + qi * p.qS + (KV8 ? 16 : 8) * h4;
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            qf[ks] = __builtin_bit_cast(bf16x8, row_ok ? *reinterpret_cast<const u32x4*>(q + 32 * ks) : z);
+            qf[ks] = __builtin_bit_cast(bf16x8, row_ok ? *reinterpret_cast<const u32x4*>(q + (KV8 ? 64 * (ks >> 1) + 8 * (ks & 1) : 32 * ks)) : z);
         }
     }
+    // the K descale rides on the score scale (one scalar load per workgroup, like kv_lens: a replayed graph sees the value of the moment)
+    float scale_log2_kd = 0.f;
+    if constexpr (KV8) scale_log2_kd = p.scale_log2 * (p.k_descale ? p.k_descale[kvh] : 1.f);
 
     // descriptors over the VISIBLE part of this (batch, K/V head): rows >= len read as 0 (contiguous form; the paged form builds
     // its descriptors per tile, below)
-    const char* Kh = (const char*)(p.K + b * p.kB + kvh * p.kH);
-    const char* Vh = (const char*)(p.V + b * p.vB + kvh * p.vH);
-    const int ksb = (int)(p.kS * 2), vsb = (int)(p.vS * 2);
-    const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, (len - 1) * ksb + D * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t vrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, (len - 1) * vsb + D * 2, 0x00020000);
-    // K A fragment (kg, ks): key 16 kg + r of the wave's 32, 16-byte chunk 4 ks + h4
+    const char* Kh = (const char*)((const KV*)p.K + b * p.kB + kvh * p.kH);
+    const char* Vh = (const char*)((const KV*)p.V + b * p.vB + kvh * p.vH);
+    const int ksb = (int)(p.kS * ES), vsb = (int)(p.vS * ES);
+    const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, (len - 1) * ksb + D * ES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t vrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, (len - 1) * vsb + D * ES, 0x00020000);
+    // K A fragment (kg, ks): key 16 kg + r of the wave's 32, 16-byte chunk 4 ks + h4 (KV8: load c = the fragments 2 c and 2 c + 1)
     const int koff = (wave * C::WKEYS + r) * ksb + h4 * 16;
     // V load n: key KPI n + lane / CPR of the wave's 32, chunk lane % CPR
     const int vkey = lane / C::CPR, vch = lane % C::CPR;
     const int voff = (wave * C::WKEYS + vkey) * vsb + vch * 16;
     const lds_ptr vimg = smem + wave * C::VIMG;
-    const int vwr = vkey * C::VROW + vch * 16;
+    const int vwr = vkey * C::VROW + vch * (32 / ES);   // (16 bytes of memory are 16 / ES elements: 32 / ES bytes of the bf16 image)
     // transposed read (dg, jj): lane 4q + pp of quarter h4 supplies row 16 jj + 4 h4 + q, columns 16 dg + 4 pp .. + 3
     const int vrd = (4 * h4 + ((lane & 15) >> 2)) * C::VROW + (lane & 3) * 8;
 
@@ -166,22 +185,22 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     // one 16-key group of one pool: a descriptor at its first row, holding its rows below len
     auto group_rsrc = [&](const __bf16* pool, int64_t page_stride, int64_t head_stride, int64_t row_stride, int entry, int key) {
         const int page = min(max(entry, 0), p.num_pages - 1);
-        const __bf16* base = pool + page * page_stride + kvh * head_stride + (key & ((1 << p.page_shift) - 1)) * row_stride;
+        const KV* base = (const KV*)pool + page * page_stride + kvh * head_stride + (key & ((1 << p.page_shift) - 1)) * row_stride;
         const int rows = min(len - key, 16);
-        const int bytes = rows > 0 ? (rows - 1) * (int)(row_stride * 2) + D * 2 : 0;
+        const int bytes = rows > 0 ? (rows - 1) * (int)(row_stride * ES) + D * ES : 0;
         const uint64_t a = (uint64_t)base;
         const uint64_t au = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
         return __builtin_amdgcn_make_buffer_rsrc((void*)au, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
-    u32x4 kn[2][C::KS], vn[C::NV];
+    u32x4 kn[2][C::KL], vn[C::NV];
     auto load_tile = [&](int t) {
         if constexpr (!PAGED) {
             const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
 #pragma unroll
             for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-                for (int ks = 0; ks < C::KS; ++ks)
+                for (int ks = 0; ks < C::KL; ++ks)
                     kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + kt + kg * 16 * ksb + ks * 64, 0, 0));
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)
@@ -197,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
             for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-                for (int ks = 0; ks < C::KS; ++ks)
+                for (int ks = 0; ks < C::KL; ++ks)
                     kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(kr[kg], gkoff + ks * 64, 0, 0));
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)   // (V load n covers the keys KPI n .. KPI n + KPI - 1 of the wave's 32: one group)
@@ -221,13 +240,27 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     for (int t = t0; t < t1; ++t) {
         // V of this tile: registers -> the wave's LDS image (the previous tile's reads are done: same wave, program order)
 #pragma unroll
-        for (int n = 0; n < C::NV; ++n) lds_write_b128(vimg, vwr + n * C::KPI * C::VROW, vn[n]);
+        for (int n = 0; n < C::NV; ++n) {
+            if constexpr (!KV8) lds_write_b128(vimg, vwr + n * C::KPI * C::VROW, vn[n]);
+            else {   // 16 e4m3fn bytes -> 16 bf16, exactly: the image is the bf16 form's
+                lds_write_b128(vimg, vwr + n * C::KPI * C::VROW, fp8x8_to_bf16x8(vn[n][0], vn[n][1]));
+                lds_write_b128(vimg, vwr + n * C::KPI * C::VROW + 16, fp8x8_to_bf16x8(vn[n][2], vn[n][3]));
+            }
+        }
         f32x4 s[2];
 #pragma unroll
         for (int kg = 0; kg < 2; ++kg) {
             s[kg] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (!KV8) {
 #pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, kn[kg][ks]), qf[ks], s[kg]);
+                for (int ks = 0; ks < C::KS; ++ks) s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, kn[kg][ks]), qf[ks], s[kg]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C::KL; ++c) {   // a 16-byte load = the A fragments of two k-groups, in the d order of qf
+                    s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][0], kn[kg][c][1])), qf[2 * c], s[kg]);
+                    s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][2], kn[kg][c][3])), qf[2 * c + 1], s[kg]);
+                }
+            }
         }
         if (t + 1 < t1) {   // (wave-uniform) next tile's K and V: in flight under the softmax and the P.V product
             if constexpr (PAGED) next_entries(t + 2);   // tile t + 1's entries arrived with the K/V of tile t: issued before them
@@ -241,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int key = kb + 16 * (j >> 2) + (j & 3);
-            x[j] = key < lim ? s[j >> 2][j & 3] * p.scale_log2 : NEG_INF;
+            x[j] = key < lim ? s[j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
             mx = fmaxf(mx, x[j]);
         }
         mx = max_all_quarters(mx);
@@ -310,7 +343,8 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     const int opr = rb * C::ROWS + orow;
     if (opr >= p.G * p.Sq) return;
     const int og = opr / p.Sq, oi = opr - og * p.Sq, oh = kvh * p.G + og;
-    const float inv = M != NEG_INF ? 1.0f / L : 0.f;                                   // empty split: O = 0
+    float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
+    if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
     const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
     const int64_t row = ((int64_t)b * p.H + oh) * p.Sq + oi;
     if (p.ns == 1) {
@@ -368,10 +402,12 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams 
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (inst_decode_bf16.hip, inst_decode_paged_bf16.hip) ----
+// ---- selectors (inst_decode_bf16.hip, inst_decode_paged_bf16.hip, inst_decode_fp8.hip, inst_decode_paged_fp8.hip) ----
 struct Kernel;
 Kernel decode_split_kernel_of(int d);
 Kernel decode_paged_split_kernel_of(int d);
+Kernel decode_fp8_split_kernel_of(int d);
+Kernel decode_paged_fp8_split_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 
 }  // namespace fa

@@ -461,6 +461,54 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                  void* stream);
 
+/*
+ * flash_attention_decode_fp8, flash_attention_decode_paged_fp8 -- flash_attention_decode / flash_attention_decode_paged against fp8
+ * K/V caches: bf16 Q, K and V stored as OCP e4m3fn bytes (not fnuz) with one fp32 descale per K/V head.  The K/V read is the cost of
+ * decode; an fp8 cache halves it and doubles the context that fits in memory.
+ *   K, V / Kpool, Vpool  the siblings' layouts with ONE-BYTE elements: rows of dHead bytes; sK / sV are element strides, which here
+ *            are bytes, each a multiple of 16 (row starts stay 16-byte aligned); NULL = dense
+ *   kDescale, vDescale   DEVICE pointers to fp32[numHeadsKV], 4-byte aligned, NULL = 1.0 for every head.  The logical cache is
+ *            K = K8 * kDescale[kvh], V = V8 * vDescale[kvh].  Read BY THE KERNEL, like kvLens: a replayed graph sees the values of the
+ *            moment.  The LSE is over the scores of the logical (descaled) K.  A descale that is not finite and positive gives an
+ *            unspecified numeric result, never a bad address
+ *   dtype    of Q: FA_DTYPE_BF16.  kv_dtype: FA_DTYPE_FP8_E4M3.  o_dtype as for the siblings
+ * Everything else -- kvLens, blockTable, LSE, workspace, numSplits, the bottom-right mask, determinism, the conventions -- is the
+ * sibling's.  flash_attention_decode_plan and flash_attention_decode_workspace_size describe these calls unchanged: the plan does not
+ * depend on the type of the cache.
+ *
+ * Conversion and precision.  e4m3fn -> bf16 is exact (3 mantissa bits, and every e4m3fn value, subnormals included, is a bf16
+ * value); it happens in registers, and from there on the arithmetic is flash_attention_decode's: bf16 MFMAs, fp32 scores and softmax,
+ * bf16 hi + lo weights.  kDescale multiplies the score scale and vDescale the normalised output, once each, in fp32; with power-of-two
+ * descales the result is exactly that of the bf16 kernel on the descaled cache.  The stated tolerance 1e-3 + 1e-3 |ref| holds against a
+ * reference computed from the DEQUANTISED values; the error of quantising a cache to fp8 is the caller's.  Range of V: |v| <= 448 *
+ * vDescale[kvh], the e4m3fn range.  Bytes at and beyond kvLens[b] and pages not read may hold any pattern, 0x7F / 0xFF (NaN) included.
+ * A NaN byte BELOW the length is data: it propagates.
+ *
+ * Paged and contiguous.  Tiles and splits are divided as in the siblings, so flash_attention_decode_paged_fp8 equals, bit for bit,
+ * flash_attention_decode_fp8 on a contiguous copy of the same pages with seqLenK = the capacity, the same descales and numSplits.
+ *
+ * Rejected before any launch: everything the sibling rejects, with the same codes; kv_dtype other than FA_DTYPE_FP8_E4M3 or dtype other
+ * than FA_DTYPE_BF16 FA_ERR_UNSUPPORTED_DTYPE; a descale pointer not aligned to 4 bytes FA_ERR_MISALIGNED; a K / V stride that is not a
+ * multiple of 16 elements FA_ERR_BAD_STRIDE.  The extent limit -- one head's K / V extent ((seqLenK + 192) x row stride), or one page's
+ * (pageSize x row stride), below 2^31 BYTES -- is counted at one byte per element: twice the rows per stride of the bf16 calls.  The
+ * capacity cap of 2^24 keys stays.
+ */
+int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                               const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace,
+                               int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                               float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                               const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                               void* stream);
+
+int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                     const int32_t* kvLens, const int32_t* blockTable,
+                                     const float* kDescale, const float* vDescale, void* workspace,
+                                     int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                     int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                     float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                     const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                     void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 

@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256]
+                                [--paged 16,128,256] [--kv fp8]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -20,6 +20,11 @@ Each line:
 --paged a,b,c   page sizes: per shape, the same K/V data scattered into pools of such pages behind a SHUFFLED block table, through
               flash_attention_decode_paged (same lengths, O, workspace and plan as `ms`): paged_ms[page] with its min / max and
               paged_ratio[page] = paged_ms / ms (profiles/decode_paged_bench.log).
+--kv fp8        per shape, the same call against the fp8 cache of that shape: the bf16 K/V quantised to float8_e4m3fn per K/V head
+              (descale = amax / 448), same Q, lengths, O, workspace and plan as `ms` and timed the same way in the same run: fp8_ms
+              with its min / max, fp8_ratio = fp8_ms / ms, and fp8_kv_tbps from the bytes actually read (one per element: kv_MB / 2).
+              With --paged, paged_fp8_ms[page] as well: the fp8 pools behind the same shuffled table
+              (profiles/decode_fp8_bench.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
 """
 import argparse
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--splits", default=None, help="comma-separated forced split counts: the sweep")
     ap.add_argument("--no-cross", action="store_true")
     ap.add_argument("--paged", default=None, help="comma-separated page sizes: add paged_ms per page size to every shape's line")
+    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
@@ -103,20 +109,36 @@ def main():
             ms = sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
             return plan, ms
 
-        def measure_paged(page):
+        def quantised(T):
+            # the fp8 cache of this shape: per K/V head, descale = amax / 448 (torch's cast gives NaN beyond 448: clamp)
+            ds = (T.float().abs().amax(dim=(0, 2, 3)) / 448.0).float()
+            T8 = torch.empty(T.shape, dtype=torch.float8_e4m3fn, device=dev)
+            for b in range(B):     # (a batch entry at a time: no fp32 copy of a 1 GB cache)
+                T8[b] = (T[b].float() / ds[:, None, None]).clamp(-448, 448).to(torch.float8_e4m3fn)
+            return T8, ds
+
+        def measure_fp8():
+            plan = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0)
+            ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            call = lambda: fa.flash_attention_decode(Q, K8, V8, lens_d, O=O, workspace=ws, k_descale=kds, v_descale=vds)
+            return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
+
+        def measure_paged(page, fp8=False):
             # the same data in pages: page j of sequence b is rows [j page, (j + 1) page) of every K/V head, stored wherever a
             # shuffle of all B * n page numbers puts it
             n = Sk // page
             perm = torch.randperm(B * n, device=dev, generator=g)
             table = perm.reshape(B, n).to(torch.int32)
             pools = []
-            for T in (K, V):
-                pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=torch.bfloat16)
+            for T in ((K8, V8) if fp8 else (K, V)):
+                T = T.view(torch.uint8) if fp8 else T      # (pages are moved as bytes)
+                pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=T.dtype)
                 pool[perm] = T.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
-                pools.append(pool)
+                pools.append(pool.view(torch.float8_e4m3fn) if fp8 else pool)
             ns = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0)["num_splits"]
             ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, ns), 16), dtype=torch.uint8, device=dev)
-            call = lambda: fa.flash_attention_decode_paged(Q, pools[0], pools[1], table, lens_d, O=O, workspace=ws)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            call = lambda: fa.flash_attention_decode_paged(Q, pools[0], pools[1], table, lens_d, O=O, workspace=ws, **kw)
             return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
 
         if args.splits:
@@ -132,6 +154,8 @@ def main():
             continue
         plan, ms = measure(0)
         med = statistics.median(ms)
+        if args.kv == "fp8":
+            (K8, kds), (V8, vds) = quantised(K), quantised(V)
         line = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "Sq": Sq, "Sk": Sk, "d": d, "ragged": ragged, "io": "bfloat16",
                 "ms": round(med, 5), "ms_min": round(ms[0], 5), "ms_max": round(ms[-1], 5), "repeats": args.repeats, "steps": args.steps,
                 "kv_MB": round(kv_bytes / 1e6, 1), "kv_TBps": round(kv_bytes / med / 1e9, 3),
@@ -149,6 +173,18 @@ def main():
                         paged_ms_min={str(k): round(v[0], 5) for k, v in pm.items()},
                         paged_ms_max={str(k): round(v[-1], 5) for k, v in pm.items()},
                         paged_ratio={str(k): round(statistics.median(v) / med, 4) for k, v in pm.items()})
+        if args.kv == "fp8":
+            f8 = measure_fp8()
+            fmed = statistics.median(f8)
+            line.update(fp8_ms=round(fmed, 5), fp8_ms_min=round(f8[0], 5), fp8_ms_max=round(f8[-1], 5), fp8_ratio=round(fmed / med, 4),
+                        fp8_kv_MB=round(kv_bytes / 2 / 1e6, 1), fp8_kv_tbps=round(kv_bytes / 2 / fmed / 1e9, 3))
+            if args.paged:
+                pf = {page: measure_paged(page, True) for page in (int(x) for x in args.paged.split(",")) if Sk % page == 0}
+                line.update(paged_fp8_ms={str(k): round(statistics.median(v), 5) for k, v in pf.items()},
+                            paged_fp8_ms_min={str(k): round(v[0], 5) for k, v in pf.items()},
+                            paged_fp8_ms_max={str(k): round(v[-1], 5) for k, v in pf.items()},
+                            paged_fp8_ratio={str(k): round(statistics.median(v) / fmed, 4) for k, v in pf.items()})
+            del K8, V8
         print(json.dumps(line), flush=True)
         del Q, K, V, O
         torch.cuda.empty_cache()
