@@ -681,6 +681,13 @@ def test_noncausal_key_permutation_invariance():
 
 
 # ------------------------------------------------------------------ parity at the STATED tolerance
+def _same_early_kernel(B, H, Sq, Sk, d, causal, o_dtype, flags_a, flags_b):
+    """plan_ex reports ONE kernel for the fp16-weights (early) query blocks of two calls that differ in their flags"""
+    ea, _ = fa.plan_ex(B, H, Sq, Sk, d, causal, fa.FA_DTYPE_BF16, o_dtype, flags_a)
+    eb, _ = fa.plan_ex(B, H, Sq, Sk, d, causal, fa.FA_DTYPE_BF16, o_dtype, flags_b)
+    return ea["q_blocks"] > 0 and eb["q_blocks"] > 0 and all(ea[k] == eb[k] for k in ("kernel_id", "q_block_rows", "kv_block_rows", "threads", "grid", "lds_bytes"))
+
+
 def _parity_table(tag, O, ref):
     from parity import parity_report
     rep = parity_report(O, ref)
@@ -720,13 +727,14 @@ def test_parity_at_stated_tolerance_cfg2_all_weight_precisions(causal):
         assert rep["pass_frac_at_1e-3"] >= floors[wd], rep
         if wd == torch.bfloat16:
             assert (np.abs(got - ref) <= 4e-3 + 4e-3 * np.abs(ref)).all(), rep
-    # the default at this size is the mixed-precision kernel: its bf16-weights units ARE the bf16-weights kernel's (bit for bit), its
-    # fp16-weights units the same arithmetic as FA_FLAG_F16_WEIGHTS on the other MFMA shape (32x32x16 against 16x16x32: the fp32 sums
-    # are taken in another order)
+    # the default at this size is the mixed-precision kernel: its bf16-weights units ARE the bf16-weights kernel's (bit for bit), and
+    # under the mask FA_FLAG_F16_WEIGHTS is that same mixed-precision kernel with every query block early (route(): Family::causal_mix
+    # with hp = nQ; plan_ex shows one kernel): its fp16-weights units are the default's, bit for bit
     E = fa.FA_EARLY_KEYS
     if causal:
         assert np.array_equal(outs[None][:, E:], outs[torch.bfloat16][:, E:])
-        assert np.abs(outs[None][:, :E] - outs[torch.float16][:, :E]).max() <= 2e-5 and not np.array_equal(outs[None][:, :E], outs[torch.bfloat16][:, :E])
+        assert _same_early_kernel(B, H, S, S, d, True, fa.FA_DTYPE_F32, 0, fa.FA_FLAG_F16_WEIGHTS)
+        assert np.array_equal(outs[None][:, :E], outs[torch.float16][:, :E]) and not np.array_equal(outs[None][:, :E], outs[torch.bfloat16][:, :E])
     else:
         assert np.array_equal(outs[None], outs[torch.bfloat16])
 
@@ -734,9 +742,9 @@ def test_parity_at_stated_tolerance_cfg2_all_weight_precisions(causal):
 def test_default_weight_precision_is_the_two_kernels_on_disjoint_rows():
     """flags = 0 on a bf16 problem = fp16 weights on the query blocks whose rows see fewer than FA_EARLY_KEYS = 1024 keys + bf16 weights
     on the rest.  Rows with bf16 weights: bit for bit the FA_FLAG_BF16_WEIGHTS call (the same code), O and LSE, every head.  Rows with
-    fp16 weights: bit for bit the FA_FLAG_F16_WEIGHTS call where the whole problem is "early" (the same kernel); in a causal problem
-    longer than FA_EARLY_KEYS they come from the mixed-precision kernel's fp16 units -- the same arithmetic on the 32x32x16 MFMA instead
-    of the 16x16x32 one, equal to fp32 summation order."""
+    fp16 weights: bit for bit the FA_FLAG_F16_WEIGHTS call -- where the whole problem is "early" it is the same call, and in a causal
+    problem longer than FA_EARLY_KEYS both calls run ONE kernel (plan_ex: the mixed-precision kernel, here in its small-problem pair
+    form; the flag only moves hp to nQ), whose fp16-weights units do not depend on hp."""
     E = fa.FA_EARLY_KEYS
 
     def three(Q, K, V, causal, lse, out_dtype=torch.float32):
@@ -748,13 +756,13 @@ def test_default_weight_precision_is_the_two_kernels_on_disjoint_rows():
         return outs
 
     for d, lse, out_dtype in ((128, True, torch.float32), (64, False, torch.bfloat16)):
-        # causal, S = 1500 > E: rows [0, 1024) early, [1024, 1500) main -- the mixed-precision kernel
+        # causal, S = 1500 > E: rows [0, 1024) early, [1024, 1500) main -- both precisions in one launch
         Q, K, V = (randn((2, 3, 1500, d), s, torch.bfloat16) for s in (601, 602, 603))
         dflt, f16, b16 = three(Q, K, V, True, lse, out_dtype)
         for k in range(len(dflt)):
             assert np.array_equal(dflt[k][:, :, E:], b16[k][:, :, E:])
-            close = 2e-5 if out_dtype == torch.float32 else 2.0 ** -7      # (bf16 output: one ulp at |O| ~ 1)
-            assert np.abs(dflt[k][:, :, :E] - f16[k][:, :, :E]).max() <= close
+            assert _same_early_kernel(2, 3, 1500, 1500, d, True, fa.FA_DTYPE_F32 if out_dtype == torch.float32 else fa.FA_DTYPE_BF16, 0, fa.FA_FLAG_F16_WEIGHTS)
+            assert np.array_equal(dflt[k][:, :, :E], f16[k][:, :, :E])      # (one kernel on both sides: no tolerance)
         assert not np.array_equal(f16[0][:, :, E:], b16[0][:, :, E:])            # (the two precisions do differ)
         assert np.abs(dflt[0][:, :, :E] - f16[0][:, :, :E]).max() < np.abs(dflt[0][:, :, :E] - b16[0][:, :, :E]).max()
         # causal cross attention against FEWER keys than FA_EARLY_KEYS: every row sees < E keys -> all early
@@ -920,6 +928,8 @@ def _rel_check(O, ref, scale, atol, rtol):
     (2, 64, 2048, 2048, 128, True, 2047),    # ... a key only the late (bf16-weights) units ever load: nothing to fall back from
     (4, 40, 512, 900, 128, False, 100),      # no mask, seqLenK < FA_EARLY_KEYS: every unit runs the fp16-weights kernel and every row sees the key
     (1, 3, 600, 600, 64, True, 300),         # the pair kernel (small problem), d = 64
+    (1, 4, 600, 600, 128, True, 300),        # ... d = 128: three passes in one kernel
+    (1, 8, 512, 700, 128, False, 100),       # ... without the mask, seqLenK < FA_EARLY_KEYS: every unit three-stage
     (2, 96, 1024, 1024, 64, True, 1023),     # d = 64 persistent, all rows early; only the last row sees the key, 63 rows share its tile masked
 ])
 def test_default_call_is_finite_and_right_for_any_finite_bf16_v(B, H, S, Sk, d, causal, k_big):
@@ -1001,9 +1011,11 @@ def test_small_noncausal_shard_against_the_whole_problem():
     assert fa.plan(B, H, S, d, False, fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32)["threads"] == 512 and fa.plan(1, 8, S, d, False, fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32)["threads"] == 256
     whole = fa.flash_attention(Q, K, V, out_dtype=torch.float32)
     part = fa.flash_attention(Q[:, 8:16].contiguous(), K[:, 8:16].contiguous(), V[:, 8:16].contiguous(), out_dtype=torch.float32)
-    whole_l, _ = fa.flash_attention(Q, K, V, out_dtype=torch.float32, return_lse=True)
-    part_l, _ = fa.flash_attention(Q[:, 8:16].contiguous(), K[:, 8:16].contiguous(), V[:, 8:16].contiguous(), out_dtype=torch.float32, return_lse=True)
+    O_whole, lse_whole = fa.flash_attention(Q, K, V, out_dtype=torch.float32, return_lse=True)
+    O_part, lse_part = fa.flash_attention(Q[:, 8:16].contiguous(), K[:, 8:16].contiguous(), V[:, 8:16].contiguous(), out_dtype=torch.float32, return_lse=True)
     torch.cuda.synchronize()
     a, b = whole[:, 8:16].cpu().numpy(), part.cpu().numpy()
     assert np.abs(a - b).max() <= 2.0 ** -9 * np.abs(a).max()
-    assert float((whole_l[:, 8:16] - part_l).abs().max()) <= 1e-6
+    # with the LSE requested on both sides: the same arithmetic, O bit for bit (the header's promise); the two LSEs as well
+    assert torch.equal(O_whole[:, 8:16], O_part)
+    assert torch.equal(lse_whole[:, 8:16], lse_part)

@@ -35,23 +35,7 @@ def expand(t, G):
 
 
 # ---- forward ---------------------------------------------------------------------------------------------------------------------
-def family(B, H, Sq, Sk, d, causal, dtype, o_dtype, flags):
-    """the kernel family a call takes, from what plan_ex reports"""
-    e, m = fa.plan_ex(B, H, Sq, Sk, d, causal, dtype, o_dtype, flags)
-    live = m if m["q_blocks"] else e
-    kid = live["kernel_id"]
-    if kid != 1:
-        return {0: "generic", 2: "fp8", 3: "f32"}[kid]
-    if live["q_block_rows"] == 128:
-        return "pair"
-    if d not in (64, 128):
-        return "bf16_padded"
-    if e["q_blocks"] and m["q_blocks"]:
-        assert e["unit_lists"] == 1
-        return "causal_mix"
-    if e["q_blocks"]:
-        return "f16_weights"
-    return "bf16"
+from forward_routes import family  # noqa: E402  (the kernel family a call takes, from what plan_ex reports)
 
 
 # (family, in dtype, out dtype, B, Hq, Hkv, Sq, Sk, d, causal, weights_dtype)
