@@ -248,12 +248,7 @@ def flash_attention(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None
             rc = lib().flash_attention_gqa(*ptrs, lse.data_ptr() if lse is not None else None, B, H, Hkv, S, Sk, d, *common, *refs,
                                            flags, _stream_ptr(stream))
         elif flags:
-            st = []
-            for t in (Q, K, V, O):
-                if t.stride(3) != 1:
-                    raise ValueError("last dimension must be contiguous")
-                st.append(FaStrides(t.stride(0), t.stride(1), t.stride(2)))
-            refs = [ctypes.byref(x) for x in st]
+            refs = [ctypes.byref(_strides(t)) for t in (Q, K, V, O)]
             rc = lib().flash_attention_ex(*ptrs, lse.data_ptr() if lse is not None else None, B, H, S, Sk, d, *common, *refs,
                                           flags, _stream_ptr(stream))
         elif dense and Sk == S and lse is not None:
@@ -261,12 +256,7 @@ def flash_attention(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None
         elif dense and Sk == S:
             rc = lib().flash_attention(*ptrs, B, H, S, d, *common, _stream_ptr(stream))
         else:
-            st = []
-            for t in (Q, K, V, O):
-                if t.stride(3) != 1:
-                    raise ValueError("last dimension must be contiguous")
-                st.append(FaStrides(t.stride(0), t.stride(1), t.stride(2)))
-            refs = [ctypes.byref(x) for x in st]
+            refs = [ctypes.byref(_strides(t)) for t in (Q, K, V, O)]
             if Sk == S and lse is None:
                 rc = lib().flash_attention_strided(*ptrs, B, H, S, d, *common, *refs, _stream_ptr(stream))
             else:
@@ -419,22 +409,71 @@ def decode_workspace_size(B, H, Sq, d, num_splits):
     return int(lib().flash_attention_decode_workspace_size(B, H, Sq, d, num_splits))
 
 
-def _decode_kv_fp8(Q, K, V, k_descale, v_descale, what):
-    """True when the call is the fp8-cache form (bf16 Q, e4m3fn K and V); checks the dtypes and the descales either way."""
+def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None):
+    """The checks both decode fronts make of Q and the tensors that play K/V (``kv``, ``layout``: their names and shape in the error
+    texts; ``table``: the paged front's block table -- pools are not indexed by the batch).  True when the call is the fp8-cache form (bf16 Q,
+    e4m3fn K and V); the dtypes and the descales are checked either way."""
     import torch
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda and (table is None or table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or (table is None and Q.shape[0] != K.shape[0]) or Q.shape[3] != K.shape[3] \
+            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
+        raise ValueError(f"Q must be [B, H, Sq, d] and {kv} {layout} with Hkv dividing H")
     f8 = getattr(torch, "float8_e4m3fn", None)
     fp8 = f8 is not None and Q.dtype == torch.bfloat16 and K.dtype == f8 and V.dtype == f8
     if not fp8 and not (Q.dtype == K.dtype == V.dtype):
-        raise TypeError(f"{what} must share a dtype")
-    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        raise TypeError(f"Q, {kv} must share a dtype")
+    for what, t in (("k_descale", k_descale), ("v_descale", v_descale)):
         if t is None:
             continue
         if not fp8:
-            raise ValueError(f"{name} belongs to an fp8 (float8_e4m3fn) K/V cache under a bf16 Q")
+            raise ValueError(f"{what} belongs to an fp8 (float8_e4m3fn) K/V cache under a bf16 Q")
         if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != Q.device or tuple(t.shape) != (K.shape[1],) \
                 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a dense fp32 tensor [Hkv] on the device of Q")
+            raise ValueError(f"{what} must be a dense fp32 tensor [Hkv] on the device of Q")
     return fp8
+
+
+def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
+            stream, k_descale, v_descale):
+    """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
+    point (fp8: its ``_fp8`` twin), ``tables`` its tensors between kvLens and the workspace, ``geometry`` its ints between seqLenQ and
+    dHead; ``decode_plan`` / ``decode_workspace_size`` are asked about ``capacity``."""
+    import torch
+    B, H, Sq, d = Q.shape
+    Hkv = K.shape[1]
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    if scale is None:
+        scale = 1.0 / float(d) ** 0.5
+    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
+    ns = decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits)["num_splits"]
+    need = decode_workspace_size(B, H, Sq, d, ns)
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif O.shape != Q.shape or not O.is_cuda:
+                raise ValueError("O must be a device tensor shaped like Q")
+            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            if workspace is None and need:
+                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
+            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
+        st = [_strides(t) for t in (Q, K, V, O)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables))
+        if fp8:
+            ptrs += (ptr(k_descale), ptr(v_descale))
+        dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 else (_dtype_code(Q.dtype),)
+        launch = getattr(lib(), symbol + "_fp8" if fp8 else symbol)
+        rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
+                    _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
 
 
 def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
@@ -454,49 +493,10 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     fp8 cache: K and V of ``torch.float8_e4m3fn`` under a bf16 Q, with ``k_descale`` / ``v_descale``: fp32 device tensors ``[Hkv]``
     (None = 1), read by the kernel like ``kv_lens``.  The logical cache is ``K.float() * k_descale[kvh]``, ``V.float() *
     v_descale[kvh]``; the conversion is exact and everything else is as for bf16 (``decode_plan`` does not depend on the cache type)."""
-    import torch
-    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
-        raise RuntimeError("flash_attention_decode needs device tensors (no CPU fallback)")
-    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] or Q.shape[3] != K.shape[3] \
-            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
-        raise ValueError("Q must be [B, H, Sq, d] and K, V [B, Hkv, capacity, d] with Hkv dividing H")
-    fp8 = _decode_kv_fp8(Q, K, V, k_descale, v_descale, "Q, K, V")
-    B, H, Sq, d = Q.shape
-    Hkv, Sk = K.shape[1:3]
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
-                                or not kv_lens.is_contiguous()):
-        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
-    if scale is None:
-        scale = 1.0 / float(d) ** 0.5
-    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = decode_plan(B, H, Hkv, Sq, Sk, d, odt, num_splits)["num_splits"]
-    need = decode_workspace_size(B, H, Sq, d, ns)
-    with torch.cuda.device(Q.device):
-        s = stream if stream is not None else torch.cuda.current_stream()
-        # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
-        with torch.cuda.stream(s):
-            if O is None:
-                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
-            elif O.shape != Q.shape or not O.is_cuda:
-                raise ValueError("O must be a device tensor shaped like Q")
-            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
-            if workspace is None and need:
-                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
-        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
-            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
-        st = [_strides(t) for t in (Q, K, V, O)]
-        head = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), lse.data_ptr() if lse is not None else None,
-                kv_lens.data_ptr() if kv_lens is not None else None)
-        ws = workspace.data_ptr() if need else None
-        tail = (_dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
-        if fp8:
-            rc = lib().flash_attention_decode_fp8(*head, k_descale.data_ptr() if k_descale is not None else None,
-                                                  v_descale.data_ptr() if v_descale is not None else None, ws, B, H, Hkv, Sq, Sk, d,
-                                                  float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(K.dtype), *tail)
-        else:
-            rc = lib().flash_attention_decode(*head, ws, B, H, Hkv, Sq, Sk, d, float(scale), bool(is_causal), _dtype_code(Q.dtype), *tail)
-    _check(rc)
-    return (O, lse) if return_lse else O
+    fp8 = _decode_inputs("flash_attention_decode", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
+    Sk = K.shape[2]
+    return _decode("flash_attention_decode", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
+                   O, workspace, stream, k_descale, v_descale)
 
 
 def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
@@ -516,54 +516,18 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     same pages, bit for bit.  fp8 pools (``torch.float8_e4m3fn`` under a bf16 Q) with ``k_descale`` / ``v_descale`` as for
     ``flash_attention_decode``.  No CPU fallback."""
     import torch
-    if not (Q.is_cuda and K_pool.is_cuda and V_pool.is_cuda and block_table.is_cuda):
-        raise RuntimeError("flash_attention_decode_paged needs device tensors (no CPU fallback)")
-    if Q.dim() != 4 or K_pool.dim() != 4 or K_pool.shape != V_pool.shape or Q.shape[3] != K_pool.shape[3] \
-            or K_pool.shape[1] < 1 or Q.shape[1] % K_pool.shape[1] != 0:
-        raise ValueError("Q must be [B, H, Sq, d] and K_pool, V_pool [P, Hkv, page, d] with Hkv dividing H")
-    fp8 = _decode_kv_fp8(Q, K_pool, V_pool, k_descale, v_descale, "Q, K_pool, V_pool")
-    B, H, Sq, d = Q.shape
-    P, Hkv, page = K_pool.shape[:3]
+    fp8 = _decode_inputs("flash_attention_decode_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
+                         v_descale, table=block_table)
+    B = Q.shape[0]
+    P, _, page = K_pool.shape[:3]
     if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
             or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
         raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
     max_pages = block_table.shape[1]
     table_stride = block_table.stride(0) if B > 1 else max_pages
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
-                                or not kv_lens.is_contiguous()):
-        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
-    if scale is None:
-        scale = 1.0 / float(d) ** 0.5
-    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = decode_plan(B, H, Hkv, Sq, max_pages * page, d, odt, num_splits)["num_splits"]
-    need = decode_workspace_size(B, H, Sq, d, ns)
-    with torch.cuda.device(Q.device):
-        s = stream if stream is not None else torch.cuda.current_stream()
-        # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
-        with torch.cuda.stream(s):
-            if O is None:
-                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
-            elif O.shape != Q.shape or not O.is_cuda:
-                raise ValueError("O must be a device tensor shaped like Q")
-            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
-            if workspace is None and need:
-                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
-        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
-            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
-        st = [_strides(t) for t in (Q, K_pool, V_pool, O)]
-        head = (Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(), O.data_ptr(), lse.data_ptr() if lse is not None else None,
-                kv_lens.data_ptr() if kv_lens is not None else None, block_table.data_ptr())
-        ws = workspace.data_ptr() if need else None
-        shape = (B, H, Hkv, Sq, P, page, max_pages, table_stride, d, float(scale), bool(is_causal), _dtype_code(Q.dtype))
-        tail = (_dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
-        if fp8:
-            rc = lib().flash_attention_decode_paged_fp8(*head, k_descale.data_ptr() if k_descale is not None else None,
-                                                        v_descale.data_ptr() if v_descale is not None else None, ws, *shape,
-                                                        _dtype_code(K_pool.dtype), *tail)
-        else:
-            rc = lib().flash_attention_decode_paged(*head, ws, *shape, *tail)
-    _check(rc)
-    return (O, lse) if return_lse else O
+    return _decode("flash_attention_decode_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
+                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                   k_descale, v_descale)
 
 
 def _library_accepts(t):

@@ -26,16 +26,30 @@ namespace fa {
 // ------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The element strides of a [*, heads, rows, d] tensor into (strideB, strideH, strideS): the caller's, or (s = NULL) the dense ones
+static void resolve_strides(const fa_strides* s, int64_t heads, int64_t rows, int64_t d, int64_t& sB, int64_t& sH, int64_t& sS) {
+    sB = s ? s->strideB : heads * rows * d;
+    sH = s ? s->strideH : rows * d;
+    sS = s ? s->strideS : d;
+}
+
+// K / V are fetched through buffer descriptors with 32-bit byte offsets: the `rows` rows of one head, strideS elements of esz bytes
+// apart, must end below 2^31 bytes.  The prefill-style paths pass seqLenK + KV_EXTENT_SLACK: two prefetch tiles of slack
+constexpr int KV_EXTENT_SLACK = 192;
+static bool kv_extent_ok(int64_t rows, int64_t strideS, int esz) { return rows * strideS * esz < (1ll << 31); }
+
+static bool is_input_dtype(int t) { return t == FA_DTYPE_F32 || t == FA_DTYPE_BF16 || t == FA_DTYPE_FP8_E4M3; }
+static bool is_output_dtype(int t) { return t == FA_DTYPE_F32 || t == FA_DTYPE_BF16 || t == FA_DTYPE_F16; }
+static bool is_f32_or_bf16(int t) { return t == FA_DTYPE_F32 || t == FA_DTYPE_BF16; }   // the backward's O / dO and gradients
+
 static int fill_params(Params& p, const void* Q, const void* K, const void* V, void* O, float* lse, int B, int H, int Hkv,
                        int S, int Sk, int d, float scale, const fa_strides* sQ, const fa_strides* sK,
                        const fa_strides* sV, const fa_strides* sO) {
     p.Q = Q; p.K = K; p.V = V; p.O = O; p.lse = lse;
-    const int64_t dS = d, dH = (int64_t)S * d, dB = (int64_t)H * S * d;      // dense Q / O
-    const int64_t kH = (int64_t)Sk * d, kB = (int64_t)Hkv * Sk * d;          // dense K / V
-    p.qB = sQ ? sQ->strideB : dB; p.qH = sQ ? sQ->strideH : dH; p.qS = sQ ? sQ->strideS : dS;
-    p.kB = sK ? sK->strideB : kB; p.kH = sK ? sK->strideH : kH; p.kS = sK ? sK->strideS : dS;
-    p.vB = sV ? sV->strideB : kB; p.vH = sV ? sV->strideH : kH; p.vS = sV ? sV->strideS : dS;
-    p.oB = sO ? sO->strideB : dB; p.oH = sO ? sO->strideH : dH; p.oS = sO ? sO->strideS : dS;
+    resolve_strides(sQ, H, S, d, p.qB, p.qH, p.qS);
+    resolve_strides(sK, Hkv, Sk, d, p.kB, p.kH, p.kS);
+    resolve_strides(sV, Hkv, Sk, d, p.vB, p.vH, p.vS);
+    resolve_strides(sO, H, S, d, p.oB, p.oH, p.oS);
     p.B = B; p.H = H; p.S = S; p.Sk = Sk; p.d = d;
     p.scale = scale;
     p.scale_log2 = scale * 1.4426950408889634f;
@@ -72,8 +86,7 @@ static int validate(const void* Q, const void* K, const void* V, void* O, int B,
     if (B <= 0 || H <= 0 || S <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
     if ((int64_t)B * H > INT32_MAX / 2 || S > (1 << 24)) return FA_ERR_BAD_SHAPE;
     if (!std::isfinite(scale)) return FA_ERR_BAD_SCALE;
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16 && o_dtype != FA_DTYPE_F16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_input_dtype(dtype) || !is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d > 256) return FA_ERR_UNSUPPORTED_DHEAD;
     if (dtype == FA_DTYPE_FP8_E4M3 && d > 128) return FA_ERR_UNSUPPORTED_DHEAD;   // fp8: MFMA path only ...
     if (dtype == FA_DTYPE_FP8_E4M3 && !(scale > 0.f)) return FA_ERR_BAD_SCALE;    // ... which folds a positive scale into exp2
@@ -259,10 +272,9 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
         return FA_ERR_BAD_STRIDE;
     const Route r = route(B, H, S, Sk, d, causal, dtype, o_dtype, scale, flags, lse != nullptr);
     if (r.kernel_id != 0) {
-        // K/V are fetched through buffer descriptors with 32-bit byte offsets: one head's extent
-        // (seqLen x row stride) must stay below 2^31 bytes (two prefetch tiles of slack included)
-        const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
-        if (((int64_t)Sk + 192) * ks * esz >= (1ll << 31) || ((int64_t)Sk + 192) * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+        // the MFMA paths' limit on one head's K / V extent (the generic kernel has none)
+        const int64_t rows = (int64_t)Sk + KV_EXTENT_SLACK;
+        if (!kv_extent_ok(rows, sK ? sK->strideS : d, esz) || !kv_extent_ok(rows, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
     }
     if (r.units > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;   // unit indices are 32-bit
     Params p;
@@ -315,7 +327,7 @@ static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int 
     if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
     if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16 && o_dtype != FA_DTYPE_F16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
     if (decode_route(B, H, Hkv, Sq, Sk, numSplits).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
@@ -353,11 +365,10 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
     const int osz = elem_size(o_dtype), esz = elem_size(kv_dtype);          // K / V: 16-byte row starts = strides in multiples of 16 / esz
     if (!strides_ok(sQ, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
-    // K / V go through buffer descriptors with 32-bit byte offsets: the prefill paths' limit on one head's extent -- of the whole
-    // cache, or of one page (page bases are 64-bit: the pool as a whole may be larger)
-    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
-    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + 192;
-    if (extent * ks * esz >= (1ll << 31) || extent * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    // the prefill paths' limit on one head's K / V extent -- of the whole cache, or of one page (page bases are 64-bit: the pool as a
+    // whole may be larger)
+    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;
+    if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
     const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)B * H * Sq;
@@ -368,10 +379,10 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
     p.part_o = (float*)workspace;
     p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
-    p.qB = sQ ? sQ->strideB : (int64_t)H * Sq * d;      p.qH = sQ ? sQ->strideH : (int64_t)Sq * d;     p.qS = sQ ? sQ->strideS : d;
-    p.kB = sK ? sK->strideB : (int64_t)Hkv * rowsK * d; p.kH = sK ? sK->strideH : (int64_t)rowsK * d;  p.kS = ks;
-    p.vB = sV ? sV->strideB : (int64_t)Hkv * rowsK * d; p.vH = sV ? sV->strideH : (int64_t)rowsK * d;  p.vS = vs;
-    p.oB = sO ? sO->strideB : (int64_t)H * Sq * d;      p.oH = sO ? sO->strideH : (int64_t)Sq * d;     p.oS = sO ? sO->strideS : d;
+    resolve_strides(sQ, H, Sq, d, p.qB, p.qH, p.qS);
+    resolve_strides(sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+    resolve_strides(sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+    resolve_strides(sO, H, Sq, d, p.oB, p.oH, p.oS);
     p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = Sk;
     p.row_blocks = r.row_blocks; p.ns = r.ns;
     p.rows = (int)rows;
@@ -449,16 +460,14 @@ int flash_attention_weights(const void* Q, const void* K, const float* LSE, floa
     if (!aligned16(Q) || !aligned16(K) || !aligned16(LSE) || !aligned16(P)) return FA_ERR_MISALIGNED;
     if (batchSize <= 0 || numHeads <= 0 || seqLenQ <= 0 || seqLenK <= 0 || dHead <= 0) return FA_ERR_BAD_SHAPE;
     if (!std::isfinite(scale)) return FA_ERR_BAD_SCALE;
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_input_dtype(dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     const int esz = elem_size(dtype);
     if (dHead > 256 || (dHead * esz) % 16 != 0) return FA_ERR_UNSUPPORTED_DHEAD;
     if (!strides_ok(sQ, esz, dHead) || !strides_ok(sK, esz, dHead)) return FA_ERR_BAD_STRIDE;
     WeightsParams p;
     p.Q = Q; p.K = K; p.lse = LSE; p.P = P;
-    p.qB = sQ ? sQ->strideB : (int64_t)numHeads * seqLenQ * dHead; p.qH = sQ ? sQ->strideH : (int64_t)seqLenQ * dHead;
-    p.qS = sQ ? sQ->strideS : dHead;
-    p.kB = sK ? sK->strideB : (int64_t)numHeads * seqLenK * dHead; p.kH = sK ? sK->strideH : (int64_t)seqLenK * dHead;
-    p.kS = sK ? sK->strideS : dHead;
+    resolve_strides(sQ, numHeads, seqLenQ, dHead, p.qB, p.qH, p.qS);
+    resolve_strides(sK, numHeads, seqLenK, dHead, p.kB, p.kH, p.kS);
     p.H = numHeads; p.Sq = seqLenQ; p.Sk = seqLenK; p.d = dHead;
     p.nQ = (seqLenQ + 15) / 16; p.nK = (seqLenK + 63) / 64;
     p.scale = scale; p.causal = is_causal;
@@ -505,7 +514,7 @@ int flash_attention_plan(int batchSize, int numHeads, int seqLen, int dHead, boo
                          int o_dtype, fa_launch_plan* plan) {
     if (!plan) return FA_ERR_NULL_POINTER;
     if (batchSize <= 0 || numHeads <= 0 || seqLen <= 0 || dHead <= 0) return FA_ERR_BAD_SHAPE;
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!fa::is_input_dtype(dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (dtype == FA_DTYPE_FP8_E4M3 && dHead > 128) return FA_ERR_UNSUPPORTED_DHEAD;
     if (dHead > 256 || (dHead * fa::elem_size(dtype)) % 16 != 0) return FA_ERR_UNSUPPORTED_DHEAD;
     // (flash_attention_plan_ex with seqLenK = seqLen and bf16 weights: one range)
@@ -572,16 +581,15 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     const int Hkv = numHeadsKV;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (o_dtype != FA_DTYPE_F32 && o_dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (grad_dtype != FA_DTYPE_F32 && grad_dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_f32_or_bf16(o_dtype) || !is_f32_or_bf16(grad_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
     const int esz = elem_size(dtype), osz = elem_size(o_dtype), gsz = elem_size(grad_dtype);
     if (!strides_ok(sQ, esz, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d) ||
         !strides_ok(sdO, osz, d) || !strides_ok(sdQ, gsz, d) || !strides_ok(sdK, gsz, d) || !strides_ok(sdV, gsz, d))
         return FA_ERR_BAD_STRIDE;
     // the forward's MFMA-path limit on one head's K / V extent
-    const int64_t ks = sK ? sK->strideS : d, vs = sV ? sV->strideS : d;
-    if (((int64_t)Sk + 192) * ks * esz >= (1ll << 31) || ((int64_t)Sk + 192) * vs * esz >= (1ll << 31)) return FA_ERR_BAD_SHAPE;
+    const int64_t extent = (int64_t)Sk + KV_EXTENT_SLACK;
+    if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
     // the main kernel's grid: one workgroup per 256-key block of every (batch, K/V head)
     const int64_t heads = (int64_t)B * H, kv_heads = (int64_t)B * Hkv, nK = (Sk + 255) / 256, rows = heads * Sq;
     if (kv_heads * nK > INT32_MAX || rows * d / 4 / 256 + 1 > INT32_MAX) return FA_ERR_BAD_SHAPE;
@@ -591,12 +599,10 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     p.dQ = dQ; p.dK = dK; p.dV = dV;
     p.delta = (float*)workspace;
     p.dq_acc = (float*)((char*)workspace + round256((size_t)rows * sizeof(float)));
-    auto st3 = [](const fa_strides* s, int64_t S, int64_t& sb, int64_t& sh, int64_t& ss, int64_t Hn, int64_t dd) {
-        sb = s ? s->strideB : Hn * S * dd; sh = s ? s->strideH : S * dd; ss = s ? s->strideS : dd;
-    };
-    st3(sQ, Sq, p.qB, p.qH, p.qS, H, d);    st3(sK, Sk, p.kB, p.kH, p.kS, Hkv, d);  st3(sV, Sk, p.vB, p.vH, p.vS, Hkv, d);
-    st3(sO, Sq, p.oB, p.oH, p.oS, H, d);    st3(sdO, Sq, p.doB, p.doH, p.doS, H, d);
-    st3(sdQ, Sq, p.dqB, p.dqH, p.dqS, H, d); st3(sdK, Sk, p.dkB, p.dkH, p.dkS, Hkv, d); st3(sdV, Sk, p.dvB, p.dvH, p.dvS, Hkv, d);
+    resolve_strides(sQ, H, Sq, d, p.qB, p.qH, p.qS);       resolve_strides(sO, H, Sq, d, p.oB, p.oH, p.oS);
+    resolve_strides(sdO, H, Sq, d, p.doB, p.doH, p.doS);   resolve_strides(sdQ, H, Sq, d, p.dqB, p.dqH, p.dqS);
+    resolve_strides(sK, Hkv, Sk, d, p.kB, p.kH, p.kS);     resolve_strides(sV, Hkv, Sk, d, p.vB, p.vH, p.vS);
+    resolve_strides(sdK, Hkv, Sk, d, p.dkB, p.dkH, p.dkS); resolve_strides(sdV, Hkv, Sk, d, p.dvB, p.dvH, p.dvS);
     p.H = H; p.Sq = Sq; p.Sk = Sk;
     p.heads = (int)heads;
     p.Hkv = Hkv; p.group = H / Hkv;

@@ -11,52 +11,10 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
+from decode_check import CAP, DEV, assert_close, randn, reference  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-CAP = fa.FA_DECODE_MAX_SPLITS
-TILE = 128   # fa_decode_plan.kv_block_rows
-
-
-def randn(shape, seed, dtype=torch.bfloat16):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g).to(dtype)
-
-
-def visible(L, Sq, causal):
-    """bool [Sq, L]: row i sees key k.  Bottom-right aligned: the Sq rows are the last rows of the L keys; at least key 0"""
-    k = torch.arange(L)[None, :]
-    if not causal:
-        return torch.ones(Sq, L, dtype=torch.bool) & (k >= 0)
-    last = (L - Sq + torch.arange(Sq)).clamp(min=0)[:, None]
-    return k <= last
-
-
-def reference(Q, K, V, lens, causal, scale=None):
-    """float64 explicit softmax over the visible keys of each sequence (CPU tensors): O [B, H, Sq, d], LSE [B, H, Sq]"""
-    B, H, Sq, d = Q.shape
-    G = H // K.shape[1]
-    scale = scale or 1.0 / d ** 0.5
-    O = torch.zeros(B, H, Sq, d, dtype=torch.float64)
-    lse = torch.zeros(B, H, Sq, dtype=torch.float64)
-    for b in range(B):
-        L = K.shape[2] if lens is None else int(lens[b])
-        k = K[b, :, :L].double().repeat_interleave(G, 0)
-        v = V[b, :, :L].double().repeat_interleave(G, 0)
-        S = (Q[b].double() @ k.transpose(-1, -2)) * scale
-        S = S.masked_fill(~visible(L, Sq, causal)[None], float("-inf"))
-        lse[b] = torch.logsumexp(S, -1)
-        O[b] = torch.softmax(S, -1) @ v
-    return O, lse
-
-
-def assert_close(O, lse, refO, refL, what=""):
-    O, lse = O.double().cpu(), lse.double().cpu()
-    assert torch.isfinite(O).all() and torch.isfinite(lse).all(), what
-    err, tol = (O - refO).abs(), 1e-3 + 1e-3 * refO.abs()
-    print(f"{what}: worst O error / tolerance {(err / tol).max().item():.3f}, worst LSE error {(lse - refL).abs().max().item():.2e}")
-    assert (err <= tol).all(), f"{what}: {int((err > tol).sum())} elements outside 1e-3 + 1e-3|ref|, worst ratio {(err / tol).max().item():.3f}"
-    lerr = (lse - refL).abs()
-    assert (lerr <= 2e-4 + 2e-6 * refL.abs()).all(), f"{what}: LSE error {lerr.max().item():.3e}"
+BF16 = torch.bfloat16
 
 
 # (B, H, Hkv, Sq, capacity, kv_lens, causal)
@@ -77,7 +35,7 @@ SWEEP = [
 @functools.lru_cache(maxsize=2)
 def sweep_case(i, d):
     B, H, Hkv, Sq, cap, lens, causal = SWEEP[i]
-    Q, K, V = randn((B, H, Sq, d), 100 + i), randn((B, Hkv, cap, d), 200 + i), randn((B, Hkv, cap, d), 300 + i)
+    Q, K, V = randn((B, H, Sq, d), 100 + i, BF16), randn((B, Hkv, cap, d), 200 + i, BF16), randn((B, Hkv, cap, d), 300 + i, BF16)
     refO, refL = reference(Q, K, V, lens, causal)
     lens_d = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
     return Q.to(DEV), K.to(DEV), V.to(DEV), lens_d, refO, refL
@@ -104,7 +62,7 @@ def test_sweep_against_float64(i, d, splits):
 def test_agrees_with_the_prefill_path_where_the_two_mean_the_same(d):
     """no mask, kv_lens = None: flash_attention() computes the same function (fp16 weights); both within the tolerance of float64"""
     B, H, Hkv, Sq, Sk = 2, 16, 4, 4, 2048
-    Q, K, V = randn((B, H, Sq, d), 1), randn((B, Hkv, Sk, d), 2), randn((B, Hkv, Sk, d), 3)
+    Q, K, V = randn((B, H, Sq, d), 1, BF16), randn((B, Hkv, Sk, d), 2, BF16), randn((B, Hkv, Sk, d), 3, BF16)
     refO, refL = reference(Q, K, V, None, False)
     Qd, Kd, Vd = Q.to(DEV), K.to(DEV), V.to(DEV)
     O, lse = fa.flash_attention_decode(Qd, Kd, Vd, out_dtype=torch.float32, return_lse=True)
@@ -119,7 +77,7 @@ def test_agrees_with_the_prefill_path_where_the_two_mean_the_same(d):
 def test_garbage_beyond_the_length_never_enters_the_result(d, causal):
     B, H, Hkv, Sq, cap = 3, 8, 2, 4, 1024
     lens = [1, 200, 1000]
-    Q, K, V = randn((B, H, Sq, d), 11), randn((B, Hkv, cap, d), 12), randn((B, Hkv, cap, d), 13)
+    Q, K, V = randn((B, H, Sq, d), 11, BF16), randn((B, Hkv, cap, d), 12, BF16), randn((B, Hkv, cap, d), 13, BF16)
     Kz, Vz, Kg, Vg = K.clone(), V.clone(), K.clone(), V.clone()
     for b, L in enumerate(lens):
         Kz[b, :, L:], Vz[b, :, L:] = 0, 0
@@ -152,8 +110,8 @@ def test_garbage_beyond_the_length_never_enters_the_result(d, causal):
 @pytest.mark.parametrize("d", [64, 128])
 def test_strided_views_of_model_layout_buffers(d):
     B, H, Hkv, Sq, cap = 2, 16, 4, 3, 777
-    q = randn((B, Sq, H * d), 21).to(DEV)
-    kc, vc = randn((B, cap, Hkv * d), 22).to(DEV), randn((B, cap, Hkv * d), 23).to(DEV)
+    q = randn((B, Sq, H * d), 21, BF16).to(DEV)
+    kc, vc = randn((B, cap, Hkv * d), 22, BF16).to(DEV), randn((B, cap, Hkv * d), 23, BF16).to(DEV)
     lens_d = torch.tensor([300, 777], dtype=torch.int32, device=DEV)
     view = lambda t, h: t.view(B, t.shape[1], h, d).transpose(1, 2)
     out = torch.zeros((B, Sq, H * d), dtype=torch.float32, device=DEV)
@@ -169,7 +127,7 @@ def test_strided_views_of_model_layout_buffers(d):
 
 def test_deterministic_and_the_lse_request_leaves_o_alone():
     B, H, Hkv, Sq, cap, d = 4, 32, 8, 2, 8192, 128
-    Q, K, V = randn((B, H, Sq, d), 31).to(DEV), randn((B, Hkv, cap, d), 32).to(DEV), randn((B, Hkv, cap, d), 33).to(DEV)
+    Q, K, V = randn((B, H, Sq, d), 31, BF16).to(DEV), randn((B, Hkv, cap, d), 32, BF16).to(DEV), randn((B, Hkv, cap, d), 33, BF16).to(DEV)
     lens_d = torch.tensor([8192, 100, 4097, 6000], dtype=torch.int32, device=DEV)
     for splits in (0, 1, 7):
         a = fa.flash_attention_decode(Q, K, V, lens_d, is_causal=True, num_splits=splits, out_dtype=torch.float32)
@@ -182,7 +140,7 @@ def test_deterministic_and_the_lse_request_leaves_o_alone():
 def test_graph_replay_reads_the_lengths_of_the_moment():
     """one captured call (a linear chain: split kernel, combine kernel); kv_lens and the cache change IN PLACE between replays"""
     B, H, Hkv, Sq, cap, d = 3, 16, 4, 1, 4096, 128
-    Q, K, V = randn((B, H, Sq, d), 41).to(DEV), randn((B, Hkv, cap, d), 42).to(DEV), randn((B, Hkv, cap, d), 43).to(DEV)
+    Q, K, V = randn((B, H, Sq, d), 41, BF16).to(DEV), randn((B, Hkv, cap, d), 42, BF16).to(DEV), randn((B, Hkv, cap, d), 43, BF16).to(DEV)
     lens_d = torch.tensor([10, 1000, 4000], dtype=torch.int32, device=DEV)
     plan = fa.decode_plan(B, H, Hkv, Sq, cap, d, fa.FA_DTYPE_F32)
     assert plan["num_splits"] > 1
@@ -201,7 +159,7 @@ def test_graph_replay_reads_the_lengths_of_the_moment():
     assert torch.equal(O, first)
     # one decode step later: a new row appended to every sequence's cache, the lengths advanced, all in place
     for b, L in enumerate([10, 1000, 4000]):
-        K[b, :, L], V[b, :, L] = randn((Hkv, d), 44 + b).to(DEV), randn((Hkv, d), 47 + b).to(DEV)
+        K[b, :, L], V[b, :, L] = randn((Hkv, d), 44 + b, BF16).to(DEV), randn((Hkv, d), 47 + b, BF16).to(DEV)
     lens_d += 1
     lens_d[0] = 3000
     graph.replay()
@@ -216,7 +174,7 @@ def test_decode_on_a_side_stream_keeps_its_workspace():
     """stream=: the kernels run on a side stream while the current stream goes on allocating blocks of the workspace's size and
     overwriting them; the workspace released at return must not be one of them while the kernels still use it"""
     B, H, Hkv, Sq, cap, d = 8, 32, 8, 4, 16384, 128
-    Q, K, V = randn((B, H, Sq, d), 51).to(DEV), randn((B, Hkv, cap, d), 52).to(DEV), randn((B, Hkv, cap, d), 53).to(DEV)
+    Q, K, V = randn((B, H, Sq, d), 51, BF16).to(DEV), randn((B, Hkv, cap, d), 52, BF16).to(DEV), randn((B, Hkv, cap, d), 53, BF16).to(DEV)
     ns = fa.decode_plan(B, H, Hkv, Sq, cap, d, fa.FA_DTYPE_F32)["num_splits"]
     n = fa.decode_workspace_size(B, H, Sq, d, ns)
     assert ns > 1 and n > 0

@@ -1,6 +1,6 @@
 """GPU tests of flash_attention_decode at its edges: lengths out of range (clamped on the device into [1, capacity]), custom scales and
 a sharp softmax, splits whose partial log-sum-exps differ by hundreds, |V| = 1e30, and the largest head extent the ABI accepts
-(one K/V head just under 2^31 bytes).  Reference, mask and the element-wise check are those of tests/test_decode.py."""
+(one K/V head just under 2^31 bytes).  Reference, mask and the element-wise check are those of tests/decode_check.py."""
 import pytest
 
 import __graft_entry__ as entry
@@ -8,9 +8,10 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from test_decode import CAP, DEV, TILE, assert_close, randn, reference, visible  # noqa: E402
+from decode_check import CAP, DEV, TILE, assert_close, randn, reference, visible  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+BF16 = torch.bfloat16
 
 
 def scores_max(Q, K, lens, causal, scale):
@@ -48,7 +49,7 @@ def test_lengths_out_of_range_are_clamped_on_the_device(d, causal):
     raw = [0, -1, -2 ** 31, cap + 1, 2 ** 31 - 1, 5, cap, 300]
     clamped = [min(max(x, 1), cap) for x in raw]
     assert clamped == [1, 1, 1, cap, cap, 5, cap, 300]
-    Q, K, V = randn((B, H, Sq, d), 71), randn((B, Hkv, cap, d), 72), randn((B, Hkv, cap, d), 73)
+    Q, K, V = randn((B, H, Sq, d), 71, BF16), randn((B, Hkv, cap, d), 72, BF16), randn((B, Hkv, cap, d), 73, BF16)
     refO, refL = reference(Q, K, V, clamped, causal)
     Qd, Kd, Vd = Q.to(DEV), K.to(DEV), V.to(DEV)
     raw_d, clamped_d = (torch.tensor(x, dtype=torch.int32, device=DEV) for x in (raw, clamped))
@@ -71,7 +72,7 @@ def test_custom_scale_and_sharp_softmax(d, kind):
     """(scale, factor on Q and K): 0.02, 3/sqrt(d), 1 with the scores kept O(1); Q and K times 3 and times 12"""
     scale, mul = SCALES[kind](d)
     B, H, Hkv, Sq, cap, lens = 2, 8, 2, 4, 3000, [777, 3000]
-    Q, K, V = (randn((B, H, Sq, d), 81) * mul).bfloat16(), (randn((B, Hkv, cap, d), 82) * mul).bfloat16(), randn((B, Hkv, cap, d), 83)
+    Q, K, V = (randn((B, H, Sq, d), 81, BF16) * mul).bfloat16(), (randn((B, Hkv, cap, d), 82, BF16) * mul).bfloat16(), randn((B, Hkv, cap, d), 83, BF16)
     lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
     for splits in (0, 1, 5):
         O, lse = fa.flash_attention_decode(Q.to(DEV), K.to(DEV), V.to(DEV), lens_d, scale=scale, is_causal=True, out_dtype=torch.float32,
@@ -88,7 +89,7 @@ def test_one_tile_hundreds_above_every_other(d, where):
     B, H, Hkv, Sq, tiles = 2, 8, 2, 2, 14
     cap = tiles * TILE
     hot = {"first": 0, "middle": 6, "last": tiles - 1}[where]
-    Q, K, V = randn((B, H, Sq, d), 91).float() + 3.0, randn((B, Hkv, cap, d), 92).float(), randn((B, Hkv, cap, d), 93)
+    Q, K, V = randn((B, H, Sq, d), 91, BF16).float() + 3.0, randn((B, Hkv, cap, d), 92, BF16).float(), randn((B, Hkv, cap, d), 93, BF16)
     K[:, :, hot * TILE:(hot + 1) * TILE] += 10.0
     Q, K = Q.bfloat16(), K.bfloat16()
     scale = 1.0 / d ** 0.5
@@ -111,7 +112,7 @@ def test_v_of_1e30_on_the_keys_that_carry_weight(d):
     B, H, Hkv, Sq, cap, lens = 2, 8, 2, 3, 1024, [100, 1000]
     g = torch.Generator().manual_seed(95)
     sign = torch.where(torch.arange(d) % 2 == 0, 1.0, -1.0)
-    Q, K = randn((B, H, Sq, d), 96), randn((B, Hkv, cap, d), 97)
+    Q, K = randn((B, H, Sq, d), 96, BF16), randn((B, Hkv, cap, d), 97, BF16)
     V = ((0.5 + torch.rand((B, Hkv, cap, d), generator=g)) * 1e30 * sign).bfloat16()
     for b, L in enumerate(lens):
         K[b, :, L::2], K[b, :, L + 1::2] = float("nan"), float("inf")

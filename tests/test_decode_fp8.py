@@ -17,79 +17,16 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
+from decode_check import CAP, DEV, F8, assert_close, dequantise, gather, max_pages_of, paged_layout, quantise, randn, reference  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-CAP = fa.FA_DECODE_MAX_SPLITS
-F8 = torch.float8_e4m3fn
+F32 = torch.float32
 SPLITS = (0, 1, 2, 3, CAP)
 SHAPES = [(1, 1), (1, 4), (5, 8), (16, 16), (2, 2)]      # (Sq, G)
 
 
-def randn(shape, seed, dtype=torch.float32):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g).to(dtype)
-
-
-def quantise(x):
-    """x fp32 [*, Hkv, rows, d] (K/V heads in dimension 1) -> (bytes uint8 of the same shape, descale fp32 [Hkv] = amax / 448).
-    torch's cast gives NaN beyond 448, not saturation: clamp, and check"""
-    ds = (x.abs().amax(dim=(0, 2, 3)) / 448.0).float()
-    b = (x / ds[None, :, None, None]).clamp(-448, 448).to(F8).view(torch.uint8)
-    assert ((b & 0x7F) != 0x7F).all(), "NaN among the quantised bytes"
-    return b, ds
-
-
-def dequantise(b, ds):
-    return b.view(F8).float().double() * ds.double()[None, :, None, None]
-
-
 def f8(t):
     return t.view(F8)
-
-
-def visible(L, Sq, causal):
-    """bool [Sq, L]: row i sees key k.  Bottom-right aligned: the Sq rows are the last rows of the L keys; at least key 0"""
-    k = torch.arange(L)[None, :]
-    if not causal:
-        return torch.ones(Sq, L, dtype=torch.bool) & (k >= 0)
-    last = (L - Sq + torch.arange(Sq)).clamp(min=0)[:, None]
-    return k <= last
-
-
-def reference(Q, K, V, lens, causal, scale=None):
-    """float64 explicit softmax over the visible keys of each sequence (CPU; K, V float64 [B, Hkv, capacity, d], dequantised):
-    O [B, H, Sq, d], LSE [B, H, Sq]"""
-    B, H, Sq, d = Q.shape
-    G = H // K.shape[1]
-    scale = scale or 1.0 / d ** 0.5
-    O = torch.zeros(B, H, Sq, d, dtype=torch.float64)
-    lse = torch.zeros(B, H, Sq, dtype=torch.float64)
-    for b in range(B):
-        L = K.shape[2] if lens is None else int(lens[b])
-        k = K[b, :, :L].repeat_interleave(G, 0)
-        v = V[b, :, :L].repeat_interleave(G, 0)
-        S = (Q[b].double() @ k.transpose(-1, -2)) * scale
-        S = S.masked_fill(~visible(L, Sq, causal)[None], float("-inf"))
-        lse[b] = torch.logsumexp(S, -1)
-        O[b] = torch.softmax(S, -1) @ v
-    return O, lse
-
-
-def assert_close(O, lse, refO, refL, what=""):
-    O, lse = O.double().cpu(), lse.double().cpu()
-    assert torch.isfinite(O).all() and torch.isfinite(lse).all(), what
-    err, tol = (O - refO).abs(), 1e-3 + 1e-3 * refO.abs()
-    lerr, ltol = (lse - refL).abs(), 2e-4 + 2e-6 * refL.abs()
-    print(f"{what}: worst O error / tolerance {(err / tol).max().item():.3f}, worst LSE error / tolerance {(lerr / ltol).max().item():.3f}")
-    assert (err <= tol).all(), f"{what}: {int((err > tol).sum())} elements outside 1e-3 + 1e-3|ref|, worst ratio {(err / tol).max().item():.3f}"
-    assert (lerr <= ltol).all(), f"{what}: LSE error {lerr.max().item():.3e}"
-
-
-def gather(pool, table):
-    """[P, Hkv, page, d] pool, [B, max_pages] table (in range) -> the contiguous cache [B, Hkv, max_pages * page, d]"""
-    B, n = table.shape
-    P, Hkv, page, d = pool.shape
-    return pool[table.long()].permute(0, 2, 1, 3, 4).reshape(B, Hkv, n * page, d).contiguous()
 
 
 # ---- 1. contiguous sweep ----
@@ -100,8 +37,8 @@ LENS = [1, 15, 16, 17, 31, 32, 33, 127, 128, 129, 317, 320]
 def contiguous_case(d, Hkv=2, cap=320):
     """one sequence per length; returns CPU bytes and descales, their dequantised float64 values, and the device tensors"""
     B = len(LENS)
-    K8, kd = quantise(randn((B, Hkv, cap, d), 100 + d))
-    V8, vd = quantise(randn((B, Hkv, cap, d), 200 + d))
+    K8, kd = quantise(randn((B, Hkv, cap, d), 100 + d, F32))
+    V8, vd = quantise(randn((B, Hkv, cap, d), 200 + d, F32))
     assert len({float(x) for x in (*kd, *vd)}) == 4         # different for K and V and for the two heads
     dev = tuple(t.to(DEV) for t in (K8, V8, kd, vd, torch.tensor(LENS, dtype=torch.int32)))
     return K8, V8, kd, vd, dequantise(K8, kd), dequantise(V8, vd), dev
@@ -133,26 +70,12 @@ def test_contiguous_sweep_against_float64(d, Sq, G):
 
 
 # ---- 2. paged sweep ----
-def max_pages_of(page):
-    return max(3, 320 // page)     # capacities 320, 320, 384, 768: more than one tile, more than two pages
-
-
-def boundary_lengths(page, cap):
-    """around every boundary: the page, the 128-key tile, the capacity"""
-    return sorted({max(1, min(L, cap)) for L in (1, page - 1, page, page + 1, 127, 128, 129, cap - 3, cap)})
-
-
 @functools.lru_cache(maxsize=2)
-def paged_case(page, d, Hkv=2, spare=7):
+def paged_case(page, d, Hkv=2):
     """pools with more pages than any sequence uses, a random permutation as the table, one sequence per boundary length"""
-    n = max_pages_of(page)
-    lens = boundary_lengths(page, n * page)
-    B = len(lens)
-    P = B * n + spare
-    Kp, kd = quantise(randn((P, Hkv, page, d), 1000 + page + d))
-    Vp, vd = quantise(randn((P, Hkv, page, d), 2000 + page + d))
-    g = torch.Generator().manual_seed(3000 + page + d)
-    table = torch.randperm(P, generator=g)[:B * n].reshape(B, n).to(torch.int32)
+    P, table, lens = paged_layout(page, d)
+    Kp, kd = quantise(randn((P, Hkv, page, d), 1000 + page + d, F32))
+    Vp, vd = quantise(randn((P, Hkv, page, d), 2000 + page + d, F32))
     dev = tuple(t.to(DEV) for t in (Kp, Vp, kd, vd, table, torch.tensor(lens, dtype=torch.int32)))
     Kf, Vf = dequantise(gather(Kp, table), kd), dequantise(gather(Vp, table), vd)
     return lens, Kf, Vf, dev
@@ -240,8 +163,8 @@ def test_descales_are_applied_per_head(d):
 def test_graph_replay_reads_the_descales_and_the_lengths_of_the_moment(d, paged):
     B, Hkv, G, Sq, page, n = 2, 2, 4, 1, 128, 32
     cap, H = n * page, G * Hkv
-    K8, kd = quantise(randn((B, Hkv, cap, d), 500 + d))
-    V8, vd = quantise(randn((B, Hkv, cap, d), 501 + d))
+    K8, kd = quantise(randn((B, Hkv, cap, d), 500 + d, F32))
+    V8, vd = quantise(randn((B, Hkv, cap, d), 501 + d, F32))
     Q = randn((B, H, Sq, d), 502, torch.bfloat16)
     lens = [1000, 3 * page]
     Kd, Vd, kdd, vdd, Qd = (t.to(DEV) for t in (K8, V8, kd, vd, Q))
@@ -320,8 +243,8 @@ def test_poison_in_unused_rows_and_pages_and_bad_unused_entries_never_enter_the_
     lens = [1, page + 1, cap - page - 3, cap - 3]      # a last page half full; whole pages unused behind it
     B = len(lens)
     P = B * n + 3
-    Kp, kd = quantise(randn((P, Hkv, page, d), 61 + page))
-    Vp, vd = quantise(randn((P, Hkv, page, d), 62 + page))
+    Kp, kd = quantise(randn((P, Hkv, page, d), 61 + page, F32))
+    Vp, vd = quantise(randn((P, Hkv, page, d), 62 + page, F32))
     g = torch.Generator().manual_seed(63 + page)
     table = (1 + torch.randperm(B * n, generator=g)).reshape(B, n).to(torch.int32)     # pages 1 .. B n; 0, P - 2, P - 1 are named by nobody
     used = [-(-L // page) for L in lens]
@@ -363,8 +286,8 @@ def test_poison_in_unused_rows_and_pages_and_bad_unused_entries_never_enter_the_
 @pytest.mark.parametrize("d", [64, 128])
 def test_sequence_major_cache_view_and_a_row_stride_larger_than_d(d):
     B, Hkv, G, Sq, cap = 3, 2, 4, 3, 333
-    K8, kd = quantise(randn((B, Hkv, cap, d), 800))
-    V8, vd = quantise(randn((B, Hkv, cap, d), 801))
+    K8, kd = quantise(randn((B, Hkv, cap, d), 800, F32))
+    V8, vd = quantise(randn((B, Hkv, cap, d), 801, F32))
     lens = [cap, 130, 17]
     Q = randn((B, G * Hkv, Sq, d), 802, torch.bfloat16)
     Kd, Vd, kdd, vdd, Qd = (t.to(DEV) for t in (K8, V8, kd, vd, Q))
@@ -390,8 +313,8 @@ def test_sequence_major_cache_view_and_a_row_stride_larger_than_d(d):
 def test_page_major_pool_view_a_wider_table_and_a_wide_row_stride(page, d):
     Hkv, G, Sq, n = 2, 4, 3, max_pages_of(page)
     B, P = 3, 3 * n + 5
-    Kp, kd = quantise(randn((P, Hkv, page, d), 81))
-    Vp, vd = quantise(randn((P, Hkv, page, d), 82))
+    Kp, kd = quantise(randn((P, Hkv, page, d), 81, F32))
+    Vp, vd = quantise(randn((P, Hkv, page, d), 82, F32))
     g = torch.Generator().manual_seed(83)
     wide = torch.full((B, n + 6), -7, dtype=torch.int32)
     wide[:, 2:2 + n] = torch.randperm(P, generator=g)[:B * n].reshape(B, n).to(torch.int32)
@@ -444,8 +367,8 @@ def test_a_pool_above_two_to_the_32_bytes(d):
     Q = randn((1, G * Hkv, Sq, d), 101, torch.bfloat16)
     data = {}
     for j, pg in enumerate(pages + aliases):
-        k8, _ = quantise(randn((1, Hkv, page, d), 110 + j))
-        v8, _ = quantise(randn((1, Hkv, page, d), 130 + j))
+        k8, _ = quantise(randn((1, Hkv, page, d), 110 + j, F32))
+        v8, _ = quantise(randn((1, Hkv, page, d), 130 + j, F32))
         data[pg] = (k8[0], v8[0])
     kd, vd = torch.tensor([4.5 / 448]), torch.tensor([4.25 / 448])
     data[P - 1][0][0, 40:44] = heavy_keys(Q, kd[0])            # the mass: on page P - 1, the fourth of the sequence
@@ -472,8 +395,8 @@ def test_a_head_extent_between_two_to_the_30_and_two_to_the_31_bytes(d):
     """1536 keys in rows 2^20 bytes apart: (1536 + 192) x 2^20 bytes, which the bf16 call refuses and a byte count doubled in the
     kernel would misplace.  The mass sits on the last keys, beyond byte 2^30"""
     Hkv, G, Sq, cap, stride = 1, 4, 2, 1536, 1 << 20
-    K8, _ = quantise(randn((1, Hkv, cap, d), 900))
-    V8, _ = quantise(randn((1, Hkv, cap, d), 901))
+    K8, _ = quantise(randn((1, Hkv, cap, d), 900, F32))
+    V8, _ = quantise(randn((1, Hkv, cap, d), 901, F32))
     kd, vd = torch.tensor([4.5 / 448]), torch.tensor([4.25 / 448])
     Q = randn((1, G * Hkv, Sq, d), 902, torch.bfloat16)
     K8[0, 0, cap - 4:] = heavy_keys(Q, kd[0])

@@ -14,82 +14,19 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
+from decode_check import CAP, DEV, assert_close, gather, max_pages_of, paged_layout, randn, reference  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-CAP = fa.FA_DECODE_MAX_SPLITS
+BF16 = torch.bfloat16
 PAGES = [16, 32, 128, 256]
 NAN = float("nan")
 
 
-def randn(shape, seed, dtype=torch.bfloat16):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g).to(dtype)
-
-
-def visible(L, Sq, causal):
-    """bool [Sq, L]: row i sees key k.  Bottom-right aligned: the Sq rows are the last rows of the L keys; at least key 0"""
-    k = torch.arange(L)[None, :]
-    if not causal:
-        return torch.ones(Sq, L, dtype=torch.bool) & (k >= 0)
-    last = (L - Sq + torch.arange(Sq)).clamp(min=0)[:, None]
-    return k <= last
-
-
-def reference(Q, K, V, lens, causal, scale=None):
-    """float64 explicit softmax over the visible keys of each sequence (CPU tensors; K, V gathered [B, Hkv, capacity, d]):
-    O [B, H, Sq, d], LSE [B, H, Sq]"""
-    B, H, Sq, d = Q.shape
-    G = H // K.shape[1]
-    scale = scale or 1.0 / d ** 0.5
-    O = torch.zeros(B, H, Sq, d, dtype=torch.float64)
-    lse = torch.zeros(B, H, Sq, dtype=torch.float64)
-    for b in range(B):
-        L = K.shape[2] if lens is None else int(lens[b])
-        k = K[b, :, :L].double().repeat_interleave(G, 0)
-        v = V[b, :, :L].double().repeat_interleave(G, 0)
-        S = (Q[b].double() @ k.transpose(-1, -2)) * scale
-        S = S.masked_fill(~visible(L, Sq, causal)[None], float("-inf"))
-        lse[b] = torch.logsumexp(S, -1)
-        O[b] = torch.softmax(S, -1) @ v
-    return O, lse
-
-
-def assert_close(O, lse, refO, refL, what=""):
-    O, lse = O.double().cpu(), lse.double().cpu()
-    assert torch.isfinite(O).all() and torch.isfinite(lse).all(), what
-    err, tol = (O - refO).abs(), 1e-3 + 1e-3 * refO.abs()
-    lerr = (lse - refL).abs()
-    print(f"{what}: worst O error / tolerance {(err / tol).max().item():.3f}, worst LSE error {lerr.max().item():.2e}")
-    assert (err <= tol).all(), f"{what}: {int((err > tol).sum())} elements outside 1e-3 + 1e-3|ref|, worst ratio {(err / tol).max().item():.3f}"
-    assert (lerr <= 2e-4 + 2e-6 * refL.abs()).all(), f"{what}: LSE error {lerr.max().item():.3e}"
-
-
-def gather(pool, table):
-    """[P, Hkv, page, d] pool, [B, max_pages] table (in range) -> the contiguous cache [B, Hkv, max_pages * page, d]"""
-    B, n = table.shape
-    P, Hkv, page, d = pool.shape
-    return pool[table.long()].permute(0, 2, 1, 3, 4).reshape(B, Hkv, n * page, d).contiguous()
-
-
-def boundary_lengths(page, cap):
-    """around every boundary: the page, the 128-key tile, the capacity"""
-    return sorted({max(1, min(L, cap)) for L in (1, page - 1, page, page + 1, 127, 128, 129, cap - 3, cap)})
-
-
-def max_pages_of(page):
-    return max(3, 320 // page)     # capacities 320, 320, 384, 768: more than one tile, more than two pages
-
-
 @functools.lru_cache(maxsize=2)
-def paged_case(page, d, Hkv=2, spare=7):
+def paged_case(page, d, Hkv=2):
     """CPU pools with more pages than any sequence uses, a random permutation as the table, one sequence per boundary length"""
-    n = max_pages_of(page)
-    lens = boundary_lengths(page, n * page)
-    B = len(lens)
-    P = B * n + spare
-    Kp, Vp = randn((P, Hkv, page, d), 1000 + page + d), randn((P, Hkv, page, d), 2000 + page + d)
-    g = torch.Generator().manual_seed(3000 + page + d)
-    table = torch.randperm(P, generator=g)[:B * n].reshape(B, n).to(torch.int32)
+    P, table, lens = paged_layout(page, d)
+    Kp, Vp = randn((P, Hkv, page, d), 1000 + page + d, BF16), randn((P, Hkv, page, d), 2000 + page + d, BF16)
     return Kp, Vp, table, lens
 
 
@@ -108,7 +45,7 @@ def test_sweep_against_float64(page, d, Sq, G):
     Kd, Vd, td, ld = device_case(page, d)
     B, Hkv = len(lens), Kp.shape[1]
     H = G * Hkv
-    Q = randn((B, H, Sq, d), 4000 + Sq + G)
+    Q = randn((B, H, Sq, d), 4000 + Sq + G, BF16)
     Kg, Vg = gather(Kp, table), gather(Vp, table)
     Qd = Q.to(DEV)
     for causal in (False, True):
@@ -137,7 +74,7 @@ def test_bitwise_equal_to_the_contiguous_path_on_a_gathered_copy(page, d):
     B, Hkv = td.shape[0], Kd.shape[1]
     Kg, Vg = gather(Kd, td), gather(Vd, td)
     for Sq, G in ((1, 4), (5, 8)):
-        Q = randn((B, G * Hkv, Sq, d), 5000 + Sq).to(DEV)
+        Q = randn((B, G * Hkv, Sq, d), 5000 + Sq, BF16).to(DEV)
         for causal in (False, True):
             for splits in (0, 1, 2, 3, CAP):
                 kw = dict(is_causal=causal, out_dtype=torch.float32, num_splits=splits, return_lse=True)
@@ -152,8 +89,8 @@ def test_bitwise_equal_to_the_contiguous_path_on_a_gathered_copy(page, d):
 def test_identity_table_over_a_contiguous_cache_viewed_as_pages(page, d):
     Hkv, G, Sq, n = 3, 4, 2, max_pages_of(page) + 2
     cap = n * page
-    K, V = randn((1, Hkv, cap, d), 51).to(DEV), randn((1, Hkv, cap, d), 52).to(DEV)
-    Q = randn((1, G * Hkv, Sq, d), 53).to(DEV)
+    K, V = randn((1, Hkv, cap, d), 51, BF16).to(DEV), randn((1, Hkv, cap, d), 52, BF16).to(DEV)
+    Q = randn((1, G * Hkv, Sq, d), 53, BF16).to(DEV)
     pool = lambda t: t[0].view(Hkv, n, page, d).transpose(0, 1)      # [n, Hkv, page, d]: no copy
     assert pool(K).data_ptr() == K.data_ptr() and not pool(K).is_contiguous()
     table = torch.arange(n, dtype=torch.int32, device=DEV)[None]
@@ -180,7 +117,7 @@ def poison_case(page, d):
     lens = [1, page + 1, cap - page - 3, cap - 3]      # a last page half full; whole pages unused behind it
     B = len(lens)
     P = B * n + 3
-    Kp, Vp = randn((P, Hkv, page, d), 61 + page), randn((P, Hkv, page, d), 62 + page)
+    Kp, Vp = randn((P, Hkv, page, d), 61 + page, BF16), randn((P, Hkv, page, d), 62 + page, BF16)
     zero_page = P - 2
     Kp[zero_page], Vp[zero_page] = 0, 0
     g = torch.Generator().manual_seed(63 + page)
@@ -191,7 +128,7 @@ def poison_case(page, d):
         Kp[last, :, L - (used[b] - 1) * page:], Vp[last, :, L - (used[b] - 1) * page:] = 0, 0
         table[b, used[b]:] = zero_page
     Kp[0], Vp[0], Kp[P - 1], Vp[P - 1] = NAN, NAN, NAN, NAN
-    Q = randn((B, G * Hkv, Sq, d), 64).to(DEV)
+    Q = randn((B, G * Hkv, Sq, d), 64, BF16).to(DEV)
     Kd, Vd, td, ld = Kp.to(DEV), Vp.to(DEV), table.to(DEV), torch.tensor(lens, dtype=torch.int32, device=DEV)
     clean = {}
     for causal in (False, True):
@@ -257,12 +194,12 @@ def test_out_of_range_unused_entries_are_never_followed(page, d):
 def test_sequences_that_share_their_first_pages(page, d):
     Hkv, G, Sq, n, shared = 2, 4, 2, max_pages_of(page) + 1, 2
     P = 3 * n
-    Kp, Vp = randn((P, Hkv, page, d), 71), randn((P, Hkv, page, d), 72)
+    Kp, Vp = randn((P, Hkv, page, d), 71, BF16), randn((P, Hkv, page, d), 72, BF16)
     table = torch.stack([torch.arange(n), torch.arange(n) + n, torch.arange(n) + 2 * n]).to(torch.int32)
     table[1, :shared] = table[0, :shared]
     table[2, :shared + 1] = table[0, :shared + 1]
     lens = [n * page - 1, shared * page + 3, shared * page]       # the third sequence is its shared prefix and nothing else
-    Q = randn((3, G * Hkv, Sq, d), 73)
+    Q = randn((3, G * Hkv, Sq, d), 73, BF16)
     refO, refL = reference(Q, gather(Kp, table), gather(Vp, table), lens, True)
     ld = torch.tensor(lens, dtype=torch.int32, device=DEV)
     for splits in (0, 3):
@@ -278,7 +215,7 @@ def test_sequences_that_share_their_first_pages(page, d):
 def test_page_major_pool_view_and_a_row_slice_of_a_wider_table(page, d):
     Hkv, G, Sq, n = 2, 4, 3, max_pages_of(page)
     B, P = 3, 3 * max_pages_of(page) + 5
-    kp, vp = randn((P, page, Hkv, d), 81).to(DEV), randn((P, page, Hkv, d), 82).to(DEV)      # [P, page, Hkv, d] storage
+    kp, vp = randn((P, page, Hkv, d), 81, BF16).to(DEV), randn((P, page, Hkv, d), 82, BF16).to(DEV)      # [P, page, Hkv, d] storage
     Kp, Vp = kp.transpose(1, 2), vp.transpose(1, 2)
     assert not Kp.is_contiguous() and Kp.shape == (P, Hkv, page, d)
     g = torch.Generator().manual_seed(83)
@@ -289,7 +226,7 @@ def test_page_major_pool_view_and_a_row_slice_of_a_wider_table(page, d):
     assert table.stride(0) == n + 6 and not table.is_contiguous()
     lens = [n * page, page + 1, n * page - page + 2]
     ld = torch.tensor(lens, dtype=torch.int32, device=DEV)
-    Q = randn((B, G * Hkv, Sq, d), 84).to(DEV)
+    Q = randn((B, G * Hkv, Sq, d), 84, BF16).to(DEV)
     O, lse = fa.flash_attention_decode_paged(Q, Kp, Vp, table, ld, is_causal=True, out_dtype=torch.float32, return_lse=True)
     Od, lsed = fa.flash_attention_decode_paged(Q, Kp.contiguous(), Vp.contiguous(), table.contiguous(), ld, is_causal=True,
                                                out_dtype=torch.float32, return_lse=True)
@@ -307,8 +244,8 @@ def test_graph_replay_reads_the_table_and_the_lengths_of_the_moment(page, d):
     page's entry is written into the table in place, the length advanced in place"""
     B, H, Hkv, Sq, n = 2, 8, 2, 1, 4096 // page
     P = B * n + 4
-    Kp, Vp = randn((P, Hkv, page, d), 91).to(DEV), randn((P, Hkv, page, d), 92).to(DEV)
-    Q = randn((B, H, Sq, d), 93).to(DEV)
+    Kp, Vp = randn((P, Hkv, page, d), 91, BF16).to(DEV), randn((P, Hkv, page, d), 92, BF16).to(DEV)
+    Q = randn((B, H, Sq, d), 93, BF16).to(DEV)
     lens = [3 * page, 1000]
     table = torch.full((B, n), P - 1, dtype=torch.int32)             # entries not yet in use name a page full of NaN
     g = torch.Generator().manual_seed(94)
@@ -355,8 +292,8 @@ def test_on_a_side_stream_keeps_its_workspace(d):
     overwriting them; the workspace released at return must not be one of them while the kernels still use it"""
     B, H, Hkv, Sq, page, n = 4, 32, 8, 4, 128, 64
     P = B * n
-    Kp, Vp = randn((P, Hkv, page, d), 95).to(DEV), randn((P, Hkv, page, d), 96).to(DEV)
-    Q = randn((B, H, Sq, d), 97).to(DEV)
+    Kp, Vp = randn((P, Hkv, page, d), 95, BF16).to(DEV), randn((P, Hkv, page, d), 96, BF16).to(DEV)
+    Q = randn((B, H, Sq, d), 97, BF16).to(DEV)
     td = torch.randperm(P, generator=torch.Generator().manual_seed(98)).reshape(B, n).to(torch.int32).to(DEV)
     ns = fa.decode_plan(B, H, Hkv, Sq, n * page, d, fa.FA_DTYPE_F32)["num_splits"]
     nbytes = fa.decode_workspace_size(B, H, Sq, d, ns)
@@ -389,9 +326,9 @@ def test_a_pool_above_four_gibibytes(d):
     pages = [5, wrap + 9, wrap - 1, P - 1, wrap, 17]
     aliases = [p - wrap for p in pages if p >= wrap]               # where a 32-bit page base would land
     assert not set(aliases) & set(pages)
-    Q = randn((1, G * Hkv, Sq, d), 101)
+    Q = randn((1, G * Hkv, Sq, d), 101, BF16)
     for j, pg in enumerate(pages + aliases):
-        Kp[pg], Vp[pg] = randn((Hkv, page, d), 110 + j).to(DEV), randn((Hkv, page, d), 130 + j).to(DEV)
+        Kp[pg], Vp[pg] = randn((Hkv, page, d), 110 + j, BF16).to(DEV), randn((Hkv, page, d), 130 + j, BF16).to(DEV)
     # the mass: on page P - 1 (the fourth of the sequence) a few keys line up with the queries
     heavy = (Q[0, :, -1].float().mean(0) * 6).to(torch.bfloat16)
     Kp[P - 1, 0, 40:44] = heavy.to(DEV)

@@ -2,8 +2,6 @@
 exists with the declared parameter list and argtypes, every invalid argument is refused with its code before anything is launched
 (fake aligned host pointers: no GPU is touched), and the binding refuses host tensors and mismatched shapes."""
 import ctypes
-import os
-import re
 
 import pytest
 
@@ -11,18 +9,11 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
+from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+
 BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
 NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
 CAP = fa.FA_DECODE_MAX_SPLITS
-
-
-def declared_parameters(name):
-    """the parameter names of `name` as include/flash_attention.h declares it"""
-    text = open(os.path.join(entry.ROOT, "include", "flash_attention.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\b(?:int|size_t)\s+" + name + r"\s*\((.*?)\)\s*;", text, flags=re.S)
-    assert m, name
-    return [re.sub(r"[\s*]+", " ", a).split()[-1] for a in m.group(1).split(",")]
 
 
 def test_the_symbol_is_exported_with_the_declared_signature():
@@ -42,8 +33,7 @@ def test_the_symbol_is_exported_with_the_declared_signature():
 
 def paged_call():
     L = fa.lib()
-    buf = (ctypes.c_char * 4096)()
-    p = (ctypes.addressof(buf) + 15) & ~15
+    buf, p = aligned_host_pointer()
     ok = dict(B=2, H=8, Hkv=2, Sq=1, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=False, dtype=BF16, o=F32, ns=1)
     none = [None] * 4
 

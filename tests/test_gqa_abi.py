@@ -3,8 +3,6 @@ with the declared signatures, an invalid K/V head count is rejected before anyth
 is touched), every other bad argument gets the code the one-K/V-head-per-query-head entry point gives it, and the Python binding
 rejects head counts that do not divide."""
 import ctypes
-import os
-import re
 
 import pytest
 
@@ -12,17 +10,10 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
+from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+
 BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
 BAD_SHAPE = -3
-
-
-def declared_parameters(name):
-    """the parameter names of `name` as include/flash_attention.h declares it"""
-    text = open(os.path.join(entry.ROOT, "include", "flash_attention.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", text, flags=re.S)
-    assert m, name
-    return [re.sub(r"[\s*]+", " ", a).split()[-1] for a in m.group(1).split(",")]
 
 
 def test_gqa_symbols_are_exported_with_the_declared_signatures():
@@ -40,11 +31,6 @@ def test_gqa_symbols_are_exported_with_the_declared_signatures():
         k = params.index("numHeadsKV")
         assert len(at) == len(params) and at[k] is ctypes.c_int and at[:k] + at[k + 1:] == list(twin.argtypes)
         assert f.restype is ctypes.c_int
-
-
-def aligned_host_pointer():
-    buf = (ctypes.c_char * 4096)()
-    return buf, (ctypes.addressof(buf) + 15) & ~15
 
 
 def forward_calls():
