@@ -16,6 +16,7 @@ entry points for that path:
 * ``flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens)`` -- the same against paged caches: pools of fixed-size
   pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.  Both also take fp8
   (``torch.float8_e4m3fn``) K/V caches under a bf16 Q, with per-K/V-head ``k_descale`` / ``v_descale``: half the bytes per token.
+  Both take ``window=W``: a sliding window, every row sees at most the last W keys up to its own position.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -47,6 +48,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_gqa", "flash_attention_backward_gqa",
            "flash_attention_decode", "flash_attention_decode_plan", "flash_attention_decode_workspace_size",
            "flash_attention_decode_paged", "flash_attention_decode_fp8", "flash_attention_decode_paged_fp8",
+           "flash_attention_decode_window", "flash_attention_decode_paged_window", "flash_attention_decode_plan_window",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -126,6 +128,12 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_decode_fp8.restype = i
         L.flash_attention_decode_paged_fp8.argtypes = [vp] * 10 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i, i] + [sp] * 4 + [vp]
         L.flash_attention_decode_paged_fp8.restype = i
+        L.flash_attention_decode_window.argtypes = [vp] * 9 + [i, i, i, i, i, i, f, b, i, i, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode_window.restype = i
+        L.flash_attention_decode_paged_window.argtypes = [vp] * 10 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_decode_paged_window.restype = i
+        L.flash_attention_decode_plan_window.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_decode_plan_window.restype = i
         L.flash_attention_decode_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_decode_plan.restype = i
         L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
@@ -397,10 +405,22 @@ def flash_attention_backward(Q, K, V, O, dO, lse, scale=None, is_causal=False, g
     return dQ, dK, dV
 
 
-def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
-    """What a flash_attention_decode call launches (fa_decode_plan as a dict); ``num_splits`` 0 = the library's choice."""
+def _window(window):
+    """``window`` of the decode fronts as the C ABI's windowSize: None and 0 = no window"""
+    window = 0 if window is None else int(window)
+    if window < 0:
+        raise ValueError("window must be None, 0 (no window) or a positive number of keys")
+    return window
+
+
+def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=0):
+    """What a flash_attention_decode call launches (fa_decode_plan as a dict); ``num_splits`` 0 = the library's choice.  ``window``
+    > 0: the call's sliding window -- the split count then follows from the window's tiles, not the capacity's."""
     p = FaDecodePlan()
-    _check(lib().flash_attention_decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    if _window(window):
+        _check(lib().flash_attention_decode_plan_window(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, _window(window), ctypes.byref(p)))
+    else:
+        _check(lib().flash_attention_decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
@@ -435,11 +455,13 @@ def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None):
 
 
 def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-            stream, k_descale, v_descale):
+            stream, k_descale, v_descale, window):
     """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
-    point (fp8: its ``_fp8`` twin), ``tables`` its tensors between kvLens and the workspace, ``geometry`` its ints between seqLenQ and
-    dHead; ``decode_plan`` / ``decode_workspace_size`` are asked about ``capacity``."""
+    point (fp8: its ``_fp8`` twin; a window: its ``_window`` twin, which takes both cache types), ``tables`` its tensors between
+    kvLens and the workspace, ``geometry`` its ints between seqLenQ and dHead; ``decode_plan`` / ``decode_workspace_size`` are asked
+    about ``capacity``."""
     import torch
+    window = _window(window)
     B, H, Sq, d = Q.shape
     Hkv = K.shape[1]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -448,7 +470,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits)["num_splits"]
+    ns = decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits, window)["num_splits"]
     need = decode_workspace_size(B, H, Sq, d, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -466,18 +488,18 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         st = [_strides(t) for t in (Q, K, V, O)]
         ptr = lambda t: t.data_ptr() if t is not None else None
         ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables))
-        if fp8:
+        if fp8 or window:
             ptrs += (ptr(k_descale), ptr(v_descale))
-        dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), symbol + "_fp8" if fp8 else symbol)
+        dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or window else (_dtype_code(Q.dtype),)
+        launch = getattr(lib(), symbol + ("_window" if window else "_fp8" if fp8 else ""))
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
-                    _dtype_code(O.dtype), ns, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+                    _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
     return (O, lse) if return_lse else O
 
 
 def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None):
     """Split-KV decode: Q ``[B, H, Sq, d]`` with 1 <= Sq <= FA_DECODE_MAX_Q new rows per sequence against a K/V cache
     ``[B, Hkv, capacity, d]`` (bf16, d = 64 or 128, Hkv dividing H; query head h reads K/V head ``h // (H // Hkv)``).
 
@@ -492,16 +514,21 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
 
     fp8 cache: K and V of ``torch.float8_e4m3fn`` under a bf16 Q, with ``k_descale`` / ``v_descale``: fp32 device tensors ``[Hkv]``
     (None = 1), read by the kernel like ``kv_lens``.  The logical cache is ``K.float() * k_descale[kvh]``, ``V.float() *
-    v_descale[kvh]``; the conversion is exact and everything else is as for bf16 (``decode_plan`` does not depend on the cache type)."""
+    v_descale[kvh]``; the conversion is exact and everything else is as for bf16 (``decode_plan`` does not depend on the cache type).
+
+    ``window``: None or 0 = none; W > 0 = a sliding window: row i sees at most the last W keys up to and including its own position,
+    ``max(limC_i - W, 0) <= k`` with ``limC_i = max(kv_lens[b] - Sq + i + 1, 1)``, below ``limC_i`` with ``is_causal`` and below
+    ``kv_lens[b]`` without (flash-attn's ``window_size=(W - 1, 0)`` / ``(W - 1, -1)``).  Keys below row 0's left edge are not read
+    and may hold anything; ``decode_plan(..., window=W)`` plans from the window's tiles.  A negative window raises ValueError."""
     fp8 = _decode_inputs("flash_attention_decode", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
     Sk = K.shape[2]
     return _decode("flash_attention_decode", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   O, workspace, stream, k_descale, v_descale)
+                   O, workspace, stream, k_descale, v_descale, window)
 
 
 def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
                                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
-                                 v_descale=None):
+                                 v_descale=None, window=None):
     """``flash_attention_decode`` against PAGED K/V caches: Q ``[B, H, Sq, d]``, pools ``[P, Hkv, page, d]`` (bf16, d = 64 or 128,
     page a power of two >= 16; strided views accepted, so a ``[P, page, Hkv, d]`` pool is ``pool.transpose(1, 2)``) and
     ``block_table``: int32 device tensor ``[B, max_pages]`` with a contiguous last dimension (a row slice of a wider table is
@@ -514,7 +541,8 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     each clamped into [0, P).  Rows beyond the length and pages not named may hold anything.  Mask, ``num_splits``, ``workspace``,
     ``O``, ``return_lse`` and ``stream`` as for ``flash_attention_decode``; the result is that call's on a contiguous copy of the
     same pages, bit for bit.  fp8 pools (``torch.float8_e4m3fn`` under a bf16 Q) with ``k_descale`` / ``v_descale`` as for
-    ``flash_attention_decode``.  No CPU fallback."""
+    ``flash_attention_decode``.  ``window`` as there: a page whose keys all lie below row 0's left edge is not read and neither is
+    its table entry, which may be any int32 (the engine may have freed the page).  No CPU fallback."""
     import torch
     fp8 = _decode_inputs("flash_attention_decode_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
                          v_descale, table=block_table)
@@ -527,7 +555,7 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     table_stride = block_table.stride(0) if B > 1 else max_pages
     return _decode("flash_attention_decode_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
                    (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                   k_descale, v_descale)
+                   k_descale, v_descale, window)
 
 
 def _library_accepts(t):

@@ -296,6 +296,8 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
 // The launch decision of flash_attention_decode, from shapes only (seqLenK is the cache CAPACITY; the lengths live in device memory).
 // Work units are (batch, K/V head, row block, split).  Library's choice of the split count: enough units for DECODE_WGS_PER_CU
 // workgroups on every CU, no split shorter than DECODE_MIN_TILES key tiles of the capacity, at most FA_DECODE_MAX_SPLITS.
+// With a window W > 0 a sequence spans at most W + Sq - 1 keys, wherever they start: at most ceil((W + Sq - 1) / TILE) + 1 tiles;
+// `tiles` is the smaller of that and the capacity's, and the split count follows from it with the same constants.
 // Measured (profiles/decode_split_sweep.log): the time is flat within 5 % from one to two workgroups per CU
 // on uniform batches -- two or three are resident per CU, so either is one resident round -- and a batch of unequal lengths, which
 // the host cannot see, balances 11 % better at two; a split of a single tile has nothing to prefetch behind and gains nothing.
@@ -306,11 +308,13 @@ struct DecodeRoute {
     int64_t grid;
 };
 
-static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits) {
+static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window) {
     DecodeRoute r{};
     const int rows = (H / Hkv) * Sq;                     // packed rows per K/V head
     r.row_blocks = (rows + DecodeCfg<128>::ROWS - 1) / DecodeCfg<128>::ROWS;
-    r.tiles = (Sk + DecodeCfg<128>::TILE - 1) / DecodeCfg<128>::TILE;
+    constexpr int TILE = DecodeCfg<128>::TILE;
+    r.tiles = (Sk + TILE - 1) / TILE;
+    if (window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)window + Sq - 1 + TILE - 1) / TILE + 1);
     const int64_t units = (int64_t)B * Hkv * r.row_blocks;
     if (numSplits > 0) r.ns = numSplits;
     else {
@@ -321,15 +325,15 @@ static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSp
     return r;
 }
 
-static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits) {
+static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits, int window) {
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
     if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
     if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
-    if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
+    if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS || window < 0) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    if (decode_route(B, H, Hkv, Sq, Sk, numSplits).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (decode_route(B, H, Hkv, Sq, Sk, numSplits, window).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 
@@ -339,6 +343,7 @@ static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 // [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
 // Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.  kv_dtype is the element type of
 // K / V: FA_DTYPE_BF16 (the type of Q), or FA_DTYPE_FP8_E4M3 with the two optional per-head descale arrays (the _fp8 entry points).
+// window: 0, or the sliding window W of the _window entry points.
 struct DecodePaging {
     const int32_t* table;
     int64_t table_stride;
@@ -347,7 +352,7 @@ struct DecodePaging {
 
 static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, const float* kDescale,
                       const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal,
-                      int dtype, int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                      int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ, const fa_strides* sK,
                       const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
     if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
@@ -359,7 +364,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
         Sk = pg->max_pages * pg->page_size;
     }
-    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits);
+    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window);
     if (rc != FA_OK) return rc;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
@@ -369,7 +374,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     // whole may be larger)
     const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;
     if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
-    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits);
+    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits, window);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)B * H * Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
@@ -395,6 +400,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
     p.k_descale = kDescale;
     p.v_descale = vDescale;
+    p.window = window;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
     const Kernel sk = pg ? (kv8 ? decode_paged_fp8_split_kernel_of(d) : decode_paged_split_kernel_of(d))
@@ -620,13 +626,13 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
 }
 
-int flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
-                                int numSplits, fa_decode_plan* plan) {
+int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                       int numSplits, int windowSize, fa_decode_plan* plan) {
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
-    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits);
+    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, windowSize);
     if (rc != FA_OK) return rc;
-    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits);
+    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize);
     plan->num_splits = r.ns;
     plan->row_blocks = r.row_blocks;
     plan->rows_per_block = DecodeCfg<128>::ROWS;
@@ -640,6 +646,11 @@ int flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int
     return FA_OK;
 }
 
+int flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                int numSplits, fa_decode_plan* plan) {
+    return flash_attention_decode_plan_window(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, numSplits, 0, plan);
+}
+
 size_t flash_attention_decode_workspace_size(int batchSize, int numHeads, int seqLenQ, int dHead, int numSplits) {
     if (batchSize <= 0 || numHeads <= 0 || seqLenQ <= 0 || dHead <= 0 || numSplits <= 1) return 0;
     const size_t rows = (size_t)batchSize * numHeads * seqLenQ;
@@ -651,7 +662,7 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
     return fa::decode_run(Q, K, V, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
+                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
 }
 
 int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -661,7 +672,7 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
+                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
 }
 
 int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -671,7 +682,7 @@ int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void
                                const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, sQ, sK, sV, sO, nullptr, stream);
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
 }
 
 int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -683,7 +694,34 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, sQ, sK, sV, sO, &pg, stream);
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
+}
+
+// a bf16 cache has no descales: the logical cache is what lies in memory
+static bool window_descales_ok(int kv_dtype, const float* kDescale, const float* vDescale) {
+    return kv_dtype == FA_DTYPE_FP8_E4M3 || (!kDescale && !vDescale);
+}
+
+int flash_attention_decode_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                                  const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                                  int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, nullptr, stream);
+}
+
+int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                        const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
+                                        int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                        int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                        int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ,
+                                        const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg, stream);
 }
 
 const char* flash_attention_error_string(int code) {

@@ -39,6 +39,15 @@
 //     bytes of V become 32 bytes of the same bf16 LDS image.  fp8 -> bf16 is exact (3 mantissa bits), in registers; from there
 //     on the MFMAs, the softmax and the P.V product are the bf16 kernel's.  k_descale is folded into the score scale, v_descale
 //     into the final 1 / l: the loop body carries neither.
+//   * WINDOW (flash_attention_decode_window, flash_attention_decode_paged_window): window = W > 0 gives every
+//     row a LOWER bound next to the upper one: row i sees lo_i <= key < lim with lo_i = max(limC_i - W, 0), limC_i the row's
+//     bottom-right causal limit (whether or not is_causal cuts the top).  first = lo_0 is the lowest key any row sees: the
+//     sequence's tiles are [first / TILE, nt), divided over the splits as before, so nothing below the first tile is fetched -- in
+//     the paged form not even its table entry (look-ups are clamped to [page of first, last page]).  Keys below `first` may hold
+//     anything.  In K that is harmless (the masked score is a select); V rows below `first` must arrive as 0 (0 x NaN would reach
+//     the accumulator), and they can only lie in the sequence's first tile, which is only ever loaded by the prologue: there a lane
+//     whose V row is below `first` uses an offset beyond any record count, and a paged 16-key group wholly below it a zero-byte
+//     descriptor.  The loop's own loads carry none of this.  window = 0: first = lo_i = 0, today's kernel term for term.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -70,6 +79,7 @@ struct DecodeParams {
     // V8 * v_descale[K/V head]
     const float* k_descale;       // optional [Hkv] (device memory); NULL = 1
     const float* v_descale;       // optional [Hkv] (device memory); NULL = 1
+    int window;                   // 0: none; W > 0: row i sees at most the last W keys up to and including its own position
 };
 
 template <int D, int ES = 2>   // ES: bytes per K/V element in memory (2: bf16, 1: e4m3fn); the LDS image of V is bf16 either way
@@ -118,17 +128,23 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     int len = p.Sk;
     if (p.kv_lens) len = min(max(p.kv_lens[b], 1), p.Sk);
     len = __builtin_amdgcn_readfirstlane(len);
-    // this sequence's tiles, divided over the splits in whole tiles
-    const int nt = (len + C::TILE - 1) / C::TILE;
-    const int t0 = (int)(((int64_t)nt * split) / p.ns), t1 = (int)(((int64_t)nt * (split + 1)) / p.ns);
+    // the lowest key any row sees: row 0's lower bound (0 without a window).  Keys below it are never part of the result
+    const int first = p.window > 0 ? max(max(len - p.Sq + 1, 1) - p.window, 0) : 0;
+    // this sequence's tiles [tlo, nt), divided over the splits in whole tiles
+    const int nt = (len + C::TILE - 1) / C::TILE, tlo = first / C::TILE;
+    const int t0 = tlo + (int)(((int64_t)(nt - tlo) * split) / p.ns), t1 = tlo + (int)(((int64_t)(nt - tlo) * (split + 1)) / p.ns);
 
     // this lane's packed row (column r of the swapped products): query head g of the group, query row i
     const int pr = rb * C::ROWS + r;
     const bool row_ok = pr < p.G * p.Sq;
     const int g = row_ok ? pr / p.Sq : 0, qi = row_ok ? pr - g * p.Sq : 0;
     const int h = kvh * p.G + g;
-    // keys this row sees: [0, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0
-    const int lim = p.causal ? max(len - p.Sq + qi + 1, 1) : len;
+    // keys this row sees: [lo, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0.
+    // The window's left edge follows the row's own position, causal or not; lo < limc <= lim: every row sees a key
+    const int limc = max(len - p.Sq + qi + 1, 1);
+    const int lim = p.causal ? limc : len;
+    const int lo = p.window > 0 ? max(limc - p.window, 0) : 0;
+    const unsigned span = (unsigned)(lim - lo);   // lo <= key < lim  <=>  (unsigned)(key - lo) < span: one compare per score
 
     // B fragment of Q^T: Q[row r][32 ks + 8 h4 .. + 7].  KV8: Q[row r][64 (ks / 2) + 16 h4 + 8 (ks % 2) .. + 7] -- the d order in
     // which a lane's 16-byte K loads hold two k-groups each
@@ -168,13 +184,14 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     // for the tile after it
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const int32_t* tb = p.block_table + b * p.table_stride;
-    const int last_page = (len - 1) >> p.page_shift;
+    const int last_page = (len - 1) >> p.page_shift, first_page = first >> p.page_shift;
     const int gkoff = r * ksb + h4 * 16, gvoff = vkey * vsb + vch * 16;
     int ev = 0, e0 = 0, e1 = 0;
-    // the table entries of tile t: only pages that hold a key < len are looked up (a tile past the end repeats the last one)
+    // the table entries of tile t: only pages that hold a key in [first, len) are looked up (a tile past the end repeats the last
+    // one, a group below `first` in the first tile takes the page of `first`: its descriptor holds no bytes)
     auto table_entries = [&](int t) {
         const int key = t * C::TILE + wv * C::WKEYS + 16 * (lane & 1);
-        return tb[min(key >> p.page_shift, last_page)];
+        return tb[max(min(key >> p.page_shift, last_page), first_page)];
     };
     // take the entries that have arrived into scalars for the next load_tile, THEN fetch tile t's into the register they leave
     auto next_entries = [&](int t) {
@@ -182,19 +199,23 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
         e1 = __builtin_amdgcn_readlane(ev, 1);
         ev = table_entries(t);
     };
-    // one 16-key group of one pool: a descriptor at its first row, holding its rows below len
-    auto group_rsrc = [&](const __bf16* pool, int64_t page_stride, int64_t head_stride, int64_t row_stride, int entry, int key) {
+    // one 16-key group of one pool: a descriptor at its first row, holding its rows below len (cut: none if all are below `first`)
+    auto group_rsrc = [&](const __bf16* pool, int64_t page_stride, int64_t head_stride, int64_t row_stride, int entry, int key, bool cut) {
         const int page = min(max(entry, 0), p.num_pages - 1);
         const KV* base = (const KV*)pool + page * page_stride + kvh * head_stride + (key & ((1 << p.page_shift) - 1)) * row_stride;
-        const int rows = min(len - key, 16);
+        const int rows = cut && key + 16 <= first ? 0 : min(len - key, 16);
         const int bytes = rows > 0 ? (rows - 1) * (int)(row_stride * ES) + D * ES : 0;
         const uint64_t a = (uint64_t)base;
         const uint64_t au = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
         return __builtin_amdgcn_make_buffer_rsrc((void*)au, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
+    // cut (the prologue's load only: the one that can be of the sequence's first tile): V rows below `first` arrive as 0 -- the
+    // lane's offset lies beyond any record count (one head's extent is below 2^31 bytes), as rows >= len lie beyond this one's
+    constexpr int BEYOND = (int)0x80000000u;
     u32x4 kn[2][C::KL], vn[C::NV];
-    auto load_tile = [&](int t) {
+    auto load_tile = [&](int t, bool cut) {
+        const int vkey0 = t * C::TILE + wave * C::WKEYS + vkey;   // the key of this lane's V load 0
         if constexpr (!PAGED) {
             const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
 #pragma unroll
@@ -204,14 +225,15 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
                     kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + kt + kg * 16 * ksb + ks * 64, 0, 0));
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)
-                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + vt + n * C::KPI * vsb, 0, 0));
+                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    vrsrc, cut && vkey0 + n * C::KPI < first ? BEYOND : voff + vt + n * C::KPI * vsb, 0, 0));
         } else {
             __amdgpu_buffer_rsrc_t kr[2], vr[2];
 #pragma unroll
             for (int kg = 0; kg < 2; ++kg) {
                 const int entry = kg ? e1 : e0, key = t * C::TILE + wv * C::WKEYS + 16 * kg;
-                kr[kg] = group_rsrc(p.K, p.kB, p.kH, p.kS, entry, key);
-                vr[kg] = group_rsrc(p.V, p.vB, p.vH, p.vS, entry, key);
+                kr[kg] = group_rsrc(p.K, p.kB, p.kH, p.kS, entry, key, cut);
+                vr[kg] = group_rsrc(p.V, p.vB, p.vH, p.vS, entry, key, cut);
             }
 #pragma unroll
             for (int kg = 0; kg < 2; ++kg)
@@ -220,7 +242,8 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
                     kn[kg][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(kr[kg], gkoff + ks * 64, 0, 0));
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)   // (V load n covers the keys KPI n .. KPI n + KPI - 1 of the wave's 32: one group)
-                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vr[n * C::KPI / 16], gvoff + (n * C::KPI % 16) * vsb, 0, 0));
+                vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    vr[n * C::KPI / 16], cut && vkey0 + n * C::KPI < first ? BEYOND : gvoff + (n * C::KPI % 16) * vsb, 0, 0));
         }
     };
 
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
             ev = table_entries(t0);
             next_entries(t0 + 1);
         }
-        load_tile(t0);
+        load_tile(t0, true);
     }
     for (int t = t0; t < t1; ++t) {
         // V of this tile: registers -> the wave's LDS image (the previous tile's reads are done: same wave, program order)
@@ -264,17 +287,17 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
         }
         if (t + 1 < t1) {   // (wave-uniform) next tile's K and V: in flight under the softmax and the P.V product
             if constexpr (PAGED) next_entries(t + 2);   // tile t + 1's entries arrived with the K/V of tile t: issued before them
-            load_tile(t + 1);
+            load_tile(t + 1, false);
         }
 
         // s[kg][reg]: key kb + 16 kg + 4 h4 + reg, packed row r
-        const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4;
+        const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4, kbl = kb - lo;
         float x[8];
         float mx = NEG_INF;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int key = kb + 16 * (j >> 2) + (j & 3);
-            x[j] = key < lim ? s[j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
+            const unsigned rel = (unsigned)(kbl + 16 * (j >> 2) + (j & 3));   // key - lo
+            x[j] = rel < span ? s[j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
             mx = fmaxf(mx, x[j]);
         }
         mx = max_all_quarters(mx);

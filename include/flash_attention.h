@@ -509,6 +509,66 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
                                      const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                      void* stream);
 
+/*
+ * flash_attention_decode_window, flash_attention_decode_paged_window -- split-KV decode with a SLIDING WINDOW: every query row sees at
+ * most the last windowSize keys up to and including its own position (Mistral, Gemma, the local layers of gpt-oss).  The argument
+ * lists are flash_attention_decode_fp8's / flash_attention_decode_paged_fp8's with windowSize after numSplits, and serve all four
+ * cache forms: kv_dtype = FA_DTYPE_BF16 (kDescale and vDescale must be NULL) or FA_DTYPE_FP8_E4M3 (the _fp8 siblings' caches and
+ * descales), contiguous or paged.  Everything not named here is the sibling's.
+ *
+ * Mask.  With len = kvLens[b] clamped into [1, capacity], limC_i = max(len - seqLenQ + i + 1, 1) (the bottom-right causal limit of row
+ * i, the "at least key 0" rule included) and lo_i = max(limC_i - windowSize, 0):
+ *   is_causal = true    row i sees the keys lo_i <= k < limC_i      (flash-attn's window_size = (windowSize - 1, 0))
+ *   is_causal = false   row i sees the keys lo_i <= k < len         (window_size = (windowSize - 1, -1): the left edge still follows
+ *                       the row's own position)
+ * Every row sees at least one key: no NaN rows.  windowSize = 0: no window -- the call is the sibling's (flash_attention_decode,
+ * _paged, _fp8, _paged_fp8 by kv_dtype and form): the same launches, the same bits.  There is no right window, no attention sink and
+ * no per-head window.
+ *
+ * Below the window.  first(b) = lo_0 is the lowest key any row of sequence b sees.  The contract mirrors the one for keys at and
+ * beyond kvLens[b]: keys below first(b) never enter the result; their K and V may hold NaN, inf, stale data or any fp8 byte (0x7F /
+ * 0xFF included).  Only the 128-key tiles from first(b) / 128 on are fetched, so the K/V bytes read follow the window, not the
+ * length.  Paged: a page whose keys ALL lie below first(b) is never read and neither is its blockTable entry, which may be any int32:
+ * a serving engine may free or reuse the page.  (Look-ups are clamped into [page of first(b), last page with a key < kvLens[b]].)
+ * A key in [first(b), kvLens[b]) that one row does not see is still data another row reads: it must be valid.
+ *
+ * Plan.  A windowed sequence spans at most windowSize + seqLenQ - 1 keys: at most ceil((windowSize + seqLenQ - 1) / 128) + 1 tiles.
+ * flash_attention_decode_plan_window chooses the split count from the smaller of that and the capacity's tiles, by the rule of
+ * flash_attention_decode_plan -- which is this function with windowSize = 0; windowSize >= seqLenK plans as no window does.  A forced
+ * numSplits is used as given; splits beyond the window's tiles come out empty (weight 0).  flash_attention_decode_workspace_size is
+ * unchanged: pass the planned num_splits.  Paged: seqLenK = maxPagesPerSeq * pageSize.
+ *
+ * Tiles and splits are divided alike in both forms: flash_attention_decode_paged_window equals, bit for bit,
+ * flash_attention_decode_window on a contiguous copy of the same pages with seqLenK = the capacity and the same numSplits, windowSize
+ * and descales.  Precision, determinism and the conventions (validated before any launch; never allocates, synchronises or prints)
+ * are the siblings'.
+ *
+ * Rejected before any launch: everything the sibling of the same kv_dtype and form rejects, with the same codes; windowSize < 0
+ * FA_ERR_BAD_SHAPE; kv_dtype other than FA_DTYPE_BF16 / FA_DTYPE_FP8_E4M3, or a non-NULL kDescale / vDescale with
+ * kv_dtype = FA_DTYPE_BF16, FA_ERR_UNSUPPORTED_DTYPE.
+ */
+int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                       int o_dtype, int numSplits /* 0 = the library chooses */, int windowSize,
+                                       fa_decode_plan* plan);
+
+int flash_attention_decode_window(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace,
+                                  int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                  float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                  int windowSize,
+                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                  void* stream);
+
+int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace,
+                                        int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                        int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                        float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                        int windowSize,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 

@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256] [--kv fp8]
+                                [--paged 16,128,256] [--kv fp8] [--window 128,4096]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -25,6 +25,11 @@ Each line:
               with its min / max, fp8_ratio = fp8_ms / ms, and fp8_kv_tbps from the bytes actually read (one per element: kv_MB / 2).
               With --paged, paged_fp8_ms[page] as well: the fp8 pools behind the same shuffled table
               (profiles/decode_fp8_bench.log).
+--window a,b,c  sliding windows: per shape and window W, the same call with window=W (same Q, cache, lengths and O; the plan and the
+              workspace are the window's): window_ms[W] with its min / max, window_splits[W], and window_kv_tbps[W] from the bytes of
+              the keys a windowed sequence can see (sum over the batch of min(kv_lens, W + Sq - 1) keys; window_kv_MB[W]).  With
+              --kv fp8 window_fp8_ms[W] / window_fp8_kv_tbps[W] as well, with --paged window_paged_ms[page][W] (and
+              window_paged_fp8_ms[page][W]) (profiles/decode_window_bench.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
 """
 import argparse
@@ -46,8 +51,10 @@ SHAPES = [  # name, B, H, Hkv, Sq, Sk, d, ragged
     ("d64_16k", 8, 32, 8, 1, 16384, 64, False),
     ("ragged", 16, 32, 8, 1, 32768, 128, True),
 ]
-# run only when named: a short cache under a single sequence (how short a split may usefully be)
-EXTRA = [("single_2k", 1, 32, 8, 1, 2048, 128, False), ("single_4k", 1, 32, 8, 1, 4096, 128, False)]
+# run only when named: a short cache under a single sequence (how short a split may usefully be; single_128 and single_4k are also the
+# yardsticks of --window 128,4096 on the long single-sequence shapes: un-windowed caches of the window's size)
+EXTRA = [("single_2k", 1, 32, 8, 1, 2048, 128, False), ("single_4k", 1, 32, 8, 1, 4096, 128, False),
+         ("single_128", 1, 32, 8, 1, 128, 128, False)]
 
 
 def timed(fn, steps, warmup):
@@ -73,6 +80,7 @@ def main():
     ap.add_argument("--splits", default=None, help="comma-separated forced split counts: the sweep")
     ap.add_argument("--no-cross", action="store_true")
     ap.add_argument("--paged", default=None, help="comma-separated page sizes: add paged_ms per page size to every shape's line")
+    ap.add_argument("--window", default=None, help="comma-separated sliding windows: add window_ms per window to every shape's line")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     args = ap.parse_args()
     import torch
@@ -117,13 +125,20 @@ def main():
                 T8[b] = (T[b].float() / ds[:, None, None]).clamp(-448, 448).to(torch.float8_e4m3fn)
             return T8, ds
 
-        def measure_fp8():
-            plan = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0)
+        def measure_fp8(window=0):
+            plan = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0, window=window)
             ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
-            call = lambda: fa.flash_attention_decode(Q, K8, V8, lens_d, O=O, workspace=ws, k_descale=kds, v_descale=vds)
+            kw = dict(window=window) if window else {}
+            call = lambda: fa.flash_attention_decode(Q, K8, V8, lens_d, O=O, workspace=ws, k_descale=kds, v_descale=vds, **kw)
             return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
 
-        def measure_paged(page, fp8=False):
+        def measure_window(window):
+            plan = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0, window=window)
+            ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            call = lambda: fa.flash_attention_decode(Q, K, V, lens_d, O=O, workspace=ws, window=window)
+            return plan, sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
+
+        def measure_paged(page, fp8=False, window=0):
             # the same data in pages: page j of sequence b is rows [j page, (j + 1) page) of every K/V head, stored wherever a
             # shuffle of all B * n page numbers puts it
             n = Sk // page
@@ -135,9 +150,11 @@ def main():
                 pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=T.dtype)
                 pool[perm] = T.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
                 pools.append(pool.view(torch.float8_e4m3fn) if fp8 else pool)
-            ns = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0)["num_splits"]
+            ns = fa.decode_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, 0, window=window)["num_splits"]
             ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, ns), 16), dtype=torch.uint8, device=dev)
             kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if window:
+                kw["window"] = window
             call = lambda: fa.flash_attention_decode_paged(Q, pools[0], pools[1], table, lens_d, O=O, workspace=ws, **kw)
             return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
 
@@ -184,6 +201,28 @@ def main():
                             paged_fp8_ms_min={str(k): round(v[0], 5) for k, v in pf.items()},
                             paged_fp8_ms_max={str(k): round(v[-1], 5) for k, v in pf.items()},
                             paged_fp8_ratio={str(k): round(statistics.median(v) / fmed, 4) for k, v in pf.items()})
+        if args.window:
+            windows = [int(x) for x in args.window.split(",")]
+            pages = [page for page in (int(x) for x in (args.paged or "").split(",") if x) if Sk % page == 0]
+            med_of = lambda v: round(statistics.median(v), 5)
+            wbytes = {W: sum(min(L, W + Sq - 1) for L in lens) * Hkv * d * 2 * 2 for W in windows}
+            wm = {W: measure_window(W) for W in windows}
+            line.update(window_ms={str(W): med_of(v) for W, (_, v) in wm.items()},
+                        window_ms_min={str(W): round(v[0], 5) for W, (_, v) in wm.items()},
+                        window_ms_max={str(W): round(v[-1], 5) for W, (_, v) in wm.items()},
+                        window_splits={str(W): pl["num_splits"] for W, (pl, _) in wm.items()},
+                        window_kv_MB={str(W): round(wbytes[W] / 1e6, 2) for W in windows},
+                        window_kv_tbps={str(W): round(wbytes[W] / statistics.median(v) / 1e9, 3) for W, (_, v) in wm.items()})
+            if pages:
+                line.update(window_paged_ms={str(page): {str(W): med_of(measure_paged(page, False, W)) for W in windows} for page in pages})
+            if args.kv == "fp8":
+                wf = {W: measure_fp8(W) for W in windows}
+                line.update(window_fp8_ms={str(W): med_of(v) for W, v in wf.items()},
+                            window_fp8_kv_tbps={str(W): round(wbytes[W] / 2 / statistics.median(v) / 1e9, 3) for W, v in wf.items()})
+                if pages:
+                    line.update(window_paged_fp8_ms={str(page): {str(W): med_of(measure_paged(page, True, W)) for W in windows}
+                                                     for page in pages})
+        if args.kv == "fp8":
             del K8, V8
         print(json.dumps(line), flush=True)
         del Q, K, V, O
