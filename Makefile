@@ -87,8 +87,18 @@ asan: $(LIB) oracle
 	    FA_LIB_PATH=$(CURDIR)/$(ASAN_DIR)/libflash_attention.so python -m pytest tests/test_abi.py tests/test_backward_abi.py tests/test_shard.py -q -p no:cacheprovider -m "not gpu"
 	@echo "asan: oracle (gcc ASan+UBSan) and library host code (clang ASan+UBSan) clean"
 
-asm: $(KSRC) $(KHDR)
-	mkdir -p build && $(HIPCC) $(HIPFLAGS) -S --cuda-device-only -o build/inst_bf16_d128.s $(PKG)/csrc/inst_bf16_d128.hip
+# Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
+# source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
+KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC))
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s: HIPFLAGS += $(MFMA_VGPR)
+
+build/asm/%.s: $(PKG)/csrc/%.hip $(KHDR)
+	@mkdir -p build/asm
+	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -o $@.tmp $<
+	grep -v __hip_cuid_ $@.tmp > $@
+	@rm -f $@.tmp
+
+asm: $(KASM)
 
 clean:
 	rm -f $(LIB) $(PKG)/fa_main tests/fa_test tests/fa_tune tests/unit_kernels tests/micro/simd_mix tests/micro/valu_rates tests/micro/atomic_latency oracle/liboracle_attention.so

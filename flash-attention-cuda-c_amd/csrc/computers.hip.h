@@ -91,10 +91,7 @@ struct WaveCompute {
     template <int SLOT, bool F16W = false, int N = 0>
     __device__ __forceinline__ void load_in_slot(Stage& st, int t_load) {
         if constexpr (N < NL) {
-            if constexpr (load_slot(N) == SLOT) {
-                if constexpr (C::MIX) st.template load<N, F16W>(t_load);
-                else st.template load<N>(t_load);
-            }
+            if constexpr (load_slot(N) == SLOT) st.template load<N, F16W>(t_load);
             load_in_slot<SLOT, F16W, N + 1>(st, t_load);
         }
     }
@@ -132,7 +129,7 @@ struct WaveCompute {
             }
         }
     }
-    // Coalesced form (Opt::coalesced_q).  load_q above has every lane read 16-byte pieces of its own row: one
+    // Coalesced form (KernelCfg::COALESCED_Q).  load_q above has every lane read 16-byte pieces of its own row: one
     // instruction touches 32 rows x 2 pieces, 64 separate 16-byte requests.  Here instruction i fetches 64/CH WHOLE
     // rows (CH = 16-byte chunks per row; lane = (row, chunk)), and the fragments are formed by one trip through
     // this wave's private LDS region: chunk c of row q is parked at chunk c ^ (q & (CH-1)), so the 16 rows of a
@@ -369,10 +366,8 @@ struct WaveCompute {
             exp_slot<SA + J, F16W>(cur, c);
             if constexpr (TRACK && J < SB / 2) max3_slot<J>(nxt);
             if constexpr (TRACK && J == SB / 2) decide(c);
-            if constexpr (J >= SB / 2 && (J - SB / 2) % WSTEP == 0 && (J - SB / 2) / WSTEP < NW) {
-                if constexpr (C::MIX) st.template write<(J - SB / 2) / WSTEP, F16W>(wr_slot);
-                else st.template write<(J - SB / 2) / WSTEP>(wr_slot);
-            }
+            if constexpr (J >= SB / 2 && (J - SB / 2) % WSTEP == 0 && (J - SB / 2) / WSTEP < NW)
+                st.template write<(J - SB / 2) / WSTEP, F16W>(wr_slot);
             __builtin_amdgcn_sched_barrier(0);
             slots_b<TRACK, J + 1, F16W>(st, wr_slot, v_cur, vbase, c, cur, nxt);
         }
@@ -463,8 +458,8 @@ struct WaveCompute {
     }
 
     // 2-byte outputs: O^T accumulators -> this wave's private LDS region as a row-major [32R rows][D] tile
-    // -> whole rows back out with 16-byte stores (each 16- or 8-lane group writes one full row).  The
-    // direct form issues 16 eight-byte stores per lane that touch 32 rows each: ~8k cycles per workgroup,
+    // -> whole rows back out with 16-byte stores (each 16- or 8-lane group writes one full row).  Storing
+    // straight from the accumulators issues 16 eight-byte stores per lane that touch 32 rows each: ~8k cycles per workgroup,
     // store-issue bound; this form ~3.3k.  16-byte chunk c of row q sits at chunk c ^ (q & mask), so the
     // ds_write_b64 of 16 lanes (16 rows, same column) spread over all banks.  `region` = 32*R*D*2 bytes
     // private to this wave; the caller guarantees the K/V ring is dead.
@@ -519,7 +514,7 @@ struct WaveCompute {
     // 4-byte outputs through LDS, 64 columns at a time: O^T accumulators -> this wave's private region as a
     // row-major [32R rows][64 floats] half tile (ds_write_b128, 16-byte chunk c of row q at chunk c ^ (q & 15):
     // the 8 lanes of a write group hit 8 different chunk columns) -> 256 contiguous bytes of a row per 16 lanes
-    // back out.  The direct form (store_o) writes 32-byte pieces of 32 different rows per instruction.
+    // back out.  Storing straight from the accumulators writes 32-byte pieces of 32 different rows per instruction.
     // `region` = 32*R*256 bytes private to this wave; the caller guarantees the K/V ring is dead.
     template <typename OutT>
     __device__ __forceinline__ void store_o_lds32(lds_ptr region, char* Oh, float* lse_head, int64_t oS_bytes, int row0, int S,

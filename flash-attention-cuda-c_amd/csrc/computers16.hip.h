@@ -61,13 +61,12 @@ struct WaveCompute16 {
     static constexpr int SPAN = SA + SB / 2;       // overall slots the exponentials are spread over
     using G = TileGeom<D, ESZ>;
     using Stage = std::conditional_t<C::MIX, MixStage<D, C::NWAVES, true, false>,
-                  std::conditional_t<C::DMA, DmaStage<D, C::NWAVES, true, false>, BufStage<D, ESZ, C::NWAVES, C::PAD, true, C::P_F16>>>;
+                  std::conditional_t<C::DMA, DmaStage<D, C::NWAVES, true, false>, BufStage<D, ESZ, C::NWAVES, C::PAD, true>>>;
     // the P.V operand type: bf16, or fp16 with the fp16-weights option (weights rounded to 11 bits instead of 8; V staged as fp16).
     // F16W is a property of the PASS, not of the kernel: the fp16-weights kernels fall back to a bf16-weights tracked pass when
     // fp16 cannot hold the unit's V (|v| > 65504 becomes inf: kernel_bf16.hip.h, run_units), so every member that touches the
-    // weights' or V's type takes it as a template argument that defaults to the kernel's C::P_F16
+    // weights' or V's type takes it as a template argument (default: bf16 weights, as in WaveCompute and the stage classes)
     template <bool F16W> using pv_of = std::conditional_t<F16W, f16x8, bf16x8>;
-    using pv_t = pv_of<C::P_F16>;
     using ScoresT = Scores16;
     static constexpr int NL = Stage::NL, NW = Stage::NW;
     static constexpr int WSTEP = 2 * NW <= SB / 2 + 1 ? 2 : 1;   // LDS writes sit in every WSTEP-th slot of the second half of phase B
@@ -92,13 +91,10 @@ struct WaveCompute16 {
     // (Later is worse -- the pieces then land after the end-of-step wait: phase A's second half -2.6 %, phase B -9 ... -13 %,
     //  profiles/r03_tune_c_dma_slots_*.log.)
     __host__ __device__ static constexpr int load_slot(int n) { return 1 + 2 * n; }
-    template <int SLOT, bool F16W = C::P_F16, int N = 0>
+    template <int SLOT, bool F16W = false, int N = 0>
     __device__ __forceinline__ void load_in_slot(Stage& st, int t_load) {
         if constexpr (N < NL) {
-            if constexpr (load_slot(N) == SLOT) {
-                if constexpr (C::MIX) st.template load<N, F16W>(t_load);   // (MixStage: V by DMA or, fp16 units, through registers)
-                else st.template load<N>(t_load);
-            }
+            if constexpr (load_slot(N) == SLOT) st.template load<N, F16W>(t_load);   // (MixStage: V by DMA or, fp16 units, through registers)
             load_in_slot<SLOT, F16W, N + 1>(st, t_load);
         }
     }
@@ -118,13 +114,13 @@ struct WaveCompute16 {
         if constexpr (C::SUM_MFMA) return lsum[qg][0];
         else return sum_all_quarters(l[qg]);
     }
-    template <bool F16W = C::P_F16>
+    template <bool F16W = false>
     __device__ __forceinline__ static pv_of<F16W> ones_frag() {
         constexpr uint32_t one2 = F16W ? 0x3c003c00u : 0x3f803f80u;
         u32x4 v = {one2, one2, one2, one2};
         return __builtin_bit_cast(pv_of<F16W>, v);
     }
-    template <bool F16W = C::P_F16>
+    template <bool F16W = false>
     __device__ __forceinline__ static uint32_t pack_p(float lo, float hi) { return F16W ? pack_f16(lo, hi) : pack_bf16(lo, hi); }
 
     // Q fragment (qg, ks) of row q = row0 + 16*qg + (lane&15): 16 bytes at byte 64*ks + 16*h4 of the row.
@@ -145,7 +141,7 @@ struct WaveCompute16 {
             }
         }
     }
-    // Coalesced form (Opt::coalesced_q): instruction i fetches 64/QCH WHOLE rows; the fragments are formed by one trip
+    // Coalesced form (KernelCfg::COALESCED_Q): instruction i fetches 64/QCH WHOLE rows; the fragments are formed by one trip
     // through this wave's private LDS region (chunk c of row q parked at chunk c ^ (q & (QCH-1))).
     static constexpr int QCH = (D * ESZ) / 16;     // 16-byte chunks per Q row
     static constexpr int QRPI = 64 / QCH;          // rows fetched per instruction
@@ -236,7 +232,7 @@ struct WaveCompute16 {
     }
 
     // ---- softmax slices ------------------------------------------------------------------------
-    template <int E, bool F16W = C::P_F16>
+    template <int E, bool F16W = false>
     __device__ __forceinline__ void exp_elem(const Scores16& cur, float c) {
         constexpr int kk = E / 16, qg = (E / 8) % 2, j = E % 8, kg = 2 * kk + (j >> 2), reg = j & 3;
         const float p = fast_exp2(fmaf(cur.s[kg][qg][reg], c, -m[qg]));
@@ -253,14 +249,14 @@ struct WaveCompute16 {
             p_even = p;
         }
     }
-    template <int SLOT, bool F16W = C::P_F16, int E = 0>
+    template <int SLOT, bool F16W = false, int E = 0>
     __device__ __forceinline__ void exp_slot(const Scores16& cur, float c) {
         if constexpr (E < NE) {
             if constexpr (elem_slot(E) == SLOT) exp_elem<E, F16W>(cur, c);
             exp_slot<SLOT, F16W, E + 1>(cur, c);
         }
     }
-    template <bool F16W = C::P_F16>
+    template <bool F16W = false>
     __device__ __forceinline__ pv_of<F16W> p_frag(int qg, int kk) const {
         u32x4 v = {pw[qg][kk][0], pw[qg][kk][1], pw[qg][kk][2], pw[qg][kk][3]};
         return __builtin_bit_cast(pv_of<F16W>, v);
@@ -300,7 +296,7 @@ struct WaveCompute16 {
 
     // ---- the slots -----------------------------------------------------------------------------
     // phase A slot I: K fragment f = I / QG, query group I % QG
-    template <int I, bool F16W = C::P_F16>
+    template <int I, bool F16W = false>
     __device__ __forceinline__ void slots_a(Stage& st, int t_load, lds_ptr k_next, lds_ptr v_cur, int kbase, int vbase,
                                             float c, const Scores16& cur, Scores16& nxt) {
         if constexpr (I < SA) {
@@ -319,7 +315,7 @@ struct WaveCompute16 {
         }
     }
     // phase B slot J: V^T fragment v = J / QG (k-step v / DG, d group v % DG), query group J % QG
-    template <bool TRACK, int J, bool F16W = C::P_F16>
+    template <bool TRACK, int J, bool F16W = false>
     __device__ __forceinline__ void slots_b(Stage& st, lds_ptr wr_slot, lds_ptr v_cur, int vbase, float c,
                                             const Scores16& cur, const Scores16& nxt) {
         if constexpr (J < SB) {
@@ -341,7 +337,7 @@ struct WaveCompute16 {
     }
 
     // One tile: cur = S(t) (consumed), nxt = S(t+1) (produced).  Same contract as WaveCompute::tile_step.
-    template <bool TRACK, bool F16W = C::P_F16>
+    template <bool TRACK, bool F16W = false>
     __device__ __forceinline__ void tile_step(Stage& st, int t_load, lds_ptr wr_slot, lds_ptr k_next, lds_ptr v_cur,
                                               int kbase, int vbase, float c, const Scores16& cur, Scores16& nxt,
                                               bool has_next, bool mask_next, int kv0_next, int q_row0, int S, int lane) {

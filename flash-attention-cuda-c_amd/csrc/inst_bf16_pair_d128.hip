@@ -8,8 +8,8 @@ namespace fa {
 
 // ONE configuration for both weight precisions: the four-wave form of the persistent kernels' mixed-precision kernel (KernelCfg::MIX) on their
 // engine (32x32x16 under the mask, 16x16x32 without) -- K by LDS-DMA, V by LDS-DMA (bf16 weights) or as fp16 through registers (the blocks
-// qb < Params::hp), exact fp32 row sums whether or not the call asks for the LSE.  (Until round 4 the fp16 blocks ran the register-staged
-// 16x16x32 kernel, whose 32 staging registers at four waves spilled 31 VGPRs into its tile loop.)  It fills both configuration slots of
+// qb < Params::hp), exact fp32 row sums whether or not the call asks for the LSE.  (The register-staged 16x16x32 fp16-weights kernel in
+// the fp16 blocks' place spills 31 VGPRs into its tile loop: 32 staging registers at four waves.)  It fills both configuration slots of
 // fwd_mfma_pair_kernel.
 template <bool CAUSAL, typename OutT>
 using PairA = KernelCfg<128, CAUSAL, OutT, 2, Opt{.m16 = CAUSAL ? 0 : -1, .sum_mfma = 0, .waves = 4, .mix = true}>;

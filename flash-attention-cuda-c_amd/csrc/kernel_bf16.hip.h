@@ -14,7 +14,7 @@
 // score registers so S(t+1) never has to be copied into S(t).  What happens inside a tile: computers.hip.h.
 // The alternatives that were built, measured and rejected (64 rows per wave, one unit per workgroup, 4-slot ring, ping-pong
 // phases, unit streaming, packed softmax arithmetic, ...) are recorded with their numbers in DESIGN.md section 4 and
-// profiles/r01_tune_*, r02_tune_*; their code lives in the history (round-2 tree), not here.
+// profiles/r01_tune_*, r02_tune_*; their code lives in the git history, not here.
 //
 // Optimistic max.  exp2 / bf16 / f32 accumulation have ~2^127 of headroom, so the first pass takes
 // every exponential relative to the row max of tile 0 and issues no per-tile max, decision or rescale
@@ -142,7 +142,7 @@ using WaveComputeOf = std::conditional_t<C::M16, WaveCompute16<C>, WaveCompute<C
 
 // One pass over all KV tiles of the workgroup's query block.  Returns (workgroup-uniform) whether the result is not finite and
 // has to be recomputed by a safer pass: the optimistic pass (TRACK = false) always reports, the tracked pass of an fp16-weights
-// kernel reports too (F16W: its V is fp16, where a finite bf16 |v| > 65504 is inf -- run_units then repeats the unit with bf16
+// kernel reports too (F16W: its V is fp16, where a finite bf16 |v| > 65504 is inf -- run_passes then repeats the unit with bf16
 // weights and bf16 V, F16W = false, which is the last resort and reports nothing).
 template <class C, bool TRACK, bool F16W = C::P_F16>
 __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>& w, typename WaveComputeOf<C>::Stage& st, lds_ptr smem,
@@ -166,21 +166,14 @@ __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>
     // Prologue: tile 0 (requested by the caller together with Q on the first pass) -> LDS, barrier; then
     // tile 1 is fetched while S(0) = K(0).Q^T and its row max are computed.
     // (MIX / P_F16: the form of the tile -- V as fp16 through registers or as bf16 -- follows the pass)
-    if constexpr (C::MIX) {
-        if (!tile0_in_flight) st.template load_all_into<F16W>(0, smem);
-        st.template write_all<F16W>(smem);
-    } else {
-        if (!tile0_in_flight) st.load_all_into(0, smem);
-        if constexpr (C::P_F16) st.template write_all<0, F16W>(smem);
-        else st.write_all(smem);
-    }
+    if (!tile0_in_flight) st.template load_all_into<F16W>(0, smem);
+    st.template write_all<F16W>(smem);
     unsigned long long tw0 = 0;
     if constexpr (C::STAMP) tw0 = cycle_stamp();
     st.wait_all();
     if constexpr (C::STAMP) acc[16] += cycle_stamp() - tw0;   // (vmcnt(0): tile 0's pieces AND the previous unit's output stores)
     __syncthreads();
-    if constexpr (C::MIX) st.template load_all_into<F16W>(1, smem + SLOT);
-    else st.load_all_into(1, smem + SLOT);     // past-the-end tiles read as zeros (buffer range check)
+    st.template load_all_into<F16W>(1, smem + SLOT);   // past-the-end tiles read as zeros (buffer range check)
     constexpr int AHEAD = C::RING - 1;                 // iteration t stages tile t + AHEAD
     if constexpr (C::STAMP) tp1 = cycle_stamp();
     if (my_tiles > 0) {
@@ -188,9 +181,7 @@ __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>
         if (needs_mask(0)) w.mask(sA, 0, q_row0, S, lane);
         w.first_max(sA, c);   // m = row max of tile 0 (the reference of the optimistic pass)
     }
-    if constexpr (C::MIX) st.template write_all<F16W>(smem + SLOT);
-    else if constexpr (C::P_F16) st.template write_all<0, F16W>(smem + SLOT);
-    else st.write_all(smem + SLOT);
+    st.template write_all<F16W>(smem + SLOT);
     st.wait_all();
     __syncthreads();
     if constexpr (C::STAMP) { tp2 = cycle_stamp(); acc[8] += tp1 - tp0; acc[9] += tp2 - tp1; }
@@ -204,21 +195,11 @@ __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>
         if constexpr (C::STAMP) t0 = cycle_stamp();
         if (kind != 2) {
             const bool has_next = kind == 0;
-            if constexpr (C::P_F16 || C::MIX)
-                w.template tile_step<TRACK, F16W>(st, t + AHEAD, smem + so_wr, smem + so_nxt, smem + so_cur + KT, kbase, vbase, c, cur, nxt,
-                                                  has_next, has_next && needs_mask(t + 1), (t + 1) * KVBLK, q_row0, S, lane);
-            else
-                w.template tile_step<TRACK>(st, t + AHEAD, smem + so_wr, smem + so_nxt, smem + so_cur + KT, kbase, vbase, c, cur, nxt,
-                                            has_next, has_next && needs_mask(t + 1), (t + 1) * KVBLK, q_row0, S, lane);
+            w.template tile_step<TRACK, F16W>(st, t + AHEAD, smem + so_wr, smem + so_nxt, smem + so_cur + KT, kbase, vbase, c, cur, nxt,
+                                              has_next, has_next && needs_mask(t + 1), (t + 1) * KVBLK, q_row0, S, lane);
         } else {
-            if constexpr (C::MIX) {
-                st.template load_all_into<F16W>(t + AHEAD, smem + so_wr);
-                st.template write_all<F16W>(smem + so_wr);
-            } else {
-                st.load_all_into(t + AHEAD, smem + so_wr);
-                if constexpr (C::P_F16) st.template write_all<0, F16W>(smem + so_wr);
-                else st.write_all(smem + so_wr);
-            }
+            st.template load_all_into<F16W>(t + AHEAD, smem + so_wr);
+            st.template write_all<F16W>(smem + so_wr);
         }
         if constexpr (C::STAMP) t4 = cycle_stamp();
         st.wait_all();   // (LDS-DMA staging: this wave's pieces of tile t + AHEAD have landed)
@@ -297,6 +278,22 @@ struct UnitCtx {
     }
 };
 
+// The passes of one unit, each the fallback of the one before; tile 0 is in flight for the first only.
+// F16W = false: the optimistic pass, then the tracked pass, which is always safe.
+// F16W = true: fp16 weights need V in fp16: a finite bf16 |v| > 65504 is inf there (and 0 * inf = NaN poisons rows that do not even see
+// the key).  Both fp16 passes report a non-finite result; the last resort is the bf16-weights tracked pass -- the one a bf16 unit falls
+// back to anyway -- which holds whatever bf16 holds (the reference's V is float: kernels/FlashAttention.cuh:60).  Data that never
+// overflows pays nothing.
+template <class C, bool F16W>
+__device__ __forceinline__ void run_passes(const Params& p, WaveComputeOf<C>& w, typename WaveComputeOf<C>::Stage& st, lds_ptr smem,
+                                           const UnitCtx<C>& u, int lane, unsigned long long (&acc)[24]) {
+    if (!attention_pass<C, false, F16W>(p, w, st, smem, u.n_tiles, u.my_tiles, u.q_row0, lane, acc, true)) return;
+    if constexpr (F16W) {
+        if (!attention_pass<C, true, true>(p, w, st, smem, u.n_tiles, u.my_tiles, u.q_row0, lane, acc, false)) return;
+    }
+    attention_pass<C, true, false>(p, w, st, smem, u.n_tiles, u.my_tiles, u.q_row0, lane, acc, false);
+}
+
 // Which units a walk takes: all of its list (the persistent kernels), or the single unit (head L.units, query block L.qb0) of a
 // workgroup of fwd_mfma_pair_kernel.
 enum class Kind { ALL, ONE };
@@ -332,13 +329,9 @@ __device__ __forceinline__ void run_units(const Params& p, const UnitList& L, ld
     typename WaveComputeOf<C>::Stage st;
     const int row_bytes = C::PAD ? p.d * ESZ : D * ESZ, orow_bytes = C::PAD ? p.d * (int)sizeof(OutT) : D * (int)sizeof(OutT);
     st.init(cur.Kh, cur.Vh, kSb, vSb, Sk, wave, lane, row_bytes);
-    // tile 0 and Q travel together (one HBM round trip); C::MIX: in the form the unit's pass takes it (wave-uniform branch)
-    if constexpr (C::MIX) {
-        if (cur.early) st.template load_all_into<true>(0, smem);
-        else st.template load_all_into<false>(0, smem);
-    } else {
-        st.load_all_into(0, smem);
-    }
+    // tile 0 and Q travel together (one HBM round trip); tile 0 in the form the unit's first pass takes it (C::MIX: wave-uniform branch)
+    if (C::MIX ? cur.early : C::P_F16) st.template load_all_into<true>(0, smem);
+    else st.template load_all_into<false>(0, smem);
     if constexpr (C::COALESCED_Q) w.load_q_rows(cur.Qh, qSb, cur.q_row0, S, lane);
     else w.load_q(cur.Qh, qSb, cur.q_row0, S, lane, row_bytes);
     unsigned long long acc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -365,27 +358,12 @@ __device__ __forceinline__ void run_units(const Params& p, const UnitList& L, ld
         // An opaque copy of the lane id keeps them inside the pass.
         int lane_p = lane;
         asm volatile("" : "+v"(lane_p));
-        if constexpr (C::MIX) {
-            // both precisions in one walk: the unit's query block says which.  An fp16 unit whose passes come out non-finite (V beyond
-            // fp16's range, see below) is repeated by the bf16-weights tracked pass -- the one a bf16 unit falls back to anyway
-            if (cur.early) {
-                if (attention_pass<C, false, true>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, true))
-                    if (attention_pass<C, true, true>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false))
-                        attention_pass<C, true, false>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false);
-            } else {
-                if (attention_pass<C, false, false>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, true))
-                    attention_pass<C, true, false>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false);
-            }
-        } else if constexpr (C::P_F16) {
-            // fp16 weights need V in fp16: a finite bf16 |v| > 65504 is inf there (and 0 * inf = NaN poisons rows that do not even see
-            // the key).  Both fp16 passes report a non-finite result; the last resort is the bf16-weights tracked pass, which holds
-            // whatever bf16 holds (the reference's V is float: kernels/FlashAttention.cuh:60).  Data that never overflows pays nothing.
-            if (attention_pass<C, false, true>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, true))
-                if (attention_pass<C, true, true>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false))
-                    attention_pass<C, true, false>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false);
+        // C::MIX: both precisions in one walk, the unit's query block says which (wave-uniform).  A configuration without an fp16 form
+        // (fp8, padded, plain bf16) never instantiates the fp16 ladder
+        if (C::MIX ? cur.early : C::P_F16) {
+            if constexpr (C::MIX || C::P_F16) run_passes<C, true>(p, w, st, smem, cur, lane_p, acc);
         } else {
-            if (attention_pass<C, false>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, true))
-                attention_pass<C, true>(p, w, st, smem, cur.n_tiles, cur.my_tiles, cur.q_row0, lane_p, acc, false);
+            run_passes<C, false>(p, w, st, smem, cur, lane_p, acc);
         }
 
         // The next unit's tile 0 and Q are requested ahead, so that their HBM round trip runs under this unit's epilogue
@@ -399,12 +377,8 @@ __device__ __forceinline__ void run_units(const Params& p, const UnitList& L, ld
         if (more) {
             nxt.set(p, g, qb, wave);
             st.init(nxt.Kh, nxt.Vh, kSb, vSb, Sk, wave, lane, row_bytes);
-            if constexpr (C::MIX) {
-                if (nxt.early) st.template load_all_into<true>(0, smem);   // (V in registers across the epilogue)
-                else st.template load_all_into<false>(0, smem);
-            } else {
-                st.load_all_into(0, smem);
-            }
+            if (C::MIX ? nxt.early : C::P_F16) st.template load_all_into<true>(0, smem);   // (V in registers across the epilogue)
+            else st.template load_all_into<false>(0, smem);
             // (opaque lane: a hoisted per-lane Q address is spilled across the tile loop, and its reload's vmcnt(0)
             // would make the Q loads wait for the tile-0 loads just issued)
             int lane_n = lane;

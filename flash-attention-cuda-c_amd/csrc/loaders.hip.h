@@ -128,6 +128,32 @@ __device__ __forceinline__ int v16_read_base(int lane) {
     return (h4 >> 1) * (D / 16 * 256) + (4 * (h4 & 1) + q) * 32 + 8 * p;
 }
 
+// The staging interface.  A stage class moves this wave's share of a 64-key tile from global memory into a ring slot, in numbered pieces
+// that the engines place in their MFMA slots.  All four classes below (BufStage, DmaStage, MixStage, HybridStageFp8) have
+//   init(Kh, Vh, kS_bytes, vS_bytes, S, wave, lane, row_bytes)   descriptors and per-lane offsets of one (batch, head)
+//   set_dst(slot)                  the ring slot the next loads go to (LDS-DMA pieces need it at load time)
+//   load<N, F16W = false>(t)       request piece N < NL of tile t
+//   write<N, F16W = false>(slot)   LDS write N < NW of the tile loaded last (whatever went by DMA has none)
+//   wait_all()                     this wave's DMA pieces have landed (then a barrier publishes the tile)
+//   load_all_into<F16W = false>(t, slot), write_all<F16W = false>(slot)   all pieces at once (StageAll): prologues, staging-only steps
+//   NL, NW, K_DMA (the K image is the DMA form, of KBLK bytes per 8-key block)
+// F16W: the pass runs with fp16 softmax weights, so V has to reach LDS as fp16.  A property of the pass, not of the kernel; a stage to
+// which it means nothing (DmaStage, HybridStageFp8, BufStage under the bf16 / fp8 / padded kernels, which never pass true) ignores it.
+template <class St>
+struct StageAll {
+    template <bool F16W = false, int N = 0>
+    __device__ __forceinline__ void load_all_into(int t, lds_ptr slot) {
+        St& st = *static_cast<St*>(this);
+        if constexpr (N == 0) st.set_dst(slot);
+        if constexpr (N < St::NL) { st.template load<N, F16W>(t); load_all_into<F16W, N + 1>(t, slot); }
+    }
+    template <bool F16W = false, int N = 0>
+    __device__ __forceinline__ void write_all(lds_ptr slot) {
+        St& st = *static_cast<St*>(this);
+        if constexpr (N < St::NW) { st.template write<N, F16W>(slot); write_all<F16W, N + 1>(slot); }
+    }
+};
+
 // K/V tile staging.  One wave-instruction = 8 keys x 128 bytes.  A 64-key tile is 8 key groups x
 // (ROWB/128) column halves; with NWAVES waves each wave owns GPW = 8/NWAVES consecutive key groups.
 //   K lanes: key 8g + (l&7),                    16-byte chunk (l>>3)          [+8 for the second 128-byte half]
@@ -138,9 +164,8 @@ __device__ __forceinline__ int v16_read_base(int lane) {
 // V16: the V image of the 16x16x32 kernels (TileGeom::v16_lds_off); its lanes are
 //   V lanes: key 8g + 4*((l>>3)&1) + ((l&7)>>1), 16-byte chunk 2*(l>>4) + (l&1)  [+8 for the second 128-byte half]
 // (each 8-lane group still writes 128 contiguous LDS bytes; +8 keys and +8 chunks cost the same strides as above).
-// VF16: bf16 V is converted to fp16 on its way into the V image (the fp16-weights option of the 16x16x32 engine).
-template <int D, int ESZ, int NWAVES = 8, bool PAD = false, bool V16 = false, bool VF16 = false>
-struct BufStage {
+template <int D, int ESZ, int NWAVES = 8, bool PAD = false, bool V16 = false>
+struct BufStage : StageAll<BufStage<D, ESZ, NWAVES, PAD, V16>> {
     using G = TileGeom<D, ESZ>;
     static constexpr int HALVES = G::ROWB / 128;                 // 128-byte halves of a row
     static constexpr int GPW = 8 / NWAVES;                       // key groups per wave
@@ -191,32 +216,28 @@ struct BufStage {
     }
     // load #N of tile t (N < LOADS: K, else V): key group g0 + n/HALVES, 128-byte half n%HALVES.  The tile
     // offset goes into the VGPR offset (v_add with scalar operands) so the hardware range check covers it.
-    template <int N>
-    __device__ __forceinline__ void load(int t) { load_to<N>(r, t); }
-    template <int N>
-    __device__ __forceinline__ void load_to(u32x4 (&dst)[NL], int t) const {
+    template <int N, bool F16W = false>
+    __device__ __forceinline__ void load(int t) {
         constexpr int n = N < LOADS ? N : N - LOADS;
         constexpr int gi = n / HALVES, hf = n % HALVES;
         if constexpr (N < LOADS)
-            dst[N] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + t * ktile + gi * kgrp + hf * 128, 0, 0));
+            r[N] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, koff + t * ktile + gi * kgrp + hf * 128, 0, 0));
         else
-            dst[N] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + t * vtile + gi * vgrp + hf * 128, 0, 0));
+            r[N] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrsrc, voff + t * vtile + gi * vgrp + hf * 128, 0, 0));
     }
     // LDS write #N: the K writes, then the V writes.  K image: +8 keys = +128 B, +8 chunks = +8 KiB.
     // V image: +8 keys = +DB*512 B, +8 bf16 chunks = +1 KiB.
-    // F16: convert bf16 V to fp16 on the way (the class's VF16 unless the caller says otherwise: the fp16-weights kernels' bf16-weights
-    // fallback pass, computers16.hip.h, writes the same image unconverted)
-    template <int N, bool F16 = VF16>
-    __device__ __forceinline__ void write(lds_ptr slot_base) const { write_from<N, F16>(r, slot_base); }
-    template <int N, bool F16 = VF16>
-    __device__ __forceinline__ void write_from(const u32x4 (&r)[NL], lds_ptr slot_base) const {
+    // F16W: bf16 V is converted to fp16 on the way (the fp16-weights kernels; their bf16-weights fallback pass writes the same image
+    // unconverted)
+    template <int N, bool F16W = false>
+    __device__ __forceinline__ void write(lds_ptr slot_base) const {
         if constexpr (N < LOADS) {
             constexpr int gi = N / HALVES, hf = N % HALVES;
             lds_write_b128(slot_base, klds + gi * 128 + hf * 8192, PAD ? keep_if(kok[hf], r[N]) : r[N]);
         } else if constexpr (ESZ == 2) {
             constexpr int n = N - LOADS, gi = n / HALVES, hf = n % HALVES;
             const u32x4 v = PAD ? keep_if(vok[hf], r[N]) : r[N];
-            lds_write_b128(slot_base + G::K_TILE, vlds + gi * (G::DB * 512) + hf * 1024, F16 ? bf16x8_to_f16x8(v) : v);
+            lds_write_b128(slot_base + G::K_TILE, vlds + gi * (G::DB * 512) + hf * 1024, F16W ? bf16x8_to_f16x8(v) : v);
         } else {
             // fp8 V (ROWB = 128, one half): 16 e4m3fn bytes -> 16 bf16 (exact), two adjacent 16-byte chunks
             constexpr int n = (N - LOADS) / 2, W = (N - LOADS) % 2;   // load n of this tensor, low / high 8 bytes
@@ -224,17 +245,11 @@ struct BufStage {
             lds_write_b128(slot_base + G::K_TILE, vlds + n * (G::DB * 512) + W * 16, fp8x8_to_bf16x8(src[2 * W], src[2 * W + 1]));
         }
     }
-    template <int N = 0> __device__ __forceinline__ void load_all_to(u32x4 (&dst)[NL], int t) const { if constexpr (N < NL) { load_to<N>(dst, t); load_all_to<N + 1>(dst, t); } }
-    template <int N = 0> __device__ __forceinline__ void write_all_from(const u32x4 (&src)[NL], lds_ptr s) const { if constexpr (N < NW) { write_from<N>(src, s); write_all_from<N + 1>(src, s); } }
-    template <int N = 0> __device__ __forceinline__ void load_all(int t) { if constexpr (N < NL) { load<N>(t); load_all<N + 1>(t); } }
-    template <int N = 0, bool F16 = VF16> __device__ __forceinline__ void write_all(lds_ptr s) const { if constexpr (N < NW) { write<N, F16>(s); write_all<N + 1, F16>(s); } }
-    // (interface shared with DmaStage, whose loads need their LDS destination)
     __device__ __forceinline__ void set_dst(lds_ptr) {}
-    __device__ __forceinline__ void load_all_into(int t, lds_ptr) { load_all(t); }
     __device__ __forceinline__ void wait_all() const {}
 };
 
-// ---- LDS-DMA staging (Opt::dma; bf16, unpadded rows, 8 waves) -------------------------------------------------------------
+// ---- LDS-DMA staging (KernelCfg::DMA: bf16, unpadded rows) ------------------------------------------------------------------
 // K/V tiles go global -> LDS by `buffer_load_dwordx4 ... lds`: no staging registers, no ds_write.  One wave-instruction writes 1 KiB
 // of LDS linearly (lane l -> M0 base + 16 l) from per-lane SOURCE addresses, so the images must be cut into 1-KiB pieces whose lane
 // order still reads whole 128-byte lines of global memory:
@@ -256,7 +271,7 @@ __device__ __forceinline__ int kd16_read_base(int lane, int blk_bytes) {  // 16x
     return (r >> 3) * blk_bytes + h4 * 128 + (r & 7) * 16;
 }
 template <int D, int NWAVES, bool V16, bool KXOR>
-struct DmaStage {
+struct DmaStage : StageAll<DmaStage<D, NWAVES, V16, KXOR>> {
     using G = TileGeom<D, 2>;
     static constexpr int HALVES = G::ROWB / 128;
     static constexpr int GPW = 8 / NWAVES;                        // 8-key groups per wave (8 waves: 1; 4 waves: 2)
@@ -307,7 +322,7 @@ struct DmaStage {
 #pragma clang diagnostic pop
     }
     // piece #N of tile t (N < LOADS: K, else V) -> ring slot `dst`: key group gi = n / HALVES of this wave, 1-KiB piece j = n % HALVES
-    template <int N>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void load(int t) const {
         constexpr int n = N < LOADS ? N : N - LOADS, gi = n / HALVES, j = n % HALVES;
         if constexpr (N < LOADS) dma16(krsrc, dst + kdst + gi * KBLK + j * 1024, koff[gi] + t * ktile + j * 128);
@@ -315,11 +330,8 @@ struct DmaStage {
     }
     // every piece this wave has issued has landed in LDS (then a barrier publishes it to the other waves)
     __device__ __forceinline__ void wait_all() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    template <int N>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void write(lds_ptr) const {}
-    template <int N = 0> __device__ __forceinline__ void load_all(int t) const { if constexpr (N < NL) { load<N>(t); load_all<N + 1>(t); } }
-    __device__ __forceinline__ void load_all_into(int t, lds_ptr slot) { set_dst(slot); load_all(t); }
-    __device__ __forceinline__ void write_all(lds_ptr) const {}
 };
 
 // ---- bf16 inputs, both weight precisions in one kernel (KernelCfg::MIX: the causal default) ------------------------------------------------
@@ -331,10 +343,10 @@ struct DmaStage {
 // hipcc's counted vmcnt for the V data never waits on a younger DMA.
 // V16 / KXOR: the engine's V image and K slot swap (32x32x16: false / true; 16x16x32: true / false), as in DmaStage.
 template <int D, int NWAVES, bool V16 = false, bool KXOR = true>
-struct MixStage {
+struct MixStage : StageAll<MixStage<D, NWAVES, V16, KXOR>> {
     using G = TileGeom<D, 2>;
     using Dma = DmaStage<D, NWAVES, V16, KXOR>;
-    using VPath = BufStage<D, 2, NWAVES, false, V16, true>;     // (its K half stays unused)
+    using VPath = BufStage<D, 2, NWAVES, false, V16>;           // (its K half stays unused)
     static constexpr int LOADS = Dma::LOADS;                     // pieces (DMA) or 16-byte loads per lane (registers) per tensor per tile
     static constexpr int NL = 2 * LOADS, NW = LOADS;             // NW: ds_write_b128 per lane per tile, fp16 form only
     static constexpr int KBLK = G::KBLK;
@@ -348,27 +360,24 @@ struct MixStage {
         v.init(Kh, Vh, kS_bytes, vS_bytes, S, wave, lane, row_bytes);
     }
     __device__ __forceinline__ void set_dst(lds_ptr slot) { d.set_dst(slot); }
-    template <int N, bool F16W>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void load(int t) {
         if constexpr (N < LOADS || !F16W) d.template load<N>(t);
         else v.template load<N>(t);                              // (BufStage numbers its V loads LOADS .. 2 LOADS - 1 too)
     }
-    template <int N, bool F16W>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void write(lds_ptr slot_base) const {
         if constexpr (F16W) v.template write<LOADS + N, true>(slot_base);
     }
     __device__ __forceinline__ void wait_all() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    template <bool F16W, int N = 0> __device__ __forceinline__ void load_all(int t) { if constexpr (N < NL) { load<N, F16W>(t); load_all<F16W, N + 1>(t); } }
-    template <bool F16W> __device__ __forceinline__ void load_all_into(int t, lds_ptr slot) { set_dst(slot); load_all<F16W>(t); }
-    template <bool F16W, int N = 0> __device__ __forceinline__ void write_all(lds_ptr s) const { if constexpr (N < NW) { write<N, F16W>(s); write_all<F16W, N + 1>(s); } }
 };
 
-// ---- fp8 inputs (Opt::dma, unpadded rows, 8 waves): K by LDS-DMA, V through registers -------------------------------------------
+// ---- fp8 inputs (KernelCfg::DMA_K8: d = 128, unpadded rows, 8 waves): K by LDS-DMA, V through registers -------------------------------------------
 // K rows are 128 bytes of e4m3: the tile's K image (8 KiB, DMA form with the 32x32x16 engine's slot swap) is eight 1-KiB pieces, one per
 // wave.  V has to be widened to bf16 between the load and the LDS write, so it keeps BufStage's register path (1 load, 2 ds_write_b128).
 // The DMA is issued BEFORE the V load of the same tile: hipcc's counted vmcnt for the V data then never waits on a younger DMA.
 template <int D, int NWAVES>
-struct HybridStageFp8 {
+struct HybridStageFp8 : StageAll<HybridStageFp8<D, NWAVES>> {
     using G = TileGeom<D, 1>;
     using VPath = BufStage<D, 1, NWAVES, false>;
     static_assert(NWAVES == 8 && G::ROWB == 128, "fp8 K by DMA: 8 waves, 128-byte rows");
@@ -389,17 +398,14 @@ struct HybridStageFp8 {
         kdst = wave * KBLK;
     }
     __device__ __forceinline__ void set_dst(lds_ptr slot) { dst = (uint32_t)(uintptr_t)slot; }
-    template <int N>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void load(int t) {
         if constexpr (N == 0) DmaStage<128, 8, false, true>::dma16(krsrc, dst + kdst, koff + t * ktile);
         else v.template load<1>(t);
     }
-    template <int N>
+    template <int N, bool F16W = false>
     __device__ __forceinline__ void write(lds_ptr slot_base) const { v.template write<N + 1>(slot_base); }
     __device__ __forceinline__ void wait_all() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    __device__ __forceinline__ void load_all(int t) { load<0>(t); load<1>(t); }
-    __device__ __forceinline__ void load_all_into(int t, lds_ptr slot) { set_dst(slot); load_all(t); }
-    __device__ __forceinline__ void write_all(lds_ptr s) const { write<0>(s); write<1>(s); }
 };
 
 }  // namespace fa
