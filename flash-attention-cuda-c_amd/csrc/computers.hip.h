@@ -34,9 +34,10 @@
 // overall slot E*SPAN/(32R), SPAN = (NA + 3*NB/4)*R, which meets "P group (g, r) complete before its PV
 // slot" with <= 1.25 elements per 32-cycle MFMA gap at d = 128.  Empty asm statements pin the partial
 // sums / maxima in their slot (hipcc otherwise sinks them behind the MFMAs).
+// The slot plan and the tile step around the two slot sequences are shared with the 16x16x32 engine: slot_engine.hip.h.
 #pragma once
 
-#include "loaders.hip.h"
+#include "slot_engine.hip.h"
 
 namespace fa {
 
@@ -46,7 +47,7 @@ struct Scores {          // raw scores of one 64-key tile: [row group][32-key ha
 };
 
 template <class C>
-struct WaveCompute {
+struct WaveCompute : SlotEngine<WaveCompute<C>, C> {
     static constexpr int D = C::D, ESZ = C::ESZ, R = 1;   // R: 32-row query groups per wave
     static constexpr int KS = D / 16;              // MFMA k-steps of one 32-key half of QK^T
     static constexpr int DB = D / 32;              // 32-wide d blocks of O^T
@@ -57,6 +58,7 @@ struct WaveCompute {
     static constexpr int FPH = NF / 2;             // ... per 32-key half = Q fragments per row group
     static constexpr int NPRE = C::NPRE < NF ? C::NPRE : NF;
     static constexpr int VPRE = C::VPRE;
+    static constexpr int GROUPS = R, RG = 32, LOG_RG = 5, FPG = FPH;   // the wave's query rows, as slot_engine.hip.h sees them
     static constexpr int NE = 32 * R;              // score elements per lane per tile
     static constexpr int SPAN = SA + (3 * SB) / 4; // overall slots the exponentials are spread over
     using G = TileGeom<D, ESZ>;
@@ -65,8 +67,6 @@ struct WaveCompute {
                                      std::conditional_t<C::DMA_K8, HybridStageFp8<D, C::NWAVES>, BufStage<D, ESZ, C::NWAVES, C::PAD>>>>;
     using ScoresT = Scores<R>;
     static constexpr int NL = Stage::NL, NW = Stage::NW;
-    static constexpr int WSTEP = 2 * NW <= SB / 2 + 1 ? 2 : 1;   // LDS writes sit in every WSTEP-th slot of the second half of phase B
-    static_assert(2 * NL <= SA && WSTEP * (NW - 1) < SB - SB / 2, "staging does not fit the slot plan");
 
     // ---- state that lives across tiles ----
     u32x4 qf[R][FPH];  // Q fragments (16 bytes each: one bf16 MFMA operand, or two fp8 operands)
@@ -81,21 +81,6 @@ struct WaveCompute {
     bool need;         // tracked pass: lazy-rescale decision for S(t+1)
     unsigned long long t_mid = 0, t_end = 0;   // STAMP builds only
 
-    __host__ __device__ static constexpr int elem_slot(int E) { return E * SPAN / NE; }
-    // overall slot (0 .. SA + SB - 1) that issues staging load / LDS-DMA piece n of the tile two ahead: the odd slots from 1 on.
-    // (Later is worse -- the pieces then land after the end-of-step wait: phase A's second half -2.6 %, phase B -9 ... -13 %,
-    //  profiles/r03_tune_c_dma_slots_*.log.)
-    __host__ __device__ static constexpr int load_slot(int n) { return 1 + 2 * n; }
-    // F16W (mixed-precision kernels, C::MIX, only): the unit runs with fp16 softmax weights -- P rounded to fp16, V staged as fp16 through
-    // registers (MixStage), P.V on v_mfma_f32_32x32x16_f16.  A property of the pass, handed down as a template argument.
-    template <int SLOT, bool F16W = false, int N = 0>
-    __device__ __forceinline__ void load_in_slot(Stage& st, int t_load) {
-        if constexpr (N < NL) {
-            if constexpr (load_slot(N) == SLOT) st.template load<N, F16W>(t_load);
-            load_in_slot<SLOT, F16W, N + 1>(st, t_load);
-        }
-    }
-
     __device__ __forceinline__ void init() {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -106,74 +91,6 @@ struct WaveCompute {
             m[r] = -INFINITY;
             l[r] = 0.f;
         }
-    }
-
-    // Q fragment u of row q: 16 bytes at byte 32u + 16h of the row.  bf16: d = 16u + 8h .. +7 (k-step u).
-    // fp8: d = 32u + 16h .. +15 -- the contraction order is permuted the same way for K (chunk 2u+h of
-    // the K image), so one 16-byte fragment feeds two MFMAs.
-    // row_bytes < D*ESZ (C::PAD): fragments past the end of the row are zero and are never read from memory.
-    __device__ __forceinline__ void load_q(const char* Qh, int64_t qS_bytes, int row0, int S, int lane, int row_bytes = D * ESZ) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int row = row0 + 32 * r + (lane & 31);
-            row = row < S ? row : S - 1;
-            const char* src = Qh + row * qS_bytes + (lane >> 5) * 16;
-#pragma unroll
-            for (int u = 0; u < FPH; ++u) {
-                if constexpr (C::PAD) {
-                    qf[r][u] = u32x4{0u, 0u, 0u, 0u};
-                    if (u * 32 + (lane >> 5) * 16 < row_bytes) qf[r][u] = *reinterpret_cast<const u32x4*>(src + u * 32);
-                } else {
-                    qf[r][u] = *reinterpret_cast<const u32x4*>(src + u * 32);
-                }
-            }
-        }
-    }
-    // Coalesced form (KernelCfg::COALESCED_Q).  load_q above has every lane read 16-byte pieces of its own row: one
-    // instruction touches 32 rows x 2 pieces, 64 separate 16-byte requests.  Here instruction i fetches 64/CH WHOLE
-    // rows (CH = 16-byte chunks per row; lane = (row, chunk)), and the fragments are formed by one trip through
-    // this wave's private LDS region: chunk c of row q is parked at chunk c ^ (q & (CH-1)), so the 16 rows of a
-    // ds_read_b128 lane group land on different banks.  Same instruction count, a quarter of the memory requests.
-    static constexpr int QCH = (D * ESZ) / 16;     // 16-byte chunks per Q row
-    static constexpr int QRPI = 64 / QCH;          // rows fetched per instruction
-    static_assert(32 / QRPI == FPH, "coalesced Q: as many loads as fragments");
-    __device__ __forceinline__ void load_q_rows(const char* Qh, int64_t qS_bytes, int row0, int S, int lane) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int i = 0; i < FPH; ++i) {
-                int row = row0 + 32 * r + i * QRPI + lane / QCH;
-                row = row < S ? row : S - 1;
-                qf[r][i] = *reinterpret_cast<const u32x4*>(Qh + row * qS_bytes + (lane % QCH) * 16);
-            }
-    }
-    // region: 32*R rows x D*ESZ bytes private to this wave, not aliased by anything live (kernel_bf16.hip.h)
-    __device__ __forceinline__ void q_rows_to_fragments(lds_ptr region, int lane) {
-        constexpr int ROWB = D * ESZ;
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int i = 0; i < FPH; ++i) {
-                const int q = 32 * r + i * QRPI + lane / QCH, c = lane % QCH;
-                lds_write_b128(region, q * ROWB + (((c ^ q) & (QCH - 1)) << 4), qf[r][i]);
-            }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // own writes only: LDS executes a wave's accesses in order
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int u = 0; u < FPH; ++u) {
-                const int q = 32 * r + (lane & 31), c = 2 * u + (lane >> 5);
-                qf[r][u] = __builtin_bit_cast(u32x4, lds_read_b128(region, q * ROWB + (((c ^ q) & (QCH - 1)) << 4)));
-            }
-    }
-
-    // Make the Q fragments look "consumed" so hipcc waits for their loads HERE and not with a
-    // pessimistic vmcnt inside the main loop (where it would also drain the tile prefetch).
-    __device__ __forceinline__ void pin_q() {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int u = 0; u < FPH; ++u) asm volatile("" : "+v"(qf[r][u]));
     }
 
     // Fragment f = (k-step u = f % FPH, 32-key half kt = f / FPH)
@@ -241,11 +158,7 @@ struct WaveCompute {
         }
         return fmaxf(a, b);
     }
-    // Tile 0 of a pass: m = its row max (m = -inf before; O and l are still 0).
-    __device__ __forceinline__ void first_max(const Scores<R>& n, float c) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) m[r] = fmaxf(m[r], max_both_halves(row_max(n, r)) * c);
-    }
+    __device__ __forceinline__ static float max_over_row(float x) { return max_both_halves(x); }
 
     // ---- softmax slices ------------------------------------------------------------------------
     // Element E (0..32R-1) = (key group g = E/(8R), row group r = (E/8)%R, j = E%8) -> score 8g+j of row group r.
@@ -277,13 +190,6 @@ struct WaveCompute {
             }
         }
     }
-    template <int SLOT, bool F16W = false, int E = 0>
-    __device__ __forceinline__ void exp_slot(const Scores<R>& cur, float c) {
-        if constexpr (E < NE) {
-            if constexpr (elem_slot(E) == SLOT) exp_elem<E, F16W>(cur, c);
-            exp_slot<SLOT, F16W, E + 1>(cur, c);
-        }
-    }
     __device__ __forceinline__ bf16x8 p_frag(int r, int g) const {
         u32x4 v = {pw[r][4 * g], pw[r][4 * g + 1], pw[r][4 * g + 2], pw[r][4 * g + 3]};
         return __builtin_bit_cast(bf16x8, v);
@@ -303,16 +209,6 @@ struct WaveCompute {
 #pragma unroll
         for (int r = 0; r < R; ++r) asm volatile("" : "+v"(mx_a[r]), "+v"(mx_b[r]));
     }
-    __device__ __forceinline__ void decide(float c) {
-        bool any = false;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float mx = max_both_halves(fmaxf(mx_a[r], mx_b[r])) * c;
-            any = any || (mx > m[r] + (float)C::THR);
-            mx_a[r] = mx;   // keep the scaled row max for the rescale body
-        }
-        need = __any(any);
-    }
 
     // V^T A-fragment of 16-key step s4, d block db: two transposed reads.  Element j of lane half h is
     // key 16*s4 + 8*(j>>2) + 4h + (j&3) -- exactly the key order of the packed P^T fragment.
@@ -330,7 +226,7 @@ struct WaveCompute {
                                             float c, const Scores<R>& cur, Scores<R>& nxt) {
         if constexpr (I < SA) {
             constexpr int f = I / (MPF * R), rem = I % (MPF * R), sub = rem / R, rg = rem % R;
-            if constexpr (C::VALU_FIRST) exp_slot<I, F16W>(cur, c);   // softmax slice covers the fragment's LDS latency
+            if constexpr (C::VALU_FIRST) this->template exp_slot<I, F16W>(cur, c);   // softmax slice covers the fragment's LDS latency
             qk_mfma<f, sub, rg>(kf[(f + NPRE - 1) % NPRE], kf[f % NPRE], nxt);
             if constexpr (C::MXQK) {
                 // both fragments of a pair stay live until the pair's MFMA: refill the two window entries after it
@@ -345,8 +241,8 @@ struct WaveCompute {
                 constexpr int v = I - (SA - VPRE);
                 vf[v % (VPRE + 1)] = v_frag(v_cur, vbase, v / DB, v % DB);
             }
-            load_in_slot<I, F16W>(st, t_load);
-            if constexpr (!C::VALU_FIRST) exp_slot<I, F16W>(cur, c);
+            this->template load_in_slot<I, F16W>(st, t_load);
+            if constexpr (!C::VALU_FIRST) this->template exp_slot<I, F16W>(cur, c);
             __builtin_amdgcn_sched_barrier(0);
             slots_a<I + 1, F16W>(st, t_load, k_next, v_cur, kbase, vbase, c, cur, nxt);
         }
@@ -363,24 +259,17 @@ struct WaveCompute {
                 constexpr int vn = v + VPRE;
                 vf[vn % (VPRE + 1)] = v_frag(v_cur, vbase, vn / DB, vn % DB);
             }
-            exp_slot<SA + J, F16W>(cur, c);
+            this->template exp_slot<SA + J, F16W>(cur, c);
             if constexpr (TRACK && J < SB / 2) max3_slot<J>(nxt);
-            if constexpr (TRACK && J == SB / 2) decide(c);
-            if constexpr (J >= SB / 2 && (J - SB / 2) % WSTEP == 0 && (J - SB / 2) / WSTEP < NW)
-                st.template write<(J - SB / 2) / WSTEP, F16W>(wr_slot);
+            if constexpr (TRACK && J == SB / 2) this->decide(c);
+            this->template write_in_slot<J, F16W>(st, wr_slot);
             __builtin_amdgcn_sched_barrier(0);
             slots_b<TRACK, J + 1, F16W>(st, wr_slot, v_cur, vbase, c, cur, nxt);
         }
     }
 
-    // One tile: cur = S(t) (consumed), nxt = S(t+1) (produced; on the wave's last tile it is computed from a tile the wave
-    // does not need and ignored: one hot code path).
-    // TRACK = true: running row max with lazy rescale (always safe).  TRACK = false: the optimistic
-    // pass -- m stays the row max of tile 0 and no max / decision / rescale is issued.
-    template <bool TRACK, bool F16W = false>
-    __device__ __forceinline__ void tile_step(Stage& st, int t_load, lds_ptr wr_slot, lds_ptr k_next, lds_ptr v_cur,
-                                              int kbase, int vbase, float c, const Scores<R>& cur, Scores<R>& nxt,
-                                              bool has_next, bool mask_next, int kv0_next, int q_row0, int S, int lane) {
+    // ---- what SlotEngine::tile_step leaves to the engine ----
+    __device__ __forceinline__ void begin_tile(Stage& st, lds_ptr wr_slot, Scores<R>& nxt) {
         st.set_dst(wr_slot);   // (LDS-DMA staging: where this iteration's loads land)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -388,50 +277,21 @@ struct WaveCompute {
             mx_a[r] = mx_b[r] = -INFINITY;
         }
         zero(nxt);
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) kf[i] = k_read(k_next, kbase, i);
-        if constexpr (C::PRIO_A) __builtin_amdgcn_s_setprio(1);
-        __builtin_amdgcn_sched_barrier(0);
-        slots_a<0, F16W>(st, t_load, k_next, v_cur, kbase, vbase, c, cur, nxt);
-        if constexpr (C::PRIO_A) {
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (C::STAMP) t_mid = cycle_stamp();
-        slots_b<TRACK, 0, F16W>(st, wr_slot, v_cur, vbase, c, cur, nxt);
-        if constexpr (C::STAMP) t_end = cycle_stamp();
+    }
+    __device__ __forceinline__ void end_sums() {
         if constexpr (C::LATE_ADD) {   // (the tile's last weight: element NE - 1 is an odd key of the last row group)
             static_assert(((NE - 1) % 8) & 1, "the last element feeds sum_b");
             sum_b[((NE - 1) / 8) % R] += p_last;
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) l[r] += sum_a[r] + sum_b[r];
-        // ONE rescale site: the masked (diagonal / ragged) tile only recomputes the scalar decision and
-        // the row max.  (Two sites that both multiply O made hipcc copy all 64 accumulator registers
-        // twice per tile on the common path.)
-        if (has_next && mask_next) {
-            mask(nxt, kv0_next, q_row0, S, lane);
-            if constexpr (TRACK) {
+    }
+    __device__ __forceinline__ void rescale(int r, float alpha) {
+        l[r] *= alpha;
 #pragma unroll
-                for (int r = 0; r < R; ++r) { mx_a[r] = row_max(nxt, r); mx_b[r] = mx_a[r]; }
-                decide(c);
-            }
-        }
-        if constexpr (TRACK) {
-            if (has_next && need) {
+        for (int i = 0; i < DB; ++i)
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float mn = fmaxf(m[r], mx_a[r]);
-                    const float alpha = fast_exp2(m[r] - mn);
-                    m[r] = mn;
-                    l[r] *= alpha;
-#pragma unroll
-                    for (int i = 0; i < DB; ++i)
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) o[r][i][k] *= alpha;
-                }
-            }
-        }
+            for (int k = 0; k < 16; ++k) o[r][i][k] *= alpha;
     }
 
     // True iff a row sum or any O accumulator of this lane is inf / NaN (x*0 is NaN for both).  Four independent
@@ -451,12 +311,6 @@ struct WaveCompute {
     }
 
     // ---- epilogues -----------------------------------------------------------------------------
-    // ln sum_k exp(scale*s_k) = (m + log2 l) * ln 2   (m is the reference max in the scaled log2 domain)
-    __device__ __forceinline__ void store_lse(float* lse_head, float l_tot, int r, int row0, int S, int lane) const {
-        const int qi = row0 + (lane & 31);
-        if (lse_head && lane < 32 && qi < S) lse_head[qi] = (m[r] + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-    }
-
     // 2-byte outputs: O^T accumulators -> this wave's private LDS region as a row-major [32R rows][D] tile
     // -> whole rows back out with 16-byte stores (each 16- or 8-lane group writes one full row).  Storing
     // straight from the accumulators issues 16 eight-byte stores per lane that touch 32 rows each: ~8k cycles per workgroup,
@@ -472,7 +326,7 @@ struct WaveCompute {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const float l_tot = sum_both_halves(l[r]);
-            store_lse(lse_head, l_tot, r, row0 + 32 * r, S, lane);
+            this->store_lse(lse_head, l_tot, r, row0, S, lane);
             const float inv = 1.0f / l_tot;
 #pragma unroll
             for (int db = 0; db < DB; ++db)
@@ -525,7 +379,7 @@ struct WaveCompute {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const float l_tot = sum_both_halves(l[r]);
-            store_lse(lse_head, l_tot, r, row0 + 32 * r, S, lane);
+            this->store_lse(lse_head, l_tot, r, row0, S, lane);
             inv[r] = 1.0f / l_tot;
         }
         const int rr = lane >> 4, cc = lane & 15;

@@ -1,7 +1,7 @@
 // computers16.hip.h -- per-wave compute of the fused forward pass on the 16x16x32 bf16 MFMA.
 //
-// Same algorithm and the same slot discipline as computers.hip.h (the counterpart of the reference's
-// kernels/computers.cuh:5-69 and kernels/utils.cuh:17-45, :58-81, :93-113), on v_mfma_f32_16x16x32_bf16 instead of
+// Same algorithm as computers.hip.h (the counterpart of the reference's kernels/computers.cuh:5-69 and kernels/utils.cuh:17-45,
+// :58-81, :93-113) under the slot discipline both engines share (slot_engine.hip.h), on v_mfma_f32_16x16x32_bf16 instead of
 // v_mfma_f32_32x32x16_bf16.  Why a second shape: on real (random) data MI355X is POWER limited, and the 16x16x32 form
 // moves half the accumulator registers per FLOP -- MFMA-only microbenchmark on random bf16 operands, whole chip:
 // 2353 TFLOP/s @ 2.27 GHz against 1854 @ 1.77 GHz for 32x32x16 (tests/micro/simd_mix, profiles/r02_simd_mix_m16.log);
@@ -37,7 +37,7 @@
 
 #include <type_traits>
 
-#include "loaders.hip.h"
+#include "slot_engine.hip.h"
 
 namespace fa {
 
@@ -46,11 +46,12 @@ struct Scores16 {        // raw scores of one 64-key tile: [16-key group][16-row
 };
 
 template <class C>
-struct WaveCompute16 {
+struct WaveCompute16 : SlotEngine<WaveCompute16<C>, C> {
     static constexpr int D = C::D, ESZ = C::ESZ;
     static_assert(ESZ == 2, "16x16x32 path: bf16 inputs");
     static constexpr int KS = D / 32;              // 32-wide k-steps of QK^T
     static constexpr int KG = 4, QG = 2;           // 16-key groups per tile, 16-row query groups per wave
+    static constexpr int GROUPS = QG, RG = 16, LOG_RG = 4, FPG = KS;   // the wave's query rows, as slot_engine.hip.h sees them
     static constexpr int DG = D / 16;              // 16-wide d groups of O^T
     static constexpr int NF = KG * KS;             // K fragments per tile
     static constexpr int NV = 2 * DG;              // V^T fragments per tile (2 k-steps of 32 keys)
@@ -69,8 +70,6 @@ struct WaveCompute16 {
     template <bool F16W> using pv_of = std::conditional_t<F16W, f16x8, bf16x8>;
     using ScoresT = Scores16;
     static constexpr int NL = Stage::NL, NW = Stage::NW;
-    static constexpr int WSTEP = 2 * NW <= SB / 2 + 1 ? 2 : 1;   // LDS writes sit in every WSTEP-th slot of the second half of phase B
-    static_assert(2 * NL <= SA && WSTEP * (NW - 1) < SB - SB / 2, "staging does not fit the slot plan");
 
     // ---- state that lives across tiles ----
     u32x4 qf[QG][KS];   // Q fragments
@@ -85,19 +84,6 @@ struct WaveCompute16 {
     float mx_a[QG], mx_b[QG], p_even, sum_a[QG], sum_b[QG];
     bool need;
     unsigned long long t_mid = 0, t_end = 0;   // STAMP builds only
-
-    __host__ __device__ static constexpr int elem_slot(int E) { return E * SPAN / NE; }
-    // overall slot (0 .. SA + SB - 1) that issues staging load / LDS-DMA piece n of the tile two ahead: the odd slots from 1 on.
-    // (Later is worse -- the pieces then land after the end-of-step wait: phase A's second half -2.6 %, phase B -9 ... -13 %,
-    //  profiles/r03_tune_c_dma_slots_*.log.)
-    __host__ __device__ static constexpr int load_slot(int n) { return 1 + 2 * n; }
-    template <int SLOT, bool F16W = false, int N = 0>
-    __device__ __forceinline__ void load_in_slot(Stage& st, int t_load) {
-        if constexpr (N < NL) {
-            if constexpr (load_slot(N) == SLOT) st.template load<N, F16W>(t_load);   // (MixStage: V by DMA or, fp16 units, through registers)
-            load_in_slot<SLOT, F16W, N + 1>(st, t_load);
-        }
-    }
 
     __device__ __forceinline__ void init() {
 #pragma unroll
@@ -122,61 +108,6 @@ struct WaveCompute16 {
     }
     template <bool F16W = false>
     __device__ __forceinline__ static uint32_t pack_p(float lo, float hi) { return F16W ? pack_f16(lo, hi) : pack_bf16(lo, hi); }
-
-    // Q fragment (qg, ks) of row q = row0 + 16*qg + (lane&15): 16 bytes at byte 64*ks + 16*h4 of the row.
-    __device__ __forceinline__ void load_q(const char* Qh, int64_t qS_bytes, int row0, int S, int lane, int row_bytes = D * ESZ) {
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) {
-            int row = row0 + 16 * qg + (lane & 15);
-            row = row < S ? row : S - 1;
-            const char* src = Qh + row * qS_bytes + (lane >> 4) * 16;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if constexpr (C::PAD) {
-                    qf[qg][ks] = u32x4{0u, 0u, 0u, 0u};
-                    if (ks * 64 + (lane >> 4) * 16 < row_bytes) qf[qg][ks] = *reinterpret_cast<const u32x4*>(src + ks * 64);
-                } else {
-                    qf[qg][ks] = *reinterpret_cast<const u32x4*>(src + ks * 64);
-                }
-            }
-        }
-    }
-    // Coalesced form (KernelCfg::COALESCED_Q): instruction i fetches 64/QCH WHOLE rows; the fragments are formed by one trip
-    // through this wave's private LDS region (chunk c of row q parked at chunk c ^ (q & (QCH-1))).
-    static constexpr int QCH = (D * ESZ) / 16;     // 16-byte chunks per Q row
-    static constexpr int QRPI = 64 / QCH;          // rows fetched per instruction
-    static constexpr int QLD = 32 / QRPI;          // loads per lane
-    static_assert(QLD == QG * KS, "coalesced Q: as many loads as fragments");
-    __device__ __forceinline__ void load_q_rows(const char* Qh, int64_t qS_bytes, int row0, int S, int lane) {
-#pragma unroll
-        for (int i = 0; i < QLD; ++i) {
-            int row = row0 + i * QRPI + lane / QCH;
-            row = row < S ? row : S - 1;
-            qf[i / KS][i % KS] = *reinterpret_cast<const u32x4*>(Qh + row * qS_bytes + (lane % QCH) * 16);
-        }
-    }
-    __device__ __forceinline__ void q_rows_to_fragments(lds_ptr region, int lane) {
-        constexpr int ROWB = D * ESZ;
-#pragma unroll
-        for (int i = 0; i < QLD; ++i) {
-            const int q = i * QRPI + lane / QCH, c = lane % QCH;
-            lds_write_b128(region, q * ROWB + (((c ^ q) & (QCH - 1)) << 4), qf[i / KS][i % KS]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // own writes only: LDS executes a wave's accesses in order
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int q = 16 * qg + (lane & 15), c = 4 * ks + (lane >> 4);
-                qf[qg][ks] = __builtin_bit_cast(u32x4, lds_read_b128(region, q * ROWB + (((c ^ q) & (QCH - 1)) << 4)));
-            }
-    }
-    __device__ __forceinline__ void pin_q() {
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[qg][ks]));
-    }
 
     // K fragment f = (key group f / KS, k-step f % KS)
     __device__ __forceinline__ u32x4 k_read(lds_ptr kimg, int kbase, int f) const {
@@ -225,11 +156,7 @@ struct WaveCompute16 {
         for (int kg = 1; kg < KG; ++kg) a = fmaxf(a, fmaxf(fmaxf(n.s[kg][qg][0], n.s[kg][qg][1]), fmaxf(n.s[kg][qg][2], n.s[kg][qg][3])));
         return a;
     }
-    // Tile 0 of a pass: m = its row max (m = -inf before; O and l are still 0).
-    __device__ __forceinline__ void first_max(const Scores16& n, float c) {
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) m[qg] = fmaxf(m[qg], max_all_quarters(row_max(n, qg)) * c);
-    }
+    __device__ __forceinline__ static float max_over_row(float x) { return max_all_quarters(x); }
 
     // ---- softmax slices ------------------------------------------------------------------------
     template <int E, bool F16W = false>
@@ -247,13 +174,6 @@ struct WaveCompute16 {
             if constexpr (!C::SUM_MFMA) asm volatile("" : "+v"(sum_a[qg]), "+v"(sum_b[qg]));
         } else {
             p_even = p;
-        }
-    }
-    template <int SLOT, bool F16W = false, int E = 0>
-    __device__ __forceinline__ void exp_slot(const Scores16& cur, float c) {
-        if constexpr (E < NE) {
-            if constexpr (elem_slot(E) == SLOT) exp_elem<E, F16W>(cur, c);
-            exp_slot<SLOT, F16W, E + 1>(cur, c);
         }
     }
     template <bool F16W = false>
@@ -275,16 +195,6 @@ struct WaveCompute16 {
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) asm volatile("" : "+v"(mx_a[qg]), "+v"(mx_b[qg]));
     }
-    __device__ __forceinline__ void decide(float c) {
-        bool any = false;
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) {
-            const float mx = max_all_quarters(fmaxf(mx_a[qg], mx_b[qg])) * c;
-            any = any || (mx > m[qg] + (float)C::THR);
-            mx_a[qg] = mx;   // keep the scaled row max for the rescale body
-        }
-        need = __any(any);
-    }
 
     // V^T A-fragment v = (k-step kk = v / DG, d group dg = v % DG): two transposed reads (16-key halves jj = 0, 1)
     __device__ __forceinline__ bf16x8 v_frag(lds_ptr vimg, int vbase, int kk, int dg) const {
@@ -301,15 +211,15 @@ struct WaveCompute16 {
                                             float c, const Scores16& cur, Scores16& nxt) {
         if constexpr (I < SA) {
             constexpr int f = I / QG, qg = I % QG;
-            if constexpr (C::VALU_FIRST) exp_slot<I, F16W>(cur, c);
+            if constexpr (C::VALU_FIRST) this->template exp_slot<I, F16W>(cur, c);
             qk_mfma<f, qg>(kf[f % NPRE], nxt);
             if constexpr (qg == QG - 1 && f + NPRE < NF) kf[f % NPRE] = k_read(k_next, kbase, f + NPRE);
             if constexpr (I >= SA - VPRE) {   // the last VPRE phase-A slots start the V^T window of phase B
                 constexpr int v = I - (SA - VPRE);
                 vf[v % (VPRE + 1)] = v_frag(v_cur, vbase, v / DG, v % DG);
             }
-            load_in_slot<I, F16W>(st, t_load);
-            if constexpr (!C::VALU_FIRST) exp_slot<I, F16W>(cur, c);
+            this->template load_in_slot<I, F16W>(st, t_load);
+            if constexpr (!C::VALU_FIRST) this->template exp_slot<I, F16W>(cur, c);
             __builtin_amdgcn_sched_barrier(0);
             slots_a<I + 1, F16W>(st, t_load, k_next, v_cur, kbase, vbase, c, cur, nxt);
         }
@@ -326,21 +236,17 @@ struct WaveCompute16 {
                 constexpr int vn = v + VPRE;
                 vf[vn % (VPRE + 1)] = v_frag(v_cur, vbase, vn / DG, vn % DG);
             }
-            exp_slot<SA + J, F16W>(cur, c);
+            this->template exp_slot<SA + J, F16W>(cur, c);
             if constexpr (TRACK && J < SB / 2) max3_slot<J>(nxt);
-            if constexpr (TRACK && J == SB / 2) decide(c);
-            if constexpr (J >= SB / 2 && (J - SB / 2) % WSTEP == 0 && (J - SB / 2) / WSTEP < NW)
-                st.template write<(J - SB / 2) / WSTEP, F16W>(wr_slot);
+            if constexpr (TRACK && J == SB / 2) this->decide(c);
+            this->template write_in_slot<J, F16W>(st, wr_slot);
             __builtin_amdgcn_sched_barrier(0);
             slots_b<TRACK, J + 1, F16W>(st, wr_slot, v_cur, vbase, c, cur, nxt);
         }
     }
 
-    // One tile: cur = S(t) (consumed), nxt = S(t+1) (produced).  Same contract as WaveCompute::tile_step.
-    template <bool TRACK, bool F16W = false>
-    __device__ __forceinline__ void tile_step(Stage& st, int t_load, lds_ptr wr_slot, lds_ptr k_next, lds_ptr v_cur,
-                                              int kbase, int vbase, float c, const Scores16& cur, Scores16& nxt,
-                                              bool has_next, bool mask_next, int kv0_next, int q_row0, int S, int lane) {
+    // ---- what SlotEngine::tile_step leaves to the engine ----
+    __device__ __forceinline__ void begin_tile(Stage& st, lds_ptr wr_slot, Scores16& nxt) {
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) {
             mx_a[qg] = mx_b[qg] = -INFINITY;
@@ -348,45 +254,18 @@ struct WaveCompute16 {
         }
         zero(nxt);
         st.set_dst(wr_slot);   // (LDS-DMA staging: where this iteration's loads land)
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) kf[i] = k_read(k_next, kbase, i);
-        if constexpr (C::PRIO_A) __builtin_amdgcn_s_setprio(1);
-        __builtin_amdgcn_sched_barrier(0);
-        slots_a<0, F16W>(st, t_load, k_next, v_cur, kbase, vbase, c, cur, nxt);
-        if constexpr (C::PRIO_A) {
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (C::STAMP) t_mid = cycle_stamp();
-        slots_b<TRACK, 0, F16W>(st, wr_slot, v_cur, vbase, c, cur, nxt);
-        if constexpr (C::STAMP) t_end = cycle_stamp();
+    }
+    __device__ __forceinline__ void end_sums() {
         if constexpr (!C::SUM_MFMA) {
 #pragma unroll
             for (int qg = 0; qg < QG; ++qg) l[qg] += sum_a[qg] + sum_b[qg];
         }
-        // ONE rescale site (two sites that both multiply O make hipcc copy all accumulator registers per tile)
-        if (has_next && mask_next) {
-            mask(nxt, kv0_next, q_row0, S, lane);
-            if constexpr (TRACK) {
+    }
+    __device__ __forceinline__ void rescale(int qg, float alpha) {
+        lsum[qg] *= alpha;
+        l[qg] *= alpha;
 #pragma unroll
-                for (int qg = 0; qg < QG; ++qg) { mx_a[qg] = row_max(nxt, qg); mx_b[qg] = mx_a[qg]; }
-                decide(c);
-            }
-        }
-        if constexpr (TRACK) {
-            if (has_next && need) {
-#pragma unroll
-                for (int qg = 0; qg < QG; ++qg) {
-                    const float mn = fmaxf(m[qg], mx_a[qg]);
-                    const float alpha = fast_exp2(m[qg] - mn);
-                    m[qg] = mn;
-                    lsum[qg] *= alpha;
-                    l[qg] *= alpha;
-#pragma unroll
-                    for (int i = 0; i < DG; ++i) o[qg][i] *= alpha;
-                }
-            }
-        }
+        for (int i = 0; i < DG; ++i) o[qg][i] *= alpha;
     }
 
     // True iff a row sum or any O accumulator of this lane is inf / NaN (x*0 is NaN for both); four independent chains.
@@ -405,12 +284,6 @@ struct WaveCompute16 {
     }
 
     // ---- epilogues -----------------------------------------------------------------------------
-    // ln sum_k exp(scale*s_k) = (m + log2 l) * ln 2
-    __device__ __forceinline__ void store_lse(float* lse_head, float l_tot, int qg, int row0, int S, int lane) const {
-        const int qi = row0 + 16 * qg + (lane & 15);
-        if (lse_head && lane < 16 && qi < S) lse_head[qi] = (m[qg] + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-    }
-
     // 2-byte outputs through this wave's private LDS region, one query group (16 rows) at a time: row-major [16 rows][D], 16-byte
     // chunk c of row q at chunk c ^ (q & mask); whole rows back out with 16-byte stores.  region: 16*D*2 bytes, not aliased by
     // anything live.  (The LDS executes a wave's accesses in order, so the second group's writes cannot overtake the first
@@ -426,7 +299,7 @@ struct WaveCompute16 {
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) {
             const float l_tot = row_sum_total(qg);
-            store_lse(lse_head, l_tot, qg, row0, S, lane);
+            this->store_lse(lse_head, l_tot, qg, row0, S, lane);
             const float inv = 1.0f / l_tot;
 #pragma unroll
             for (int dg = 0; dg < DG; ++dg) {
@@ -470,7 +343,7 @@ struct WaveCompute16 {
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) {
             const float l_tot = row_sum_total(qg);
-            store_lse(lse_head, l_tot, qg, row0, S, lane);
+            this->store_lse(lse_head, l_tot, qg, row0, S, lane);
             const float inv = 1.0f / l_tot;
 #pragma unroll
             for (int hf = 0; hf < D / 64; ++hf) {
