@@ -17,6 +17,9 @@ entry points for that path:
   pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.  Both also take fp8
   (``torch.float8_e4m3fn``) K/V caches under a bf16 Q, with per-K/V-head ``k_descale`` / ``v_descale``: half the bytes per token.
   Both take ``window=W``: a sliding window, every row sees at most the last W keys up to its own position.
+* ``kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens)`` / ``kv_cache_append_paged(..., block_table, kv_lens)`` -- the write
+  side of those caches: the last Sq rows of every sequence, bf16, copied into a bf16 cache or quantised (divide by the per-head
+  descale, saturate, round to nearest even) into an fp8 one, in place, positions and pages found on the device.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -49,6 +52,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_decode", "flash_attention_decode_plan", "flash_attention_decode_workspace_size",
            "flash_attention_decode_paged", "flash_attention_decode_fp8", "flash_attention_decode_paged_fp8",
            "flash_attention_decode_window", "flash_attention_decode_paged_window", "flash_attention_decode_plan_window",
+           "flash_attention_kv_append", "flash_attention_kv_append_paged",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -138,6 +142,10 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_decode_plan.restype = i
         L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
         L.flash_attention_decode_workspace_size.restype = ctypes.c_size_t
+        L.flash_attention_kv_append.argtypes = [vp] * 7 + [i, i, i, i, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_kv_append.restype = i
+        L.flash_attention_kv_append_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, ctypes.c_int64, i, i, i] + [sp] * 4 + [vp]
+        L.flash_attention_kv_append_paged.restype = i
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -556,6 +564,72 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     return _decode("flash_attention_decode_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
                    (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
                    k_descale, v_descale, window)
+
+
+def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None):
+    """What kv_cache_append and kv_cache_append_paged share: the tensor checks of the decode fronts (``_decode_inputs``, the new rows
+    in the place of Q), the bounds of Sq, and the call."""
+    import torch
+    if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
+        raise ValueError(f"K_new, V_new must be [B, Hkv, Sq, d] of one dtype, with the K/V heads of {kv} {layout}")
+    if not V_new.is_cuda:
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    fp8 = _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=table)
+    B, Hkv, Sq, d = K_new.shape
+    if Sq < 1 or Sq > capacity:
+        raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    with torch.cuda.device(K_new.device):
+        st = [_strides(t) for t in (K_new, V_new, K, V)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = getattr(lib(), symbol)(K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(), ptr(kv_lens), *map(ptr, tables),
+                                    ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype),
+                                    _dtype_code(K.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+    _check(rc)
+
+
+def kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens=None, k_descale=None, v_descale=None, stream=None):
+    """Write the new rows of every sequence into the K/V caches ``flash_attention_decode`` reads, in place.  Returns None.
+
+    ``K_new``, ``V_new``: bf16 ``[B, Hkv, Sq, d]`` device tensors, d = 64 or 128, 1 <= Sq <= capacity (not capped at
+    FA_DECODE_MAX_Q: the same call fills a cache after a prefill); strided views are accepted (last dimension contiguous), so the
+    K and V slices of a fused projection pass without a copy.  ``K_cache``, ``V_cache``: ``[B, Hkv, capacity, d]``, bf16 (a bit
+    copy) or ``torch.float8_e4m3fn`` with ``k_descale`` / ``v_descale`` (fp32 device tensors ``[Hkv]``, None = 1): the stored byte
+    is the e4m3fn code of ``clamp(x.float() / descale[kvh], -448, 448)``, rounded to nearest even once; +-inf stores +-448, NaN a
+    NaN code, and the sign of zero is kept.
+
+    Positions: the rows are the LAST Sq rows of the sequence and ``kv_lens[b]`` (int32 device tensor ``[B]``, None = the capacity)
+    already counts them: with ``L = min(kv_lens[b], capacity)`` row i goes to position ``L - Sq + i``, written if that is >= 0;
+    ``kv_lens[b] <= 0`` writes nothing.  A decode step is ``kv_lens += Sq; kv_cache_append(...); flash_attention_decode(...,
+    is_causal=True)`` on one tensor of lengths.  Lengths and descales are read by the kernel: the call never synchronises and a
+    captured graph sees the values of the moment.  Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
+    cap = K_cache.shape[2] if K_cache.dim() == 4 else 0
+    _append("flash_attention_kv_append", "kv_cache_append", "K_cache, V_cache", "[B, Hkv, capacity, d]", K_new, V_new, K_cache, V_cache,
+            cap, (), (cap,), kv_lens, k_descale, v_descale, stream)
+
+
+def kv_cache_append_paged(K_new, V_new, K_pool, V_pool, block_table, kv_lens=None, k_descale=None, v_descale=None, stream=None):
+    """``kv_cache_append`` into PAGED caches: pools ``[P, Hkv, page, d]`` (bf16 or float8_e4m3fn; page a power of two >= 16; strided
+    views accepted, so a ``[P, page, Hkv, d]`` pool is ``pool.transpose(1, 2)``) and ``block_table``, an int32 device tensor
+    ``[B, max_pages]`` with a contiguous last dimension (a row slice of a wider table is fine).  Position p of sequence b is row
+    ``p % page`` of page ``block_table[b, p // page]``; the capacity is ``max_pages * page``.
+
+    Only the entries of pages that receive a row are read, by the kernel.  An entry outside [0, P) is NOT clamped (decode may
+    clamp: it only reads): the rows that would go to that page are skipped and nothing else is touched.  Two sequences that write
+    the same row of one page: the winner is unspecified.  Everything else as for ``kv_cache_append``.  Returns None."""
+    import torch
+    table = block_table
+    B = K_new.shape[0] if K_new.dim() == 4 else 0
+    P, _, page = K_pool.shape[:3] if K_pool.dim() == 4 else (0, 0, 0)
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] != B or table.shape[1] < 1 \
+            or table.stride(1) != 1 or (B > 1 and table.stride(0) < table.shape[1]):
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    max_pages = table.shape[1]
+    table_stride = table.stride(0) if B > 1 else max_pages
+    _append("flash_attention_kv_append_paged", "kv_cache_append_paged", "K_pool, V_pool", "[P, Hkv, page, d]", K_new, V_new, K_pool, V_pool,
+            max_pages * page, (table,), (P, page, max_pages, table_stride), kv_lens, k_descale, v_descale, stream, table=table)
 
 
 def _library_accepts(t):

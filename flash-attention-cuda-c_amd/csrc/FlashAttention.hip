@@ -18,6 +18,7 @@
 #include "weights.hip.h"
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
+#include "kv_append.hip.h"
 
 namespace fa {
 
@@ -409,6 +410,55 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     if (e != hipSuccess || r.ns == 1) return (int)e;
     return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
 }
+
+// ---- K/V cache append (kv_append.hip.h) ----
+// flash_attention_kv_append and flash_attention_kv_append_paged: one validation and launch.  The caches are decode_run's: the same
+// layouts, element sizes, stride rules, paging checks and extent limits, so a cache this call accepts is one the decode call of the
+// same kv_dtype accepts.  Sq is not capped at FA_DECODE_MAX_Q (the call also fills a cache after a prefill), only at the capacity.
+static int kv_append_run(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,
+                         const float* vDescale, int B, int Hkv, int Sq, int Sk, int d, int dtype, int kv_dtype, const fa_strides* sKnew,
+                         const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV, const DecodePaging* pg, void* stream) {
+    if (!Knew || !Vnew || !K || !V || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(Knew) || !aligned16(Vnew) || !aligned16(K) || !aligned16(V)) return FA_ERR_MISALIGNED;
+    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
+    if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
+    if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
+    if (pg) {
+        if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
+        if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
+        Sk = pg->max_pages * pg->page_size;
+    }
+    if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || Sq > Sk || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (kv_dtype == FA_DTYPE_BF16 && (kDescale || vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
+    if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
+    const int esz = elem_size(kv_dtype);
+    if (!strides_ok(sKnew, 2, d) || !strides_ok(sVnew, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d)) return FA_ERR_BAD_STRIDE;
+    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;   // decode_run's limit: what is written can be read
+    if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
+    const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
+    const int64_t grid = (int64_t)B * Hkv * row_blocks * 2;
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    const int rowsK = pg ? pg->page_size : Sk;
+    KvAppendParams p;
+    p.Knew = (const __bf16*)Knew; p.Vnew = (const __bf16*)Vnew; p.K = K; p.V = V;
+    p.kv_lens = kvLens;
+    p.block_table = pg ? pg->table : nullptr;
+    p.k_descale = kDescale; p.v_descale = vDescale;
+    resolve_strides(sKnew, Hkv, Sq, d, p.knB, p.knH, p.knS);
+    resolve_strides(sVnew, Hkv, Sq, d, p.vnB, p.vnH, p.vnS);
+    resolve_strides(sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+    resolve_strides(sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.Hkv = Hkv; p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    const Kernel k = kv_append_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
+    return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(stream), p);
+}
 }  // namespace fa
 
 extern "C" {
@@ -722,6 +772,24 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
                           scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg, stream);
+}
+
+int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,
+                              const float* vDescale, int batchSize, int numHeadsKV, int seqLenNew, int seqLenK, int dHead, int dtype,
+                              int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                              void* stream) {
+    return fa::kv_append_run(Knew, Vnew, K, V, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, seqLenK, dHead, dtype,
+                             kv_dtype, sKnew, sVnew, sK, sV, nullptr, stream);
+}
+
+int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int32_t* kvLens,
+                                    const int32_t* blockTable, const float* kDescale, const float* vDescale, int batchSize,
+                                    int numHeadsKV, int seqLenNew, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                    int dHead, int dtype, int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew,
+                                    const fa_strides* sK, const fa_strides* sV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::kv_append_run(Knew, Vnew, Kpool, Vpool, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, 0, dHead, dtype,
+                             kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
 }
 
 const char* flash_attention_error_string(int code) {

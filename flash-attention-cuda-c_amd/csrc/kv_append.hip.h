@@ -1,0 +1,141 @@
+// kv_append.hip.h -- the WRITE side of the decode caches (flash_attention_kv_append, flash_attention_kv_append_paged; DESIGN.md
+// section 18): the last Sq rows of every sequence, given as bf16 [B, Hkv, Sq, d], go into the cache that split-KV decode
+// (decode_bf16.hip.h) reads -- contiguous [B, Hkv, capacity, d] or pools of pages behind a block table; bf16 (a bit copy) or OCP
+// e4m3fn with one fp32 descale per K/V head (divide, saturate, round to nearest even once).
+//
+//   * POSITIONS.  L = min(kv_lens[b], capacity) ALREADY counts the new rows: new row i is key position p = L - Sq + i, written when
+//     p >= 0; L <= 0 writes nothing.  Lengths, descales and table entries are read here, never by the host.
+//   * WORK.  One launch does K and V.  A workgroup is (sequence, K/V head, block of 64 key POSITIONS, K or V).  Blocks are aligned
+//     in position space, not in the new rows' index: block rb covers positions [64 (first / 64 + rb), + 64) cut to [first, L),
+//     first = max(L - Sq, 0), so ceil(Sq / 64) + 1 blocks reach every row wherever first falls.  Each of the four waves owns 16
+//     consecutive positions aligned to 16; a page is a power of two >= 16 rows, so a wave's rows lie in ONE page: the length, the
+//     descale and the page entry are wave-uniform scalars, read once per wave.  A wave that holds no position of [first, L) returns
+//     before it reads its table entry: only the entries of pages that receive a row are read.
+//   * A LANE owns 8 consecutive d of one row: one 16-byte load of the new row; fp8: 8 correctly rounded divisions, the clamp to
+//     +-448 in fp32, 4 v_cvt_pk_fp8_f32, one 8-byte store; bf16: the 16 bytes stored as loaded.  D / 8 lanes hold a row and 512 / D
+//     rows share a wave instruction: the stores of a wave are whole rows, contiguous runs in one page.
+//   * A table entry outside [0, numPages) is NOT clamped (decode may clamp: it only reads): the wave skips its rows.
+//   * Every address is 64-bit arithmetic on the element strides.  No LDS, no scratch, no atomics; every store is a vector store.
+//   * NaN.  The clamp would lose a NaN (max / min return the other operand), and what the conversion instruction does with one by
+//     itself is not relied on: 0x7F is OR-ed into the byte of every element whose quotient is NaN (0x7F or 0xFF: a NaN code).
+#pragma once
+
+#include "../../include/flash_attention.h"
+#include "launchers.hip.h"
+#include "utils.hip.h"
+
+namespace fa {
+
+struct KvAppendParams {
+    const __bf16* Knew;
+    const __bf16* Vnew;
+    void* K;                      // the cache, or (paged) the pool
+    void* V;
+    const int32_t* kv_lens;       // optional [B] (device memory); NULL = the capacity
+    const int32_t* block_table;   // paged: [B][table_stride] page numbers (device memory)
+    const float* k_descale;       // fp8: optional [Hkv] (device memory); NULL = 1
+    const float* v_descale;
+    int64_t knB, knH, knS, vnB, vnH, vnS;   // element strides of the new rows (bf16)
+    int64_t kB, kH, kS, vB, vH, vS;         // element strides of the caches (paged: kB / vB the page strides); fp8: bytes
+    int64_t table_stride;
+    int Hkv, Sq, cap;             // cap: the capacity (paged: max_pages * page size)
+    int row_blocks;               // position blocks per (sequence, K/V head): ceil(Sq / 64) + 1
+    int num_pages, page_shift;    // paged: page size = 1 << page_shift, >= 16
+};
+
+struct KvAppendCfg {
+    static constexpr int THREADS = 256, WAVES = 4;
+    static constexpr int WROWS = 16;               // positions per wave: one page holds them all (page sizes are powers of two >= 16)
+    static constexpr int BLOCK = WAVES * WROWS;    // positions per workgroup
+};
+
+// the quotient saturated to +-448 in fp32: the conversion never sees an overflow (a NaN does not survive this: see above)
+__device__ __forceinline__ float kv_saturate(float q) { return __builtin_fminf(__builtin_fmaxf(q, -448.f), 448.f); }
+
+// four bf16 (two words) -> four e4m3fn bytes, the lowest d in the lowest byte
+__device__ __forceinline__ uint32_t kv_quantise4(uint32_t w0, uint32_t w1, float ds) {
+    const float q0 = bf16_lo(w0) / ds, q1 = bf16_hi(w0) / ds, q2 = bf16_lo(w1) / ds, q3 = bf16_hi(w1) / ds;   // correctly rounded
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(kv_saturate(q0), kv_saturate(q1), 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(kv_saturate(q2), kv_saturate(q3), r, true);
+    const uint32_t nan = (q0 != q0 ? 0x7Fu : 0u) | (q1 != q1 ? 0x7F00u : 0u) | (q2 != q2 ? 0x7F0000u : 0u) | (q3 != q3 ? 0x7F000000u : 0u);
+    return (uint32_t)r | nan;
+}
+
+template <int D, bool KV8, bool PAGED>
+__global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendParams p) {
+    using C = KvAppendCfg;
+    constexpr int LPR = D / 8;           // lanes per row
+    constexpr int RPI = 64 / LPR;        // rows per wave instruction
+    constexpr int PASSES = C::WROWS / RPI;
+    constexpr int ES = KV8 ? 1 : 2;      // bytes per cache element
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+
+    // blockIdx -> (sequence, K/V head, position block, K or V); K / V runs fastest
+    int u = blockIdx.x;
+    const int isV = u & 1; u >>= 1;
+    const int rb = u % p.row_blocks; u /= p.row_blocks;
+    const int kvh = u % p.Hkv;
+    const int b = u / p.Hkv;
+
+    int len = p.cap;
+    if (p.kv_lens) len = min(p.kv_lens[b], p.cap);
+    len = __builtin_amdgcn_readfirstlane(len);
+    if (len <= 0) return;                                  // an inactive slot: nothing is written
+    const int first = max(len - p.Sq, 0);                  // the position of the first row written
+    // this wave's 16 positions
+    const int pw = ((first / C::BLOCK + rb) * C::WAVES + wave) * C::WROWS;
+    if (pw + C::WROWS <= first || pw >= len) return;       // (before the table entry is read)
+
+    const __bf16* src = isV ? p.Vnew : p.Knew;
+    const int64_t nB = isV ? p.vnB : p.knB, nH = isV ? p.vnH : p.knH, nS = isV ? p.vnS : p.knS;
+    const int64_t cB = isV ? p.vB : p.kB, cH = isV ? p.vH : p.kH, cS = isV ? p.vS : p.kS;
+    char* dst = (char*)(isV ? p.V : p.K);
+
+    int row0 = pw;                                         // the wave's first row within its cache slab
+    if constexpr (PAGED) {
+        const int entry = __builtin_amdgcn_readfirstlane(p.block_table[b * p.table_stride + (pw >> p.page_shift)]);
+        if (entry < 0 || entry >= p.num_pages) return;     // not clamped: a clamped write would land in another sequence's page
+        dst += (int64_t)entry * cB * ES;
+        row0 = pw & ((1 << p.page_shift) - 1);
+    } else {
+        dst += (int64_t)b * cB * ES;
+    }
+    dst += (int64_t)kvh * cH * ES;
+    src += (int64_t)b * nB + (int64_t)kvh * nH;
+
+    float ds = 1.f;
+    if constexpr (KV8) {
+        const float* dp = isV ? p.v_descale : p.k_descale;
+        if (dp) ds = dp[kvh];
+    }
+
+    const int lr = lane / LPR, col = (lane % LPR) * 8;
+    const int shift = len - p.Sq;                          // position - shift = the new row's index (>= 0 from `first` on)
+    u32x4 x[PASSES];
+    bool ok[PASSES];
+#pragma unroll
+    for (int j = 0; j < PASSES; ++j) {
+        const int pos = pw + j * RPI + lr;
+        ok[j] = pos >= first && pos < len;
+        x[j] = u32x4{0u, 0u, 0u, 0u};
+        if (ok[j]) x[j] = *reinterpret_cast<const u32x4*>(src + (int64_t)(pos - shift) * nS + col);
+    }
+#pragma unroll
+    for (int j = 0; j < PASSES; ++j) {
+        if (!ok[j]) continue;
+        char* out = dst + ((int64_t)(row0 + j * RPI + lr) * cS + col) * ES;
+        if constexpr (KV8) {
+            u32x2 y;
+            y[0] = kv_quantise4(x[j][0], x[j][1], ds);
+            y[1] = kv_quantise4(x[j][2], x[j][3], ds);
+            *reinterpret_cast<u32x2*>(out) = y;
+        } else {
+            *reinterpret_cast<u32x4*>(out) = x[j];
+        }
+    }
+}
+
+// the instantiation for (d, fp8 cache, paged): inst_kv_append.hip
+Kernel kv_append_kernel_of(int d, bool kv8, bool paged);
+
+}  // namespace fa

@@ -569,6 +569,65 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                         void* stream);
 
+/*
+ * flash_attention_kv_append, flash_attention_kv_append_paged -- the WRITE side of the decode caches: the new rows of every sequence go
+ * into the cache that flash_attention_decode* reads -- a bit copy into a bf16 cache, or quantised to OCP e4m3fn with one fp32 descale
+ * per K/V head into an fp8 cache.  One launch writes K and V; a decode step is `kv_lens += Sq; append; decode`, one graph.
+ *   Knew, Vnew [batchSize, numHeadsKV, seqLenNew, dHead] bf16 (dtype = FA_DTYPE_BF16).  sKnew / sVnew: element strides or NULL (dense);
+ *            the last dimension is contiguous, so the K and V slices of a fused [B, S, (H + 2 Hkv) d] projection pass without a copy
+ *   K, V / Kpool, Vpool  the caches of the decode call of the same kv_dtype and form: [batchSize, numHeadsKV, seqLenK, dHead], seqLenK
+ *            the CAPACITY, or pools [numPages, numHeadsKV, pageSize, dHead] (strideB = the page stride) behind blockTable; bf16
+ *            (kv_dtype = FA_DTYPE_BF16; kDescale and vDescale must be NULL) or one-byte e4m3fn elements (FA_DTYPE_FP8_E4M3; strides in
+ *            bytes).  The layouts, stride rules and extent limits are the decode calls': what this call accepts, decode accepts
+ *   dHead    64 or 128.  1 <= seqLenNew <= capacity: NOT capped at FA_DECODE_MAX_Q -- the same call fills the cache after a prefill
+ *
+ * Positions.  The rows appended are the rows decode's bottom-right mask treats as the query rows' own: the LAST seqLenNew rows of the
+ * sequence, and kvLens[b] ALREADY counts them.  With L = min(kvLens[b], capacity), new row i goes to key position p = L - seqLenNew + i
+ * and is written only if p >= 0.  kvLens[b] <= 0 writes nothing for that sequence (an inactive slot of a fixed-batch graph); NULL
+ * kvLens = the capacity.  This differs from decode's clamp of the length into [1, capacity] only for kvLens[b] <= 0, where decode
+ * reads key 0 and this call writes nothing.  One device tensor of lengths serves both calls of a step; this call writes no length.
+ * kvLens, the descales and the table entries are DEVICE memory read BY THE KERNEL: the host never synchronises, and a replayed graph
+ * sees the values of the moment.
+ *
+ * Paged.  Position p is row p % pageSize of page blockTable[b * tableStride + p / pageSize].  Only the entries of pages that receive
+ * a row are read.  An entry outside [0, numPages) is NOT clamped (decode may clamp because it only reads; a clamped write would land
+ * in another sequence's page): the rows that would go to such a page are skipped and nothing else is touched.  Two sequences that
+ * write the same row of the same page: the winner is unspecified, the address never bad.  Page bases are 64-bit: pools above 2^32
+ * bytes work.
+ *
+ * Values.  kv_dtype = FA_DTYPE_BF16: the 2-byte pattern is copied unchanged, NaN payloads and -0 included.
+ * kv_dtype = FA_DTYPE_FP8_E4M3: the stored byte is the e4m3fn code of clamp(fp32(x) / descale[kvh], -448, 448): the correctly rounded
+ * fp32 quotient, then ONE rounding to nearest even to e4m3fn, subnormals included.  The sign is kept on values that round to zero (-0
+ * and negative underflow store 0x80); +-inf stores +-448 (0x7E / 0xFE); NaN stores a NaN code (0x7F or 0xFF).  A NULL descale is
+ * 1.0; a descale that is not finite and positive gives unspecified bytes, never a bad address.  The reader's logical cache is then
+ * K8 * kDescale[kvh], V8 * vDescale[kvh] (flash_attention_decode_fp8).
+ *
+ * Conventions.  Everything is validated before the launch; the calls never allocate, synchronise or print; the same inputs give the
+ * same bytes (no atomics; every cache byte has one writer).  Rejected with the decode calls' codes for the same mistake: null pointers
+ * (a NULL blockTable included) FA_ERR_NULL_POINTER; a base not aligned to 16 bytes, kvLens / blockTable / a descale not aligned to 4
+ * FA_ERR_MISALIGNED; a stride that is not a multiple of 16 bytes or a row stride below dHead FA_ERR_BAD_STRIDE; batchSize, numHeadsKV
+ * or seqLenK <= 0, seqLenNew < 1 or above the capacity, a capacity above 2^24, numPages <= 0, maxPagesPerSeq <= 0, pageSize < 16 or
+ * not a power of two, tableStride < maxPagesPerSeq, one head's extent ((seqLenK + 192) x row stride; paged: pageSize x row stride)
+ * of 2^31 bytes or more FA_ERR_BAD_SHAPE; dtype other than FA_DTYPE_BF16, kv_dtype other than FA_DTYPE_BF16 / FA_DTYPE_FP8_E4M3, or
+ * a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE; any other dHead FA_ERR_UNSUPPORTED_DHEAD.
+ * Not done here: rotary embedding, fp8 new rows, per-token or per-block descales, writing kvLens.
+ */
+int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V,
+                              const int32_t* kvLens, const float* kDescale, const float* vDescale,
+                              int batchSize, int numHeadsKV, int seqLenNew, int seqLenK, int dHead,
+                              int dtype /* of Knew, Vnew: FA_DTYPE_BF16 */, int kv_dtype /* FA_DTYPE_BF16 | FA_DTYPE_FP8_E4M3 */,
+                              const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                              void* stream);
+
+int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                                    const int32_t* kvLens, const int32_t* blockTable,
+                                    const float* kDescale, const float* vDescale,
+                                    int batchSize, int numHeadsKV, int seqLenNew,
+                                    int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                    int dtype, int kv_dtype,
+                                    const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                                    void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 

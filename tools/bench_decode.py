@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256] [--kv fp8] [--window 128,4096]
+                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -30,6 +30,15 @@ Each line:
               the keys a windowed sequence can see (sum over the batch of min(kv_lens, W + Sq - 1) keys; window_kv_MB[W]).  With
               --kv fp8 window_fp8_ms[W] / window_fp8_kv_tbps[W] as well, with --paged window_paged_ms[page][W] (and
               window_paged_fp8_ms[page][W]) (profiles/decode_window_bench.log).
+--append        the write side (kv_cache_append, kv_cache_append_paged): per shape and cache form -- "bf16", with --kv fp8 "fp8", with
+              --paged "paged<page>" (and "paged<page>_fp8"), behind a shuffled block table -- timed like `ms` in the same run:
+              append_ms[form]       one call that appends the shape's own Sq new rows per sequence at the shape's lengths (K and V)
+              torch_append_ms[form] the same result built with torch ops on the same data: positions (and pages) from kv_lens and the
+                                    table on the device, decode_check.quantise's expression with the given descales, one indexed
+                                    write per tensor; append_matches_torch[form]: the two caches hold the same bytes
+              fill_ms[form], fill_tbps[form]  one call with Sq = 4096 and kv_lens = None (the cache's last 4096 rows: a fill after a
+                                    prefill); bytes read + written = B Hkv 4096 d x 2 tensors x (2 + bytes per cache element)
+              each with _min / _max over the windows (profiles/kv_append_bench.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
 """
 import argparse
@@ -81,6 +90,7 @@ def main():
     ap.add_argument("--no-cross", action="store_true")
     ap.add_argument("--paged", default=None, help="comma-separated page sizes: add paged_ms per page size to every shape's line")
     ap.add_argument("--window", default=None, help="comma-separated sliding windows: add window_ms per window to every shape's line")
+    ap.add_argument("--append", action="store_true", help="add append_ms / torch_append_ms / fill_ms / fill_tbps per cache form to every shape's line")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     args = ap.parse_args()
     import torch
@@ -158,6 +168,50 @@ def main():
             call = lambda: fa.flash_attention_decode_paged(Q, pools[0], pools[1], table, lens_d, O=O, workspace=ws, **kw)
             return sorted(timed(call, args.steps, args.warmup) for _ in range(args.repeats))
 
+        def measure_append(fp8, page):
+            # a cache of this shape and form to write into (its contents do not matter), new rows ~ N(0, 1), the shape's lengths
+            cdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                n = Sk // page
+                table = torch.randperm(B * n, device=dev, generator=g).reshape(B, n).to(torch.int32)
+                Kc, Vc = (torch.empty(B * n, Hkv, page, d, device=dev, dtype=cdt) for _ in range(2))
+                call_of = lambda Kn, Vn, L: lambda: fa.kv_cache_append_paged(Kn, Vn, Kc, Vc, table, L, **kw)
+            else:
+                Kc, Vc = (torch.empty(B, Hkv, Sk, d, device=dev, dtype=cdt) for _ in range(2))
+                call_of = lambda Kn, Vn, L: lambda: fa.kv_cache_append(Kn, Vn, Kc, Vc, L, **kw)
+            rows = lambda n: tuple(torch.randn(B, Hkv, n, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+            Kn, Vn = rows(Sq)
+            ours = sorted(timed(call_of(Kn, Vn, lens_d), args.steps, args.warmup) for _ in range(args.repeats))
+            # the same with torch ops: nothing built on the host per call (every length of these shapes is >= Sq: no row is dropped)
+            Ku, Vu = (Kc.view(torch.uint8), Vc.view(torch.uint8)) if fp8 else (Kc, Vc)
+            ar, bi = torch.arange(Sq, device=dev), torch.arange(B, device=dev)[:, None]
+
+            def torch_append():
+                pos = ((lens_d.clamp(max=Sk) - Sq)[:, None] + ar).long()
+                for new, cache, ds in ((Kn, Ku, kds if fp8 else None), (Vn, Vu, vds if fp8 else None)):
+                    x = (new.float() / ds[None, :, None, None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8) if fp8 else new
+                    if page:
+                        cache[table.gather(1, pos // page).long(), :, pos % page] = x.transpose(1, 2)
+                    else:
+                        cache[bi, :, pos] = x.transpose(1, 2)
+
+            Kc.view(torch.uint8).zero_()
+            Vc.view(torch.uint8).zero_()
+            call_of(Kn, Vn, lens_d)()
+            kept = (Kc.view(torch.uint8).clone(), Vc.view(torch.uint8).clone())
+            Kc.view(torch.uint8).zero_()
+            Vc.view(torch.uint8).zero_()
+            theirs = sorted(timed(torch_append, args.steps, args.warmup) for _ in range(args.repeats))
+            same = bool(torch.equal(kept[0], Kc.view(torch.uint8)) and torch.equal(kept[1], Vc.view(torch.uint8)))
+            out = {"append_ms": ours, "torch_append_ms": theirs, "append_matches_torch": same}
+            del kept
+            if Sk >= 4096:
+                Kf, Vf = rows(4096)
+                out["fill_ms"] = sorted(timed(call_of(Kf, Vf, None), max(10, args.steps // 10), 3) for _ in range(args.repeats))
+                out["fill_bytes"] = B * Hkv * 4096 * d * 2 * (2 + (1 if fp8 else 2))
+            return out
+
         if args.splits:
             for ns in [int(x) for x in args.splits.split(",")]:
                 if ns > -(-Sk // 128):
@@ -222,6 +276,19 @@ def main():
                 if pages:
                     line.update(window_paged_fp8_ms={str(page): {str(W): med_of(measure_paged(page, True, W)) for W in windows}
                                                      for page in pages})
+        if args.append:
+            forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+            for page in (int(x) for x in (args.paged or "").split(",") if x):
+                if Sk % page == 0:
+                    forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+            am = {form: measure_append(fp8, page) for form, fp8, page in forms}
+            for key in ("append_ms", "torch_append_ms", "fill_ms"):
+                have = {f: v[key] for f, v in am.items() if key in v}
+                line[key] = {f: round(statistics.median(v), 5) for f, v in have.items()}
+                line[key + "_min"] = {f: round(v[0], 5) for f, v in have.items()}
+                line[key + "_max"] = {f: round(v[-1], 5) for f, v in have.items()}
+            line["append_matches_torch"] = {f: v["append_matches_torch"] for f, v in am.items()}
+            line["fill_tbps"] = {f: round(v["fill_bytes"] / statistics.median(v["fill_ms"]) / 1e9, 3) for f, v in am.items() if "fill_ms" in v}
         if args.kv == "fp8":
             del K8, V8
         print(json.dumps(line), flush=True)
