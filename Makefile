@@ -25,6 +25,10 @@ build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
 tests/fa_tune tests/fa_tune_c128: HIPFLAGS += $(MFMA_VGPR)
+# the chunked-prefill kernel at d = 128 (extend_bf16.hip.h, four 16-row tiles per wave, launch bounds 256, 1): 206 accumulation registers
+# in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
+EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
+$(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)
 
 build/obj/%.o: $(PKG)/csrc/%.hip $(KHDR)
 	@mkdir -p build/obj
@@ -90,7 +94,7 @@ asan: $(LIB) oracle
 # Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC))
-build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s: HIPFLAGS += $(MFMA_VGPR)
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s $(patsubst build/obj/%.o,build/asm/%.s,$(EXTEND_OBJ)): HIPFLAGS += $(MFMA_VGPR)
 
 build/asm/%.s: $(PKG)/csrc/%.hip $(KHDR)
 	@mkdir -p build/asm

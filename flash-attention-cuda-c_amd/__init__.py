@@ -17,6 +17,9 @@ entry points for that path:
   pages ``[P, Hkv, page, d]`` and an int32 block table ``[B, max_pages]``, read on the device.  Both also take fp8
   (``torch.float8_e4m3fn``) K/V caches under a bf16 Q, with per-K/V-head ``k_descale`` / ``v_descale``: half the bytes per token.
   Both take ``window=W``: a sliding window, every row sees at most the last W keys up to its own position.
+* ``flash_attention_extend(Q, K, V, kv_lens)`` / ``flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens)`` --
+  chunked prefill against the same caches, all four forms: any number of new rows up to the capacity, decode's mask and
+  arithmetic (``extend_plan``).
 * ``kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens)`` / ``kv_cache_append_paged(..., block_table, kv_lens)`` -- the write
   side of those caches: the last Sq rows of every sequence, bf16, copied into a bf16 cache or quantised (divide by the per-head
   descale, saturate, round to nearest even) into an fp8 one, in place, positions and pages found on the device.
@@ -53,6 +56,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_decode_paged", "flash_attention_decode_fp8", "flash_attention_decode_paged_fp8",
            "flash_attention_decode_window", "flash_attention_decode_paged_window", "flash_attention_decode_plan_window",
            "flash_attention_kv_append", "flash_attention_kv_append_paged",
+           "flash_attention_extend", "flash_attention_extend_paged", "flash_attention_extend_plan",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -146,6 +150,12 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_kv_append.restype = i
         L.flash_attention_kv_append_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, ctypes.c_int64, i, i, i] + [sp] * 4 + [vp]
         L.flash_attention_kv_append_paged.restype = i
+        L.flash_attention_extend.argtypes = L.flash_attention_decode_fp8.argtypes
+        L.flash_attention_extend.restype = i
+        L.flash_attention_extend_paged.argtypes = L.flash_attention_decode_paged_fp8.argtypes
+        L.flash_attention_extend_paged.restype = i
+        L.flash_attention_extend_plan.argtypes = L.flash_attention_decode_plan.argtypes
+        L.flash_attention_extend_plan.restype = i
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -432,6 +442,14 @@ def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, windo
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
+def extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
+    """What a flash_attention_extend call launches (fa_decode_plan as a dict; ``Sk`` the capacity); ``num_splits`` 0 = the library's
+    choice.  ``rows_per_block`` packed rows ``g * Sq + i`` of one K/V head form a row block; ``decode_workspace_size`` serves unchanged."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+
+
 def decode_workspace_size(B, H, Sq, d, num_splits):
     """Bytes of device scratch flash_attention_decode needs for ``num_splits`` splits as planned (0 for one split)."""
     return int(lib().flash_attention_decode_workspace_size(B, H, Sq, d, num_splits))
@@ -463,13 +481,14 @@ def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None):
 
 
 def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-            stream, k_descale, v_descale, window):
+            stream, k_descale, v_descale, window, plan=None):
     """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
     point (fp8: its ``_fp8`` twin; a window: its ``_window`` twin, which takes both cache types), ``tables`` its tensors between
     kvLens and the workspace, ``geometry`` its ints between seqLenQ and dHead; ``decode_plan`` / ``decode_workspace_size`` are asked
-    about ``capacity``."""
+    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name."""
     import torch
     window = _window(window)
+    both = plan is not None or bool(window)
     B, H, Sq, d = Q.shape
     Hkv = K.shape[1]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -478,7 +497,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits, window)["num_splits"]
+    ns = (plan(B, H, Hkv, Sq, capacity, d, odt, num_splits) if plan else decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits, window))["num_splits"]
     need = decode_workspace_size(B, H, Sq, d, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -496,10 +515,10 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         st = [_strides(t) for t in (Q, K, V, O)]
         ptr = lambda t: t.data_ptr() if t is not None else None
         ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables))
-        if fp8 or window:
+        if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
-        dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or window else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), symbol + ("_window" if window else "_fp8" if fp8 else ""))
+        dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
+        launch = getattr(lib(), symbol + ("" if plan else "_window" if window else "_fp8" if fp8 else ""))
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
                     _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
@@ -564,6 +583,43 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     return _decode("flash_attention_decode_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
                    (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
                    k_descale, v_descale, window)
+
+
+def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
+                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+    """Chunked prefill against a decode cache: Q ``[B, H, Sq, d]`` with 1 <= Sq <= capacity new rows per sequence against the K/V
+    cache ``[B, Hkv, capacity, d]`` that ``flash_attention_decode`` reads (bf16, or ``torch.float8_e4m3fn`` under a bf16 Q with
+    ``k_descale`` / ``v_descale``; d = 64 or 128, Hkv dividing H).  Everything is ``flash_attention_decode``'s -- ``kv_lens`` (which
+    already counts the new rows: ``kv_lens += Sq; kv_cache_append; flash_attention_extend``), the bottom-right ``is_causal``,
+    ``num_splits``, ``workspace`` (``decode_workspace_size`` bytes for ``extend_plan``'s split count), ``O``, ``return_lse``,
+    ``stream`` -- without the cap on Sq and without ``window``.  For Sq <= 16 the result is that call's, bit for bit, under the same
+    forced ``num_splits``.  No CPU fallback."""
+    fp8 = _decode_inputs("flash_attention_extend", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
+    Sk = K.shape[2]
+    return _decode("flash_attention_extend", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
+                   O, workspace, stream, k_descale, v_descale, None, plan=extend_plan)
+
+
+def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
+                                 v_descale=None):
+    """``flash_attention_extend`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
+    ``[B, max_pages]`` of ``flash_attention_decode_paged``, with that call's rules for the table, the lengths and the capacity
+    ``max_pages * page`` (``extend_plan`` is asked with ``Sk = max_pages * page``).  The result is ``flash_attention_extend``'s on a
+    contiguous copy of the same pages, bit for bit.  No ``window``.  No CPU fallback."""
+    import torch
+    fp8 = _decode_inputs("flash_attention_extend_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
+                         v_descale, table=block_table)
+    B = Q.shape[0]
+    P, _, page = K_pool.shape[:3]
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
+            or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    max_pages = block_table.shape[1]
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    return _decode("flash_attention_extend_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
+                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                   k_descale, v_descale, None, plan=extend_plan)
 
 
 def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None):

@@ -18,6 +18,7 @@
 #include "weights.hip.h"
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
+#include "extend_bf16.hip.h"
 #include "kv_append.hip.h"
 
 namespace fa {
@@ -303,38 +304,52 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
 // on uniform batches -- two or three are resident per CU, so either is one resident round -- and a batch of unequal lengths, which
 // the host cannot see, balances 11 % better at two; a split of a single tile has nothing to prefetch behind and gains nothing.
 constexpr int DECODE_WGS_PER_CU = 2, DECODE_MIN_TILES = 2;
+// flash_attention_extend (extend_bf16.hip.h; `extend_d` below = its head dimension, 0 = the decode call): the same rule with
+// units = B * Hkv * row blocks of ExtendCfg::ROWS packed rows.  Workgroups per CU: as many as are resident (ExtendCfg::WGS_PER_CU) -- in the forced
+// sweep (profiles/extend_rt_sweep.log) a split beyond one resident round only costs: at 512 rows on an 8 k
+// prefix, d = 128, two splits of 256 units are 14 % slower than one, and with units short of a round the time is flat within 5 %
+// from half a round to one.  EXTEND_MIN_TILES is decode's value, not re-measured: no benchmark shape has a cache short enough for
+// it to bind.  A long chunk's units fill the chip by themselves and ns = 1.
+constexpr int EXTEND_MIN_TILES = 2;
+static int extend_rows_per_block(int d) { return d == 128 ? ExtendCfg<128>::ROWS : ExtendCfg<64>::ROWS; }
+static int extend_wgs_per_cu(int d) { return d == 128 ? ExtendCfg<128>::WGS_PER_CU : ExtendCfg<64>::WGS_PER_CU; }
 
 struct DecodeRoute {
     int ns, row_blocks, tiles;
     int64_t grid;
 };
 
-static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window) {
+static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window, int extend_d = 0) {
     DecodeRoute r{};
     const int rows = (H / Hkv) * Sq;                     // packed rows per K/V head
-    r.row_blocks = (rows + DecodeCfg<128>::ROWS - 1) / DecodeCfg<128>::ROWS;
+    const int block = extend_d ? extend_rows_per_block(extend_d) : DecodeCfg<128>::ROWS;
+    r.row_blocks = (int)(((int64_t)rows + block - 1) / block);
     constexpr int TILE = DecodeCfg<128>::TILE;
     r.tiles = (Sk + TILE - 1) / TILE;
     if (window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)window + Sq - 1 + TILE - 1) / TILE + 1);
     const int64_t units = (int64_t)B * Hkv * r.row_blocks;
     if (numSplits > 0) r.ns = numSplits;
     else {
-        const int64_t want = ((int64_t)DECODE_WGS_PER_CU * device_cus() + units - 1) / units;
-        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / DECODE_MIN_TILES, (int64_t)FA_DECODE_MAX_SPLITS}));
+        const int64_t want = ((int64_t)(extend_d ? extend_wgs_per_cu(extend_d) : DECODE_WGS_PER_CU) * device_cus() + units - 1) / units;
+        const int min_tiles = extend_d ? EXTEND_MIN_TILES : DECODE_MIN_TILES;
+        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / min_tiles, (int64_t)FA_DECODE_MAX_SPLITS}));
     }
     r.grid = units * r.ns;
     return r;
 }
 
-static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits, int window) {
+// extend: the flash_attention_extend calls -- seqLenQ up to the capacity, not FA_DECODE_MAX_Q
+static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits, int window,
+                              bool extend = false) {
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (Sq > (extend ? Sk : FA_DECODE_MAX_Q) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (extend && (int64_t)B * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
     if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
     if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS || window < 0) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    if (decode_route(B, H, Hkv, Sq, Sk, numSplits, window).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (decode_route(B, H, Hkv, Sq, Sk, numSplits, window, extend ? d : 0).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 
@@ -354,7 +369,7 @@ struct DecodePaging {
 static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, const float* kDescale,
                       const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal,
                       int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ, const fa_strides* sK,
-                      const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
+                      const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream, bool extend = false) {
     if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
     if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
@@ -365,7 +380,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
         Sk = pg->max_pages * pg->page_size;
     }
-    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window);
+    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window, extend);
     if (rc != FA_OK) return rc;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
@@ -375,7 +390,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     // whole may be larger)
     const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;
     if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
-    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits, window);
+    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits, window, extend ? d : 0);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)B * H * Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
@@ -404,8 +419,10 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     p.window = window;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
-    const Kernel sk = pg ? (kv8 ? decode_paged_fp8_split_kernel_of(d) : decode_paged_split_kernel_of(d))
-                         : (kv8 ? decode_fp8_split_kernel_of(d) : decode_split_kernel_of(d));
+    const Kernel sk = extend ? (pg ? (kv8 ? extend_paged_fp8_split_kernel_of(d) : extend_paged_split_kernel_of(d))
+                                   : (kv8 ? extend_fp8_split_kernel_of(d) : extend_split_kernel_of(d)))
+                      : pg   ? (kv8 ? decode_paged_fp8_split_kernel_of(d) : decode_paged_split_kernel_of(d))
+                             : (kv8 ? decode_fp8_split_kernel_of(d) : decode_split_kernel_of(d));
     hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
     if (e != hipSuccess || r.ns == 1) return (int)e;
     return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
@@ -772,6 +789,47 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
                           scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg, stream);
+}
+
+int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                int numSplits, fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0, true);
+    if (rc != FA_OK) return rc;
+    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0, dHead);
+    plan->num_splits = r.ns;
+    plan->row_blocks = r.row_blocks;
+    plan->rows_per_block = extend_rows_per_block(dHead);
+    plan->kv_block_rows = DecodeCfg<128>::TILE;
+    plan->threads = DecodeCfg<128>::THREADS;
+    plan->grid = (int)r.grid;
+    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
+    plan->combine_grid = r.ns > 1 ? batchSize * numHeads * seqLenQ : 0;   // one workgroup per (batch, head, query row)
+    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    return FA_OK;
+}
+
+int flash_attention_extend(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                           const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                           int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
+                           int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                           const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream, true);
+}
+
+int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                 const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                 int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                 int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                                 const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
+                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream, true);
 }
 
 int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,

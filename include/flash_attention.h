@@ -628,6 +628,65 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
                                     const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
                                     void* stream);
 
+/*
+ * flash_attention_extend, flash_attention_extend_paged -- CHUNKED PREFILL against the decode caches: seqLenQ new query rows per
+ * sequence, 1 .. the capacity, against the caches flash_attention_decode* reads and flash_attention_kv_append* writes.  A chunk of a
+ * chunked prefill, a prompt behind a cached prefix, a speculative draft longer than FA_DECODE_MAX_Q rows.  The argument lists are
+ * flash_attention_decode_fp8's / flash_attention_decode_paged_fp8's, word for word, and like the _window calls the two entry points
+ * serve all four cache forms: kv_dtype = FA_DTYPE_BF16 (kDescale and vDescale must be NULL) or FA_DTYPE_FP8_E4M3 (optional per-head
+ * descales).
+ *
+ * Contract.  Everything not named below is the decode sibling's of the same form and kv_dtype: layouts, strides and the 2^31-byte
+ * extent rules; kvLens, the descales and the table entries read by the kernel and clamped as decode clamps them; keys at and beyond the
+ * length may hold anything; a pool may exceed 2^32 bytes; o_dtype F32, BF16 or F16, rounded once at the store; the optional LSE (the
+ * same bits of O with or without it); the caller-owned workspace of flash_attention_decode_workspace_size(batchSize, numHeads,
+ * seqLenQ, dHead, plan.num_splits) bytes (that function has no cap on seqLenQ and serves unchanged); the same bits run to run, no
+ * atomics; validation before any launch; no allocation, no host synchronisation, nothing printed, graph-capturable.
+ *
+ * What differs from decode.
+ *   seqLenQ  1 <= seqLenQ <= capacity (seqLenK, or maxPagesPerSeq * pageSize), not capped at FA_DECODE_MAX_Q.  batchSize * numHeads *
+ *            seqLenQ and the grid must fit in an int32.  seqLenQ <= FA_DECODE_MAX_Q is legal and means what decode means: the result
+ *            is then flash_attention_decode*'s of the same arguments and the same forced numSplits, bit for bit (O and LSE), so a
+ *            serving engine may cross 16 rows from one step to the next
+ *   mask     decode's, unchanged: kvLens[b] ALREADY counts the new rows (`kv_lens += Sq; append; extend` is one graph).  With
+ *            len = clamp(kvLens[b], 1, capacity), row i sees k < max(len - seqLenQ + i + 1, 1) with is_causal and k < len without;
+ *            "at least key 0" covers len < seqLenQ.  No NaN rows
+ *   tiles    a row block (plan.rows_per_block packed rows g * seqLenQ + i of one K/V head; blocks are NOT head-aligned: row_blocks =
+ *            ceil(G * seqLenQ / rows_per_block)) walks only the 128-key tiles one of its rows can see: ntb = ceil(max over the
+ *            block's rows of the row's limit / 128); the tiles [0, ntb) are divided over numSplits in whole tiles by decode's formula
+ *            (split s takes [ntb s / ns, ntb (s + 1) / ns)).  Under the causal mask the lower row blocks of a long chunk read less.
+ *            A split past the end comes out empty (O = 0, LSE = -inf, weight 0), as in decode.  Paged and contiguous divide alike:
+ *            flash_attention_extend_paged equals flash_attention_extend on a contiguous copy of the same pages with seqLenK = the
+ *            capacity and the same numSplits, bit for bit
+ *   plan     flash_attention_extend_plan: fa_decode_plan for these calls (seqLenK = the capacity).  grid = batchSize * numHeadsKV *
+ *            row_blocks * num_splits.  numSplits = 0: decode's rule with units = batchSize * numHeadsKV * row_blocks -- a long chunk
+ *            fills the chip by its units alone and runs unsplit
+ *   precision  decode's: fp32 scores and softmax, weights as a bf16 hi + lo pair, fp32 accumulation, no fp16 anywhere and no range
+ *            caveat on V; e4m3fn -> bf16 exactly, in registers, kDescale folded into the score scale and vDescale into the final 1 / l
+ * Rejected before any launch: everything the decode sibling of the same form and kv_dtype rejects, with the same codes, except the
+ * FA_DECODE_MAX_Q cap; seqLenQ > capacity FA_ERR_BAD_SHAPE; a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE.
+ * Not done here: sliding windows, a per-sequence count of new rows (every sequence brings seqLenQ rows), attention sinks, fp8 Q, a
+ * backward, automatic routing from or to any existing call.
+ */
+int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
+
+int flash_attention_extend(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                           const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace,
+                           int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                           float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                           const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                           void* stream);
+
+int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                 const int32_t* kvLens, const int32_t* blockTable,
+                                 const float* kDescale, const float* vDescale, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                 int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                 float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                 const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                 void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 

@@ -40,6 +40,22 @@ Each line:
                                     prefill); bytes read + written = B Hkv 4096 d x 2 tensors x (2 + bytes per cache element)
               each with _min / _max over the windows (profiles/kv_append_bench.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
+--extend        flash_attention_extend / flash_attention_extend_paged (chunked prefill against the decode caches) instead of decode:
+              one line per shape and cache form -- "bf16", with --kv fp8 "fp8", with --paged "paged<page>" (and "paged<page>_fp8") --
+              over its own shapes (H32 Hkv8, d = 128 unless named; a chunk of Sq new rows behind a cached prefix, kv_lens = prefix + Sq):
+                chunk512_8k B1 Sq512 prefix 8192    chunk512_32k B1 Sq512 prefix 32768    chunk2048_0 B1 Sq2048 no prefix
+                chunk64_32k B1 Sq64 prefix 32768    batch8_ragged B8 Sq512 prefixes spread 1 k ... 32 k    d64_chunk512_8k d64
+              extend_ms         one call (O and the workspace given), timed like `ms`; splits, row_blocks, rows_per_block, grid: its plan
+              sliced_decode_ms  what the decode call can do for the same result: flash_attention_decode* over 16-row slices of Q,
+                                slice j with the lengths kv_lens - Sq + 16 (j + 1) (per-slice length tensors built beforehand);
+                                extend_vs_sliced_max_abs: the largest difference of the two results
+              prefill_pair_ms   ("bf16" only) what the prefill call can do: flash_attention (grouped-query) not causal over the prefix
+                                view plus causal over the chunk's own keys, both with their LSE, merged with torch ops in fp32 -- per
+                                sequence where the prefixes differ; pair_vs_extend_max_abs likewise
+              gather_ms, dequantise_ms  (paged / fp8 forms) the torch gather into a contiguous cache and the dequantisation to bf16
+                                that the prefill route would need first, each timed on its own
+              each with _min / _max over the windows (profiles/extend_bench.log).  With --splits: the forced
+              sweep of flash_attention_extend on the bf16 cache, one line per (shape, split count).
 """
 import argparse
 import json
@@ -80,6 +96,150 @@ def timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+EXTEND_SHAPES = [  # name, B, H, Hkv, Sq, prefixes, d
+    ("chunk512_8k", 1, 32, 8, 512, [8192], 128),
+    ("chunk512_32k", 1, 32, 8, 512, [32768], 128),
+    ("chunk2048_0", 1, 32, 8, 2048, [0], 128),
+    ("chunk64_32k", 1, 32, 8, 64, [32768], 128),
+    ("batch8_ragged", 8, 32, 8, 512, [1024 + (32768 - 1024) * b // 7 for b in range(8)], 128),
+    ("d64_chunk512_8k", 1, 32, 8, 512, [8192], 64),
+]
+
+
+def extend_main(args, fa, dev):
+    import torch
+    f8 = torch.float8_e4m3fn
+    shapes = EXTEND_SHAPES
+    if args.shape:
+        unknown = set(args.shape) - {x[0] for x in EXTEND_SHAPES}
+        if unknown:
+            raise SystemExit(f"unknown --extend shape(s): {sorted(unknown)}")
+        shapes = [x for x in EXTEND_SHAPES if x[0] in args.shape]
+    windows = lambda call, steps=None: sorted(timed(call, steps or args.steps, args.warmup) for _ in range(args.repeats))
+    stats = lambda key, v: {key: round(statistics.median(v), 5), key + "_min": round(v[0], 5), key + "_max": round(v[-1], 5)}
+    primed = False
+    for name, B, H, Hkv, Sq, prefixes, d in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        lens = [p + Sq for p in prefixes]
+        Sk = -(-max(lens) // 256) * 256                     # the capacity: whole pages of every --paged size
+        Q = torch.randn(B, H, Sq, d, device=dev, generator=g).to(torch.bfloat16)
+        K, V = (torch.randn(B, Hkv, Sk, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        O = torch.empty(B, H, Sq, d, device=dev, dtype=torch.bfloat16)
+        base = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "Sq": Sq, "prefix": prefixes if B > 1 else prefixes[0], "capacity": Sk, "d": d,
+                "io": "bfloat16", "repeats": args.repeats, "steps": args.steps}
+
+        def extend_call(Kc, Vc, table, kw, ns=0):
+            plan = fa.extend_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, ns)
+            ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            if table is None:
+                return plan, lambda: fa.flash_attention_extend(Q, Kc, Vc, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+            return plan, lambda: fa.flash_attention_extend_paged(Q, Kc, Vc, table, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+
+        def prime(call):
+            nonlocal primed
+            if not primed:   # >= 1 s of calls before the first timed window
+                t = 0.0
+                while t < 1000.0:
+                    t += timed(call, 20, 0) * 20
+                primed = True
+
+        if args.splits:
+            for ns in [int(x) for x in args.splits.split(",")]:
+                if ns > -(-Sk // 128):
+                    continue
+                plan, call = extend_call(K, V, None, {}, ns)
+                prime(call)
+                print(json.dumps(dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("extend_ms", windows(call)))), flush=True)
+            del Q, K, V, O
+            torch.cuda.empty_cache()
+            continue
+
+        def sliced_call(Kc, Vc, table, kw):
+            # flash_attention_decode* in 16-row slices: slice j holds the query rows [16 j, 16 j + 16) and sees kv_lens - Sq + its last row + 1
+            Os = torch.empty_like(O)
+            cuts = [(j, min(j + 16, Sq)) for j in range(0, Sq, 16)]
+            slens = [(lens_d - Sq + e).contiguous() for _, e in cuts]
+            ns = fa.decode_plan(B, H, Hkv, 16, Sk, d, fa.FA_DTYPE_BF16, 0)["num_splits"]
+            ws = torch.empty(max(fa.decode_workspace_size(B, H, 16, d, ns), 16), dtype=torch.uint8, device=dev)
+
+            def call():
+                for (a, e), L in zip(cuts, slens):
+                    if table is None:
+                        fa.flash_attention_decode(Q[:, :, a:e], Kc, Vc, L, is_causal=True, O=Os[:, :, a:e], workspace=ws, **kw)
+                    else:
+                        fa.flash_attention_decode_paged(Q[:, :, a:e], Kc, Vc, table, L, is_causal=True, O=Os[:, :, a:e], workspace=ws, **kw)
+            return Os, call
+
+        def pair_call():
+            # the prefill kernels: not causal over the prefix, causal (top-left = bottom-right: square) over the chunk's own keys
+            Op = torch.empty(B, H, Sq, d, device=dev, dtype=torch.float32)
+
+            def one(b0, b1, p):
+                q = Q[b0:b1]
+                o2, l2 = fa.flash_attention(q, K[b0:b1, :, p:p + Sq], V[b0:b1, :, p:p + Sq], is_causal=True, out_dtype=torch.float32, return_lse=True)
+                if p == 0:
+                    Op[b0:b1] = o2
+                    return
+                o1, l1 = fa.flash_attention(q, K[b0:b1, :, :p], V[b0:b1, :, :p], out_dtype=torch.float32, return_lse=True)
+                w1 = torch.sigmoid(l1 - l2)[..., None]
+                Op[b0:b1] = o1 * w1 + o2 * (1 - w1)
+
+            def call():
+                if len(set(prefixes)) == 1:
+                    one(0, B, prefixes[0])
+                else:
+                    for b, p in enumerate(prefixes):
+                        one(b, b + 1, p)
+            return Op, call
+
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in (int(x) for x in (args.paged or "").split(",") if x):
+            forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        if args.kv == "fp8":
+            quant = lambda T: (lambda ds: ((T.float() / ds[None, :, None, None]).clamp(-448, 448).to(f8), ds))((T.float().abs().amax(dim=(0, 2, 3)) / 448.0).float())
+            (K8, kds), (V8, vds) = quant(K), quant(V)
+        for form, fp8, page in forms:
+            Kc, Vc, table = (K8, V8, None) if fp8 else (K, V, None)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            line = dict(base, form=form)
+            if page:
+                n = Sk // page
+                perm = torch.randperm(B * n, device=dev, generator=g)
+                table = perm.reshape(B, n).to(torch.int32)
+                pools = []
+                for T in (Kc, Vc):
+                    T = T.view(torch.uint8) if fp8 else T      # (pages are moved as bytes)
+                    pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=T.dtype)
+                    pool[perm] = T.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
+                    pools.append(pool.view(f8) if fp8 else pool)
+                Kc, Vc = pools
+                tl = table.long()
+                gather = lambda: [P.view(torch.uint8 if fp8 else P.dtype)[tl].permute(0, 2, 1, 3, 4).reshape(B, Hkv, Sk, d) for P in (Kc, Vc)]
+                line.update(stats("gather_ms", windows(gather, max(10, args.steps // 10))))
+            if fp8:
+                deq = lambda: [(T.to(torch.bfloat16) * ds[None, :, None, None].to(torch.bfloat16)) for T, ds in ((K8, kds), (V8, vds))]
+                line.update(stats("dequantise_ms", windows(deq, max(10, args.steps // 10))))
+            plan, call = extend_call(Kc, Vc, table, kw)
+            prime(call)
+            line.update(stats("extend_ms", windows(call)))
+            line.update(splits=plan["num_splits"], row_blocks=plan["row_blocks"], rows_per_block=plan["rows_per_block"], grid=plan["grid"])
+            Os, scall = sliced_call(Kc, Vc, table, kw)
+            line.update(stats("sliced_decode_ms", windows(scall, max(3, args.steps // 20))))
+            line["extend_vs_sliced_max_abs"] = round((O.float() - Os.float()).abs().max().item(), 6)
+            line["sliced_over_extend"] = round(line["sliced_decode_ms"] / line["extend_ms"], 2)
+            if form == "bf16":
+                Op, pcall = pair_call()
+                line.update(stats("prefill_pair_ms", windows(pcall, max(10, args.steps // 10))))
+                line["pair_vs_extend_max_abs"] = round((O.float() - Op).abs().max().item(), 6)
+                line["pair_over_extend"] = round(line["prefill_pair_ms"] / line["extend_ms"], 2)
+                del Op
+            print(json.dumps(line), flush=True)
+            del Os
+        del Q, K, V, O
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -91,12 +251,15 @@ def main():
     ap.add_argument("--paged", default=None, help="comma-separated page sizes: add paged_ms per page size to every shape's line")
     ap.add_argument("--window", default=None, help="comma-separated sliding windows: add window_ms per window to every shape's line")
     ap.add_argument("--append", action="store_true", help="add append_ms / torch_append_ms / fill_ms / fill_tbps per cache form to every shape's line")
+    ap.add_argument("--extend", action="store_true", help="time flash_attention_extend on its own shapes, beside the decode-slice and prefill-pair routes")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.extend:
+        return extend_main(args, fa, dev)
     shapes = SHAPES
     if args.shape:
         unknown = set(args.shape) - {x[0] for x in SHAPES + EXTRA}
