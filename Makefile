@@ -25,7 +25,8 @@ build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
 tests/fa_tune tests/fa_tune_c128: HIPFLAGS += $(MFMA_VGPR)
-# the chunked-prefill kernel at d = 128 (extend_bf16.hip.h, four 16-row tiles per wave, launch bounds 256, 1): 206 accumulation registers
+# the chunked-prefill instantiations of the split-KV kernel at d = 128 (decode_bf16.hip.h with RT = 4: four 16-row tiles per wave, launch
+# bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
 # in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
 EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
 $(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)

@@ -18,7 +18,6 @@
 #include "weights.hip.h"
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
-#include "extend_bf16.hip.h"
 #include "kv_append.hip.h"
 
 namespace fa {
@@ -294,7 +293,7 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
     return (int)launch(r.kernel, r.grid, r.threads, r.lds_bytes, st, p);
 }
 
-// ---- split-KV decode (decode_bf16.hip.h) ----
+// ---- split-KV decode and chunked prefill against the decode caches (decode_bf16.hip.h: one kernel, split_kv_kernel) ----
 // The launch decision of flash_attention_decode, from shapes only (seqLenK is the cache CAPACITY; the lengths live in device memory).
 // Work units are (batch, K/V head, row block, split).  Library's choice of the split count: enough units for DECODE_WGS_PER_CU
 // workgroups on every CU, no split shorter than DECODE_MIN_TILES key tiles of the capacity, at most FA_DECODE_MAX_SPLITS.
@@ -304,58 +303,73 @@ static int run(const void* Q, const void* K, const void* V, void* O, float* lse,
 // on uniform batches -- two or three are resident per CU, so either is one resident round -- and a batch of unequal lengths, which
 // the host cannot see, balances 11 % better at two; a split of a single tile has nothing to prefetch behind and gains nothing.
 constexpr int DECODE_WGS_PER_CU = 2, DECODE_MIN_TILES = 2;
-// flash_attention_extend (extend_bf16.hip.h; `extend_d` below = its head dimension, 0 = the decode call): the same rule with
+// flash_attention_extend (the same kernel with ExtendCfg::RT 16-row tiles per wave): the same rule with
 // units = B * Hkv * row blocks of ExtendCfg::ROWS packed rows.  Workgroups per CU: as many as are resident (ExtendCfg::WGS_PER_CU) -- in the forced
 // sweep (profiles/extend_rt_sweep.log) a split beyond one resident round only costs: at 512 rows on an 8 k
 // prefix, d = 128, two splits of 256 units are 14 % slower than one, and with units short of a round the time is flat within 5 %
 // from half a round to one.  EXTEND_MIN_TILES is decode's value, not re-measured: no benchmark shape has a cache short enough for
 // it to bind.  A long chunk's units fill the chip by themselves and ns = 1.
 constexpr int EXTEND_MIN_TILES = 2;
-static int extend_rows_per_block(int d) { return d == 128 ? ExtendCfg<128>::ROWS : ExtendCfg<64>::ROWS; }
-static int extend_wgs_per_cu(int d) { return d == 128 ? ExtendCfg<128>::WGS_PER_CU : ExtendCfg<64>::WGS_PER_CU; }
+
+// What a call family is to the launch decision: built once per entry point (decode_form, extend_form), read by decode_check_shape,
+// decode_route and decode_run
+using SplitKernelOf = Kernel (*)(int d);
+struct SplitForm {
+    int rows_per_block;    // packed rows of a row block: 16 per 16-row tile of a wave
+    int wgs_per_cu;        // resident workgroups per CU the split rule fills
+    int min_tiles;         // no split shorter than this many key tiles of the capacity
+    bool q_to_capacity;    // seqLenQ is capped at the capacity, not at FA_DECODE_MAX_Q
+    const SplitKernelOf (*split_kernel_of)[2];   // [paged][kv8]: the selectors of the family's four cache forms
+};
+static constexpr SplitKernelOf DECODE_KERNELS[2][2] = {{decode_split_kernel_of, decode_fp8_split_kernel_of},
+                                                       {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}};
+static constexpr SplitKernelOf EXTEND_KERNELS[2][2] = {{extend_split_kernel_of, extend_fp8_split_kernel_of},
+                                                       {extend_paged_split_kernel_of, extend_paged_fp8_split_kernel_of}};
+static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, DECODE_KERNELS}; }
+static SplitForm extend_form(int d) {   // (any d but 128 takes the d = 64 values: decode_check_shape refuses it before they matter)
+    return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS}
+                    : SplitForm{ExtendCfg<64>::ROWS, ExtendCfg<64>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS};
+}
 
 struct DecodeRoute {
     int ns, row_blocks, tiles;
     int64_t grid;
 };
 
-static DecodeRoute decode_route(int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window, int extend_d = 0) {
+static DecodeRoute decode_route(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window) {
     DecodeRoute r{};
     const int rows = (H / Hkv) * Sq;                     // packed rows per K/V head
-    const int block = extend_d ? extend_rows_per_block(extend_d) : DecodeCfg<128>::ROWS;
-    r.row_blocks = (int)(((int64_t)rows + block - 1) / block);
+    r.row_blocks = (int)(((int64_t)rows + f.rows_per_block - 1) / f.rows_per_block);
     constexpr int TILE = DecodeCfg<128>::TILE;
     r.tiles = (Sk + TILE - 1) / TILE;
     if (window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)window + Sq - 1 + TILE - 1) / TILE + 1);
     const int64_t units = (int64_t)B * Hkv * r.row_blocks;
     if (numSplits > 0) r.ns = numSplits;
     else {
-        const int64_t want = ((int64_t)(extend_d ? extend_wgs_per_cu(extend_d) : DECODE_WGS_PER_CU) * device_cus() + units - 1) / units;
-        const int min_tiles = extend_d ? EXTEND_MIN_TILES : DECODE_MIN_TILES;
-        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / min_tiles, (int64_t)FA_DECODE_MAX_SPLITS}));
+        const int64_t want = ((int64_t)f.wgs_per_cu * device_cus() + units - 1) / units;
+        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / f.min_tiles, (int64_t)FA_DECODE_MAX_SPLITS}));
     }
     r.grid = units * r.ns;
     return r;
 }
 
-// extend: the flash_attention_extend calls -- seqLenQ up to the capacity, not FA_DECODE_MAX_Q
-static int decode_check_shape(int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits, int window,
-                              bool extend = false) {
+static int decode_check_shape(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits,
+                              int window) {
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if (Sq > (extend ? Sk : FA_DECODE_MAX_Q) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
-    if (extend && (int64_t)B * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (Sq > (f.q_to_capacity ? Sk : FA_DECODE_MAX_Q) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (f.q_to_capacity && (int64_t)B * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
     if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
     if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS || window < 0) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    if (decode_route(B, H, Hkv, Sq, Sk, numSplits, window, extend ? d : 0).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 
 static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// flash_attention_decode and flash_attention_decode_paged: one validation and launch sequence.  Contiguous: K / V are
+// flash_attention_decode*, flash_attention_extend*: one validation and launch sequence.  Contiguous: K / V are
 // [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
 // Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.  kv_dtype is the element type of
 // K / V: FA_DTYPE_BF16 (the type of Q), or FA_DTYPE_FP8_E4M3 with the two optional per-head descale arrays (the _fp8 entry points).
@@ -366,10 +380,10 @@ struct DecodePaging {
     int num_pages, page_size, max_pages;
 };
 
-static int decode_run(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, const float* kDescale,
-                      const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale, bool is_causal,
-                      int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ, const fa_strides* sK,
-                      const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream, bool extend = false) {
+static int decode_run(const SplitForm& f, const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                      const float* kDescale, const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale,
+                      bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ,
+                      const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
     if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
     if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
@@ -380,7 +394,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
         Sk = pg->max_pages * pg->page_size;
     }
-    int rc = decode_check_shape(B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window, extend);
+    int rc = decode_check_shape(f, B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window);
     if (rc != FA_OK) return rc;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
@@ -390,7 +404,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     // whole may be larger)
     const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;
     if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
-    const DecodeRoute r = decode_route(B, H, Hkv, Sq, Sk, numSplits, window, extend ? d : 0);
+    const DecodeRoute r = decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)B * H * Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
@@ -419,10 +433,7 @@ static int decode_run(const void* Q, const void* K, const void* V, void* O, floa
     p.window = window;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
-    const Kernel sk = extend ? (pg ? (kv8 ? extend_paged_fp8_split_kernel_of(d) : extend_paged_split_kernel_of(d))
-                                   : (kv8 ? extend_fp8_split_kernel_of(d) : extend_split_kernel_of(d)))
-                      : pg   ? (kv8 ? decode_paged_fp8_split_kernel_of(d) : decode_paged_split_kernel_of(d))
-                             : (kv8 ? decode_fp8_split_kernel_of(d) : decode_split_kernel_of(d));
+    const Kernel sk = f.split_kernel_of[pg != nullptr][kv8](d);
     hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
     if (e != hipSuccess || r.ns == 1) return (int)e;
     return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
@@ -697,12 +708,14 @@ int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeads
                                        int numSplits, int windowSize, fa_decode_plan* plan) {
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
-    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, windowSize);
+    const SplitForm f = decode_form();
+    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
+                                      windowSize);
     if (rc != FA_OK) return rc;
-    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize);
+    const DecodeRoute r = decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize);
     plan->num_splits = r.ns;
     plan->row_blocks = r.row_blocks;
-    plan->rows_per_block = DecodeCfg<128>::ROWS;
+    plan->rows_per_block = f.rows_per_block;
     plan->kv_block_rows = DecodeCfg<128>::TILE;
     plan->threads = DecodeCfg<128>::THREADS;
     plan->grid = (int)r.grid;
@@ -728,8 +741,8 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
-    return fa::decode_run(Q, K, V, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ,
+                          seqLenK, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
 }
 
 int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -738,8 +751,8 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV,
+                          seqLenQ, 0, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
 }
 
 int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -748,8 +761,9 @@ int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void
                                int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                                const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
+                          stream);
 }
 
 int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -760,8 +774,9 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
                                      const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
+                          stream);
 }
 
 // a bf16 cache has no descales: the logical cache is what lies in memory
@@ -775,8 +790,9 @@ int flash_attention_decode_window(const void* Q, const void* K, const void* V, v
                                   int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
                                   const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, nullptr, stream);
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
+                          nullptr, stream);
 }
 
 int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -787,20 +803,22 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                                         const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg, stream);
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
+                          &pg, stream);
 }
 
 int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
                                 int numSplits, fa_decode_plan* plan) {
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
-    const int rc = decode_check_shape(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0, true);
+    const SplitForm f = extend_form(dHead);
+    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0);
     if (rc != FA_OK) return rc;
-    const DecodeRoute r = decode_route(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0, dHead);
+    const DecodeRoute r = decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0);
     plan->num_splits = r.ns;
     plan->row_blocks = r.row_blocks;
-    plan->rows_per_block = extend_rows_per_block(dHead);
+    plan->rows_per_block = f.rows_per_block;
     plan->kv_block_rows = DecodeCfg<128>::TILE;
     plan->threads = DecodeCfg<128>::THREADS;
     plan->grid = (int)r.grid;
@@ -816,8 +834,9 @@ int flash_attention_extend(const void* Q, const void* K, const void* V, void* O,
                            int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                            const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream, true);
+    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
+                          stream);
 }
 
 int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -828,8 +847,9 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ, 0, dHead,
-                          scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream, true);
+    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
+                          stream);
 }
 
 int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,

@@ -1,5 +1,6 @@
-// decode_bf16.hip.h -- split-KV decode: 1 .. FA_DECODE_MAX_Q new query rows per sequence against a long K/V cache, every sequence
-// of the batch at its own length (flash_attention_decode).
+// decode_bf16.hip.h -- the split-KV kernel of the cache-reading calls.  Decode: 1 .. FA_DECODE_MAX_Q new query rows per sequence against a
+// long K/V cache, every sequence of the batch at its own length (flash_attention_decode).  Chunked prefill: the
+// same kernel with RT > 1, seqLenQ up to the capacity (flash_attention_extend; the RT bullet below).
 //
 // The prefill kernels (kernel_bf16.hip.h) are built around 256 query rows per workgroup and one workgroup per (head, query block)
 // walking all keys.  Decode is the opposite shape: a handful of rows, and the K/V read IS the cost.  So here
@@ -47,7 +48,16 @@
 //     anything.  In K that is harmless (the masked score is a select); V rows below `first` must arrive as 0 (0 x NaN would reach
 //     the accumulator), and they can only lie in the sequence's first tile, which is only ever loaded by the prologue: there a lane
 //     whose V row is below `first` uses an offset beyond any record count, and a paged 16-key group wholly below it a zero-byte
-//     descriptor.  The loop's own loads carry none of this.  window = 0: first = lo_i = 0, today's kernel term for term.
+//     descriptor.  The loop's own loads carry none of this.  window = 0: first = lo_i = 0.  The decode instantiations are
+//     WINDOW = true; with WINDOW = false (chunked prefill: DecodeParams::window is not read) every term of this bullet folds away.
+//   * RT (flash_attention_extend, flash_attention_extend_paged): a row block is 16 RT packed rows -- RT 16-row
+//     tiles per wave; decode is RT = 1.  One K fragment and one transposed V read per d group feed RT MFMAs: the cache is read once
+//     per 16 RT rows, which is the point of the chunked-prefill call.  The per-row state (Q fragments, m, l, O^T, the mask limits,
+//     the weights and alpha) is an array over rt, and a row of an MFMA column depends on no other column: for seqLenQ <= 16 the
+//     chunked-prefill result is flash_attention_decode's bit for bit, being the same text.  A row block walks only the tiles one of
+//     its rows can see: ntb = ceil(max over its rows of lim / 128), divided over the splits in whole tiles; under the causal mask
+//     the lower blocks of a long chunk read less.  The end-of-loop merge of the four waves runs once per rt through the same 16-row
+//     buffer (the wave's V image), with a second barrier between two tiles: LDS stays at the RT = 1 size.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -85,7 +95,7 @@ struct DecodeParams {
 template <int D, int ES = 2>   // ES: bytes per K/V element in memory (2: bf16, 1: e4m3fn); the LDS image of V is bf16 either way
 struct DecodeCfg {
     static constexpr int WAVES = 4, THREADS = 256;
-    static constexpr int ROWS = 16;                    // packed rows per workgroup: M of the 16x16x32 MFMA
+    static constexpr int ROWS = 16;                    // packed rows per 16-row tile: M of the 16x16x32 MFMA
     static constexpr int WKEYS = 32;                   // keys per wave per tile: K of the P.V MFMA
     static constexpr int TILE = WAVES * WKEYS;         // keys per workgroup per inner-loop tile
     static constexpr int KS = D / 32;                  // 32-wide k-steps of the Q K^T product
@@ -102,17 +112,34 @@ struct DecodeCfg {
     static_assert(ROWS * OROW <= VIMG, "the merge buffer reuses the V image");
 };
 
+// Chunked prefill: 16-row tiles per wave.  RT = 2 runs two workgroups per CU, RT = 4 one (its accumulators fill the register file);
+// RT = 8 spills.  Measured (profiles/extend_rt_sweep.log): at d = 128 RT = 4 with the MFMAs in VGPR form (the
+// Makefile's flag on the inst_extend units) is 4 ... 17 % faster than RT = 2 behind a cached prefix and 16 % slower on a chunk with no
+// prefix; at d = 64 the two are equal and RT = 2 keeps the occupancy.  FA_EXTEND_RT: a build-time override for such a comparison
+template <int D>
+struct ExtendCfg {
+#ifdef FA_EXTEND_RT
+    static constexpr int RT = FA_EXTEND_RT;
+#else
+    static constexpr int RT = D == 128 ? 4 : 2;
+#endif
+    static constexpr int ROWS = RT * DecodeCfg<D>::ROWS;   // packed rows per workgroup
+    static constexpr int WGS_PER_CU = RT >= 4 ? 1 : 2;     // resident workgroups per CU: what the split rule fills
+};
+
 __device__ __forceinline__ void store_out(void* O, int o_dtype, int64_t idx, float v) {
     if (o_dtype == FA_DTYPE_F32) ((float*)O)[idx] = v;
     else if (o_dtype == FA_DTYPE_BF16) ((__bf16*)O)[idx] = (__bf16)v;
     else ((_Float16*)O)[idx] = (_Float16)v;
 }
 
-template <int D, bool PAGED, bool KV8 = false>
-__global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams p) {
+// Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false.
+template <int D, int RT, bool PAGED, bool KV8, bool WINDOW>
+__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const DecodeParams p) {
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
+    constexpr int RPB = RT * C::ROWS;   // packed rows per row block
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const lds_ptr smem = (lds_ptr)smem_raw;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -129,32 +156,41 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     if (p.kv_lens) len = min(max(p.kv_lens[b], 1), p.Sk);
     len = __builtin_amdgcn_readfirstlane(len);
     // the lowest key any row sees: row 0's lower bound (0 without a window).  Keys below it are never part of the result
-    const int first = p.window > 0 ? max(max(len - p.Sq + 1, 1) - p.window, 0) : 0;
-    // this sequence's tiles [tlo, nt), divided over the splits in whole tiles
-    const int nt = (len + C::TILE - 1) / C::TILE, tlo = first / C::TILE;
-    const int t0 = tlo + (int)(((int64_t)(nt - tlo) * split) / p.ns), t1 = tlo + (int)(((int64_t)(nt - tlo) * (split + 1)) / p.ns);
+    const int first = WINDOW && p.window > 0 ? max(max(len - p.Sq + 1, 1) - p.window, 0) : 0;
+    // the tiles this row block can see: below the largest limit of its rows.  Causal: the limit grows with the query row, and the
+    // largest query row of the block is the last one -- unless the block reaches into the next head, then it holds a row Sq - 1.
+    // RT = 1: the host caps Sq at FA_DECODE_MAX_Q = 16, so a 16-row block always holds a row with lim = len (its last row is the last
+    // of all, or it holds the last query row of a head): limb = len without the arithmetic
+    const int nrows = p.G * p.Sq, pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
+    const int gl = prl / p.Sq, qmax = pr0 / p.Sq != gl ? p.Sq - 1 : prl - gl * p.Sq;
+    const int limb = RT > 1 && p.causal ? max(len - p.Sq + qmax + 1, 1) : len;
+    // this block's tiles [tlo, ntb), divided over the splits in whole tiles
+    const int ntb = (limb + C::TILE - 1) / C::TILE, tlo = first / C::TILE;
+    const int t0 = tlo + (int)(((int64_t)(ntb - tlo) * split) / p.ns), t1 = tlo + (int)(((int64_t)(ntb - tlo) * (split + 1)) / p.ns);
 
-    // this lane's packed row (column r of the swapped products): query head g of the group, query row i
-    const int pr = rb * C::ROWS + r;
-    const bool row_ok = pr < p.G * p.Sq;
-    const int g = row_ok ? pr / p.Sq : 0, qi = row_ok ? pr - g * p.Sq : 0;
-    const int h = kvh * p.G + g;
-    // keys this row sees: [lo, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0.
-    // The window's left edge follows the row's own position, causal or not; lo < limc <= lim: every row sees a key
-    const int limc = max(len - p.Sq + qi + 1, 1);
-    const int lim = p.causal ? limc : len;
-    const int lo = p.window > 0 ? max(limc - p.window, 0) : 0;
-    const unsigned span = (unsigned)(lim - lo);   // lo <= key < lim  <=>  (unsigned)(key - lo) < span: one compare per score
-
-    // B fragment of Q^T: Q[row r][32 ks + 8 h4 .. + 7].  KV8: Q[row r][64 (ks / 2) + 16 h4 + 8 (ks % 2) .. + 7] -- the d order in
-    // which a lane's 16-byte K loads hold two k-groups each
-    bf16x8 qf[C::KS];
-    {
+    // this lane's packed rows (column r of the swapped products, tile rt): query head g of the group, query row i.  The keys the row
+    // sees are [lo, lim).  Bottom-right aligned mask: the Sq rows are the LAST rows of the sequence; at least key 0.  The window's
+    // left edge follows the row's own position, causal or not; lo < limc <= lim: every row sees a key
+    int lo[RT];
+    unsigned span[RT];   // lo <= key < lim  <=>  (unsigned)(key - lo) < span: one compare per score
+    // B fragments of Q^T: Q[row][32 ks + 8 h4 .. + 7].  KV8: Q[row][64 (ks / 2) + 16 h4 + 8 (ks % 2) .. + 7] -- the d order in which
+    // a lane's 16-byte K loads hold two k-groups each
+    bf16x8 qf[RT][C::KS];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int pr = pr0 + rt * C::ROWS + r;
+        const bool row_ok = pr < nrows;
+        const int g = row_ok ? pr / p.Sq : 0, qi = row_ok ? pr - g * p.Sq : 0;
+        const int h = kvh * p.G + g;
+        const int limc = max(len - p.Sq + qi + 1, 1);
+        const int lim = p.causal ? limc : len;
+        lo[rt] = WINDOW && p.window > 0 ? max(limc - p.window, 0) : 0;
+        span[rt] = (unsigned)(lim - lo[rt]);
         const __bf16* q = p.Q + b * p.qB + h * p.qH + qi * p.qS + (KV8 ? 16 : 8) * h4;
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            qf[ks] = __builtin_bit_cast(bf16x8, row_ok ? *reinterpret_cast<const u32x4*>(q + (KV8 ? 64 * (ks >> 1) + 8 * (ks & 1) : 32 * ks)) : z);
+            qf[rt][ks] = __builtin_bit_cast(bf16x8, row_ok ? *reinterpret_cast<const u32x4*>(q + (KV8 ? 64 * (ks >> 1) + 8 * (ks & 1) : 32 * ks)) : z);
         }
     }
     // the K descale rides on the score scale (one scalar load per workgroup, like kv_lens: a replayed graph sees the value of the moment)
@@ -191,7 +227,8 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     // one, a group below `first` in the first tile takes the page of `first`: its descriptor holds no bytes)
     auto table_entries = [&](int t) {
         const int key = t * C::TILE + wv * C::WKEYS + 16 * (lane & 1);
-        return tb[max(min(key >> p.page_shift, last_page), first_page)];
+        const int page = min(key >> p.page_shift, last_page);
+        return tb[WINDOW ? max(page, first_page) : page];
     };
     // take the entries that have arrived into scalars for the next load_tile, THEN fetch tile t's into the register they leave
     auto next_entries = [&](int t) {
@@ -203,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     auto group_rsrc = [&](const __bf16* pool, int64_t page_stride, int64_t head_stride, int64_t row_stride, int entry, int key, bool cut) {
         const int page = min(max(entry, 0), p.num_pages - 1);
         const KV* base = (const KV*)pool + page * page_stride + kvh * head_stride + (key & ((1 << p.page_shift) - 1)) * row_stride;
-        const int rows = cut && key + 16 <= first ? 0 : min(len - key, 16);
+        const int rows = WINDOW && cut && key + 16 <= first ? 0 : min(len - key, 16);
         const int bytes = rows > 0 ? (rows - 1) * (int)(row_stride * ES) + D * ES : 0;
         const uint64_t a = (uint64_t)base;
         const uint64_t au = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
@@ -216,6 +253,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
     u32x4 kn[2][C::KL], vn[C::NV];
     auto load_tile = [&](int t, bool cut) {
         const int vkey0 = t * C::TILE + wave * C::WKEYS + vkey;   // the key of this lane's V load 0
+        auto below_first = [&](int n) { return WINDOW && cut && vkey0 + n * C::KPI < first; };
         if constexpr (!PAGED) {
             const int kt = t * C::TILE * ksb, vt = t * C::TILE * vsb;
 #pragma unroll
@@ -226,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)
                 vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    vrsrc, cut && vkey0 + n * C::KPI < first ? BEYOND : voff + vt + n * C::KPI * vsb, 0, 0));
+                    vrsrc, below_first(n) ? BEYOND : voff + vt + n * C::KPI * vsb, 0, 0));
         } else {
             __amdgpu_buffer_rsrc_t kr[2], vr[2];
 #pragma unroll
@@ -243,15 +281,20 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
 #pragma unroll
             for (int n = 0; n < C::NV; ++n)   // (V load n covers the keys KPI n .. KPI n + KPI - 1 of the wave's 32: one group)
                 vn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    vr[n * C::KPI / 16], cut && vkey0 + n * C::KPI < first ? BEYOND : gvoff + (n * C::KPI % 16) * vsb, 0, 0));
+                    vr[n * C::KPI / 16], below_first(n) ? BEYOND : gvoff + (n * C::KPI % 16) * vsb, 0, 0));
         }
     };
 
     const float NEG_INF = -__builtin_inff();
-    float m = NEG_INF, l = 0.f;   // running max (log2 domain, shared by the row's four lanes) and this lane's share of the sum
-    f32x4 o[C::DG];               // O^T: d = 16 dg + 4 h4 + reg, packed row r
+    float m[RT], l[RT];   // per tile rt: running max (log2 domain, shared by the row's four lanes), this lane's share of the sum
+    f32x4 o[RT][C::DG];   // O^T: d = 16 dg + 4 h4 + reg, packed row r of tile rt
 #pragma unroll
-    for (int dg = 0; dg < C::DG; ++dg) o[dg] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int rt = 0; rt < RT; ++rt) {
+        m[rt] = NEG_INF;
+        l[rt] = 0.f;
+#pragma unroll
+        for (int dg = 0; dg < C::DG; ++dg) o[rt][dg] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
     if (t0 < t1) {
         if constexpr (PAGED) {
@@ -270,18 +313,29 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
                 lds_write_b128(vimg, vwr + n * C::KPI * C::VROW + 16, fp8x8_to_bf16x8(vn[n][2], vn[n][3]));
             }
         }
-        f32x4 s[2];
+        // one K fragment feeds the RT row tiles
+        f32x4 s[RT][2];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) s[rt][0] = s[rt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kg = 0; kg < 2; ++kg) {
-            s[kg] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (!KV8) {
 #pragma unroll
-                for (int ks = 0; ks < C::KS; ++ks) s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, kn[kg][ks]), qf[ks], s[kg]);
+                for (int ks = 0; ks < C::KS; ++ks) {
+                    const bf16x8 a = __builtin_bit_cast(bf16x8, kn[kg][ks]);
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) s[rt][kg] = mfma_16x16x32(a, qf[rt][ks], s[rt][kg]);
+                }
             } else {
 #pragma unroll
                 for (int c = 0; c < C::KL; ++c) {   // a 16-byte load = the A fragments of two k-groups, in the d order of qf
-                    s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][0], kn[kg][c][1])), qf[2 * c], s[kg]);
-                    s[kg] = mfma_16x16x32(__builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][2], kn[kg][c][3])), qf[2 * c + 1], s[kg]);
+                    const bf16x8 a0 = __builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][0], kn[kg][c][1]));
+                    const bf16x8 a1 = __builtin_bit_cast(bf16x8, fp8x8_to_bf16x8(kn[kg][c][2], kn[kg][c][3]));
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) {
+                        s[rt][kg] = mfma_16x16x32(a0, qf[rt][2 * c], s[rt][kg]);
+                        s[rt][kg] = mfma_16x16x32(a1, qf[rt][2 * c + 1], s[rt][kg]);
+                    }
                 }
             }
         }
@@ -290,96 +344,111 @@ __global__ __launch_bounds__(256, 2) void decode_split_kernel(const DecodeParams
             load_tile(t + 1, false);
         }
 
-        // s[kg][reg]: key kb + 16 kg + 4 h4 + reg, packed row r
-        const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4, kbl = kb - lo;
-        float x[8];
-        float mx = NEG_INF;
+        // s[rt][kg][reg]: key kb + 16 kg + reg, packed row r of tile rt
+        const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4;
+        bf16x8 phi[RT], plo[RT];
+        float alpha[RT];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned rel = (unsigned)(kbl + 16 * (j >> 2) + (j & 3));   // key - lo
-            x[j] = rel < span ? s[j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
-            mx = fmaxf(mx, x[j]);
-        }
-        mx = max_all_quarters(mx);
-        const float m_new = fmaxf(m, mx);
-        const float m_use = m_new == NEG_INF ? 0.f : m_new;   // nothing visible yet: exp2(-inf - 0) = 0, never inf - inf
-        const float alpha = fast_exp2(m - m_use);
-        m = m_new;
-        float sum = 0.f;
-        uint32_t hi[4], lo[4];
+        for (int rt = 0; rt < RT; ++rt) {
+            const int kbl = kb - lo[rt];
+            float x[8];
+            float mx = NEG_INF;
 #pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            const float p0 = fast_exp2(x[j] - m_use), p1 = fast_exp2(x[j + 1] - m_use);
-            sum += p0 + p1;
-            // weights as a bf16 pair: hi = bf16(p), lo = bf16(p - hi) -- 16 significant bits between them
-            hi[j >> 1] = pack_bf16(p0, p1);
-            lo[j >> 1] = pack_bf16(p0 - bf16_lo(hi[j >> 1]), p1 - bf16_hi(hi[j >> 1]));
+            for (int j = 0; j < 8; ++j) {
+                const unsigned rel = (unsigned)(kbl + 16 * (j >> 2) + (j & 3));   // key - lo
+                x[j] = rel < span[rt] ? s[rt][j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
+                mx = fmaxf(mx, x[j]);
+            }
+            mx = max_all_quarters(mx);
+            const float m_new = fmaxf(m[rt], mx);
+            const float m_use = m_new == NEG_INF ? 0.f : m_new;   // nothing visible yet: exp2(-inf - 0) = 0, never inf - inf
+            alpha[rt] = fast_exp2(m[rt] - m_use);
+            m[rt] = m_new;
+            float sum = 0.f;
+            uint32_t whi[4], wlo[4];
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                const float p0 = fast_exp2(x[j] - m_use), p1 = fast_exp2(x[j + 1] - m_use);
+                sum += p0 + p1;
+                // weights as a bf16 pair: hi = bf16(p), lo = bf16(p - hi) -- 16 significant bits between them
+                whi[j >> 1] = pack_bf16(p0, p1);
+                wlo[j >> 1] = pack_bf16(p0 - bf16_lo(whi[j >> 1]), p1 - bf16_hi(whi[j >> 1]));
+            }
+            l[rt] = l[rt] * alpha[rt] + sum;
+            // B fragment of P^T: element j of quarter h4 = the MFMA's k index 8 h4 + j = key 16 (j >> 2) + 4 h4 + (j & 3)
+            phi[rt] = __builtin_bit_cast(bf16x8, u32x4{whi[0], whi[1], whi[2], whi[3]});
+            plo[rt] = __builtin_bit_cast(bf16x8, u32x4{wlo[0], wlo[1], wlo[2], wlo[3]});
         }
-        l = l * alpha + sum;
-        // B fragment of P^T: element j of quarter h4 = the MFMA's k index 8 h4 + j = key 16 (j >> 2) + 4 h4 + (j & 3)
-        const bf16x8 phi = __builtin_bit_cast(bf16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
-        const bf16x8 plo = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
 #pragma unroll
         for (int dg = 0; dg < C::DG; ++dg) {
-            // A fragment of V^T in that key order: rows 4 h4 .. + 3 (j < 4), rows 16 + 4 h4 .. + 3 (j >= 4)
+            // A fragment of V^T in that key order, read once for the RT tiles: rows 4 h4 .. + 3 (j < 4), rows 16 + 4 h4 .. + 3 (j >= 4)
             const s16x4 a0 = lds_read_tr16_b64(vimg, vrd + dg * 32);
             const s16x4 a1 = lds_read_tr16_b64(vimg, vrd + 16 * C::VROW + dg * 32);
             typedef __attribute__((ext_vector_type(8))) short s16x8;
             const bf16x8 a = __builtin_bit_cast(bf16x8, s16x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]});
-            o[dg] *= alpha;
-            o[dg] = mfma_16x16x32(a, phi, o[dg]);
-            o[dg] = mfma_16x16x32(a, plo, o[dg]);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                o[rt][dg] *= alpha[rt];
+                o[rt][dg] = mfma_16x16x32(a, phi[rt], o[rt][dg]);
+                o[rt][dg] = mfma_16x16x32(a, plo[rt], o[rt][dg]);
+            }
         }
     }
 
-    // ---- merge the four waves' (m, l, O^T) through LDS: each wave writes into its own V image, one barrier ----
-    l = sum_all_quarters(l);
+    // ---- merge the four waves' (m, l, O^T) through LDS, one 16-row tile at a time: each wave writes the tile into its own V image,
+    // one barrier, every thread sums one row's share over the waves; RT > 1: a second barrier keeps the next tile's writes behind
+    // these reads ----
     FA_LDS float* ml = reinterpret_cast<FA_LDS float*>(smem + C::ML_OFF);
-    if (h4 == 0) {
-        ml[wave * C::ROWS + r] = m;
-        ml[(C::WAVES + wave) * C::ROWS + r] = l;
-    }
-#pragma unroll
-    for (int dg = 0; dg < C::DG; ++dg)
-        *reinterpret_cast<FA_LDS f32x4*>(vimg + r * C::OROW + (16 * dg + 4 * h4) * 4) = o[dg];
-    __syncthreads();
-
-    // thread -> packed row tid / 16, DPT consecutive d
-    constexpr int DPT = D / 16;
+    constexpr int DPT = D / 16;   // thread -> packed row tid / 16 of the tile, DPT consecutive d
     const int orow = tid >> 4, d0 = (tid & 15) * DPT;
-    float M = NEG_INF;
 #pragma unroll
-    for (int w = 0; w < C::WAVES; ++w) M = fmaxf(M, ml[w * C::ROWS + orow]);
-    float L = 0.f, acc[DPT];
-#pragma unroll
-    for (int j = 0; j < DPT; ++j) acc[j] = 0.f;
-    if (M != NEG_INF) {
-#pragma unroll
-        for (int w = 0; w < C::WAVES; ++w) {
-            const float wgt = fast_exp2(ml[w * C::ROWS + orow] - M);   // a wave that saw nothing: exp2(-inf) = 0
-            L += wgt * ml[(C::WAVES + w) * C::ROWS + orow];
-            FA_LDS const float* src = reinterpret_cast<FA_LDS const float*>(smem + w * C::VIMG + orow * C::OROW) + d0;
-#pragma unroll
-            for (int j = 0; j < DPT; ++j) acc[j] += wgt * src[j];
+    for (int rt = 0; rt < RT; ++rt) {
+        if (rt > 0) __syncthreads();
+        const float lr = sum_all_quarters(l[rt]);
+        if (h4 == 0) {
+            ml[wave * C::ROWS + r] = m[rt];
+            ml[(C::WAVES + wave) * C::ROWS + r] = lr;
         }
-    }
-    const int opr = rb * C::ROWS + orow;
-    if (opr >= p.G * p.Sq) return;
-    const int og = opr / p.Sq, oi = opr - og * p.Sq, oh = kvh * p.G + og;
-    float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
-    if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
-    const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
-    const int64_t row = ((int64_t)b * p.H + oh) * p.Sq + oi;
-    if (p.ns == 1) {
-        const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + d0;
 #pragma unroll
-        for (int j = 0; j < DPT; ++j) store_out(p.O, p.o_dtype, base + j, acc[j] * inv);
-        if (p.lse && (tid & 15) == 0) p.lse[row] = lse;
-    } else {
-        float* dst = p.part_o + ((int64_t)split * p.rows + row) * D + d0;
+        for (int dg = 0; dg < C::DG; ++dg)
+            *reinterpret_cast<FA_LDS f32x4*>(vimg + r * C::OROW + (16 * dg + 4 * h4) * 4) = o[rt][dg];
+        __syncthreads();
+
+        float M = NEG_INF;
 #pragma unroll
-        for (int j = 0; j < DPT; ++j) dst[j] = acc[j] * inv;
-        if ((tid & 15) == 0) p.part_lse[(int64_t)split * p.rows + row] = lse;
+        for (int w = 0; w < C::WAVES; ++w) M = fmaxf(M, ml[w * C::ROWS + orow]);
+        float L = 0.f, acc[DPT];
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) acc[j] = 0.f;
+        if (M != NEG_INF) {
+#pragma unroll
+            for (int w = 0; w < C::WAVES; ++w) {
+                const float wgt = fast_exp2(ml[w * C::ROWS + orow] - M);   // a wave that saw nothing: exp2(-inf) = 0
+                L += wgt * ml[(C::WAVES + w) * C::ROWS + orow];
+                FA_LDS const float* src = reinterpret_cast<FA_LDS const float*>(smem + w * C::VIMG + orow * C::OROW) + d0;
+#pragma unroll
+                for (int j = 0; j < DPT; ++j) acc[j] += wgt * src[j];
+            }
+        }
+        const int opr = pr0 + rt * C::ROWS + orow;
+        if (opr < nrows) {   // (no early exit: the barriers of the tiles to come are the whole workgroup's)
+            const int og = opr / p.Sq, oi = opr - og * p.Sq, oh = kvh * p.G + og;
+            float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
+            if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
+            const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
+            const int64_t row = ((int64_t)b * p.H + oh) * p.Sq + oi;
+            if (p.ns == 1) {
+                const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + d0;
+#pragma unroll
+                for (int j = 0; j < DPT; ++j) store_out(p.O, p.o_dtype, base + j, acc[j] * inv);
+                if (p.lse && (tid & 15) == 0) p.lse[row] = lse;
+            } else {
+                float* dst = p.part_o + ((int64_t)split * p.rows + row) * D + d0;
+#pragma unroll
+                for (int j = 0; j < DPT; ++j) dst[j] = acc[j] * inv;
+                if ((tid & 15) == 0) p.part_lse[(int64_t)split * p.rows + row] = lse;
+            }
+        }
     }
 }
 
@@ -425,12 +494,16 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams 
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (inst_decode_bf16.hip, inst_decode_paged_bf16.hip, inst_decode_fp8.hip, inst_decode_paged_fp8.hip) ----
+// ---- selectors (the inst_decode_*.hip and inst_extend_*.hip units: one per cache form and call family) ----
 struct Kernel;
 Kernel decode_split_kernel_of(int d);
 Kernel decode_paged_split_kernel_of(int d);
 Kernel decode_fp8_split_kernel_of(int d);
 Kernel decode_paged_fp8_split_kernel_of(int d);
+Kernel extend_split_kernel_of(int d);
+Kernel extend_paged_split_kernel_of(int d);
+Kernel extend_fp8_split_kernel_of(int d);
+Kernel extend_paged_fp8_split_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 
 }  // namespace fa

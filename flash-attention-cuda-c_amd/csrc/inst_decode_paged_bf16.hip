@@ -7,7 +7,8 @@
 namespace fa {
 
 Kernel decode_paged_split_kernel_of(int d) {
-    return d == 128 ? kernel_of<decode_split_kernel<128, true>>(DecodeCfg<128>::LDS_BYTES) : kernel_of<decode_split_kernel<64, true>>(DecodeCfg<64>::LDS_BYTES);
+    return d == 128 ? kernel_of<split_kv_kernel<128, 1, true, false, true>>(DecodeCfg<128, 2>::LDS_BYTES)
+                    : kernel_of<split_kv_kernel<64, 1, true, false, true>>(DecodeCfg<64, 2>::LDS_BYTES);
 }
 
 }  // namespace fa

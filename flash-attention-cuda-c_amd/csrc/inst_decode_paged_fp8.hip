@@ -7,7 +7,8 @@
 namespace fa {
 
 Kernel decode_paged_fp8_split_kernel_of(int d) {
-    return d == 128 ? kernel_of<decode_split_kernel<128, true, true>>(DecodeCfg<128, 1>::LDS_BYTES) : kernel_of<decode_split_kernel<64, true, true>>(DecodeCfg<64, 1>::LDS_BYTES);
+    return d == 128 ? kernel_of<split_kv_kernel<128, 1, true, true, true>>(DecodeCfg<128, 1>::LDS_BYTES)
+                    : kernel_of<split_kv_kernel<64, 1, true, true, true>>(DecodeCfg<64, 1>::LDS_BYTES);
 }
 
 }  // namespace fa

@@ -1,6 +1,6 @@
 // kv_append.hip.h -- the WRITE side of the decode caches (flash_attention_kv_append, flash_attention_kv_append_paged; DESIGN.md
-// section 18): the last Sq rows of every sequence, given as bf16 [B, Hkv, Sq, d], go into the cache that split-KV decode
-// (decode_bf16.hip.h) reads -- contiguous [B, Hkv, capacity, d] or pools of pages behind a block table; bf16 (a bit copy) or OCP
+// section 18): the last Sq rows of every sequence, given as bf16 [B, Hkv, Sq, d], go into the cache that the split-KV kernel
+// (decode_bf16.hip.h: decode and chunked prefill) reads -- contiguous [B, Hkv, capacity, d] or pools of pages behind a block table; bf16 (a bit copy) or OCP
 // e4m3fn with one fp32 descale per K/V head (divide, saturate, round to nearest even once).
 //
 //   * POSITIONS.  L = min(kv_lens[b], capacity) ALREADY counts the new rows: new row i is key position p = L - Sq + i, written when

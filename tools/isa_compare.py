@@ -3,6 +3,7 @@
 function numbers in block labels ignored) and by their resource metadata (VGPRs, SGPRs, AGPRs, LDS, scratch).
 usage: isa_compare.py old.s new.s              -- one file each
        isa_compare.py old_dir new_dir          -- every *.s in each directory
+       isa_compare.py old new REGEX=REPL ...   -- rename the old side's symbols first (re.sub), for a kernel whose name changed
 Kernels are paired by symbol name; prints one line per kernel that differs or exists on one side only, then a summary line."""
 import glob
 import os
@@ -61,6 +62,8 @@ def load(path):
 
 
 a, b = load(sys.argv[1]), load(sys.argv[2])
+for pattern, _, repl in (arg.partition("=") for arg in sys.argv[3:]):
+    a = {re.sub(pattern, repl, k): v for k, v in a.items()}
 same = 0
 for k in sorted(set(a) | set(b)):
     if k not in a or k not in b:
