@@ -28,6 +28,7 @@ tests/fa_tune tests/fa_tune_c128: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill instantiations of the split-KV kernel at d = 128 (decode_bf16.hip.h with RT = 4: four 16-row tiles per wave, launch
 # bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
 # in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
+# (the wildcard takes the ragged instantiations, inst_extend_varlen_*.hip, with them: the same kernel with a per-sequence row count)
 EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
 $(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)
 
@@ -76,14 +77,22 @@ tests/micro/%: tests/micro/%.hip
 # runs in a process of its own with the matching runtime preloaded; tests/main.cpp (the C++ harness) is compiled and linked under the
 # same flags as a build check (running it needs a GPU).
 ASAN_DIR  := build/asan
+CLANGXX   := /opt/rocm/lib/llvm/bin/clang++
 CLANG_ASAN_RT := $(shell /opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 GCC_ASAN_RT   := $(shell gcc -print-file-name=libasan.so)
 SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
-asan: $(LIB) oracle
+# asan-host: the library's host code under the sanitizers, and tests/host_ladder.cpp -- a stand-alone program (its own main, built
+# with the same flags, nothing preloaded) that walks the validation ladders and the plans of the ragged entry points -- built and run.
+asan-host: $(LIB)
 	@mkdir -p $(ASAN_DIR)
-	gcc -O1 -march=x86-64-v3 -fopenmp -fPIC -Wall -Wextra -std=c11 $(SANFLAGS) -shared -o $(ASAN_DIR)/liboracle_attention.so oracle/cpu_attention.c -lm
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/libflash_attention.so $(ASAN_DIR)/FlashAttention.o $(filter-out build/obj/FlashAttention.o,$(KOBJ))
+	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_ladder tests/host_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
+	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_ladder
+
+asan: asan-host oracle
+	gcc -O1 -march=x86-64-v3 -fopenmp -fPIC -Wall -Wextra -std=c11 $(SANFLAGS) -shared -o $(ASAN_DIR)/liboracle_attention.so oracle/cpu_attention.c -lm
 	$(HIPCC) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/fa_test tests/main.cpp -L$(ASAN_DIR) -lflash_attention -Loracle -loracle_attention \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../oracle'
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 LD_PRELOAD=$(GCC_ASAN_RT) \
@@ -108,4 +117,4 @@ asm: $(KASM)
 clean:
 	rm -f $(LIB) $(PKG)/fa_main tests/fa_test tests/fa_tune tests/unit_kernels tests/micro/simd_mix tests/micro/valu_rates tests/micro/atomic_latency oracle/liboracle_attention.so
 	rm -rf build
-.PHONY: all lib tune oracle clean asm asan
+.PHONY: all lib tune oracle clean asm asan asan-host

@@ -20,6 +20,10 @@ entry points for that path:
 * ``flash_attention_extend(Q, K, V, kv_lens)`` / ``flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens)`` --
   chunked prefill against the same caches, all four forms: any number of new rows up to the capacity, decode's mask and
   arithmetic (``extend_plan``).
+* ``flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens)`` / ``flash_attention_extend_paged_varlen(Q, K_pool, V_pool,
+  block_table, cu_seqlens_q, kv_lens)`` -- RAGGED chunked prefill: every sequence its own number of new rows (decode rows, chunks,
+  idle slots in one call), Q and O packed by token ``[T, H, d]``, the offsets read on the device (``extend_varlen_plan``); and
+  ``kv_cache_append_varlen`` / ``kv_cache_append_paged_varlen``, the append of such a batch's new rows.
 * ``kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens)`` / ``kv_cache_append_paged(..., block_table, kv_lens)`` -- the write
   side of those caches: the last Sq rows of every sequence, bf16, copied into a bf16 cache or quantised (divide by the per-head
   descale, saturate, round to nearest even) into an fp8 one, in place, positions and pages found on the device.
@@ -47,6 +51,7 @@ FA_FLAG_BF16_WEIGHTS = 2    # ... to bf16 on every row; flags = 0: fp16 on the r
 FA_EARLY_KEYS = 1024
 FA_DECODE_MAX_Q = 16        # flash_attention_decode: most new query rows per sequence
 FA_DECODE_MAX_SPLITS = 64   # ... and the cap of num_splits
+FA_VARLEN_MAX_BATCH = 1024  # flash_attention_extend_varlen, kv_cache_append_varlen: most sequences per call
 
 # every symbol include/flash_attention.h declares
 EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", "flash_attention_cross", "flash_attention_ex", "flash_attention_weights", "flash_attention_shard_range", "flash_attention_sharded",
@@ -57,6 +62,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_decode_window", "flash_attention_decode_paged_window", "flash_attention_decode_plan_window",
            "flash_attention_kv_append", "flash_attention_kv_append_paged",
            "flash_attention_extend", "flash_attention_extend_paged", "flash_attention_extend_plan",
+           "flash_attention_extend_varlen", "flash_attention_extend_paged_varlen", "flash_attention_extend_varlen_plan",
+           "flash_attention_kv_append_varlen", "flash_attention_kv_append_paged_varlen",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -156,6 +163,17 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_extend_paged.restype = i
         L.flash_attention_extend_plan.argtypes = L.flash_attention_decode_plan.argtypes
         L.flash_attention_extend_plan.restype = i
+        # the ragged calls: the uniform siblings' lists with cuSeqlensQ before kvLens (seqLenQ / seqLenNew in the place of totalQ)
+        L.flash_attention_extend_varlen.argtypes = [vp] * 10 + L.flash_attention_extend.argtypes[9:]
+        L.flash_attention_extend_varlen.restype = i
+        L.flash_attention_extend_paged_varlen.argtypes = [vp] * 11 + L.flash_attention_extend_paged.argtypes[10:]
+        L.flash_attention_extend_paged_varlen.restype = i
+        L.flash_attention_extend_varlen_plan.argtypes = L.flash_attention_extend_plan.argtypes
+        L.flash_attention_extend_varlen_plan.restype = i
+        L.flash_attention_kv_append_varlen.argtypes = [vp] * 8 + L.flash_attention_kv_append.argtypes[7:]
+        L.flash_attention_kv_append_varlen.restype = i
+        L.flash_attention_kv_append_paged_varlen.argtypes = [vp] * 9 + L.flash_attention_kv_append_paged.argtypes[8:]
+        L.flash_attention_kv_append_paged_varlen.restype = i
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -450,21 +468,47 @@ def extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
+def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
+    """What a flash_attention_extend_varlen call launches (fa_decode_plan as a dict; ``total_q`` the bound on the packed rows, ``Sk``
+    the capacity); ``num_splits`` 0 = the library's choice.  ``row_blocks`` is the host's BOUND on the row blocks of the whole batch,
+    ``(G * total_q + B * (rows_per_block - 1)) // rows_per_block``; the workspace is ``decode_workspace_size(1, H, total_q, d, ns)``."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+
+
 def decode_workspace_size(B, H, Sq, d, num_splits):
     """Bytes of device scratch flash_attention_decode needs for ``num_splits`` splits as planned (0 for one split)."""
     return int(lib().flash_attention_decode_workspace_size(B, H, Sq, d, num_splits))
 
 
-def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None):
+def _cu_seqlens(cu_seqlens_q, device_of):
+    """the checks of a ragged front's ``cu_seqlens_q``; returns the batch size"""
+    import torch
+    cu = cu_seqlens_q
+    if not getattr(cu, "is_cuda", False) or cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous() \
+            or cu.device != device_of.device:
+        raise ValueError("cu_seqlens_q must be a dense int32 device tensor [B + 1] on the device of the rows")
+    return cu.shape[0] - 1
+
+
+def _token_view(t, what):
+    """a token-packed ``[T, heads, d]`` tensor as the ``[1, heads, T, d]`` view the shared fronts take (no copy)"""
+    if t.dim() != 3:
+        raise ValueError(f"{what} must be packed by token: [T, heads, d]")
+    return t.unsqueeze(0).transpose(1, 2)
+
+
+def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None, batch=None):
     """The checks both decode fronts make of Q and the tensors that play K/V (``kv``, ``layout``: their names and shape in the error
     texts; ``table``: the paged front's block table -- pools are not indexed by the batch).  True when the call is the fp8-cache form (bf16 Q,
     e4m3fn K and V); the dtypes and the descales are checked either way."""
     import torch
     if not (Q.is_cuda and K.is_cuda and V.is_cuda and (table is None or table.is_cuda)):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
-    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or (table is None and Q.shape[0] != K.shape[0]) or Q.shape[3] != K.shape[3] \
-            or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
-        raise ValueError(f"Q must be [B, H, Sq, d] and {kv} {layout} with Hkv dividing H")
+    if Q.dim() != 4 or K.dim() != 4 or K.shape != V.shape or (table is None and (Q.shape[0] if batch is None else batch) != K.shape[0]) \
+            or Q.shape[3] != K.shape[3] or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
+        raise ValueError(f"Q must be {'[B, H, Sq, d]' if batch is None else '[T, H, d]'} and {kv} {layout} with Hkv dividing H")
     f8 = getattr(torch, "float8_e4m3fn", None)
     fp8 = f8 is not None and Q.dtype == torch.bfloat16 and K.dtype == f8 and V.dtype == f8
     if not fp8 and not (Q.dtype == K.dtype == V.dtype):
@@ -481,15 +525,21 @@ def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None):
 
 
 def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-            stream, k_descale, v_descale, window, plan=None):
+            stream, k_descale, v_descale, window, plan=None, cu_seqlens_q=None):
     """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
     point (fp8: its ``_fp8`` twin; a window: its ``_window`` twin, which takes both cache types), ``tables`` its tensors between
     kvLens and the workspace, ``geometry`` its ints between seqLenQ and dHead; ``decode_plan`` / ``decode_workspace_size`` are asked
-    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name."""
+    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name.
+    The ragged fronts pass ``cu_seqlens_q`` (checked by them) and Q -- and O, if given -- as ``_token_view``s: Sq is then the bound
+    on the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled."""
     import torch
     window = _window(window)
     both = plan is not None or bool(window)
     B, H, Sq, d = Q.shape
+    ragged = cu_seqlens_q is not None
+    if ragged:
+        B = cu_seqlens_q.shape[0] - 1
+    new = torch.zeros if ragged else torch.empty      # ragged: rows no sequence owns are not written
     Hkv = K.shape[1]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
                                 or not kv_lens.is_contiguous()):
@@ -498,23 +548,25 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
     ns = (plan(B, H, Hkv, Sq, capacity, d, odt, num_splits) if plan else decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits, window))["num_splits"]
-    need = decode_workspace_size(B, H, Sq, d, ns)
+    need = decode_workspace_size(1 if ragged else B, H, Sq, d, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
         # the workspace (like an O or LSE allocated here) belongs to the stream the kernels run on: see flash_attention_backward
         with torch.cuda.stream(s):
             if O is None:
-                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+                O = new((Sq, H, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device).unsqueeze(0).transpose(1, 2) if ragged \
+                    else new((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
             elif O.shape != Q.shape or not O.is_cuda:
                 raise ValueError("O must be a device tensor shaped like Q")
-            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            lse = new((H, Sq) if ragged else (B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
             if workspace is None and need:
                 workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
         if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
             raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
         st = [_strides(t) for t in (Q, K, V, O)]
         ptr = lambda t: t.data_ptr() if t is not None else None
-        ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables))
+        ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), ptr(lse), *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens),
+                *map(ptr, tables))
         if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
         dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
@@ -522,6 +574,8 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
                     _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
+    if ragged:
+        O = O.transpose(1, 2).squeeze(0)      # back to [T, H, d]
     return (O, lse) if return_lse else O
 
 
@@ -622,17 +676,77 @@ def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
                    k_descale, v_descale, None, plan=extend_plan)
 
 
-def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None):
-    """What kv_cache_append and kv_cache_append_paged share: the tensor checks of the decode fronts (``_decode_inputs``, the new rows
-    in the place of Q), the bounds of Sq, and the call."""
+def _table_geometry(block_table, B):
+    """(max_pages, table_stride) of a ragged front's block table, after the paged fronts' checks"""
     import torch
+    t = block_table
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
+
+
+def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
+                                  return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+    """RAGGED chunked prefill against a decode cache: one call for a mixed batch -- decoding sequences, chunks of a prefill, idle
+    slots -- on token-major tensors.  Q ``[T, H, d]`` bf16 (strided views accepted, last dimension contiguous), packed by token;
+    ``cu_seqlens_q``: int32 device tensor ``[B + 1]``, sequence b owns the rows ``cu[b] .. cu[b + 1] - 1`` (each pair clamped into
+    [0, T]; a sequence without rows is an idle slot), read by the kernel like ``kv_lens``; K, V: the cache ``[B, Hkv, capacity, d]``
+    of ``flash_attention_extend``, bf16 or ``torch.float8_e4m3fn`` with ``k_descale`` / ``v_descale``.  T is a bound (the allocation):
+    rows beyond ``cu[-1]`` are not written.
+
+    Per sequence everything is ``flash_attention_extend``'s with that sequence's row count: ``kv_lens[b]`` already counts the new
+    rows, the bottom-right ``is_causal``, the tiles and splits -- the O and LSE of a sequence are, bit for bit, those of
+    ``flash_attention_extend`` on that sequence alone under the same forced ``num_splits``.  ``num_splits`` 0 = the library's choice
+    (``extend_varlen_plan``); ``workspace``: ``decode_workspace_size(1, H, T, d, ns)`` bytes.  Returns O ``[T, H, d]`` or, with
+    ``return_lse``, ``(O, LSE)`` with the LSE fp32 ``[H, T]``; an O or LSE allocated here is zero-filled.  No CPU fallback."""
+    Qv = _token_view(Q, "Q")
+    B = _cu_seqlens(cu_seqlens_q, Q) if Q.is_cuda else None
+    fp8 = _decode_inputs("flash_attention_extend_varlen", "K, V", "[B, Hkv, capacity, d]", Qv, K, V, k_descale, v_descale, batch=B)
+    Sk = K.shape[2]
+    return _decode("flash_attention_extend_varlen", fp8, Qv, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits,
+                   return_lse, None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, None,
+                   plan=extend_varlen_plan, cu_seqlens_q=cu_seqlens_q)
+
+
+def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
+                                        out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
+                                        k_descale=None, v_descale=None):
+    """``flash_attention_extend_varlen`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
+    ``[B, max_pages]`` of ``flash_attention_extend_paged`` (``extend_varlen_plan`` is asked with ``Sk = max_pages * page``).  The
+    table row and the length of a sequence without rows are not read.  The result is ``flash_attention_extend_varlen``'s on a
+    contiguous copy of the same pages, bit for bit.  No CPU fallback."""
+    Qv = _token_view(Q, "Q")
+    fp8 = _decode_inputs("flash_attention_extend_paged_varlen", "K_pool, V_pool", "[P, Hkv, page, d]", Qv, K_pool, V_pool, k_descale,
+                         v_descale, table=block_table)
+    B = _cu_seqlens(cu_seqlens_q, Q)
+    P, _, page = K_pool.shape[:3]
+    max_pages, table_stride = _table_geometry(block_table, B)
+    return _decode("flash_attention_extend_paged_varlen", fp8, Qv, K_pool, V_pool, max_pages * page, (block_table,),
+                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
+                   None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, None, plan=extend_varlen_plan,
+                   cu_seqlens_q=cu_seqlens_q)
+
+
+def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None,
+            cu_seqlens_q=None):
+    """What kv_cache_append and kv_cache_append_paged share: the tensor checks of the decode fronts (``_decode_inputs``, the new rows
+    in the place of Q), the bounds of Sq, and the call.  The ragged fronts pass ``cu_seqlens_q`` and the new rows as ``_token_view``s:
+    Sq is then the bound on the packed rows (not capped at the capacity) and the batch is cu_seqlens_q's."""
+    import torch
+    ragged = cu_seqlens_q is not None
     if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
-        raise ValueError(f"K_new, V_new must be [B, Hkv, Sq, d] of one dtype, with the K/V heads of {kv} {layout}")
+        raise ValueError(f"K_new, V_new must be {'[T, Hkv, d]' if ragged else '[B, Hkv, Sq, d]'} of one dtype, with the K/V heads of {kv} {layout}")
     if not V_new.is_cuda:
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
-    fp8 = _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=table)
+    batch = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
+    fp8 = _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=table, batch=batch)
     B, Hkv, Sq, d = K_new.shape
-    if Sq < 1 or Sq > capacity:
+    if ragged:
+        B = batch
+        if table is not None:      # (the paged ragged front leaves the table's checks to here, where the batch is known)
+            max_pages, table_stride = _table_geometry(table, B)
+            geometry = (K.shape[0], K.shape[2], max_pages, table_stride)
+    if Sq < 1 or (Sq > capacity and not ragged):
         raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
                                 or not kv_lens.is_contiguous()):
@@ -640,7 +754,8 @@ def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geom
     with torch.cuda.device(K_new.device):
         st = [_strides(t) for t in (K_new, V_new, K, V)]
         ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = getattr(lib(), symbol)(K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(), ptr(kv_lens), *map(ptr, tables),
+        rc = getattr(lib(), symbol)(K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                    *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables),
                                     ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype),
                                     _dtype_code(K.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
     _check(rc)
@@ -686,6 +801,31 @@ def kv_cache_append_paged(K_new, V_new, K_pool, V_pool, block_table, kv_lens=Non
     table_stride = table.stride(0) if B > 1 else max_pages
     _append("flash_attention_kv_append_paged", "kv_cache_append_paged", "K_pool, V_pool", "[P, Hkv, page, d]", K_new, V_new, K_pool, V_pool,
             max_pages * page, (table,), (P, page, max_pages, table_stride), kv_lens, k_descale, v_descale, stream, table=table)
+
+
+def kv_cache_append_varlen(K_new, V_new, K_cache, V_cache, cu_seqlens_q, kv_lens=None, k_descale=None, v_descale=None, stream=None):
+    """RAGGED ``kv_cache_append``: the new rows of a mixed batch, packed by token -- ``K_new``, ``V_new`` bf16 ``[T, Hkv, d]`` (strided
+    views accepted, last dimension contiguous) with ``cu_seqlens_q`` (int32 device tensor ``[B + 1]``: the one
+    ``flash_attention_extend_varlen`` takes) -- go into the caches ``[B, Hkv, capacity, d]``.  Per sequence, with ``sq_b`` its row
+    count and ``L = min(kv_lens[b], capacity)``: row i goes to position ``L - sq_b + i`` when that is >= 0; ``L <= 0`` or
+    ``sq_b == 0`` writes nothing; rows beyond ``cu[-1]`` are not read.  The bytes written for a sequence are those of
+    ``kv_cache_append`` for that sequence alone; every other byte keeps its value.  T is not capped at the capacity.  A step of a
+    mixed batch is ``kv_lens += q_lens; kv_cache_append_varlen(...); flash_attention_extend_varlen(..., is_causal=True)``, one
+    graph.  Returns None.  No CPU fallback."""
+    cap = K_cache.shape[2] if K_cache.dim() == 4 else 0
+    _append("flash_attention_kv_append_varlen", "kv_cache_append_varlen", "K_cache, V_cache", "[B, Hkv, capacity, d]",
+            _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), K_cache, V_cache, cap, (), (cap,), kv_lens, k_descale, v_descale, stream,
+            cu_seqlens_q=cu_seqlens_q)
+
+
+def kv_cache_append_paged_varlen(K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, k_descale=None, v_descale=None,
+                                 stream=None):
+    """``kv_cache_append_varlen`` into PAGED caches: the pools and the ``block_table`` ``[B, max_pages]`` of ``kv_cache_append_paged``,
+    with that call's rules -- only the entries of pages that receive a row are read, an entry outside [0, P) is skipped and never
+    clamped.  Returns None."""
+    _append("flash_attention_kv_append_paged_varlen", "kv_cache_append_paged_varlen", "K_pool, V_pool", "[P, Hkv, page, d]",
+            _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), K_pool, V_pool, 0, (block_table,), None, kv_lens, k_descale, v_descale,
+            stream, table=block_table, cu_seqlens_q=cu_seqlens_q)
 
 
 def _library_accepts(t):

@@ -310,6 +310,10 @@ constexpr int DECODE_WGS_PER_CU = 2, DECODE_MIN_TILES = 2;
 // from half a round to one.  EXTEND_MIN_TILES is decode's value, not re-measured: no benchmark shape has a cache short enough for
 // it to bind.  A long chunk's units fill the chip by themselves and ns = 1.
 constexpr int EXTEND_MIN_TILES = 2;
+// flash_attention_extend_varlen (the same kernel, the row count a per-sequence device value): extend's rule and constants with
+// units = Hkv * NB, NB the host's BOUND on the batch's row blocks (decode_route) -- the host cannot see the real count, nor how unequal
+// the units are (a decode row's unit walks a whole cache, a chunk's lower blocks a part of it).  NOT measured for mixed batches: the
+// forced sweep of tools/bench_decode.py --varlen (profiles/extend_varlen_bench.log) shows what the rule costs.
 
 // What a call family is to the launch decision: built once per entry point (decode_form, extend_form), read by decode_check_shape,
 // decode_route and decode_run
@@ -320,15 +324,25 @@ struct SplitForm {
     int min_tiles;         // no split shorter than this many key tiles of the capacity
     bool q_to_capacity;    // seqLenQ is capped at the capacity, not at FA_DECODE_MAX_Q
     const SplitKernelOf (*split_kernel_of)[2];   // [paged][kv8]: the selectors of the family's four cache forms
+    bool varlen;           // ragged: "Sq" is totalQ, the bound on the token-packed rows of the whole batch (not capped at the capacity),
+                           // row_blocks the bound NB over the batch, batchSize <= FA_VARLEN_MAX_BATCH and cuSeqlensQ is required
 };
 static constexpr SplitKernelOf DECODE_KERNELS[2][2] = {{decode_split_kernel_of, decode_fp8_split_kernel_of},
                                                        {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}};
 static constexpr SplitKernelOf EXTEND_KERNELS[2][2] = {{extend_split_kernel_of, extend_fp8_split_kernel_of},
                                                        {extend_paged_split_kernel_of, extend_paged_fp8_split_kernel_of}};
-static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, DECODE_KERNELS}; }
+static constexpr SplitKernelOf VARLEN_KERNELS[2][2] = {{extend_varlen_split_kernel_of, extend_varlen_fp8_split_kernel_of},
+                                                       {extend_varlen_paged_split_kernel_of, extend_varlen_paged_fp8_split_kernel_of}};
+static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, DECODE_KERNELS, false}; }
 static SplitForm extend_form(int d) {   // (any d but 128 takes the d = 64 values: decode_check_shape refuses it before they matter)
-    return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS}
-                    : SplitForm{ExtendCfg<64>::ROWS, ExtendCfg<64>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS};
+    return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS, false}
+                    : SplitForm{ExtendCfg<64>::ROWS, ExtendCfg<64>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS, false};
+}
+static SplitForm extend_varlen_form(int d) {
+    SplitForm f = extend_form(d);
+    f.split_kernel_of = VARLEN_KERNELS;
+    f.varlen = true;
+    return f;
 }
 
 struct DecodeRoute {
@@ -338,12 +352,16 @@ struct DecodeRoute {
 
 static DecodeRoute decode_route(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window) {
     DecodeRoute r{};
-    const int rows = (H / Hkv) * Sq;                     // packed rows per K/V head
-    r.row_blocks = (int)(((int64_t)rows + f.rows_per_block - 1) / f.rows_per_block);
+    const int64_t rows = (int64_t)(H / Hkv) * Sq;        // packed rows per K/V head (ragged: of the whole batch, at most)
+    // ragged: NB = floor((G totalQ + B (rows_per_block - 1)) / rows_per_block) >= sum_b ceil(G sq_b / rows_per_block) for every
+    // partition of at most totalQ rows over the B sequences (each term is at most (G sq_b + rows_per_block - 1) / rows_per_block,
+    // and a sum of integers below a bound is below its floor)
+    r.row_blocks = (int)std::min<int64_t>(f.varlen ? (rows + (int64_t)B * (f.rows_per_block - 1)) / f.rows_per_block
+                                                   : (rows + f.rows_per_block - 1) / f.rows_per_block, INT32_MAX);
     constexpr int TILE = DecodeCfg<128>::TILE;
     r.tiles = (Sk + TILE - 1) / TILE;
     if (window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)window + Sq - 1 + TILE - 1) / TILE + 1);
-    const int64_t units = (int64_t)B * Hkv * r.row_blocks;
+    const int64_t units = (int64_t)(f.varlen ? 1 : B) * Hkv * r.row_blocks;
     if (numSplits > 0) r.ns = numSplits;
     else {
         const int64_t want = ((int64_t)f.wgs_per_cu * device_cus() + units - 1) / units;
@@ -356,14 +374,16 @@ static DecodeRoute decode_route(const SplitForm& f, int B, int H, int Hkv, int S
 static int decode_check_shape(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits,
                               int window) {
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if (Sq > (f.q_to_capacity ? Sk : FA_DECODE_MAX_Q) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
-    if (f.q_to_capacity && (int64_t)B * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if ((!f.varlen && Sq > (f.q_to_capacity ? Sk : FA_DECODE_MAX_Q)) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (f.q_to_capacity && (int64_t)(f.varlen ? 1 : B) * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (f.varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
     if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
     if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS || window < 0) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    if (decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window).grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    const DecodeRoute r = decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window);
+    if (r.grid > INT32_MAX || r.row_blocks == INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 
@@ -373,26 +393,39 @@ static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 // [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
 // Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.  kv_dtype is the element type of
 // K / V: FA_DTYPE_BF16 (the type of Q), or FA_DTYPE_FP8_E4M3 with the two optional per-head descale arrays (the _fp8 entry points).
-// window: 0, or the sliding window W of the _window entry points.
+// window: 0, or the sliding window W of the _window entry points.  Ragged (f.varlen; flash_attention_extend*_varlen): Sq is totalQ, Q / O
+// are packed by token (strideB is not read; NULL strides: [totalQ, H, d]), the LSE and the slabs are [H, totalQ], and cuSeqlensQ --
+// NULL in every other call -- is required.
 struct DecodePaging {
     const int32_t* table;
     int64_t table_stride;
     int num_pages, page_size, max_pages;
 };
 
-static int decode_run(const SplitForm& f, const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
-                      const float* kDescale, const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale,
+// the strides of a token-packed [totalQ, heads, d] tensor: the caller's with strideB out of the way, or (s = NULL) the dense ones
+static fa_strides token_strides(const fa_strides* s, int64_t heads, int64_t d) {
+    return s ? fa_strides{0, s->strideH, s->strideS} : fa_strides{0, d, heads * d};
+}
+
+static int decode_run(const SplitForm& f, const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                      const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale,
                       bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ,
                       const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
-    if (!Q || !K || !V || !O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!Q || !K || !V || !O || (pg && !pg->table) || (f.varlen && !cuSeqlensQ)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
     if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
+    if (reinterpret_cast<uintptr_t>(cuSeqlensQ) & 3u) return FA_ERR_MISALIGNED;
     if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
     if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
     if (pg) {
         if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
         Sk = pg->max_pages * pg->page_size;
+    }
+    fa_strides tQ{}, tO{};   // ragged: Q and O on their token strides
+    if (f.varlen) {
+        tQ = token_strides(sQ, H, d); sQ = &tQ;
+        tO = token_strides(sO, H, d); sO = &tO;
     }
     int rc = decode_check_shape(f, B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window);
     if (rc != FA_OK) return rc;
@@ -406,11 +439,11 @@ static int decode_run(const SplitForm& f, const void* Q, const void* K, const vo
     if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
     const DecodeRoute r = decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window);
     if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
-    const int64_t rows = (int64_t)B * H * Sq;
+    const int64_t rows = (int64_t)(f.varlen ? 1 : B) * H * Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
     const int rowsK = pg ? pg->page_size : Sk;   // rows of one head of one batch entry / page
-    DecodeParams p;
+    VarlenDecodeParams p;   // (what every other form launches with is its DecodeParams part)
     p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
     p.part_o = (float*)workspace;
     p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
@@ -431,24 +464,34 @@ static int decode_run(const SplitForm& f, const void* Q, const void* K, const vo
     p.k_descale = kDescale;
     p.v_descale = vDescale;
     p.window = window;
+    p.cu_q = cuSeqlensQ;
+    p.B = B;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
     const Kernel sk = f.split_kernel_of[pg != nullptr][kv8](d);
-    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
+    if (f.varlen) {
+        const hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
+        if (e != hipSuccess || r.ns == 1) return (int)e;
+        return (int)launch(extend_varlen_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
+    }
+    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, (DecodeParams)p);
     if (e != hipSuccess || r.ns == 1) return (int)e;
-    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
+    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, (DecodeParams)p);
 }
 
 // ---- K/V cache append (kv_append.hip.h) ----
 // flash_attention_kv_append and flash_attention_kv_append_paged: one validation and launch.  The caches are decode_run's: the same
 // layouts, element sizes, stride rules, paging checks and extent limits, so a cache this call accepts is one the decode call of the
 // same kv_dtype accepts.  Sq is not capped at FA_DECODE_MAX_Q (the call also fills a cache after a prefill), only at the capacity.
-static int kv_append_run(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,
+// Ragged (varlen; flash_attention_kv_append*_varlen): Sq is totalQ, not capped at the capacity; Knew / Vnew are packed by token
+// (strideB is not read; NULL strides: [totalQ, Hkv, d]); cuSeqlensQ -- NULL in the uniform calls -- is required; the token-major kernel.
+static int kv_append_run(bool varlen, const void* Knew, const void* Vnew, void* K, void* V, const int32_t* cuSeqlensQ, const int32_t* kvLens, const float* kDescale,
                          const float* vDescale, int B, int Hkv, int Sq, int Sk, int d, int dtype, int kv_dtype, const fa_strides* sKnew,
                          const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV, const DecodePaging* pg, void* stream) {
-    if (!Knew || !Vnew || !K || !V || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!Knew || !Vnew || !K || !V || (pg && !pg->table) || (varlen && !cuSeqlensQ)) return FA_ERR_NULL_POINTER;
     if (!aligned16(Knew) || !aligned16(Vnew) || !aligned16(K) || !aligned16(V)) return FA_ERR_MISALIGNED;
     if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
+    if (reinterpret_cast<uintptr_t>(cuSeqlensQ) & 3u) return FA_ERR_MISALIGNED;
     if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
     if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
     if (pg) {
@@ -457,17 +500,25 @@ static int kv_append_run(const void* Knew, const void* Vnew, void* K, void* V, c
         Sk = pg->max_pages * pg->page_size;
     }
     if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if (Sk > (1 << 24) || Sq > Sk || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || (!varlen && Sq > Sk) || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
     if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (kv_dtype == FA_DTYPE_BF16 && (kDescale || vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
     const int esz = elem_size(kv_dtype);
+    fa_strides tK{}, tV{};   // ragged: the new rows on their token strides
+    if (varlen) {
+        tK = token_strides(sKnew, Hkv, d); sKnew = &tK;
+        tV = token_strides(sVnew, Hkv, d); sVnew = &tV;
+    }
     if (!strides_ok(sKnew, 2, d) || !strides_ok(sVnew, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d)) return FA_ERR_BAD_STRIDE;
     const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;   // decode_run's limit: what is written can be read
     if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
     const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
-    const int64_t grid = (int64_t)B * Hkv * row_blocks * 2;
+    const int tokens_per_block = KvAppendCfg::THREADS / (d / 8);                     // ragged: a row per d / 8 lanes
+    const int token_blocks = (int)(((int64_t)Sq + tokens_per_block - 1) / tokens_per_block);
+    const int64_t grid = varlen ? (int64_t)Hkv * token_blocks * 2 : (int64_t)B * Hkv * row_blocks * 2;
     if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
     const int rowsK = pg ? pg->page_size : Sk;
@@ -484,6 +535,11 @@ static int kv_append_run(const void* Knew, const void* Vnew, void* K, void* V, c
     p.Hkv = Hkv; p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks;
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    if (varlen) {
+        const KvAppendVarlenParams pv{p, cuSeqlensQ, B, token_blocks};
+        const Kernel kr = kv_append_varlen_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
+        return (int)launch(kr, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(stream), pv);
+    }
     const Kernel k = kv_append_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
     return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(stream), p);
 }
@@ -704,6 +760,20 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
 }
 
+// what the three plan functions report of a route
+static void fill_split_plan(fa_decode_plan* plan, const fa::SplitForm& f, const fa::DecodeRoute& r, int dHead, int64_t rows) {
+    using namespace fa;
+    plan->num_splits = r.ns;
+    plan->row_blocks = r.row_blocks;
+    plan->rows_per_block = f.rows_per_block;
+    plan->kv_block_rows = DecodeCfg<128>::TILE;
+    plan->threads = DecodeCfg<128>::THREADS;
+    plan->grid = (int)r.grid;
+    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
+    plan->combine_grid = r.ns > 1 ? (int)rows : 0;   // one workgroup per (batch, head, query row); ragged: per (head, token)
+    plan->combine_threads = r.ns > 1 ? 256 : 0;
+}
+
 int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
                                        int numSplits, int windowSize, fa_decode_plan* plan) {
     using namespace fa;
@@ -712,17 +782,8 @@ int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeads
     const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
                                       windowSize);
     if (rc != FA_OK) return rc;
-    const DecodeRoute r = decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize);
-    plan->num_splits = r.ns;
-    plan->row_blocks = r.row_blocks;
-    plan->rows_per_block = f.rows_per_block;
-    plan->kv_block_rows = DecodeCfg<128>::TILE;
-    plan->threads = DecodeCfg<128>::THREADS;
-    plan->grid = (int)r.grid;
-    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
-    const int64_t rows = (int64_t)batchSize * numHeads * seqLenQ;
-    plan->combine_grid = r.ns > 1 ? (int)rows : 0;   // one workgroup per (batch, head, query row)
-    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize), dHead,
+                    (int64_t)batchSize * numHeads * seqLenQ);
     return FA_OK;
 }
 
@@ -741,7 +802,7 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ,
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ,
                           seqLenK, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
 }
 
@@ -751,7 +812,7 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV,
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV,
                           seqLenQ, 0, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
 }
 
@@ -761,7 +822,7 @@ int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void
                                int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                                const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
                           seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
                           stream);
 }
@@ -774,7 +835,7 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
                                      const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
                           numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
                           stream);
 }
@@ -790,7 +851,7 @@ int flash_attention_decode_window(const void* Q, const void* K, const void* V, v
                                   int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
                                   const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
                           seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
                           nullptr, stream);
 }
@@ -803,7 +864,7 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                                         const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
                           numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
                           &pg, stream);
 }
@@ -815,16 +876,8 @@ int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int
     const SplitForm f = extend_form(dHead);
     const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0);
     if (rc != FA_OK) return rc;
-    const DecodeRoute r = decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0);
-    plan->num_splits = r.ns;
-    plan->row_blocks = r.row_blocks;
-    plan->rows_per_block = f.rows_per_block;
-    plan->kv_block_rows = DecodeCfg<128>::TILE;
-    plan->threads = DecodeCfg<128>::THREADS;
-    plan->grid = (int)r.grid;
-    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
-    plan->combine_grid = r.ns > 1 ? batchSize * numHeads * seqLenQ : 0;   // one workgroup per (batch, head, query row)
-    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0), dHead,
+                    (int64_t)batchSize * numHeads * seqLenQ);
     return FA_OK;
 }
 
@@ -834,7 +887,7 @@ int flash_attention_extend(const void* Q, const void* K, const void* V, void* O,
                            int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                            const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
                           seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
                           stream);
 }
@@ -847,7 +900,7 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
                           numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
                           stream);
 }
@@ -856,7 +909,7 @@ int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void*
                               const float* vDescale, int batchSize, int numHeadsKV, int seqLenNew, int seqLenK, int dHead, int dtype,
                               int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
                               void* stream) {
-    return fa::kv_append_run(Knew, Vnew, K, V, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, seqLenK, dHead, dtype,
+    return fa::kv_append_run(false, Knew, Vnew, K, V, nullptr, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, seqLenK, dHead, dtype,
                              kv_dtype, sKnew, sVnew, sK, sV, nullptr, stream);
 }
 
@@ -866,8 +919,64 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
                                     int dHead, int dtype, int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew,
                                     const fa_strides* sK, const fa_strides* sV, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::kv_append_run(Knew, Vnew, Kpool, Vpool, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, 0, dHead, dtype,
+    return fa::kv_append_run(false, Knew, Vnew, Kpool, Vpool, nullptr, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, 0, dHead, dtype,
                              kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
+}
+
+int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, int o_dtype,
+                                       int numSplits, fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const SplitForm f = extend_varlen_form(dHead);
+    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0);
+    if (rc != FA_OK) return rc;
+    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, numSplits, 0), dHead,
+                    (int64_t)numHeads * totalQ);
+    return FA_OK;
+}
+
+int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int batchSize,
+                                  int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                  int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
+                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(fa::extend_varlen_form(dHead), Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace, batchSize,
+                          numHeads, numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK,
+                          sV, sO, nullptr, stream);
+}
+
+int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                                        int numHeadsKV, int totalQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                        int dHead, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(fa::extend_varlen_form(dHead), Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace,
+                          batchSize, numHeads, numHeadsKV, totalQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ,
+                          sK, sV, sO, &pg, stream);
+}
+
+int flash_attention_kv_append_varlen(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* cuSeqlensQ,
+                                     const int32_t* kvLens, const float* kDescale, const float* vDescale, int batchSize, int numHeadsKV,
+                                     int totalQ, int seqLenK, int dHead, int dtype, int kv_dtype, const fa_strides* sKnew,
+                                     const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV, void* stream) {
+    return fa::kv_append_run(true, Knew, Vnew, K, V, cuSeqlensQ, kvLens, kDescale, vDescale, batchSize, numHeadsKV, totalQ, seqLenK, dHead,
+                             dtype, kv_dtype, sKnew, sVnew, sK, sV, nullptr, stream);
+}
+
+int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int32_t* cuSeqlensQ,
+                                           const int32_t* kvLens, const int32_t* blockTable, const float* kDescale,
+                                           const float* vDescale, int batchSize, int numHeadsKV, int totalQ, int numPages, int pageSize,
+                                           int maxPagesPerSeq, int64_t tableStride, int dHead, int dtype, int kv_dtype,
+                                           const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                                           void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::kv_append_run(true, Knew, Vnew, Kpool, Vpool, cuSeqlensQ, kvLens, kDescale, vDescale, batchSize, numHeadsKV, totalQ, 0,
+                             dHead, dtype, kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
 }
 
 const char* flash_attention_error_string(int code) {

@@ -58,6 +58,16 @@
 //     its rows can see: ntb = ceil(max over its rows of lim / 128), divided over the splits in whole tiles; under the causal mask
 //     the lower blocks of a long chunk read less.  The end-of-loop merge of the four waves runs once per rt through the same 16-row
 //     buffer (the wave's V image), with a second barrier between two tiles: LDS stays at the RT = 1 size.
+//   * VARLEN (flash_attention_extend_varlen, flash_attention_extend_paged_varlen): the row count is a
+//     per-sequence DEVICE value, sq_b = cu_q[b + 1] - cu_q[b] (both clamped into [0, totalQ]), and Q, O, the LSE and the slabs are
+//     packed by token: row i of sequence b is packed row cu_q[b] + i.  Everything above derives its mask limits, tile counts and split
+//     ranges from (len, Sq) of the ONE sequence a workgroup works on, so only two things change.  The unit decoding: the grid holds
+//     Hkv * NB * ns workgroups, NB a host-side bound on sum_b ceil(G sq_b / RPB); every wave finds the sequence and the row block of
+//     its block index by a wave-wide scan of the per-sequence block counts, 64 sequences per step (unit_of), and a workgroup whose
+//     index lies beyond the real total returns before any barrier.  No extra launch, no workspace.  And the addressing: Sq becomes
+//     the scalar sq_b, a Q / O row is token cu_q[b] + i on the token strides, a slab / LSE row is h * totalQ + cu_q[b] + i.  The
+//     per-row text is untouched: sequence b's bits are those of the RT > 1 kernel on that sequence alone.  With VARLEN = false every
+//     term of this bullet folds away.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -90,6 +100,23 @@ struct DecodeParams {
     const float* k_descale;       // optional [Hkv] (device memory); NULL = 1
     const float* v_descale;       // optional [Hkv] (device memory); NULL = 1
     int window;                   // 0: none; W > 0: row i sees at most the last W keys up to and including its own position
+};
+
+// The ragged (VARLEN) kernels' argument: Q / O / LSE are packed by token, Sq holds totalQ (the bound on the packed rows),
+// rows = H * totalQ, row_blocks the bound NB on the row blocks of one K/V head over the whole batch, qB / oB are not read.  A type of
+// its own: DecodeParams is 256 bytes, and one field more changes how the compiler fetches the arguments of -- and allocates the
+// registers of -- the paged instantiations that never read it
+struct VarlenDecodeParams : DecodeParams {
+    const int32_t* cu_q;          // [B + 1] (device memory): sequence b owns the packed rows [cu_q[b], cu_q[b + 1]), clamped into [0, Sq]
+    int B;
+};
+template <bool VARLEN>
+struct SplitParamsOf {
+    using type = DecodeParams;
+};
+template <>
+struct SplitParamsOf<true> {
+    using type = VarlenDecodeParams;
 };
 
 template <int D, int ES = 2>   // ES: bytes per K/V element in memory (2: bf16, 1: e4m3fn); the LDS image of V is bf16 either way
@@ -133,9 +160,50 @@ __device__ __forceinline__ void store_out(void* O, int o_dtype, int64_t idx, flo
     else ((_Float16*)O)[idx] = (_Float16)v;
 }
 
-// Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false.
-template <int D, int RT, bool PAGED, bool KV8, bool WINDOW>
-__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const DecodeParams p) {
+// VARLEN: what a block index of one K/V head works on -- sequence b, its row block rb, its first packed row q0 and its row count sq
+struct VarlenUnit {
+    int b, rb, q0, sq;
+};
+
+// Block index j in [0, NB) -> the unit, or false beyond the real total sum_b ceil(G sq_b / RPB).  Every wave runs this by itself (no
+// LDS, no barrier) and arrives at the same scalars: per step, lane i takes sequence base + i -- its two clamped offsets, its block
+// count -- an inclusive scan over the wave gives the running totals, and the first lane whose total exceeds j names the sequence.
+// A sequence without rows has no blocks and is never named.  Offsets that are not non-decreasing still give b < B and rows inside
+// [0, totalQ): each sequence's pair is clamped by itself
+template <int RPB>
+__device__ __forceinline__ bool varlen_unit_of(const VarlenDecodeParams& p, int j, int lane, VarlenUnit& u) {
+    int done = 0;   // the row blocks of the sequences before this step
+    for (int base = 0; base < p.B; base += WAVE) {
+        const int s = min(base + lane, p.B - 1);
+        const int q0 = min(max(p.cu_q[s], 0), p.Sq), q1 = min(max(p.cu_q[s + 1], q0), p.Sq);
+        const int sq = base + lane < p.B ? q1 - q0 : 0;
+        const int cnt = (int)(((unsigned)(p.G * sq) + RPB - 1) / RPB);   // (G sq <= H totalQ < 2^31: the host's limit)
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int v = __shfl_up(incl, o);
+            if (lane >= o) incl += v;
+        }
+        const int total = __builtin_amdgcn_readlane(incl, WAVE - 1);
+        if (j < done + total) {
+            const unsigned long long hit = __ballot(done + incl > j);
+            if (hit == 0) return false;   // (only totals that overflowed: offsets far from non-decreasing)
+            const int l = __builtin_ctzll(hit);
+            u.b = base + l;
+            u.rb = j - done - __builtin_amdgcn_readlane(incl - cnt, l);
+            u.q0 = __builtin_amdgcn_readlane(q0, l);
+            u.sq = __builtin_amdgcn_readlane(sq, l);
+            return u.sq > 0 && u.rb >= 0;
+        }
+        done += total;
+    }
+    return false;
+}
+
+// Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false; ragged chunked prefill: that with VARLEN.
+template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false>
+__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN>::type p) {
+    static_assert(!VARLEN || !WINDOW, "the ragged form has no window");
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
@@ -148,22 +216,30 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const De
     // blockIdx -> (batch, K/V head, row block, split); the split index runs fastest
     int u = blockIdx.x;
     const int split = u % p.ns; u /= p.ns;
-    const int rb = u % p.row_blocks; u /= p.row_blocks;
-    const int kvh = u % p.Hkv;
-    const int b = u / p.Hkv;
+    // VARLEN: (K/V head, block index over the whole batch, split); the sequence and its row block are looked up, and a block index
+    // beyond the real total leaves here, the whole workgroup alike and before any barrier
+    VarlenUnit vu{};
+    if constexpr (VARLEN) {
+        if (!varlen_unit_of<RPB>(p, u % p.row_blocks, lane, vu)) return;
+    }
+    const int rb = VARLEN ? vu.rb : u % p.row_blocks; u /= p.row_blocks;
+    const int kvh = VARLEN ? u : u % p.Hkv;
+    const int b = VARLEN ? vu.b : u / p.Hkv;
 
     int len = p.Sk;
     if (p.kv_lens) len = min(max(p.kv_lens[b], 1), p.Sk);
     len = __builtin_amdgcn_readfirstlane(len);
+    const int Sq = VARLEN ? vu.sq : p.Sq;   // the rows of this sequence
+    const int q0 = VARLEN ? vu.q0 : 0;      // ... and the first of them among the packed rows of Q, O, the LSE and the slabs
     // the lowest key any row sees: row 0's lower bound (0 without a window).  Keys below it are never part of the result
-    const int first = WINDOW && p.window > 0 ? max(max(len - p.Sq + 1, 1) - p.window, 0) : 0;
+    const int first = WINDOW && p.window > 0 ? max(max(len - Sq + 1, 1) - p.window, 0) : 0;
     // the tiles this row block can see: below the largest limit of its rows.  Causal: the limit grows with the query row, and the
     // largest query row of the block is the last one -- unless the block reaches into the next head, then it holds a row Sq - 1.
     // RT = 1: the host caps Sq at FA_DECODE_MAX_Q = 16, so a 16-row block always holds a row with lim = len (its last row is the last
     // of all, or it holds the last query row of a head): limb = len without the arithmetic
-    const int nrows = p.G * p.Sq, pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
-    const int gl = prl / p.Sq, qmax = pr0 / p.Sq != gl ? p.Sq - 1 : prl - gl * p.Sq;
-    const int limb = RT > 1 && p.causal ? max(len - p.Sq + qmax + 1, 1) : len;
+    const int nrows = p.G * Sq, pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
+    const int gl = prl / Sq, qmax = pr0 / Sq != gl ? Sq - 1 : prl - gl * Sq;
+    const int limb = RT > 1 && p.causal ? max(len - Sq + qmax + 1, 1) : len;
     // this block's tiles [tlo, ntb), divided over the splits in whole tiles
     const int ntb = (limb + C::TILE - 1) / C::TILE, tlo = first / C::TILE;
     const int t0 = tlo + (int)(((int64_t)(ntb - tlo) * split) / p.ns), t1 = tlo + (int)(((int64_t)(ntb - tlo) * (split + 1)) / p.ns);
@@ -180,13 +256,13 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const De
     for (int rt = 0; rt < RT; ++rt) {
         const int pr = pr0 + rt * C::ROWS + r;
         const bool row_ok = pr < nrows;
-        const int g = row_ok ? pr / p.Sq : 0, qi = row_ok ? pr - g * p.Sq : 0;
+        const int g = row_ok ? pr / Sq : 0, qi = row_ok ? pr - g * Sq : 0;
         const int h = kvh * p.G + g;
-        const int limc = max(len - p.Sq + qi + 1, 1);
+        const int limc = max(len - Sq + qi + 1, 1);
         const int lim = p.causal ? limc : len;
         lo[rt] = WINDOW && p.window > 0 ? max(limc - p.window, 0) : 0;
         span[rt] = (unsigned)(lim - lo[rt]);
-        const __bf16* q = p.Q + b * p.qB + h * p.qH + qi * p.qS + (KV8 ? 16 : 8) * h4;
+        const __bf16* q = p.Q + (VARLEN ? 0 : b * p.qB) + h * p.qH + (q0 + qi) * p.qS + (KV8 ? 16 : 8) * h4;
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
             const u32x4 z = {0u, 0u, 0u, 0u};
@@ -432,13 +508,13 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const De
         }
         const int opr = pr0 + rt * C::ROWS + orow;
         if (opr < nrows) {   // (no early exit: the barriers of the tiles to come are the whole workgroup's)
-            const int og = opr / p.Sq, oi = opr - og * p.Sq, oh = kvh * p.G + og;
+            const int og = opr / Sq, oi = opr - og * Sq, oh = kvh * p.G + og;
             float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
             if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
             const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
-            const int64_t row = ((int64_t)b * p.H + oh) * p.Sq + oi;
+            const int64_t row = VARLEN ? (int64_t)oh * p.Sq + q0 + oi : ((int64_t)b * p.H + oh) * Sq + oi;
             if (p.ns == 1) {
-                const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + d0;
+                const int64_t base = (VARLEN ? 0 : b * p.oB) + oh * p.oH + (q0 + oi) * p.oS + d0;
 #pragma unroll
                 for (int j = 0; j < DPT; ++j) store_out(p.O, p.o_dtype, base + j, acc[j] * inv);
                 if (p.lse && (tid & 15) == 0) p.lse[row] = lse;
@@ -459,13 +535,19 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const De
 // partial LSEs, one split per lane, and reduces max and sum across its lanes; thread t then sums four consecutive d over the splits
 // t / (D/4), + 256 / (D/4), ..., and the 256 / (D/4) partial sums are added through LDS in slot order.  At least one split of a row is
 // not empty (every sequence has a key), so m is finite and an empty split's weight is exp(-inf) = 0.
-template <int D>
-__global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams p) {
+// VARLEN (the ragged form: B = 1 to this kernel, Sq = totalQ, oB not read): a row is (head, token), and the tokens no sequence owns --
+// below cu_q[0], at and beyond cu_q[B] -- have no partial results and are not written: their workgroups leave before the first barrier.
+template <int D, bool VARLEN = false>
+__global__ __launch_bounds__(256) void decode_combine_kernel(const typename SplitParamsOf<VARLEN>::type p) {
     static_assert(FA_DECODE_MAX_SPLITS <= WAVE, "one split per lane");
     constexpr int TPR = D / 4, SLOTS = 256 / TPR;
     __shared__ float wgt[WAVE];
     __shared__ f32x4 part[SLOTS][TPR];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    if constexpr (VARLEN) {
+        const int t = row % p.Sq;
+        if (t < min(max(p.cu_q[0], 0), p.Sq) || t >= min(max(p.cu_q[p.B], 0), p.Sq)) return;
+    }
     const float mine = lane < p.ns ? p.part_lse[(int64_t)lane * p.rows + row] : -__builtin_inff();
     float M = mine;
 #pragma unroll
@@ -488,13 +570,13 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams 
     for (int j = 1; j < SLOTS; ++j) sum += part[j][c];
     const float inv = 1.0f / W;
     const int oi = row % p.Sq, bh = row / p.Sq, oh = bh % p.H, b = bh / p.H;
-    const int64_t base = b * p.oB + oh * p.oH + oi * p.oS + 4 * c;
+    const int64_t base = (VARLEN ? 0 : b * p.oB) + oh * p.oH + oi * p.oS + 4 * c;
 #pragma unroll
     for (int j = 0; j < 4; ++j) store_out(p.O, p.o_dtype, base + j, sum[j] * inv);
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (the inst_decode_*.hip and inst_extend_*.hip units: one per cache form and call family) ----
+// ---- selectors (the inst_decode_*.hip, inst_extend_*.hip and inst_extend_varlen_*.hip units: one per cache form and call family) ----
 struct Kernel;
 Kernel decode_split_kernel_of(int d);
 Kernel decode_paged_split_kernel_of(int d);
@@ -504,6 +586,11 @@ Kernel extend_split_kernel_of(int d);
 Kernel extend_paged_split_kernel_of(int d);
 Kernel extend_fp8_split_kernel_of(int d);
 Kernel extend_paged_fp8_split_kernel_of(int d);
+Kernel extend_varlen_split_kernel_of(int d);
+Kernel extend_varlen_paged_split_kernel_of(int d);
+Kernel extend_varlen_fp8_split_kernel_of(int d);
+Kernel extend_varlen_paged_fp8_split_kernel_of(int d);
+Kernel extend_varlen_combine_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 
 }  // namespace fa

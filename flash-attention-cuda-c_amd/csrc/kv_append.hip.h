@@ -18,6 +18,7 @@
 //   * Every address is 64-bit arithmetic on the element strides.  No LDS, no scratch, no atomics; every store is a vector store.
 //   * NaN.  The clamp would lose a NaN (max / min return the other operand), and what the conversion instruction does with one by
 //     itself is not relied on: 0x7F is OR-ed into the byte of every element whose quotient is NaN (0x7F or 0xFF: a NaN code).
+// The ragged form (new rows packed by token, a per-sequence row count) is a second, token-major kernel below.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -135,7 +136,87 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendParams p) 
     }
 }
 
+// The RAGGED append (flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen): the new rows are
+// packed by token, [totalQ, Hkv, d], and sequence b owns the tokens [cu_q[b], cu_q[b + 1]) (each pair clamped into [0, totalQ] as the
+// ragged attention clamps it).  TOKEN-major: a group of D / 8 lanes owns one token row of one K/V head of K or V; it finds its
+// sequence by a binary search in cu_q (the LAST b with cu_q[b] <= t: sequences without rows share their offset with the one behind
+// them and are passed over), then does what the uniform kernel does for one row -- L = min(kv_lens[b], cap), position
+// L - sq_b + (t - cu_q[b]), written if >= 0; its own table entry, skipped outside [0, num_pages); the same load, kv_quantise4 and
+// store, so the bytes are the uniform kernel's for that sequence alone.  A token no sequence owns writes nothing.  The waves are not
+// aligned in position space (a wave's rows may lie in several sequences and pages: the length, the entry and the position are
+// per-lane values), which costs the uniform kernel's scalar loads but needs no unit lookup and no second launch.
+struct KvAppendVarlenParams {
+    KvAppendParams a;             // Sq: totalQ; knB / vnB, row_blocks: not read
+    const int32_t* cu_q;          // [B + 1] (device memory)
+    int B;
+    int token_blocks;             // ceil(totalQ / (256 / (D / 8)))
+};
+
+template <int D, bool KV8, bool PAGED>
+__global__ __launch_bounds__(256) void kv_append_varlen_kernel(const KvAppendVarlenParams pv) {
+    const KvAppendParams& p = pv.a;
+    constexpr int LPR = D / 8;           // lanes per row
+    constexpr int TPB = 256 / LPR;       // tokens per workgroup
+    constexpr int ES = KV8 ? 1 : 2;      // bytes per cache element
+
+    // blockIdx -> (K/V head, token block, K or V); K / V runs fastest
+    int u = blockIdx.x;
+    const int isV = u & 1; u >>= 1;
+    const int tb = u % pv.token_blocks;
+    const int kvh = u / pv.token_blocks;
+    const int t = tb * TPB + (int)threadIdx.x / LPR, col = ((int)threadIdx.x % LPR) * 8;
+    if (t >= p.Sq) return;
+
+    // the last sequence whose first token is at or below t
+    int lo = 0, hi = pv.B;               // cu_q[lo] <= t (or lo = 0) and cu_q[hi] > t (or hi = B)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pv.cu_q[mid] <= t) lo = mid; else hi = mid;
+    }
+    const int b = lo;
+    const int q0 = min(max(pv.cu_q[b], 0), p.Sq), q1 = min(max(pv.cu_q[b + 1], q0), p.Sq);
+    if (t < q0 || t >= q1) return;       // a token no sequence owns
+
+    int len = p.cap;
+    if (p.kv_lens) len = min(p.kv_lens[b], p.cap);
+    if (len <= 0) return;                                  // an inactive slot: nothing is written
+    const int pos = len - (q1 - q0) + (t - q0);            // < len <= cap
+    if (pos < 0) return;                                   // more new rows than the length: the leading ones are dropped
+
+    const __bf16* src = isV ? p.Vnew : p.Knew;
+    const int64_t nH = isV ? p.vnH : p.knH, nS = isV ? p.vnS : p.knS;
+    const int64_t cB = isV ? p.vB : p.kB, cH = isV ? p.vH : p.kH, cS = isV ? p.vS : p.kS;
+    char* dst = (char*)(isV ? p.V : p.K);
+
+    int row = pos;
+    if constexpr (PAGED) {
+        const int entry = p.block_table[b * p.table_stride + (pos >> p.page_shift)];
+        if (entry < 0 || entry >= p.num_pages) return;     // not clamped: a clamped write would land in another sequence's page
+        dst += (int64_t)entry * cB * ES;
+        row = pos & ((1 << p.page_shift) - 1);
+    } else {
+        dst += (int64_t)b * cB * ES;
+    }
+    dst += ((int64_t)kvh * cH + (int64_t)row * cS + col) * ES;
+
+    float ds = 1.f;
+    if constexpr (KV8) {
+        const float* dp = isV ? p.v_descale : p.k_descale;
+        if (dp) ds = dp[kvh];
+    }
+    const u32x4 x = *reinterpret_cast<const u32x4*>(src + (int64_t)t * nS + (int64_t)kvh * nH + col);
+    if constexpr (KV8) {
+        u32x2 y;
+        y[0] = kv_quantise4(x[0], x[1], ds);
+        y[1] = kv_quantise4(x[2], x[3], ds);
+        *reinterpret_cast<u32x2*>(dst) = y;
+    } else {
+        *reinterpret_cast<u32x4*>(dst) = x;
+    }
+}
+
 // the instantiation for (d, fp8 cache, paged): inst_kv_append.hip
 Kernel kv_append_kernel_of(int d, bool kv8, bool paged);
+Kernel kv_append_varlen_kernel_of(int d, bool kv8, bool paged);
 
 }  // namespace fa

@@ -665,8 +665,8 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
  *            caveat on V; e4m3fn -> bf16 exactly, in registers, kDescale folded into the score scale and vDescale into the final 1 / l
  * Rejected before any launch: everything the decode sibling of the same form and kv_dtype rejects, with the same codes, except the
  * FA_DECODE_MAX_Q cap; seqLenQ > capacity FA_ERR_BAD_SHAPE; a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE.
- * Not done here: sliding windows, a per-sequence count of new rows (every sequence brings seqLenQ rows), attention sinks, fp8 Q, a
- * backward, automatic routing from or to any existing call.
+ * Not done here: sliding windows, attention sinks, fp8 Q, a backward, automatic routing from or to any existing call.  A per-sequence
+ * count of new rows is flash_attention_extend_varlen's (below): here every sequence brings seqLenQ rows.
  */
 int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
                                 int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
@@ -686,6 +686,108 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
                                  float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                  void* stream);
+
+/*
+ * flash_attention_extend_varlen, flash_attention_extend_paged_varlen -- RAGGED chunked prefill against the decode caches: every
+ * sequence of the batch brings its OWN number of new query rows, 0 .. totalQ, given in device memory.  One step of a continuous-batching
+ * engine -- some sequences decoding (1 row, or a short draft), some in the middle of a chunked prefill, some idle -- is one call on the
+ * token-major tensors the engine holds, with no regrouping and no padding.  The argument lists are flash_attention_extend's /
+ * flash_attention_extend_paged's with seqLenQ replaced by totalQ and cuSeqlensQ added directly before kvLens; both calls serve bf16 and
+ * e4m3fn caches through kv_dtype.
+ *
+ * Contract.  Everything not named below is flash_attention_extend*'s of the same form and kv_dtype: cache layouts, strides and extent
+ * rules; kvLens, the descales and the table entries read by the kernel and clamped as there; keys at and beyond the length may hold
+ * anything; pools may exceed 2^32 bytes; o_dtype F32, BF16 or F16, rounded once; the optional LSE (the same bits of O with or without
+ * it); no atomics, the same bits run to run; validation before any launch; no allocation, no host synchronisation, nothing printed,
+ * graph-capturable.
+ *   Q, O     PACKED BY TOKEN: row t of totalQ rows, head h, is at t * strideS + h * strideH elements (strideB is ignored, whatever it
+ *            holds).  NULL strides = the token-major [totalQ, numHeads, dHead] an engine holds: strideS = numHeads * dHead, strideH = dHead
+ *   LSE      optional dense fp32 [numHeads, totalQ]
+ *   totalQ   a HOST-side BOUND on the packed rows (the allocation; fixed under a captured graph), >= 1 and NOT capped at the capacity.
+ *            The rows in use are given by cuSeqlensQ
+ *   cuSeqlensQ  DEVICE pointer to int32[batchSize + 1], 4-byte aligned, required; read by the kernels, never by the host.  With
+ *            q0 = clamp(cuSeqlensQ[b], 0, totalQ) and q1 = clamp(cuSeqlensQ[b + 1], q0, totalQ), sequence b owns the rows [q0, q1):
+ *            sq_b = q1 - q0 new rows.  sq_b = 0 is legal (an idle slot): nothing of that sequence is computed, and its kvLens entry and
+ *            table row are not read.  Rows owned by no sequence -- in particular [cuSeqlensQ[batchSize], totalQ) -- are NOT written:
+ *            not O, not the LSE.  Entries that are not non-decreasing give an unspecified result, but every access stays inside the
+ *            totalQ rows
+ *   mask, tiles, arithmetic  flash_attention_extend's PER SEQUENCE, with sq_b where it has seqLenQ.  kvLens[b] ALREADY counts the new
+ *            rows (`kv_lens += q_lens; append; attend` is one graph); with len = clamp(kvLens[b], 1, capacity) row i of sequence b sees
+ *            k < max(len - sq_b + i + 1, 1) with is_causal and k < len without; sq_b > len keeps key 0.  The packed rows of a K/V head
+ *            are g * sq_b + i, in ceil(G * sq_b / rows_per_block) row blocks; a row block walks only the ntb tiles one of its rows can
+ *            see, divided over numSplits by decode's formula
+ *   seam     the O and LSE of sequence b are, BIT FOR BIT, what flash_attention_extend* returns for that sequence alone: batchSize = 1,
+ *            seqLenQ = sq_b, the same cache form and the same FORCED numSplits -- and for sq_b <= FA_DECODE_MAX_Q therefore
+ *            flash_attention_decode*'s as well.  (The per-row text of the kernel is the same; only the unit decoding and the addresses
+ *            differ.)  flash_attention_extend_paged_varlen equals flash_attention_extend_varlen on a contiguous copy of the same pages
+ *   workspace  flash_attention_decode_workspace_size(1, numHeads, totalQ, dHead, plan.num_splits) bytes -- that function, unchanged:
+ *            the slabs are [numSplits][numHeads * totalQ] rows.  Not needed (may be NULL) when the plan says num_splits == 1
+ *   plan     flash_attention_extend_varlen_plan: fa_decode_plan for these calls (seqLenK = the capacity).  rows_per_block is
+ *            flash_attention_extend_plan's.  row_blocks is a BOUND over the whole batch, which the host can compute without the offsets:
+ *            NB = floor((G * totalQ + batchSize * (rows_per_block - 1)) / rows_per_block) >= sum_b ceil(G * sq_b / rows_per_block).
+ *            grid = numHeadsKV * NB * num_splits; a workgroup finds its sequence and row block from cuSeqlensQ by itself (no extra
+ *            launch, no workspace at num_splits == 1) and one beyond the real total returns at once.  combine_grid = numHeads * totalQ.
+ *            numSplits = 0: flash_attention_extend_plan's rule and constants with units = numHeadsKV * NB; that rule is not measured
+ *            for mixed batches
+ * Limits.  numHeads * totalQ and the grid must fit in an int32; batchSize <= FA_VARLEN_MAX_BATCH; totalQ >= 1.
+ * Rejected before any launch: everything flash_attention_extend* of the same form rejects, with the same codes and in the same order,
+ * except its seqLenQ > capacity; a NULL cuSeqlensQ FA_ERR_NULL_POINTER; one not aligned to 4 bytes FA_ERR_MISALIGNED; totalQ < 1,
+ * batchSize > FA_VARLEN_MAX_BATCH and the int32 limits FA_ERR_BAD_SHAPE.
+ * Not done here: sliding windows, a per-unit choice of rows_per_block, reordering units by length, attention sinks, fp8 Q, routing.
+ */
+#define FA_VARLEN_MAX_BATCH 1024    /* sequences per ragged call: the unit lookup scans them 64 at a time, 16 steps at the most */
+
+int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                       int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
+
+int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                  const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                  const float* kDescale, const float* vDescale, void* workspace,
+                                  int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                  float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                  void* stream);
+
+int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace,
+                                        int batchSize, int numHeads, int numHeadsKV, int totalQ,
+                                        int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                        float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream);
+
+/*
+ * flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen -- the RAGGED cache append: flash_attention_kv_append /
+ * _paged with Knew / Vnew packed by token -- [totalQ, numHeadsKV, dHead] bf16 on the stride rule of flash_attention_extend_varlen's Q
+ * (row t, K/V head h at t * strideS + h * strideH; strideB ignored; NULL = dense token-major) -- seqLenNew replaced by totalQ and
+ * cuSeqlensQ (that call's: the same device tensor serves both) added directly before kvLens.  Everything not named here is the
+ * uniform call's of the same form and kv_dtype.
+ *   positions  per sequence, with L = min(kvLens[b], capacity) and sq_b from cuSeqlensQ: new row i goes to position L - sq_b + i when
+ *            that is >= 0 (sq_b > L: the leading rows are dropped); L <= 0 or sq_b = 0 writes nothing; tokens owned by no sequence are
+ *            not read.  Table entries outside [0, numPages) are skipped, never clamped
+ *   values   the uniform call's: a bit copy, or / descale, saturation at +-448, one rounding to nearest even and the NaN rule
+ *   seam     the bytes written for sequence b are exactly those of flash_attention_kv_append* called for that sequence alone with
+ *            seqLenNew = sq_b; every other byte of the cache keeps its value.  One launch writes K and V, with vector stores only
+ * totalQ >= 1 is not capped at the capacity; batchSize <= FA_VARLEN_MAX_BATCH.  Rejected before any launch: everything the uniform
+ * call rejects, with the same codes, except its seqLenNew > capacity; a NULL cuSeqlensQ FA_ERR_NULL_POINTER, one not aligned to 4
+ * bytes FA_ERR_MISALIGNED, batchSize > FA_VARLEN_MAX_BATCH FA_ERR_BAD_SHAPE.
+ */
+int flash_attention_kv_append_varlen(const void* Knew, const void* Vnew, void* K, void* V,
+                                     const int32_t* cuSeqlensQ, const int32_t* kvLens, const float* kDescale, const float* vDescale,
+                                     int batchSize, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                     int dtype /* of Knew, Vnew: FA_DTYPE_BF16 */, int kv_dtype /* FA_DTYPE_BF16 | FA_DTYPE_FP8_E4M3 */,
+                                     const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                                     void* stream);
+
+int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                                           const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                           const float* kDescale, const float* vDescale,
+                                           int batchSize, int numHeadsKV, int totalQ,
+                                           int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                           int dtype, int kv_dtype,
+                                           const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
+                                           void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);

@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append]
+                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -56,6 +56,25 @@ Each line:
                                 that the prefill route would need first, each timed on its own
               each with _min / _max over the windows (profiles/extend_bench.log).  With --splits: the forced
               sweep of flash_attention_extend on the bf16 cache, one line per (shape, split count).
+--varlen        flash_attention_extend_varlen / flash_attention_extend_paged_varlen (ragged chunked prefill: a per-sequence row count,
+              Q / O packed by token) on mixed batches: one line per shape and cache form ("bf16", --kv fp8, --paged as for --extend).
+              Shapes (H32 Hkv8, causal, d = 128 and, named d64_..., d = 64; kv_lens = prefix + rows):
+                decode63_chunk512  63 decoding sequences (1 row) on 8 k ... 32 k, plus one 512-row chunk on 8 k
+                chunks8_64_1024    8 chunks of 64, 128, 192, 256, 384, 512, 768, 1024 rows on 1 k ... 32 k
+                uniform8x512_8k    8 x 512 rows on 8 k           decode64_16k  64 x 1 row on 16 k
+              varlen_ms         one ragged call (O and the workspace given), timed like `ms`; splits, row_blocks_bound (the plan's NB),
+                                row_blocks_real (what the lookup finds), rows_per_block, grid: its plan
+              grouped_ms        what a caller does today: one flash_attention_decode* for the 1-row sequences plus one
+                                flash_attention_extend* per distinct chunk length (grouped_calls of them), on PRE-GROUPED tensors --
+                                the regrouping copies are not charged; varlen_vs_grouped_max_abs: the largest difference
+              regroup_ms        those copies on their own: Q from token-major into [Bg, H, rows, d] per group, O back
+              extend_ms / ms    (a uniform batch: one group) grouped_ms under the name of the call it is -- the same problem through
+                                flash_attention_extend (the cost of being ragged) or, 1-row sequences only, through
+                                flash_attention_decode (the cost of row blocks of 32 / 64 rows on decode rows)
+              append_varlen_ms  one kv_cache_append*_varlen call for the batch's new rows; append_ms: today's, one kv_cache_append*
+                                call per group on pre-grouped new rows
+              each with _min / _max over the windows (profiles/extend_varlen_bench.log).  With --splits: the
+              forced sweep of the ragged call on the bf16 cache, one line per (shape, split count).
 """
 import argparse
 import json
@@ -240,6 +259,182 @@ def extend_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def varlen_shapes():
+    """name, d, [(rows, prefix)] per sequence, in batch order; sequences of one row count are neighbours, so that the grouped calls
+    of `grouped_ms` take slices of the batch"""
+    out = []
+    for d in (128, 64):
+        s = "" if d == 128 else "d64_"
+        out += [(s + "decode63_chunk512", d, [(1, 8192 + (32768 - 8192) * b // 62) for b in range(63)] + [(512, 8192)]),
+                (s + "chunks8_64_1024", d, [(r, 1024 + (32768 - 1024) * b // 7) for b, r in enumerate((64, 128, 192, 256, 384, 512, 768, 1024))]),
+                (s + "uniform8x512_8k", d, [(512, 8192)] * 8),
+                (s + "decode64_16k", d, [(1, 16384 - 1)] * 64)]
+    return out
+
+
+def varlen_main(args, fa, dev):
+    """--varlen: flash_attention_extend_varlen / _paged_varlen on mixed batches (H32 Hkv8, causal), beside what a caller does today"""
+    import torch
+    f8 = torch.float8_e4m3fn
+    H, Hkv = 32, 8
+    shapes = varlen_shapes()
+    if args.shape:
+        unknown = set(args.shape) - {x[0] for x in shapes}
+        if unknown:
+            raise SystemExit(f"unknown --varlen shape(s): {sorted(unknown)}")
+        shapes = [x for x in shapes if x[0] in args.shape]
+    windows = lambda call, steps=None: sorted(timed(call, steps or args.steps, args.warmup) for _ in range(args.repeats))
+    stats = lambda key, v: {key: round(statistics.median(v), 5), key + "_min": round(v[0], 5), key + "_max": round(v[-1], 5)}
+    primed = False
+    for name, d, seqs in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        B, sq = len(seqs), [r for r, _ in seqs]
+        lens = [r + p for r, p in seqs]
+        cu = [0]
+        for r in sq:
+            cu.append(cu[-1] + r)
+        T = cu[-1]
+        Sk = -(-max(lens) // 256) * 256                     # the capacity: whole pages of every --paged size
+        Q = torch.randn(T, H, d, device=dev, generator=g).to(torch.bfloat16)
+        K, V = (torch.randn(B, Hkv, Sk, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        Kn, Vn = (torch.randn(T, Hkv, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        cu_d, lens_d = torch.tensor(cu, dtype=torch.int32, device=dev), torch.tensor(lens, dtype=torch.int32, device=dev)
+        O = torch.zeros(T, H, d, device=dev, dtype=torch.bfloat16)
+        # the groups of today's calls: runs of one row count -> (first sequence, one past the last, rows)
+        groups = []
+        for b, r in enumerate(sq):
+            if groups and groups[-1][2] == r:
+                groups[-1][1] = b + 1
+            else:
+                groups.append([b, b + 1, r])
+        base = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "d": d, "totalQ": T, "rows": sq if len(set(sq)) > 1 else sq[0],
+                "kv_len_min": min(lens), "kv_len_max": max(lens), "capacity": Sk, "io": "bfloat16", "repeats": args.repeats, "steps": args.steps}
+
+        def varlen_call(Kc, Vc, table, kw, ns=0):
+            plan = fa.extend_varlen_plan(B, H, Hkv, T, Sk, d, fa.FA_DTYPE_BF16, ns)
+            ws = torch.empty(max(fa.decode_workspace_size(1, H, T, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            if table is None:
+                return plan, lambda: fa.flash_attention_extend_varlen(Q, Kc, Vc, cu_d, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+            return plan, lambda: fa.flash_attention_extend_paged_varlen(Q, Kc, Vc, table, cu_d, lens_d, is_causal=True, O=O, workspace=ws,
+                                                                        num_splits=ns, **kw)
+
+        def prime(call):
+            nonlocal primed
+            if not primed:   # >= 1 s of calls before the first timed window
+                t = 0.0
+                while t < 1000.0:
+                    t += timed(call, 20, 0) * 20
+                primed = True
+
+        if args.splits:
+            for ns in [int(x) for x in args.splits.split(",")]:
+                if ns > -(-Sk // 128):
+                    continue
+                plan, call = varlen_call(K, V, None, {}, ns)
+                prime(call)
+                print(json.dumps(dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("varlen_ms", windows(call)))), flush=True)
+            del Q, K, V, O, Kn, Vn
+            torch.cuda.empty_cache()
+            continue
+
+        def regroup_calls():
+            """the copies between the engine's token-major tensors and the [Bg, H, rows, d] tensors of the grouped calls: Q in, O back"""
+            Qg = [torch.empty(b1 - b0, H, r, d, device=dev, dtype=torch.bfloat16) for b0, b1, r in groups]
+            Og = [torch.empty_like(q) for q in Qg]
+            Oback = torch.empty_like(O)
+
+            def call():
+                for (b0, b1, r), q, o in zip(groups, Qg, Og):
+                    q.copy_(Q[cu[b0]:cu[b1]].view(b1 - b0, r, H, d).transpose(1, 2))
+                    Oback[cu[b0]:cu[b1]].view(b1 - b0, r, H, d).copy_(o.transpose(1, 2))
+            call()
+            return Qg, Og, call
+
+        def grouped_call(Qg, Og, Kc, Vc, table, kw):
+            """one flash_attention_decode* for the rows <= 16, one flash_attention_extend* per other row count, on pre-grouped tensors"""
+            calls = []
+            for (b0, b1, r), q, o in zip(groups, Qg, Og):
+                n = b1 - b0
+                L = lens_d[b0:b1].contiguous()
+                front = "flash_attention_decode" if r <= fa.FA_DECODE_MAX_Q else "flash_attention_extend"
+                plan = (fa.decode_plan if r <= fa.FA_DECODE_MAX_Q else fa.extend_plan)(n, H, Hkv, r, Sk, d, fa.FA_DTYPE_BF16, 0)
+                ws = torch.empty(max(fa.decode_workspace_size(n, H, r, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+                if table is None:
+                    calls.append(lambda f=getattr(fa, front), q=q, o=o, L=L, ws=ws, b0=b0, b1=b1:
+                                 f(q, Kc[b0:b1], Vc[b0:b1], L, is_causal=True, O=o, workspace=ws, **kw))
+                else:
+                    calls.append(lambda f=getattr(fa, front + "_paged"), q=q, o=o, L=L, ws=ws, t=table[b0:b1]:
+                                 f(q, Kc, Vc, t, L, is_causal=True, O=o, workspace=ws, **kw))
+            return lambda: [c() for c in calls]
+
+        def append_calls(Kc, Vc, table, kw):
+            """(the ragged append, today's appends: one uniform call per group on pre-grouped new rows) into copies of the cache form"""
+            Kw, Vw = Kc.clone(), Vc.clone()
+            Kg = [Kn[cu[b0]:cu[b1]].view(b1 - b0, r, Hkv, d).transpose(1, 2).contiguous() for b0, b1, r in groups]
+            Vg = [Vn[cu[b0]:cu[b1]].view(b1 - b0, r, Hkv, d).transpose(1, 2).contiguous() for b0, b1, r in groups]
+            Lg = [lens_d[b0:b1].contiguous() for b0, b1, _ in groups]
+            if table is None:
+                ragged = lambda: fa.kv_cache_append_varlen(Kn, Vn, Kw, Vw, cu_d, lens_d, **kw)
+                today = lambda: [fa.kv_cache_append(k, v, Kw[b0:b1], Vw[b0:b1], L, **kw) for (b0, b1, _), k, v, L in zip(groups, Kg, Vg, Lg)]
+            else:
+                ragged = lambda: fa.kv_cache_append_paged_varlen(Kn, Vn, Kw, Vw, table, cu_d, lens_d, **kw)
+                today = lambda: [fa.kv_cache_append_paged(k, v, Kw, Vw, table[b0:b1], L, **kw) for (b0, b1, _), k, v, L in zip(groups, Kg, Vg, Lg)]
+            return ragged, today
+
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in (int(x) for x in (args.paged or "").split(",") if x):
+            forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        if args.kv == "fp8":
+            def quant(Tn):
+                ds = (Tn.float().abs().amax(dim=(0, 2, 3)) / 448.0).float()
+                T8 = torch.empty(Tn.shape, dtype=f8, device=dev)
+                for b in range(B):     # (a batch entry at a time: no fp32 copy of the whole cache)
+                    T8[b] = (Tn[b].float() / ds[:, None, None]).clamp(-448, 448).to(f8)
+                return T8, ds
+            (K8, kds), (V8, vds) = quant(K), quant(V)
+        Qg, Og, rcall = regroup_calls()
+        regroup = stats("regroup_ms", windows(rcall))
+        for form, fp8, page in forms:
+            Kc, Vc, table = (K8, V8, None) if fp8 else (K, V, None)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            line = dict(base, form=form)
+            if page:
+                n = Sk // page
+                perm = torch.randperm(B * n, device=dev, generator=g)
+                table = perm.reshape(B, n).to(torch.int32)
+                pools = []
+                for Tn in (Kc, Vc):
+                    Tn = Tn.view(torch.uint8) if fp8 else Tn      # (pages are moved as bytes)
+                    pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=Tn.dtype)
+                    pool[perm] = Tn.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
+                    pools.append(pool.view(f8) if fp8 else pool)
+                Kc, Vc = pools
+            plan, call = varlen_call(Kc, Vc, table, kw)
+            prime(call)
+            line.update(stats("varlen_ms", windows(call)))
+            line.update(splits=plan["num_splits"], row_blocks_bound=plan["row_blocks"], rows_per_block=plan["rows_per_block"], grid=plan["grid"],
+                        row_blocks_real=sum(-(-(H // Hkv) * r // plan["rows_per_block"]) for r in sq))
+            gcall = grouped_call(Qg, Og, Kc, Vc, table, kw)
+            line.update(stats("grouped_ms", windows(gcall)))
+            line["grouped_calls"] = len(groups)
+            line.update(regroup)
+            worst = max(((O[cu[b0]:cu[b1]].view(b1 - b0, r, H, d).transpose(1, 2).float() - o.float()).abs().max().item()
+                         for (b0, b1, r), o in zip(groups, Og)))
+            line["varlen_vs_grouped_max_abs"] = round(worst, 6)
+            line["varlen_over_grouped"] = round(line["varlen_ms"] / line["grouped_ms"], 3)
+            line["varlen_over_grouped_and_regroup"] = round(line["varlen_ms"] / (line["grouped_ms"] + line["regroup_ms"]), 3)
+            if len(groups) == 1:   # a uniform batch: grouped_ms IS the uniform call of the same problem -- the cost of being ragged
+                line["extend_ms" if sq[0] > fa.FA_DECODE_MAX_Q else "ms"] = line["grouped_ms"]
+            ragged, today = append_calls(Kc, Vc, table, kw)
+            line.update(stats("append_varlen_ms", windows(ragged)))
+            line.update(stats("append_ms", windows(today)))
+            print(json.dumps(line), flush=True)
+        del Q, K, V, O, Kn, Vn, Qg, Og
+        if args.kv == "fp8":
+            del K8, V8
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -252,6 +447,7 @@ def main():
     ap.add_argument("--window", default=None, help="comma-separated sliding windows: add window_ms per window to every shape's line")
     ap.add_argument("--append", action="store_true", help="add append_ms / torch_append_ms / fill_ms / fill_tbps per cache form to every shape's line")
     ap.add_argument("--extend", action="store_true", help="time flash_attention_extend on its own shapes, beside the decode-slice and prefill-pair routes")
+    ap.add_argument("--varlen", action="store_true", help="time flash_attention_extend_varlen on mixed batches, beside the grouped calls of today")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     args = ap.parse_args()
     import torch
@@ -260,6 +456,8 @@ def main():
     dev = torch.device("cuda:0")
     if args.extend:
         return extend_main(args, fa, dev)
+    if args.varlen:
+        return varlen_main(args, fa, dev)
     shapes = SHAPES
     if args.shape:
         unknown = set(args.shape) - {x[0] for x in SHAPES + EXTRA}
