@@ -19,10 +19,11 @@ entry points for that path:
   Both take ``window=W``: a sliding window, every row sees at most the last W keys up to its own position.
 * ``flash_attention_extend(Q, K, V, kv_lens)`` / ``flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens)`` --
   chunked prefill against the same caches, all four forms: any number of new rows up to the capacity, decode's mask and
-  arithmetic (``extend_plan``).
+  arithmetic (``extend_plan``); ``flash_attention_extend_window`` / ``flash_attention_extend_paged_window`` add ``window=W``.
 * ``flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens)`` / ``flash_attention_extend_paged_varlen(Q, K_pool, V_pool,
   block_table, cu_seqlens_q, kv_lens)`` -- RAGGED chunked prefill: every sequence its own number of new rows (decode rows, chunks,
-  idle slots in one call), Q and O packed by token ``[T, H, d]``, the offsets read on the device (``extend_varlen_plan``); and
+  idle slots in one call), Q and O packed by token ``[T, H, d]``, the offsets read on the device (``extend_varlen_plan``);
+  ``flash_attention_extend_varlen_window`` / ``flash_attention_extend_paged_varlen_window`` add ``window=W``; and
   ``kv_cache_append_varlen`` / ``kv_cache_append_paged_varlen``, the append of such a batch's new rows.
 * ``kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens)`` / ``kv_cache_append_paged(..., block_table, kv_lens)`` -- the write
   side of those caches: the last Sq rows of every sequence, bf16, copied into a bf16 cache or quantised (divide by the per-head
@@ -64,6 +65,9 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_extend", "flash_attention_extend_paged", "flash_attention_extend_plan",
            "flash_attention_extend_varlen", "flash_attention_extend_paged_varlen", "flash_attention_extend_varlen_plan",
            "flash_attention_kv_append_varlen", "flash_attention_kv_append_paged_varlen",
+           "flash_attention_extend_window", "flash_attention_extend_paged_window", "flash_attention_extend_plan_window",
+           "flash_attention_extend_varlen_window", "flash_attention_extend_paged_varlen_window",
+           "flash_attention_extend_varlen_plan_window",
            "flash_attention_error_string", "flash_attention_version")
 
 
@@ -174,6 +178,18 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_kv_append_varlen.restype = i
         L.flash_attention_kv_append_paged_varlen.argtypes = [vp] * 9 + L.flash_attention_kv_append_paged.argtypes[8:]
         L.flash_attention_kv_append_paged_varlen.restype = i
+        L.flash_attention_extend_window.argtypes = L.flash_attention_decode_window.argtypes
+        L.flash_attention_extend_window.restype = i
+        L.flash_attention_extend_paged_window.argtypes = L.flash_attention_decode_paged_window.argtypes
+        L.flash_attention_extend_paged_window.restype = i
+        L.flash_attention_extend_varlen_window.argtypes = [vp] * 10 + L.flash_attention_extend_window.argtypes[9:]
+        L.flash_attention_extend_varlen_window.restype = i
+        L.flash_attention_extend_paged_varlen_window.argtypes = [vp] * 11 + L.flash_attention_extend_paged_window.argtypes[10:]
+        L.flash_attention_extend_paged_varlen_window.restype = i
+        L.flash_attention_extend_plan_window.argtypes = L.flash_attention_decode_plan_window.argtypes
+        L.flash_attention_extend_plan_window.restype = i
+        L.flash_attention_extend_varlen_plan_window.argtypes = L.flash_attention_decode_plan_window.argtypes
+        L.flash_attention_extend_varlen_plan_window.restype = i
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -460,20 +476,29 @@ def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, windo
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
-def extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
+def extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=None):
     """What a flash_attention_extend call launches (fa_decode_plan as a dict; ``Sk`` the capacity); ``num_splits`` 0 = the library's
-    choice.  ``rows_per_block`` packed rows ``g * Sq + i`` of one K/V head form a row block; ``decode_workspace_size`` serves unchanged."""
+    choice.  ``rows_per_block`` packed rows ``g * Sq + i`` of one K/V head form a row block; ``decode_workspace_size`` serves unchanged.
+    ``window`` > 0: the call's sliding window -- the split count then follows from the window's tiles, as in ``decode_plan``."""
     p = FaDecodePlan()
-    _check(lib().flash_attention_extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    if _window(window):
+        _check(lib().flash_attention_extend_plan_window(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, _window(window), ctypes.byref(p)))
+    else:
+        _check(lib().flash_attention_extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
-def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0):
+def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=None):
     """What a flash_attention_extend_varlen call launches (fa_decode_plan as a dict; ``total_q`` the bound on the packed rows, ``Sk``
     the capacity); ``num_splits`` 0 = the library's choice.  ``row_blocks`` is the host's BOUND on the row blocks of the whole batch,
-    ``(G * total_q + B * (rows_per_block - 1)) // rows_per_block``; the workspace is ``decode_workspace_size(1, H, total_q, d, ns)``."""
+    ``(G * total_q + B * (rows_per_block - 1)) // rows_per_block``; the workspace is ``decode_workspace_size(1, H, total_q, d, ns)``.
+    ``window`` > 0: the call's sliding window (the tiles bound uses ``total_q`` for the row count)."""
     p = FaDecodePlan()
-    _check(lib().flash_attention_extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    if _window(window):
+        _check(lib().flash_attention_extend_varlen_plan_window(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, _window(window),
+                                                               ctypes.byref(p)))
+    else:
+        _check(lib().flash_attention_extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
     return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
 
 
@@ -529,7 +554,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
     """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
     point (fp8: its ``_fp8`` twin; a window: its ``_window`` twin, which takes both cache types), ``tables`` its tensors between
     kvLens and the workspace, ``geometry`` its ints between seqLenQ and dHead; ``decode_plan`` / ``decode_workspace_size`` are asked
-    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name.
+    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name (a window, from the ``_window`` fronts: its ``_window`` twin).
     The ragged fronts pass ``cu_seqlens_q`` (checked by them) and Q -- and O, if given -- as ``_token_view``s: Sq is then the bound
     on the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled."""
     import torch
@@ -547,7 +572,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = (plan(B, H, Hkv, Sq, capacity, d, odt, num_splits) if plan else decode_plan(B, H, Hkv, Sq, capacity, d, odt, num_splits, window))["num_splits"]
+    ns = (plan or decode_plan)(B, H, Hkv, Sq, capacity, d, odt, num_splits, window)["num_splits"]
     need = decode_workspace_size(1 if ragged else B, H, Sq, d, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -570,7 +595,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
         dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), symbol + ("" if plan else "_window" if window else "_fp8" if fp8 else ""))
+        launch = getattr(lib(), symbol + ("_window" if window else "" if plan else "_fp8" if fp8 else ""))
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
                     _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
@@ -639,6 +664,15 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
                    k_descale, v_descale, window)
 
 
+def _extend(window, Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
+            O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+    """what ``flash_attention_extend`` and ``flash_attention_extend_window`` share: the former is this with ``window`` None"""
+    fp8 = _decode_inputs("flash_attention_extend", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
+    Sk = K.shape[2]
+    return _decode("flash_attention_extend", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
+                   O, workspace, stream, k_descale, v_descale, window, plan=extend_plan)
+
+
 def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
                            O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
     """Chunked prefill against a decode cache: Q ``[B, H, Sq, d]`` with 1 <= Sq <= capacity new rows per sequence against the K/V
@@ -646,21 +680,27 @@ def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     ``k_descale`` / ``v_descale``; d = 64 or 128, Hkv dividing H).  Everything is ``flash_attention_decode``'s -- ``kv_lens`` (which
     already counts the new rows: ``kv_lens += Sq; kv_cache_append; flash_attention_extend``), the bottom-right ``is_causal``,
     ``num_splits``, ``workspace`` (``decode_workspace_size`` bytes for ``extend_plan``'s split count), ``O``, ``return_lse``,
-    ``stream`` -- without the cap on Sq and without ``window``.  For Sq <= 16 the result is that call's, bit for bit, under the same
-    forced ``num_splits``.  No CPU fallback."""
-    fp8 = _decode_inputs("flash_attention_extend", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
-    Sk = K.shape[2]
-    return _decode("flash_attention_extend", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   O, workspace, stream, k_descale, v_descale, None, plan=extend_plan)
+    ``stream`` -- without the cap on Sq and without ``window`` (that is ``flash_attention_extend_window``).  For Sq <= 16 the result is
+    that call's, bit for bit, under the same forced ``num_splits``.  No CPU fallback."""
+    return _extend(None, Q, K, V, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, k_descale,
+                   v_descale)
 
 
-def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
-                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
-                                 v_descale=None):
-    """``flash_attention_extend`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
-    ``[B, max_pages]`` of ``flash_attention_decode_paged``, with that call's rules for the table, the lengths and the capacity
-    ``max_pages * page`` (``extend_plan`` is asked with ``Sk = max_pages * page``).  The result is ``flash_attention_extend``'s on a
-    contiguous copy of the same pages, bit for bit.  No ``window``.  No CPU fallback."""
+def flash_attention_extend_window(Q, K, V, kv_lens=None, window=None, **kw):
+    """``flash_attention_extend`` with a SLIDING WINDOW: the same arguments plus ``window``.  W > 0: decode's rule with this call's Sq --
+    row i sees ``max(limC_i - W, 0) <= k`` with ``limC_i = max(kv_lens[b] - Sq + i + 1, 1)``, below ``limC_i`` with ``is_causal`` and
+    below ``kv_lens[b]`` without.  Keys below row 0's left edge are not read and may hold anything.  A row block walks only the tiles from
+    its own rows' left edge on, so a long windowed chunk reads about W + rows keys per block, not the whole prefix
+    (``extend_plan(..., window=W)``).  None or 0: ``flash_attention_extend`` itself, the same launches and bits.  For Sq <= 16 the result
+    is ``flash_attention_decode(window=W)``'s, bit for bit, under the same forced ``num_splits``.  A negative window raises ValueError.
+    No CPU fallback."""
+    return _extend(window, Q, K, V, kv_lens, **kw)
+
+
+def _extend_paged(window, Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
+                  v_descale=None):
+    """what ``flash_attention_extend_paged`` and ``flash_attention_extend_paged_window`` share: the former is this with ``window`` None"""
     import torch
     fp8 = _decode_inputs("flash_attention_extend_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
                          v_descale, table=block_table)
@@ -673,7 +713,25 @@ def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     table_stride = block_table.stride(0) if B > 1 else max_pages
     return _decode("flash_attention_extend_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
                    (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                   k_descale, v_descale, None, plan=extend_plan)
+                   k_descale, v_descale, window, plan=extend_plan)
+
+
+def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
+                                 v_descale=None):
+    """``flash_attention_extend`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
+    ``[B, max_pages]`` of ``flash_attention_decode_paged``, with that call's rules for the table, the lengths and the capacity
+    ``max_pages * page`` (``extend_plan`` is asked with ``Sk = max_pages * page``).  The result is ``flash_attention_extend``'s on a
+    contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_window``).  No CPU fallback."""
+    return _extend_paged(None, Q, K_pool, V_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
+                         workspace, stream, k_descale, v_descale)
+
+
+def flash_attention_extend_paged_window(Q, K_pool, V_pool, block_table, kv_lens=None, window=None, **kw):
+    """``flash_attention_extend_paged`` with a sliding window, as ``flash_attention_extend_window``: a page wholly below row 0's left
+    edge is not read and neither is its table entry, which may be any int32.  The result is ``flash_attention_extend_window``'s on a
+    contiguous copy of the same pages, bit for bit.  No CPU fallback."""
+    return _extend_paged(window, Q, K_pool, V_pool, block_table, kv_lens, **kw)
 
 
 def _table_geometry(block_table, B):
@@ -683,6 +741,18 @@ def _table_geometry(block_table, B):
     if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
         raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
     return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
+
+
+def _extend_varlen(window, Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
+                   return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+    """what ``flash_attention_extend_varlen`` and ``flash_attention_extend_varlen_window`` share: the former is this with ``window`` None"""
+    Qv = _token_view(Q, "Q")
+    B = _cu_seqlens(cu_seqlens_q, Q) if Q.is_cuda else None
+    fp8 = _decode_inputs("flash_attention_extend_varlen", "K, V", "[B, Hkv, capacity, d]", Qv, K, V, k_descale, v_descale, batch=B)
+    Sk = K.shape[2]
+    return _decode("flash_attention_extend_varlen", fp8, Qv, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits,
+                   return_lse, None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, window,
+                   plan=extend_varlen_plan, cu_seqlens_q=cu_seqlens_q)
 
 
 def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
@@ -698,23 +768,24 @@ def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=Non
     rows, the bottom-right ``is_causal``, the tiles and splits -- the O and LSE of a sequence are, bit for bit, those of
     ``flash_attention_extend`` on that sequence alone under the same forced ``num_splits``.  ``num_splits`` 0 = the library's choice
     (``extend_varlen_plan``); ``workspace``: ``decode_workspace_size(1, H, T, d, ns)`` bytes.  Returns O ``[T, H, d]`` or, with
-    ``return_lse``, ``(O, LSE)`` with the LSE fp32 ``[H, T]``; an O or LSE allocated here is zero-filled.  No CPU fallback."""
-    Qv = _token_view(Q, "Q")
-    B = _cu_seqlens(cu_seqlens_q, Q) if Q.is_cuda else None
-    fp8 = _decode_inputs("flash_attention_extend_varlen", "K, V", "[B, Hkv, capacity, d]", Qv, K, V, k_descale, v_descale, batch=B)
-    Sk = K.shape[2]
-    return _decode("flash_attention_extend_varlen", fp8, Qv, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits,
-                   return_lse, None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, None,
-                   plan=extend_varlen_plan, cu_seqlens_q=cu_seqlens_q)
+    ``return_lse``, ``(O, LSE)`` with the LSE fp32 ``[H, T]``; an O or LSE allocated here is zero-filled.  No ``window``
+    (``flash_attention_extend_varlen_window``).  No CPU fallback."""
+    return _extend_varlen(None, Q, K, V, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
+                          stream, k_descale, v_descale)
 
 
-def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
-                                        out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
-                                        k_descale=None, v_descale=None):
-    """``flash_attention_extend_varlen`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
-    ``[B, max_pages]`` of ``flash_attention_extend_paged`` (``extend_varlen_plan`` is asked with ``Sk = max_pages * page``).  The
-    table row and the length of a sequence without rows are not read.  The result is ``flash_attention_extend_varlen``'s on a
-    contiguous copy of the same pages, bit for bit.  No CPU fallback."""
+def flash_attention_extend_varlen_window(Q, K, V, cu_seqlens_q, kv_lens=None, window=None, **kw):
+    """``flash_attention_extend_varlen`` with a sliding window: ``flash_attention_extend_window``'s rule per sequence with its own row
+    count (``extend_varlen_plan(..., window=W)``); None or 0: ``flash_attention_extend_varlen`` itself.  The O and LSE of a sequence are,
+    bit for bit, those of ``flash_attention_extend_window`` on that sequence alone under the same forced ``num_splits``.  No CPU
+    fallback."""
+    return _extend_varlen(window, Q, K, V, cu_seqlens_q, kv_lens, **kw)
+
+
+def _extend_paged_varlen(window, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
+                         out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
+                         k_descale=None, v_descale=None):
+    """what ``flash_attention_extend_paged_varlen`` and ``flash_attention_extend_paged_varlen_window`` share: the former is this with ``window`` None"""
     Qv = _token_view(Q, "Q")
     fp8 = _decode_inputs("flash_attention_extend_paged_varlen", "K_pool, V_pool", "[P, Hkv, page, d]", Qv, K_pool, V_pool, k_descale,
                          v_descale, table=block_table)
@@ -723,8 +794,25 @@ def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqle
     max_pages, table_stride = _table_geometry(block_table, B)
     return _decode("flash_attention_extend_paged_varlen", fp8, Qv, K_pool, V_pool, max_pages * page, (block_table,),
                    (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, None, plan=extend_varlen_plan,
+                   None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, window, plan=extend_varlen_plan,
                    cu_seqlens_q=cu_seqlens_q)
+
+
+def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
+                                        out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
+                                        k_descale=None, v_descale=None):
+    """``flash_attention_extend_varlen`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
+    ``[B, max_pages]`` of ``flash_attention_extend_paged`` (``extend_varlen_plan`` is asked with ``Sk = max_pages * page``).  The
+    table row and the length of a sequence without rows are not read.  The result is ``flash_attention_extend_varlen``'s on a
+    contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_varlen_window``).  No CPU fallback."""
+    return _extend_paged_varlen(None, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits,
+                                return_lse, O, workspace, stream, k_descale, v_descale)
+
+
+def flash_attention_extend_paged_varlen_window(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, window=None, **kw):
+    """``flash_attention_extend_paged_varlen`` with a sliding window, as ``flash_attention_extend_varlen_window``; pages below a
+    sequence's window as in ``flash_attention_extend_paged_window``.  No CPU fallback."""
+    return _extend_paged_varlen(window, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, **kw)
 
 
 def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None,

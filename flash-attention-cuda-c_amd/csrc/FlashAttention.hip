@@ -314,6 +314,9 @@ constexpr int EXTEND_MIN_TILES = 2;
 // units = Hkv * NB, NB the host's BOUND on the batch's row blocks (decode_route) -- the host cannot see the real count, nor how unequal
 // the units are (a decode row's unit walks a whole cache, a chunk's lower blocks a part of it).  NOT measured for mixed batches: the
 // forced sweep of tools/bench_decode.py --varlen (profiles/extend_varlen_bench.log) shows what the rule costs.
+// The _window calls of both extend families (WINDOW = true units, a per-row-block tile range: decode_bf16.hip.h):
+// `tiles` is decode's windowed bound with Sq = seqLenQ or totalQ, and the split count follows by extend's unchanged rule and
+// constants.  NOT measured for windowed chunks: tools/bench_decode.py --extend --window with --splits shows what the rule costs.
 
 // What a call family is to the launch decision: built once per entry point (decode_form, extend_form), read by decode_check_shape,
 // decode_route and decode_run
@@ -323,16 +326,24 @@ struct SplitForm {
     int wgs_per_cu;        // resident workgroups per CU the split rule fills
     int min_tiles;         // no split shorter than this many key tiles of the capacity
     bool q_to_capacity;    // seqLenQ is capped at the capacity, not at FA_DECODE_MAX_Q
-    const SplitKernelOf (*split_kernel_of)[2];   // [paged][kv8]: the selectors of the family's four cache forms
+    const SplitKernelOf (*split_kernel_of)[2][2];   // [window][paged][kv8]: the selectors of the family's cache forms, without and with
+                           // a window (decode: one set, WINDOW = true, serves both; extend: windowSize = 0 launches the WINDOW = false units)
     bool varlen;           // ragged: "Sq" is totalQ, the bound on the token-packed rows of the whole batch (not capped at the capacity),
                            // row_blocks the bound NB over the batch, batchSize <= FA_VARLEN_MAX_BATCH and cuSeqlensQ is required
 };
-static constexpr SplitKernelOf DECODE_KERNELS[2][2] = {{decode_split_kernel_of, decode_fp8_split_kernel_of},
-                                                       {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}};
-static constexpr SplitKernelOf EXTEND_KERNELS[2][2] = {{extend_split_kernel_of, extend_fp8_split_kernel_of},
-                                                       {extend_paged_split_kernel_of, extend_paged_fp8_split_kernel_of}};
-static constexpr SplitKernelOf VARLEN_KERNELS[2][2] = {{extend_varlen_split_kernel_of, extend_varlen_fp8_split_kernel_of},
-                                                       {extend_varlen_paged_split_kernel_of, extend_varlen_paged_fp8_split_kernel_of}};
+static constexpr SplitKernelOf DECODE_KERNELS[2][2][2] = {{{decode_split_kernel_of, decode_fp8_split_kernel_of},
+                                                           {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}},
+                                                          {{decode_split_kernel_of, decode_fp8_split_kernel_of},
+                                                           {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}}};
+static constexpr SplitKernelOf EXTEND_KERNELS[2][2][2] = {{{extend_split_kernel_of, extend_fp8_split_kernel_of},
+                                                           {extend_paged_split_kernel_of, extend_paged_fp8_split_kernel_of}},
+                                                          {{extend_window_split_kernel_of, extend_window_fp8_split_kernel_of},
+                                                           {extend_window_paged_split_kernel_of, extend_window_paged_fp8_split_kernel_of}}};
+static constexpr SplitKernelOf VARLEN_KERNELS[2][2][2] = {
+    {{extend_varlen_split_kernel_of, extend_varlen_fp8_split_kernel_of},
+     {extend_varlen_paged_split_kernel_of, extend_varlen_paged_fp8_split_kernel_of}},
+    {{extend_window_varlen_split_kernel_of, extend_window_varlen_fp8_split_kernel_of},
+     {extend_window_varlen_paged_split_kernel_of, extend_window_varlen_paged_fp8_split_kernel_of}}};
 static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, DECODE_KERNELS, false}; }
 static SplitForm extend_form(int d) {   // (any d but 128 takes the d = 64 values: decode_check_shape refuses it before they matter)
     return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS, false}
@@ -468,7 +479,7 @@ static int decode_run(const SplitForm& f, const void* Q, const void* K, const vo
     p.B = B;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
-    const Kernel sk = f.split_kernel_of[pg != nullptr][kv8](d);
+    const Kernel sk = f.split_kernel_of[window > 0][pg != nullptr][kv8](d);
     if (f.varlen) {
         const hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
         if (e != hipSuccess || r.ns == 1) return (int)e;
@@ -869,16 +880,33 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                           &pg, stream);
 }
 
-int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
-                                int numSplits, fa_decode_plan* plan) {
+int flash_attention_extend_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                       int numSplits, int windowSize, fa_decode_plan* plan) {
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
     const SplitForm f = extend_form(dHead);
-    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0);
+    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
+                                      windowSize);
     if (rc != FA_OK) return rc;
-    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, 0), dHead,
+    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize), dHead,
                     (int64_t)batchSize * numHeads * seqLenQ);
     return FA_OK;
+}
+
+int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                                int numSplits, fa_decode_plan* plan) {
+    return flash_attention_extend_plan_window(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, numSplits, 0, plan);
+}
+
+int flash_attention_extend_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                           const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                           int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
+                           int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                           const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
+                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, nullptr,
+                          stream);
 }
 
 int flash_attention_extend(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -886,9 +914,20 @@ int flash_attention_extend(const void* Q, const void* K, const void* V, void* O,
                            int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
                            int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                            const fa_strides* sO, void* stream) {
+    return flash_attention_extend_window(Q, K, V, O, LSE, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV, seqLenQ,
+                                         seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, stream);
+}
+
+int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                 const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                 int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                 int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                 const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
-                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg,
                           stream);
 }
 
@@ -898,11 +937,9 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
                                  int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
                                  int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
-    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
-                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
-                          stream);
+    return flash_attention_extend_paged_window(Q, Kpool, Vpool, O, LSE, kvLens, blockTable, kDescale, vDescale, workspace, batchSize,
+                                               numHeads, numHeadsKV, seqLenQ, numPages, pageSize, maxPagesPerSeq, tableStride, dHead, scale,
+                                               is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* kvLens, const float* kDescale,
@@ -923,16 +960,34 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
                              kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
 }
 
-int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, int o_dtype,
-                                       int numSplits, fa_decode_plan* plan) {
+int flash_attention_extend_varlen_plan_window(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                              int o_dtype, int numSplits, int windowSize, fa_decode_plan* plan) {
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
     const SplitForm f = extend_varlen_form(dHead);
-    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits, 0);
+    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
+                                      windowSize);
     if (rc != FA_OK) return rc;
-    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, numSplits, 0), dHead,
+    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, numSplits, windowSize), dHead,
                     (int64_t)numHeads * totalQ);
     return FA_OK;
+}
+
+int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, int o_dtype,
+                                       int numSplits, fa_decode_plan* plan) {
+    return flash_attention_extend_varlen_plan_window(batchSize, numHeads, numHeadsKV, totalQ, seqLenK, dHead, o_dtype, numSplits, 0,
+                                                     plan);
+}
+
+int flash_attention_extend_varlen_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int batchSize,
+                                  int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::decode_run(fa::extend_varlen_form(dHead), Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace, batchSize,
+                          numHeads, numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK,
+                          sV, sO, nullptr, stream);
 }
 
 int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
@@ -940,10 +995,23 @@ int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, v
                                   int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
                                   int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                   const fa_strides* sV, const fa_strides* sO, void* stream) {
+    return flash_attention_extend_varlen_window(Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
+                                                numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits,
+                                                0, sQ, sK, sV, sO, stream);
+}
+
+int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                                        int numHeadsKV, int totalQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                        int dHead, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int windowSize,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::extend_varlen_form(dHead), Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace, batchSize,
-                          numHeads, numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK,
-                          sV, sO, nullptr, stream);
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run(fa::extend_varlen_form(dHead), Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace,
+                          batchSize, numHeads, numHeadsKV, totalQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ,
+                          sK, sV, sO, &pg, stream);
 }
 
 int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
@@ -953,11 +1021,10 @@ int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const 
                                         int dHead, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits,
                                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                         void* stream) {
-    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::extend_varlen_form(dHead), Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace,
-                          batchSize, numHeads, numHeadsKV, totalQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ,
-                          sK, sV, sO, &pg, stream);
+    return flash_attention_extend_paged_varlen_window(Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, blockTable, kDescale, vDescale,
+                                                      workspace, batchSize, numHeads, numHeadsKV, totalQ, numPages, pageSize,
+                                                      maxPagesPerSeq, tableStride, dHead, scale, is_causal, dtype, kv_dtype, o_dtype,
+                                                      numSplits, 0, sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_kv_append_varlen(const void* Knew, const void* Vnew, void* K, void* V, const int32_t* cuSeqlensQ,

@@ -49,7 +49,19 @@
 //     the accumulator), and they can only lie in the sequence's first tile, which is only ever loaded by the prologue: there a lane
 //     whose V row is below `first` uses an offset beyond any record count, and a paged 16-key group wholly below it a zero-byte
 //     descriptor.  The loop's own loads carry none of this.  window = 0: first = lo_i = 0.  The decode instantiations are
-//     WINDOW = true; with WINDOW = false (chunked prefill: DecodeParams::window is not read) every term of this bullet folds away.
+//     WINDOW = true; with WINDOW = false (un-windowed chunked prefill: DecodeParams::window is not read) every term of this bullet
+//     folds away.
+//   * WINDOW at RT > 1 (flash_attention_extend*_window), uniform or VARLEN: the per-row bounds lo / span are
+//     the same text over rt, with Sq the sequence's row count.  The tile range follows the window PER ROW BLOCK: a block whose
+//     smallest query row is qmin (0 if the block reaches into the next head, else its first row's) starts at
+//     firstb = max(max(len - Sq + qmin + 1, 1) - W, 0), tile tlo_b = firstb / TILE, and its tiles [tlo_b, ntb) are divided over the
+//     splits as before: a long windowed chunk reads about W + rows keys per block, not the whole prefix.  Sq <= FA_DECODE_MAX_Q:
+//     firstb = first, so the range -- and with it every bit -- is decode's.  The "V below first" logic stays keyed on the
+//     sequence-wide `first`: firstb >= first, keys in [first, firstb) are data (another block reads them; here they are masked
+//     with P = 0 against finite V), and the tile that holds `first` is tile tlo = first / TILE <= tlo_b <= t0 of every split, which a
+//     block can only load as its own t0, i.e. by the prologue -- the loop loads tiles above t0 only.  Known cost: row blocks are
+//     not head-aligned, and a block that straddles two heads of a long windowed chunk walks from lo_0 to len (only when
+//     G Sq is no multiple of the row block).  At RT = 1 and at WINDOW = false the per-block term is not compiled.
 //   * RT (flash_attention_extend, flash_attention_extend_paged): a row block is 16 RT packed rows -- RT 16-row
 //     tiles per wave; decode is RT = 1.  One K fragment and one transposed V read per d group feed RT MFMAs: the cache is read once
 //     per 16 RT rows, which is the point of the chunked-prefill call.  The per-row state (Q fragments, m, l, O^T, the mask limits,
@@ -200,10 +212,10 @@ __device__ __forceinline__ bool varlen_unit_of(const VarlenDecodeParams& p, int 
     return false;
 }
 
-// Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false; ragged chunked prefill: that with VARLEN.
+// Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false (windowSize = 0) or true (the _window calls);
+// ragged chunked prefill: those with VARLEN.
 template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false>
 __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN>::type p) {
-    static_assert(!VARLEN || !WINDOW, "the ragged form has no window");
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
@@ -240,8 +252,17 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
     const int nrows = p.G * Sq, pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
     const int gl = prl / Sq, qmax = pr0 / Sq != gl ? Sq - 1 : prl - gl * Sq;
     const int limb = RT > 1 && p.causal ? max(len - Sq + qmax + 1, 1) : len;
+    // the lowest key a row of THIS BLOCK sees: the lower bound of its smallest query row -- row 0 if the block reaches into the next
+    // head, else its first row's.  RT = 1, no window, or Sq <= FA_DECODE_MAX_Q (the decode seam: the range stays decode's): `first`
+    int firstb = first;
+    if constexpr (RT > 1 && WINDOW) {
+        if (p.window > 0 && Sq > FA_DECODE_MAX_Q) {
+            const int g0 = pr0 / Sq, qmin = g0 != gl ? 0 : pr0 - g0 * Sq;
+            firstb = max(max(len - Sq + qmin + 1, 1) - p.window, 0);
+        }
+    }
     // this block's tiles [tlo, ntb), divided over the splits in whole tiles
-    const int ntb = (limb + C::TILE - 1) / C::TILE, tlo = first / C::TILE;
+    const int ntb = (limb + C::TILE - 1) / C::TILE, tlo = firstb / C::TILE;
     const int t0 = tlo + (int)(((int64_t)(ntb - tlo) * split) / p.ns), t1 = tlo + (int)(((int64_t)(ntb - tlo) * (split + 1)) / p.ns);
 
     // this lane's packed rows (column r of the swapped products, tile rt): query head g of the group, query row i.  The keys the row
@@ -590,6 +611,14 @@ Kernel extend_varlen_split_kernel_of(int d);
 Kernel extend_varlen_paged_split_kernel_of(int d);
 Kernel extend_varlen_fp8_split_kernel_of(int d);
 Kernel extend_varlen_paged_fp8_split_kernel_of(int d);
+Kernel extend_window_split_kernel_of(int d);
+Kernel extend_window_paged_split_kernel_of(int d);
+Kernel extend_window_fp8_split_kernel_of(int d);
+Kernel extend_window_paged_fp8_split_kernel_of(int d);
+Kernel extend_window_varlen_split_kernel_of(int d);
+Kernel extend_window_varlen_paged_split_kernel_of(int d);
+Kernel extend_window_varlen_fp8_split_kernel_of(int d);
+Kernel extend_window_varlen_paged_fp8_split_kernel_of(int d);
 Kernel extend_varlen_combine_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 

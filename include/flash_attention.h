@@ -665,8 +665,8 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
  *            caveat on V; e4m3fn -> bf16 exactly, in registers, kDescale folded into the score scale and vDescale into the final 1 / l
  * Rejected before any launch: everything the decode sibling of the same form and kv_dtype rejects, with the same codes, except the
  * FA_DECODE_MAX_Q cap; seqLenQ > capacity FA_ERR_BAD_SHAPE; a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE.
- * Not done here: sliding windows, attention sinks, fp8 Q, a backward, automatic routing from or to any existing call.  A per-sequence
- * count of new rows is flash_attention_extend_varlen's (below): here every sequence brings seqLenQ rows.
+ * Not done here: attention sinks, fp8 Q, a backward, automatic routing from or to any existing call.  A per-sequence count of new rows
+ * is flash_attention_extend_varlen's (below): here every sequence brings seqLenQ rows.  A sliding window is the _window calls' (below).
  */
 int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
                                 int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
@@ -733,7 +733,8 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
  * Rejected before any launch: everything flash_attention_extend* of the same form rejects, with the same codes and in the same order,
  * except its seqLenQ > capacity; a NULL cuSeqlensQ FA_ERR_NULL_POINTER; one not aligned to 4 bytes FA_ERR_MISALIGNED; totalQ < 1,
  * batchSize > FA_VARLEN_MAX_BATCH and the int32 limits FA_ERR_BAD_SHAPE.
- * Not done here: sliding windows, a per-unit choice of rows_per_block, reordering units by length, attention sinks, fp8 Q, routing.
+ * Not done here: a per-unit choice of rows_per_block, reordering units by length, attention sinks, fp8 Q, routing.  A sliding window
+ * is the _window calls' (below).
  */
 #define FA_VARLEN_MAX_BATCH 1024    /* sequences per ragged call: the unit lookup scans them 64 at a time, 16 steps at the most */
 
@@ -756,6 +757,95 @@ int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const 
                                         float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
                                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                         void* stream);
+
+/*
+ * flash_attention_extend_window, flash_attention_extend_paged_window, flash_attention_extend_varlen_window,
+ * flash_attention_extend_paged_varlen_window -- chunked prefill and the ragged call with a SLIDING WINDOW: the window of
+ * flash_attention_decode_window on every member of the split-KV family, so that a sliding-window model (Mistral, Gemma, the local
+ * layers of gpt-oss) prefills a chunk against the cache and runs the mixed decode + prefill step with this library.  Each call takes
+ * its sibling's argument list (flash_attention_extend, _extend_paged, _extend_varlen, _extend_paged_varlen) with windowSize directly
+ * after numSplits, as the decode _window calls do, and serves all four cache forms.  Everything not named here is the sibling's.
+ *
+ * Mask (decode's, unchanged).  Per sequence, with len = clamp(kvLens[b], 1, capacity) and Sq the sequence's row count (seqLenQ, or
+ * sq_b from cuSeqlensQ): limC_i = max(len - Sq + i + 1, 1), lo_i = max(limC_i - windowSize, 0); row i sees lo_i <= k < limC_i with
+ * is_causal and lo_i <= k < len without.  Every row sees a key.  windowSize = 0 IS the sibling call: the same launches (the sibling's
+ * kernels) and the same bits.  windowSize >= capacity masks nothing and gives the sibling's bits as well.
+ *
+ * Below the window.  first(b) = lo_0.  Keys below first(b) never enter the result and may hold NaN, inf, stale data or any fp8 byte;
+ * paged: a page wholly below first(b) is never read and neither is its blockTable entry, which may be any int32.  Keys in
+ * [first(b), len) are data: a key one row block does not see is one another reads.
+ *
+ * Tiles: a range PER ROW BLOCK.  A row block (plan.rows_per_block packed rows g * Sq + i of one K/V head, not head-aligned) whose
+ * rows are the query rows qmin .. qmax of the chunk walks the 128-key tiles [tlo_b, ntb): ntb as in the sibling (the block's largest
+ * limit), tlo_b = firstb / 128 with firstb = max(max(len - Sq + qmin + 1, 1) - windowSize, 0), and qmin = 0 when the block reaches
+ * into the next head, else the query row of its first packed row.  For Sq > FA_DECODE_MAX_Q that is exactly the hull of the tiles
+ * that hold a key some row of the block sees: a long windowed chunk reads about windowSize + rows_per_block keys per block, not the
+ * whole prefix.  The block's tiles are divided over numSplits by decode's formula (split s takes
+ * [tlo_b + (ntb - tlo_b) s / ns, tlo_b + (ntb - tlo_b) (s + 1) / ns)); a split past the end comes out empty.
+ *   Sq <= FA_DECODE_MAX_Q: qmin = 0 for every block -- the range is decode's [first(b) / 128, ntb), so flash_attention_extend_window is
+ *   flash_attention_decode_window of the same arguments and the same forced numSplits, bit for bit (O and LSE).
+ * Known cost: row blocks are not head-aligned.  A block that straddles two heads of a long windowed chunk holds rows 0 and Sq - 1 and
+ * walks from lo_0 to len, the whole chunk's span.  That happens only when G * Sq is no multiple of rows_per_block (for a chunk longer
+ * than a block: when Sq is none).
+ *
+ * Seams, bit for bit (O and LSE, under the same forced numSplits): the paged calls equal the contiguous ones on a contiguous copy of
+ * the same pages; sequence b of a ragged call equals flash_attention_extend*_window on that sequence alone (batchSize = 1, seqLenQ =
+ * sq_b), and for sq_b <= FA_DECODE_MAX_Q flash_attention_decode*_window; rows no sequence owns are not written.
+ *
+ * Plan.  flash_attention_extend_plan_window / flash_attention_extend_varlen_plan_window: the sibling's plan with tiles = min(the
+ * capacity's tiles, ceil((windowSize + Sq - 1) / 128) + 1), Sq = seqLenQ or totalQ, as in flash_attention_decode_plan_window; the
+ * split count follows by flash_attention_extend_plan's unchanged rule and constants.  That rule is NOT measured for windowed chunks
+ * (DESIGN.md section 22).  flash_attention_extend_plan and flash_attention_extend_varlen_plan are these with windowSize = 0;
+ * windowSize >= seqLenK plans as no window does.  rows_per_block is the sibling's.  The workspace functions are unchanged.
+ *
+ * Rejected before any launch: everything the sibling rejects, with the same codes and in the same order; windowSize < 0
+ * FA_ERR_BAD_SHAPE.
+ * Not done here: attention sinks, a right window, per-head windows, ring-buffer caches, windows in the prefill / backward kernels.
+ */
+int flash_attention_extend_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                       int o_dtype, int numSplits /* 0 = the library chooses */, int windowSize,
+                                       fa_decode_plan* plan);
+
+int flash_attention_extend_varlen_plan_window(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                              int o_dtype, int numSplits /* 0 = the library chooses */, int windowSize,
+                                              fa_decode_plan* plan);
+
+int flash_attention_extend_window(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace,
+                                  int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                  float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                  int windowSize,
+                                  const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                  void* stream);
+
+int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace,
+                                        int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                        int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                        float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                        int windowSize,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream);
+
+int flash_attention_extend_varlen_window(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                         const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                         const float* kDescale, const float* vDescale, void* workspace,
+                                         int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                         float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                         int windowSize,
+                                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                         void* stream);
+
+int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                               const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                               const float* kDescale, const float* vDescale, void* workspace,
+                                               int batchSize, int numHeads, int numHeadsKV, int totalQ,
+                                               int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                               float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype,
+                                               int numSplits, int windowSize,
+                                               const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                               void* stream);
 
 /*
  * flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen -- the RAGGED cache append: flash_attention_kv_append /

@@ -75,6 +75,13 @@ Each line:
                                 call per group on pre-grouped new rows
               each with _min / _max over the windows (profiles/extend_varlen_bench.log).  With --splits: the
               forced sweep of the ragged call on the bf16 cache, one line per (shape, split count).
+--window with --extend / --varlen   the windowed calls (flash_attention_extend*_window, flash_attention_extend*_varlen_window)
+              beside the un-windowed call of the same shape in the same run: per cache form, extend_window_ms[W] / varlen_window_ms[W]
+              with their _min / _max and window_splits[W] (the window's plan) next to extend_ms / varlen_ms; the comparison routes
+              (sliced decode, prefill pair, grouped calls, appends) are not timed.  --extend --window adds two shapes, B1 behind a
+              32 k prefix: chunk1024_32k (Sq a multiple of rows_per_block) and chunk1000_32k (it is not: the row blocks that straddle
+              two heads walk the whole chunk's span).  With --splits: the forced sweep, one line per (shape, split count) with
+              extend_ms / varlen_ms and the windowed times at that count (profiles/extend_window_bench.log).
 """
 import argparse
 import json
@@ -123,17 +130,23 @@ EXTEND_SHAPES = [  # name, B, H, Hkv, Sq, prefixes, d
     ("batch8_ragged", 8, 32, 8, 512, [1024 + (32768 - 1024) * b // 7 for b in range(8)], 128),
     ("d64_chunk512_8k", 1, 32, 8, 512, [8192], 64),
 ]
+# with --window (or when named): a long chunk whose length is, and one whose length is not, a multiple of rows_per_block
+EXTEND_WINDOW_SHAPES = [
+    ("chunk1024_32k", 1, 32, 8, 1024, [32768], 128),
+    ("chunk1000_32k", 1, 32, 8, 1000, [32768], 128),
+]
 
 
 def extend_main(args, fa, dev):
     import torch
     f8 = torch.float8_e4m3fn
-    shapes = EXTEND_SHAPES
+    wins = [int(x) for x in (args.window or "").split(",") if x]
+    shapes = EXTEND_SHAPES + (EXTEND_WINDOW_SHAPES if wins else [])
     if args.shape:
-        unknown = set(args.shape) - {x[0] for x in EXTEND_SHAPES}
+        unknown = set(args.shape) - {x[0] for x in EXTEND_SHAPES + EXTEND_WINDOW_SHAPES}
         if unknown:
             raise SystemExit(f"unknown --extend shape(s): {sorted(unknown)}")
-        shapes = [x for x in EXTEND_SHAPES if x[0] in args.shape]
+        shapes = [x for x in EXTEND_SHAPES + EXTEND_WINDOW_SHAPES if x[0] in args.shape]
     windows = lambda call, steps=None: sorted(timed(call, steps or args.steps, args.warmup) for _ in range(args.repeats))
     stats = lambda key, v: {key: round(statistics.median(v), 5), key + "_min": round(v[0], 5), key + "_max": round(v[-1], 5)}
     primed = False
@@ -148,12 +161,26 @@ def extend_main(args, fa, dev):
         base = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "Sq": Sq, "prefix": prefixes if B > 1 else prefixes[0], "capacity": Sk, "d": d,
                 "io": "bfloat16", "repeats": args.repeats, "steps": args.steps}
 
-        def extend_call(Kc, Vc, table, kw, ns=0):
-            plan = fa.extend_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, ns)
+        def extend_call(Kc, Vc, table, kw, ns=0, W=0):
+            plan = fa.extend_plan(B, H, Hkv, Sq, Sk, d, fa.FA_DTYPE_BF16, ns, window=W)
             ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            kw = dict(kw, window=W) if W else kw
+            front, paged = (fa.flash_attention_extend_window, fa.flash_attention_extend_paged_window) if W else (
+                fa.flash_attention_extend, fa.flash_attention_extend_paged)
             if table is None:
-                return plan, lambda: fa.flash_attention_extend(Q, Kc, Vc, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
-            return plan, lambda: fa.flash_attention_extend_paged(Q, Kc, Vc, table, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+                return plan, lambda: front(Q, Kc, Vc, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+            return plan, lambda: paged(Q, Kc, Vc, table, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+
+        def windowed(call_of, key):
+            """{key_ms: {W: median}, key_ms_min / _max, window_splits}: the windowed call per --window value"""
+            out = {key + "_ms": {}, key + "_ms_min": {}, key + "_ms_max": {}, "window_splits": {}}
+            for W in wins:
+                plan, call = call_of(W)
+                v = windows(call)
+                out[key + "_ms"][str(W)], out[key + "_ms_min"][str(W)], out[key + "_ms_max"][str(W)] = (
+                    round(statistics.median(v), 5), round(v[0], 5), round(v[-1], 5))
+                out["window_splits"][str(W)] = plan["num_splits"]
+            return out
 
         def prime(call):
             nonlocal primed
@@ -169,7 +196,11 @@ def extend_main(args, fa, dev):
                     continue
                 plan, call = extend_call(K, V, None, {}, ns)
                 prime(call)
-                print(json.dumps(dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("extend_ms", windows(call)))), flush=True)
+                line = dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("extend_ms", windows(call)))
+                if wins:
+                    line.update(windowed(lambda W: extend_call(K, V, None, {}, ns, W), "extend_window"))
+                    del line["window_splits"]
+                print(json.dumps(line), flush=True)
             del Q, K, V, O
             torch.cuda.empty_cache()
             continue
@@ -235,14 +266,19 @@ def extend_main(args, fa, dev):
                 Kc, Vc = pools
                 tl = table.long()
                 gather = lambda: [P.view(torch.uint8 if fp8 else P.dtype)[tl].permute(0, 2, 1, 3, 4).reshape(B, Hkv, Sk, d) for P in (Kc, Vc)]
-                line.update(stats("gather_ms", windows(gather, max(10, args.steps // 10))))
-            if fp8:
+                if not wins:
+                    line.update(stats("gather_ms", windows(gather, max(10, args.steps // 10))))
+            if fp8 and not wins:
                 deq = lambda: [(T.to(torch.bfloat16) * ds[None, :, None, None].to(torch.bfloat16)) for T, ds in ((K8, kds), (V8, vds))]
                 line.update(stats("dequantise_ms", windows(deq, max(10, args.steps // 10))))
             plan, call = extend_call(Kc, Vc, table, kw)
             prime(call)
             line.update(stats("extend_ms", windows(call)))
             line.update(splits=plan["num_splits"], row_blocks=plan["row_blocks"], rows_per_block=plan["rows_per_block"], grid=plan["grid"])
+            if wins:   # the windowed call beside the un-windowed one; the comparison routes are not timed
+                line.update(windowed(lambda W: extend_call(Kc, Vc, table, kw, 0, W), "extend_window"))
+                print(json.dumps(line), flush=True)
+                continue
             Os, scall = sliced_call(Kc, Vc, table, kw)
             line.update(stats("sliced_decode_ms", windows(scall, max(3, args.steps // 20))))
             line["extend_vs_sliced_max_abs"] = round((O.float() - Os.float()).abs().max().item(), 6)
@@ -277,6 +313,7 @@ def varlen_main(args, fa, dev):
     import torch
     f8 = torch.float8_e4m3fn
     H, Hkv = 32, 8
+    wins = [int(x) for x in (args.window or "").split(",") if x]
     shapes = varlen_shapes()
     if args.shape:
         unknown = set(args.shape) - {x[0] for x in shapes}
@@ -310,13 +347,15 @@ def varlen_main(args, fa, dev):
         base = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "d": d, "totalQ": T, "rows": sq if len(set(sq)) > 1 else sq[0],
                 "kv_len_min": min(lens), "kv_len_max": max(lens), "capacity": Sk, "io": "bfloat16", "repeats": args.repeats, "steps": args.steps}
 
-        def varlen_call(Kc, Vc, table, kw, ns=0):
-            plan = fa.extend_varlen_plan(B, H, Hkv, T, Sk, d, fa.FA_DTYPE_BF16, ns)
+        def varlen_call(Kc, Vc, table, kw, ns=0, W=0):
+            plan = fa.extend_varlen_plan(B, H, Hkv, T, Sk, d, fa.FA_DTYPE_BF16, ns, window=W)
             ws = torch.empty(max(fa.decode_workspace_size(1, H, T, d, plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            kw = dict(kw, window=W) if W else kw
+            front, paged = (fa.flash_attention_extend_varlen_window, fa.flash_attention_extend_paged_varlen_window) if W else (
+                fa.flash_attention_extend_varlen, fa.flash_attention_extend_paged_varlen)
             if table is None:
-                return plan, lambda: fa.flash_attention_extend_varlen(Q, Kc, Vc, cu_d, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
-            return plan, lambda: fa.flash_attention_extend_paged_varlen(Q, Kc, Vc, table, cu_d, lens_d, is_causal=True, O=O, workspace=ws,
-                                                                        num_splits=ns, **kw)
+                return plan, lambda: front(Q, Kc, Vc, cu_d, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
+            return plan, lambda: paged(Q, Kc, Vc, table, cu_d, lens_d, is_causal=True, O=O, workspace=ws, num_splits=ns, **kw)
 
         def prime(call):
             nonlocal primed
@@ -326,13 +365,28 @@ def varlen_main(args, fa, dev):
                     t += timed(call, 20, 0) * 20
                 primed = True
 
+        def windowed(call_of, key):
+            """{key_ms: {W: median}, key_ms_min / _max, window_splits}: the windowed call per --window value"""
+            out = {key + "_ms": {}, key + "_ms_min": {}, key + "_ms_max": {}, "window_splits": {}}
+            for W in wins:
+                plan, call = call_of(W)
+                v = windows(call)
+                out[key + "_ms"][str(W)], out[key + "_ms_min"][str(W)], out[key + "_ms_max"][str(W)] = (
+                    round(statistics.median(v), 5), round(v[0], 5), round(v[-1], 5))
+                out["window_splits"][str(W)] = plan["num_splits"]
+            return out
+
         if args.splits:
             for ns in [int(x) for x in args.splits.split(",")]:
                 if ns > -(-Sk // 128):
                     continue
                 plan, call = varlen_call(K, V, None, {}, ns)
                 prime(call)
-                print(json.dumps(dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("varlen_ms", windows(call)))), flush=True)
+                line = dict({"shape": name, "forced_splits": ns, "grid": plan["grid"]}, **stats("varlen_ms", windows(call)))
+                if wins:
+                    line.update(windowed(lambda W: varlen_call(K, V, None, {}, ns, W), "varlen_window"))
+                    del line["window_splits"]
+                print(json.dumps(line), flush=True)
             del Q, K, V, O, Kn, Vn
             torch.cuda.empty_cache()
             continue
@@ -392,8 +446,11 @@ def varlen_main(args, fa, dev):
                     T8[b] = (Tn[b].float() / ds[:, None, None]).clamp(-448, 448).to(f8)
                 return T8, ds
             (K8, kds), (V8, vds) = quant(K), quant(V)
-        Qg, Og, rcall = regroup_calls()
-        regroup = stats("regroup_ms", windows(rcall))
+        if not wins:
+            Qg, Og, rcall = regroup_calls()
+            regroup = stats("regroup_ms", windows(rcall))
+        else:
+            Qg = Og = None
         for form, fp8, page in forms:
             Kc, Vc, table = (K8, V8, None) if fp8 else (K, V, None)
             kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
@@ -414,6 +471,10 @@ def varlen_main(args, fa, dev):
             line.update(stats("varlen_ms", windows(call)))
             line.update(splits=plan["num_splits"], row_blocks_bound=plan["row_blocks"], rows_per_block=plan["rows_per_block"], grid=plan["grid"],
                         row_blocks_real=sum(-(-(H // Hkv) * r // plan["rows_per_block"]) for r in sq))
+            if wins:   # the windowed call beside the un-windowed one; the comparison routes are not timed
+                line.update(windowed(lambda W: varlen_call(Kc, Vc, table, kw, 0, W), "varlen_window"))
+                print(json.dumps(line), flush=True)
+                continue
             gcall = grouped_call(Qg, Og, Kc, Vc, table, kw)
             line.update(stats("grouped_ms", windows(gcall)))
             line["grouped_calls"] = len(groups)

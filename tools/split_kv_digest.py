@@ -22,6 +22,11 @@ and its digest is fed, in this order, by the 24 calls of
   out      f32, bf16
   lengths  (1, 300), (129, 300)
 so that the log stays small enough to commit (416 lines); a line that differs names the case to take apart.
+
+After those, in a second pass over d (so that the lines above keep their content and order):
+  extend   with window 7, 130: the cases above with the windowed call (flash_attention_extend*_window(window=W)), 256 lines
+  varlen   the ragged call on token-packed Q, both sequences with rows of their own -- rows (5, 130) and (17, 40) -- G, causal,
+           splits, kv as above, window 0, 7, 130; the same 24 calls per line, 192 lines
 """
 import hashlib
 import itertools
@@ -44,7 +49,7 @@ def main():
     lens_d = [torch.tensor(v, dtype=torch.int32).to(dev) for v in LENS]
     kds, vds = torch.tensor([0.75, 1.5]), torch.tensor([1.25, 0.5])
 
-    for d in (64, 128):
+    def caches_of(d):
         g = torch.Generator().manual_seed(1000 + d)
         K, V = (torch.randn(B, HKV, CAP, d, generator=g).to(torch.bfloat16) for _ in range(2))
         # the cache forms of this d: name -> (K, V, block table or None, descales or None), all on the device
@@ -69,7 +74,10 @@ def main():
                 table = perm.reshape(B, n).to(torch.int32).to(dev)
                 caches[f"paged{page}", kv] = (pools[0].to(dev), pools[1].to(dev), table, desc)
                 caches[f"paged{page}+s", kv] = (strided(pools[0]), strided(pools[1]), table, desc)
-        for call, sqs, windows in (("decode", (1, 5, 16), (0, 7, 130)), ("extend", (5, 17, 40, 130), (0,))):
+        return caches
+
+    def uniform(d, caches, cases):
+        for call, sqs, windows in cases:
             for G, Sq in itertools.product((1, 4), sqs):
                 gq = torch.Generator().manual_seed(7 * d + 1000 * G + Sq)
                 Q = torch.randn(B, HKV * G, Sq, d, generator=gq).to(torch.bfloat16).to(dev)
@@ -78,15 +86,42 @@ def main():
                     for form, out, L in itertools.product([f for f, k in caches if k == kv], (torch.float32, torch.bfloat16), lens_d):
                         Kc, Vc, table, desc = caches[form, kv]
                         kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out)
-                        if call == "decode":
+                        if call == "decode" or W:
                             kw["window"] = W
+                        win = "_window" if call == "extend" and W else ""     # (the extend fronts take a window under a name of their own)
                         if table is None:
-                            O, lse = getattr(fa, "flash_attention_" + call)(Q, Kc, Vc, L, **kw)
+                            O, lse = getattr(fa, f"flash_attention_{call}{win}")(Q, Kc, Vc, L, **kw)
                         else:
-                            O, lse = getattr(fa, f"flash_attention_{call}_paged")(Q, Kc, Vc, table, L, **kw)
+                            O, lse = getattr(fa, f"flash_attention_{call}_paged{win}")(Q, Kc, Vc, table, L, **kw)
                         h.update(O.cpu().view(torch.uint8).numpy().tobytes())
                         h.update(lse.cpu().numpy().tobytes())
                     print(f"{call} d{d} G{G} Sq{Sq} causal{causal} splits{ns} window{W} {kv} {h.hexdigest()}", flush=False)
+
+    def ragged(d, caches):
+        for G, sq in itertools.product((1, 4), ((5, 130), (17, 40))):
+            gq = torch.Generator().manual_seed(7 * d + 1000 * G + sum(sq))
+            Q = torch.randn(sum(sq), HKV * G, d, generator=gq).to(torch.bfloat16).to(dev)
+            cu = torch.tensor([0, sq[0], sum(sq)], dtype=torch.int32).to(dev)
+            for causal, ns, W, kv in itertools.product((0, 1), (1, 3), (0, 7, 130), ("bf16", "fp8")):
+                h = hashlib.sha256()
+                for form, out, L in itertools.product([f for f, k in caches if k == kv], (torch.float32, torch.bfloat16), lens_d):
+                    Kc, Vc, table, desc = caches[form, kv]
+                    kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out, **(dict(window=W) if W else {}))
+                    if table is None:
+                        O, lse = (fa.flash_attention_extend_varlen_window if W else fa.flash_attention_extend_varlen)(Q, Kc, Vc, cu, L, **kw)
+                    else:
+                        O, lse = (fa.flash_attention_extend_paged_varlen_window if W else fa.flash_attention_extend_paged_varlen)(
+                            Q, Kc, Vc, table, cu, L, **kw)
+                    h.update(O.cpu().view(torch.uint8).numpy().tobytes())
+                    h.update(lse.cpu().numpy().tobytes())
+                print(f"varlen d{d} G{G} rows{sq[0]}+{sq[1]} causal{causal} splits{ns} window{W} {kv} {h.hexdigest()}", flush=False)
+
+    for d in (64, 128):
+        uniform(d, caches_of(d), (("decode", (1, 5, 16), (0, 7, 130)), ("extend", (5, 17, 40, 130), (0,))))
+    for d in (64, 128):
+        caches = caches_of(d)
+        uniform(d, caches, (("extend", (5, 17, 40, 130), (7, 130)),))
+        ragged(d, caches)
     sys.stdout.flush()
 
 
