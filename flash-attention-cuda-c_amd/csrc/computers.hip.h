@@ -123,6 +123,8 @@ struct WaveCompute : SlotEngine<WaveCompute<C>, C> {
     }
 
     // S^T = K.Q^T for all row groups, compiler-scheduled: used once per pass for tile 0.
+    // (Reading the K fragments NPRE ahead, as the tile step does, turns the sixteen lgkmcnt(0) of this stretch into counted waits and
+    // measures nothing: profiles/ARMS_seam.md, seam_qk0_prefetch_arm.patch.)
     template <int I = 0>
     __device__ __forceinline__ void qk_all(lds_ptr kimg, int kbase, Scores<R>& n) {
         if constexpr (I == 0) zero(n);

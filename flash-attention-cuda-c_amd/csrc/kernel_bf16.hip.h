@@ -46,6 +46,9 @@ struct Opt {
                                  // on v_mfma_f32_16x16x32_f16 (needs |V| <= 65504): FA_FLAG_F16_WEIGHTS, and by default the query blocks whose rows see few keys
     bool mix = false;            // 32x32x16 engine, LDS-DMA kernels: the units of the query blocks qb < Params::hp run with fp16 softmax weights (V staged
                                  // as fp16 through registers: MixStage), the others with bf16 weights, in list order inside ONE walk: the causal default
+    // switches of the unit seam, each -1 = the library's choice, 0 / 1 = forced off / on (tests/fa_tune_seam.hip times them against each other)
+    int kv_clamp = -1;           // KernelCfg::KV_CLAMP
+    int q_nt = -1;               // KernelCfg::Q_CACHE: non-temporal Q loads
 };
 
 template <int D_, bool CAUSAL_, typename OutT_, int ESZ_ = 2, Opt O = Opt{}>
@@ -65,6 +68,23 @@ struct KernelCfg {
     // re-read (causal, fp32 O: plain 1058, sc1 1073, nt 1076, sc0 sc1 1076 TFLOP/s; bf16 O +0.5 %; without the mask -0.3 %:
     // profiles/r03_tune_d_output_store_policy_*.log)
     static constexpr int O_CACHE = CAUSAL_ ? 2 : 0;
+    // Cache policy of the Q loads (utils.hip.h: load_global_b128; slot_engine.hip.h: load_q, load_q_rows): every Q byte is read exactly
+    // once, through the same L2 that holds the K/V its heads re-read.  2 = non-temporal, under the mask.  What it rests on
+    // (profiles/ARMS_seam.md has every run): the HBM reads of a launch fall by 35 ... 46 MB in all three collections, together with
+    // KV_CLAMP; in time the two switches together give +2.0 % on bench.py alternated with the parent's library on the committed tree
+    // (profiles/seam_ab_cfg2.log).  Alone, interleaved in one process, it measured +1.2 % in the first session (an earlier build, arms
+    // not in this tree: profiles/seam_tune_pieces_cfg2.log -- the result relied on) and did not resolve in the two later runs.
+    // Without the mask three runs gave -1 %, +0.5 % and +1.5 %: not shown faster, stays plain
+    static constexpr int Q_CACHE = (O.q_nt < 0 ? CAUSAL_ : O.q_nt != 0) ? 2 : 0;
+    // Under the mask a unit's K/V buffer descriptors end at its diagonal (run_units: kv_rows): the tiles past it, which the ring's
+    // look-ahead stages and no wave reads, fail the range check and arrive as zeros without a memory access.  No value of such a
+    // tile reaches m, l or O in any pass: a wave's QK^T on a tile >= its my_tiles runs in a kind-1 step only (has_next = false:
+    // tile_step then skips the mask, the decision's use and the rescale; max3_slot / decide write mx_a, mx_b and need, which
+    // begin_tile and the next decide overwrite before anything reads them), and P.V of such a tile is never issued.  5.6 % of the
+    // L2 -> LDS bytes of the causal headline shape.  Alone it measured +0.65 % in the first session (same log, the result relied on) and
+    // did not resolve in the two later runs; with Q_CACHE: see there.
+    // (The unit decode's divisions as multiply and shift with host constants: measured, not adopted -- profiles/seam_fastdiv_arm.patch)
+    static constexpr bool KV_CLAMP = CAUSAL_ && O.kv_clamp != 0;
     // Q rows fetched whole and turned into fragments through LDS (q_rows_to_fragments): on at d = 128 (+0.8 %), off at d = 64
     // (the 37 us cfg1 loses 1.8 % to the extra LDS trip)
     static constexpr bool COALESCED_Q = D_ == 128 && !O.pad;
@@ -276,6 +296,8 @@ struct UnitCtx {
         wave_live = q_row0 < p.S;
         my_tiles = !wave_live ? 0 : (C::CAUSAL ? min(n_tiles, (q_row0 + WROWS - 1) / KVBLK + 1) : n_tiles);
     }
+    // rows of K and V the unit's buffer descriptors cover: all, or (KernelCfg::KV_CLAMP) those of the tiles up to its diagonal
+    __device__ __forceinline__ int kv_rows(int Sk) const { return C::KV_CLAMP ? min(Sk, 64 * n_tiles) : Sk; }
 };
 
 // The passes of one unit, each the fallback of the one before; tile 0 is in flight for the first only.
@@ -328,7 +350,7 @@ __device__ __forceinline__ void run_units(const Params& p, const UnitList& L, ld
     WaveComputeOf<C> w;
     typename WaveComputeOf<C>::Stage st;
     const int row_bytes = C::PAD ? p.d * ESZ : D * ESZ, orow_bytes = C::PAD ? p.d * (int)sizeof(OutT) : D * (int)sizeof(OutT);
-    st.init(cur.Kh, cur.Vh, kSb, vSb, Sk, wave, lane, row_bytes);
+    st.init(cur.Kh, cur.Vh, kSb, vSb, cur.kv_rows(Sk), wave, lane, row_bytes);
     // tile 0 and Q travel together (one HBM round trip); tile 0 in the form the unit's first pass takes it (C::MIX: wave-uniform branch)
     if (C::MIX ? cur.early : C::P_F16) st.template load_all_into<true>(0, smem);
     else st.template load_all_into<false>(0, smem);
@@ -376,7 +398,7 @@ __device__ __forceinline__ void run_units(const Params& p, const UnitList& L, ld
         const bool more = next_unit<C, KIND>(L, round, g, qb);
         if (more) {
             nxt.set(p, g, qb, wave);
-            st.init(nxt.Kh, nxt.Vh, kSb, vSb, Sk, wave, lane, row_bytes);
+            st.init(nxt.Kh, nxt.Vh, kSb, vSb, nxt.kv_rows(Sk), wave, lane, row_bytes);
             if (C::MIX ? nxt.early : C::P_F16) st.template load_all_into<true>(0, smem);   // (V in registers across the epilogue)
             else st.template load_all_into<false>(0, smem);
             // (opaque lane: a hoisted per-lane Q address is spilled across the tile loop, and its reload's vmcnt(0)

@@ -75,9 +75,9 @@ struct SlotEngine {
             for (int u = 0; u < W::FPG; ++u) {
                 if constexpr (C::PAD) {
                     w.qf[g][u] = u32x4{0u, 0u, 0u, 0u};
-                    if (u * FSTRIDE + (lane >> W::LOG_RG) * 16 < row_bytes) w.qf[g][u] = *reinterpret_cast<const u32x4*>(src + u * FSTRIDE);
+                    if (u * FSTRIDE + (lane >> W::LOG_RG) * 16 < row_bytes) w.qf[g][u] = load_global_b128<C::Q_CACHE>(src + u * FSTRIDE);
                 } else {
-                    w.qf[g][u] = *reinterpret_cast<const u32x4*>(src + u * FSTRIDE);
+                    w.qf[g][u] = load_global_b128<C::Q_CACHE>(src + u * FSTRIDE);
                 }
             }
         }
@@ -94,7 +94,7 @@ struct SlotEngine {
         for (int i = 0; i < W::GROUPS * W::FPG; ++i) {
             int row = row0 + i * QRPI + lane / QCH;
             row = row < S ? row : S - 1;
-            self().qf[i / W::FPG][i % W::FPG] = *reinterpret_cast<const u32x4*>(Qh + row * qS_bytes + (lane % QCH) * 16);
+            self().qf[i / W::FPG][i % W::FPG] = load_global_b128<C::Q_CACHE>(Qh + row * qS_bytes + (lane % QCH) * 16);
         }
     }
     // region: 32 rows x D*ESZ bytes private to this wave, not aliased by anything live (kernel_bf16.hip.h)

@@ -90,6 +90,15 @@ __device__ __forceinline__ void store_global_b128(void* p, u32x4 v) {
     else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// 16-byte global load with a cache policy (KernelCfg::Q_CACHE): 0 plain; 2 nt (a line that is read once: it should not push
+// lines out of the XCD's L2 that are about to be re-read).  A load hipcc keeps count of, like the plain one.
+template <int POLICY>
+__device__ __forceinline__ u32x4 load_global_b128(const void* p) {
+    static_assert(POLICY == 0 || POLICY == 2, "load policies: plain or nt");
+    if constexpr (POLICY == 0) return *reinterpret_cast<const u32x4*>(p);
+    else return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+}
+
 // ---- cross-half exchange: value of lane l^32 ---------------------------------------------------
 __device__ __forceinline__ float other_half(float x) {
     // v_permlane32_swap vdst, src swaps vdst[32..63] with src[0..31]; with both = x the pair
