@@ -70,6 +70,24 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_extend_varlen_plan_window",
            "flash_attention_error_string", "flash_attention_version")
 
+# The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
+# point and an ``_fp8`` twin; every extend entry point takes both cache types, and so does every ``_window`` one.
+_SPLIT_SYMBOLS = {
+    ("decode", False, False): (("flash_attention_decode", "flash_attention_decode_fp8"), ("flash_attention_decode_window",) * 2),
+    ("decode", True, False): (("flash_attention_decode_paged", "flash_attention_decode_paged_fp8"),
+                              ("flash_attention_decode_paged_window",) * 2),
+    ("extend", False, False): (("flash_attention_extend",) * 2, ("flash_attention_extend_window",) * 2),
+    ("extend", True, False): (("flash_attention_extend_paged",) * 2, ("flash_attention_extend_paged_window",) * 2),
+    ("extend", False, True): (("flash_attention_extend_varlen",) * 2, ("flash_attention_extend_varlen_window",) * 2),
+    ("extend", True, True): (("flash_attention_extend_paged_varlen",) * 2, ("flash_attention_extend_paged_varlen_window",) * 2),
+}
+# ... _APPEND_SYMBOLS[paged, ragged], and the plan of a family: _PLAN_SYMBOLS[family, ragged][window > 0]
+_APPEND_SYMBOLS = {(False, False): "flash_attention_kv_append", (True, False): "flash_attention_kv_append_paged",
+                   (False, True): "flash_attention_kv_append_varlen", (True, True): "flash_attention_kv_append_paged_varlen"}
+_PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
+                 ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
+                 ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
+
 
 class FaStrides(ctypes.Structure):
     _fields_ = [("strideB", ctypes.c_int64), ("strideH", ctypes.c_int64), ("strideS", ctypes.c_int64)]
@@ -139,57 +157,29 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_backward_gqa.restype = i
         L.flash_attention_backward_workspace_size.argtypes = [i, i, i, i]
         L.flash_attention_backward_workspace_size.restype = ctypes.c_size_t
-        L.flash_attention_decode.argtypes = [vp] * 7 + [i, i, i, i, i, i, f, b, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode.restype = i
-        L.flash_attention_decode_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode_paged.restype = i
-        L.flash_attention_decode_fp8.argtypes = [vp] * 9 + [i, i, i, i, i, i, f, b, i, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode_fp8.restype = i
-        L.flash_attention_decode_paged_fp8.argtypes = [vp] * 10 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode_paged_fp8.restype = i
-        L.flash_attention_decode_window.argtypes = [vp] * 9 + [i, i, i, i, i, i, f, b, i, i, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode_window.restype = i
-        L.flash_attention_decode_paged_window.argtypes = [vp] * 10 + [i, i, i, i, i, i, i, ctypes.c_int64, i, f, b, i, i, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_decode_paged_window.restype = i
-        L.flash_attention_decode_plan_window.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
-        L.flash_attention_decode_plan_window.restype = i
-        L.flash_attention_decode_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(FaDecodePlan)]
-        L.flash_attention_decode_plan.restype = i
         L.flash_attention_decode_workspace_size.argtypes = [i, i, i, i, i]
         L.flash_attention_decode_workspace_size.restype = ctypes.c_size_t
-        L.flash_attention_kv_append.argtypes = [vp] * 7 + [i, i, i, i, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_kv_append.restype = i
-        L.flash_attention_kv_append_paged.argtypes = [vp] * 8 + [i, i, i, i, i, i, ctypes.c_int64, i, i, i] + [sp] * 4 + [vp]
-        L.flash_attention_kv_append_paged.restype = i
-        L.flash_attention_extend.argtypes = L.flash_attention_decode_fp8.argtypes
-        L.flash_attention_extend.restype = i
-        L.flash_attention_extend_paged.argtypes = L.flash_attention_decode_paged_fp8.argtypes
-        L.flash_attention_extend_paged.restype = i
-        L.flash_attention_extend_plan.argtypes = L.flash_attention_decode_plan.argtypes
-        L.flash_attention_extend_plan.restype = i
-        # the ragged calls: the uniform siblings' lists with cuSeqlensQ before kvLens (seqLenQ / seqLenNew in the place of totalQ)
-        L.flash_attention_extend_varlen.argtypes = [vp] * 10 + L.flash_attention_extend.argtypes[9:]
-        L.flash_attention_extend_varlen.restype = i
-        L.flash_attention_extend_paged_varlen.argtypes = [vp] * 11 + L.flash_attention_extend_paged.argtypes[10:]
-        L.flash_attention_extend_paged_varlen.restype = i
-        L.flash_attention_extend_varlen_plan.argtypes = L.flash_attention_extend_plan.argtypes
-        L.flash_attention_extend_varlen_plan.restype = i
-        L.flash_attention_kv_append_varlen.argtypes = [vp] * 8 + L.flash_attention_kv_append.argtypes[7:]
-        L.flash_attention_kv_append_varlen.restype = i
-        L.flash_attention_kv_append_paged_varlen.argtypes = [vp] * 9 + L.flash_attention_kv_append_paged.argtypes[8:]
-        L.flash_attention_kv_append_paged_varlen.restype = i
-        L.flash_attention_extend_window.argtypes = L.flash_attention_decode_window.argtypes
-        L.flash_attention_extend_window.restype = i
-        L.flash_attention_extend_paged_window.argtypes = L.flash_attention_decode_paged_window.argtypes
-        L.flash_attention_extend_paged_window.restype = i
-        L.flash_attention_extend_varlen_window.argtypes = [vp] * 10 + L.flash_attention_extend_window.argtypes[9:]
-        L.flash_attention_extend_varlen_window.restype = i
-        L.flash_attention_extend_paged_varlen_window.argtypes = [vp] * 11 + L.flash_attention_extend_paged_window.argtypes[10:]
-        L.flash_attention_extend_paged_varlen_window.restype = i
-        L.flash_attention_extend_plan_window.argtypes = L.flash_attention_decode_plan_window.argtypes
-        L.flash_attention_extend_plan_window.restype = i
-        L.flash_attention_extend_varlen_plan_window.argtypes = L.flash_attention_decode_plan_window.argtypes
-        L.flash_attention_extend_varlen_plan_window.restype = i
+        # the split-KV and append families, from their parts: the tensors, cuSeqlensQ (ragged) before kvLens, the block table (paged),
+        # the descales (every call but the bf16-only decode pair), then the ints with the cache geometry in the middle, kv_dtype next to
+        # dtype where there are descales, windowSize after numSplits, the strides and the stream
+        paging = lambda paged: [i, i, i, ctypes.c_int64] if paged else [i]      # numPages, pageSize, maxPagesPerSeq, tableStride / seqLenK
+        for (family, paged, ragged), by_window in _SPLIT_SYMBOLS.items():
+            for window, by_cache in enumerate(by_window):
+                for fp8, name in enumerate(by_cache):
+                    both = family == "extend" or bool(window) or bool(fp8)     # the entry point has descales and kv_dtype
+                    fn = getattr(L, name)
+                    fn.argtypes = [vp] * 5 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] * both + [vp] + [i] * 4 + paging(paged) \
+                        + [i, f, b, i] + [i] * both + [i, i] + [i] * window + [sp] * 4 + [vp]
+                    fn.restype = i
+        for (paged, ragged), name in _APPEND_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.argtypes = [vp] * 4 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, i] + [sp] * 4 + [vp]
+            fn.restype = i
+        for by_window in _PLAN_SYMBOLS.values():
+            for window, name in enumerate(by_window):
+                fn = getattr(L, name)
+                fn.argtypes = [i] * 8 + [i] * window + [ctypes.POINTER(FaDecodePlan)]
+                fn.restype = i
         L.flash_attention_error_string.argtypes = [i]
         L.flash_attention_error_string.restype = ctypes.c_char_p
         L.flash_attention_version.argtypes = []
@@ -465,27 +455,33 @@ def _window(window):
     return window
 
 
+def _split_plan(family, ragged, B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window):
+    """the filled fa_decode_plan of a call, from the family's plan entry point or (a window) its ``_window`` twin"""
+    p = FaDecodePlan()
+    window = _window(window)
+    plain, windowed = _PLAN_SYMBOLS[family, ragged]
+    if window:
+        _check(getattr(lib(), windowed)(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window, ctypes.byref(p)))
+    else:
+        _check(getattr(lib(), plain)(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
+    return p
+
+
+def _plan_dict(p):
+    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+
+
 def decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=0):
     """What a flash_attention_decode call launches (fa_decode_plan as a dict); ``num_splits`` 0 = the library's choice.  ``window``
     > 0: the call's sliding window -- the split count then follows from the window's tiles, not the capacity's."""
-    p = FaDecodePlan()
-    if _window(window):
-        _check(lib().flash_attention_decode_plan_window(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, _window(window), ctypes.byref(p)))
-    else:
-        _check(lib().flash_attention_decode_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
-    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+    return _plan_dict(_split_plan("decode", False, B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window))
 
 
 def extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=None):
     """What a flash_attention_extend call launches (fa_decode_plan as a dict; ``Sk`` the capacity); ``num_splits`` 0 = the library's
     choice.  ``rows_per_block`` packed rows ``g * Sq + i`` of one K/V head form a row block; ``decode_workspace_size`` serves unchanged.
     ``window`` > 0: the call's sliding window -- the split count then follows from the window's tiles, as in ``decode_plan``."""
-    p = FaDecodePlan()
-    if _window(window):
-        _check(lib().flash_attention_extend_plan_window(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, _window(window), ctypes.byref(p)))
-    else:
-        _check(lib().flash_attention_extend_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
-    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+    return _plan_dict(_split_plan("extend", False, B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window))
 
 
 def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=None):
@@ -493,13 +489,7 @@ def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_spl
     the capacity); ``num_splits`` 0 = the library's choice.  ``row_blocks`` is the host's BOUND on the row blocks of the whole batch,
     ``(G * total_q + B * (rows_per_block - 1)) // rows_per_block``; the workspace is ``decode_workspace_size(1, H, total_q, d, ns)``.
     ``window`` > 0: the call's sliding window (the tiles bound uses ``total_q`` for the row count)."""
-    p = FaDecodePlan()
-    if _window(window):
-        _check(lib().flash_attention_extend_varlen_plan_window(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, _window(window),
-                                                               ctypes.byref(p)))
-    else:
-        _check(lib().flash_attention_extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, ctypes.byref(p)))
-    return {k: getattr(p, k) for k, _ in FaDecodePlan._fields_}
+    return _plan_dict(_split_plan("extend", True, B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, window))
 
 
 def decode_workspace_size(B, H, Sq, d, num_splits):
@@ -549,21 +539,43 @@ def _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=None, 
     return fp8
 
 
-def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-            stream, k_descale, v_descale, window, plan=None, cu_seqlens_q=None):
-    """What flash_attention_decode and flash_attention_decode_paged share, after their own checks: ``symbol`` is the front's C entry
-    point (fp8: its ``_fp8`` twin; a window: its ``_window`` twin, which takes both cache types), ``tables`` its tensors between
-    kvLens and the workspace, ``geometry`` its ints between seqLenQ and dHead; ``decode_plan`` / ``decode_workspace_size`` are asked
-    about ``capacity``.  The extend fronts pass ``plan=extend_plan``: their entry point takes both cache types under its own name (a window, from the ``_window`` fronts: its ``_window`` twin).
-    The ragged fronts pass ``cu_seqlens_q`` (checked by them) and Q -- and O, if given -- as ``_token_view``s: Sq is then the bound
-    on the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled."""
+def _table_geometry(block_table, B):
+    """(max_pages, table_stride) of a paged front's block table, after its checks"""
     import torch
-    window = _window(window)
-    both = plan is not None or bool(window)
-    B, H, Sq, d = Q.shape
-    ragged = cu_seqlens_q is not None
+    t = block_table
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
+
+
+def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None):
+    """Every flash_attention_decode* / flash_attention_extend* front: ``family`` is "decode" or "extend", a ``block_table`` makes the call
+    paged (K, V are then the pools) and ``cu_seqlens_q`` ragged (Q -- and O, if given -- are then packed by token: Sq is the bound on
+    the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled).  The checks of the
+    tensors, the plan and the workspace for the capacity, then the entry point of _SPLIT_SYMBOLS: the ones that take both cache types
+    get the descales and the cache's dtype code, the ``_window`` ones the window."""
+    import torch
+    paged, ragged = block_table is not None, cu_seqlens_q is not None
+    symbols = _SPLIT_SYMBOLS[family, paged, ragged]
+    name = symbols[0][0]      # in the error texts: the un-windowed front's
+    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K, V", "[B, Hkv, capacity, d]")
     if ragged:
-        B = cu_seqlens_q.shape[0] - 1
+        Q = _token_view(Q, "Q")
+    # (a contiguous cache is checked against the batch, so cu_seqlens_q comes before the tensors; with a table it comes after them)
+    B = _cu_seqlens(cu_seqlens_q, Q) if ragged and not paged and Q.is_cuda else None
+    fp8 = _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=block_table, batch=B)
+    B = _cu_seqlens(cu_seqlens_q, Q) if ragged else Q.shape[0]
+    if paged:
+        max_pages, table_stride = _table_geometry(block_table, B)
+        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
+    else:
+        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
+    if ragged and O is not None:
+        O = _token_view(O, "O")
+    window = _window(window)
+    both = family == "extend" or bool(window)
+    _, H, Sq, d = Q.shape
     new = torch.zeros if ragged else torch.empty      # ragged: rows no sequence owns are not written
     Hkv = K.shape[1]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -572,7 +584,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = (plan or decode_plan)(B, H, Hkv, Sq, capacity, d, odt, num_splits, window)["num_splits"]
+    ns = _split_plan(family, ragged, B, H, Hkv, Sq, capacity, d, odt, num_splits, window).num_splits
     need = decode_workspace_size(1 if ragged else B, H, Sq, d, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -595,7 +607,7 @@ def _decode(symbol, fp8, Q, K, V, capacity, tables, geometry, kv_lens, scale, is
         if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
         dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), symbol + ("_window" if window else "" if plan else "_fp8" if fp8 else ""))
+        launch = getattr(lib(), symbols[bool(window)][fp8])
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
                     _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
@@ -626,10 +638,8 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     ``max(limC_i - W, 0) <= k`` with ``limC_i = max(kv_lens[b] - Sq + i + 1, 1)``, below ``limC_i`` with ``is_causal`` and below
     ``kv_lens[b]`` without (flash-attn's ``window_size=(W - 1, 0)`` / ``(W - 1, -1)``).  Keys below row 0's left edge are not read
     and may hold anything; ``decode_plan(..., window=W)`` plans from the window's tiles.  A negative window raises ValueError."""
-    fp8 = _decode_inputs("flash_attention_decode", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
-    Sk = K.shape[2]
-    return _decode("flash_attention_decode", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   O, workspace, stream, k_descale, v_descale, window)
+    return _split_front("decode", Q, K, V, None, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                        k_descale, v_descale, window)
 
 
 def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
@@ -649,28 +659,8 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     same pages, bit for bit.  fp8 pools (``torch.float8_e4m3fn`` under a bf16 Q) with ``k_descale`` / ``v_descale`` as for
     ``flash_attention_decode``.  ``window`` as there: a page whose keys all lie below row 0's left edge is not read and neither is
     its table entry, which may be any int32 (the engine may have freed the page).  No CPU fallback."""
-    import torch
-    fp8 = _decode_inputs("flash_attention_decode_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
-                         v_descale, table=block_table)
-    B = Q.shape[0]
-    P, _, page = K_pool.shape[:3]
-    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
-            or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
-        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
-    max_pages = block_table.shape[1]
-    table_stride = block_table.stride(0) if B > 1 else max_pages
-    return _decode("flash_attention_decode_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
-                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                   k_descale, v_descale, window)
-
-
-def _extend(window, Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-            O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
-    """what ``flash_attention_extend`` and ``flash_attention_extend_window`` share: the former is this with ``window`` None"""
-    fp8 = _decode_inputs("flash_attention_extend", "K, V", "[B, Hkv, capacity, d]", Q, K, V, k_descale, v_descale)
-    Sk = K.shape[2]
-    return _decode("flash_attention_extend", fp8, Q, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   O, workspace, stream, k_descale, v_descale, window, plan=extend_plan)
+    return _split_front("decode", Q, K_pool, V_pool, block_table, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
+                        workspace, stream, k_descale, v_descale, window)
 
 
 def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
@@ -682,8 +672,8 @@ def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     ``num_splits``, ``workspace`` (``decode_workspace_size`` bytes for ``extend_plan``'s split count), ``O``, ``return_lse``,
     ``stream`` -- without the cap on Sq and without ``window`` (that is ``flash_attention_extend_window``).  For Sq <= 16 the result is
     that call's, bit for bit, under the same forced ``num_splits``.  No CPU fallback."""
-    return _extend(None, Q, K, V, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, k_descale,
-                   v_descale)
+    return _split_front("extend", Q, K, V, None, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                        k_descale, v_descale)
 
 
 def flash_attention_extend_window(Q, K, V, kv_lens=None, window=None, **kw):
@@ -694,26 +684,7 @@ def flash_attention_extend_window(Q, K, V, kv_lens=None, window=None, **kw):
     (``extend_plan(..., window=W)``).  None or 0: ``flash_attention_extend`` itself, the same launches and bits.  For Sq <= 16 the result
     is ``flash_attention_decode(window=W)``'s, bit for bit, under the same forced ``num_splits``.  A negative window raises ValueError.
     No CPU fallback."""
-    return _extend(window, Q, K, V, kv_lens, **kw)
-
-
-def _extend_paged(window, Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
-                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
-                  v_descale=None):
-    """what ``flash_attention_extend_paged`` and ``flash_attention_extend_paged_window`` share: the former is this with ``window`` None"""
-    import torch
-    fp8 = _decode_inputs("flash_attention_extend_paged", "K_pool, V_pool", "[P, Hkv, page, d]", Q, K_pool, V_pool, k_descale,
-                         v_descale, table=block_table)
-    B = Q.shape[0]
-    P, _, page = K_pool.shape[:3]
-    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 \
-            or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
-        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
-    max_pages = block_table.shape[1]
-    table_stride = block_table.stride(0) if B > 1 else max_pages
-    return _decode("flash_attention_extend_paged", fp8, Q, K_pool, V_pool, max_pages * page, (block_table,),
-                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                   k_descale, v_descale, window, plan=extend_plan)
+    return _split_front("extend", Q, K, V, None, None, kv_lens, window=window, **kw)
 
 
 def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
@@ -723,36 +694,15 @@ def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     ``[B, max_pages]`` of ``flash_attention_decode_paged``, with that call's rules for the table, the lengths and the capacity
     ``max_pages * page`` (``extend_plan`` is asked with ``Sk = max_pages * page``).  The result is ``flash_attention_extend``'s on a
     contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_window``).  No CPU fallback."""
-    return _extend_paged(None, Q, K_pool, V_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
-                         workspace, stream, k_descale, v_descale)
+    return _split_front("extend", Q, K_pool, V_pool, block_table, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
+                        workspace, stream, k_descale, v_descale)
 
 
 def flash_attention_extend_paged_window(Q, K_pool, V_pool, block_table, kv_lens=None, window=None, **kw):
     """``flash_attention_extend_paged`` with a sliding window, as ``flash_attention_extend_window``: a page wholly below row 0's left
     edge is not read and neither is its table entry, which may be any int32.  The result is ``flash_attention_extend_window``'s on a
     contiguous copy of the same pages, bit for bit.  No CPU fallback."""
-    return _extend_paged(window, Q, K_pool, V_pool, block_table, kv_lens, **kw)
-
-
-def _table_geometry(block_table, B):
-    """(max_pages, table_stride) of a ragged front's block table, after the paged fronts' checks"""
-    import torch
-    t = block_table
-    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
-    return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
-
-
-def _extend_varlen(window, Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
-                   return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
-    """what ``flash_attention_extend_varlen`` and ``flash_attention_extend_varlen_window`` share: the former is this with ``window`` None"""
-    Qv = _token_view(Q, "Q")
-    B = _cu_seqlens(cu_seqlens_q, Q) if Q.is_cuda else None
-    fp8 = _decode_inputs("flash_attention_extend_varlen", "K, V", "[B, Hkv, capacity, d]", Qv, K, V, k_descale, v_descale, batch=B)
-    Sk = K.shape[2]
-    return _decode("flash_attention_extend_varlen", fp8, Qv, K, V, Sk, (), (Sk,), kv_lens, scale, is_causal, out_dtype, num_splits,
-                   return_lse, None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, window,
-                   plan=extend_varlen_plan, cu_seqlens_q=cu_seqlens_q)
+    return _split_front("extend", Q, K_pool, V_pool, block_table, None, kv_lens, window=window, **kw)
 
 
 def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
@@ -770,8 +720,8 @@ def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=Non
     (``extend_varlen_plan``); ``workspace``: ``decode_workspace_size(1, H, T, d, ns)`` bytes.  Returns O ``[T, H, d]`` or, with
     ``return_lse``, ``(O, LSE)`` with the LSE fp32 ``[H, T]``; an O or LSE allocated here is zero-filled.  No ``window``
     (``flash_attention_extend_varlen_window``).  No CPU fallback."""
-    return _extend_varlen(None, Q, K, V, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-                          stream, k_descale, v_descale)
+    return _split_front("extend", Q, K, V, None, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
+                        stream, k_descale, v_descale)
 
 
 def flash_attention_extend_varlen_window(Q, K, V, cu_seqlens_q, kv_lens=None, window=None, **kw):
@@ -779,23 +729,7 @@ def flash_attention_extend_varlen_window(Q, K, V, cu_seqlens_q, kv_lens=None, wi
     count (``extend_varlen_plan(..., window=W)``); None or 0: ``flash_attention_extend_varlen`` itself.  The O and LSE of a sequence are,
     bit for bit, those of ``flash_attention_extend_window`` on that sequence alone under the same forced ``num_splits``.  No CPU
     fallback."""
-    return _extend_varlen(window, Q, K, V, cu_seqlens_q, kv_lens, **kw)
-
-
-def _extend_paged_varlen(window, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
-                         out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
-                         k_descale=None, v_descale=None):
-    """what ``flash_attention_extend_paged_varlen`` and ``flash_attention_extend_paged_varlen_window`` share: the former is this with ``window`` None"""
-    Qv = _token_view(Q, "Q")
-    fp8 = _decode_inputs("flash_attention_extend_paged_varlen", "K_pool, V_pool", "[P, Hkv, page, d]", Qv, K_pool, V_pool, k_descale,
-                         v_descale, table=block_table)
-    B = _cu_seqlens(cu_seqlens_q, Q)
-    P, _, page = K_pool.shape[:3]
-    max_pages, table_stride = _table_geometry(block_table, B)
-    return _decode("flash_attention_extend_paged_varlen", fp8, Qv, K_pool, V_pool, max_pages * page, (block_table,),
-                   (P, page, max_pages, table_stride), kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
-                   None if O is None else _token_view(O, "O"), workspace, stream, k_descale, v_descale, window, plan=extend_varlen_plan,
-                   cu_seqlens_q=cu_seqlens_q)
+    return _split_front("extend", Q, K, V, None, cu_seqlens_q, kv_lens, window=window, **kw)
 
 
 def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
@@ -805,35 +739,42 @@ def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqle
     ``[B, max_pages]`` of ``flash_attention_extend_paged`` (``extend_varlen_plan`` is asked with ``Sk = max_pages * page``).  The
     table row and the length of a sequence without rows are not read.  The result is ``flash_attention_extend_varlen``'s on a
     contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_varlen_window``).  No CPU fallback."""
-    return _extend_paged_varlen(None, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits,
-                                return_lse, O, workspace, stream, k_descale, v_descale)
+    return _split_front("extend", Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits,
+                        return_lse, O, workspace, stream, k_descale, v_descale)
 
 
 def flash_attention_extend_paged_varlen_window(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, window=None, **kw):
     """``flash_attention_extend_paged_varlen`` with a sliding window, as ``flash_attention_extend_varlen_window``; pages below a
     sequence's window as in ``flash_attention_extend_paged_window``.  No CPU fallback."""
-    return _extend_paged_varlen(window, Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, **kw)
+    return _split_front("extend", Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, window=window, **kw)
 
 
-def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geometry, kv_lens, k_descale, v_descale, stream, table=None,
-            cu_seqlens_q=None):
-    """What kv_cache_append and kv_cache_append_paged share: the tensor checks of the decode fronts (``_decode_inputs``, the new rows
-    in the place of Q), the bounds of Sq, and the call.  The ragged fronts pass ``cu_seqlens_q`` and the new rows as ``_token_view``s:
-    Sq is then the bound on the packed rows (not capped at the capacity) and the batch is cu_seqlens_q's."""
+def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream):
+    """The four kv_cache_append* fronts (``name``: the front's, in the error texts): a ``block_table`` makes the call paged (K, V are
+    then the pools) and ``cu_seqlens_q`` ragged (the new rows are then packed by token: Sq is the bound on the packed rows, not capped
+    at the capacity, and the batch is cu_seqlens_q's).  The tensor checks of the decode fronts (``_decode_inputs``, the new rows in
+    the place of Q), the bounds of Sq, and the entry point of _APPEND_SYMBOLS."""
     import torch
-    ragged = cu_seqlens_q is not None
+    paged, ragged = block_table is not None, cu_seqlens_q is not None
+    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K_cache, V_cache", "[B, Hkv, capacity, d]")
+    if ragged:
+        K_new, V_new = _token_view(K_new, "K_new"), _token_view(V_new, "V_new")
+    elif paged:      # (the uniform paged front checks its table first; the ragged one where the batch is known)
+        _table_geometry(block_table, K_new.shape[0] if K_new.dim() == 4 else 0)
     if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
         raise ValueError(f"K_new, V_new must be {'[T, Hkv, d]' if ragged else '[B, Hkv, Sq, d]'} of one dtype, with the K/V heads of {kv} {layout}")
     if not V_new.is_cuda:
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
-    batch = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
-    fp8 = _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=table, batch=batch)
-    B, Hkv, Sq, d = K_new.shape
-    if ragged:
-        B = batch
-        if table is not None:      # (the paged ragged front leaves the table's checks to here, where the batch is known)
-            max_pages, table_stride = _table_geometry(table, B)
-            geometry = (K.shape[0], K.shape[2], max_pages, table_stride)
+    B = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
+    _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=block_table, batch=B)
+    _, Hkv, Sq, d = K_new.shape
+    if not ragged:
+        B = K_new.shape[0]
+    if paged:
+        max_pages, table_stride = _table_geometry(block_table, B)
+        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
+    else:
+        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
     if Sq < 1 or (Sq > capacity and not ragged):
         raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -842,10 +783,10 @@ def _append(symbol, name, kv, layout, K_new, V_new, K, V, capacity, tables, geom
     with torch.cuda.device(K_new.device):
         st = [_strides(t) for t in (K_new, V_new, K, V)]
         ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = getattr(lib(), symbol)(K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                    *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables),
-                                    ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype),
-                                    _dtype_code(K.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+        rc = getattr(lib(), _APPEND_SYMBOLS[paged, ragged])(
+            K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(), *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens),
+            *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype), _dtype_code(K.dtype),
+            *[ctypes.byref(x) for x in st], _stream_ptr(stream))
     _check(rc)
 
 
@@ -864,9 +805,7 @@ def kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens=None, k_descale=None
     ``kv_lens[b] <= 0`` writes nothing.  A decode step is ``kv_lens += Sq; kv_cache_append(...); flash_attention_decode(...,
     is_causal=True)`` on one tensor of lengths.  Lengths and descales are read by the kernel: the call never synchronises and a
     captured graph sees the values of the moment.  Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
-    cap = K_cache.shape[2] if K_cache.dim() == 4 else 0
-    _append("flash_attention_kv_append", "kv_cache_append", "K_cache, V_cache", "[B, Hkv, capacity, d]", K_new, V_new, K_cache, V_cache,
-            cap, (), (cap,), kv_lens, k_descale, v_descale, stream)
+    _append_front("kv_cache_append", K_new, V_new, K_cache, V_cache, None, None, kv_lens, k_descale, v_descale, stream)
 
 
 def kv_cache_append_paged(K_new, V_new, K_pool, V_pool, block_table, kv_lens=None, k_descale=None, v_descale=None, stream=None):
@@ -878,17 +817,7 @@ def kv_cache_append_paged(K_new, V_new, K_pool, V_pool, block_table, kv_lens=Non
     Only the entries of pages that receive a row are read, by the kernel.  An entry outside [0, P) is NOT clamped (decode may
     clamp: it only reads): the rows that would go to that page are skipped and nothing else is touched.  Two sequences that write
     the same row of one page: the winner is unspecified.  Everything else as for ``kv_cache_append``.  Returns None."""
-    import torch
-    table = block_table
-    B = K_new.shape[0] if K_new.dim() == 4 else 0
-    P, _, page = K_pool.shape[:3] if K_pool.dim() == 4 else (0, 0, 0)
-    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] != B or table.shape[1] < 1 \
-            or table.stride(1) != 1 or (B > 1 and table.stride(0) < table.shape[1]):
-        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
-    max_pages = table.shape[1]
-    table_stride = table.stride(0) if B > 1 else max_pages
-    _append("flash_attention_kv_append_paged", "kv_cache_append_paged", "K_pool, V_pool", "[P, Hkv, page, d]", K_new, V_new, K_pool, V_pool,
-            max_pages * page, (table,), (P, page, max_pages, table_stride), kv_lens, k_descale, v_descale, stream, table=table)
+    _append_front("kv_cache_append_paged", K_new, V_new, K_pool, V_pool, block_table, None, kv_lens, k_descale, v_descale, stream)
 
 
 def kv_cache_append_varlen(K_new, V_new, K_cache, V_cache, cu_seqlens_q, kv_lens=None, k_descale=None, v_descale=None, stream=None):
@@ -900,10 +829,7 @@ def kv_cache_append_varlen(K_new, V_new, K_cache, V_cache, cu_seqlens_q, kv_lens
     ``kv_cache_append`` for that sequence alone; every other byte keeps its value.  T is not capped at the capacity.  A step of a
     mixed batch is ``kv_lens += q_lens; kv_cache_append_varlen(...); flash_attention_extend_varlen(..., is_causal=True)``, one
     graph.  Returns None.  No CPU fallback."""
-    cap = K_cache.shape[2] if K_cache.dim() == 4 else 0
-    _append("flash_attention_kv_append_varlen", "kv_cache_append_varlen", "K_cache, V_cache", "[B, Hkv, capacity, d]",
-            _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), K_cache, V_cache, cap, (), (cap,), kv_lens, k_descale, v_descale, stream,
-            cu_seqlens_q=cu_seqlens_q)
+    _append_front("kv_cache_append_varlen", K_new, V_new, K_cache, V_cache, None, cu_seqlens_q, kv_lens, k_descale, v_descale, stream)
 
 
 def kv_cache_append_paged_varlen(K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, k_descale=None, v_descale=None,
@@ -911,9 +837,8 @@ def kv_cache_append_paged_varlen(K_new, V_new, K_pool, V_pool, block_table, cu_s
     """``kv_cache_append_varlen`` into PAGED caches: the pools and the ``block_table`` ``[B, max_pages]`` of ``kv_cache_append_paged``,
     with that call's rules -- only the entries of pages that receive a row are read, an entry outside [0, P) is skipped and never
     clamped.  Returns None."""
-    _append("flash_attention_kv_append_paged_varlen", "kv_cache_append_paged_varlen", "K_pool, V_pool", "[P, Hkv, page, d]",
-            _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), K_pool, V_pool, 0, (block_table,), None, kv_lens, k_descale, v_descale,
-            stream, table=block_table, cu_seqlens_q=cu_seqlens_q)
+    _append_front("kv_cache_append_paged_varlen", K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale,
+                  stream)
 
 
 def _library_accepts(t):

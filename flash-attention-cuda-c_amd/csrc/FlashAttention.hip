@@ -318,62 +318,96 @@ constexpr int EXTEND_MIN_TILES = 2;
 // `tiles` is decode's windowed bound with Sq = seqLenQ or totalQ, and the split count follows by extend's unchanged rule and
 // constants.  NOT measured for windowed chunks: tools/bench_decode.py --extend --window with --splits shows what the rule costs.
 
-// What a call family is to the launch decision: built once per entry point (decode_form, extend_form), read by decode_check_shape,
-// decode_route and decode_run
-using SplitKernelOf = Kernel (*)(int d);
+// What a call family is to the launch decision: built once per entry point (decode_form, extend_form, extend_varlen_form), read by
+// decode_check_shape, decode_route and decode_run
 struct SplitForm {
     int rows_per_block;    // packed rows of a row block: 16 per 16-row tile of a wave
     int wgs_per_cu;        // resident workgroups per CU the split rule fills
     int min_tiles;         // no split shorter than this many key tiles of the capacity
-    bool q_to_capacity;    // seqLenQ is capped at the capacity, not at FA_DECODE_MAX_Q
-    const SplitKernelOf (*split_kernel_of)[2][2];   // [window][paged][kv8]: the selectors of the family's cache forms, without and with
-                           // a window (decode: one set, WINDOW = true, serves both; extend: windowSize = 0 launches the WINDOW = false units)
+    bool extend;           // chunked prefill: the RT > 1 units, and seqLenQ is capped at the capacity, not at FA_DECODE_MAX_Q
     bool varlen;           // ragged: "Sq" is totalQ, the bound on the token-packed rows of the whole batch (not capped at the capacity),
                            // row_blocks the bound NB over the batch, batchSize <= FA_VARLEN_MAX_BATCH and cuSeqlensQ is required
 };
-static constexpr SplitKernelOf DECODE_KERNELS[2][2][2] = {{{decode_split_kernel_of, decode_fp8_split_kernel_of},
-                                                           {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}},
-                                                          {{decode_split_kernel_of, decode_fp8_split_kernel_of},
-                                                           {decode_paged_split_kernel_of, decode_paged_fp8_split_kernel_of}}};
-static constexpr SplitKernelOf EXTEND_KERNELS[2][2][2] = {{{extend_split_kernel_of, extend_fp8_split_kernel_of},
-                                                           {extend_paged_split_kernel_of, extend_paged_fp8_split_kernel_of}},
-                                                          {{extend_window_split_kernel_of, extend_window_fp8_split_kernel_of},
-                                                           {extend_window_paged_split_kernel_of, extend_window_paged_fp8_split_kernel_of}}};
-static constexpr SplitKernelOf VARLEN_KERNELS[2][2][2] = {
-    {{extend_varlen_split_kernel_of, extend_varlen_fp8_split_kernel_of},
-     {extend_varlen_paged_split_kernel_of, extend_varlen_paged_fp8_split_kernel_of}},
-    {{extend_window_varlen_split_kernel_of, extend_window_varlen_fp8_split_kernel_of},
-     {extend_window_varlen_paged_split_kernel_of, extend_window_varlen_paged_fp8_split_kernel_of}}};
-static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, DECODE_KERNELS, false}; }
+static SplitForm decode_form() { return {DecodeCfg<128>::ROWS, DECODE_WGS_PER_CU, DECODE_MIN_TILES, false, false}; }
 static SplitForm extend_form(int d) {   // (any d but 128 takes the d = 64 values: decode_check_shape refuses it before they matter)
-    return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS, false}
-                    : SplitForm{ExtendCfg<64>::ROWS, ExtendCfg<64>::WGS_PER_CU, EXTEND_MIN_TILES, true, EXTEND_KERNELS, false};
+    return d == 128 ? SplitForm{ExtendCfg<128>::ROWS, ExtendCfg<128>::WGS_PER_CU, EXTEND_MIN_TILES, true, false}
+                    : SplitForm{ExtendCfg<64>::ROWS, ExtendCfg<64>::WGS_PER_CU, EXTEND_MIN_TILES, true, false};
 }
 static SplitForm extend_varlen_form(int d) {
     SplitForm f = extend_form(d);
-    f.split_kernel_of = VARLEN_KERNELS;
     f.varlen = true;
     return f;
 }
+
+// The K/V cache of a call, read (flash_attention_decode*, flash_attention_extend*) or written (flash_attention_kv_append*).  Contiguous:
+// K / V are [B, Hkv, capacity, d] and paging is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride) and
+// the capacity is maxPagesPerSeq * pageSize (cache_capacity).  kv_dtype is the element type of K / V: FA_DTYPE_BF16, or FA_DTYPE_FP8_E4M3
+// with the two optional per-head descale arrays.
+struct DecodePaging {
+    const int32_t* table;
+    int64_t table_stride;
+    int num_pages, page_size, max_pages;
+};
+struct KvCache {
+    const void *K, *V;
+    const int32_t* kv_lens;
+    const float *k_descale, *v_descale;
+    int kv_dtype;
+    int capacity;                  // seqLenK; paged: cache_capacity derives it
+    const fa_strides *sK, *sV;
+    const DecodePaging* paging;
+};
+
+// A call of the split-KV kernel: every flash_attention_decode* / flash_attention_extend* entry point fills one (a member it has no
+// argument for stays 0 / NULL) and the three plan functions fill its shape.  window: 0, or the sliding window W of the _window entry
+// points.  Ragged (form.varlen; flash_attention_extend*_varlen): Sq is totalQ, Q / O are packed by token (strideB is not read; NULL
+// strides: [totalQ, H, d]), the LSE and the slabs are [H, totalQ], and cu_seqlens_q -- NULL in every other call -- is required.
+struct SplitCall {
+    SplitForm form;
+    const void* Q;
+    void* O;
+    float* LSE;
+    const int32_t* cu_seqlens_q;
+    KvCache cache;
+    void* workspace;
+    int B, H, Hkv, Sq, d;
+    float scale;
+    bool is_causal;
+    int dtype, o_dtype, num_splits, window;
+    const fa_strides *sQ, *sO;
+    void* stream;
+};
+
+// A call of the append kernels: Sq new rows per sequence (ragged: totalQ token-packed rows, cu_seqlens_q required) into the cache
+struct AppendCall {
+    bool varlen;
+    const void *Knew, *Vnew;
+    const int32_t* cu_seqlens_q;
+    KvCache cache;
+    int B, Hkv, Sq, d, dtype;
+    const fa_strides *sKnew, *sVnew;
+    void* stream;
+};
 
 struct DecodeRoute {
     int ns, row_blocks, tiles;
     int64_t grid;
 };
 
-static DecodeRoute decode_route(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int numSplits, int window) {
+static DecodeRoute decode_route(const SplitCall& c) {
+    const SplitForm& f = c.form;
     DecodeRoute r{};
-    const int64_t rows = (int64_t)(H / Hkv) * Sq;        // packed rows per K/V head (ragged: of the whole batch, at most)
+    const int64_t rows = (int64_t)(c.H / c.Hkv) * c.Sq;        // packed rows per K/V head (ragged: of the whole batch, at most)
     // ragged: NB = floor((G totalQ + B (rows_per_block - 1)) / rows_per_block) >= sum_b ceil(G sq_b / rows_per_block) for every
     // partition of at most totalQ rows over the B sequences (each term is at most (G sq_b + rows_per_block - 1) / rows_per_block,
     // and a sum of integers below a bound is below its floor)
-    r.row_blocks = (int)std::min<int64_t>(f.varlen ? (rows + (int64_t)B * (f.rows_per_block - 1)) / f.rows_per_block
+    r.row_blocks = (int)std::min<int64_t>(f.varlen ? (rows + (int64_t)c.B * (f.rows_per_block - 1)) / f.rows_per_block
                                                    : (rows + f.rows_per_block - 1) / f.rows_per_block, INT32_MAX);
     constexpr int TILE = DecodeCfg<128>::TILE;
-    r.tiles = (Sk + TILE - 1) / TILE;
-    if (window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)window + Sq - 1 + TILE - 1) / TILE + 1);
-    const int64_t units = (int64_t)(f.varlen ? 1 : B) * Hkv * r.row_blocks;
-    if (numSplits > 0) r.ns = numSplits;
+    r.tiles = (c.cache.capacity + TILE - 1) / TILE;
+    if (c.window > 0) r.tiles = (int)std::min<int64_t>(r.tiles, ((int64_t)c.window + c.Sq - 1 + TILE - 1) / TILE + 1);
+    const int64_t units = (int64_t)(f.varlen ? 1 : c.B) * c.Hkv * r.row_blocks;
+    if (c.num_splits > 0) r.ns = c.num_splits;
     else {
         const int64_t want = ((int64_t)f.wgs_per_cu * device_cus() + units - 1) / units;
         r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / f.min_tiles, (int64_t)FA_DECODE_MAX_SPLITS}));
@@ -382,104 +416,137 @@ static DecodeRoute decode_route(const SplitForm& f, int B, int H, int Hkv, int S
     return r;
 }
 
-static int decode_check_shape(const SplitForm& f, int B, int H, int Hkv, int Sq, int Sk, int d, int dtype, int o_dtype, int numSplits,
-                              int window) {
+// the shape of a call or a plan: B, H, Hkv, Sq, d, the capacity, the types, the forced split count and the window
+static int decode_check_shape(const SplitCall& c) {
+    const SplitForm& f = c.form;
+    const int B = c.B, H = c.H, Sq = c.Sq, Sk = c.cache.capacity, d = c.d;
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if ((!f.varlen && Sq > (f.q_to_capacity ? Sk : FA_DECODE_MAX_Q)) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
-    if (f.q_to_capacity && (int64_t)(f.varlen ? 1 : B) * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if ((!f.varlen && Sq > (f.extend ? Sk : FA_DECODE_MAX_Q)) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (f.extend && (int64_t)(f.varlen ? 1 : B) * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
     if (f.varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
-    if (!kv_heads_ok(H, Hkv)) return FA_ERR_BAD_SHAPE;
-    if (numSplits < 0 || numSplits > FA_DECODE_MAX_SPLITS || window < 0) return FA_ERR_BAD_SHAPE;
-    if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!kv_heads_ok(H, c.Hkv)) return FA_ERR_BAD_SHAPE;
+    if (c.num_splits < 0 || c.num_splits > FA_DECODE_MAX_SPLITS || c.window < 0) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_output_dtype(c.o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    const DecodeRoute r = decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window);
+    const DecodeRoute r = decode_route(c);
     if (r.grid > INT32_MAX || r.row_blocks == INT32_MAX) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 
 static size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// flash_attention_decode*, flash_attention_extend*: one validation and launch sequence.  Contiguous: K / V are
-// [B, Hkv, Sk, d] caches and table is NULL.  Paged: K / V are [numPages, Hkv, pageSize, d] pools (strideB = the page stride),
-// Sk = maxPagesPerSeq * pageSize is the capacity and the split kernel is the paged instantiation.  kv_dtype is the element type of
-// K / V: FA_DTYPE_BF16 (the type of Q), or FA_DTYPE_FP8_E4M3 with the two optional per-head descale arrays (the _fp8 entry points).
-// window: 0, or the sliding window W of the _window entry points.  Ragged (f.varlen; flash_attention_extend*_varlen): Sq is totalQ, Q / O
-// are packed by token (strideB is not read; NULL strides: [totalQ, H, d]), the LSE and the slabs are [H, totalQ], and cuSeqlensQ --
-// NULL in every other call -- is required.
-struct DecodePaging {
-    const int32_t* table;
-    int64_t table_stride;
-    int num_pages, page_size, max_pages;
-};
-
 // the strides of a token-packed [totalQ, heads, d] tensor: the caller's with strideB out of the way, or (s = NULL) the dense ones
 static fa_strides token_strides(const fa_strides* s, int64_t heads, int64_t d) {
     return s ? fa_strides{0, s->strideH, s->strideS} : fa_strides{0, d, heads * d};
 }
 
-static int decode_run(const SplitForm& f, const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
-                      const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int B, int H, int Hkv, int Sq, int Sk, int d, float scale,
-                      bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int window, const fa_strides* sQ,
-                      const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, const DecodePaging* pg, void* stream) {
-    if (!Q || !K || !V || !O || (pg && !pg->table) || (f.varlen && !cuSeqlensQ)) return FA_ERR_NULL_POINTER;
-    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(LSE) || !aligned16(workspace)) return FA_ERR_MISALIGNED;
-    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
-    if (reinterpret_cast<uintptr_t>(cuSeqlensQ) & 3u) return FA_ERR_MISALIGNED;
-    if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
-    if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
-    if (pg) {
+// ---- what decode_run and kv_append_run ask of a cache, in the order both ask it: a cache the append accepts is one the decode call
+// of the same kv_dtype accepts.  Each call makes checks of its own in between, so these stay separate steps ----
+static bool misaligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3u; }
+
+// after the NULL and 16-byte checks of the tensors: the int32 and fp32 arrays the kernel reads
+static int cache_check_arrays(const KvCache& c, const int32_t* cuSeqlensQ) {
+    if (c.kv_lens && misaligned4(c.kv_lens)) return FA_ERR_MISALIGNED;
+    if (misaligned4(cuSeqlensQ)) return FA_ERR_MISALIGNED;
+    if (c.paging && misaligned4(c.paging->table)) return FA_ERR_MISALIGNED;
+    if (misaligned4(c.k_descale) || misaligned4(c.v_descale)) return FA_ERR_MISALIGNED;
+    return FA_OK;
+}
+
+// then the paging geometry, which makes the capacity
+static int cache_capacity(KvCache& c) {
+    if (const DecodePaging* pg = c.paging) {
         if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
         if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
-        Sk = pg->max_pages * pg->page_size;
+        c.capacity = pg->max_pages * pg->page_size;
     }
+    return FA_OK;
+}
+
+// K / V: 16-byte row starts = strides in multiples of 16 / the element size
+static bool cache_strides_ok(const KvCache& c, int d) {
+    const int esz = elem_size(c.kv_dtype);
+    return strides_ok(c.sK, esz, d) && strides_ok(c.sV, esz, d);
+}
+
+// last, the prefill paths' limit on one head's K / V extent -- of the whole cache, or of one page (page bases are 64-bit: the pool as a
+// whole may be larger)
+static bool cache_extent_ok(const KvCache& c, int d) {
+    const int esz = elem_size(c.kv_dtype);
+    const int64_t extent = c.paging ? c.paging->page_size : (int64_t)c.capacity + KV_EXTENT_SLACK;
+    return kv_extent_ok(extent, c.sK ? c.sK->strideS : d, esz) && kv_extent_ok(extent, c.sV ? c.sV->strideS : d, esz);
+}
+
+// rows of one head of one batch entry / page: what NULL K / V strides are dense over
+static int cache_rows(const KvCache& c) { return c.paging ? c.paging->page_size : c.capacity; }
+
+// The instantiation a call launches, of the twenty that exist: decode's four are WINDOW = true and serve window = 0 too; chunked
+// prefill with windowSize = 0 launches its WINDOW = false units
+static Kernel split_kernel(const SplitCall& c) {
+    return by_bool(c.cache.paging != nullptr, [&]<bool PAGED>() {
+        return by_bool(c.cache.kv_dtype == FA_DTYPE_FP8_E4M3, [&]<bool KV8>() {
+            if (!c.form.extend) return split_kernel_of<false, false, true, PAGED, KV8>(c.d);
+            return by_bool(c.form.varlen, [&]<bool VARLEN>() {
+                return by_bool(c.window > 0, [&]<bool WINDOW>() { return split_kernel_of<true, VARLEN, WINDOW, PAGED, KV8>(c.d); });
+            });
+        });
+    });
+}
+
+// flash_attention_decode*, flash_attention_extend*: one validation and launch sequence
+static int decode_run(SplitCall c) {
+    const SplitForm& f = c.form;
+    const DecodePaging* pg = c.cache.paging;
+    const int H = c.H, Hkv = c.Hkv, Sq = c.Sq, d = c.d;
+    if (!c.Q || !c.cache.K || !c.cache.V || !c.O || (pg && !pg->table) || (f.varlen && !c.cu_seqlens_q)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Q) || !aligned16(c.cache.K) || !aligned16(c.cache.V) || !aligned16(c.O) || !aligned16(c.LSE) || !aligned16(c.workspace))
+        return FA_ERR_MISALIGNED;
+    int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
+    if (rc != FA_OK) return rc;
+    if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
     fa_strides tQ{}, tO{};   // ragged: Q and O on their token strides
     if (f.varlen) {
-        tQ = token_strides(sQ, H, d); sQ = &tQ;
-        tO = token_strides(sO, H, d); sO = &tO;
+        tQ = token_strides(c.sQ, H, d); c.sQ = &tQ;
+        tO = token_strides(c.sO, H, d); c.sO = &tO;
     }
-    int rc = decode_check_shape(f, B, H, Hkv, Sq, Sk, d, dtype, o_dtype, numSplits, window);
-    if (rc != FA_OK) return rc;
-    if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
-    const int osz = elem_size(o_dtype), esz = elem_size(kv_dtype);          // K / V: 16-byte row starts = strides in multiples of 16 / esz
-    if (!strides_ok(sQ, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d) || !strides_ok(sO, osz, d)) return FA_ERR_BAD_STRIDE;
-    // the prefill paths' limit on one head's K / V extent -- of the whole cache, or of one page (page bases are 64-bit: the pool as a
-    // whole may be larger)
-    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;
-    if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
-    const DecodeRoute r = decode_route(f, B, H, Hkv, Sq, Sk, numSplits, window);
-    if (r.ns > 1 && !workspace) return FA_ERR_NULL_POINTER;
-    const int64_t rows = (int64_t)(f.varlen ? 1 : B) * H * Sq;
+    if ((rc = decode_check_shape(c)) != FA_OK) return rc;
+    if (c.cache.kv_dtype != FA_DTYPE_BF16 && c.cache.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
+    if (!strides_ok(c.sQ, 2, d) || !cache_strides_ok(c.cache, d) || !strides_ok(c.sO, elem_size(c.o_dtype), d)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(c.cache, d)) return FA_ERR_BAD_SHAPE;
+    const DecodeRoute r = decode_route(c);
+    if (r.ns > 1 && !c.workspace) return FA_ERR_NULL_POINTER;
+    const int64_t rows = (int64_t)(f.varlen ? 1 : c.B) * H * Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
-    const int rowsK = pg ? pg->page_size : Sk;   // rows of one head of one batch entry / page
+    const int rowsK = cache_rows(c.cache);
     VarlenDecodeParams p;   // (what every other form launches with is its DecodeParams part)
-    p.Q = (const __bf16*)Q; p.K = (const __bf16*)K; p.V = (const __bf16*)V; p.O = O; p.lse = LSE; p.kv_lens = kvLens;
-    p.part_o = (float*)workspace;
-    p.part_lse = r.ns > 1 ? (float*)((char*)workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
-    resolve_strides(sQ, H, Sq, d, p.qB, p.qH, p.qS);
-    resolve_strides(sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
-    resolve_strides(sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
-    resolve_strides(sO, H, Sq, d, p.oB, p.oH, p.oS);
-    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = Sk;
+    p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.cache.K; p.V = (const __bf16*)c.cache.V; p.O = c.O; p.lse = c.LSE;
+    p.kv_lens = c.cache.kv_lens;
+    p.part_o = (float*)c.workspace;
+    p.part_lse = r.ns > 1 ? (float*)((char*)c.workspace + round16((size_t)rows * r.ns * d * sizeof(float))) : nullptr;
+    resolve_strides(c.sQ, H, Sq, d, p.qB, p.qH, p.qS);
+    resolve_strides(c.cache.sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+    resolve_strides(c.cache.sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+    resolve_strides(c.sO, H, Sq, d, p.oB, p.oH, p.oS);
+    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.Sk = c.cache.capacity;
     p.row_blocks = r.row_blocks; p.ns = r.ns;
     p.rows = (int)rows;
-    p.o_dtype = o_dtype;
-    p.causal = is_causal;
-    p.scale_log2 = scale * 1.4426950408889634f;
+    p.o_dtype = c.o_dtype;
+    p.causal = c.is_causal;
+    p.scale_log2 = c.scale * 1.4426950408889634f;
     p.block_table = pg ? pg->table : nullptr;
     p.table_stride = pg ? pg->table_stride : 0;
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
-    p.k_descale = kDescale;
-    p.v_descale = vDescale;
-    p.window = window;
-    p.cu_q = cuSeqlensQ;
-    p.B = B;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
-    const Kernel sk = f.split_kernel_of[window > 0][pg != nullptr][kv8](d);
+    p.k_descale = c.cache.k_descale;
+    p.v_descale = c.cache.v_descale;
+    p.window = c.window;
+    p.cu_q = c.cu_seqlens_q;
+    p.B = c.B;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    const Kernel sk = split_kernel(c);
     if (f.varlen) {
         const hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
         if (e != hipSuccess || r.ns == 1) return (int)e;
@@ -491,68 +558,62 @@ static int decode_run(const SplitForm& f, const void* Q, const void* K, const vo
 }
 
 // ---- K/V cache append (kv_append.hip.h) ----
-// flash_attention_kv_append and flash_attention_kv_append_paged: one validation and launch.  The caches are decode_run's: the same
-// layouts, element sizes, stride rules, paging checks and extent limits, so a cache this call accepts is one the decode call of the
-// same kv_dtype accepts.  Sq is not capped at FA_DECODE_MAX_Q (the call also fills a cache after a prefill), only at the capacity.
+// flash_attention_kv_append*: one validation and launch.  The caches are decode_run's and so are their checks (cache_*, above).  Sq is
+// not capped at FA_DECODE_MAX_Q (the call also fills a cache after a prefill), only at the capacity.
 // Ragged (varlen; flash_attention_kv_append*_varlen): Sq is totalQ, not capped at the capacity; Knew / Vnew are packed by token
-// (strideB is not read; NULL strides: [totalQ, Hkv, d]); cuSeqlensQ -- NULL in the uniform calls -- is required; the token-major kernel.
-static int kv_append_run(bool varlen, const void* Knew, const void* Vnew, void* K, void* V, const int32_t* cuSeqlensQ, const int32_t* kvLens, const float* kDescale,
-                         const float* vDescale, int B, int Hkv, int Sq, int Sk, int d, int dtype, int kv_dtype, const fa_strides* sKnew,
-                         const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV, const DecodePaging* pg, void* stream) {
-    if (!Knew || !Vnew || !K || !V || (pg && !pg->table) || (varlen && !cuSeqlensQ)) return FA_ERR_NULL_POINTER;
-    if (!aligned16(Knew) || !aligned16(Vnew) || !aligned16(K) || !aligned16(V)) return FA_ERR_MISALIGNED;
-    if (kvLens && (reinterpret_cast<uintptr_t>(kvLens) & 3u)) return FA_ERR_MISALIGNED;
-    if (reinterpret_cast<uintptr_t>(cuSeqlensQ) & 3u) return FA_ERR_MISALIGNED;
-    if (pg && (reinterpret_cast<uintptr_t>(pg->table) & 3u)) return FA_ERR_MISALIGNED;
-    if ((reinterpret_cast<uintptr_t>(kDescale) | reinterpret_cast<uintptr_t>(vDescale)) & 3u) return FA_ERR_MISALIGNED;
-    if (pg) {
-        if (pg->num_pages <= 0 || pg->max_pages <= 0 || pg->page_size < 16 || (pg->page_size & (pg->page_size - 1))) return FA_ERR_BAD_SHAPE;
-        if ((int64_t)pg->max_pages * pg->page_size > (1 << 24) || pg->table_stride < pg->max_pages) return FA_ERR_BAD_SHAPE;
-        Sk = pg->max_pages * pg->page_size;
-    }
+// (strideB is not read; NULL strides: [totalQ, Hkv, d]); cu_seqlens_q -- NULL in the uniform calls -- is required; the token-major kernel.
+static int kv_append_run(AppendCall c) {
+    const DecodePaging* pg = c.cache.paging;
+    const int B = c.B, Hkv = c.Hkv, Sq = c.Sq, d = c.d, kv_dtype = c.cache.kv_dtype;
+    if (!c.Knew || !c.Vnew || !c.cache.K || !c.cache.V || (pg && !pg->table) || (c.varlen && !c.cu_seqlens_q)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Knew) || !aligned16(c.Vnew) || !aligned16(c.cache.K) || !aligned16(c.cache.V)) return FA_ERR_MISALIGNED;
+    int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
+    if (rc != FA_OK) return rc;
+    if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
+    const int Sk = c.cache.capacity;
     if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
-    if (Sk > (1 << 24) || (!varlen && Sq > Sk) || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
-    if (varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
-    if (dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (Sk > (1 << 24) || (!c.varlen && Sq > Sk) || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    if (kv_dtype == FA_DTYPE_BF16 && (kDescale || vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
+    if (kv_dtype == FA_DTYPE_BF16 && (c.cache.k_descale || c.cache.v_descale)) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    const int esz = elem_size(kv_dtype);
     fa_strides tK{}, tV{};   // ragged: the new rows on their token strides
-    if (varlen) {
-        tK = token_strides(sKnew, Hkv, d); sKnew = &tK;
-        tV = token_strides(sVnew, Hkv, d); sVnew = &tV;
+    if (c.varlen) {
+        tK = token_strides(c.sKnew, Hkv, d); c.sKnew = &tK;
+        tV = token_strides(c.sVnew, Hkv, d); c.sVnew = &tV;
     }
-    if (!strides_ok(sKnew, 2, d) || !strides_ok(sVnew, 2, d) || !strides_ok(sK, esz, d) || !strides_ok(sV, esz, d)) return FA_ERR_BAD_STRIDE;
-    const int64_t extent = pg ? pg->page_size : (int64_t)Sk + KV_EXTENT_SLACK;   // decode_run's limit: what is written can be read
-    if (!kv_extent_ok(extent, sK ? sK->strideS : d, esz) || !kv_extent_ok(extent, sV ? sV->strideS : d, esz)) return FA_ERR_BAD_SHAPE;
+    if (!strides_ok(c.sKnew, 2, d) || !strides_ok(c.sVnew, 2, d) || !cache_strides_ok(c.cache, d)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(c.cache, d)) return FA_ERR_BAD_SHAPE;   // what is written can be read
     const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
     const int tokens_per_block = KvAppendCfg::THREADS / (d / 8);                     // ragged: a row per d / 8 lanes
     const int token_blocks = (int)(((int64_t)Sq + tokens_per_block - 1) / tokens_per_block);
-    const int64_t grid = varlen ? (int64_t)Hkv * token_blocks * 2 : (int64_t)B * Hkv * row_blocks * 2;
+    const int64_t grid = c.varlen ? (int64_t)Hkv * token_blocks * 2 : (int64_t)B * Hkv * row_blocks * 2;
     if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
-    const int rowsK = pg ? pg->page_size : Sk;
+    const int rowsK = cache_rows(c.cache);
     KvAppendParams p;
-    p.Knew = (const __bf16*)Knew; p.Vnew = (const __bf16*)Vnew; p.K = K; p.V = V;
-    p.kv_lens = kvLens;
+    p.Knew = (const __bf16*)c.Knew; p.Vnew = (const __bf16*)c.Vnew;
+    p.K = const_cast<void*>(c.cache.K); p.V = const_cast<void*>(c.cache.V);   // (the entry points take them writable)
+    p.kv_lens = c.cache.kv_lens;
     p.block_table = pg ? pg->table : nullptr;
-    p.k_descale = kDescale; p.v_descale = vDescale;
-    resolve_strides(sKnew, Hkv, Sq, d, p.knB, p.knH, p.knS);
-    resolve_strides(sVnew, Hkv, Sq, d, p.vnB, p.vnH, p.vnS);
-    resolve_strides(sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
-    resolve_strides(sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+    p.k_descale = c.cache.k_descale; p.v_descale = c.cache.v_descale;
+    resolve_strides(c.sKnew, Hkv, Sq, d, p.knB, p.knH, p.knS);
+    resolve_strides(c.sVnew, Hkv, Sq, d, p.vnB, p.vnH, p.vnS);
+    resolve_strides(c.cache.sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+    resolve_strides(c.cache.sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
     p.table_stride = pg ? pg->table_stride : 0;
     p.Hkv = Hkv; p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks;
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
-    if (varlen) {
-        const KvAppendVarlenParams pv{p, cuSeqlensQ, B, token_blocks};
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    if (c.varlen) {
+        const KvAppendVarlenParams pv{p, c.cu_seqlens_q, B, token_blocks};
         const Kernel kr = kv_append_varlen_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
-        return (int)launch(kr, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(stream), pv);
+        return (int)launch(kr, (unsigned)grid, KvAppendCfg::THREADS, 0, st, pv);
     }
     const Kernel k = kv_append_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
-    return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(stream), p);
+    return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, st, p);
 }
 }  // namespace fa
 
@@ -771,31 +832,31 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
     return (int)launch(bwd_post_kernel_of(d, grad_dtype), (unsigned)((rows * d / 4 + 255) / 256), 256, 0, st, p);
 }
 
-// what the three plan functions report of a route
-static void fill_split_plan(fa_decode_plan* plan, const fa::SplitForm& f, const fa::DecodeRoute& r, int dHead, int64_t rows) {
+// The three plan functions: the shape's refusals, then what the route launches
+static int split_plan(const fa::SplitCall& c, fa_decode_plan* plan) {
     using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const int rc = decode_check_shape(c);
+    if (rc != FA_OK) return rc;
+    const DecodeRoute r = decode_route(c);
     plan->num_splits = r.ns;
     plan->row_blocks = r.row_blocks;
-    plan->rows_per_block = f.rows_per_block;
+    plan->rows_per_block = c.form.rows_per_block;
     plan->kv_block_rows = DecodeCfg<128>::TILE;
     plan->threads = DecodeCfg<128>::THREADS;
     plan->grid = (int)r.grid;
-    plan->lds_bytes = dHead == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
-    plan->combine_grid = r.ns > 1 ? (int)rows : 0;   // one workgroup per (batch, head, query row); ragged: per (head, token)
+    plan->lds_bytes = c.d == 128 ? DecodeCfg<128>::LDS_BYTES : DecodeCfg<64>::LDS_BYTES;
+    // one workgroup per (batch, head, query row); ragged: per (head, token)
+    plan->combine_grid = r.ns > 1 ? (int)((int64_t)(c.form.varlen ? 1 : c.B) * c.H * c.Sq) : 0;
     plan->combine_threads = r.ns > 1 ? 256 : 0;
+    return FA_OK;
 }
 
 int flash_attention_decode_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
                                        int numSplits, int windowSize, fa_decode_plan* plan) {
-    using namespace fa;
-    if (!plan) return FA_ERR_NULL_POINTER;
-    const SplitForm f = decode_form();
-    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
-                                      windowSize);
-    if (rc != FA_OK) return rc;
-    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize), dHead,
-                    (int64_t)batchSize * numHeads * seqLenQ);
-    return FA_OK;
+    return split_plan({.form = fa::decode_form(), .cache = {.capacity = seqLenK}, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV,
+                       .Sq = seqLenQ, .d = dHead, .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits, .window = windowSize},
+                      plan);
 }
 
 int flash_attention_decode_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
@@ -813,8 +874,11 @@ int flash_attention_decode(const void* Q, const void* K, const void* V, void* O,
                            int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale,
                            bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                            const fa_strides* sV, const fa_strides* sO, void* stream) {
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV, seqLenQ,
-                          seqLenK, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr, stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .kv_dtype = FA_DTYPE_BF16, .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -823,8 +887,11 @@ int flash_attention_decode_paged(const void* Q, const void* Kpool, const void* V
                                  bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK,
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, nullptr, nullptr, workspace, batchSize, numHeads, numHeadsKV,
-                          seqLenQ, 0, dHead, scale, is_causal, dtype, FA_DTYPE_BF16, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg, stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .kv_dtype = FA_DTYPE_BF16, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -833,9 +900,12 @@ int flash_attention_decode_fp8(const void* Q, const void* K, const void* V, void
                                int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                                const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
-                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, nullptr,
-                          stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                                     .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -846,9 +916,12 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
                                      const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
-                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, &pg,
-                          stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 // a bf16 cache has no descales: the logical cache is what lies in memory
@@ -862,9 +935,12 @@ int flash_attention_decode_window(const void* Q, const void* K, const void* V, v
                                   int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
                                   const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::decode_form(), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
-                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
-                          nullptr, stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                                     .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -875,22 +951,19 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                                         const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::decode_form(), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
-                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO,
-                          &pg, stream);
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_extend_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
                                        int numSplits, int windowSize, fa_decode_plan* plan) {
-    using namespace fa;
-    if (!plan) return FA_ERR_NULL_POINTER;
-    const SplitForm f = extend_form(dHead);
-    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
-                                      windowSize);
-    if (rc != FA_OK) return rc;
-    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, numSplits, windowSize), dHead,
-                    (int64_t)batchSize * numHeads * seqLenQ);
-    return FA_OK;
+    return split_plan({.form = fa::extend_form(dHead), .cache = {.capacity = seqLenK}, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV,
+                       .Sq = seqLenQ, .d = dHead, .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits, .window = windowSize},
+                      plan);
 }
 
 int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
@@ -904,9 +977,12 @@ int flash_attention_extend_window(const void* Q, const void* K, const void* V, v
                            int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
                            const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::extend_form(dHead), Q, K, V, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads, numHeadsKV,
-                          seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, nullptr,
-                          stream);
+    return fa::decode_run({.form = fa::extend_form(dHead), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                                     .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_extend(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -926,9 +1002,12 @@ int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const 
                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::extend_form(dHead), Q, Kpool, Vpool, O, LSE, nullptr, kvLens, kDescale, vDescale, workspace, batchSize, numHeads,
-                          numHeadsKV, seqLenQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, &pg,
-                          stream);
+    return fa::decode_run({.form = fa::extend_form(dHead), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -946,8 +1025,11 @@ int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void*
                               const float* vDescale, int batchSize, int numHeadsKV, int seqLenNew, int seqLenK, int dHead, int dtype,
                               int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
                               void* stream) {
-    return fa::kv_append_run(false, Knew, Vnew, K, V, nullptr, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, seqLenK, dHead, dtype,
-                             kv_dtype, sKnew, sVnew, sK, sV, nullptr, stream);
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream});
 }
 
 int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int32_t* kvLens,
@@ -956,21 +1038,19 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
                                     int dHead, int dtype, int kv_dtype, const fa_strides* sKnew, const fa_strides* sVnew,
                                     const fa_strides* sK, const fa_strides* sV, void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::kv_append_run(false, Knew, Vnew, Kpool, Vpool, nullptr, kvLens, kDescale, vDescale, batchSize, numHeadsKV, seqLenNew, 0, dHead, dtype,
-                             kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream});
 }
 
 int flash_attention_extend_varlen_plan_window(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
                                               int o_dtype, int numSplits, int windowSize, fa_decode_plan* plan) {
-    using namespace fa;
-    if (!plan) return FA_ERR_NULL_POINTER;
-    const SplitForm f = extend_varlen_form(dHead);
-    const int rc = decode_check_shape(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, dHead, FA_DTYPE_BF16, o_dtype, numSplits,
-                                      windowSize);
-    if (rc != FA_OK) return rc;
-    fill_split_plan(plan, f, decode_route(f, batchSize, numHeads, numHeadsKV, totalQ, seqLenK, numSplits, windowSize), dHead,
-                    (int64_t)numHeads * totalQ);
-    return FA_OK;
+    return split_plan({.form = fa::extend_varlen_form(dHead), .cache = {.capacity = seqLenK}, .B = batchSize, .H = numHeads,
+                       .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits,
+                       .window = windowSize},
+                      plan);
 }
 
 int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, int o_dtype,
@@ -985,9 +1065,12 @@ int flash_attention_extend_varlen_window(const void* Q, const void* K, const voi
                                   int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
                                   const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    return fa::decode_run(fa::extend_varlen_form(dHead), Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace, batchSize,
-                          numHeads, numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK,
-                          sV, sO, nullptr, stream);
+    return fa::decode_run({.form = fa::extend_varlen_form(dHead), .Q = Q, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                                     .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
@@ -1009,9 +1092,12 @@ int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool,
                                         void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run(fa::extend_varlen_form(dHead), Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, workspace,
-                          batchSize, numHeads, numHeadsKV, totalQ, 0, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ,
-                          sK, sV, sO, &pg, stream);
+    return fa::decode_run({.form = fa::extend_varlen_form(dHead), .Q = Q, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
 }
 
 int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
@@ -1031,8 +1117,11 @@ int flash_attention_kv_append_varlen(const void* Knew, const void* Vnew, void* K
                                      const int32_t* kvLens, const float* kDescale, const float* vDescale, int batchSize, int numHeadsKV,
                                      int totalQ, int seqLenK, int dHead, int dtype, int kv_dtype, const fa_strides* sKnew,
                                      const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV, void* stream) {
-    return fa::kv_append_run(true, Knew, Vnew, K, V, cuSeqlensQ, kvLens, kDescale, vDescale, batchSize, numHeadsKV, totalQ, seqLenK, dHead,
-                             dtype, kv_dtype, sKnew, sVnew, sK, sV, nullptr, stream);
+    return fa::kv_append_run({.varlen = true, .Knew = Knew, .Vnew = Vnew, .cu_seqlens_q = cuSeqlensQ,
+                              .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream});
 }
 
 int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int32_t* cuSeqlensQ,
@@ -1042,9 +1131,13 @@ int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, v
                                            const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
                                            void* stream) {
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::kv_append_run(true, Knew, Vnew, Kpool, Vpool, cuSeqlensQ, kvLens, kDescale, vDescale, batchSize, numHeadsKV, totalQ, 0,
-                             dHead, dtype, kv_dtype, sKnew, sVnew, sK, sV, &pg, stream);
+    return fa::kv_append_run({.varlen = true, .Knew = Knew, .Vnew = Vnew, .cu_seqlens_q = cuSeqlensQ,
+                              .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream});
 }
+
 
 const char* flash_attention_error_string(int code) {
     switch (code) {

@@ -597,28 +597,13 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const typename Spli
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (the inst_decode_*.hip, inst_extend_*.hip and inst_extend_varlen_*.hip units: one per cache form and call family) ----
+// ---- selectors (the inst_decode_*.hip and inst_extend_*.hip units: one per cache form and call family) ----
 struct Kernel;
-Kernel decode_split_kernel_of(int d);
-Kernel decode_paged_split_kernel_of(int d);
-Kernel decode_fp8_split_kernel_of(int d);
-Kernel decode_paged_fp8_split_kernel_of(int d);
-Kernel extend_split_kernel_of(int d);
-Kernel extend_paged_split_kernel_of(int d);
-Kernel extend_fp8_split_kernel_of(int d);
-Kernel extend_paged_fp8_split_kernel_of(int d);
-Kernel extend_varlen_split_kernel_of(int d);
-Kernel extend_varlen_paged_split_kernel_of(int d);
-Kernel extend_varlen_fp8_split_kernel_of(int d);
-Kernel extend_varlen_paged_fp8_split_kernel_of(int d);
-Kernel extend_window_split_kernel_of(int d);
-Kernel extend_window_paged_split_kernel_of(int d);
-Kernel extend_window_fp8_split_kernel_of(int d);
-Kernel extend_window_paged_fp8_split_kernel_of(int d);
-Kernel extend_window_varlen_split_kernel_of(int d);
-Kernel extend_window_varlen_paged_split_kernel_of(int d);
-Kernel extend_window_varlen_fp8_split_kernel_of(int d);
-Kernel extend_window_varlen_paged_fp8_split_kernel_of(int d);
+// The split kernel at D = d (128, else 64) with RT = EXTEND ? ExtendCfg<D>::RT : 1 and LDS for the cache's element size.  Defined in
+// split_kv_inst.hip.h and instantiated explicitly, once each, by the units: the four decode forms (EXTEND = VARLEN = false, WINDOW = true,
+// which also serves window = 0) and all sixteen chunked-prefill forms.  No other combination exists
+template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8>
+Kernel split_kernel_of(int d);
 Kernel extend_varlen_combine_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
 

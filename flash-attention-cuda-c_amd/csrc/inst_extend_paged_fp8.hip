@@ -1,14 +1,10 @@
 // inst_extend_paged_fp8.hip -- the paged fp8 (e4m3fn) cache form of chunked prefill against the decode caches: the split-KV kernel with
 // ExtendCfg::RT 16-row tiles per wave and no window, at D = 64 / 128 (one translation unit of libflash_attention.so: see launchers.hip.h and
 // decode_bf16.hip.h; built with the MFMAs in VGPR form: Makefile).  The combine kernel is decode's (inst_decode_bf16.hip).
-#include "decode_bf16.hip.h"
-#include "launchers.hip.h"
+#include "split_kv_inst.hip.h"
 
 namespace fa {
 
-Kernel extend_paged_fp8_split_kernel_of(int d) {
-    return d == 128 ? kernel_of<split_kv_kernel<128, ExtendCfg<128>::RT, true, true, false>>(DecodeCfg<128, 1>::LDS_BYTES)
-                    : kernel_of<split_kv_kernel<64, ExtendCfg<64>::RT, true, true, false>>(DecodeCfg<64, 1>::LDS_BYTES);
-}
+template Kernel split_kernel_of<true, false, false, true, true>(int);   // EXTEND, VARLEN, WINDOW, PAGED, KV8
 
 }  // namespace fa
