@@ -52,6 +52,7 @@ FA_FLAG_BF16_WEIGHTS = 2    # ... to bf16 on every row; flags = 0: fp16 on the r
 FA_EARLY_KEYS = 1024
 FA_DECODE_MAX_Q = 16        # flash_attention_decode: most new query rows per sequence
 FA_DECODE_MAX_SPLITS = 64   # ... and the cap of num_splits
+FA_DECODE_MAX_WORKGROUPS = 1 << 24   # the K/V-cache calls: plan grid, and rows of O under num_splits > 1, stay below it (FA_ERR_BAD_SHAPE)
 FA_VARLEN_MAX_BATCH = 1024  # flash_attention_extend_varlen, kv_cache_append_varlen: most sequences per call
 
 # every symbol include/flash_attention.h declares

@@ -431,6 +431,10 @@ static int decode_check_shape(const SplitCall& c) {
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
     const DecodeRoute r = decode_route(c);
     if (r.grid > INT32_MAX || r.row_blocks == INT32_MAX) return FA_ERR_BAD_SHAPE;
+    // one launch holds fewer than 2^32 threads (the runtime refuses more with a launch error, after the split kernel has run): the
+    // split kernel's grid of 256-thread workgroups and, under more than one split, the combine kernel's workgroup per row of O
+    const int64_t rows = (int64_t)(f.varlen ? 1 : B) * H * Sq;
+    if (r.grid >= FA_DECODE_MAX_WORKGROUPS || (r.ns > 1 && rows >= FA_DECODE_MAX_WORKGROUPS)) return FA_ERR_BAD_SHAPE;
     return FA_OK;
 }
 

@@ -406,6 +406,12 @@ int flash_attention_backward_gqa(const void* Q, const void* K, const void* V, co
  */
 #define FA_DECODE_MAX_Q 16          /* more new rows than this: that is chunked prefill, use flash_attention_gqa */
 #define FA_DECODE_MAX_SPLITS 64     /* cap of numSplits */
+/* Launch limit of every flash_attention_decode* / flash_attention_extend* call and plan: one launch holds fewer than 2^32 threads, in
+ * workgroups of 256.  plan.grid must stay below this, and so must the rows of O (batchSize * numHeads * seqLenQ; ragged: numHeads *
+ * totalQ) whenever num_splits > 1 -- the combine kernel runs one workgroup per row.  At or above it: FA_ERR_BAD_SHAPE, from the plan
+ * and from the call, before any launch.  numSplits = 0 never asks for a second split at such a row count (the units alone fill the
+ * chip), so only a FORCED numSplits > 1 meets the row limit */
+#define FA_DECODE_MAX_WORKGROUPS (1 << 24)
 
 typedef struct fa_decode_plan {
     int num_splits;      /* key-range splits per (batch, K/V head, row block) the call will use */
@@ -645,7 +651,8 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
  *
  * What differs from decode.
  *   seqLenQ  1 <= seqLenQ <= capacity (seqLenK, or maxPagesPerSeq * pageSize), not capped at FA_DECODE_MAX_Q.  batchSize * numHeads *
- *            seqLenQ and the grid must fit in an int32.  seqLenQ <= FA_DECODE_MAX_Q is legal and means what decode means: the result
+ *            seqLenQ and the grid must fit in an int32, and stay below FA_DECODE_MAX_WORKGROUPS as said there (2^24 rows of O under
+ *            two forced splits are refused; under numSplits = 0 they run unsplit).  seqLenQ <= FA_DECODE_MAX_Q is legal and means what decode means: the result
  *            is then flash_attention_decode*'s of the same arguments and the same forced numSplits, bit for bit (O and LSE), so a
  *            serving engine may cross 16 rows from one step to the next
  *   mask     decode's, unchanged: kvLens[b] ALREADY counts the new rows (`kv_lens += Sq; append; extend` is one graph).  With
@@ -729,7 +736,8 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
  *            launch, no workspace at num_splits == 1) and one beyond the real total returns at once.  combine_grid = numHeads * totalQ.
  *            numSplits = 0: flash_attention_extend_plan's rule and constants with units = numHeadsKV * NB; that rule is not measured
  *            for mixed batches
- * Limits.  numHeads * totalQ and the grid must fit in an int32; batchSize <= FA_VARLEN_MAX_BATCH; totalQ >= 1.
+ * Limits.  numHeads * totalQ and the grid must fit in an int32 and respect FA_DECODE_MAX_WORKGROUPS; batchSize <= FA_VARLEN_MAX_BATCH;
+ *            totalQ >= 1.
  * Rejected before any launch: everything flash_attention_extend* of the same form rejects, with the same codes and in the same order,
  * except its seqLenQ > capacity; a NULL cuSeqlensQ FA_ERR_NULL_POINTER; one not aligned to 4 bytes FA_ERR_MISALIGNED; totalQ < 1,
  * batchSize > FA_VARLEN_MAX_BATCH and the int32 limits FA_ERR_BAD_SHAPE.

@@ -89,9 +89,12 @@ int main() {
     BOTH(Extend, c.B = FA_VARLEN_MAX_BATCH, FA_ERR_NULL_POINTER);
     BOTH(Extend, c.T = 100000, FA_ERR_NULL_POINTER);                  // above the capacity: accepted
     BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = 1 << 27; c.ws = buffer, FA_ERR_BAD_SHAPE);            // numHeads * totalQ = 2^31
-    BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = (1 << 27) - 1, FA_ERR_NULL_POINTER);                  // ... 2^31 - 16
+    BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = (1 << 27) - 1; c.ws = buffer, FA_ERR_BAD_SHAPE);      // ... 2^31 - 16: FA_DECODE_MAX_WORKGROUPS
+    BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = 1 << 20; c.ws = buffer, FA_ERR_BAD_SHAPE);            // 2^24 rows of O under two splits
+    BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = (1 << 20) - 1, FA_ERR_NULL_POINTER);                  // ... 2^24 - 16
     BOTH(Extend, c.H = 16; c.Hkv = 16; c.T = 1 << 26; c.d = 64; c.ns = 64; c.ws = buffer, FA_ERR_BAD_SHAPE);   // the grid
-    BOTH(Extend, c.T = INT_MAX; c.H = 1; c.Hkv = 1; c.B = FA_VARLEN_MAX_BATCH, FA_ERR_NULL_POINTER);
+    BOTH(Extend, c.T = INT_MAX; c.H = 1; c.Hkv = 1; c.B = FA_VARLEN_MAX_BATCH; c.ws = buffer, FA_ERR_BAD_SHAPE);
+    BOTH(Extend, c.T = (1 << 24) - 1; c.H = 1; c.Hkv = 1; c.B = FA_VARLEN_MAX_BATCH, FA_ERR_NULL_POINTER);
     BOTH(Extend, c.Hkv = 3; c.ws = buffer, FA_ERR_BAD_SHAPE);
     BOTH(Extend, c.ns = FA_DECODE_MAX_SPLITS + 1; c.ws = buffer, FA_ERR_BAD_SHAPE);
     BOTH(Extend, c.dtype = FA_DTYPE_F32, FA_ERR_UNSUPPORTED_DTYPE);
@@ -127,7 +130,7 @@ int main() {
     EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH + 1, 8, 2, 300, 1024, 128, FA_DTYPE_F32, 0, &p), FA_ERR_BAD_SHAPE);
     for (int d : {64, 128})
         for (int B : {1, 3, 64, 130, FA_VARLEN_MAX_BATCH})
-            for (int T : {1, 17, 575, 4096, 1 << 20})
+            for (int T : {1, 17, 575, 4096, 1 << 17})   // (2^20 tokens of 32 heads are 2^25 rows of O: one split only, below)
                 for (int ns : {0, 1, 3, FA_DECODE_MAX_SPLITS}) {
                     const int H = 32, Hkv = 8, G = H / Hkv;
                     EXPECT(flash_attention_extend_varlen_plan(B, H, Hkv, T, 32768, d, FA_DTYPE_BF16, ns, &p), FA_OK);
@@ -142,8 +145,16 @@ int main() {
                     const size_t want = p.num_splits > 1 ? ((rows * ns_ * d * 4 + 15) & ~(size_t)15) + ((rows * ns_ * 4 + 15) & ~(size_t)15) : 0;
                     EXPECT(flash_attention_decode_workspace_size(1, H, T, d, p.num_splits), want);
                 }
-    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, INT_MAX, 1 << 24, 64, FA_DTYPE_F32, 1, &p), FA_OK);
-    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, INT_MAX, 1 << 24, 64, FA_DTYPE_F32, 64, &p), FA_ERR_BAD_SHAPE);
+    EXPECT(flash_attention_extend_varlen_plan(3, 32, 8, 1 << 20, 32768, 128, FA_DTYPE_BF16, 0, &p), FA_OK);
+    EXPECT(p.num_splits, 1);
+    EXPECT(flash_attention_extend_varlen_plan(3, 32, 8, 1 << 20, 32768, 128, FA_DTYPE_BF16, 3, &p), FA_ERR_BAD_SHAPE);
+    // a launch holds fewer than 2^32 threads: the grid under any split count, the rows of O under more than one
+    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, INT_MAX, 1 << 24, 64, FA_DTYPE_F32, 1, &p), FA_ERR_BAD_SHAPE);
+    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, 1 << 28, 1 << 24, 64, FA_DTYPE_F32, 1, &p), FA_OK);
+    EXPECT(p.grid < FA_DECODE_MAX_WORKGROUPS, true);
+    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, 1 << 28, 1 << 24, 64, FA_DTYPE_F32, 2, &p), FA_ERR_BAD_SHAPE);
+    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, (1 << 24) - 1, 1 << 24, 64, FA_DTYPE_F32, 2, &p), FA_OK);
+    EXPECT(flash_attention_extend_varlen_plan(FA_VARLEN_MAX_BATCH, 1, 1, 1 << 24, 1 << 24, 64, FA_DTYPE_F32, 2, &p), FA_ERR_BAD_SHAPE);
 
     // ---- the append ladder ----
     BOTH(Append, c.Kn = nullptr, FA_ERR_NULL_POINTER);

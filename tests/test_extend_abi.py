@@ -163,6 +163,39 @@ def test_the_plan():
     assert fa.lib().flash_attention_extend_plan(1, 32, 8, 20, 1024, 128, F32, 0, None) == NULL_POINTER
 
 
+def test_a_launch_stays_below_2_pow_32_threads():
+    """FA_DECODE_MAX_WORKGROUPS: the combine kernel runs one 256-thread workgroup per row of O, and the runtime refuses a launch of 2^32
+    threads after the split kernel has run (tests/test_long_cache.py met that at B H Sq = 2^24).  The plan and the call refuse it first"""
+    M = fa.FA_DECODE_MAX_WORKGROUPS
+    assert M == 1 << 24
+    B, H, Hkv, Sq, Sk, d = 2048, 8, 2, 1024, 1024, 64
+    assert B * H * Sq == M
+    for ns in (2, 3, CAP):
+        assert plan(B, H, Hkv, Sq, Sk, d, BF16, ns)[0] == BAD_SHAPE
+    for ns in (0, 1):                                             # one split has no combine launch; the library's choice at this size is one
+        rc, p = plan(B, H, Hkv, Sq, Sk, d, BF16, ns)
+        assert rc == 0 and p["num_splits"] == 1 and p["combine_grid"] == 0 and p["grid"] < M
+    rc, p = plan(B - 1, H, Hkv, Sq, Sk, d, BF16, 2)
+    assert rc == 0 and p["combine_grid"] == (B - 1) * H * Sq == M - H * Sq
+    # the split kernel's own grid: units * splits
+    units = (B - 1) * Hkv * p["row_blocks"]
+    ok, over = (M - 1) // units, -(-M // units)
+    assert 1 < ok < over <= CAP
+    rc, p = plan(B - 1, H, Hkv, Sq, Sk, d, BF16, ok)
+    assert rc == 0 and p["grid"] == units * ok < M
+    assert plan(B - 1, H, Hkv, Sq, Sk, d, BF16, over)[0] == BAD_SHAPE
+    # the same from the calls (fake pointers: a call that passes every check stops at its missing workspace), and from the ragged plan
+    contiguous, paged, _ = calls(BF16)
+    big = dict(B=B, H=H, Hkv=Hkv, Sq=Sq, d=d)
+    assert contiguous(Sk=Sk, **big) == BAD_SHAPE and paged(P=64, page=64, maxp=16, ts=16, **big) == BAD_SHAPE
+    assert contiguous(Sk=Sk, **dict(big, B=B - 1)) == NULL_POINTER and paged(P=64, page=64, maxp=16, ts=16, **dict(big, B=B - 1)) == NULL_POINTER
+    with pytest.raises(fa.FlashAttentionError) as e:
+        fa.extend_varlen_plan(4, H, Hkv, M // H, Sk, d, BF16, 2)
+    assert e.value.code == BAD_SHAPE
+    assert fa.extend_varlen_plan(4, H, Hkv, M // H - 1, Sk, d, BF16, 2)["combine_grid"] == M - H
+    assert fa.extend_varlen_plan(4, H, Hkv, M // H, Sk, d, BF16, 0)["num_splits"] == 1
+
+
 def test_the_workspace_formula_has_no_cap_on_the_chunk():
     """partial O [ns][rows][d] fp32, then partial LSE [ns][rows] fp32, each rounded up to 16 bytes; nothing for one split"""
     r16 = lambda n: (n + 15) & ~15

@@ -136,10 +136,18 @@ def test_total_q_is_a_bound_of_its_own_not_capped_by_the_capacity(kv):
     assert paged(T=33, page=16, maxp=2, ts=2) == NULL_POINTER
     # numHeads * totalQ must fit in an int32 (whatever the batch), and so must the grid
     assert contiguous(H=16, Hkv=16, T=1 << 27, ws=p) == BAD_SHAPE
-    assert contiguous(H=16, Hkv=16, T=(1 << 27) - 1) == NULL_POINTER                   # 2^31 - 16 rows: on to the workspace check
-    # the grid: d = 64 has 32-row blocks, NB = 2^21 + 1, 16 * NB * 64 > 2^31 - 1; with 32 splits it fits
-    assert contiguous(H=16, Hkv=16, T=1 << 26, d=64, ns=CAP, ws=p) == BAD_SHAPE
-    assert contiguous(H=16, Hkv=16, T=1 << 26, d=64, ns=32) == NULL_POINTER
+    assert contiguous(H=16, Hkv=16, T=1 << 26, d=64, ns=CAP, ws=p) == BAD_SHAPE       # (the grid: 16 * (2^21 + 1) * 64 > 2^31 - 1)
+    # ... and a launch holds fewer than 2^32 threads, FA_DECODE_MAX_WORKGROUPS = 2^24 workgroups of 256 (a launch of more is refused by
+    # the runtime, after the split kernel has run: tests/test_long_cache.py): the rows of O under more than one split -- the combine
+    # kernel's workgroups -- and the split kernel's grid under any.  (2^31 - 16 rows, which this test took for accepted, never ran)
+    M = fa.FA_DECODE_MAX_WORKGROUPS
+    assert contiguous(H=16, Hkv=16, T=(1 << 27) - 1, ws=p) == BAD_SHAPE
+    assert contiguous(H=16, Hkv=16, T=M // 16, ws=p) == BAD_SHAPE                      # 2^24 rows under two splits
+    assert contiguous(H=16, Hkv=16, T=M // 16 - 1) == NULL_POINTER                     # 2^24 - 16 rows: on to the workspace check
+    assert plan(2, 16, 16, M // 16, 1024, 128, ns=1)[0] == 0                           # one split has no combine launch
+    # the grid: d = 64 has 32-row blocks, NB = 2^14 + 1, 16 * NB * 64 >= 2^24; with 32 splits it fits
+    assert contiguous(H=16, Hkv=16, T=1 << 19, d=64, ns=CAP, ws=p) == BAD_SHAPE
+    assert contiguous(H=16, Hkv=16, T=1 << 19, d=64, ns=32) == NULL_POINTER
     # the library's own split count: a few rows on a long cache plan more than one split and the workspace is missing
     assert fa.extend_varlen_plan(2, 8, 2, 17, 32768, 128, F32)["num_splits"] > 1
     assert contiguous(ns=0, T=17, Sk=32768) == NULL_POINTER and paged(ns=0, T=17, maxp=512, ts=512) == NULL_POINTER
