@@ -28,7 +28,8 @@ tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill instantiations of the split-KV kernel at d = 128 (decode_bf16.hip.h with RT = 4: four 16-row tiles per wave, launch
 # bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
 # in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
-# (the wildcard takes the ragged instantiations, inst_extend_varlen_*.hip, with them: the same kernel with a per-sequence row count)
+# (the wildcard takes the ragged instantiations, inst_extend_varlen_*.hip, with them: the same kernel with a per-sequence row count;
+# and the attention-sink ones, inst_extend_sink_*.hip: the same kernel with one more term in its epilogue.  inst_decode_sink_*.hip: RT = 1, no flag)
 EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
 $(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)
 
@@ -86,7 +87,8 @@ CLANG_ASAN_RT := $(shell /opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_
 GCC_ASAN_RT   := $(shell gcc -print-file-name=libasan.so)
 SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # asan-host: the library's host code under the sanitizers, and tests/host_ladder.cpp -- a stand-alone program (its own main, built
-# with the same flags, nothing preloaded) that walks the validation ladders and the plans of the ragged entry points -- built and run.
+# with the same flags, nothing preloaded) that walks the validation ladders and the plans of the ragged entry points -- built and run;
+# tests/host_sink_ladder.cpp likewise: the ladders of the six attention-sink entry points beside their _window twins.
 asan-host: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip
@@ -94,6 +96,9 @@ asan-host: $(LIB)
 	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_ladder tests/host_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_ladder
+	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_sink_ladder tests/host_sink_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
+	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_sink_ladder
 
 asan: asan-host oracle
 	gcc -O1 -march=x86-64-v3 -fopenmp -fPIC -Wall -Wextra -std=c11 $(SANFLAGS) -shared -o $(ASAN_DIR)/liboracle_attention.so oracle/cpu_attention.c -lm

@@ -69,6 +69,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_extend_window", "flash_attention_extend_paged_window", "flash_attention_extend_plan_window",
            "flash_attention_extend_varlen_window", "flash_attention_extend_paged_varlen_window",
            "flash_attention_extend_varlen_plan_window",
+           "flash_attention_sink_decode", "flash_attention_sink_decode_paged", "flash_attention_sink_extend",
+           "flash_attention_sink_extend_paged", "flash_attention_sink_extend_varlen", "flash_attention_sink_extend_paged_varlen",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -81,6 +83,12 @@ _SPLIT_SYMBOLS = {
     ("extend", True, False): (("flash_attention_extend_paged",) * 2, ("flash_attention_extend_paged_window",) * 2),
     ("extend", False, True): (("flash_attention_extend_varlen",) * 2, ("flash_attention_extend_varlen_window",) * 2),
     ("extend", True, True): (("flash_attention_extend_paged_varlen",) * 2, ("flash_attention_extend_paged_varlen_window",) * 2),
+}
+# ... with ``sinks``: _SINK_SYMBOLS[family, paged, ragged], the ``_window`` entry point's signature with ``sinks`` after the descales
+_SINK_SYMBOLS = {
+    ("decode", False, False): "flash_attention_sink_decode", ("decode", True, False): "flash_attention_sink_decode_paged",
+    ("extend", False, False): "flash_attention_sink_extend", ("extend", True, False): "flash_attention_sink_extend_paged",
+    ("extend", False, True): "flash_attention_sink_extend_varlen", ("extend", True, True): "flash_attention_sink_extend_paged_varlen",
 }
 # ... _APPEND_SYMBOLS[paged, ragged], and the plan of a family: _PLAN_SYMBOLS[family, ragged][window > 0]
 _APPEND_SYMBOLS = {(False, False): "flash_attention_kv_append", (True, False): "flash_attention_kv_append_paged",
@@ -162,16 +170,18 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_decode_workspace_size.restype = ctypes.c_size_t
         # the split-KV and append families, from their parts: the tensors, cuSeqlensQ (ragged) before kvLens, the block table (paged),
         # the descales (every call but the bf16-only decode pair), then the ints with the cache geometry in the middle, kv_dtype next to
-        # dtype where there are descales, windowSize after numSplits, the strides and the stream
+        # dtype where there are descales, windowSize after numSplits, the strides and the stream; the sinks entry point of a form is
+        # its ``_window`` one with sinks after the descales
         paging = lambda paged: [i, i, i, ctypes.c_int64] if paged else [i]      # numPages, pageSize, maxPagesPerSeq, tableStride / seqLenK
         for (family, paged, ragged), by_window in _SPLIT_SYMBOLS.items():
             for window, by_cache in enumerate(by_window):
                 for fp8, name in enumerate(by_cache):
                     both = family == "extend" or bool(window) or bool(fp8)     # the entry point has descales and kv_dtype
-                    fn = getattr(L, name)
-                    fn.argtypes = [vp] * 5 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] * both + [vp] + [i] * 4 + paging(paged) \
-                        + [i, f, b, i] + [i] * both + [i, i] + [i] * window + [sp] * 4 + [vp]
-                    fn.restype = i
+                    fns = [(getattr(L, name), 0)] + ([(getattr(L, _SINK_SYMBOLS[family, paged, ragged]), 1)] if window else [])
+                    for fn, sink in fns:
+                        fn.argtypes = [vp] * 5 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] * both + [vp] * sink + [vp] + [i] * 4 \
+                            + paging(paged) + [i, f, b, i] + [i] * both + [i, i] + [i] * window + [sp] * 4 + [vp]
+                        fn.restype = i
         for (paged, ragged), name in _APPEND_SYMBOLS.items():
             fn = getattr(L, name)
             fn.argtypes = [vp] * 4 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, i] + [sp] * 4 + [vp]
@@ -550,12 +560,15 @@ def _table_geometry(block_table, B):
 
 
 def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
-                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None):
+                 num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None,
+                 sinks=None):
     """Every flash_attention_decode* / flash_attention_extend* front: ``family`` is "decode" or "extend", a ``block_table`` makes the call
     paged (K, V are then the pools) and ``cu_seqlens_q`` ragged (Q -- and O, if given -- are then packed by token: Sq is the bound on
     the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled).  The checks of the
     tensors, the plan and the workspace for the capacity, then the entry point of _SPLIT_SYMBOLS: the ones that take both cache types
-    get the descales and the cache's dtype code, the ``_window`` ones the window."""
+    get the descales and the cache's dtype code, the ``_window`` ones the window.  ``sinks`` (a dense fp32 ``[H]`` tensor on Q's device:
+    one attention-sink logit per query head, natural-log units, not scaled; read by the kernel): the same plan and workspace, then the
+    form's entry point of _SINK_SYMBOLS, which takes the descales, the cache's dtype code and the window (0 = none) in every form."""
     import torch
     paged, ragged = block_table is not None, cu_seqlens_q is not None
     symbols = _SPLIT_SYMBOLS[family, paged, ragged]
@@ -575,8 +588,11 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
     if ragged and O is not None:
         O = _token_view(O, "O")
     window = _window(window)
-    both = family == "extend" or bool(window)
+    both = family == "extend" or bool(window) or sinks is not None
     _, H, Sq, d = Q.shape
+    if sinks is not None and (getattr(sinks, "dtype", None) != torch.float32 or not sinks.is_cuda or sinks.device != Q.device
+                              or tuple(sinks.shape) != (H,) or not sinks.is_contiguous()):
+        raise ValueError("sinks must be a dense fp32 tensor [H] on the device of Q")
     new = torch.zeros if ragged else torch.empty      # ragged: rows no sequence owns are not written
     Hkv = K.shape[1]
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
@@ -607,10 +623,13 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
                 *map(ptr, tables))
         if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
+        if sinks is not None:
+            ptrs += (sinks.data_ptr(),)
         dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), symbols[bool(window)][fp8])
+        launch = getattr(lib(), _SINK_SYMBOLS[family, paged, ragged] if sinks is not None else symbols[bool(window)][fp8])
         rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
-                    _dtype_code(O.dtype), ns, *((window,) if window else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
+                    _dtype_code(O.dtype), ns, *((window,) if window or sinks is not None else ()), *[ctypes.byref(x) for x in st],
+                    _stream_ptr(s))
     _check(rc)
     if ragged:
         O = O.transpose(1, 2).squeeze(0)      # back to [T, H, d]
@@ -618,7 +637,7 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
 
 
 def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None):
+                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None, sinks=None):
     """Split-KV decode: Q ``[B, H, Sq, d]`` with 1 <= Sq <= FA_DECODE_MAX_Q new rows per sequence against a K/V cache
     ``[B, Hkv, capacity, d]`` (bf16, d = 64 or 128, Hkv dividing H; query head h reads K/V head ``h // (H // Hkv)``).
 
@@ -638,14 +657,21 @@ def flash_attention_decode(Q, K, V, kv_lens=None, scale=None, is_causal=False, o
     ``window``: None or 0 = none; W > 0 = a sliding window: row i sees at most the last W keys up to and including its own position,
     ``max(limC_i - W, 0) <= k`` with ``limC_i = max(kv_lens[b] - Sq + i + 1, 1)``, below ``limC_i`` with ``is_causal`` and below
     ``kv_lens[b]`` without (flash-attn's ``window_size=(W - 1, 0)`` / ``(W - 1, -1)``).  Keys below row 0's left edge are not read
-    and may hold anything; ``decode_plan(..., window=W)`` plans from the window's tiles.  A negative window raises ValueError."""
+    and may hold anything; ``decode_plan(..., window=W)`` plans from the window's tiles.  A negative window raises ValueError.
+
+    ``sinks``: None, or ATTENTION SINKS: a dense fp32 device tensor ``[H]``, one logit per query head (natural-log units, not
+    multiplied by ``scale``), read by the kernel like ``kv_lens``.  Every row's softmax gains one key of that score and value 0,
+    whatever the mask, the window and the length, once per row: ``O = sum_k exp(s_k) v_k / (sum_k exp(s_k) + exp(sink_h))`` and the
+    returned LSE includes the sink.  ``-inf`` is no sink (the call's bits without ``sinks``); any finite value gives finite results;
+    ``+inf`` / NaN are the caller's error.  The plan and the workspace do not depend on it.  Anything but such a tensor raises
+    ValueError.  Every decode and extend front takes it, with this meaning."""
     return _split_front("decode", Q, K, V, None, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                        k_descale, v_descale, window)
+                        k_descale, v_descale, window, sinks)
 
 
 def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
                                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
-                                 v_descale=None, window=None):
+                                 v_descale=None, window=None, sinks=None):
     """``flash_attention_decode`` against PAGED K/V caches: Q ``[B, H, Sq, d]``, pools ``[P, Hkv, page, d]`` (bf16, d = 64 or 128,
     page a power of two >= 16; strided views accepted, so a ``[P, page, Hkv, d]`` pool is ``pool.transpose(1, 2)``) and
     ``block_table``: int32 device tensor ``[B, max_pages]`` with a contiguous last dimension (a row slice of a wider table is
@@ -659,22 +685,23 @@ def flash_attention_decode_paged(Q, K_pool, V_pool, block_table, kv_lens=None, s
     ``O``, ``return_lse`` and ``stream`` as for ``flash_attention_decode``; the result is that call's on a contiguous copy of the
     same pages, bit for bit.  fp8 pools (``torch.float8_e4m3fn`` under a bf16 Q) with ``k_descale`` / ``v_descale`` as for
     ``flash_attention_decode``.  ``window`` as there: a page whose keys all lie below row 0's left edge is not read and neither is
-    its table entry, which may be any int32 (the engine may have freed the page).  No CPU fallback."""
+    its table entry, which may be any int32 (the engine may have freed the page).  ``sinks`` as there.  No CPU fallback."""
     return _split_front("decode", Q, K_pool, V_pool, block_table, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
-                        workspace, stream, k_descale, v_descale, window)
+                        workspace, stream, k_descale, v_descale, window, sinks)
 
 
 def flash_attention_extend(Q, K, V, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+                           O=None, workspace=None, stream=None, k_descale=None, v_descale=None, sinks=None):
     """Chunked prefill against a decode cache: Q ``[B, H, Sq, d]`` with 1 <= Sq <= capacity new rows per sequence against the K/V
     cache ``[B, Hkv, capacity, d]`` that ``flash_attention_decode`` reads (bf16, or ``torch.float8_e4m3fn`` under a bf16 Q with
     ``k_descale`` / ``v_descale``; d = 64 or 128, Hkv dividing H).  Everything is ``flash_attention_decode``'s -- ``kv_lens`` (which
     already counts the new rows: ``kv_lens += Sq; kv_cache_append; flash_attention_extend``), the bottom-right ``is_causal``,
     ``num_splits``, ``workspace`` (``decode_workspace_size`` bytes for ``extend_plan``'s split count), ``O``, ``return_lse``,
     ``stream`` -- without the cap on Sq and without ``window`` (that is ``flash_attention_extend_window``).  For Sq <= 16 the result is
-    that call's, bit for bit, under the same forced ``num_splits``.  No CPU fallback."""
+    that call's, bit for bit, under the same forced ``num_splits``.  ``sinks``: attention sinks, as in ``flash_attention_decode``.
+    No CPU fallback."""
     return _split_front("extend", Q, K, V, None, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
-                        k_descale, v_descale)
+                        k_descale, v_descale, sinks=sinks)
 
 
 def flash_attention_extend_window(Q, K, V, kv_lens=None, window=None, **kw):
@@ -690,13 +717,13 @@ def flash_attention_extend_window(Q, K, V, kv_lens=None, window=None, **kw):
 
 def flash_attention_extend_paged(Q, K_pool, V_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
                                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None,
-                                 v_descale=None):
+                                 v_descale=None, sinks=None):
     """``flash_attention_extend`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
     ``[B, max_pages]`` of ``flash_attention_decode_paged``, with that call's rules for the table, the lengths and the capacity
     ``max_pages * page`` (``extend_plan`` is asked with ``Sk = max_pages * page``).  The result is ``flash_attention_extend``'s on a
     contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_window``).  No CPU fallback."""
     return _split_front("extend", Q, K_pool, V_pool, block_table, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O,
-                        workspace, stream, k_descale, v_descale)
+                        workspace, stream, k_descale, v_descale, sinks=sinks)
 
 
 def flash_attention_extend_paged_window(Q, K_pool, V_pool, block_table, kv_lens=None, window=None, **kw):
@@ -707,7 +734,7 @@ def flash_attention_extend_paged_window(Q, K_pool, V_pool, block_table, kv_lens=
 
 
 def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
-                                  return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+                                  return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, sinks=None):
     """RAGGED chunked prefill against a decode cache: one call for a mixed batch -- decoding sequences, chunks of a prefill, idle
     slots -- on token-major tensors.  Q ``[T, H, d]`` bf16 (strided views accepted, last dimension contiguous), packed by token;
     ``cu_seqlens_q``: int32 device tensor ``[B + 1]``, sequence b owns the rows ``cu[b] .. cu[b + 1] - 1`` (each pair clamped into
@@ -722,7 +749,7 @@ def flash_attention_extend_varlen(Q, K, V, cu_seqlens_q, kv_lens=None, scale=Non
     ``return_lse``, ``(O, LSE)`` with the LSE fp32 ``[H, T]``; an O or LSE allocated here is zero-filled.  No ``window``
     (``flash_attention_extend_varlen_window``).  No CPU fallback."""
     return _split_front("extend", Q, K, V, None, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace,
-                        stream, k_descale, v_descale)
+                        stream, k_descale, v_descale, sinks=sinks)
 
 
 def flash_attention_extend_varlen_window(Q, K, V, cu_seqlens_q, kv_lens=None, window=None, **kw):
@@ -735,13 +762,13 @@ def flash_attention_extend_varlen_window(Q, K, V, cu_seqlens_q, kv_lens=None, wi
 
 def flash_attention_extend_paged_varlen(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
                                         out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None,
-                                        k_descale=None, v_descale=None):
+                                        k_descale=None, v_descale=None, sinks=None):
     """``flash_attention_extend_varlen`` against PAGED K/V caches: the pools ``[P, Hkv, page, d]`` and the int32 ``block_table``
     ``[B, max_pages]`` of ``flash_attention_extend_paged`` (``extend_varlen_plan`` is asked with ``Sk = max_pages * page``).  The
     table row and the length of a sequence without rows are not read.  The result is ``flash_attention_extend_varlen``'s on a
     contiguous copy of the same pages, bit for bit.  No ``window`` (``flash_attention_extend_paged_varlen_window``).  No CPU fallback."""
     return _split_front("extend", Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, num_splits,
-                        return_lse, O, workspace, stream, k_descale, v_descale)
+                        return_lse, O, workspace, stream, k_descale, v_descale, sinks=sinks)
 
 
 def flash_attention_extend_paged_varlen_window(Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens=None, window=None, **kw):

@@ -362,6 +362,8 @@ struct KvCache {
 // argument for stays 0 / NULL) and the three plan functions fill its shape.  window: 0, or the sliding window W of the _window entry
 // points.  Ragged (form.varlen; flash_attention_extend*_varlen): Sq is totalQ, Q / O are packed by token (strideB is not read; NULL
 // strides: [totalQ, H, d]), the LSE and the slabs are [H, totalQ], and cu_seqlens_q -- NULL in every other call -- is required.
+// sinks: NULL, or the [H] attention-sink logits of the flash_attention_sink_* entry points (the last member: every other entry point's
+// initialiser leaves it NULL).
 struct SplitCall {
     SplitForm form;
     const void* Q;
@@ -376,6 +378,7 @@ struct SplitCall {
     int dtype, o_dtype, num_splits, window;
     const fa_strides *sQ, *sO;
     void* stream;
+    const float* sinks;
 };
 
 // A call of the append kernels: Sq new rows per sequence (ragged: totalQ token-packed rows, cu_seqlens_q required) into the cache
@@ -485,11 +488,16 @@ static bool cache_extent_ok(const KvCache& c, int d) {
 // rows of one head of one batch entry / page: what NULL K / V strides are dense over
 static int cache_rows(const KvCache& c) { return c.paging ? c.paging->page_size : c.capacity; }
 
-// The instantiation a call launches, of the twenty that exist: decode's four are WINDOW = true and serve window = 0 too; chunked
-// prefill with windowSize = 0 launches its WINDOW = false units
-static Kernel split_kernel(const SplitCall& c) {
+// The instantiation a call launches, of the twenty that exist without sinks: decode's four are WINDOW = true and serve window = 0 too; chunked
+// prefill with windowSize = 0 launches its WINDOW = false units.  sink (a sinks call under ONE split: the kernel that writes O applies
+// the sink): the twelve SINK forms, all WINDOW = true -- chunked prefill with windowSize = 0 then runs at window = 0, as decode does
+static Kernel split_kernel(const SplitCall& c, bool sink) {
     return by_bool(c.cache.paging != nullptr, [&]<bool PAGED>() {
         return by_bool(c.cache.kv_dtype == FA_DTYPE_FP8_E4M3, [&]<bool KV8>() {
+            if (sink)
+                return c.form.extend
+                           ? by_bool(c.form.varlen, [&]<bool VARLEN>() { return split_kernel_of<true, VARLEN, true, PAGED, KV8, true>(c.d); })
+                           : split_kernel_of<false, false, true, PAGED, KV8, true>(c.d);
             if (!c.form.extend) return split_kernel_of<false, false, true, PAGED, KV8>(c.d);
             return by_bool(c.form.varlen, [&]<bool VARLEN>() {
                 return by_bool(c.window > 0, [&]<bool WINDOW>() { return split_kernel_of<true, VARLEN, WINDOW, PAGED, KV8>(c.d); });
@@ -508,6 +516,7 @@ static int decode_run(SplitCall c) {
         return FA_ERR_MISALIGNED;
     int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
     if (rc != FA_OK) return rc;
+    if (misaligned4(c.sinks)) return FA_ERR_MISALIGNED;
     if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
     fa_strides tQ{}, tO{};   // ragged: Q and O on their token strides
     if (f.varlen) {
@@ -525,7 +534,7 @@ static int decode_run(SplitCall c) {
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
     const int rowsK = cache_rows(c.cache);
-    VarlenDecodeParams p;   // (what every other form launches with is its DecodeParams part)
+    SinkVarlenDecodeParams p;   // (what every form launches with is a part of it: go, below)
     p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.cache.K; p.V = (const __bf16*)c.cache.V; p.O = c.O; p.lse = c.LSE;
     p.kv_lens = c.cache.kv_lens;
     p.part_o = (float*)c.workspace;
@@ -549,16 +558,25 @@ static int decode_run(SplitCall c) {
     p.window = c.window;
     p.cu_q = c.cu_seqlens_q;
     p.B = c.B;
+    p.sinks = c.sinks;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
-    const Kernel sk = split_kernel(c);
-    if (f.varlen) {
-        const hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, p);
-        if (e != hipSuccess || r.ns == 1) return (int)e;
-        return (int)launch(extend_varlen_combine_kernel_of(d), (unsigned)rows, 256, 0, st, p);
-    }
-    hipError_t e = launch(sk, (unsigned)r.grid, DecodeCfg<128>::THREADS, sk.lds_bytes, st, (DecodeParams)p);
+    // Sinks (c.sinks): the kernel that writes O applies them -- under one split the SINK split kernel; under more
+    // the split kernel is the call's own without sinks (the slabs hold the keys alone) and the SINK combine adds the sink, once per row
+    const bool sink = c.sinks != nullptr;
+    const Kernel sk = split_kernel(c, sink && r.ns == 1);
+    const auto go = [&](const Kernel& k, unsigned grid, int lds, bool with_sinks) {   // each kernel with its exact parameter type
+        if (f.varlen) return with_sinks ? launch(k, grid, 256, lds, st, p) : launch(k, grid, 256, lds, st, (VarlenDecodeParams)p);
+        SinkDecodeParams ps;
+        (DecodeParams&)ps = p;
+        ps.sinks = p.sinks;
+        return with_sinks ? launch(k, grid, 256, lds, st, ps) : launch(k, grid, 256, lds, st, (DecodeParams)p);
+    };
+    static_assert(DecodeCfg<128>::THREADS == 256);
+    const hipError_t e = go(sk, (unsigned)r.grid, sk.lds_bytes, sink && r.ns == 1);
     if (e != hipSuccess || r.ns == 1) return (int)e;
-    return (int)launch(decode_combine_kernel_of(d), (unsigned)rows, 256, 0, st, (DecodeParams)p);
+    const Kernel ck = f.varlen ? (sink ? extend_varlen_sink_combine_kernel_of(d) : extend_varlen_combine_kernel_of(d))
+                               : (sink ? decode_sink_combine_kernel_of(d) : decode_combine_kernel_of(d));
+    return (int)go(ck, (unsigned)rows, 0, sink);
 }
 
 // ---- K/V cache append (kv_append.hip.h) ----
@@ -933,18 +951,44 @@ static bool window_descales_ok(int kv_dtype, const float* kDescale, const float*
     return kv_dtype == FA_DTYPE_FP8_E4M3 || (!kDescale && !vDescale);
 }
 
-int flash_attention_decode_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
-                                  const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
-                                  int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
-                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
-                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+int flash_attention_sink_decode(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                                const float* kDescale, const float* vDescale, const float* sinks, void* workspace, int batchSize,
+                                int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
                            .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
                                      .capacity = seqLenK, .sK = sK, .sV = sV},
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
                            .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
+}
+
+int flash_attention_decode_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                                  const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                                  int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+    return flash_attention_sink_decode(Q, K, V, O, LSE, kvLens, kDescale, vDescale, nullptr, workspace, batchSize, numHeads, numHeadsKV,
+                                       seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK,
+                                       sV, sO, stream);
+}
+
+int flash_attention_sink_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                      const int32_t* blockTable, const float* kDescale, const float* vDescale, const float* sinks,
+                                      void* workspace, int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                      int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                      int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                      const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
 }
 
 int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -953,14 +997,9 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
                                         int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
                                         int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ,
                                         const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
-    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
-    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
-    return fa::decode_run({.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
-                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
-                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
-                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
-                           .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+    return flash_attention_sink_decode_paged(Q, Kpool, Vpool, O, LSE, kvLens, blockTable, kDescale, vDescale, nullptr, workspace, batchSize,
+                                             numHeads, numHeadsKV, seqLenQ, numPages, pageSize, maxPagesPerSeq, tableStride, dHead, scale,
+                                             is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_extend_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
@@ -975,18 +1014,28 @@ int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int
     return flash_attention_extend_plan_window(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, numSplits, 0, plan);
 }
 
-int flash_attention_extend_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
-                           const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
-                           int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
-                           int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
-                           const fa_strides* sO, void* stream) {
+int flash_attention_sink_extend(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                                const float* kDescale, const float* vDescale, const float* sinks, void* workspace, int batchSize,
+                                int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     return fa::decode_run({.form = fa::extend_form(dHead), .Q = Q, .O = O, .LSE = LSE,
                            .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
                                      .capacity = seqLenK, .sK = sK, .sV = sV},
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
                            .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
+}
+
+int flash_attention_extend_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
+                           const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                           int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype, int kv_dtype,
+                           int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                           const fa_strides* sO, void* stream) {
+    return flash_attention_sink_extend(Q, K, V, O, LSE, kvLens, kDescale, vDescale, nullptr, workspace, batchSize, numHeads, numHeadsKV,
+                                       seqLenQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK,
+                                       sV, sO, stream);
 }
 
 int flash_attention_extend(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens,
@@ -998,12 +1047,12 @@ int flash_attention_extend(const void* Q, const void* K, const void* V, void* O,
                                          seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, 0, sQ, sK, sV, sO, stream);
 }
 
-int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
-                                 const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
-                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
-                                 int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
-                                 int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
-                                 const fa_strides* sV, const fa_strides* sO, void* stream) {
+int flash_attention_sink_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                      const int32_t* blockTable, const float* kDescale, const float* vDescale, const float* sinks,
+                                      void* workspace, int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                      int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                      int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                      const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run({.form = fa::extend_form(dHead), .Q = Q, .O = O, .LSE = LSE,
@@ -1011,7 +1060,18 @@ int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const 
                                      .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
                            .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
+}
+
+int flash_attention_extend_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                                 const int32_t* blockTable, const float* kDescale, const float* vDescale, void* workspace,
+                                 int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize,
+                                 int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                 int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                 const fa_strides* sV, const fa_strides* sO, void* stream) {
+    return flash_attention_sink_extend_paged(Q, Kpool, Vpool, O, LSE, kvLens, blockTable, kDescale, vDescale, nullptr, workspace, batchSize,
+                                             numHeads, numHeadsKV, seqLenQ, numPages, pageSize, maxPagesPerSeq, tableStride, dHead, scale,
+                                             is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize, sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
@@ -1063,18 +1123,29 @@ int flash_attention_extend_varlen_plan(int batchSize, int numHeads, int numHeads
                                                      plan);
 }
 
-int flash_attention_extend_varlen_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
-                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int batchSize,
-                                  int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
-                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
-                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+int flash_attention_sink_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                                       const int32_t* kvLens, const float* kDescale, const float* vDescale, const float* sinks,
+                                       void* workspace, int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                       float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int windowSize,
+                                       const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                       void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     return fa::decode_run({.form = fa::extend_varlen_form(dHead), .Q = Q, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ,
                            .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
                                      .capacity = seqLenK, .sK = sK, .sV = sV},
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead,
                            .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
+}
+
+int flash_attention_extend_varlen_window(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                                  const int32_t* kvLens, const float* kDescale, const float* vDescale, void* workspace, int batchSize,
+                                  int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead, float scale, bool is_causal, int dtype,
+                                  int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                                  const fa_strides* sV, const fa_strides* sO, void* stream) {
+    return flash_attention_sink_extend_varlen(Q, K, V, O, LSE, cuSeqlensQ, kvLens, kDescale, vDescale, nullptr, workspace, batchSize,
+                                              numHeads, numHeadsKV, totalQ, seqLenK, dHead, scale, is_causal, dtype, kv_dtype, o_dtype,
+                                              numSplits, windowSize, sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* cuSeqlensQ,
@@ -1087,13 +1158,13 @@ int flash_attention_extend_varlen(const void* Q, const void* K, const void* V, v
                                                 0, sQ, sK, sV, sO, stream);
 }
 
-int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
-                                        const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
-                                        const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
-                                        int numHeadsKV, int totalQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
-                                        int dHead, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int windowSize,
-                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
-                                        void* stream) {
+int flash_attention_sink_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                             const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                             const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                             int batchSize, int numHeads, int numHeadsKV, int totalQ, int numPages, int pageSize,
+                                             int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                             int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ,
+                                             const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
     if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::decode_run({.form = fa::extend_varlen_form(dHead), .Q = Q, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ,
@@ -1101,7 +1172,20 @@ int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool,
                                      .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead,
                            .scale = scale, .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
-                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream});
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks});
+}
+
+int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                        const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                        const float* kDescale, const float* vDescale, void* workspace, int batchSize, int numHeads,
+                                        int numHeadsKV, int totalQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                        int dHead, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, int windowSize,
+                                        const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                        void* stream) {
+    return flash_attention_sink_extend_paged_varlen(Q, Kpool, Vpool, O, LSE, cuSeqlensQ, kvLens, blockTable, kDescale, vDescale, nullptr,
+                                                    workspace, batchSize, numHeads, numHeadsKV, totalQ, numPages, pageSize, maxPagesPerSeq,
+                                                    tableStride, dHead, scale, is_causal, dtype, kv_dtype, o_dtype, numSplits, windowSize,
+                                                    sQ, sK, sV, sO, stream);
 }
 
 int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,

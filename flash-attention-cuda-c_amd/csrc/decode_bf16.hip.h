@@ -80,6 +80,12 @@
 //     the scalar sq_b, a Q / O row is token cu_q[b] + i on the token strides, a slab / LSE row is h * totalQ + cu_q[b] + i.  The
 //     per-row text is untouched: sequence b's bits are those of the RT > 1 kernel on that sequence alone.  With VARLEN = false every
 //     term of this bullet folds away.
+//   * SINK (flash_attention_sink_*): an attention sink is a logit per QUERY head (sinks[h], natural log, not scaled)
+//     that joins every row's softmax as one more key with value 0, whatever the mask, the window and the length, once per row.  The loop
+//     knows nothing of it: it is added to (M, L) in the epilogue of the kernel that writes O -- under one split this kernel (the p.ns == 1
+//     branch), under more the combine kernel, which takes it as one more partial result with O = 0; the slabs hold the keys alone either
+//     way.  The SINK forms take parameter types of their own (SinkDecodeParams, SinkVarlenDecodeParams: the struct + the pointer), so the
+//     SINK = false kernels' arguments are what they were; sinks = -inf reproduces their bits.  With SINK = false every term folds away.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -122,13 +128,29 @@ struct VarlenDecodeParams : DecodeParams {
     const int32_t* cu_q;          // [B + 1] (device memory): sequence b owns the packed rows [cu_q[b], cu_q[b + 1]), clamped into [0, Sq]
     int B;
 };
-template <bool VARLEN>
+// The attention-sink (SINK) kernels' arguments (flash_attention_sink_*): types of their own for the same reason --
+// DecodeParams and VarlenDecodeParams keep their size and layout, so the kernels that take them stay what they were
+struct SinkDecodeParams : DecodeParams {
+    const float* sinks;           // [H] (device memory): one logit per QUERY head, natural-log units, not multiplied by the scale
+};
+struct SinkVarlenDecodeParams : VarlenDecodeParams {
+    const float* sinks;
+};
+template <bool VARLEN, bool SINK = false>
 struct SplitParamsOf {
     using type = DecodeParams;
 };
 template <>
-struct SplitParamsOf<true> {
+struct SplitParamsOf<true, false> {
     using type = VarlenDecodeParams;
+};
+template <>
+struct SplitParamsOf<false, true> {
+    using type = SinkDecodeParams;
+};
+template <>
+struct SplitParamsOf<true, true> {
+    using type = SinkVarlenDecodeParams;
 };
 
 template <int D, int ES = 2>   // ES: bytes per K/V element in memory (2: bf16, 1: e4m3fn); the LDS image of V is bf16 either way
@@ -213,9 +235,11 @@ __device__ __forceinline__ bool varlen_unit_of(const VarlenDecodeParams& p, int 
 }
 
 // Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false (windowSize = 0) or true (the _window calls);
-// ragged chunked prefill: those with VARLEN.
-template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false>
-__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN>::type p) {
+// ragged chunked prefill: those with VARLEN.  SINK (WINDOW = true only; launched with ns = 1 only -- under more splits the sink is the
+// combine's): the epilogue adds the row's head's sink, a key with value 0, to (M, L) before it normalises; the loop is the same text.
+template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false, bool SINK = false>
+__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN, SINK>::type p) {
+    static_assert(!SINK || WINDOW, "the SINK forms are WINDOW = true: a sinks call without a window runs them at window = 0");
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
@@ -532,7 +556,24 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
             const int og = opr / Sq, oi = opr - og * Sq, oh = kvh * p.G + og;
             float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
             if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
-            const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;   // ... LSE = -inf
+            float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;         // ... LSE = -inf
+            if constexpr (SINK) {
+                // one more key of score sinks[head] (natural log, no scale) and value 0, once per row: with sk its log2-domain score,
+                //   M' = max(M, sk),  L' = L exp2(M - M') + exp2(sk - M'),  O = acc exp2(M - M') / L',  LSE = (M' + log2 L') ln 2
+                // -- every exponent is <= 0, so a sink of any finite size gives finite O and LSE.  sinks = -inf: M' = M, exp2(0) = 1,
+                // exp2(-inf) = 0 and every bit is the SINK = false form's.  (ns > 1: the slabs hold the keys alone)
+                if (p.ns == 1) {
+                    const float sk = p.sinks[oh] * 1.4426950408889634f;
+                    const float M2 = fmaxf(M, sk);
+                    if (M2 != NEG_INF) {
+                        const float e = fast_exp2(M - M2);
+                        const float L2 = L * e + fast_exp2(sk - M2);
+                        inv = 1.0f / L2 * e;
+                        if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;
+                        lse = (M2 + __log2f(L2)) * 0.6931471805599453f;
+                    }
+                }
+            }
             const int64_t row = VARLEN ? (int64_t)oh * p.Sq + q0 + oi : ((int64_t)b * p.H + oh) * Sq + oi;
             if (p.ns == 1) {
                 const int64_t base = (VARLEN ? 0 : b * p.oB) + oh * p.oH + (q0 + oi) * p.oS + d0;
@@ -558,8 +599,11 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
 // not empty (every sequence has a key), so m is finite and an empty split's weight is exp(-inf) = 0.
 // VARLEN (the ragged form: B = 1 to this kernel, Sq = totalQ, oB not read): a row is (head, token), and the tokens no sequence owns --
 // below cu_q[0], at and beyond cu_q[B] -- have no partial results and are not written: their workgroups leave before the first barrier.
-template <int D, bool VARLEN = false>
-__global__ __launch_bounds__(256) void decode_combine_kernel(const typename SplitParamsOf<VARLEN>::type p) {
+// SINK (flash_attention_sink_* under more than one split): the row's head's sink is one more partial result with
+// O = 0 and LSE = sinks[head]: m = max(m, sink), one term exp(sink - m) more in the sum of the weights.  sinks = -inf: that term is
+// exp(-inf) = 0, m is the splits' and every bit is the SINK = false form's.
+template <int D, bool VARLEN = false, bool SINK = false>
+__global__ __launch_bounds__(256) void decode_combine_kernel(const typename SplitParamsOf<VARLEN, SINK>::type p) {
     static_assert(FA_DECODE_MAX_SPLITS <= WAVE, "one split per lane");
     constexpr int TPR = D / 4, SLOTS = 256 / TPR;
     __shared__ float wgt[WAVE];
@@ -573,10 +617,16 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const typename Spli
     float M = mine;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    float sink = 0.f;
+    if constexpr (SINK) {
+        sink = p.sinks[row / p.Sq % p.H];
+        M = fmaxf(M, sink);
+    }
     const float w = __expf(mine - M);
     float W = w;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) W += __shfl_xor(W, o);   // (a butterfly: the same sum, bit for bit, in every lane and wave)
+    if constexpr (SINK) W += __expf(sink - M);
     if (tid < WAVE) wgt[tid] = w;
     __syncthreads();
     const int c = tid % TPR, slot = tid / TPR;
@@ -601,10 +651,13 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const typename Spli
 struct Kernel;
 // The split kernel at D = d (128, else 64) with RT = EXTEND ? ExtendCfg<D>::RT : 1 and LDS for the cache's element size.  Defined in
 // split_kv_inst.hip.h and instantiated explicitly, once each, by the units: the four decode forms (EXTEND = VARLEN = false, WINDOW = true,
-// which also serves window = 0) and all sixteen chunked-prefill forms.  No other combination exists
-template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8>
+// which also serves window = 0) and all sixteen chunked-prefill forms; with SINK the twelve WINDOW = true forms of those, by the
+// inst_decode_sink_*.hip and inst_extend_sink_*.hip units.  No other combination exists
+template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK = false>
 Kernel split_kernel_of(int d);
 Kernel extend_varlen_combine_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);
+Kernel extend_varlen_sink_combine_kernel_of(int d);   // (the SINK combines: inst_extend_sink_varlen_bf16.hip, inst_decode_sink_bf16.hip)
+Kernel decode_sink_combine_kernel_of(int d);
 
 }  // namespace fa

@@ -528,8 +528,8 @@ int flash_attention_decode_paged_fp8(const void* Q, const void* Kpool, const voi
  *   is_causal = false   row i sees the keys lo_i <= k < len         (window_size = (windowSize - 1, -1): the left edge still follows
  *                       the row's own position)
  * Every row sees at least one key: no NaN rows.  windowSize = 0: no window -- the call is the sibling's (flash_attention_decode,
- * _paged, _fp8, _paged_fp8 by kv_dtype and form): the same launches, the same bits.  There is no right window, no attention sink and
- * no per-head window.
+ * _paged, _fp8, _paged_fp8 by kv_dtype and form): the same launches, the same bits.  There is no right window and no per-head window (attention
+ * sinks: flash_attention_sink_decode*, below).
  *
  * Below the window.  first(b) = lo_0 is the lowest key any row of sequence b sees.  The contract mirrors the one for keys at and
  * beyond kvLens[b]: keys below first(b) never enter the result; their K and V may hold NaN, inf, stale data or any fp8 byte (0x7F /
@@ -672,7 +672,7 @@ int flash_attention_kv_append_paged(const void* Knew, const void* Vnew, void* Kp
  *            caveat on V; e4m3fn -> bf16 exactly, in registers, kDescale folded into the score scale and vDescale into the final 1 / l
  * Rejected before any launch: everything the decode sibling of the same form and kv_dtype rejects, with the same codes, except the
  * FA_DECODE_MAX_Q cap; seqLenQ > capacity FA_ERR_BAD_SHAPE; a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE.
- * Not done here: attention sinks, fp8 Q, a backward, automatic routing from or to any existing call.  A per-sequence count of new rows
+ * Not done here: fp8 Q, a backward, automatic routing from or to any existing call.  A per-sequence count of new rows
  * is flash_attention_extend_varlen's (below): here every sequence brings seqLenQ rows.  A sliding window is the _window calls' (below).
  */
 int flash_attention_extend_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
@@ -741,7 +741,7 @@ int flash_attention_extend_paged(const void* Q, const void* Kpool, const void* V
  * Rejected before any launch: everything flash_attention_extend* of the same form rejects, with the same codes and in the same order,
  * except its seqLenQ > capacity; a NULL cuSeqlensQ FA_ERR_NULL_POINTER; one not aligned to 4 bytes FA_ERR_MISALIGNED; totalQ < 1,
  * batchSize > FA_VARLEN_MAX_BATCH and the int32 limits FA_ERR_BAD_SHAPE.
- * Not done here: a per-unit choice of rows_per_block, reordering units by length, attention sinks, fp8 Q, routing.  A sliding window
+ * Not done here: a per-unit choice of rows_per_block, reordering units by length, fp8 Q, routing.  A sliding window
  * is the _window calls' (below).
  */
 #define FA_VARLEN_MAX_BATCH 1024    /* sequences per ragged call: the unit lookup scans them 64 at a time, 16 steps at the most */
@@ -808,7 +808,7 @@ int flash_attention_extend_paged_varlen(const void* Q, const void* Kpool, const 
  *
  * Rejected before any launch: everything the sibling rejects, with the same codes and in the same order; windowSize < 0
  * FA_ERR_BAD_SHAPE.
- * Not done here: attention sinks, a right window, per-head windows, ring-buffer caches, windows in the prefill / backward kernels.
+ * Not done here: a right window, per-head windows, ring-buffer caches, windows and attention sinks in the prefill / backward kernels.
  */
 int flash_attention_extend_plan_window(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
                                        int o_dtype, int numSplits /* 0 = the library chooses */, int windowSize,
@@ -854,6 +854,89 @@ int flash_attention_extend_paged_varlen_window(const void* Q, const void* Kpool,
                                                int numSplits, int windowSize,
                                                const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
                                                void* stream);
+
+/*
+ * flash_attention_sink_decode, _decode_paged, _extend, _extend_paged, _extend_varlen, _extend_paged_varlen -- ATTENTION SINKS in the
+ * K/V-cache calls: a learned logit per query head that takes part in every row's softmax as one more key whose value is 0 (the
+ * sink-trained GQA models: alternating full and windowed layers).  Each call is its _window twin -- flash_attention_decode_window,
+ * flash_attention_decode_paged_window, flash_attention_extend_window, flash_attention_extend_paged_window,
+ * flash_attention_extend_varlen_window, flash_attention_extend_paged_varlen_window -- with one argument more, directly after vDescale:
+ *   sinks    [numHeads] fp32 (device memory), or NULL.  One logit per QUERY head: packed row g * Sq + i of K/V head kvh uses
+ *            sinks[kvh * (numHeads / numHeadsKV) + g].  Natural-log units, NOT multiplied by scale.  Read by the kernel, like kvLens
+ *            and the descales: no host synchronisation, and a replayed graph sees the values of the moment
+ * For a row with the visible scores s_k = scale q.k:
+ *   O   = sum_k exp(s_k) v_k / (sum_k exp(s_k) + exp(sink_h))
+ *   LSE = ln(sum_k exp(s_k) + exp(sink_h))                              (the returned LSE includes the sink)
+ * The sink is visible to every row whatever the mask, the window and the length, and it is counted once per row, not once per split.
+ * sink = -inf is "no sink": O and LSE are, bit for bit, those of the call without sinks.  A finite value of any size gives finite O
+ * and LSE (a sink far above every score: O = 0, LSE = sink).  +inf and NaN are the caller's error: the row's O and LSE are then NaN.
+ *
+ * sinks = NULL is the _window twin itself: the same launches, the same bits.  windowSize = 0: no window.  Plans and workspace sizes
+ * do not depend on sinks: flash_attention_decode_plan_window / flash_attention_extend_plan_window /
+ * flash_attention_extend_varlen_plan_window and flash_attention_decode_workspace_size describe these calls.  The launches are the
+ * twin's in number, grids and LDS: under one split the split kernel's SINK form, under more the twin's split kernel (the slabs hold
+ * the keys alone) and the combine kernel's SINK form.  Every equality of the twins holds with sinks too: paged = contiguous on a copy
+ * of the same pages, seqLenQ <= FA_DECODE_MAX_Q chunked prefill = decode, a ragged sequence = the uniform call on it alone, and
+ * nothing beyond the length or below the window is read.
+ *
+ * Rejected before any launch: everything the twin rejects, with the same codes and in the same order; a sinks pointer not aligned
+ * to 4 bytes FA_ERR_MISALIGNED, directly after the twin's alignment checks of kvLens, cuSeqlensQ, blockTable and the descales.
+ * Not done here: sinks in flash_attention / flash_attention_ex and in the backward, per-row or per-token sinks, bf16 sink arrays.
+ */
+int flash_attention_sink_decode(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                const int32_t* kvLens, const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                int windowSize,
+                                const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                void* stream);
+
+int flash_attention_sink_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                      const int32_t* kvLens, const int32_t* blockTable,
+                                      const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                      int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                      float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                      int windowSize,
+                                      const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                      void* stream);
+
+int flash_attention_sink_extend(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                const int32_t* kvLens, const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                                float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                int windowSize,
+                                const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                void* stream);
+
+int flash_attention_sink_extend_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                      const int32_t* kvLens, const int32_t* blockTable,
+                                      const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                      int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                      float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                      int windowSize,
+                                      const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                      void* stream);
+
+int flash_attention_sink_extend_varlen(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                       const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                       const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                       int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                       float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                                       int windowSize,
+                                       const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                       void* stream);
+
+int flash_attention_sink_extend_paged_varlen(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                             const int32_t* cuSeqlensQ, const int32_t* kvLens, const int32_t* blockTable,
+                                             const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                             int batchSize, int numHeads, int numHeadsKV, int totalQ,
+                                             int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                             float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype,
+                                             int numSplits, int windowSize,
+                                             const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                             void* stream);
 
 /*
  * flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen -- the RAGGED cache append: flash_attention_kv_append /

@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen]
+                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -82,6 +82,14 @@ Each line:
               32 k prefix: chunk1024_32k (Sq a multiple of rows_per_block) and chunk1000_32k (it is not: the row blocks that straddle
               two heads walk the whole chunk's span).  With --splits: the forced sweep, one line per (shape, split count) with
               extend_ms / varlen_ms and the windowed times at that count (profiles/extend_window_bench.log).
+--sinks         attention sinks (``sinks=``: the flash_attention_sink_* entry points) beside the same call without them: a mode of its own
+              over the shapes of decode, --extend or --varlen.  One line per shape and cache form ("bf16", with --kv fp8 "fp8", with --paged
+              "paged<page>" and "paged<page>_fp8"), every figure per window (0 = none, then every --window value): the two calls share Q, the cache,
+              the lengths, O, the plan and the workspace, and are timed ALTERNATED -- --repeats times (a window of --steps calls without
+              sinks, then one with) -- after the usual priming:
+              ms       the call without sinks: [median, min, max] of its windows -- min .. max is the noise of this run
+              sink_ms  the call with sinks (a [H] vector of logits around the row's LSE), likewise
+              sink_ratio = sink_ms / ms (medians); splits: the plan both calls run under (profiles/sink_bench.log).
 """
 import argparse
 import json
@@ -496,6 +504,101 @@ def varlen_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def sinks_main(args, fa, dev):
+    """--sinks: every shape of the chosen family with and without ``sinks=``, alternated"""
+    import torch
+    f8 = torch.float8_e4m3fn
+    wins = [0] + [int(x) for x in (args.window or "").split(",") if x]
+    pages = [int(x) for x in (args.paged or "").split(",") if x]
+    if args.varlen:
+        cases = [(name, d, 32, 8, [r for r, _ in seqs], [r + p for r, p in seqs]) for name, d, seqs in varlen_shapes()]
+    elif args.extend:
+        cases = [(name, d, H, Hkv, [Sq] * B, [p + Sq for p in prefixes]) for name, B, H, Hkv, Sq, prefixes, d in EXTEND_SHAPES + EXTEND_WINDOW_SHAPES]
+    else:
+        cases = [(name, d, H, Hkv, [Sq] * B, [1024 + (Sk - 1024) * b // (B - 1) for b in range(B)] if ragged else [Sk] * B)
+                 for name, B, H, Hkv, Sq, Sk, d, ragged in SHAPES + EXTRA]
+    if args.shape:
+        unknown = set(args.shape) - {c[0] for c in cases}
+        if unknown:
+            raise SystemExit(f"unknown shape(s): {sorted(unknown)}")
+        cases = [c for c in cases if c[0] in args.shape]
+    elif not args.varlen:
+        cases = [c for c in cases if c[0] not in {x[0] for x in EXTRA + EXTEND_WINDOW_SHAPES}]
+    family = "varlen" if args.varlen else "extend" if args.extend else "decode"
+    plan_of = {"decode": fa.decode_plan, "extend": fa.extend_plan, "varlen": fa.extend_varlen_plan}[family]
+    primed = False
+    for name, d, H, Hkv, sq, lens in cases:
+        g = torch.Generator(device=dev).manual_seed(0)
+        B, T = len(sq), sum(sq)
+        Sk = -(-max(lens) // 256) * 256 if family != "decode" else max(lens)
+        Q = torch.randn((T, H, d) if family == "varlen" else (B, H, sq[0], d), device=dev, generator=g).to(torch.bfloat16)
+        K, V = (torch.randn(B, Hkv, Sk, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        cu = [0]
+        for r in sq:
+            cu.append(cu[-1] + r)
+        cu_d = torch.tensor(cu, dtype=torch.int32, device=dev)
+        O = torch.zeros_like(Q)
+        # logits around the LSE of a row of N(0, 1) data: ln(keys) + 1/2 for the longest sequence, spread by +-2 over the heads
+        sinks = (torch.linspace(-2.0, 2.0, H) + torch.log(torch.tensor(float(max(lens)))) + 0.5).to(dev)
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in pages:
+            if Sk % page == 0:
+                forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        if args.kv == "fp8":
+            def quant(Tn):
+                ds = (Tn.float().abs().amax(dim=(0, 2, 3)) / 448.0).float()
+                T8 = torch.empty(Tn.shape, dtype=f8, device=dev)
+                for b in range(B):     # (a batch entry at a time: no fp32 copy of the whole cache)
+                    T8[b] = (Tn[b].float() / ds[:, None, None]).clamp(-448, 448).to(f8)
+                return T8, ds
+            (K8, kds), (V8, vds) = quant(K), quant(V)
+        for form, fp8, page in forms:
+            Kc, Vc, table = (K8, V8, None) if fp8 else (K, V, None)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                n = Sk // page
+                perm = torch.randperm(B * n, device=dev, generator=g)
+                table = perm.reshape(B, n).to(torch.int32)
+                pools = []
+                for Tn in (Kc, Vc):
+                    Tn = Tn.view(torch.uint8) if fp8 else Tn      # (pages are moved as bytes)
+                    pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=Tn.dtype)
+                    pool[perm] = Tn.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
+                    pools.append(pool.view(f8) if fp8 else pool)
+                Kc, Vc = pools
+            front = getattr(fa, {"decode": "flash_attention_decode", "extend": "flash_attention_extend", "varlen": "flash_attention_extend"}[family]
+                            + ("_paged" if page else "") + ("_varlen" if family == "varlen" else "") + ("" if family == "decode" else "_window"))
+            head = [Q, Kc, Vc] + ([table] if page else []) + ([cu_d] if family == "varlen" else []) + [lens_d]
+            line = {"shape": name, "form": form, "splits": {}, "ms": {}, "sink_ms": {}, "sink_ratio": {}}
+            for W in wins:
+                plan = plan_of(B, H, Hkv, T if family == "varlen" else sq[0], Sk, d, fa.FA_DTYPE_BF16, 0, window=W)
+                ws = torch.empty(max(fa.decode_workspace_size(1 if family == "varlen" else B, H, T if family == "varlen" else sq[0], d,
+                                                              plan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+                common = dict(kw, is_causal=family != "decode", O=O, workspace=ws, window=W)
+                plain = lambda: front(*head, **common)
+                sunk = lambda: front(*head, sinks=sinks, **common)
+                if not primed:   # >= 1 s of calls before the first timed window
+                    t = 0.0
+                    while t < 1000.0:
+                        t += timed(plain, 50, 0) * 50
+                    primed = True
+                a, b = [], []
+                for _ in range(args.repeats):
+                    a.append(timed(plain, args.steps, args.warmup))
+                    b.append(timed(sunk, args.steps, args.warmup))
+                a, b = sorted(a), sorted(b)
+                line["splits"][str(W)] = plan["num_splits"]
+                line["ms"][str(W)] = [round(x, 5) for x in (statistics.median(a), a[0], a[-1])]
+                line["sink_ms"][str(W)] = [round(x, 5) for x in (statistics.median(b), b[0], b[-1])]
+                line["sink_ratio"][str(W)] = round(statistics.median(b) / statistics.median(a), 4)
+            print(json.dumps(line), flush=True)
+        del Q, K, V, O
+        if args.kv == "fp8":
+            del K8, V8
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -510,11 +613,14 @@ def main():
     ap.add_argument("--extend", action="store_true", help="time flash_attention_extend on its own shapes, beside the decode-slice and prefill-pair routes")
     ap.add_argument("--varlen", action="store_true", help="time flash_attention_extend_varlen on mixed batches, beside the grouped calls of today")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
+    ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.sinks:
+        return sinks_main(args, fa, dev)
     if args.extend:
         return extend_main(args, fa, dev)
     if args.varlen:

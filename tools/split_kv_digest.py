@@ -27,6 +27,12 @@ After those, in a second pass over d (so that the lines above keep their content
   extend   with window 7, 130: the cases above with the windowed call (flash_attention_extend*_window(window=W)), 256 lines
   varlen   the ragged call on token-packed Q, both sequences with rows of their own -- rows (5, 130) and (17, 40) -- G, causal,
            splits, kv as above, window 0, 7, 130; the same 24 calls per line, 192 lines
+
+After those 864 lines, in a third pass (so that they keep their content and order): every case above once more, in the same order, as
+the call WITH attention sinks (``sinks=``: the flash_attention_sink_* entry points), each line prefixed "sink" and carrying the first 16
+hex digits of its SHA-256 (profiles/sink_digest.log holds these lines alone): 864 lines more.  The
+sink vector at H = 8 is (-inf, 0, 1.5, 3, 4.5, 5.5, 6.5, 8); at H = 2 it is (0, 5.5), every fourth element from the second
+(tests/sink_check.py: sinks_for).
 """
 import hashlib
 import itertools
@@ -38,6 +44,7 @@ sys.path.insert(0, ROOT)
 
 B, HKV, CAP = 2, 2, 384
 LENS = [(1, 300), (129, 300)]
+SINKS8 = (float("-inf"), 0.0, 1.5, 3.0, 4.5, 5.5, 6.5, 8.0)
 
 
 def main():
@@ -76,7 +83,15 @@ def main():
                 caches[f"paged{page}+s", kv] = (strided(pools[0]), strided(pools[1]), table, desc)
         return caches
 
-    def uniform(d, caches, cases):
+    def sinks_of(H, on):
+        """the keyword of the third pass: the sink vector of H query heads"""
+        if not on:
+            return {}
+        step = max(len(SINKS8) // H, 1)
+        return dict(sinks=torch.tensor([SINKS8[(1 + h * step) % len(SINKS8)] if H < len(SINKS8) else SINKS8[h % len(SINKS8)]
+                                        for h in range(H)], dtype=torch.float32).to(dev))
+
+    def uniform(d, caches, cases, sinks=False):
         for call, sqs, windows in cases:
             for G, Sq in itertools.product((1, 4), sqs):
                 gq = torch.Generator().manual_seed(7 * d + 1000 * G + Sq)
@@ -85,7 +100,7 @@ def main():
                     h = hashlib.sha256()
                     for form, out, L in itertools.product([f for f, k in caches if k == kv], (torch.float32, torch.bfloat16), lens_d):
                         Kc, Vc, table, desc = caches[form, kv]
-                        kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out)
+                        kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out, **sinks_of(HKV * G, sinks))
                         if call == "decode" or W:
                             kw["window"] = W
                         win = "_window" if call == "extend" and W else ""     # (the extend fronts take a window under a name of their own)
@@ -95,9 +110,9 @@ def main():
                             O, lse = getattr(fa, f"flash_attention_{call}_paged{win}")(Q, Kc, Vc, table, L, **kw)
                         h.update(O.cpu().view(torch.uint8).numpy().tobytes())
                         h.update(lse.cpu().numpy().tobytes())
-                    print(f"{call} d{d} G{G} Sq{Sq} causal{causal} splits{ns} window{W} {kv} {h.hexdigest()}", flush=False)
+                    print(f"{'sink ' if sinks else ''}{call} d{d} G{G} Sq{Sq} causal{causal} splits{ns} window{W} {kv} {h.hexdigest()[:16 if sinks else 64]}")
 
-    def ragged(d, caches):
+    def ragged(d, caches, sinks=False):
         for G, sq in itertools.product((1, 4), ((5, 130), (17, 40))):
             gq = torch.Generator().manual_seed(7 * d + 1000 * G + sum(sq))
             Q = torch.randn(sum(sq), HKV * G, d, generator=gq).to(torch.bfloat16).to(dev)
@@ -106,7 +121,8 @@ def main():
                 h = hashlib.sha256()
                 for form, out, L in itertools.product([f for f, k in caches if k == kv], (torch.float32, torch.bfloat16), lens_d):
                     Kc, Vc, table, desc = caches[form, kv]
-                    kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out, **(dict(window=W) if W else {}))
+                    kw = dict(desc, is_causal=bool(causal), num_splits=ns, return_lse=True, out_dtype=out, **(dict(window=W) if W else {}),
+                              **sinks_of(HKV * G, sinks))
                     if table is None:
                         O, lse = (fa.flash_attention_extend_varlen_window if W else fa.flash_attention_extend_varlen)(Q, Kc, Vc, cu, L, **kw)
                     else:
@@ -114,7 +130,8 @@ def main():
                             Q, Kc, Vc, table, cu, L, **kw)
                     h.update(O.cpu().view(torch.uint8).numpy().tobytes())
                     h.update(lse.cpu().numpy().tobytes())
-                print(f"varlen d{d} G{G} rows{sq[0]}+{sq[1]} causal{causal} splits{ns} window{W} {kv} {h.hexdigest()}", flush=False)
+                print(f"{'sink ' if sinks else ''}varlen d{d} G{G} rows{sq[0]}+{sq[1]} causal{causal} splits{ns} window{W} {kv} "
+                      f"{h.hexdigest()[:16 if sinks else 64]}")
 
     for d in (64, 128):
         uniform(d, caches_of(d), (("decode", (1, 5, 16), (0, 7, 130)), ("extend", (5, 17, 40, 130), (0,))))
@@ -122,6 +139,12 @@ def main():
         caches = caches_of(d)
         uniform(d, caches, (("extend", (5, 17, 40, 130), (7, 130)),))
         ragged(d, caches)
+    for d in (64, 128):
+        uniform(d, caches_of(d), (("decode", (1, 5, 16), (0, 7, 130)), ("extend", (5, 17, 40, 130), (0,))), sinks=True)
+    for d in (64, 128):
+        caches = caches_of(d)
+        uniform(d, caches, (("extend", (5, 17, 40, 130), (7, 130)),), sinks=True)
+        ragged(d, caches, sinks=True)
     sys.stdout.flush()
 
 
