@@ -18,6 +18,7 @@ import decode_check as dc  # noqa: E402
 import extend_window_check as ewc  # noqa: E402
 import kv_append_check as kvc  # noqa: E402
 import weight_probe as wp  # noqa: E402
+from abi_decl import c_call  # noqa: E402
 
 DEV = "cuda:0"
 bf, f32, u8, i32 = torch.bfloat16, torch.float32, torch.uint8, torch.int32
@@ -205,21 +206,21 @@ class Cache:
             d["kd"], d["vd"] = self.kd, self.vd
         return d
 
-    def geometry(self):
-        """the ints between seqLenQ and dHead"""
+    def values(self, v):
+        """what a call on the placed tensors `v` takes from the cache, by abi_decl's names: K, V and their strides, the lengths,
+        cuSeqlensQ of a ragged call, the descales, the cache's type, and the capacity or the table and the paging geometry"""
+        _, (sK, sV) = strides(v["K"], v["V"])                   # (a byref holds on to its fa_strides)
+        out = dict(K=v["K"].data_ptr(), V=v["V"].data_ptr(), sK=sK, sV=sV, lens=v["lens"].data_ptr(), cu=ptr(v, "cu"), kd=ptr(v, "kd"),
+                   vd=ptr(v, "vd"), kv=CODE[self.K.dtype], B=self.B, Hkv=HKV, d=self.d)
         if not self.page:
-            return (CAPACITY,)
-        return (self.K.shape[0], self.page, CAPACITY // self.page, self.table.shape[1])
-
-    def pointers(self, v, lens="lens", cu=None):
-        """the pointers between the LSE (or V) and the workspace: [cu,] kvLens, [table,] kDescale, vDescale"""
-        return (*((v[cu].data_ptr(),) if cu else ()), v[lens].data_ptr(), *((v["table"].data_ptr(),) if self.page else ()),
-                ptr(v, "kd"), ptr(v, "vd"))
+            return dict(out, Sk=CAPACITY)
+        return dict(out, table=v["table"].data_ptr(), P=self.K.shape[0], page=self.page, maxp=CAPACITY // self.page, ts=self.table.shape[1])
 
 
-def split_kv_call(family, cache, Q, lens, causal, ns, W, cu=None, odt=f32):
+def split_kv_call(family, cache, Q, lens, causal, ns, W, cu=None, odt=f32, sink=False):
     """decode / extend: Q [B, H, Sq, d]; varlen: Q [T, H, d] packed by token with cu (B + 1 ints).  O in `odt`, the LSE fp32.  The plan is
-    asserted: the forced split count is taken, and the combine kernel runs exactly when there is more than one split"""
+    asserted: the forced split count is taken, and the combine kernel runs exactly when there is more than one split.  sink: through
+    the family's flash_attention_sink_* entry point, on the tensor `sinks` that the caller adds to specs and data"""
     d, H, B = cache.d, HKV * G, cache.B
     ragged = family == "varlen"
     rows = Q.shape[0] if ragged else Q.shape[2]
@@ -230,18 +231,16 @@ def split_kv_call(family, cache, Q, lens, causal, ns, W, cu=None, odt=f32):
     data = dict(cache.data(), Q=Q, lens=torch.tensor(lens, dtype=i32))
     if ragged:
         specs["cu"], data["cu"] = spec((B + 1,), i32, side=True), torch.tensor(cu, dtype=i32)
-    name = "flash_attention_" + ("decode" if family == "decode" else "extend") + ("_paged" if cache.page else "") + ("_varlen" if ragged else "") + "_window"
+    name = ("decode" if family == "decode" else "extend") + ("_paged" if cache.page else "") + ("_varlen" if ragged else "")
+    name = "flash_attention_" + ("sink_" + name if sink else name + "_window")
 
     def go(v):
-        keep, refs = strides(v["K"], v["V"])
-        if ragged:
-            refs = [None, *refs, None]                         # NULL: the token-major [T, H, d] an engine holds
-        else:
-            keep2, qo = strides(v["Q"], v["O"])
-            refs = [qo[0], *refs, qo[1]]
-        rc = getattr(fa.lib(), name)(v["Q"].data_ptr(), v["K"].data_ptr(), v["V"].data_ptr(), v["O"].data_ptr(), v["lse"].data_ptr(),
-                                     *cache.pointers(v, cu="cu" if ragged else None), ptr(v, "ws"), B, H, HKV, rows, *cache.geometry(), d,
-                                     1.0 / math.sqrt(d), causal, fa.FA_DTYPE_BF16, CODE[cache.K.dtype], CODE[odt], ns, W, *refs, stream())
+        _, (sQ, sO) = (None, (None, None)) if ragged else strides(v["Q"], v["O"])    # NULL: the token-major [T, H, d] an engine holds
+        values = dict(cache.values(v), Q=v["Q"].data_ptr(), O=v["O"].data_ptr(), LSE=v["lse"].data_ptr(), ws=ptr(v, "ws"), H=H, Sq=rows,
+                      scale=1.0 / math.sqrt(d), causal=causal, dtype=fa.FA_DTYPE_BF16, o=CODE[odt], ns=ns, W=W, sQ=sQ, sO=sO, stream=stream())
+        if sink:
+            values["sinks"] = v["sinks"].data_ptr()
+        rc = c_call(name, values)
         assert rc == 0, (name, fa.error_string(rc))
 
     return Call(specs, data, go, ["O", "lse"], fa.decode_workspace_size(1 if ragged else B, H, rows, d, ns),
@@ -260,15 +259,9 @@ def append_call(cache, Knew, Vnew, lens, cu=None):
     name = "flash_attention_kv_append" + ("_paged" if cache.page else "") + ("_varlen" if ragged else "")
 
     def go(v):
-        keep, refs = strides(v["K"], v["V"])
-        if ragged:
-            refs = [None, None, *refs]
-        else:
-            keep2, new = strides(v["Knew"], v["Vnew"])
-            refs = [*new, *refs]
-        rc = getattr(fa.lib(), name)(v["Knew"].data_ptr(), v["Vnew"].data_ptr(), v["K"].data_ptr(), v["V"].data_ptr(),
-                                     *cache.pointers(v, cu="cu" if ragged else None), cache.B, HKV, rows, *cache.geometry(), cache.d,
-                                     fa.FA_DTYPE_BF16, CODE[cache.K.dtype], *refs, stream())
+        _, (sKn, sVn) = (None, (None, None)) if ragged else strides(v["Knew"], v["Vnew"])
+        rc = c_call(name, dict(cache.values(v), Kn=v["Knew"].data_ptr(), Vn=v["Vnew"].data_ptr(), Sq=rows, dtype=fa.FA_DTYPE_BF16,
+                               sKn=sKn, sVn=sVn, stream=stream()))
         assert rc == 0, (name, fa.error_string(rc))
 
     return Call(specs, data, go, ["K", "V"], 0, name)

@@ -8,7 +8,7 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
+from abi_decl import BF16, F16, F32, FP8  # noqa: E402
 
 
 def test_backward_symbols_are_exported():

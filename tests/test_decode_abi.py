@@ -9,11 +9,9 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, declared_parameters, host_call)
 
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
 CUS_WITHOUT_A_DEVICE = 256
 
 
@@ -40,17 +38,7 @@ def test_decode_symbols_are_exported_with_the_declared_signatures():
 
 
 def decode_call():
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    ok = dict(B=2, H=8, Hkv=2, Sq=1, Sk=4096, d=128, scale=0.125, causal=False, dtype=BF16, o=F32, ns=1)
-    none = [None] * 4
-
-    def call(Q=p, K=p, V=p, O=p, LSE=None, lens=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(ok, **kw)
-        return L.flash_attention_decode(Q, K, V, O, LSE, lens, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["Sk"], a["d"], a["scale"],
-                                        a["causal"], a["dtype"], a["o"], a["ns"], *strides, None)
-
-    return call, p
+    return host_call("flash_attention_decode", dict(B=2, H=8, Hkv=2, Sq=1, Sk=4096, d=128, scale=0.125, causal=False, dtype=BF16, o=F32, ns=1))
 
 
 def test_every_invalid_argument_is_refused_before_any_launch():

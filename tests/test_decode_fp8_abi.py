@@ -10,11 +10,8 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, MetaTensor as T, declared_parameters, host_calls)
 
 
 def test_the_symbols_are_exported_with_the_declared_signatures():
@@ -41,24 +38,9 @@ def test_the_symbols_are_exported_with_the_declared_signatures():
 
 def calls():
     """(contiguous call, paged call, an aligned host pointer); keyword arguments override a valid call"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, H=8, Hkv=2, Sq=1, Sk=1024, d=128, scale=0.125, causal=False, dtype=BF16, kv=FP8, o=F32, ns=1)
     okp = dict(B=2, H=8, Hkv=2, Sq=1, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=False, dtype=BF16, kv=FP8, o=F32, ns=1)
-
-    def contiguous(Q=p, K=p, V=p, O=p, LSE=None, lens=None, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_decode_fp8(Q, K, V, O, LSE, lens, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["Sk"], a["d"],
-                                            a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"], *strides, None)
-
-    def paged(Q=p, K=p, V=p, O=p, LSE=None, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_decode_paged_fp8(Q, K, V, O, LSE, lens, table, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["P"],
-                                                  a["page"], a["maxp"], a["ts"], a["d"], a["scale"], a["causal"], a["dtype"], a["kv"],
-                                                  a["o"], a["ns"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_decode_fp8", okc), ("flash_attention_decode_paged_fp8", okp))
 
 
 def test_what_the_siblings_refuse_is_refused_with_the_same_codes():
@@ -134,9 +116,7 @@ def test_the_extent_limits_are_counted_in_bytes():
     assert contiguous(Sk=1 << 24, ns=2, ws=None) == BAD_SHAPE
     assert contiguous(Sk=(1 << 24) - 193, ns=2, ws=None) == NULL_POINTER
     assert contiguous(Sk=(1 << 24) - 192, ns=2, ws=None) == BAD_SHAPE
-    bf16 = fa.lib().flash_attention_decode
-    assert bf16(p, p, p, p, None, None, None, 2, 8, 2, 1, (1 << 24) - 193, 128, 0.125, False, BF16, F32, 2, None, None, None, None,
-                None) == BAD_SHAPE
+    assert contiguous(symbol="flash_attention_decode", Sk=(1 << 24) - 193, ns=2, ws=None) == BAD_SHAPE
     # a wide row stride, for K and for V: 1024 rows + 192 at 2^21 bytes is 2^31 + ...; at 2^20 bytes it fits (bf16: it would not)
     for stride, want in ((1 << 21, BAD_SHAPE), (1 << 20, NULL_POINTER)):
         s = fa.FaStrides(1 << 40, 1 << 36, stride)
@@ -170,15 +150,6 @@ def test_the_plan_does_not_depend_on_the_cache_type():
         assert contiguous(Sk=page * maxp, ns=0, ws=None) == NULL_POINTER, (page, maxp)
     assert fa.decode_plan(2, 8, 2, 1, 1024, 128, F32, 1)["lds_bytes"] == 37376      # the bf16 V image, whatever the cache holds
     assert "kv_dtype" not in declared_parameters("flash_attention_decode_plan")
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
 
 
 def test_binding_refusals():

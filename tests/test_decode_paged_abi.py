@@ -9,11 +9,8 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, declared_parameters, host_call)
 
 
 def test_the_symbol_is_exported_with_the_declared_signature():
@@ -32,18 +29,8 @@ def test_the_symbol_is_exported_with_the_declared_signature():
 
 
 def paged_call():
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
     ok = dict(B=2, H=8, Hkv=2, Sq=1, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=False, dtype=BF16, o=F32, ns=1)
-    none = [None] * 4
-
-    def call(Q=p, K=p, V=p, O=p, LSE=None, lens=None, table=p, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(ok, **kw)
-        return L.flash_attention_decode_paged(Q, K, V, O, LSE, lens, table, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["P"], a["page"],
-                                              a["maxp"], a["ts"], a["d"], a["scale"], a["causal"], a["dtype"], a["o"], a["ns"],
-                                              *strides, None)
-
-    return call, p
+    return host_call("flash_attention_decode_paged", ok)
 
 
 def test_what_flash_attention_decode_refuses_is_refused_with_the_same_codes():

@@ -3,6 +3,7 @@ flash_attention_decode_plan_window) at the C ABI and in the binding: the symbols
 every invalid argument is refused with its code before anything is launched (fake aligned host pointers: no GPU is touched; no call
 here is valid as a whole), the plan follows the window's tiles, and the tests' own reference mask equals a brute-force double loop."""
 import ctypes
+import functools
 
 import pytest
 
@@ -10,12 +11,8 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
-TILE = 128
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, MetaTensor as T, declared_parameters, host_calls, plan_call, tiles)
 
 
 def test_the_symbols_are_exported_with_the_declared_signatures():
@@ -55,25 +52,10 @@ def test_the_symbols_are_exported_with_the_declared_signatures():
 def calls(kv):
     """(contiguous call, paged call, an aligned host pointer) for a cache of type `kv`; keyword arguments override a call that is
     valid but for its workspace: two splits and none given, so that a call that passes every other check stops at NULL_POINTER"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, H=8, Hkv=2, Sq=1, Sk=1024, d=128, scale=0.125, causal=False, dtype=BF16, kv=kv, o=F32, ns=2, W=128)
     okp = dict(B=2, H=8, Hkv=2, Sq=1, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=False, dtype=BF16, kv=kv, o=F32, ns=2,
                W=128)
-
-    def contiguous(Q=p, K=p, V=p, O=p, LSE=None, lens=None, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_decode_window(Q, K, V, O, LSE, lens, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["Sk"], a["d"],
-                                               a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"], a["W"], *strides, None)
-
-    def paged(Q=p, K=p, V=p, O=p, LSE=None, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_decode_paged_window(Q, K, V, O, LSE, lens, table, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["P"],
-                                                     a["page"], a["maxp"], a["ts"], a["d"], a["scale"], a["causal"], a["dtype"],
-                                                     a["kv"], a["o"], a["ns"], a["W"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_decode_window", okc), ("flash_attention_decode_paged_window", okp))
 
 
 @pytest.mark.parametrize("W", [128, 0, 5000])
@@ -146,14 +128,7 @@ def test_the_new_refusals(kv):
     assert fa.decode_plan(2, 8, 2, 1, 32768, 128, F32, 0, window=128)["num_splits"] == 1
 
 
-def plan_window(B, H, Hkv, Sq, Sk, d, o, ns, W):
-    p = fa.FaDecodePlan()
-    rc = fa.lib().flash_attention_decode_plan_window(B, H, Hkv, Sq, Sk, d, o, ns, W, ctypes.byref(p))
-    return rc, {k: getattr(p, k) for k, _ in fa.FaDecodePlan._fields_}
-
-
-def tiles(n):
-    return -(-n // TILE)
+plan_window = functools.partial(plan_call, "flash_attention_decode_plan_window")
 
 
 def test_the_plan_follows_the_window():
@@ -192,7 +167,7 @@ def test_the_plan_follows_the_window():
     assert plan_window(1, 32, 8, 17, 1024, 128, F32, 0, 128)[0] == BAD_SHAPE
     assert plan_window(1, 32, 8, 1, 1024, 96, F32, 0, 128)[0] == BAD_DHEAD
     assert plan_window(1, 32, 8, 1, 1024, 128, FP8, 0, 128)[0] == BAD_DTYPE
-    assert fa.lib().flash_attention_decode_plan_window(1, 32, 8, 1, 1024, 128, F32, 0, 128, None) == NULL_POINTER
+    assert plan_window(1, 32, 8, 1, 1024, 128, F32, 0, 128, null_plan=True)[0] == NULL_POINTER
     with pytest.raises(ValueError, match="window"):
         fa.decode_plan(1, 32, 8, 1, 1024, 128, F32, 0, window=-1)
 
@@ -221,15 +196,6 @@ def test_the_reference_mask_equals_a_brute_force_double_loop():
                         assert torch.equal(got, visible(L, Sq, causal)), (L, Sq, causal, W)
                 assert torch.equal(visible_window(L, Sq, causal, 0), visible(L, Sq, causal))
                 assert first_visible(L, Sq, 0) == 0
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
 
 
 def test_binding_refusals():

@@ -3,6 +3,7 @@ the C ABI and in the binding: the symbols exist with the declared parameter list
 its code before anything is launched (fake aligned host pointers: no GPU is touched; no call here is valid as a whole), and the plan
 is the documented one."""
 import ctypes
+import functools
 
 import pytest
 
@@ -10,12 +11,8 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
-TILE = 128
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, TILE, MetaTensor as T, declared_parameters, host_calls, plan_call)
 
 
 def test_the_symbols_are_exported_with_the_declared_signatures():
@@ -35,24 +32,9 @@ def test_the_symbols_are_exported_with_the_declared_signatures():
 def calls(kv):
     """(contiguous call, paged call, an aligned host pointer) for a cache of type `kv`; keyword arguments override a call that is
     valid but for its workspace: two splits and none given, so that a call that passes every other check stops at NULL_POINTER"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, H=8, Hkv=2, Sq=300, Sk=1024, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32, ns=2)
     okp = dict(B=2, H=8, Hkv=2, Sq=300, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32, ns=2)
-
-    def contiguous(Q=p, K=p, V=p, O=p, LSE=None, lens=None, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_extend(Q, K, V, O, LSE, lens, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["Sk"], a["d"],
-                                        a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"], *strides, None)
-
-    def paged(Q=p, K=p, V=p, O=p, LSE=None, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_extend_paged(Q, K, V, O, LSE, lens, table, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["Sq"], a["P"],
-                                              a["page"], a["maxp"], a["ts"], a["d"], a["scale"], a["causal"], a["dtype"],
-                                              a["kv"], a["o"], a["ns"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_extend", okc), ("flash_attention_extend_paged", okp))
 
 
 @pytest.mark.parametrize("kv", [BF16, FP8])
@@ -121,10 +103,7 @@ def test_the_chunk_is_capped_by_the_capacity_not_by_decodes_sixteen(kv):
     assert contiguous(ns=0, Sq=17, Sk=32768) == NULL_POINTER and paged(ns=0, Sq=17, maxp=512, ts=512) == NULL_POINTER
 
 
-def plan(B, H, Hkv, Sq, Sk, d, o=F32, ns=0):
-    p = fa.FaDecodePlan()
-    rc = fa.lib().flash_attention_extend_plan(B, H, Hkv, Sq, Sk, d, o, ns, ctypes.byref(p))
-    return rc, {k: getattr(p, k) for k, _ in fa.FaDecodePlan._fields_}
+plan = functools.partial(plan_call, "flash_attention_extend_plan")
 
 
 def test_the_plan():
@@ -155,12 +134,12 @@ def test_the_plan():
     # seqLenQ = 17 and seqLenQ = capacity are accepted, capacity + 1 is not; the decode plan still stops at 16
     assert plan(1, 32, 8, 17, 1024, 128)[0] == 0 and plan(1, 32, 8, 1024, 1024, 128)[0] == 0
     assert plan(1, 32, 8, 1025, 1024, 128)[0] == BAD_SHAPE
-    assert fa.lib().flash_attention_decode_plan(1, 32, 8, 17, 1024, 128, F32, 0, ctypes.byref(fa.FaDecodePlan())) == BAD_SHAPE
+    assert plan_call("flash_attention_decode_plan", 1, 32, 8, 17, 1024, 128, F32, 0)[0] == BAD_SHAPE
     assert plan(1, 32, 8, 0, 1024, 128)[0] == BAD_SHAPE and plan(1, 32, 3, 20, 1024, 128)[0] == BAD_SHAPE
     assert plan(1, 32, 8, 20, 1024, 128, ns=-1)[0] == BAD_SHAPE and plan(1, 32, 8, 20, 1024, 128, ns=CAP + 1)[0] == BAD_SHAPE
     assert plan(1, 32, 8, 20, 1024, 96)[0] == BAD_DHEAD
     assert plan(1, 32, 8, 20, 1024, 128, FP8)[0] == BAD_DTYPE
-    assert fa.lib().flash_attention_extend_plan(1, 32, 8, 20, 1024, 128, F32, 0, None) == NULL_POINTER
+    assert plan(1, 32, 8, 20, 1024, 128, F32, 0, null_plan=True)[0] == NULL_POINTER
 
 
 def test_a_launch_stays_below_2_pow_32_threads():
@@ -203,15 +182,6 @@ def test_the_workspace_formula_has_no_cap_on_the_chunk():
         rows = B * H * Sq
         assert fa.decode_workspace_size(B, H, Sq, d, ns) == r16(rows * ns * d * 4) + r16(rows * ns * 4)
     assert fa.decode_workspace_size(1, 32, 300, 128, 1) == 0 and fa.decode_workspace_size(1, 32, 300, 128, 0) == 0
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
 
 
 def test_binding_refusals():

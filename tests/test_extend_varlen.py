@@ -13,6 +13,7 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
+from abi_decl import c_call  # noqa: E402
 from decode_check import CAP, DEV, F8, assert_close, dequantise, gather, quantise, randn, reference  # noqa: E402
 from test_decode_edges import SCALES, assert_close_with_score_noise  # noqa: E402
 
@@ -83,10 +84,11 @@ def raw_varlen(Q, K, V, O, lse, cu, lens, splits, causal):
     ns = fa.extend_varlen_plan(B, H, Hkv, T, Sk, d, fa.FA_DTYPE_F32, splits)["num_splits"]
     need = fa.decode_workspace_size(1, H, T, d, ns)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
-    rc = fa.lib().flash_attention_extend_varlen(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), lse.data_ptr(), cu.data_ptr(),
-                                                lens.data_ptr(), None, None, ws.data_ptr() if need else None, B, H, Hkv, T, Sk, d,
-                                                1.0 / d ** 0.5, causal, fa.FA_DTYPE_BF16, fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, ns,
-                                                None, None, None, None, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = c_call("flash_attention_extend_varlen", dict(
+        Q=Q.data_ptr(), K=K.data_ptr(), V=V.data_ptr(), O=O.data_ptr(), LSE=lse.data_ptr(), cu=cu.data_ptr(), lens=lens.data_ptr(), kd=None,
+        vd=None, ws=ws.data_ptr() if need else None, B=B, H=H, Hkv=Hkv, T=T, Sk=Sk, d=d, scale=1.0 / d ** 0.5, causal=causal,
+        dtype=fa.FA_DTYPE_BF16, kv=fa.FA_DTYPE_BF16, o=fa.FA_DTYPE_F32, ns=ns, strides=[None] * 4,
+        stream=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     assert rc == 0, rc
     return ws
 

@@ -4,6 +4,7 @@ binding: the symbols exist with parameter lists that differ from their uniform s
 totalQ, cuSeqlensQ before kvLens), every invalid argument is refused with its code before anything is launched (fake aligned host
 pointers: no GPU is touched; no call here is valid as a whole), and the plan is the documented one."""
 import ctypes
+import functools
 import random
 
 import pytest
@@ -12,13 +13,10 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, TILE, MetaTensor, declared_parameters, host_calls, plan_call)
 
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
 MAXB = fa.FA_VARLEN_MAX_BATCH
-TILE = 128
 
 SIBLINGS = (("flash_attention_extend_varlen", "flash_attention_extend", "seqLenQ"),
             ("flash_attention_extend_paged_varlen", "flash_attention_extend_paged", "seqLenQ"),
@@ -49,24 +47,9 @@ def test_the_symbols_are_exported_with_the_declared_signatures():
 def calls(kv):
     """(contiguous call, paged call, an aligned host pointer) for a cache of type `kv`; keyword arguments override a call that is
     valid but for its workspace: two splits and none given, so that a call that passes every other check stops at NULL_POINTER"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, H=8, Hkv=2, T=300, Sk=1024, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32, ns=2)
     okp = dict(B=2, H=8, Hkv=2, T=300, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32, ns=2)
-
-    def contiguous(Q=p, K=p, V=p, O=p, LSE=None, cu=p, lens=None, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_extend_varlen(Q, K, V, O, LSE, cu, lens, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["T"], a["Sk"], a["d"],
-                                               a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"], *strides, None)
-
-    def paged(Q=p, K=p, V=p, O=p, LSE=None, cu=p, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_extend_paged_varlen(Q, K, V, O, LSE, cu, lens, table, kd, vd, ws, a["B"], a["H"], a["Hkv"], a["T"], a["P"],
-                                                     a["page"], a["maxp"], a["ts"], a["d"], a["scale"], a["causal"], a["dtype"],
-                                                     a["kv"], a["o"], a["ns"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_extend_varlen", okc), ("flash_attention_extend_paged_varlen", okp))
 
 
 @pytest.mark.parametrize("kv", [BF16, FP8])
@@ -153,10 +136,7 @@ def test_total_q_is_a_bound_of_its_own_not_capped_by_the_capacity(kv):
     assert contiguous(ns=0, T=17, Sk=32768) == NULL_POINTER and paged(ns=0, T=17, maxp=512, ts=512) == NULL_POINTER
 
 
-def plan(B, H, Hkv, T, Sk, d, o=F32, ns=0):
-    p = fa.FaDecodePlan()
-    rc = fa.lib().flash_attention_extend_varlen_plan(B, H, Hkv, T, Sk, d, o, ns, ctypes.byref(p))
-    return rc, {k: getattr(p, k) for k, _ in fa.FaDecodePlan._fields_}
+plan = functools.partial(plan_call, "flash_attention_extend_varlen_plan")
 
 
 def test_the_plan():
@@ -193,7 +173,7 @@ def test_the_plan():
     assert plan(1, 32, 8, 20, 1024, 128, ns=-1)[0] == BAD_SHAPE and plan(1, 32, 8, 20, 1024, 128, ns=CAP + 1)[0] == BAD_SHAPE
     assert plan(1, 32, 8, 20, 1024, 96)[0] == BAD_DHEAD
     assert plan(1, 32, 8, 20, 1024, 128, FP8)[0] == BAD_DTYPE
-    assert fa.lib().flash_attention_extend_varlen_plan(1, 32, 8, 20, 1024, 128, F32, 0, None) == NULL_POINTER
+    assert plan(1, 32, 8, 20, 1024, 128, F32, 0, null_plan=True)[0] == NULL_POINTER
 
 
 def test_the_bound_covers_every_partition():
@@ -232,23 +212,9 @@ def test_the_workspace_formula():
 
 
 def append_calls(kv):
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, Hkv=2, T=300, Sk=1024, d=128, dtype=BF16, kv=kv)
     okp = dict(B=2, Hkv=2, T=300, P=64, page=64, maxp=16, ts=16, d=128, dtype=BF16, kv=kv)
-
-    def contiguous(Kn=p, Vn=p, K=p, V=p, cu=p, lens=None, kd=None, vd=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_kv_append_varlen(Kn, Vn, K, V, cu, lens, kd, vd, a["B"], a["Hkv"], a["T"], a["Sk"], a["d"], a["dtype"],
-                                                  a["kv"], *strides, None)
-
-    def paged(Kn=p, Vn=p, K=p, V=p, cu=p, lens=None, table=p, kd=None, vd=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_kv_append_paged_varlen(Kn, Vn, K, V, cu, lens, table, kd, vd, a["B"], a["Hkv"], a["T"], a["P"], a["page"],
-                                                        a["maxp"], a["ts"], a["d"], a["dtype"], a["kv"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_kv_append_varlen", okc), ("flash_attention_kv_append_paged_varlen", okp))
 
 
 @pytest.mark.parametrize("kv", [BF16, FP8])
@@ -284,27 +250,12 @@ def test_the_append_refuses_what_the_uniform_append_refuses(kv):
         assert paged(**kw) == BAD_SHAPE, kw
     # totalQ above the capacity passes the shape checks: the next refusal in line is reached (an unsupported dHead)
     assert contiguous(T=5000, d=96) == BAD_DHEAD and paged(T=5000, d=96) == BAD_DHEAD
-    assert fa.lib().flash_attention_kv_append(p, p, p, p, None, None, None, 2, 2, 5000, 1024, 96, BF16, kv, None, None, None, None, None) == BAD_SHAPE
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
-        self._t = t
-
-    def unsqueeze(self, i):
-        return T(self._t.unsqueeze(i), self.device)
-
-    def transpose(self, a, b):
-        return T(self._t.transpose(a, b), self.device)
+    assert contiguous(symbol="flash_attention_kv_append", Sq=5000, d=96) == BAD_SHAPE
 
 
 def test_binding_refusals():
     torch = pytest.importorskip("torch")
+    T = MetaTensor
     q = torch.zeros(40, 8, 64, dtype=torch.bfloat16)
     k = torch.zeros(2, 2, 64, 64, dtype=torch.bfloat16)
     kn = torch.zeros(40, 2, 64, dtype=torch.bfloat16)

@@ -11,12 +11,10 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, MetaTensor as T, aligned_host_pointer, declared_parameters, host_call, tiles)
+from abi_decl import plan_call as plan_window  # noqa: E402
 
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
-TILE = 128
 CALLS = ("flash_attention_extend", "flash_attention_extend_paged", "flash_attention_extend_varlen", "flash_attention_extend_paged_varlen")
 PLANS = ("flash_attention_extend_plan", "flash_attention_extend_varlen_plan")
 
@@ -45,26 +43,15 @@ def test_the_six_symbols_are_exported_with_the_declared_signatures():
 def calls(kv):
     """{name: call(W, **overrides)} for the four forms and an aligned host pointer.  W = None calls the un-windowed sibling.  Every
     call is valid but for its workspace: two splits and none given, so that passing every other check ends at NULL_POINTER"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
+    host = aligned_host_pointer()
     ok = dict(B=2, H=8, Hkv=2, Sq=300, Sk=1024, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32,
               ns=2)
 
     def make(name):
-        paged, ragged = "paged" in name, "varlen" in name
+        sibling = host_call(name, ok, host)[0]
+        return lambda W, **kw: sibling(**kw) if W is None else sibling(symbol=name + "_window", W=W, **kw)
 
-        def call(W, Q=p, K=p, V=p, O=p, LSE=None, cu=p, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-            a = dict(ok, **kw)
-            fn = getattr(L, name if W is None else name + "_window")
-            args = [Q, K, V, O, LSE] + ([cu] if ragged else []) + [lens] + ([table] if paged else []) + [kd, vd, ws, a["B"], a["H"],
-                                                                                                        a["Hkv"], a["Sq"]]
-            args += [a["P"], a["page"], a["maxp"], a["ts"]] if paged else [a["Sk"]]
-            args += [a["d"], a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"]] + ([] if W is None else [W])
-            return fn(*args, *strides, None)
-        return call
-
-    return {name: make(name) for name in CALLS}, p
+    return {name: make(name) for name in CALLS}, host[1]
 
 
 def ladder(p, kv, paged, ragged):
@@ -140,16 +127,6 @@ def test_a_negative_window_is_refused_and_any_other_passes_on(kv):
     assert fns["flash_attention_extend_paged"](4096, ns=0, Sq=17, maxp=512, ts=512) == NULL_POINTER
 
 
-def plan_window(fn, B, H, Hkv, Sq, Sk, d, o, ns, W):
-    p = fa.FaDecodePlan()
-    rc = getattr(fa.lib(), fn)(B, H, Hkv, Sq, Sk, d, o, ns, W, ctypes.byref(p))
-    return rc, {k: getattr(p, k) for k, _ in fa.FaDecodePlan._fields_}
-
-
-def tiles(n):
-    return -(-n // TILE)
-
-
 @pytest.mark.parametrize("ragged", [False, True])
 def test_the_plan_follows_the_window(ragged):
     fn = "flash_attention_extend_varlen_plan_window" if ragged else "flash_attention_extend_plan_window"
@@ -186,7 +163,7 @@ def test_the_plan_follows_the_window(ragged):
     assert plan_window(fn, 1, 32, 8, 0, 1024, 128, F32, 0, 128)[0] == BAD_SHAPE
     assert plan_window(fn, 1, 32, 8, 20, 1024, 96, F32, 0, 128)[0] == BAD_DHEAD
     assert plan_window(fn, 1, 32, 8, 20, 1024, 128, FP8, 0, 128)[0] == BAD_DTYPE
-    assert getattr(fa.lib(), fn)(1, 32, 8, 20, 1024, 128, F32, 0, 128, None) == NULL_POINTER
+    assert plan_window(fn, 1, 32, 8, 20, 1024, 128, F32, 0, 128, null_plan=True)[0] == NULL_POINTER
     if not ragged:
         assert plan_window(fn, 1, 32, 8, 1025, 1024, 128, F32, 0, 128)[0] == BAD_SHAPE
     with pytest.raises(ValueError, match="window"):
@@ -216,17 +193,6 @@ def test_the_block_range_model_is_the_hull_of_the_tiles_a_block_sees():
                                     assert got[0] <= hull[0] and hull[1] <= got[1]
                                 checked += 1
     assert checked > 30000
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
-        self.unsqueeze = lambda n: T(t.unsqueeze(n), device)
-        self.transpose = lambda a, b: T(t.transpose(a, b), device)
 
 
 def test_binding_refusals():

@@ -10,10 +10,7 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-BAD_SHAPE = -3
+from abi_decl import BAD_SHAPE, BF16, F16, F32, FP8, aligned_host_pointer, declared_parameters  # noqa: E402
 
 
 def test_gqa_symbols_are_exported_with_the_declared_signatures():

@@ -13,10 +13,8 @@ torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
 import kv_append_check as kc  # noqa: E402
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
-
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_STRIDE = -1, -2, -3, -4, -5, -7
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SHAPE, BAD_STRIDE, BF16, F16, F32, FP8, MISALIGNED, NULL_POINTER,  # noqa: E402
+                      MetaTensor as T, declared_parameters, host_calls)
 
 
 def test_the_symbols_are_exported_with_the_declared_signatures():
@@ -48,23 +46,9 @@ def test_the_symbols_are_exported_with_the_declared_signatures():
 
 def calls(kv):
     """(contiguous call, paged call, an aligned host pointer) for cache type kv; keyword arguments override a valid call"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
     okc = dict(B=2, Hkv=2, Sq=3, Sk=1024, d=128, dtype=BF16, kv=kv)
     okp = dict(B=2, Hkv=2, Sq=3, P=64, page=64, maxp=16, ts=16, d=128, dtype=BF16, kv=kv)
-
-    def contiguous(Kn=p, Vn=p, K=p, V=p, lens=None, kd=None, vd=None, strides=none, _keep=buf, **kw):
-        a = dict(okc, **kw)
-        return L.flash_attention_kv_append(Kn, Vn, K, V, lens, kd, vd, a["B"], a["Hkv"], a["Sq"], a["Sk"], a["d"], a["dtype"], a["kv"],
-                                           *strides, None)
-
-    def paged(Kn=p, Vn=p, K=p, V=p, lens=None, table=p, kd=None, vd=None, strides=none, _keep=buf, **kw):
-        a = dict(okp, **kw)
-        return L.flash_attention_kv_append_paged(Kn, Vn, K, V, lens, table, kd, vd, a["B"], a["Hkv"], a["Sq"], a["P"], a["page"],
-                                                 a["maxp"], a["ts"], a["d"], a["dtype"], a["kv"], *strides, None)
-
-    return contiguous, paged, p
+    return host_calls(("flash_attention_kv_append", okc), ("flash_attention_kv_append_paged", okp))
 
 
 # A call that passes every check would LAUNCH (on a machine with a device: write through the host pointers).  So there is no "valid
@@ -202,15 +186,6 @@ def test_the_position_rule_is_the_headers():
             table = torch.tensor([[1, 7]])
             pool = kc.append(new, torch.zeros(3, 1, 16, 8, dtype=torch.int16), [L], table=table)
             assert torch.equal(pool[1, 0], exp[0, 0, :16]) and not pool[0].any() and not pool[2].any(), (L, Sq)
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
 
 
 def test_binding_refusals():

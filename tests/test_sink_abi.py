@@ -19,11 +19,9 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-from abi_decl import aligned_host_pointer, declared_parameters  # noqa: E402
+from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
+                      NULL_POINTER, MetaTensor as T, aligned_host_pointer, declared_parameters, host_call)
 
-BF16, F32, FP8, F16 = fa.FA_DTYPE_BF16, fa.FA_DTYPE_F32, fa.FA_DTYPE_FP8_E4M3, fa.FA_DTYPE_F16
-NULL_POINTER, MISALIGNED, BAD_SHAPE, BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_STRIDE = -1, -2, -3, -4, -5, -6, -7
-CAP = fa.FA_DECODE_MAX_SPLITS
 # the sink entry point -> its _window twin
 TWINS = {
     "flash_attention_sink_decode": "flash_attention_decode_window",
@@ -59,26 +57,14 @@ def test_the_six_symbols_are_exported_with_the_declared_signatures():
 def calls(kv):
     """{sink entry point: call(W, sinks, **overrides)} on an aligned host pointer.  sinks = UNSET calls the _window twin.  Every call is
     valid but for its workspace: two splits and none given, so that passing every other check ends at NULL_POINTER"""
-    L = fa.lib()
-    buf, p = aligned_host_pointer()
-    none = [None] * 4
+    host = aligned_host_pointer()
     ok = dict(B=2, H=8, Hkv=2, Sk=1024, P=64, page=64, maxp=16, ts=16, d=128, scale=0.125, causal=True, dtype=BF16, kv=kv, o=F32, ns=2)
 
     def make(name):
-        paged, ragged, decode = "paged" in name, "varlen" in name, "decode" in name
+        sink = host_call(name, dict(ok, Sq=4 if "decode" in name else 300), host)[0]
+        return lambda W, sinks, **kw: sink(symbol=TWINS[name], W=W, **kw) if sinks is UNSET else sink(W=W, sinks=sinks, **kw)
 
-        def call(W, sinks, Q=p, K=p, V=p, O=p, LSE=None, cu=p, lens=None, table=p, kd=None, vd=None, ws=None, strides=none, _keep=buf, **kw):
-            a = dict(ok, Sq=4 if decode else 300)
-            a.update(kw)
-            fn = getattr(L, TWINS[name] if sinks is UNSET else name)
-            args = [Q, K, V, O, LSE] + ([cu] if ragged else []) + [lens] + ([table] if paged else []) + [kd, vd]
-            args += ([] if sinks is UNSET else [sinks]) + [ws, a["B"], a["H"], a["Hkv"], a["Sq"]]
-            args += [a["P"], a["page"], a["maxp"], a["ts"]] if paged else [a["Sk"]]
-            args += [a["d"], a["scale"], a["causal"], a["dtype"], a["kv"], a["o"], a["ns"], W]
-            return fn(*args, *strides, None)
-        return call
-
-    return {name: make(name) for name in TWINS}, p
+    return {name: make(name) for name in TWINS}, host[1]
 
 
 def ladder(p, paged, ragged, decode):
@@ -169,17 +155,6 @@ def test_a_misaligned_sinks_pointer_is_refused_at_its_place(kv):
         else:
             assert call(128, s, ws=p, Sk=0) == MISALIGNED, name
         assert call(-1, s, ws=p) == MISALIGNED, name
-
-
-class T:
-    """a tensor's metadata with is_cuda = True: the binding's checks run, nothing is launched"""
-    is_cuda = True
-
-    def __init__(self, t, device="cuda:0"):
-        self.shape, self.dtype, self.dim, self.stride, self.device = t.shape, t.dtype, t.dim, t.stride, device
-        self.is_contiguous = t.is_contiguous
-        self.unsqueeze = lambda n: T(t.unsqueeze(n), device)
-        self.transpose = lambda a, b: T(t.transpose(a, b), device)
 
 
 def test_binding_refusals():

@@ -5,8 +5,6 @@ inputs at 4 mod 16, the ``sinks`` array among them -- with the workspace enterin
 the run on plain allocations bit for bit, the arena untouched outside O, the LSE and the workspace, and the result is also held to the
 float64 reference with sinks (sink_check.py; decode_check.assert_close, unchanged).  One split (the split kernel's SINK form reads the
 array) and three (the combine's does).  The calls, the placements and the arena are memory_contract.py's, imported."""
-import math
-
 import pytest
 
 import __graft_entry__ as entry
@@ -27,28 +25,9 @@ assert (mc.HKV, mc.CAPACITY, len(LENS)) == (sc.HKV, sc.CAP, sc.B)
 
 def sink_call(family, cache, Q, lens, causal, ns, W, sinks, cu=None):
     """memory_contract.split_kv_call's tensors plus ``sinks`` as a side input, through the family's flash_attention_sink_* entry point"""
-    base = mc.split_kv_call(family, cache, Q, lens, causal, ns, W, cu=cu)
-    ragged = family == "varlen"
-    rows = Q.shape[0] if ragged else Q.shape[2]
-    d, B = cache.d, cache.B
-    specs = dict(base.specs, sinks=mc.spec((H,), f32, side=True))
-    data = dict(base.data, sinks=sinks)
-    name = "flash_attention_sink_" + ("decode" if family == "decode" else "extend") + ("_paged" if cache.page else "") + ("_varlen" if ragged else "")
-
-    def go(v):
-        keep, refs = mc.strides(v["K"], v["V"])
-        if ragged:
-            refs = [None, *refs, None]
-        else:
-            keep2, qo = mc.strides(v["Q"], v["O"])
-            refs = [qo[0], *refs, qo[1]]
-        rc = getattr(fa.lib(), name)(v["Q"].data_ptr(), v["K"].data_ptr(), v["V"].data_ptr(), v["O"].data_ptr(), v["lse"].data_ptr(),
-                                     *cache.pointers(v, cu="cu" if ragged else None), v["sinks"].data_ptr(), mc.ptr(v, "ws"), B, H, mc.HKV,
-                                     rows, *cache.geometry(), d, 1.0 / math.sqrt(d), causal, fa.FA_DTYPE_BF16, mc.CODE[cache.K.dtype],
-                                     mc.CODE[f32], ns, W, *refs, mc.stream())
-        assert rc == 0, (name, fa.error_string(rc))
-
-    return mc.Call(specs, data, go, ["O", "lse"], base.ws_bytes, f"{name} d {d} rows {rows} causal {causal} splits {ns} window {W}")
+    call = mc.split_kv_call(family, cache, Q, lens, causal, ns, W, cu=cu, sink=True)
+    call.specs["sinks"], call.data["sinks"] = mc.spec((H,), f32, side=True), sinks
+    return call
 
 
 @pytest.mark.parametrize("page,fp8", [(None, False), (16, False), (None, True), (128, True)])
