@@ -28,6 +28,9 @@ entry points for that path:
 * ``kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens)`` / ``kv_cache_append_paged(..., block_table, kv_lens)`` -- the write
   side of those caches: the last Sq rows of every sequence, bf16, copied into a bf16 cache or quantised (divide by the per-head
   descale, saturate, round to nearest even) into an fp8 one, in place, positions and pages found on the device.
+* ``rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens)`` and its ``_paged`` / ``_varlen`` / ``_paged_varlen``
+  forms -- the append with the rotary embedding fused in: K rotated at its cache positions into the cache, V appended, the step's Q
+  rotated at the same positions, one launch (``rope_table`` makes the cos / sin table).
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -71,6 +74,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_extend_varlen_plan_window",
            "flash_attention_sink_decode", "flash_attention_sink_decode_paged", "flash_attention_sink_extend",
            "flash_attention_sink_extend_paged", "flash_attention_sink_extend_varlen", "flash_attention_sink_extend_paged_varlen",
+           "flash_attention_rope_append", "flash_attention_rope_append_paged", "flash_attention_rope_append_varlen",
+           "flash_attention_rope_append_paged_varlen",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -93,6 +98,9 @@ _SINK_SYMBOLS = {
 # ... _APPEND_SYMBOLS[paged, ragged], and the plan of a family: _PLAN_SYMBOLS[family, ragged][window > 0]
 _APPEND_SYMBOLS = {(False, False): "flash_attention_kv_append", (True, False): "flash_attention_kv_append_paged",
                    (False, True): "flash_attention_kv_append_varlen", (True, True): "flash_attention_kv_append_paged_varlen"}
+# ... _ROPE_SYMBOLS[paged, ragged]: the append twin with the rotary embedding fused in
+_ROPE_SYMBOLS = {(False, False): "flash_attention_rope_append", (True, False): "flash_attention_rope_append_paged",
+                 (False, True): "flash_attention_rope_append_varlen", (True, True): "flash_attention_rope_append_paged_varlen"}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -185,6 +193,12 @@ def lib() -> ctypes.CDLL:
         for (paged, ragged), name in _APPEND_SYMBOLS.items():
             fn = getattr(L, name)
             fn.argtypes = [vp] * 4 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, i] + [sp] * 4 + [vp]
+            fn.restype = i
+        # the rope twins: Q first, Qout after the new rows, cosSin after the caches; numHeads after batchSize; rotDim, maxPos and
+        # interleaved after dHead; sQ first of the strides and sQout after the new rows'
+        for (paged, ragged), name in _ROPE_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.argtypes = [vp] * 7 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 4 + paging(paged) + [i] * 6 + [sp] * 6 + [vp]
             fn.restype = i
         for by_window in _PLAN_SYMBOLS.values():
             for window, name in enumerate(by_window):
@@ -867,6 +881,123 @@ def kv_cache_append_paged_varlen(K_new, V_new, K_pool, V_pool, block_table, cu_s
     clamped.  Returns None."""
     _append_front("kv_cache_append_paged_varlen", K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale,
                   stream)
+
+
+def rope_table(max_pos, rot_dim, base=10000.0, device=None):
+    """The cos / sin table the ``rope_cache_append*`` calls read: fp32 ``[max_pos, rot_dim]``, row p = ``cos(p * theta_j)`` for
+    ``j < rot_dim / 2`` then ``sin(p * theta_j)``, ``theta_j = base ** (-2 j / rot_dim)`` -- computed in float64 and rounded once.
+    Any other frequency rule (NTK, YaRN, ...) is a table of the caller's own in this layout."""
+    import torch
+    if rot_dim < 2 or rot_dim % 2 or max_pos < 1:
+        raise ValueError("rope_table: max_pos >= 1 and an even rot_dim")
+    theta = float(base) ** (-torch.arange(0, rot_dim, 2, dtype=torch.float64) / rot_dim)
+    angle = torch.arange(max_pos, dtype=torch.float64)[:, None] * theta[None, :]
+    return torch.cat([angle.cos(), angle.sin()], dim=1).to(torch.float32).to(device)
+
+
+def _rope_front(name, Q, K_new, V_new, K, V, cos_sin, block_table, cu_seqlens_q, kv_lens, interleaved, k_descale, v_descale, Q_out,
+                stream):
+    """The four rope_cache_append* fronts: ``_append_front``'s checks of the new rows and the caches, then Q, Q_out and the table,
+    and the entry point of _ROPE_SYMBOLS."""
+    import torch
+    paged, ragged = block_table is not None, cu_seqlens_q is not None
+    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K_cache, V_cache", "[B, Hkv, capacity, d]")
+    if ragged:
+        K_new, V_new, Q = _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), _token_view(Q, "Q")
+        if Q_out is not None:
+            Q_out = _token_view(Q_out, "Q_out")
+    elif paged:
+        _table_geometry(block_table, K_new.shape[0] if K_new.dim() == 4 else 0)
+    if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
+        raise ValueError(f"K_new, V_new must be {'[T, Hkv, d]' if ragged else '[B, Hkv, Sq, d]'} of one dtype, with the K/V heads of {kv} {layout}")
+    if not V_new.is_cuda or not Q.is_cuda:
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    B = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
+    _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=block_table, batch=B)
+    _, Hkv, Sq, d = K_new.shape
+    if Q.dim() != 4 or Q.dtype != K_new.dtype or Q.device != K_new.device or (Q.shape[0], Q.shape[2], Q.shape[3]) != (K_new.shape[0], Sq, d) \
+            or Q.shape[1] < 1 or Q.shape[1] % Hkv:
+        raise ValueError(f"Q must be {'[T, H, d]' if ragged else '[B, H, Sq, d]'} of the dtype and on the device of K_new, with Hkv dividing H")
+    if not ragged:
+        B = K_new.shape[0]
+    if paged:
+        max_pages, table_stride = _table_geometry(block_table, B)
+        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
+    else:
+        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
+    if Sq < 1 or (Sq > capacity and not ragged):
+        raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    t = cos_sin
+    if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != Q.device or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError("cos_sin must be a dense fp32 tensor [max_pos, rot_dim] on the device of Q")
+    max_pos, rot_dim = t.shape
+    if rot_dim % 16 or not 16 <= rot_dim <= d or max_pos < capacity:
+        raise ValueError(f"cos_sin [max_pos, rot_dim]: rot_dim a multiple of 16 in 16 .. d, max_pos at least the capacity ({capacity})")
+    if Q_out is not None and (not getattr(Q_out, "is_cuda", False) or Q_out.shape != Q.shape or Q_out.dtype != Q.dtype or Q_out.device != Q.device):
+        raise ValueError("Q_out must be a device tensor shaped like Q, of its dtype, on its device")
+    with torch.cuda.device(Q.device):
+        if Q_out is None:
+            s = stream if stream is not None else torch.cuda.current_stream()
+            with torch.cuda.stream(s):
+                Q_out = torch.empty((Sq, Q.shape[1], d), dtype=Q.dtype, device=Q.device).unsqueeze(0).transpose(1, 2) if ragged \
+                    else torch.empty(Q.shape, dtype=Q.dtype, device=Q.device)
+        st = [_strides(x) for x in (Q, K_new, V_new, Q_out, K, V)]
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        rc = getattr(lib(), _ROPE_SYMBOLS[paged, ragged])(
+            Q.data_ptr(), K_new.data_ptr(), V_new.data_ptr(), Q_out.data_ptr(), K.data_ptr(), V.data_ptr(), t.data_ptr(),
+            *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Q.shape[1], Hkv,
+            Sq, *geometry, d, rot_dim, max_pos, int(bool(interleaved)), _dtype_code(K_new.dtype), _dtype_code(K.dtype),
+            *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+    _check(rc)
+    return Q_out.transpose(1, 2).squeeze(0) if ragged else Q_out
+
+
+def rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens=None, interleaved=False, k_descale=None, v_descale=None,
+                      Q_out=None, stream=None):
+    """``kv_cache_append`` with the rotary embedding fused in: ONE launch rotates the new K rows at their cache positions and stores
+    them into ``K_cache`` (bf16 or float8_e4m3fn), appends ``V_new`` exactly as ``kv_cache_append`` does, and rotates the step's query
+    rows ``Q`` (bf16 ``[B, H, Sq, d]``, Hkv dividing H; strided views accepted) at the same positions.  Returns the rotated queries:
+    ``Q_out`` (None allocates; ``Q_out=Q`` rotates in place).
+
+    ``cos_sin``: fp32 device tensor ``[max_pos, rot_dim]`` (``rope_table``): row p is ``cos(p theta_j)``, ``j < rot_dim / 2``, then
+    ``sin(p theta_j)``; rot_dim a multiple of 16 up to d (columns beyond it pass through), max_pos at least the capacity.
+    ``interleaved``: False = NeoX pairs ``(j, j + rot_dim / 2)``, True = GPT-J pairs ``(2j, 2j + 1)``.
+
+    Positions: K and V as in ``kv_cache_append``; Q row i is rotated at ``max(clamp(kv_lens[b], 1, capacity) - Sq + i, 0)``, the
+    position ``flash_attention_decode`` / ``flash_attention_extend`` give it, and every Q row is written.  Values:
+    ``y1 = fma(x1, c, -(x2 s))``, ``y2 = fma(x2, c, x1 s)`` in fp32, rounded once to bf16; K then goes through ``kv_cache_append``'s
+    value rule, so the caches equal ``kv_cache_append`` of the bf16 rotation of K, byte for byte.  A decode step is ``kv_lens += Sq;
+    Qr = rope_cache_append(...); flash_attention_decode(Qr, ...)``, one graph.  No CPU fallback."""
+    return _rope_front("rope_cache_append", Q, K_new, V_new, K_cache, V_cache, cos_sin, None, None, kv_lens, interleaved, k_descale,
+                       v_descale, Q_out, stream)
+
+
+def rope_cache_append_paged(Q, K_new, V_new, K_pool, V_pool, block_table, cos_sin, kv_lens=None, interleaved=False, k_descale=None,
+                            v_descale=None, Q_out=None, stream=None):
+    """``rope_cache_append`` into the PAGED caches of ``kv_cache_append_paged`` (max_pos at least ``max_pages * page``).  A table
+    entry outside [0, P) skips the K and V rows of its page; their Q rows are still written."""
+    return _rope_front("rope_cache_append_paged", Q, K_new, V_new, K_pool, V_pool, cos_sin, block_table, None, kv_lens, interleaved,
+                       k_descale, v_descale, Q_out, stream)
+
+
+def rope_cache_append_varlen(Q, K_new, V_new, K_cache, V_cache, cu_seqlens_q, cos_sin, kv_lens=None, interleaved=False, k_descale=None,
+                             v_descale=None, Q_out=None, stream=None):
+    """RAGGED ``rope_cache_append``: ``Q`` ``[T, H, d]`` and ``K_new``, ``V_new`` ``[T, Hkv, d]`` packed by token with ``cu_seqlens_q``,
+    as in ``kv_cache_append_varlen``; returns the rotated queries ``[T, H, d]``.  Every token a sequence owns is written; tokens
+    nobody owns are neither read nor written (a ``Q_out`` allocated here holds unspecified values there).  A step of a mixed batch is
+    ``kv_lens += q_lens; Qr = rope_cache_append_varlen(...); flash_attention_extend_varlen(Qr, ...)``."""
+    return _rope_front("rope_cache_append_varlen", Q, K_new, V_new, K_cache, V_cache, cos_sin, None, cu_seqlens_q, kv_lens, interleaved,
+                       k_descale, v_descale, Q_out, stream)
+
+
+def rope_cache_append_paged_varlen(Q, K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, cos_sin, kv_lens=None, interleaved=False,
+                                   k_descale=None, v_descale=None, Q_out=None, stream=None):
+    """``rope_cache_append_varlen`` into PAGED caches: the pools and the table of ``kv_cache_append_paged``."""
+    return _rope_front("rope_cache_append_paged_varlen", Q, K_new, V_new, K_pool, V_pool, cos_sin, block_table, cu_seqlens_q, kv_lens,
+                       interleaved, k_descale, v_descale, Q_out, stream)
 
 
 def _library_accepts(t):

@@ -19,6 +19,7 @@
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
 #include "kv_append.hip.h"
+#include "rope_append.hip.h"
 
 namespace fa {
 
@@ -392,6 +393,16 @@ struct AppendCall {
     void* stream;
 };
 
+// What flash_attention_rope_append* adds to the append call of the same form: the query rows in and out, the cos / sin table and the
+// pair style
+struct RopeCall {
+    const void* Q;
+    void* Qout;
+    const float* cos_sin;
+    int H, rot_dim, max_pos, interleaved;
+    const fa_strides *sQ, *sQout;
+};
+
 struct DecodeRoute {
     int ns, row_blocks, tiles;
     int64_t grid;
@@ -584,11 +595,22 @@ static int decode_run(SplitCall c) {
 // not capped at FA_DECODE_MAX_Q (the call also fills a cache after a prefill), only at the capacity.
 // Ragged (varlen; flash_attention_kv_append*_varlen): Sq is totalQ, not capped at the capacity; Knew / Vnew are packed by token
 // (strideB is not read; NULL strides: [totalQ, Hkv, d]); cu_seqlens_q -- NULL in the uniform calls -- is required; the token-major kernel.
-static int kv_append_run(AppendCall c) {
+// flash_attention_rope_append* (rope_append.hip.h): the same ladder with the steps of `rope` (NULL in the plain
+// calls) beside the twin's of the same kind -- pointers, alignment, shape, then after the dHead check rotDim, maxPos and the pair
+// style, strides -- and the fused kernels.  Heads: the grid is (units of the twin without its K/V heads and its K-or-V bit) x head
+// slices; a slice is a run of consecutive K/V heads one workgroup loops over, reading each position's table row once.  As many slices
+// as bring the grid to ROPE_WGS_PER_CU workgroups per CU, and no more: a decode step spreads its heads over the device, a long cache
+// fill reads the table once per position.  (Eight: a workgroup's four waves each wait on one batch of loads at a time, so the bytes
+// in flight come from the number of resident waves; the register count allows three workgroups per CU, and several rounds of them
+// even out the tail.  The re-reads of a table row by the slices of one position are L2 hits.)
+constexpr int ROPE_WGS_PER_CU = 8;
+static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
     const DecodePaging* pg = c.cache.paging;
     const int B = c.B, Hkv = c.Hkv, Sq = c.Sq, d = c.d, kv_dtype = c.cache.kv_dtype;
     if (!c.Knew || !c.Vnew || !c.cache.K || !c.cache.V || (pg && !pg->table) || (c.varlen && !c.cu_seqlens_q)) return FA_ERR_NULL_POINTER;
+    if (rope && (!rope->Q || !rope->Qout || !rope->cos_sin)) return FA_ERR_NULL_POINTER;
     if (!aligned16(c.Knew) || !aligned16(c.Vnew) || !aligned16(c.cache.K) || !aligned16(c.cache.V)) return FA_ERR_MISALIGNED;
+    if (rope && (!aligned16(rope->Q) || !aligned16(rope->Qout) || !aligned16(rope->cos_sin))) return FA_ERR_MISALIGNED;
     int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
     if (rc != FA_OK) return rc;
     if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
@@ -596,22 +618,33 @@ static int kv_append_run(AppendCall c) {
     if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
     if (Sk > (1 << 24) || (!c.varlen && Sq > Sk) || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
     if (c.varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
+    const int H = rope ? rope->H : Hkv;
+    if (rope && (!kv_heads_ok(H, Hkv) || (int64_t)B * H > INT32_MAX / 2)) return FA_ERR_BAD_SHAPE;
     if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (kv_dtype == FA_DTYPE_BF16 && (c.cache.k_descale || c.cache.v_descale)) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
     if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
-    fa_strides tK{}, tV{};   // ragged: the new rows on their token strides
+    if (rope) {
+        if (rope->rot_dim < 16 || rope->rot_dim > d || rope->rot_dim % 16) return FA_ERR_BAD_SHAPE;
+        if (rope->max_pos < Sk) return FA_ERR_BAD_SHAPE;   // every position the kernel can form lies in the table
+        if (rope->interleaved != 0 && rope->interleaved != 1) return FA_ERR_BAD_FLAGS;
+    }
+    fa_strides tK{}, tV{}, tQ{}, tO{};   // ragged: the new rows on their token strides
+    const fa_strides *sQ = rope ? rope->sQ : nullptr, *sQout = rope ? rope->sQout : nullptr;
     if (c.varlen) {
         tK = token_strides(c.sKnew, Hkv, d); c.sKnew = &tK;
         tV = token_strides(c.sVnew, Hkv, d); c.sVnew = &tV;
+        tQ = token_strides(sQ, H, d); sQ = &tQ;
+        tO = token_strides(sQout, H, d); sQout = &tO;
     }
     if (!strides_ok(c.sKnew, 2, d) || !strides_ok(c.sVnew, 2, d) || !cache_strides_ok(c.cache, d)) return FA_ERR_BAD_STRIDE;
+    if (rope && (!strides_ok(sQ, 2, d) || !strides_ok(sQout, 2, d))) return FA_ERR_BAD_STRIDE;
     if (!cache_extent_ok(c.cache, d)) return FA_ERR_BAD_SHAPE;   // what is written can be read
     const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
     const int tokens_per_block = KvAppendCfg::THREADS / (d / 8);                     // ragged: a row per d / 8 lanes
     const int token_blocks = (int)(((int64_t)Sq + tokens_per_block - 1) / tokens_per_block);
     const int64_t grid = c.varlen ? (int64_t)Hkv * token_blocks * 2 : (int64_t)B * Hkv * row_blocks * 2;
-    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;   // (the fused calls' limit too: their own grid is never larger)
 
     const int rowsK = cache_rows(c.cache);
     KvAppendParams p;
@@ -629,6 +662,27 @@ static int kv_append_run(AppendCall c) {
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    if (rope) {
+        static_assert(RopeAppendCfg::BLOCK == KvAppendCfg::BLOCK && RopeAppendCfg::THREADS == KvAppendCfg::THREADS);
+        RopeAppendParams r;
+        r.a = p;
+        r.Q = (const __bf16*)rope->Q; r.Qout = (__bf16*)rope->Qout; r.cos_sin = rope->cos_sin;
+        resolve_strides(sQ, H, Sq, d, r.qB, r.qH, r.qS);
+        resolve_strides(sQout, H, Sq, d, r.oB, r.oH, r.oS);
+        r.G = H / Hkv; r.rot = rope->rot_dim; r.interleaved = rope->interleaved;
+        const int rope_token_blocks = (int)(((int64_t)Sq + 2 * tokens_per_block - 1) / (2 * tokens_per_block));   // a row per d / 16 lanes
+        const int64_t base = c.varlen ? (int64_t)rope_token_blocks : (int64_t)B * row_blocks;                      // <= grid / (2 Hkv)
+        const int64_t want = ((int64_t)ROPE_WGS_PER_CU * device_cus() + base - 1) / base;
+        r.heads_per_slice = (int)((Hkv + std::min<int64_t>(want, Hkv) - 1) / std::min<int64_t>(want, Hkv));
+        r.head_slices = (Hkv + r.heads_per_slice - 1) / r.heads_per_slice;
+        const unsigned rope_grid = (unsigned)(base * r.head_slices);
+        const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
+        if (c.varlen) {
+            const RopeAppendVarlenParams rv{r, c.cu_seqlens_q, B, rope_token_blocks};
+            return (int)launch(rope_append_varlen_kernel_of(d, kv8, pg != nullptr), rope_grid, RopeAppendCfg::THREADS, 0, st, rv);
+        }
+        return (int)launch(rope_append_kernel_of(d, kv8, pg != nullptr), rope_grid, RopeAppendCfg::THREADS, 0, st, r);
+    }
     if (c.varlen) {
         const KvAppendVarlenParams pv{p, c.cu_seqlens_q, B, token_blocks};
         const Kernel kr = kv_append_varlen_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
@@ -1224,6 +1278,69 @@ int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, v
                                         .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
                               .B = batchSize, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = dtype, .sKnew = sKnew,
                               .sVnew = sVnew, .stream = stream});
+}
+
+int flash_attention_rope_append(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V, const float* cosSin,
+                                const int32_t* kvLens, const float* kDescale, const float* vDescale, int batchSize, int numHeads,
+                                int numHeadsKV, int seqLenNew, int seqLenK, int dHead, int rotDim, int maxPos, int interleaved, int dtype,
+                                int kv_dtype, const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
+                                const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream) {
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout};
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
+}
+
+int flash_attention_rope_append_paged(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                      const float* cosSin, const int32_t* kvLens, const int32_t* blockTable, const float* kDescale,
+                                      const float* vDescale, int batchSize, int numHeads, int numHeadsKV, int seqLenNew, int numPages,
+                                      int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, int rotDim, int maxPos,
+                                      int interleaved, int dtype, int kv_dtype, const fa_strides* sQ, const fa_strides* sKnew,
+                                      const fa_strides* sVnew, const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV,
+                                      void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout};
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
+}
+
+int flash_attention_rope_append_varlen(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V,
+                                       const float* cosSin, const int32_t* cuSeqlensQ, const int32_t* kvLens, const float* kDescale,
+                                       const float* vDescale, int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK,
+                                       int dHead, int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype, const fa_strides* sQ,
+                                       const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sQout, const fa_strides* sK,
+                                       const fa_strides* sV, void* stream) {
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout};
+    return fa::kv_append_run({.varlen = true, .Knew = Knew, .Vnew = Vnew, .cu_seqlens_q = cuSeqlensQ,
+                              .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
+}
+
+int flash_attention_rope_append_paged_varlen(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                             const float* cosSin, const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                             const int32_t* blockTable, const float* kDescale, const float* vDescale, int batchSize,
+                                             int numHeads, int numHeadsKV, int totalQ, int numPages, int pageSize, int maxPagesPerSeq,
+                                             int64_t tableStride, int dHead, int rotDim, int maxPos, int interleaved, int dtype,
+                                             int kv_dtype, const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
+                                             const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout};
+    return fa::kv_append_run({.varlen = true, .Knew = Knew, .Vnew = Vnew, .cu_seqlens_q = cuSeqlensQ,
+                              .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = totalQ, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
 }
 
 

@@ -616,7 +616,8 @@ int flash_attention_decode_paged_window(const void* Q, const void* Kpool, const 
  * not a power of two, tableStride < maxPagesPerSeq, one head's extent ((seqLenK + 192) x row stride; paged: pageSize x row stride)
  * of 2^31 bytes or more FA_ERR_BAD_SHAPE; dtype other than FA_DTYPE_BF16, kv_dtype other than FA_DTYPE_BF16 / FA_DTYPE_FP8_E4M3, or
  * a non-NULL descale with a bf16 cache FA_ERR_UNSUPPORTED_DTYPE; any other dHead FA_ERR_UNSUPPORTED_DHEAD.
- * Not done here: rotary embedding, fp8 new rows, per-token or per-block descales, writing kvLens.
+ * Rotary embedding: flash_attention_rope_append* (below) are these calls with the rotation of K and of the step's Q fused in.
+ * Not done here: fp8 new rows, per-token or per-block descales, writing kvLens.
  */
 int flash_attention_kv_append(const void* Knew, const void* Vnew, void* K, void* V,
                               const int32_t* kvLens, const float* kDescale, const float* vDescale,
@@ -969,6 +970,84 @@ int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, v
                                            int dtype, int kv_dtype,
                                            const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sK, const fa_strides* sV,
                                            void* stream);
+
+/*
+ * flash_attention_rope_append, _paged, _varlen, _paged_varlen -- the cache append with the ROTARY EMBEDDING fused in: each is its
+ * flash_attention_kv_append* twin plus the step's query rows and a cos / sin table.  One launch rotates the new K rows at their cache
+ * positions and stores them into the K cache, appends the new V rows exactly as the twin does, and rotates the Q rows at the same
+ * positions into Qout.  A step is `kv_lens += Sq; rope_append; decode | extend` (ragged: `kv_lens += q_lens; rope_append_varlen;
+ * extend_varlen`) on one device tensor of lengths: one graph, no host synchronisation, no rotated K in memory besides the cache.
+ * Everything not named here -- Knew, Vnew, the caches, kvLens, the table, the descales, their strides and limits -- is the twin's.
+ *   Q, Qout  bf16 [batchSize, numHeads, seqLenNew, dHead]; ragged: packed by token, [totalQ, numHeads, dHead], on the stride rule of
+ *            flash_attention_extend_varlen's Q.  sQ / sQout: element strides or NULL (dense); the last dimension is contiguous, so
+ *            the Q slice of a fused QKV projection passes without a copy.  Qout may be the very same view as Q (in place: same
+ *            base, same strides); any other overlap is unspecified.  numHeads is a multiple of numHeadsKV
+ *   cosSin   fp32 [maxPos, rotDim], device memory, dense, base aligned to 16 bytes: row p holds cos(p theta_j) for j < rotDim / 2,
+ *            then sin(p theta_j) -- the common cos_sin_cache layout.  The call never computes a sine: frequency scaling (NTK, YaRN,
+ *            ...) is whatever the caller put into the table.  Read BY THE KERNEL
+ *   rotDim   a multiple of 16, 16 <= rotDim <= dHead (partial rotary): the columns >= rotDim pass through unrotated
+ *   maxPos   >= the capacity (seqLenK; paged: maxPagesPerSeq * pageSize): every position the kernel can form is then inside the
+ *            table, and nothing is clamped on the device
+ *   interleaved  0: NeoX / half-split pairs (j, j + rotDim / 2); 1: GPT-J pairs (2j, 2j + 1).  Both with angle index j
+ *
+ * Positions.  K and V: the twin's rule unchanged -- L = min(kvLens[b], capacity), row i goes to p = L - seqLenNew + i, written iff
+ * p >= 0; L <= 0 writes nothing; a table entry outside [0, numPages) skips the K / V rows of its page (their Q rows are still
+ * written).  Q: EVERY row of every sequence is written (ragged: every token a sequence owns; tokens nobody owns are neither read nor
+ * written), rotated at pq = max(clamp(kvLens[b], 1, capacity) - seqLenNew + i, 0): the position decode's and extend's bottom-right mask
+ * gives the row, their "at least key 0" rule for kvLens[b] < seqLenNew and their clamp of an inactive slot included.  For every row
+ * whose K is written pq = p.  NULL kvLens = the capacity.
+ *
+ * Values, to the bit.  x1, x2: the pair as fp32 (exact from bf16); c, s: the table's cos and sin of (position, j).
+ *     y1 = fmaf(x1, c, -(x2 * s)),  y2 = fmaf(x2, c, x1 * s)      the lone product rounded to fp32 first, the other fused
+ * then y is rounded ONCE to bf16, to nearest even.  That bf16 value is Qout's element.  For K it goes through exactly the twin's
+ * value rule: a bit copy into a bf16 cache; divided by the descale, saturated at +-448, rounded once, with the twin's NaN rule, into
+ * an e4m3fn cache.  So flash_attention_rope_append* == flash_attention_kv_append* applied to the bf16 rotation of Knew, byte for byte.
+ * The columns >= rotDim of K and all of V have the twin's bits (NaN payloads, -0); the columns >= rotDim of Q are a bit copy.  NaN in
+ * gives NaN out, the pattern unspecified.  With cos = 1, sin = 0 a finite x comes back with its value; -0 may lose its sign (-0 + +0).
+ *
+ * Conventions: the twin's -- validated before the launch; no allocation, no synchronisation, nothing printed; one writer per byte.
+ * Rejected with the twin's codes for the twin's mistakes, in the twin's order, the new checks beside the twin's of the same kind:
+ * a NULL Q, Qout or cosSin FA_ERR_NULL_POINTER; one of them not aligned to 16 bytes FA_ERR_MISALIGNED; numHeads <= 0, not a multiple
+ * of numHeadsKV, numHeads * (numHeads / numHeadsKV) >= 2^31 or batchSize * numHeads > INT32_MAX / 2 FA_ERR_BAD_SHAPE (with the
+ * twin's shape checks); then, after the dHead check, rotDim not a multiple of 16 or outside [16, dHead] FA_ERR_BAD_SHAPE, maxPos
+ * below the capacity FA_ERR_BAD_SHAPE, interleaved neither 0 nor 1 FA_ERR_BAD_FLAGS; a stride of Q or Qout that is not a multiple of
+ * 16 bytes, or a row stride below dHead, FA_ERR_BAD_STRIDE (after the twin's strides).  The grid limit is the twin's.
+ * Not done here: explicit position ids or offsets, sines computed on the device, fp8 or fp32 new rows, per-token descales, writing
+ * kvLens, rotary embedding in flash_attention() or the backward, dHead other than 64 / 128.
+ */
+int flash_attention_rope_append(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V,
+                                const float* cosSin, const int32_t* kvLens, const float* kDescale, const float* vDescale,
+                                int batchSize, int numHeads, int numHeadsKV, int seqLenNew, int seqLenK, int dHead,
+                                int rotDim, int maxPos, int interleaved /* 0 half-split pairs | 1 adjacent pairs */,
+                                int dtype /* of Q, Knew, Vnew, Qout: FA_DTYPE_BF16 */, int kv_dtype /* FA_DTYPE_BF16 | FA_DTYPE_FP8_E4M3 */,
+                                const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sQout,
+                                const fa_strides* sK, const fa_strides* sV, void* stream);
+
+int flash_attention_rope_append_paged(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                      const float* cosSin, const int32_t* kvLens, const int32_t* blockTable,
+                                      const float* kDescale, const float* vDescale,
+                                      int batchSize, int numHeads, int numHeadsKV, int seqLenNew,
+                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                      int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
+                                      const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sQout,
+                                      const fa_strides* sK, const fa_strides* sV, void* stream);
+
+int flash_attention_rope_append_varlen(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V,
+                                       const float* cosSin, const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                       const float* kDescale, const float* vDescale,
+                                       int batchSize, int numHeads, int numHeadsKV, int totalQ, int seqLenK, int dHead,
+                                       int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
+                                       const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sQout,
+                                       const fa_strides* sK, const fa_strides* sV, void* stream);
+
+int flash_attention_rope_append_paged_varlen(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                             const float* cosSin, const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                             const int32_t* blockTable, const float* kDescale, const float* vDescale,
+                                             int batchSize, int numHeads, int numHeadsKV, int totalQ,
+                                             int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                             int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
+                                             const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
+                                             const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);

@@ -2,7 +2,7 @@
 """Time flash_attention_decode (split-KV decode): one JSON line per shape.
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
-                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks]
+                                [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks] [--rope]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -39,6 +39,22 @@ Each line:
               fill_ms[form], fill_tbps[form]  one call with Sq = 4096 and kv_lens = None (the cache's last 4096 rows: a fill after a
                                     prefill); bytes read + written = B Hkv 4096 d x 2 tensors x (2 + bytes per cache element)
               each with _min / _max over the windows (profiles/kv_append_bench.log).
+--rope          the append with the rotary embedding fused in (rope_cache_append, rope_cache_append_paged) beside the routes without it: a
+              mode of its own over the --append shapes, one line per shape, every figure per cache form ("bf16", with --kv fp8 "fp8",
+              with --paged "paged<page>" and "paged<page>_fp8"); full rotary (rot_dim = d), half-split pairs, the shape's lengths:
+              rope_append_ms[form]  one fused call: Q and K rotated, K and V into the cache, Qout written
+              unfused_ms[form]      what a caller does today: torch ops that take the positions from kv_lens on the device, gather
+                                    cos / sin, rotate Q and K in fp32 and round them to bf16, then kv_cache_append* of the rotated K
+              append_ms[form]       the plain kv_cache_append* of the same rows: the floor (no Q traffic, no rotation)
+              the three ALTERNATED, --repeats windows of --steps calls each; _min / _max their spread
+              rope_matches_unfused[form]  the two routes agree as far as their arithmetic lets them: torch rounds x1 c and x2 s each
+                                    to fp32 before the subtraction, the fused expression one of them, so before the rounding to bf16
+                                    the two differ by at most 2^-23 (|x1| + |x2|).  Qout and a bf16 K cache: |a - b| <= one bf16 ulp
+                                    of the larger, 2^-7 max(|a|, |b|), plus 2^-21 of the largest |x|; an fp8 K cache: codes one
+                                    apart at the most; the V cache: the same bytes
+              rope_fill_ms, unfused_fill_ms, fill_ms, q_copy_fill_ms[form]  (Sk >= 4096) the same three with Sq = 4096 and
+                                    kv_lens = None, and a plain bf16 copy of that Q: the fused fill is expected near fill_ms +
+                                    q_copy_fill_ms (profiles/rope_append_gpu.log).
 --splits a,b,c  the forced-split sweep: one line per (shape, split count) with ms only (profiles/decode_split_sweep.log).
 --extend        flash_attention_extend / flash_attention_extend_paged (chunked prefill against the decode caches) instead of decode:
               one line per shape and cache form -- "bf16", with --kv fp8 "fp8", with --paged "paged<page>" (and "paged<page>_fp8") --
@@ -599,6 +615,111 @@ def sinks_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def rope_main(args, fa, dev):
+    import torch
+    bf = torch.bfloat16
+    shapes = [x for x in SHAPES + EXTRA if x[0] in args.shape] if args.shape else SHAPES
+    for name, B, H, Hkv, Sq, Sk, d, ragged in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        lens = [1024 + (Sk - 1024) * b // (B - 1) for b in range(B)] if ragged else [Sk] * B
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        table_cs = fa.rope_table(Sk, d, device=dev)
+        half = d // 2
+        kds, vds = (torch.rand(Hkv, device=dev, generator=g) * 0.05 + 0.01 for _ in range(2))
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in (int(x) for x in (args.paged or "").split(",") if x):
+            if Sk % page == 0:
+                forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        line = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "Sq": Sq, "Sk": Sk, "d": d, "ragged": ragged, "rot_dim": d, "repeats": args.repeats,
+                "steps": args.steps}
+        out = {}
+
+        def routes(rows, L, Kc, Vc, table, kw):
+            """(fused, unfused, plain append, copy of Q, the tensors) for `rows` new rows per sequence at the lengths L (None: the capacity)"""
+            Q = torch.randn(B, H, rows, d, device=dev, generator=g).to(bf)
+            Kn, Vn = (torch.randn(B, Hkv, rows, d, device=dev, generator=g).to(bf) for _ in range(2))
+            Qo = torch.empty_like(Q)
+            ar = torch.arange(rows, device=dev)
+            if table is not None:
+                fused = lambda: fa.rope_cache_append_paged(Q, Kn, Vn, Kc, Vc, table, table_cs, L, Q_out=Qo, **kw)
+                plain_of = lambda k: fa.kv_cache_append_paged(k, Vn, Kc, Vc, table, L, **kw)
+            else:
+                fused = lambda: fa.rope_cache_append(Q, Kn, Vn, Kc, Vc, table_cs, L, Q_out=Qo, **kw)
+                plain_of = lambda k: fa.kv_cache_append(k, Vn, Kc, Vc, L, **kw)
+            Qu = torch.empty_like(Q)
+
+            def rotate(x, c, s):
+                xf = x.float()
+                x1, x2 = xf[..., :half], xf[..., half:]
+                return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(bf)
+
+            def unfused():
+                length = lens_d.clamp(1, Sk) if L is not None else torch.full((B,), Sk, dtype=torch.int32, device=dev)
+                pos = ((length - rows)[:, None] + ar).clamp(min=0).long()
+                cs = table_cs[pos]
+                c, s = cs[:, None, :, :half], cs[:, None, :, half:]
+                Qu.copy_(rotate(Q, c, s))
+                plain_of(rotate(Kn, c, s))
+
+            return fused, unfused, (lambda: plain_of(Kn)), (lambda: Qo.copy_(Q)), Qo, Qu, Q, Kn
+
+        def close(a, b, x):
+            """the two routes' bf16 values (x: what was rotated) or e4m3fn codes agree as the tool's docstring says"""
+            if a.element_size() == 1:
+                code = lambda t: (t.view(torch.uint8) & 0x7F).int() * (1 - 2 * (t.view(torch.uint8) >> 7).int())   # sign and magnitude
+                return int((code(a) - code(b)).abs().max()) <= 1
+            a, b = a.float(), b.float()
+            return bool(((a - b).abs() <= 2.0 ** -7 * torch.maximum(a.abs(), b.abs()) + 2.0 ** -21 * float(x.float().abs().max())).all())
+
+        for form, fp8, page in forms:
+            cdt = torch.float8_e4m3fn if fp8 else bf
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                n = Sk // page
+                table = torch.randperm(B * n, device=dev, generator=g).reshape(B, n).to(torch.int32)
+                Kc, Vc = (torch.zeros(B * n, Hkv, page, d, device=dev, dtype=torch.uint8 if fp8 else bf).view(cdt) for _ in range(2))
+            else:
+                table = None
+                Kc, Vc = (torch.zeros(B, Hkv, Sk, d, device=dev, dtype=torch.uint8 if fp8 else bf).view(cdt) for _ in range(2))
+            fused, unfused, plain, _, Qo, Qu, Q, Kn = routes(Sq, lens_d, Kc, Vc, table, kw)
+            fused()
+            keptK, keptV = Kc.clone(), Vc.clone()
+            Kc.view(torch.uint8).zero_()
+            Vc.view(torch.uint8).zero_()
+            unfused()
+            res = {"rope_matches_unfused": close(Qo, Qu, Q) and close(keptK, Kc, Kn)
+                   and bool(torch.equal(keptV.view(torch.uint8), Vc.view(torch.uint8)))}
+            del keptK, keptV, Q, Kn
+            t = {"rope_append_ms": [], "unfused_ms": [], "append_ms": []}
+            for _ in range(args.repeats):      # alternated: one window of each
+                t["rope_append_ms"].append(timed(fused, args.steps, args.warmup))
+                t["unfused_ms"].append(timed(unfused, args.steps, args.warmup))
+                t["append_ms"].append(timed(plain, args.steps, args.warmup))
+            del fused, unfused, plain, Qo, Qu
+            if Sk >= 4096:
+                fused, unfused, plain, copy, Qo, Qu, Q, Kn = routes(4096, None, Kc, Vc, table, kw)
+                steps = max(10, args.steps // 10)
+                t.update(rope_fill_ms=[], unfused_fill_ms=[], fill_ms=[], q_copy_fill_ms=[])
+                for _ in range(args.repeats):
+                    t["rope_fill_ms"].append(timed(fused, steps, 3))
+                    t["unfused_fill_ms"].append(timed(unfused, steps, 3))
+                    t["fill_ms"].append(timed(plain, steps, 3))
+                    t["q_copy_fill_ms"].append(timed(copy, steps, 3))
+                del fused, unfused, plain, copy, Qo, Qu, Q, Kn
+            res.update({k: sorted(v) for k, v in t.items()})
+            out[form] = res
+            del Kc, Vc
+            torch.cuda.empty_cache()
+        for key in ("rope_append_ms", "unfused_ms", "append_ms", "rope_fill_ms", "unfused_fill_ms", "fill_ms", "q_copy_fill_ms"):
+            have = {f: v[key] for f, v in out.items() if key in v}
+            if have:
+                line[key] = {f: round(statistics.median(v), 5) for f, v in have.items()}
+                line[key + "_min"] = {f: round(v[0], 5) for f, v in have.items()}
+                line[key + "_max"] = {f: round(v[-1], 5) for f, v in have.items()}
+        line["rope_matches_unfused"] = {f: v["rope_matches_unfused"] for f, v in out.items()}
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -614,11 +735,14 @@ def main():
     ap.add_argument("--varlen", action="store_true", help="time flash_attention_extend_varlen on mixed batches, beside the grouped calls of today")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
+    ap.add_argument("--rope", action="store_true", help="time rope_cache_append* beside the unfused torch route and the plain append, alternated")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.rope:
+        return rope_main(args, fa, dev)
     if args.sinks:
         return sinks_main(args, fa, dev)
     if args.extend:
