@@ -24,7 +24,7 @@ MFMA_VGPR := -mllvm -amdgpu-mfma-vgpr-form=1
 build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
-tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam: HIPFLAGS += $(MFMA_VGPR)
+tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill instantiations of the split-KV kernel at d = 128 (decode_bf16.hip.h with RT = 4: four 16-row tiles per wave, launch
 # bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
 # in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
@@ -67,6 +67,10 @@ tests/fa_tune: tests/fa_tune.hip $(KHDR) oracle/liboracle_attention.so
 # the seam switches of KernelCfg, one at a time, interleaved (profiles/ARMS_seam.md)
 tests/fa_tune_seam: tests/fa_tune_seam.hip $(KHDR)
 	$(HIPCC) $(HIPFLAGS) -o $@ tests/fa_tune_seam.hip
+
+# the switches of a wave's last tile (KernelCfg::TAIL, TAIL_HALF), interleaved (profiles/ARMS_tail.md)
+tests/fa_tune_tail: tests/fa_tune_tail.hip $(KHDR)
+	$(HIPCC) $(HIPFLAGS) -o $@ tests/fa_tune_tail.hip
 
 # ... with the causal d = 128 variants only (a third of the compile time)
 tests/fa_tune_c128: tests/fa_tune.hip $(KHDR) oracle/liboracle_attention.so
@@ -128,6 +132,6 @@ build/asm/%.s: $(PKG)/csrc/%.hip $(KHDR)
 asm: $(KASM)
 
 clean:
-	rm -f $(LIB) $(PKG)/fa_main tests/fa_test tests/fa_tune tests/fa_tune_seam tests/unit_kernels tests/micro/simd_mix tests/micro/valu_rates tests/micro/atomic_latency oracle/liboracle_attention.so
+	rm -f $(LIB) $(PKG)/fa_main tests/fa_test tests/fa_tune tests/fa_tune_seam tests/fa_tune_tail tests/unit_kernels tests/micro/simd_mix tests/micro/valu_rates tests/micro/atomic_latency oracle/liboracle_attention.so
 	rm -rf build
 .PHONY: all lib tune oracle clean asm asan asan-host

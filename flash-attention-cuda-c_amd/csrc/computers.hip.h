@@ -270,6 +270,48 @@ struct WaveCompute : SlotEngine<WaveCompute<C>, C> {
         }
     }
 
+    // The phase-B-only step of a wave's last tile (SlotEngine::tail_step).  Lead-in: the first VPRE V^T fragments, the tile's staging
+    // pieces, the weights of k-step 0.  Tail slot J: the P.V MFMA of fragment J, the V^T fragment VPRE ahead, and of the weights of the
+    // k-step after this one the share that completes it before its first MFMA.  Slots J0 .. J1 - 1 of a step of ST slots.
+    __host__ __device__ static constexpr int tail_elem_slot(int E) { return (E / 8 - 1) * DB + (E % 8) * DB / 8; }
+    template <int E, bool F16W = false>
+    __device__ __forceinline__ void tail_pre(Stage& st, int t_load, lds_ptr v_cur, int vbase, float c, const Scores<R>& cur) {
+        static_assert(R == 1 && NL <= 8 && VPRE <= DB, "tail step: one row group, the lead-in carries every piece");
+        if constexpr (E < 8) {
+            if constexpr (E < VPRE) vf[E % (VPRE + 1)] = v_frag(v_cur, vbase, E / DB, E % DB);
+            if constexpr (E < NL) st.template load<E, F16W>(t_load);
+            this->template exp_elem<E, F16W>(cur, c);
+            tail_pre<E + 1, F16W>(st, t_load, v_cur, vbase, c, cur);
+        }
+    }
+    template <int J, int ST, int E = 8, bool F16W = false>
+    __device__ __forceinline__ void tail_exp(const Scores<R>& cur, float c) {
+        if constexpr (E < 8 * (ST / DB)) {
+            if constexpr (tail_elem_slot(E) == J) this->template exp_elem<E, F16W>(cur, c);
+            tail_exp<J, ST, E + 1, F16W>(cur, c);
+        }
+    }
+    template <int J, int J1, int ST, bool F16W = false>
+    __device__ __forceinline__ void slots_t(lds_ptr v_cur, int vbase, float c, const Scores<R>& cur) {
+        if constexpr (J < J1) {
+            constexpr int s4 = J / DB, db = J % DB;
+            if constexpr (F16W) o[0][db] = mfma_32x32x16(__builtin_bit_cast(f16x8, vf[J % (VPRE + 1)]), __builtin_bit_cast(f16x8, p_frag(0, s4)), o[0][db]);
+            else o[0][db] = mfma_32x32x16(vf[J % (VPRE + 1)], p_frag(0, s4), o[0][db]);
+            if constexpr (J + VPRE < ST) {
+                constexpr int vn = J + VPRE;
+                vf[vn % (VPRE + 1)] = v_frag(v_cur, vbase, vn / DB, vn % DB);
+            }
+            tail_exp<J, ST, 8, F16W>(cur, c);
+            __builtin_amdgcn_sched_barrier(0);
+            slots_t<J + 1, J1, ST, F16W>(v_cur, vbase, c, cur);
+        }
+    }
+    __device__ __forceinline__ void begin_tail(Stage& st, lds_ptr wr_slot) {
+        st.set_dst(wr_slot);
+#pragma unroll
+        for (int r = 0; r < R; ++r) sum_a[r] = sum_b[r] = 0.f;
+    }
+
     // ---- what SlotEngine::tile_step leaves to the engine ----
     __device__ __forceinline__ void begin_tile(Stage& st, lds_ptr wr_slot, Scores<R>& nxt) {
         st.set_dst(wr_slot);   // (LDS-DMA staging: where this iteration's loads land)

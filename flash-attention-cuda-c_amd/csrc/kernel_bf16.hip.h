@@ -49,6 +49,9 @@ struct Opt {
     // switches of the unit seam, each -1 = the library's choice, 0 / 1 = forced off / on (tests/fa_tune_seam.hip times them against each other)
     int kv_clamp = -1;           // KernelCfg::KV_CLAMP
     int q_nt = -1;               // KernelCfg::Q_CACHE: non-temporal Q loads
+    // switches of a wave's last tile (tests/fa_tune_tail.hip), same convention
+    int tail = -1;               // KernelCfg::TAIL: the last tile's step is phase B alone
+    int tail_half = -1;          // KernelCfg::TAIL_HALF: ... and skips the wholly masked key half of a diagonal tile (-1: with tail)
 };
 
 template <int D_, bool CAUSAL_, typename OutT_, int ESZ_ = 2, Opt O = Opt{}>
@@ -85,6 +88,15 @@ struct KernelCfg {
     // did not resolve in the two later runs; with Q_CACHE: see there.
     // (The unit decode's divisions as multiply and shift with host constants: measured, not adopted -- profiles/seam_fastdiv_arm.patch)
     static constexpr bool KV_CLAMP = CAUSAL_ && O.kv_clamp != 0;
+    // The optimistic passes run a wave's last tile (the kind-1 steps of attention_pass) through SlotEngine::tail_step: no look-ahead
+    // QK^T on a tile the wave does not need (16 MFMAs and 16 K fragment reads at d = 128), and for the wave whose 32 rows start on a
+    // 64-row boundary no exponentials, V^T reads and P.V MFMAs on the 32 keys of its diagonal tile that every row masks (TAIL_HALF).
+    // Per 256-row unit of query block qb wave w then issues 8 qb + w + 1 (w odd) or 8 qb + w + 1 1/2 (w even) groups of 16 MFMAs instead of
+    // 8 qb + 2 (w / 2) + 3: -1.9 % of the MFMAs of the causal headline shape, derived and counted (profiles/ARMS_tail.md).  The
+    // tracked and last-resort passes keep tile_step for every tile.  The library's choice: the mixed-precision kernels under the
+    // mask (32x32x16 engine); what it measured: profiles/ARMS_tail.md
+    static constexpr bool TAIL = ESZ_ == 2 && O.m16 == 0 && (O.tail < 0 ? CAUSAL_ && O.mix : O.tail != 0);
+    static constexpr bool TAIL_HALF = TAIL && CAUSAL_ && O.tail_half != 0;
     // Q rows fetched whole and turned into fragments through LDS (q_rows_to_fragments): on at d = 128 (+0.8 %), off at d = 64
     // (the 37 us cfg1 loses 1.8 % to the extra LDS trip)
     static constexpr bool COALESCED_Q = D_ == 128 && !O.pad;
@@ -208,12 +220,18 @@ __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>
 
     // ring slot byte offsets of tiles t, t+1, t+AHEAD
     int so_cur = 0, so_nxt = SLOT, so_wr = AHEAD * SLOT;
-    // kind: 0 = full step (a next tile exists), 1 = the wave's last tile (its QK^T runs on a tile it does not need), 2 = staging
+    // kind: 0 = full step (a next tile exists), 1 = the wave's last tile (C::TAIL, optimistic pass: tail_step; else its QK^T runs on a
+    // tile it does not need), 2 = staging
     // only (the wave is past its causal diagonal but still stages its share of the tiles the other waves need)
-    auto step = [&](int t, int kind, typename WC::ScoresT& cur, typename WC::ScoresT& nxt) {
+    // TAIL_SITE: the call is the wave's last tile of an optimistic pass under C::TAIL (tail_step)
+    auto step = [&]<bool TAIL_SITE = false>(int t, int kind, typename WC::ScoresT& cur, typename WC::ScoresT& nxt) {
         unsigned long long t0 = 0, t4 = 0, t6 = 0;
         if constexpr (C::STAMP) t0 = cycle_stamp();
-        if (kind != 2) {
+        if constexpr (TAIL_SITE) {
+            // (wave-uniform: the wave's rows start on a 64-row boundary and this is its diagonal tile)
+            const bool half = C::TAIL_HALF && (q_row0 & 63) == 0 && t * KVBLK + 32 > q_row0 + 31;
+            w.template tail_step<F16W>(st, t + AHEAD, smem + so_wr, smem + so_cur + KT, vbase, c, cur, half);
+        } else if (kind != 2) {
             const bool has_next = kind == 0;
             w.template tile_step<TRACK, F16W>(st, t + AHEAD, smem + so_wr, smem + so_nxt, smem + so_cur + KT, kbase, vbase, c, cur, nxt,
                                               has_next, has_next && needs_mask(t + 1), (t + 1) * KVBLK, q_row0, S, lane);
@@ -235,9 +253,29 @@ __device__ __forceinline__ bool attention_pass(const Params& p, WaveComputeOf<C>
         so_wr = tmp;
     };
     auto kind_of = [&](int t) { return t + 1 < my_tiles ? 0 : (t < my_tiles ? 1 : 2); };
-    for (int t = 0; t < n_tiles; t += 2) {
-        step(t, kind_of(t), sA, sB);
-        if (t + 1 < n_tiles) step(t + 1, kind_of(t + 1), sB, sA);
+    if constexpr (C::TAIL && !TRACK) {
+        // The same steps in the same order, grouped by kind: the full steps keep their loop of two unrolled calls, the wave's last
+        // tile follows it at ONE site, then the staging-only steps.  (With tail bodies inside the one loop, or one per parity behind
+        // it, hipcc allocates 256 VGPRs and spills 60 ... 600 at d = 128: profiles/ARMS_tail.md.)
+        const int last = my_tiles - 1;   // the wave's last tile; -1: none
+        for (int t = 0; t < last; t += 2) {
+            step(t, 0, sA, sB);
+            if (t + 1 < last) step(t + 1, 0, sB, sA);
+        }
+        if (last >= 0) {
+            if (last & 1) sA = sB;       // ONE tail site: 32 register moves on odd parity
+            step.template operator()<true>(last, 1, sA, sB);
+        }
+        for (int t = my_tiles; t < n_tiles; ++t) {
+            int ts = t;   // (opaque: as an induction variable hipcc keeps this loop's per-lane staging offsets in registers across the unit loop)
+            asm volatile("" : "+s"(ts));
+            step(ts, 2, sA, sB);
+        }
+    } else {
+        for (int t = 0; t < n_tiles; t += 2) {
+            step(t, kind_of(t), sA, sB);
+            if (t + 1 < n_tiles) step(t + 1, kind_of(t + 1), sB, sA);
+        }
     }
     if constexpr (TRACK && !F16W) return false;
     else {

@@ -147,7 +147,7 @@ struct SlotEngine {
 
     // ---- the tile step ---------------------------------------------------------------------------
     // One tile: cur = S(t) (consumed), nxt = S(t+1) (produced; on the wave's last tile it is computed from a tile the wave does not
-    // need and ignored: one hot code path).  TRACK = true: running row max with lazy rescale (always safe).  TRACK = false: the
+    // need and ignored: one hot code path; under KernelCfg::TAIL the optimistic passes run that tile through tail_step instead).  TRACK = true: running row max with lazy rescale (always safe).  TRACK = false: the
     // optimistic pass -- m stays the row max of tile 0 and no max / decision / rescale is issued.
     template <bool TRACK, bool F16W = false, class St, class Sc>
     __device__ __forceinline__ void tile_step(St& st, int t_load, lds_ptr wr_slot, lds_ptr k_next, lds_ptr v_cur, int kbase, int vbase, float c,
@@ -188,6 +188,38 @@ struct SlotEngine {
                 }
             }
         }
+    }
+
+    // The wave's LAST tile in an optimistic pass (KernelCfg::TAIL; attention_pass: the kind-1 steps): phase B alone.  cur = S(t) is
+    // consumed -- its exponentials, the packs, the P.V MFMAs with their V^T reads VPRE ahead -- and nothing is produced: no next
+    // score buffer, no K fragment window, no K read, no QK^T, no mask, no decision.  The wave's pieces of tile t_load still go to
+    // ring slot wr_slot (the waves below it in the unit read them), all requested in front of the first MFMA, the fp16 form's LDS
+    // writes behind the last.  One-MFMA slots fenced like slots_b (the engine's slots_t).  Same weights, sums and products in the
+    // same order as tile_step: the result keeps its bits.
+    // half (wave-uniform): keys 0 .. 31 of the tile only -- for the wave whose rows start on a 64-row boundary the keys 32 .. 63 of its
+    // diagonal tile are masked in every row: their weights are exp2(-inf) = +0, which neither a row sum nor (V finite) an accumulator
+    // notices.  The two forms share the lead-in and the slots of k-step 0 and part behind them (tail_rest<HALF>).  (As two whole
+    // bodies hipcc hoists what they have in common -- 32 v_fma, the staging offsets -- in front of the branch and spills it.)
+    template <bool HALF, bool F16W, class Sc>
+    __device__ __forceinline__ void tail_rest(lds_ptr v_cur, int vbase, float c, const Sc& cur) {
+        constexpr int DB = W::DB, ST = (HALF ? 2 : 4) * DB;
+        self().template slots_t<DB, ST, ST, F16W>(v_cur, vbase, c, cur);
+    }
+    template <bool F16W = false, class St, class Sc>
+    __device__ __forceinline__ void tail_step(St& st, int t_load, lds_ptr wr_slot, lds_ptr v_cur, int vbase, float c, const Sc& cur, bool half) {
+        W& w = self();
+        constexpr int DB = W::DB;
+        w.begin_tail(st, wr_slot);
+        __builtin_amdgcn_sched_barrier(0);
+        w.template tail_pre<0, F16W>(st, t_load, v_cur, vbase, c, cur);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (C::STAMP) w.t_mid = cycle_stamp();
+        w.template slots_t<0, DB, 2 * DB, F16W>(v_cur, vbase, c, cur);   // (the V^T fragments of k-step 1 are read in either form)
+        if (half) tail_rest<true, F16W>(v_cur, vbase, c, cur);
+        else tail_rest<false, F16W>(v_cur, vbase, c, cur);
+        st.template write_all<F16W>(wr_slot);
+        if constexpr (C::STAMP) w.t_end = cycle_stamp();
+        w.end_sums();
     }
 
     // ---- epilogue -------------------------------------------------------------------------------
