@@ -90,23 +90,21 @@ CLANGXX   := /opt/rocm/lib/llvm/bin/clang++
 CLANG_ASAN_RT := $(shell /opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 GCC_ASAN_RT   := $(shell gcc -print-file-name=libasan.so)
 SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
-# asan-host: the library's host code under the sanitizers, and tests/host_ladder.cpp -- a stand-alone program (its own main, built
-# with the same flags, nothing preloaded) that walks the validation ladders and the plans of the ragged entry points -- built and run;
-# tests/host_sink_ladder.cpp likewise: the ladders of the six attention-sink entry points beside their _window twins.
-# tests/host_rope_ladder.cpp likewise: the ladders of the four flash_attention_rope_append* entry points beside their kv_append twins.
-asan-host: $(LIB)
+# asan-host: the library's host code under the sanitizers, and the LADDERS -- stand-alone programs (their own main, the same flags,
+# nothing preloaded; tests/host_ladder.h is what they share), each built and run: the validation ladders and plans of the ragged entry
+# points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins
+LADDERS := host_ladder host_sink_ladder host_rope_ladder
+$(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip
-	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/libflash_attention.so $(ASAN_DIR)/FlashAttention.o $(filter-out build/obj/FlashAttention.o,$(KOBJ))
-	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_ladder tests/host_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
+	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared $(SANFLAGS) -shared-libsan -o $@ $(ASAN_DIR)/FlashAttention.o $(filter-out build/obj/FlashAttention.o,$(KOBJ))
+
+ladder-%: tests/%.cpp tests/host_ladder.h $(ASAN_DIR)/libflash_attention.so
+	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/$* $< -L$(ASAN_DIR) -lflash_attention \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_ladder
-	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_sink_ladder tests/host_sink_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
-	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_sink_ladder
-	$(CLANGXX) -O1 -std=c++17 $(SANFLAGS) -shared-libsan -o $(ASAN_DIR)/host_rope_ladder tests/host_rope_ladder.cpp -L$(ASAN_DIR) -lflash_attention \
-	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(dir $(CLANG_ASAN_RT))
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/host_rope_ladder
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(ASAN_DIR)/$*
+
+asan-host: $(addprefix ladder-,$(LADDERS))
 
 asan: asan-host oracle
 	gcc -O1 -march=x86-64-v3 -fopenmp -fPIC -Wall -Wextra -std=c11 $(SANFLAGS) -shared -o $(ASAN_DIR)/liboracle_attention.so oracle/cpu_attention.c -lm

@@ -573,6 +573,23 @@ def _table_geometry(block_table, B):
     return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
 
 
+def _cache_geometry(K, block_table, B):
+    """(capacity, tables, geometry) of the cache a front got -- ``K`` with its ``block_table`` is a pool, without one the contiguous
+    cache: the rows a sequence can hold, the table pointers and the integers the entry point takes for the cache's shape"""
+    if block_table is None:
+        return K.shape[2], (), (K.shape[2],)
+    max_pages, table_stride = _table_geometry(block_table, B)
+    return max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
+
+
+def _check_kv_lens(kv_lens, B):
+    """the check every cache front makes of its optional ``kv_lens``"""
+    import torch
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
+                                or not kv_lens.is_contiguous()):
+        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+
+
 def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None,
                  sinks=None):
@@ -594,11 +611,7 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
     B = _cu_seqlens(cu_seqlens_q, Q) if ragged and not paged and Q.is_cuda else None
     fp8 = _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=block_table, batch=B)
     B = _cu_seqlens(cu_seqlens_q, Q) if ragged else Q.shape[0]
-    if paged:
-        max_pages, table_stride = _table_geometry(block_table, B)
-        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
-    else:
-        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
+    capacity, tables, geometry = _cache_geometry(K, block_table, B)
     if ragged and O is not None:
         O = _token_view(O, "O")
     window = _window(window)
@@ -609,9 +622,7 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
         raise ValueError("sinks must be a dense fp32 tensor [H] on the device of Q")
     new = torch.zeros if ragged else torch.empty      # ragged: rows no sequence owns are not written
     Hkv = K.shape[1]
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
-                                or not kv_lens.is_contiguous()):
-        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
+    _check_kv_lens(kv_lens, B)
     if scale is None:
         scale = 1.0 / float(d) ** 0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
@@ -791,45 +802,73 @@ def flash_attention_extend_paged_varlen_window(Q, K_pool, V_pool, block_table, c
     return _split_front("extend", Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, window=window, **kw)
 
 
-def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream):
-    """The four kv_cache_append* fronts (``name``: the front's, in the error texts): a ``block_table`` makes the call paged (K, V are
-    then the pools) and ``cu_seqlens_q`` ragged (the new rows are then packed by token: Sq is the bound on the packed rows, not capped
-    at the capacity, and the batch is cu_seqlens_q's).  The tensor checks of the decode fronts (``_decode_inputs``, the new rows in
-    the place of Q), the bounds of Sq, and the entry point of _APPEND_SYMBOLS."""
+def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream, rope=None):
+    """The kv_cache_append* and rope_cache_append* fronts (``name``: the front's, in the error texts): a ``block_table`` makes the call
+    paged (K, V are then the pools) and ``cu_seqlens_q`` ragged (the new rows are then packed by token: Sq is the bound on the packed
+    rows, not capped at the capacity, and the batch is cu_seqlens_q's).  The tensor checks of the decode fronts (``_decode_inputs``,
+    the new rows in the place of Q), the bounds of Sq, and the entry point of _APPEND_SYMBOLS.  ``rope`` = (Q, Q_out, cos_sin,
+    interleaved) makes it the fused call: Q, Q_out and the table are checked as well, the entry point is _ROPE_SYMBOLS' and the
+    rotated queries are returned (ragged: ``[T, H, d]``)."""
     import torch
     paged, ragged = block_table is not None, cu_seqlens_q is not None
+    Q, Q_out, cos_sin, interleaved = rope or (None,) * 4
     kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K_cache, V_cache", "[B, Hkv, capacity, d]")
     if ragged:
         K_new, V_new = _token_view(K_new, "K_new"), _token_view(V_new, "V_new")
+        if rope:
+            Q = _token_view(Q, "Q")
+            if Q_out is not None:
+                Q_out = _token_view(Q_out, "Q_out")
     elif paged:      # (the uniform paged front checks its table first; the ragged one where the batch is known)
         _table_geometry(block_table, K_new.shape[0] if K_new.dim() == 4 else 0)
     if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
         raise ValueError(f"K_new, V_new must be {'[T, Hkv, d]' if ragged else '[B, Hkv, Sq, d]'} of one dtype, with the K/V heads of {kv} {layout}")
-    if not V_new.is_cuda:
+    if not V_new.is_cuda or (rope and not Q.is_cuda):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
     B = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
     _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=block_table, batch=B)
     _, Hkv, Sq, d = K_new.shape
+    if rope and (Q.dim() != 4 or Q.dtype != K_new.dtype or Q.device != K_new.device
+                 or (Q.shape[0], Q.shape[2], Q.shape[3]) != (K_new.shape[0], Sq, d) or Q.shape[1] < 1 or Q.shape[1] % Hkv):
+        raise ValueError(f"Q must be {'[T, H, d]' if ragged else '[B, H, Sq, d]'} of the dtype and on the device of K_new, with Hkv dividing H")
     if not ragged:
         B = K_new.shape[0]
-    if paged:
-        max_pages, table_stride = _table_geometry(block_table, B)
-        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
-    else:
-        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
+    capacity, tables, geometry = _cache_geometry(K, block_table, B)
     if Sq < 1 or (Sq > capacity and not ragged):
         raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
-                                or not kv_lens.is_contiguous()):
-        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
-    with torch.cuda.device(K_new.device):
-        st = [_strides(t) for t in (K_new, V_new, K, V)]
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = getattr(lib(), _APPEND_SYMBOLS[paged, ragged])(
-            K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(), *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens),
-            *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype), _dtype_code(K.dtype),
+    _check_kv_lens(kv_lens, B)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if not rope:
+        with torch.cuda.device(K_new.device):
+            st = [_strides(t) for t in (K_new, V_new, K, V)]
+            rc = getattr(lib(), _APPEND_SYMBOLS[paged, ragged])(
+                K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr(), *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens),
+                *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Hkv, Sq, *geometry, d, _dtype_code(K_new.dtype), _dtype_code(K.dtype),
+                *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+        _check(rc)
+        return None
+    t = cos_sin
+    if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != Q.device or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError("cos_sin must be a dense fp32 tensor [max_pos, rot_dim] on the device of Q")
+    max_pos, rot_dim = t.shape
+    if rot_dim % 16 or not 16 <= rot_dim <= d or max_pos < capacity:
+        raise ValueError(f"cos_sin [max_pos, rot_dim]: rot_dim a multiple of 16 in 16 .. d, max_pos at least the capacity ({capacity})")
+    if Q_out is not None and (not getattr(Q_out, "is_cuda", False) or Q_out.shape != Q.shape or Q_out.dtype != Q.dtype or Q_out.device != Q.device):
+        raise ValueError("Q_out must be a device tensor shaped like Q, of its dtype, on its device")
+    with torch.cuda.device(Q.device):
+        if Q_out is None:
+            s = stream if stream is not None else torch.cuda.current_stream()
+            with torch.cuda.stream(s):
+                Q_out = torch.empty((Sq, Q.shape[1], d), dtype=Q.dtype, device=Q.device).unsqueeze(0).transpose(1, 2) if ragged \
+                    else torch.empty(Q.shape, dtype=Q.dtype, device=Q.device)
+        st = [_strides(x) for x in (Q, K_new, V_new, Q_out, K, V)]
+        rc = getattr(lib(), _ROPE_SYMBOLS[paged, ragged])(
+            Q.data_ptr(), K_new.data_ptr(), V_new.data_ptr(), Q_out.data_ptr(), K.data_ptr(), V.data_ptr(), t.data_ptr(),
+            *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Q.shape[1], Hkv,
+            Sq, *geometry, d, rot_dim, max_pos, int(bool(interleaved)), _dtype_code(K_new.dtype), _dtype_code(K.dtype),
             *[ctypes.byref(x) for x in st], _stream_ptr(stream))
     _check(rc)
+    return Q_out.transpose(1, 2).squeeze(0) if ragged else Q_out
 
 
 def kv_cache_append(K_new, V_new, K_cache, V_cache, kv_lens=None, k_descale=None, v_descale=None, stream=None):
@@ -895,66 +934,6 @@ def rope_table(max_pos, rot_dim, base=10000.0, device=None):
     return torch.cat([angle.cos(), angle.sin()], dim=1).to(torch.float32).to(device)
 
 
-def _rope_front(name, Q, K_new, V_new, K, V, cos_sin, block_table, cu_seqlens_q, kv_lens, interleaved, k_descale, v_descale, Q_out,
-                stream):
-    """The four rope_cache_append* fronts: ``_append_front``'s checks of the new rows and the caches, then Q, Q_out and the table,
-    and the entry point of _ROPE_SYMBOLS."""
-    import torch
-    paged, ragged = block_table is not None, cu_seqlens_q is not None
-    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K_cache, V_cache", "[B, Hkv, capacity, d]")
-    if ragged:
-        K_new, V_new, Q = _token_view(K_new, "K_new"), _token_view(V_new, "V_new"), _token_view(Q, "Q")
-        if Q_out is not None:
-            Q_out = _token_view(Q_out, "Q_out")
-    elif paged:
-        _table_geometry(block_table, K_new.shape[0] if K_new.dim() == 4 else 0)
-    if K_new.dim() != 4 or V_new.dim() != 4 or K_new.shape != V_new.shape or K_new.dtype != V_new.dtype or (K.dim() == 4 and K_new.shape[1] != K.shape[1]):
-        raise ValueError(f"K_new, V_new must be {'[T, Hkv, d]' if ragged else '[B, Hkv, Sq, d]'} of one dtype, with the K/V heads of {kv} {layout}")
-    if not V_new.is_cuda or not Q.is_cuda:
-        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
-    B = _cu_seqlens(cu_seqlens_q, K_new) if ragged and K_new.is_cuda else None
-    _decode_inputs(name, kv, layout, K_new, K, V, k_descale, v_descale, table=block_table, batch=B)
-    _, Hkv, Sq, d = K_new.shape
-    if Q.dim() != 4 or Q.dtype != K_new.dtype or Q.device != K_new.device or (Q.shape[0], Q.shape[2], Q.shape[3]) != (K_new.shape[0], Sq, d) \
-            or Q.shape[1] < 1 or Q.shape[1] % Hkv:
-        raise ValueError(f"Q must be {'[T, H, d]' if ragged else '[B, H, Sq, d]'} of the dtype and on the device of K_new, with Hkv dividing H")
-    if not ragged:
-        B = K_new.shape[0]
-    if paged:
-        max_pages, table_stride = _table_geometry(block_table, B)
-        capacity, tables, geometry = max_pages * K.shape[2], (block_table,), (K.shape[0], K.shape[2], max_pages, table_stride)
-    else:
-        capacity, tables, geometry = K.shape[2], (), (K.shape[2],)
-    if Sq < 1 or (Sq > capacity and not ragged):
-        raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.shape != (B,)
-                                or not kv_lens.is_contiguous()):
-        raise ValueError("kv_lens must be a dense int32 device tensor [B]")
-    t = cos_sin
-    if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != Q.device or t.dim() != 2 or not t.is_contiguous():
-        raise ValueError("cos_sin must be a dense fp32 tensor [max_pos, rot_dim] on the device of Q")
-    max_pos, rot_dim = t.shape
-    if rot_dim % 16 or not 16 <= rot_dim <= d or max_pos < capacity:
-        raise ValueError(f"cos_sin [max_pos, rot_dim]: rot_dim a multiple of 16 in 16 .. d, max_pos at least the capacity ({capacity})")
-    if Q_out is not None and (not getattr(Q_out, "is_cuda", False) or Q_out.shape != Q.shape or Q_out.dtype != Q.dtype or Q_out.device != Q.device):
-        raise ValueError("Q_out must be a device tensor shaped like Q, of its dtype, on its device")
-    with torch.cuda.device(Q.device):
-        if Q_out is None:
-            s = stream if stream is not None else torch.cuda.current_stream()
-            with torch.cuda.stream(s):
-                Q_out = torch.empty((Sq, Q.shape[1], d), dtype=Q.dtype, device=Q.device).unsqueeze(0).transpose(1, 2) if ragged \
-                    else torch.empty(Q.shape, dtype=Q.dtype, device=Q.device)
-        st = [_strides(x) for x in (Q, K_new, V_new, Q_out, K, V)]
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        rc = getattr(lib(), _ROPE_SYMBOLS[paged, ragged])(
-            Q.data_ptr(), K_new.data_ptr(), V_new.data_ptr(), Q_out.data_ptr(), K.data_ptr(), V.data_ptr(), t.data_ptr(),
-            *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Q.shape[1], Hkv,
-            Sq, *geometry, d, rot_dim, max_pos, int(bool(interleaved)), _dtype_code(K_new.dtype), _dtype_code(K.dtype),
-            *[ctypes.byref(x) for x in st], _stream_ptr(stream))
-    _check(rc)
-    return Q_out.transpose(1, 2).squeeze(0) if ragged else Q_out
-
-
 def rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens=None, interleaved=False, k_descale=None, v_descale=None,
                       Q_out=None, stream=None):
     """``kv_cache_append`` with the rotary embedding fused in: ONE launch rotates the new K rows at their cache positions and stores
@@ -971,16 +950,16 @@ def rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens=None, 
     ``y1 = fma(x1, c, -(x2 s))``, ``y2 = fma(x2, c, x1 s)`` in fp32, rounded once to bf16; K then goes through ``kv_cache_append``'s
     value rule, so the caches equal ``kv_cache_append`` of the bf16 rotation of K, byte for byte.  A decode step is ``kv_lens += Sq;
     Qr = rope_cache_append(...); flash_attention_decode(Qr, ...)``, one graph.  No CPU fallback."""
-    return _rope_front("rope_cache_append", Q, K_new, V_new, K_cache, V_cache, cos_sin, None, None, kv_lens, interleaved, k_descale,
-                       v_descale, Q_out, stream)
+    return _append_front("rope_cache_append", K_new, V_new, K_cache, V_cache, None, None, kv_lens, k_descale, v_descale, stream,
+                         rope=(Q, Q_out, cos_sin, interleaved))
 
 
 def rope_cache_append_paged(Q, K_new, V_new, K_pool, V_pool, block_table, cos_sin, kv_lens=None, interleaved=False, k_descale=None,
                             v_descale=None, Q_out=None, stream=None):
     """``rope_cache_append`` into the PAGED caches of ``kv_cache_append_paged`` (max_pos at least ``max_pages * page``).  A table
     entry outside [0, P) skips the K and V rows of its page; their Q rows are still written."""
-    return _rope_front("rope_cache_append_paged", Q, K_new, V_new, K_pool, V_pool, cos_sin, block_table, None, kv_lens, interleaved,
-                       k_descale, v_descale, Q_out, stream)
+    return _append_front("rope_cache_append_paged", K_new, V_new, K_pool, V_pool, block_table, None, kv_lens, k_descale, v_descale, stream,
+                         rope=(Q, Q_out, cos_sin, interleaved))
 
 
 def rope_cache_append_varlen(Q, K_new, V_new, K_cache, V_cache, cu_seqlens_q, cos_sin, kv_lens=None, interleaved=False, k_descale=None,
@@ -989,15 +968,15 @@ def rope_cache_append_varlen(Q, K_new, V_new, K_cache, V_cache, cu_seqlens_q, co
     as in ``kv_cache_append_varlen``; returns the rotated queries ``[T, H, d]``.  Every token a sequence owns is written; tokens
     nobody owns are neither read nor written (a ``Q_out`` allocated here holds unspecified values there).  A step of a mixed batch is
     ``kv_lens += q_lens; Qr = rope_cache_append_varlen(...); flash_attention_extend_varlen(Qr, ...)``."""
-    return _rope_front("rope_cache_append_varlen", Q, K_new, V_new, K_cache, V_cache, cos_sin, None, cu_seqlens_q, kv_lens, interleaved,
-                       k_descale, v_descale, Q_out, stream)
+    return _append_front("rope_cache_append_varlen", K_new, V_new, K_cache, V_cache, None, cu_seqlens_q, kv_lens, k_descale, v_descale, stream,
+                         rope=(Q, Q_out, cos_sin, interleaved))
 
 
 def rope_cache_append_paged_varlen(Q, K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, cos_sin, kv_lens=None, interleaved=False,
                                    k_descale=None, v_descale=None, Q_out=None, stream=None):
     """``rope_cache_append_varlen`` into PAGED caches: the pools and the table of ``kv_cache_append_paged``."""
-    return _rope_front("rope_cache_append_paged_varlen", Q, K_new, V_new, K_pool, V_pool, cos_sin, block_table, cu_seqlens_q, kv_lens,
-                       interleaved, k_descale, v_descale, Q_out, stream)
+    return _append_front("rope_cache_append_paged_varlen", K_new, V_new, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream,
+                         rope=(Q, Q_out, cos_sin, interleaved))
 
 
 def _library_accepts(t):

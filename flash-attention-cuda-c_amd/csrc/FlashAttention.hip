@@ -663,7 +663,6 @@ static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
     if (rope) {
-        static_assert(RopeAppendCfg::BLOCK == KvAppendCfg::BLOCK && RopeAppendCfg::THREADS == KvAppendCfg::THREADS);
         RopeAppendParams r;
         r.a = p;
         r.Q = (const __bf16*)rope->Q; r.Qout = (__bf16*)rope->Qout; r.cos_sin = rope->cos_sin;
@@ -679,9 +678,9 @@ static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
         const bool kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
         if (c.varlen) {
             const RopeAppendVarlenParams rv{r, c.cu_seqlens_q, B, rope_token_blocks};
-            return (int)launch(rope_append_varlen_kernel_of(d, kv8, pg != nullptr), rope_grid, RopeAppendCfg::THREADS, 0, st, rv);
+            return (int)launch(rope_append_varlen_kernel_of(d, kv8, pg != nullptr), rope_grid, KvAppendCfg::THREADS, 0, st, rv);
         }
-        return (int)launch(rope_append_kernel_of(d, kv8, pg != nullptr), rope_grid, RopeAppendCfg::THREADS, 0, st, r);
+        return (int)launch(rope_append_kernel_of(d, kv8, pg != nullptr), rope_grid, KvAppendCfg::THREADS, 0, st, r);
     }
     if (c.varlen) {
         const KvAppendVarlenParams pv{p, c.cu_seqlens_q, B, token_blocks};

@@ -5,23 +5,23 @@
 
 namespace fa {
 
-template <int D>
+// (the ragged, token-major form is VARLEN)
+template <int D, bool VARLEN>
 static Kernel kv_append_of(bool kv8, bool paged) {
-    if (kv8) return paged ? kernel_of<kv_append_kernel<D, true, true>>(0) : kernel_of<kv_append_kernel<D, true, false>>(0);
-    return paged ? kernel_of<kv_append_kernel<D, false, true>>(0) : kernel_of<kv_append_kernel<D, false, false>>(0);
+    return by_bool(kv8, [&]<bool KV8>() {
+        return by_bool(paged, [&]<bool PAGED>() {
+            if constexpr (VARLEN) return kernel_of<kv_append_varlen_kernel<D, KV8, PAGED>>(0);
+            else return kernel_of<kv_append_kernel<D, KV8, PAGED>>(0);
+        });
+    });
 }
 
-Kernel kv_append_kernel_of(int d, bool kv8, bool paged) { return d == 128 ? kv_append_of<128>(kv8, paged) : kv_append_of<64>(kv8, paged); }
-
-// the ragged (token-major) append
-template <int D>
-static Kernel kv_append_varlen_of(bool kv8, bool paged) {
-    if (kv8) return paged ? kernel_of<kv_append_varlen_kernel<D, true, true>>(0) : kernel_of<kv_append_varlen_kernel<D, true, false>>(0);
-    return paged ? kernel_of<kv_append_varlen_kernel<D, false, true>>(0) : kernel_of<kv_append_varlen_kernel<D, false, false>>(0);
+Kernel kv_append_kernel_of(int d, bool kv8, bool paged) {
+    return d == 128 ? kv_append_of<128, false>(kv8, paged) : kv_append_of<64, false>(kv8, paged);
 }
 
 Kernel kv_append_varlen_kernel_of(int d, bool kv8, bool paged) {
-    return d == 128 ? kv_append_varlen_of<128>(kv8, paged) : kv_append_varlen_of<64>(kv8, paged);
+    return d == 128 ? kv_append_of<128, true>(kv8, paged) : kv_append_of<64, true>(kv8, paged);
 }
 
 }  // namespace fa

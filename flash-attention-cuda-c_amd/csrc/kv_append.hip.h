@@ -62,6 +62,19 @@ __device__ __forceinline__ uint32_t kv_quantise4(uint32_t w0, uint32_t w1, float
     return (uint32_t)r | nan;
 }
 
+// 8 bf16 into a cache row: a bit copy, or kv_quantise4 twice and one 8-byte store
+template <bool KV8>
+__device__ __forceinline__ void kv_store8(char* out, u32x4 x, float ds) {
+    if constexpr (KV8) {
+        u32x2 y;
+        y[0] = kv_quantise4(x[0], x[1], ds);
+        y[1] = kv_quantise4(x[2], x[3], ds);
+        *reinterpret_cast<u32x2*>(out) = y;
+    } else {
+        *reinterpret_cast<u32x4*>(out) = x;
+    }
+}
+
 template <int D, bool KV8, bool PAGED>
 __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendParams p) {
     using C = KvAppendCfg;
@@ -124,15 +137,7 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendParams p) 
 #pragma unroll
     for (int j = 0; j < PASSES; ++j) {
         if (!ok[j]) continue;
-        char* out = dst + ((int64_t)(row0 + j * RPI + lr) * cS + col) * ES;
-        if constexpr (KV8) {
-            u32x2 y;
-            y[0] = kv_quantise4(x[j][0], x[j][1], ds);
-            y[1] = kv_quantise4(x[j][2], x[j][3], ds);
-            *reinterpret_cast<u32x2*>(out) = y;
-        } else {
-            *reinterpret_cast<u32x4*>(out) = x[j];
-        }
+        kv_store8<KV8>(dst + ((int64_t)(row0 + j * RPI + lr) * cS + col) * ES, x[j], ds);
     }
 }
 
@@ -141,8 +146,8 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendParams p) 
 // ragged attention clamps it).  TOKEN-major: a group of D / 8 lanes owns one token row of one K/V head of K or V; it finds its
 // sequence by a binary search in cu_q (the LAST b with cu_q[b] <= t: sequences without rows share their offset with the one behind
 // them and are passed over), then does what the uniform kernel does for one row -- L = min(kv_lens[b], cap), position
-// L - sq_b + (t - cu_q[b]), written if >= 0; its own table entry, skipped outside [0, num_pages); the same load, kv_quantise4 and
-// store, so the bytes are the uniform kernel's for that sequence alone.  A token no sequence owns writes nothing.  The waves are not
+// L - sq_b + (t - cu_q[b]), written if >= 0; its own table entry, skipped outside [0, num_pages); the same load and kv_store8,
+// so the bytes are the uniform kernel's for that sequence alone.  A token no sequence owns writes nothing.  The waves are not
 // aligned in position space (a wave's rows may lie in several sequences and pages: the length, the entry and the position are
 // per-lane values), which costs the uniform kernel's scalar loads but needs no unit lookup and no second launch.
 struct KvAppendVarlenParams {
@@ -205,14 +210,7 @@ __global__ __launch_bounds__(256) void kv_append_varlen_kernel(const KvAppendVar
         if (dp) ds = dp[kvh];
     }
     const u32x4 x = *reinterpret_cast<const u32x4*>(src + (int64_t)t * nS + (int64_t)kvh * nH + col);
-    if constexpr (KV8) {
-        u32x2 y;
-        y[0] = kv_quantise4(x[0], x[1], ds);
-        y[1] = kv_quantise4(x[2], x[3], ds);
-        *reinterpret_cast<u32x2*>(dst) = y;
-    } else {
-        *reinterpret_cast<u32x4*>(dst) = x;
-    }
+    kv_store8<KV8>(dst, x, ds);
 }
 
 // the instantiation for (d, fp8 cache, paged): inst_kv_append.hip

@@ -16,16 +16,16 @@
 //     ONCE per position -- reused over every head the lane loops on.  Qout == Q (in place) has one reader-writer per element: no LDS.
 //   * VALUES (pinned to the bit; rope_pair).  x1, x2 the pair as fp32, c, s from the table: y1 = fmaf(x1, c, -(x2 * s)),
 //     y2 = fmaf(x2, c, x1 * s), the lone product rounded to fp32 first; y rounded ONCE to bf16 (nearest even).  That bf16 is Qout's
-//     element; for K it goes through kv_append.hip.h's value rule (bit copy, or kv_quantise4), so the caches hold what
+//     element; for K it goes through kv_append.hip.h's store (kv_store8), so the caches hold what
 //     kv_append_kernel stores for the bf16 rotation of K, byte for byte.  V and the columns >= rot never pass through arithmetic.
 //   * HEADS.  The units of one K/V head are its K row, its V row and the rows of its G = H / Hkv query heads.  A workgroup takes a
 //     SLICE of heads_per_slice consecutive K/V heads and loops over their units; the host makes as many slices as fill the device and
 //     no more (FlashAttention.hip: kv_append_run), so a position's table row is read once per slice, not once per head.  Units
 //     are taken UB at a time: all their loads are issued, then they are rotated and stored.
-//   * UNIFORM kernel: kv_append_kernel's decomposition in the space of v.  A workgroup is (sequence, block of 64 virtual positions,
-//     head slice); block rb covers [64 (floor(first / 64) + rb), + 64) cut to [first, Lq), first = Lq - Sq; each wave owns 16
-//     positions aligned to 16 (one page; all negative or none); the length, the descales and the page entry are wave-uniform, and
-//     a wave reads its page entry only if it writes K / V rows.  An entry outside [0, num_pages) skips the K / V rows, not the Q rows.
+//   * UNIFORM kernel: kv_append_kernel's decomposition (KvAppendCfg: blocks of 64, waves of 16 aligned positions, one page each) in
+//     the space of v, first = Lq - Sq: a wave's positions are all negative or none.  The length, the descales and the page entry are
+//     wave-uniform; a wave reads its page entry only if it writes K / V rows.  An entry outside [0, num_pages) skips the K / V rows,
+//     not the Q rows.
 //   * RAGGED kernel: kv_append_varlen_kernel's: token-major, D / 16 lanes per token, a binary search in cu_q, per-lane position and
 //     page entry; a token no sequence owns is neither read nor written.
 //   * Every address is 64-bit arithmetic on element strides.  No LDS, no scratch, no atomics; every store is a vector store of 16
@@ -83,19 +83,6 @@ __device__ __forceinline__ void rope_rotate(u32x4& a, u32x4& b, const float (&c)
             a[w] = pack_bf16(y1l, y1h);
             b[w] = pack_bf16(y2l, y2h);
         }
-    }
-}
-
-// 8 bf16 into a cache row: a bit copy, or the twin's quantisation
-template <bool KV8>
-__device__ __forceinline__ void rope_store_cache(char* out, u32x4 x, float ds) {
-    if constexpr (KV8) {
-        u32x2 y;
-        y[0] = kv_quantise4(x[0], x[1], ds);
-        y[1] = kv_quantise4(x[2], x[3], ds);
-        *reinterpret_cast<u32x2*>(out) = y;
-    } else {
-        *reinterpret_cast<u32x4*>(out) = x;
     }
 }
 
@@ -168,8 +155,8 @@ __device__ __forceinline__ void rope_heads(const RopeAppendParams& r, int slice,
                         char* dst = (char*)(u == 0 ? p.K : p.V);
                         const int64_t cH = u == 0 ? p.kH : p.vH, cS = u == 0 ? p.kS : p.vS;
                         dst += ((u == 0 ? k_row : v_row) + (int64_t)kvh * cH + j * (RSTEP * cS)) * ES;
-                        rope_store_cache<KV8>(dst + col_a * ES, xa[t][j], u == 0 ? kds : vds);
-                        rope_store_cache<KV8>(dst + col_b * ES, xb[t][j], u == 0 ? kds : vds);
+                        kv_store8<KV8>(dst + col_a * ES, xa[t][j], u == 0 ? kds : vds);
+                        kv_store8<KV8>(dst + col_b * ES, xb[t][j], u == 0 ? kds : vds);
                     } else {
                         __bf16* dst = r.Qout + ((int64_t)kvh * r.G + (u - 2)) * r.oH + o_row + j * (RSTEP * r.oS);
                         *reinterpret_cast<u32x4*>(dst + col_a) = xa[t][j];
@@ -181,15 +168,9 @@ __device__ __forceinline__ void rope_heads(const RopeAppendParams& r, int slice,
     }
 }
 
-struct RopeAppendCfg {
-    static constexpr int THREADS = 256, WAVES = 4;
-    static constexpr int WROWS = 16;               // virtual positions per wave
-    static constexpr int BLOCK = WAVES * WROWS;    // ... per workgroup
-};
-
 template <int D, bool KV8, bool PAGED>
 __global__ __launch_bounds__(256) void rope_append_kernel(const RopeAppendParams r) {
-    using C = RopeAppendCfg;
+    using C = KvAppendCfg;             // WROWS, BLOCK: of VIRTUAL positions here
     const KvAppendParams& p = r.a;
     constexpr int LPR = D / 16;          // lanes per row
     constexpr int RPI = 64 / LPR;        // rows per wave instruction

@@ -8,8 +8,9 @@
 * `plan_call`, `tiles`, `MetaTensor`: the plan functions by name, the key tiles of a length, a tensor's metadata for the binding's checks.
 
 Users: the CPU tests of the K/V-cache calls (test_decode_abi, test_decode_paged_abi, test_decode_fp8_abi, test_decode_window_abi,
-test_extend_abi, test_extend_window_abi, test_extend_varlen_abi, test_kv_append_abi, test_sink_abi), the device-pointer calls of the GPU
-tests (memory_contract.py and with it test_memory_contract / test_sink_memory_contract, test_extend_varlen.py), and -- for the
+test_extend_abi, test_extend_window_abi, test_extend_varlen_abi, test_kv_append_abi, test_rope_append_abi, test_sink_abi), the
+device-pointer calls of the GPU tests (memory_contract.py and with it test_memory_contract / test_sink_memory_contract,
+test_extend_varlen.py, rope_call.py and with it test_rope_append* / test_rope_memory_contract), and -- for the
 constants and the host pointer -- test_gqa_abi and test_backward_abi."""
 import ctypes
 import functools
@@ -56,8 +57,10 @@ KEYS = {
     "d": ("dHead",), "scale": ("scale",), "causal": ("is_causal",), "dtype": ("dtype",), "kv": ("kv_dtype",), "o": ("o_dtype",),
     "ns": ("numSplits",), "W": ("windowSize",), "sQ": ("sQ",), "sK": ("sK",), "sV": ("sV",), "sO": ("sO",), "sKn": ("sKnew",),
     "sVn": ("sVnew",), "stream": ("stream",), "plan": ("plan",),
+    # flash_attention_rope_append*
+    "Qo": ("Qout",), "cs": ("cosSin",), "rot": ("rotDim",), "maxpos": ("maxPos",), "il": ("interleaved",), "sQo": ("sQout",),
 }
-STRIDES = ("sQ", "sK", "sV", "sO", "sKnew", "sVnew")
+STRIDES = ("sQ", "sK", "sV", "sO", "sKnew", "sVnew", "sQout")
 
 
 def c_call(symbol, values):
@@ -94,15 +97,17 @@ def aligned_host_pointer():
 
 
 def host_call(symbol, ok, host=None):
-    """-> (call, p): call(**overrides) is `symbol` on the aligned host pointer p -- every tensor, cuSeqlensQ and the block table at p;
-    no LSE, lengths, descales, workspace, strides or stream -- and the ints of `ok`, each overridden by name.  `symbol=` in the
-    overrides calls a sibling on the same arguments.  Calls that share memory pass one `host` = aligned_host_pointer()"""
+    """-> (call, p): call(**overrides) is `symbol` on the aligned host pointer p -- every tensor, cuSeqlensQ, the block table and the
+    cos / sin table at p; no LSE, lengths, descales, workspace, stream or strides (as many NULLs as the symbol declares fa_strides*)
+    -- and the ints of `ok`, each overridden by name.  `symbol=` in the overrides calls a sibling on the same arguments.  Calls that
+    share memory pass one `host` = aligned_host_pointer()"""
     buf, p = host or aligned_host_pointer()
-    base = dict(dict(Q=p, K=p, V=p, O=p, Kn=p, Vn=p, cu=p, table=p, LSE=None, lens=None, kd=None, vd=None, ws=None, strides=[None] * 4,
-                     stream=None), **ok)
+    base = dict(dict(Q=p, K=p, V=p, O=p, Kn=p, Vn=p, Qo=p, cs=p, cu=p, table=p, LSE=None, lens=None, kd=None, vd=None, ws=None, stream=None),
+                **ok)
 
     def call(symbol=symbol, _keep=buf, **overrides):
-        return c_call(symbol, dict(base, **overrides))
+        no_strides = [None] * sum(n in STRIDES for n in _declared(symbol))
+        return c_call(symbol, dict(base, strides=no_strides) | overrides)
 
     return call, p
 

@@ -5,23 +5,9 @@
 // -fsanitize=address,undefined against the library whose host code is built the same way, and runs it.
 // usage: host_ladder          exit status 0 = every call returned what is written here
 #include <climits>
-#include <cstdint>
-#include <cstdio>
 #include <initializer_list>
 
-#include "../include/flash_attention.h"
-
-static int failures = 0;
-#define EXPECT(call, want)                                                                   \
-    do {                                                                                     \
-        const long long got_ = (long long)(call), want_ = (long long)(want);                 \
-        if (got_ != want_) {                                                                 \
-            std::printf("line %d: %s = %lld, expected %lld\n", __LINE__, #call, got_, want_); \
-            ++failures;                                                                      \
-        }                                                                                    \
-    } while (0)
-
-alignas(16) static char buffer[256];
+#include "host_ladder.h"
 
 struct Extend {   // valid but for the workspace of its two splits: stops at FA_ERR_NULL_POINTER
     const void *Q = buffer, *K = buffer, *V = buffer;
@@ -63,17 +49,13 @@ struct Append {   // every call made with it is stopped by the argument under te
     }
 };
 
-template <class C, class F>
-static void both(F change, int want, int line) {
-    C c;
-    change(c);
-    const int a = c.contiguous(), b = c.paged();
-    if (a != want || b != want) {
-        std::printf("line %d: contiguous %d, paged %d, expected %d\n", line, a, b, want);
-        ++failures;
-    }
+static const char* const FORM[2] = {"contiguous", "paged"};
+
+template <class C>
+static std::array<Got, 1> one(const C& c, int form) {
+    return {{{"returned", form ? c.paged() : c.contiguous()}}};
 }
-#define BOTH(C, change, want) both<C>([](C& c) { change; }, want, __LINE__)
+#define BOTH(C, change, want) rung<C>(FORM, [](C& c) { change; }, one<C>, want, 3, __LINE__)
 
 int main() {
     // ---- the attention ladder, in the order of the checks ----
@@ -179,6 +161,5 @@ int main() {
         c = Append(); c.Sk = 0;
         EXPECT(c.contiguous(), FA_ERR_BAD_SHAPE);
     }
-    std::printf(failures ? "host_ladder: %d FAILED\n" : "host_ladder: all refusals and plans as declared\n", failures);
-    return failures ? 1 : 0;
+    return report("host_ladder", "all refusals and plans as declared");
 }

@@ -5,13 +5,7 @@
 // at least one way (a call that is valid as a whole would launch), so nothing is launched and no GPU is needed.  `make asan-host` builds
 // it with -fsanitize=address,undefined against the library whose host code is built the same way, and runs it next to host_ladder.
 // usage: host_rope_ladder          exit status 0 = every call returned what is written here
-#include <cstdint>
-#include <cstdio>
-
-#include "../include/flash_attention.h"
-
-static int failures = 0;
-alignas(16) static char buffer[256];
+#include "host_ladder.h"
 
 struct Call {   // valid as a whole: every use below breaks it
     const void *Q = buffer, *Kn = buffer, *Vn = buffer;
@@ -53,36 +47,16 @@ static const char* const FORM[4] = {"rope_append", "rope_append_paged", "rope_ap
 enum { ALL = 0xF, PAGED = 0xA, CONTIGUOUS = 0x5, RAGGED = 0xC, UNIFORM = 0x3 };
 
 // one rung of the twin's ladder on the forms of `mask`: the twin and the rope call both return `want`
-template <class F>
-static void rung(F change, int want, int mask, int line) {
-    for (int form = 0; form < 4; ++form) {
-        if (!(mask >> form & 1)) continue;
-        Call c;
-        change(c);
-        const int t = c.twin(form), r = c.rope(form);
-        if (t != want || r != want) {
-            std::printf("line %d, %s: twin %d, rope %d, expected %d\n", line, FORM[form], t, r, want);
-            ++failures;
-        }
-    }
+static std::array<Got, 2> twin_and_rope(const Call& c, int form) {
+    return {{{"twin", c.twin(form)}, {"rope", c.rope(form)}}};
 }
-#define RUNG(change, want, mask) rung([](Call& c) { change; }, want, mask, __LINE__)
+#define RUNG(change, want, mask) rung<Call>(FORM, [](Call& c) { change; }, twin_and_rope, want, mask, __LINE__)
 
 // a rung of the rope calls alone
-template <class F>
-static void own(F change, int want, int mask, int line) {
-    for (int form = 0; form < 4; ++form) {
-        if (!(mask >> form & 1)) continue;
-        Call c;
-        change(c);
-        const int r = c.rope(form);
-        if (r != want) {
-            std::printf("line %d, %s: %d, expected %d\n", line, FORM[form], r, want);
-            ++failures;
-        }
-    }
+static std::array<Got, 1> rope_alone(const Call& c, int form) {
+    return {{{"rope", c.rope(form)}}};
 }
-#define OWN(change, want, mask) own([](Call& c) { change; }, want, mask, __LINE__)
+#define OWN(change, want, mask) rung<Call>(FORM, [](Call& c) { change; }, rope_alone, want, mask, __LINE__)
 
 int main() {
     static const fa_strides low{64, 16, 8}, odd_batch{-7, 64, 512}, odd_row{1 << 20, 1 << 16, 68}, fine{1 << 20, 1 << 12, 80};
@@ -155,6 +129,5 @@ int main() {
     OWN(c.sQo = &odd_batch; c.il = 3, FA_ERR_BAD_FLAGS, RAGGED);                    // ragged: strideB is not read
     OWN(c.sQ = &fine; c.sQo = &fine; c.il = 3, FA_ERR_BAD_FLAGS, ALL);              // good strides pass on
     OWN(c.sQ = &low; c.Sk = (1 << 24) - 192; c.maxpos = 1 << 24, FA_ERR_BAD_STRIDE, CONTIGUOUS);   // the strides before the extent
-    std::printf(failures ? "host_rope_ladder: %d FAILED\n" : "host_rope_ladder: all refusals as declared\n", failures);
-    return failures ? 1 : 0;
+    return report("host_rope_ladder", "all refusals as declared");
 }

@@ -6,13 +6,7 @@
 // nothing is launched and no GPU is needed.  `make asan-host` builds it with -fsanitize=address,undefined against the library whose
 // host code is built the same way, and runs it next to host_ladder.
 // usage: host_sink_ladder          exit status 0 = every call returned what is written here
-#include <cstdint>
-#include <cstdio>
-
-#include "../include/flash_attention.h"
-
-static int failures = 0;
-alignas(16) static char buffer[256];
+#include "host_ladder.h"
 
 struct Call {   // valid but for the workspace of its two splits: stops at FA_ERR_NULL_POINTER, the last rung
     const void *Q = buffer, *K = buffer, *V = buffer;
@@ -66,36 +60,16 @@ static const char* const FORM[6] = {"decode", "decode_paged", "extend", "extend_
 enum { ALL = 0x3F, PAGED = 0x2A, CONTIGUOUS = 0x15, RAGGED = 0x30, DECODE = 0x03 };
 
 // one rung on the forms of `mask`: the twin, the sink call without sinks and the sink call with sinks all return `want`
-template <class F>
-static void rung(F change, int want, int mask, int line) {
-    for (int form = 0; form < 6; ++form) {
-        if (!(mask >> form & 1)) continue;
-        Call c;
-        change(c);
-        const int t = c.twin(form), n = c.sink(form, nullptr), s = c.sink(form, (const float*)(buffer + 32));
-        if (t != want || n != want || s != want) {
-            std::printf("line %d, %s: twin %d, sinks = NULL %d, with sinks %d, expected %d\n", line, FORM[form], t, n, s, want);
-            ++failures;
-        }
-    }
+static std::array<Got, 3> three(const Call& c, int form) {
+    return {{{"twin", c.twin(form)}, {"sinks = NULL", c.sink(form, nullptr)}, {"with sinks", c.sink(form, (const float*)(buffer + 32))}}};
 }
-#define RUNG(change, want, mask) rung([](Call& c) { change; }, want, mask, __LINE__)
+#define RUNG(change, want, mask) rung<Call>(FORM, [](Call& c) { change; }, three, want, mask, __LINE__)
 
 // a sinks pointer at 2 mod 4 beside another fault: the code of whichever is checked first
-template <class F>
-static void misaligned(F change, int want, int mask, int line) {
-    for (int form = 0; form < 6; ++form) {
-        if (!(mask >> form & 1)) continue;
-        Call c;
-        change(c);
-        const int s = c.sink(form, (const float*)(buffer + 34));
-        if (s != want) {
-            std::printf("line %d, %s: misaligned sinks %d, expected %d\n", line, FORM[form], s, want);
-            ++failures;
-        }
-    }
+static std::array<Got, 1> misaligned_sinks(const Call& c, int form) {
+    return {{{"misaligned sinks", c.sink(form, (const float*)(buffer + 34))}}};
 }
-#define MISALIGNED(change, want, mask) misaligned([](Call& c) { change; }, want, mask, __LINE__)
+#define MISALIGNED(change, want, mask) rung<Call>(FORM, [](Call& c) { change; }, misaligned_sinks, want, mask, __LINE__)
 
 int main() {
     static const fa_strides low{64, 16, 8}, odd_batch{-7, 64, 512};
@@ -166,6 +140,5 @@ int main() {
                 }
             }
     }
-    std::printf(failures ? "host_sink_ladder: %d FAILED\n" : "host_sink_ladder: all refusals as declared\n", failures);
-    return failures ? 1 : 0;
+    return report("host_sink_ladder", "all refusals as declared");
 }

@@ -1,65 +1,20 @@
-"""What the tests of flash_attention_rope_append* share besides the reference (tests/rope_check.py; no tests in here): the calls BY
-NAME from include/flash_attention.h, as tests/abi_decl.py makes them, with the short keys of the arguments these entry points add.
+"""What the tests of flash_attention_rope_append* share besides the reference (tests/rope_check.py; no tests in here): device-tensor
+launchers over the calls BY NAME of tests/abi_decl.py (c_call; the host-pointer calls of the ladders are abi_decl.host_calls).
 
-* `c_call(symbol, values)`: abi_decl.c_call over `KEYS` = abi_decl's and Qo / cs / rot / maxpos / il / sQo.
-* `host_calls(...)`: abi_decl.host_calls for these entry points -- every tensor and the table on one aligned HOST pointer, six strides.
 * `launch(...)`: a call on device tensors -- the form (contiguous / paged, uniform / ragged) from which arguments are given, the
   strides from the tensors, the cache type from the caches' integer dtype (int16: bf16 patterns, uint8: e4m3fn bytes).
-* `twin(...)`: flash_attention_kv_append* of the same form on the same caches, by name through abi_decl.c_call.
+* `twin(...)`: flash_attention_kv_append* of the same form on the same live device tensors.  (memory_contract.append_call is not this:
+  it describes a call on CPU data for the placement harness, which allocates, guards and compares; this one launches.)
 """
 import ctypes
 
 import torch
 
-import abi_decl
-from abi_decl import BF16, FP8, fa
+from abi_decl import BF16, FP8, c_call, fa
 
-KEYS = dict(abi_decl.KEYS, Qo=("Qout",), cs=("cosSin",), rot=("rotDim",), maxpos=("maxPos",), il=("interleaved",), sQo=("sQout",))
-STRIDES = ("sQ", "sKnew", "sVnew", "sQout", "sK", "sV")          # in declared order
 ROPE = {(False, False): "flash_attention_rope_append", (True, False): "flash_attention_rope_append_paged",
         (False, True): "flash_attention_rope_append_varlen", (True, True): "flash_attention_rope_append_paged_varlen"}
 TWIN = {k: v.replace("rope_append", "kv_append") for k, v in ROPE.items()}
-
-
-def c_call(symbol, values):
-    """abi_decl.c_call with the keys above: every declared parameter is looked up under its short key, none may be missing or given
-    twice; `strides` = the six fa_strides* together, in declared order"""
-    values = dict(values)
-    together = values.pop("strides", None)
-    unknown = set(values) - set(KEYS)
-    assert not unknown, (symbol, sorted(unknown))
-    params = abi_decl.declared_parameters(symbol)
-    found = {}
-    if together is not None:
-        names = [n for n in params if n in STRIDES]
-        assert len(names) == len(together), (symbol, names)
-        found = {n: [s] for n, s in zip(names, together)}
-    for key, value in values.items():
-        for n in KEYS[key]:
-            if n in params:
-                found.setdefault(n, []).append(value)
-    args = []
-    for n in params:
-        if len(found.get(n, ())) != 1:
-            raise KeyError(f"{symbol}: {len(found.get(n, ()))} values for the declared parameter {n}")
-        args.append(found[n][0])
-    return getattr(fa.lib(), symbol)(*args)
-
-
-def host_calls(*symbols_and_oks):
-    """(symbol, ok), ... -> (call, ..., p): call(**overrides) is `symbol` with every tensor, cuSeqlensQ, the block table and the
-    cos / sin table at the aligned host pointer p, no lengths, descales, strides or stream, and the ints of `ok`"""
-    buf, p = abi_decl.aligned_host_pointer()
-
-    def make(symbol, ok):
-        base = dict(dict(Q=p, Kn=p, Vn=p, Qo=p, K=p, V=p, cs=p, cu=p, table=p, lens=None, kd=None, vd=None, strides=[None] * 6, stream=None), **ok)
-
-        def call(_keep=buf, **overrides):
-            return c_call(symbol, dict(base, **overrides))
-
-        return call
-
-    return (*(make(s, ok) for s, ok in symbols_and_oks), p)
 
 
 def strides3(t, ragged=False):
@@ -112,5 +67,5 @@ def twin(Kn, Vn, K, V, lens=None, kd=None, vd=None, block_table=None, cu=None):
                   stream=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), **_geometry(K, block_table))
     if ragged:
         values["cu"] = cu.data_ptr()
-    rc = abi_decl.c_call(TWIN[block_table is not None, ragged], values)
+    rc = c_call(TWIN[block_table is not None, ragged], values)
     assert rc == 0, (rc, fa.error_string(rc))

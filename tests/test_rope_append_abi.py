@@ -13,7 +13,7 @@ fa = entry.load_package()
 
 import rope_call as call  # noqa: E402
 from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SHAPE, BAD_STRIDE, BF16, F16, F32, FA_ERR, FP8, MISALIGNED, NULL_POINTER,  # noqa: E402
-                      MetaTensor as T, declared_parameters)
+                      MetaTensor as T, declared_parameters, host_calls)
 
 BAD_FLAGS = FA_ERR["BAD_FLAGS"]
 FORMS = [(False, False), (True, False), (False, True), (True, True)]
@@ -45,7 +45,7 @@ def calls(kv):
     overrides something"""
     okc = dict(B=2, H=8, Hkv=2, Sq=3, Sk=1024, d=128, rot=64, maxpos=1024, il=0, dtype=BF16, kv=kv)
     okp = dict(B=2, H=8, Hkv=2, Sq=3, P=64, page=64, maxp=16, ts=16, d=128, rot=64, maxpos=1024, il=0, dtype=BF16, kv=kv)
-    return call.host_calls(*((call.ROPE[paged, ragged], okp if paged else okc) for paged, ragged in FORMS))
+    return host_calls(*((call.ROPE[paged, ragged], okp if paged else okc) for paged, ragged in FORMS))
 
 
 @pytest.mark.parametrize("kv", [BF16, FP8])

@@ -42,7 +42,7 @@ def rope_call_of(cache, Q, Knew, Vnew, table, lens, il, cu=None):
         values = dict(cache.values(v), Q=v["Q"].data_ptr(), Kn=v["Knew"].data_ptr(), Vn=v["Vnew"].data_ptr(), Qo=v["Qout"].data_ptr(),
                       cs=v["cs"].data_ptr(), H=Q.shape[1], Sq=rows, rot=table.shape[1], maxpos=table.shape[0], il=int(il),
                       dtype=fa.FA_DTYPE_BF16, sQ=sQ, sKn=sKn, sVn=sVn, sQo=sQo, stream=mc.stream())
-        rc_ = rope_call.c_call(name, values)
+        rc_ = mc.c_call(name, values)
         assert rc_ == 0, (name, fa.error_string(rc_))
 
     return mc.Call(specs, data, go, ["Qout", "K", "V"], 0, f"{name} d {cache.d} rows {rows} interleaved {il}")
