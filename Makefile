@@ -29,7 +29,8 @@ tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS
 # bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
 # in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
 # (the wildcard takes the ragged instantiations, inst_extend_varlen_*.hip, with them: the same kernel with a per-sequence row count;
-# and the attention-sink ones, inst_extend_sink_*.hip: the same kernel with one more term in its epilogue.  inst_decode_sink_*.hip: RT = 1, no flag)
+# and the attention-sink ones, inst_extend_sink_*.hip: the same kernel with one more term in its epilogue.  inst_decode_sink_*.hip: RT = 1, no flag;
+# inst_extend_tree_*.hip / inst_decode_tree_*.hip, the tree-masked forms, likewise)
 EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
 $(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)
 
@@ -92,8 +93,9 @@ GCC_ASAN_RT   := $(shell gcc -print-file-name=libasan.so)
 SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # asan-host: the library's host code under the sanitizers, and the LADDERS -- stand-alone programs (their own main, the same flags,
 # nothing preloaded; tests/host_ladder.h is what they share), each built and run: the validation ladders and plans of the ragged entry
-# points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins
-LADDERS := host_ladder host_sink_ladder host_rope_ladder
+# points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins,
+# of the two tree-masked ones beside their sink twins
+LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder
 $(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip

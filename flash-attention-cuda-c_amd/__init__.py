@@ -31,6 +31,9 @@ entry points for that path:
 * ``rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens)`` and its ``_paged`` / ``_varlen`` / ``_paged_varlen``
   forms -- the append with the rotary embedding fused in: K rotated at its cache positions into the cache, V appended, the step's Q
   rotated at the same positions, one launch (``rope_table`` makes the cos / sin table).
+* ``flash_attention_tree(Q, K, V, tree_mask, kv_lens)`` / ``flash_attention_tree_paged(Q, K_pool, V_pool, block_table, tree_mask,
+  kv_lens)`` -- tree-masked verification of a speculative draft: up to 64 draft nodes per sequence, already appended, each row seeing
+  the cached prefix and the nodes its 64-bit mask word names (``tree_mask_from_parents``, ``tree_depths``, ``tree_plan``).
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -57,6 +60,7 @@ FA_DECODE_MAX_Q = 16        # flash_attention_decode: most new query rows per se
 FA_DECODE_MAX_SPLITS = 64   # ... and the cap of num_splits
 FA_DECODE_MAX_WORKGROUPS = 1 << 24   # the K/V-cache calls: plan grid, and rows of O under num_splits > 1, stay below it (FA_ERR_BAD_SHAPE)
 FA_VARLEN_MAX_BATCH = 1024  # flash_attention_extend_varlen, kv_cache_append_varlen: most sequences per call
+FA_TREE_MAX_Q = 64          # flash_attention_tree: most draft nodes per sequence (one uint64 mask word per node)
 
 # every symbol include/flash_attention.h declares
 EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", "flash_attention_cross", "flash_attention_ex", "flash_attention_weights", "flash_attention_shard_range", "flash_attention_sharded",
@@ -76,6 +80,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_sink_extend_paged", "flash_attention_sink_extend_varlen", "flash_attention_sink_extend_paged_varlen",
            "flash_attention_rope_append", "flash_attention_rope_append_paged", "flash_attention_rope_append_varlen",
            "flash_attention_rope_append_paged_varlen",
+           "flash_attention_tree", "flash_attention_tree_paged", "flash_attention_tree_plan",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -95,6 +100,9 @@ _SINK_SYMBOLS = {
     ("extend", False, False): "flash_attention_sink_extend", ("extend", True, False): "flash_attention_sink_extend_paged",
     ("extend", False, True): "flash_attention_sink_extend_varlen", ("extend", True, True): "flash_attention_sink_extend_paged_varlen",
 }
+# ... the tree-masked verification calls: _TREE_SYMBOLS[paged], the sinks entry point of decode without is_causal and with ``treeMask``
+# after ``sinks``
+_TREE_SYMBOLS = {False: "flash_attention_tree", True: "flash_attention_tree_paged"}
 # ... _APPEND_SYMBOLS[paged, ragged], and the plan of a family: _PLAN_SYMBOLS[family, ragged][window > 0]
 _APPEND_SYMBOLS = {(False, False): "flash_attention_kv_append", (True, False): "flash_attention_kv_append_paged",
                    (False, True): "flash_attention_kv_append_varlen", (True, True): "flash_attention_kv_append_paged_varlen"}
@@ -190,6 +198,12 @@ def lib() -> ctypes.CDLL:
                         fn.argtypes = [vp] * 5 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] * both + [vp] * sink + [vp] + [i] * 4 \
                             + paging(paged) + [i, f, b, i] + [i] * both + [i, i] + [i] * window + [sp] * 4 + [vp]
                         fn.restype = i
+        for paged, name in _TREE_SYMBOLS.items():      # sinks and treeMask after the descales; no is_causal; windowSize always
+            fn = getattr(L, name)
+            fn.argtypes = [vp] * 6 + [vp] * paged + [vp] * 5 + [i] * 4 + paging(paged) + [i, f] + [i] * 5 + [sp] * 4 + [vp]
+            fn.restype = i
+        L.flash_attention_tree_plan.argtypes = [i] * 9 + [ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_tree_plan.restype = i
         for (paged, ragged), name in _APPEND_SYMBOLS.items():
             fn = getattr(L, name)
             fn.argtypes = [vp] * 4 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, i] + [sp] * 4 + [vp]
@@ -484,6 +498,9 @@ def _split_plan(family, ragged, B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, windo
     """the filled fa_decode_plan of a call, from the family's plan entry point or (a window) its ``_window`` twin"""
     p = FaDecodePlan()
     window = _window(window)
+    if family == "tree":      # one plan entry point, the window always among its arguments
+        _check(lib().flash_attention_tree_plan(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window, ctypes.byref(p)))
+        return p
     plain, windowed = _PLAN_SYMBOLS[family, ragged]
     if window:
         _check(getattr(lib(), windowed)(B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window, ctypes.byref(p)))
@@ -515,6 +532,12 @@ def extend_varlen_plan(B, H, Hkv, total_q, Sk, d, o_dtype=FA_DTYPE_BF16, num_spl
     ``(G * total_q + B * (rows_per_block - 1)) // rows_per_block``; the workspace is ``decode_workspace_size(1, H, total_q, d, ns)``.
     ``window`` > 0: the call's sliding window (the tiles bound uses ``total_q`` for the row count)."""
     return _plan_dict(_split_plan("extend", True, B, H, Hkv, total_q, Sk, d, o_dtype, num_splits, window))
+
+
+def tree_plan(B, H, Hkv, Sq, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=0, window=0):
+    """What a flash_attention_tree call launches (fa_decode_plan as a dict): ``decode_plan`` for Sq <= FA_DECODE_MAX_Q draft nodes,
+    ``extend_plan`` for 17 .. FA_TREE_MAX_Q, under the same ``window``; ``decode_workspace_size`` serves unchanged."""
+    return _plan_dict(_split_plan("tree", False, B, H, Hkv, Sq, Sk, d, o_dtype, num_splits, window))
 
 
 def decode_workspace_size(B, H, Sq, d, num_splits):
@@ -592,18 +615,22 @@ def _check_kv_lens(kv_lens, B):
 
 def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
                  num_splits=0, return_lse=False, O=None, workspace=None, stream=None, k_descale=None, v_descale=None, window=None,
-                 sinks=None):
+                 sinks=None, tree_mask=None):
     """Every flash_attention_decode* / flash_attention_extend* front: ``family`` is "decode" or "extend", a ``block_table`` makes the call
     paged (K, V are then the pools) and ``cu_seqlens_q`` ragged (Q -- and O, if given -- are then packed by token: Sq is the bound on
     the packed rows, the batch is cu_seqlens_q's, the LSE is ``[H, T]``, and an O or LSE allocated here is zero-filled).  The checks of the
     tensors, the plan and the workspace for the capacity, then the entry point of _SPLIT_SYMBOLS: the ones that take both cache types
     get the descales and the cache's dtype code, the ``_window`` ones the window.  ``sinks`` (a dense fp32 ``[H]`` tensor on Q's device:
     one attention-sink logit per query head, natural-log units, not scaled; read by the kernel): the same plan and workspace, then the
-    form's entry point of _SINK_SYMBOLS, which takes the descales, the cache's dtype code and the window (0 = none) in every form."""
+    form's entry point of _SINK_SYMBOLS, which takes the descales, the cache's dtype code and the window (0 = none) in every form.
+    ``family`` "tree" (flash_attention_tree*: ``tree_mask``, a dense int64 ``[B, Sq]`` tensor on Q's device, read by the kernel as
+    bit patterns): the plan of flash_attention_tree_plan, then the entry point of _TREE_SYMBOLS -- the sinks one of decode without
+    is_causal, with ``sinks`` (or NULL) and the mask."""
     import torch
     paged, ragged = block_table is not None, cu_seqlens_q is not None
-    symbols = _SPLIT_SYMBOLS[family, paged, ragged]
-    name = symbols[0][0]      # in the error texts: the un-windowed front's
+    tree = family == "tree"
+    symbols = _SPLIT_SYMBOLS["decode" if tree else family, paged, ragged]
+    name = _TREE_SYMBOLS[paged] if tree else symbols[0][0]      # in the error texts: the un-windowed front's
     kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K, V", "[B, Hkv, capacity, d]")
     if ragged:
         Q = _token_view(Q, "Q")
@@ -615,11 +642,14 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
     if ragged and O is not None:
         O = _token_view(O, "O")
     window = _window(window)
-    both = family == "extend" or bool(window) or sinks is not None
+    both = family == "extend" or bool(window) or sinks is not None or tree
     _, H, Sq, d = Q.shape
     if sinks is not None and (getattr(sinks, "dtype", None) != torch.float32 or not sinks.is_cuda or sinks.device != Q.device
                               or tuple(sinks.shape) != (H,) or not sinks.is_contiguous()):
         raise ValueError("sinks must be a dense fp32 tensor [H] on the device of Q")
+    if tree and (getattr(tree_mask, "dtype", None) != torch.int64 or not tree_mask.is_cuda or tree_mask.device != Q.device
+                 or tuple(tree_mask.shape) != (B, Sq) or not tree_mask.is_contiguous()):
+        raise ValueError("tree_mask must be a dense int64 tensor [B, Sq] on the device of Q")
     new = torch.zeros if ragged else torch.empty      # ragged: rows no sequence owns are not written
     Hkv = K.shape[1]
     _check_kv_lens(kv_lens, B)
@@ -648,13 +678,15 @@ def _split_front(family, Q, K, V, block_table=None, cu_seqlens_q=None, kv_lens=N
                 *map(ptr, tables))
         if fp8 or both:
             ptrs += (ptr(k_descale), ptr(v_descale))
-        if sinks is not None:
-            ptrs += (sinks.data_ptr(),)
+        if sinks is not None or tree:
+            ptrs += (ptr(sinks),)
+        if tree:
+            ptrs += (tree_mask.data_ptr(),)
         dtypes = (_dtype_code(Q.dtype), _dtype_code(K.dtype)) if fp8 or both else (_dtype_code(Q.dtype),)
-        launch = getattr(lib(), _SINK_SYMBOLS[family, paged, ragged] if sinks is not None else symbols[bool(window)][fp8])
-        rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale), bool(is_causal), *dtypes,
-                    _dtype_code(O.dtype), ns, *((window,) if window or sinks is not None else ()), *[ctypes.byref(x) for x in st],
-                    _stream_ptr(s))
+        launch = getattr(lib(), name if tree else _SINK_SYMBOLS[family, paged, ragged] if sinks is not None else symbols[bool(window)][fp8])
+        rc = launch(*ptrs, workspace.data_ptr() if need else None, B, H, Hkv, Sq, *geometry, d, float(scale),
+                    *(() if tree else (bool(is_causal),)), *dtypes, _dtype_code(O.dtype), ns,
+                    *((window,) if window or sinks is not None or tree else ()), *[ctypes.byref(x) for x in st], _stream_ptr(s))
     _check(rc)
     if ragged:
         O = O.transpose(1, 2).squeeze(0)      # back to [T, H, d]
@@ -800,6 +832,71 @@ def flash_attention_extend_paged_varlen_window(Q, K_pool, V_pool, block_table, c
     """``flash_attention_extend_paged_varlen`` with a sliding window, as ``flash_attention_extend_varlen_window``; pages below a
     sequence's window as in ``flash_attention_extend_paged_window``.  No CPU fallback."""
     return _split_front("extend", Q, K_pool, V_pool, block_table, cu_seqlens_q, kv_lens, window=window, **kw)
+
+
+def flash_attention_tree(Q, K, V, tree_mask, kv_lens=None, scale=None, out_dtype=None, num_splits=0, return_lse=False, k_descale=None,
+                         v_descale=None, window=0, sinks=None, stream=None):
+    """TREE-MASKED VERIFICATION of a speculative draft: Q ``[B, H, Sq, d]`` holds the 1 <= Sq <= FA_TREE_MAX_Q draft nodes of the
+    step, already appended to the cache ``[B, Hkv, capacity, d]`` (bf16 or fp8 with descales) and counted by ``kv_lens``: node j is
+    key ``base + j`` with ``base = kv_lens[b] - Sq``, node i is query row i of every head.
+
+    ``tree_mask``: dense ``torch.int64`` device tensor ``[B, Sq]``, read by the kernel as bit patterns (no host synchronisation; a
+    replayed graph sees the words of the moment): bit j of word (b, i) set = row i sees node j.  Row i sees key k iff the causal
+    call (``flash_attention_decode(..., is_causal=True)`` with the same ``window``) shows it AND (``k < base``, or bit ``k - base``
+    is set, or k is the row's own key).  So the own key is always visible, bits above i and at or beyond Sq are ignored, and an
+    all-ones word or a chain is the causal call itself, bit for bit (Sq <= 16: ``flash_attention_decode``; above:
+    ``flash_attention_extend``).  ``window`` counts cache positions, not tree depth.  ``sinks``, ``num_splits``, ``out_dtype``,
+    ``return_lse``, the descales and ``stream`` as for ``flash_attention_decode``; ``tree_plan`` describes the launches.
+    ``tree_mask_from_parents`` builds the words from parent indices.  No CPU fallback."""
+    return _split_front("tree", Q, K, V, None, None, kv_lens, scale, True, out_dtype, num_splits, return_lse, None, None, stream,
+                        k_descale, v_descale, window, sinks, tree_mask)
+
+
+def flash_attention_tree_paged(Q, K_pool, V_pool, block_table, tree_mask, kv_lens=None, scale=None, out_dtype=None, num_splits=0,
+                               return_lse=False, k_descale=None, v_descale=None, window=0, sinks=None, stream=None):
+    """``flash_attention_tree`` against PAGED caches (pools ``[P, Hkv, page, d]`` and ``block_table`` as for
+    ``flash_attention_decode_paged``): the result is that call's on a contiguous copy of the same pages, bit for bit."""
+    return _split_front("tree", Q, K_pool, V_pool, block_table, None, kv_lens, scale, True, out_dtype, num_splits, return_lse, None, None,
+                        stream, k_descale, v_descale, window, sinks, tree_mask)
+
+
+def _tree_parents(parents):
+    """the checks of a parent array: integers ``[B, Sq]``, Sq <= FA_TREE_MAX_Q, -1 for a root, else ``0 <= parent < index``"""
+    import torch
+    p = torch.as_tensor(parents)
+    if p.dim() != 2 or p.shape[1] < 1 or p.shape[1] > FA_TREE_MAX_Q or p.dtype.is_floating_point or p.dtype == torch.bool:
+        raise ValueError(f"parents must be integers [B, Sq] with 1 <= Sq <= {FA_TREE_MAX_Q}")
+    p = p.long()
+    if bool(((p < -1) | (p >= torch.arange(p.shape[1], device=p.device)[None, :])).any()):      # (a device tensor: one synchronisation)
+        raise ValueError("parents must be -1 (a root) or the index of an earlier node")
+    return p
+
+
+def tree_mask_from_parents(parents):
+    """The ``tree_mask`` words of a draft tree given as parent indices: ``parents`` ``[B, Sq]`` integers (a tensor on any device, or
+    nested lists), -1 for a root, else ``parent < index`` (nodes in any topological order).  Returns ``torch.int64 [B, Sq]`` on the
+    device of ``parents``: word i has the bits of node i's ancestors and its own (ancestor-closed)."""
+    import torch
+    p = _tree_parents(parents)
+    w = torch.zeros_like(p)
+    one = torch.ones((), dtype=torch.int64, device=p.device)
+    for i in range(p.shape[1]):
+        up = torch.gather(w, 1, p[:, i:i + 1].clamp(min=0))[:, 0]
+        w[:, i] = torch.where(p[:, i] >= 0, up, torch.zeros_like(up)) | (one << i)
+    return w
+
+
+def tree_depths(parents):
+    """Depth of every node of a draft tree (``parents`` as for ``tree_mask_from_parents``): ``torch.int32 [B, Sq]``, 0 for a root.
+    Node i's position in ITS sequence is ``base + depth`` -- what a depth-based rotary embedding needs (``rope_cache_append`` rotates
+    at cache positions ``base + i``)."""
+    import torch
+    p = _tree_parents(parents)
+    dep = torch.zeros_like(p)
+    for i in range(p.shape[1]):
+        up = torch.gather(dep, 1, p[:, i:i + 1].clamp(min=0))[:, 0]
+        dep[:, i] = torch.where(p[:, i] >= 0, up + 1, torch.zeros_like(up))
+    return dep.to(torch.int32)
 
 
 def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream, rope=None):

@@ -364,7 +364,8 @@ struct KvCache {
 // points.  Ragged (form.varlen; flash_attention_extend*_varlen): Sq is totalQ, Q / O are packed by token (strideB is not read; NULL
 // strides: [totalQ, H, d]), the LSE and the slabs are [H, totalQ], and cu_seqlens_q -- NULL in every other call -- is required.
 // sinks: NULL, or the [H] attention-sink logits of the flash_attention_sink_* entry points (the last member: every other entry point's
-// initialiser leaves it NULL).
+// initialiser leaves it NULL).  tree_mask: NULL, or the [B, Sq] words of flash_attention_tree* (the last member, NULL in
+// every other initialiser): the TREE split kernel under any split count, Sq capped at FA_TREE_MAX_Q, is_causal set by the entry point.
 struct SplitCall {
     SplitForm form;
     const void* Q;
@@ -380,6 +381,7 @@ struct SplitCall {
     const fa_strides *sQ, *sO;
     void* stream;
     const float* sinks;
+    const uint64_t* tree_mask;
 };
 
 // A call of the append kernels: Sq new rows per sequence (ragged: totalQ token-packed rows, cu_seqlens_q required) into the cache
@@ -436,6 +438,7 @@ static int decode_check_shape(const SplitCall& c) {
     const int B = c.B, H = c.H, Sq = c.Sq, Sk = c.cache.capacity, d = c.d;
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
     if ((!f.varlen && Sq > (f.extend ? Sk : FA_DECODE_MAX_Q)) || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.tree_mask && Sq > FA_TREE_MAX_Q) return FA_ERR_BAD_SHAPE;   // (one 64-bit word per draft node)
     if (f.extend && (int64_t)(f.varlen ? 1 : B) * H * Sq > INT32_MAX) return FA_ERR_BAD_SHAPE;
     if (f.varlen && B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
     if (!kv_heads_ok(H, c.Hkv)) return FA_ERR_BAD_SHAPE;
@@ -501,10 +504,13 @@ static int cache_rows(const KvCache& c) { return c.paging ? c.paging->page_size 
 
 // The instantiation a call launches, of the twenty that exist without sinks: decode's four are WINDOW = true and serve window = 0 too; chunked
 // prefill with windowSize = 0 launches its WINDOW = false units.  sink (a sinks call under ONE split: the kernel that writes O applies
-// the sink): the twelve SINK forms, all WINDOW = true -- chunked prefill with windowSize = 0 then runs at window = 0, as decode does
+// the sink): the twelve SINK forms, all WINDOW = true -- chunked prefill with windowSize = 0 then runs at window = 0, as decode does.
+// A tree call (c.tree_mask) launches one of the eight TREE forms whatever the split count and whether or not it has sinks
 static Kernel split_kernel(const SplitCall& c, bool sink) {
     return by_bool(c.cache.paging != nullptr, [&]<bool PAGED>() {
         return by_bool(c.cache.kv_dtype == FA_DTYPE_FP8_E4M3, [&]<bool KV8>() {
+            if (c.tree_mask)
+                return by_bool(c.form.extend, [&]<bool EXTEND>() { return split_kernel_of<EXTEND, false, true, PAGED, KV8, true, true>(c.d); });
             if (sink)
                 return c.form.extend
                            ? by_bool(c.form.varlen, [&]<bool VARLEN>() { return split_kernel_of<true, VARLEN, true, PAGED, KV8, true>(c.d); })
@@ -528,6 +534,7 @@ static int decode_run(SplitCall c) {
     int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
     if (rc != FA_OK) return rc;
     if (misaligned4(c.sinks)) return FA_ERR_MISALIGNED;
+    if (reinterpret_cast<uintptr_t>(c.tree_mask) & 7u) return FA_ERR_MISALIGNED;
     if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
     fa_strides tQ{}, tO{};   // ragged: Q and O on their token strides
     if (f.varlen) {
@@ -573,17 +580,21 @@ static int decode_run(SplitCall c) {
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
     // Sinks (c.sinks): the kernel that writes O applies them -- under one split the SINK split kernel; under more
     // the split kernel is the call's own without sinks (the slabs hold the keys alone) and the SINK combine adds the sink, once per row
-    const bool sink = c.sinks != nullptr;
+    // Tree masks (c.tree_mask): the split kernel is the TREE form under any split count -- it takes the sinks
+    // pointer, NULL or not, and reads it under one split only -- and the combine is the one the call would launch without the mask
+    const bool sink = c.sinks != nullptr, tree = c.tree_mask != nullptr;
     const Kernel sk = split_kernel(c, sink && r.ns == 1);
-    const auto go = [&](const Kernel& k, unsigned grid, int lds, bool with_sinks) {   // each kernel with its exact parameter type
+    const auto go = [&](const Kernel& k, unsigned grid, int lds, bool with_sinks, bool with_tree = false) {   // each kernel with its exact parameter type
         if (f.varlen) return with_sinks ? launch(k, grid, 256, lds, st, p) : launch(k, grid, 256, lds, st, (VarlenDecodeParams)p);
-        SinkDecodeParams ps;
-        (DecodeParams&)ps = p;
-        ps.sinks = p.sinks;
-        return with_sinks ? launch(k, grid, 256, lds, st, ps) : launch(k, grid, 256, lds, st, (DecodeParams)p);
+        TreeDecodeParams pt;
+        (DecodeParams&)pt = p;
+        pt.sinks = p.sinks;
+        pt.tree_mask = c.tree_mask;
+        if (with_tree) return launch(k, grid, 256, lds, st, pt);
+        return with_sinks ? launch(k, grid, 256, lds, st, (SinkDecodeParams)pt) : launch(k, grid, 256, lds, st, (DecodeParams)p);
     };
     static_assert(DecodeCfg<128>::THREADS == 256);
-    const hipError_t e = go(sk, (unsigned)r.grid, sk.lds_bytes, sink && r.ns == 1);
+    const hipError_t e = go(sk, (unsigned)r.grid, sk.lds_bytes, sink && r.ns == 1, tree);
     if (e != hipSuccess || r.ns == 1) return (int)e;
     const Kernel ck = f.varlen ? (sink ? extend_varlen_sink_combine_kernel_of(d) : extend_varlen_combine_kernel_of(d))
                                : (sink ? decode_sink_combine_kernel_of(d) : decode_combine_kernel_of(d));
@@ -1342,6 +1353,51 @@ int flash_attention_rope_append_paged_varlen(const void* Q, const void* Knew, co
                              &rope);
 }
 
+
+// ---- tree-masked verification: the sinks entry points of decode with the mask words, is_causal set ----
+// the call family of a draft of seqLenQ nodes: decode's up to FA_DECODE_MAX_Q, chunked prefill's above (any d but 64 / 128 is refused later)
+static fa::SplitForm tree_form(int seqLenQ, int dHead) { return seqLenQ <= FA_DECODE_MAX_Q ? fa::decode_form() : fa::extend_form(dHead); }
+
+int flash_attention_tree_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype, int numSplits,
+                              int windowSize, fa_decode_plan* plan) {
+    if (!plan) return FA_ERR_NULL_POINTER;
+    if (seqLenQ > FA_TREE_MAX_Q) return FA_ERR_BAD_SHAPE;
+    return seqLenQ <= FA_DECODE_MAX_Q
+               ? flash_attention_decode_plan_window(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, numSplits, windowSize, plan)
+               : flash_attention_extend_plan_window(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, numSplits, windowSize, plan);
+}
+
+int flash_attention_tree(const void* Q, const void* K, const void* V, void* O, float* LSE, const int32_t* kvLens, const float* kDescale,
+                         const float* vDescale, const float* sinks, const uint64_t* treeMask, void* workspace, int batchSize, int numHeads,
+                         int numHeadsKV, int seqLenQ, int seqLenK, int dHead, float scale, int dtype, int kv_dtype, int o_dtype,
+                         int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV,
+                         const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!treeMask) return FA_ERR_NULL_POINTER;   // (with the other pointers: decode_run's first step returns the same code)
+    return fa::decode_run({.form = tree_form(seqLenQ, dHead), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                                     .capacity = seqLenK, .sK = sK, .sV = sV},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = true, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks, .tree_mask = treeMask});
+}
+
+int flash_attention_tree_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* kvLens,
+                               const int32_t* blockTable, const float* kDescale, const float* vDescale, const float* sinks,
+                               const uint64_t* treeMask, void* workspace, int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                               int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, int dtype,
+                               int kv_dtype, int o_dtype, int numSplits, int windowSize, const fa_strides* sQ, const fa_strides* sK,
+                               const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!treeMask) return FA_ERR_NULL_POINTER;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::decode_run({.form = tree_form(seqLenQ, dHead), .Q = Q, .O = O, .LSE = LSE,
+                           .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                     .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                           .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
+                           .scale = scale, .is_causal = true, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
+                           .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks, .tree_mask = treeMask});
+}
 
 const char* flash_attention_error_string(int code) {
     switch (code) {

@@ -86,6 +86,21 @@
 //     branch), under more the combine kernel, which takes it as one more partial result with O = 0; the slabs hold the keys alone either
 //     way.  The SINK forms take parameter types of their own (SinkDecodeParams, SinkVarlenDecodeParams: the struct + the pointer), so the
 //     SINK = false kernels' arguments are what they were; sinks = -inf reproduces their bits.  With SINK = false every term folds away.
+//   * TREE (flash_attention_tree, flash_attention_tree_paged): the Sq rows are the nodes of a speculative draft
+//     TREE, already in the cache as its last Sq keys -- node j is key base + j, base = len - Sq -- and row i sees, of those, only the
+//     nodes whose bit is set in its 64-bit word tree_mask[b * Sq + i] and, always, its own key; below `base` the mask is the causal
+//     one (p.causal is set), the window and the sinks are the twin's.  The one change to the arithmetic is the select of a score:
+//     `rel < span` gains "and (key < base or bit key - base of the row's word)".  A tile wholly below `base` (t TILE + TILE <= base,
+//     wave-uniform) takes the select as it was; only the one or two tiles that reach into [base, len) fetch the rows' words (an L2
+//     hit; they are not held across the loop: the RT = 4, d = 128 form has no registers to spare) and take the masked select -- the
+//     tree term is a branch of its own behind the select, which sets the scores it refuses to -inf and takes the maximum again:
+//     written into the select itself it was if-converted and every tile of the cache paid its 64-bit shifts (+30 ... 60 % at RT = 4).  The
+//     row's own bit is set in the fetched word, and its index, max(i, -base), is recovered from lo + span, so the row index is not
+//     kept either; a row clamped to key 0 (len < Sq) fetches a word whose other bits no visible key reads.  Everything after the
+//     select is the same text: a chain or an all-ones word gives the causal twin's bits.  The TREE forms are WINDOW = true, SINK =
+//     true, VARLEN = false with a parameter type of their own (TreeDecodeParams); their epilogue reads sinks where the SINK form
+//     does -- under ns = 1, a NULL pointer there being -inf -- and under more splits the slabs hold the keys alone and the combine
+//     kernels, sink or not, are launched unchanged.  With TREE = false every term folds away.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -136,9 +151,17 @@ struct SinkDecodeParams : DecodeParams {
 struct SinkVarlenDecodeParams : VarlenDecodeParams {
     const float* sinks;
 };
-template <bool VARLEN, bool SINK = false>
+// The tree-masked (TREE) kernels' argument (flash_attention_tree*), again a type of its own: sinks may be NULL here
+struct TreeDecodeParams : SinkDecodeParams {
+    const uint64_t* tree_mask;    // [B][Sq] (device memory): bit j of word (b, i) set = query row i sees draft node j = key len - Sq + j
+};
+template <bool VARLEN, bool SINK = false, bool TREE = false>
 struct SplitParamsOf {
     using type = DecodeParams;
+};
+template <>
+struct SplitParamsOf<false, true, true> {
+    using type = TreeDecodeParams;
 };
 template <>
 struct SplitParamsOf<true, false> {
@@ -237,9 +260,11 @@ __device__ __forceinline__ bool varlen_unit_of(const VarlenDecodeParams& p, int 
 // Decode: RT = 1, WINDOW = true.  Chunked prefill: RT = ExtendCfg<D>::RT, WINDOW = false (windowSize = 0) or true (the _window calls);
 // ragged chunked prefill: those with VARLEN.  SINK (WINDOW = true only; launched with ns = 1 only -- under more splits the sink is the
 // combine's): the epilogue adds the row's head's sink, a key with value 0, to (M, L) before it normalises; the loop is the same text.
-template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false, bool SINK = false>
-__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN, SINK>::type p) {
+// TREE (SINK = true, VARLEN = false only; launched under any ns): the masked select in the tiles that reach into the draft's keys.
+template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false, bool SINK = false, bool TREE = false>
+__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN, SINK, TREE>::type p) {
     static_assert(!SINK || WINDOW, "the SINK forms are WINDOW = true: a sinks call without a window runs them at window = 0");
+    static_assert(!TREE || (SINK && !VARLEN), "the TREE forms are WINDOW = true, SINK = true, VARLEN = false");
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
@@ -467,6 +492,10 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
 
         // s[rt][kg][reg]: key kb + 16 kg + reg, packed row r of tile rt
         const int kb = t * C::TILE + wave * C::WKEYS + 4 * h4;
+        // TREE: does this tile reach into the draft's keys [base, len)?  Wave-uniform (t, len and Sq are scalars); a tile wholly below
+        // `base` takes the select as it was
+        const int base = len - Sq;
+        const bool drafts = TREE && t * C::TILE + C::TILE > base;
         bf16x8 phi[RT], plo[RT];
         float alpha[RT];
 #pragma unroll
@@ -479,6 +508,24 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
                 const unsigned rel = (unsigned)(kbl + 16 * (j >> 2) + (j & 3));   // key - lo
                 x[j] = rel < span[rt] ? s[rt][j >> 2][j & 3] * (KV8 ? scale_log2_kd : p.scale_log2) : NEG_INF;
                 mx = fmaxf(mx, x[j]);
+            }
+            if constexpr (TREE) {
+                // the tree term of the select, as a branch of its own (the load keeps it one: none of it is computed in the tiles below
+                // `base`): the scores of the nodes the row's word does not name become -inf and the maximum is taken again.  The word is
+                // fetched here and not kept: that of query row `own` = lim - 1 - base = max(i, -base) in [0, Sq), with the own bit set.
+                // (A row clamped to key 0 reads the word of another row: key 0 is its own key and its only one.)  node = key - base:
+                // below 0 the cached prefix; a key the select above kept has a node below Sq <= 64
+                if (drafts) {
+                    const int own = lo[rt] + (int)span[rt] - 1 - base;
+                    const uint64_t word = p.tree_mask[(int64_t)b * Sq + own] | (1ull << own);
+                    mx = NEG_INF;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int node = kb - base + 16 * (j >> 2) + (j & 3);
+                        if (node >= 0 && !((word >> (node & 63)) & 1)) x[j] = NEG_INF;
+                        mx = fmaxf(mx, x[j]);
+                    }
+                }
             }
             mx = max_all_quarters(mx);
             const float m_new = fmaxf(m[rt], mx);
@@ -563,7 +610,9 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
                 // -- every exponent is <= 0, so a sink of any finite size gives finite O and LSE.  sinks = -inf: M' = M, exp2(0) = 1,
                 // exp2(-inf) = 0 and every bit is the SINK = false form's.  (ns > 1: the slabs hold the keys alone)
                 if (p.ns == 1) {
-                    const float sk = p.sinks[oh] * 1.4426950408889634f;
+                    float sink = NEG_INF;   // (TREE: the call may come without sinks, and -inf is no sink)
+                    if (!TREE || p.sinks) sink = p.sinks[oh];
+                    const float sk = sink * 1.4426950408889634f;
                     const float M2 = fmaxf(M, sk);
                     if (M2 != NEG_INF) {
                         const float e = fast_exp2(M - M2);
@@ -652,8 +701,9 @@ struct Kernel;
 // The split kernel at D = d (128, else 64) with RT = EXTEND ? ExtendCfg<D>::RT : 1 and LDS for the cache's element size.  Defined in
 // split_kv_inst.hip.h and instantiated explicitly, once each, by the units: the four decode forms (EXTEND = VARLEN = false, WINDOW = true,
 // which also serves window = 0) and all sixteen chunked-prefill forms; with SINK the twelve WINDOW = true forms of those, by the
-// inst_decode_sink_*.hip and inst_extend_sink_*.hip units.  No other combination exists
-template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK = false>
+// inst_decode_sink_*.hip and inst_extend_sink_*.hip units; with TREE (and SINK, WINDOW; VARLEN = false) the eight of {decode, chunked
+// prefill} x the four cache forms, by the inst_decode_tree_*.hip and inst_extend_tree_*.hip units.  No other combination exists
+template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK = false, bool TREE = false>
 Kernel split_kernel_of(int d);
 Kernel extend_varlen_combine_kernel_of(int d);
 Kernel decode_combine_kernel_of(int d);

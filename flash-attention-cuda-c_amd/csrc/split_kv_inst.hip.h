@@ -9,11 +9,11 @@
 namespace fa {
 
 // EXTEND: chunked prefill, ExtendCfg::RT 16-row tiles per wave (decode: one); the LDS size is that of the cache's element size
-template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK>
+template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK, bool TREE>
 Kernel split_kernel_of(int d) {
     constexpr int ES = KV8 ? 1 : 2;
-    return d == 128 ? kernel_of<split_kv_kernel<128, EXTEND ? ExtendCfg<128>::RT : 1, PAGED, KV8, WINDOW, VARLEN, SINK>>(DecodeCfg<128, ES>::LDS_BYTES)
-                    : kernel_of<split_kv_kernel<64, EXTEND ? ExtendCfg<64>::RT : 1, PAGED, KV8, WINDOW, VARLEN, SINK>>(DecodeCfg<64, ES>::LDS_BYTES);
+    return d == 128 ? kernel_of<split_kv_kernel<128, EXTEND ? ExtendCfg<128>::RT : 1, PAGED, KV8, WINDOW, VARLEN, SINK, TREE>>(DecodeCfg<128, ES>::LDS_BYTES)
+                    : kernel_of<split_kv_kernel<64, EXTEND ? ExtendCfg<64>::RT : 1, PAGED, KV8, WINDOW, VARLEN, SINK, TREE>>(DecodeCfg<64, ES>::LDS_BYTES);
 }
 
 }  // namespace fa

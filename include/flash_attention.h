@@ -940,6 +940,65 @@ int flash_attention_sink_extend_paged_varlen(const void* Q, const void* Kpool, c
                                              void* stream);
 
 /*
+ * flash_attention_tree, flash_attention_tree_paged -- TREE-MASKED VERIFICATION for speculative decoding (Medusa, EAGLE, SpecInfer and
+ * the tree modes of the serving engines): one step verifies a TREE of draft tokens, each node attending to the cached prefix and to its
+ * own ancestors only.  Each call is flash_attention_sink_decode / flash_attention_sink_decode_paged without is_causal and with one
+ * argument more, directly after sinks:
+ *   treeMask [batchSize, seqLenQ] uint64 (device memory), dense: word (b, i) is treeMask[b * seqLenQ + i].  Read by the kernel, like
+ *            kvLens: no host synchronisation, and a replayed graph sees the words of the moment (dynamic trees change every step).
+ *   seqLenQ  1 <= seqLenQ <= FA_TREE_MAX_Q draft nodes per sequence.  kv_dtype selects a bf16 or an e4m3fn cache: all four cache forms.
+ * The seqLenQ rows are the draft nodes of the step.  The caller HAS ALREADY APPENDED them (flash_attention_kv_append*) and kvLens counts
+ * them: with len = kvLens[b] and base = len - seqLenQ, node j is key base + j, and node i is query row i of every query head.  Bit j of
+ * word (b, i) set means: row i sees node j.  The rule, per row i and key k, with lim_i = max(len - seqLenQ + i + 1, 1) and
+ * lo_i = max(lim_i - windowSize, 0) (windowSize = 0: lo_i = 0) exactly as the twin computes them under is_causal = true: k is visible iff
+ *   lo_i <= k < lim_i                                                        (k is visible to the causal twin), and
+ *   k < base, or bit k - base of the row's word is set, or k == lim_i - 1    (the prefix, a marked node, or the row's own key).
+ * So: the own key is always visible and no row is empty; the len < seqLenQ clamp still holds (a row clamped to key 0 sees key 0 alone);
+ * bits j > i and bits >= seqLenQ are ignored; an all-ones word, or a chain (bits 0 .. i), is the causal twin.  The window rule stays
+ * INDEX-based: it counts positions in the cache, not tree depth (a node's window reaches windowSize keys back from its own slot base + i,
+ * siblings' slots included in the count though not in the sum).  sinks apply as in the twin; sinks = NULL means no sinks.  Draft K/V rows
+ * are data -- other rows may see them -- and must be finite, as any visible key must be.
+ *
+ * Equalities (bit for bit, O and LSE, at the same windowSize, sinks and forced numSplits): a chain or all-ones mask is
+ * flash_attention_sink_decode* (seqLenQ <= FA_DECODE_MAX_Q) or flash_attention_sink_extend* (above) with is_causal = true; the paged call is the
+ * contiguous call on a copy of the same pages; garbage in the ignored bits changes nothing; sinks = NULL is a vector of -inf.  The
+ * launches are the twin's in number, grids and LDS -- seqLenQ <= FA_DECODE_MAX_Q decode's, 17 .. FA_TREE_MAX_Q chunked prefill's:
+ * flash_attention_tree_plan forwards to flash_attention_decode_plan_window or flash_attention_extend_plan_window by that rule, and
+ * flash_attention_decode_workspace_size serves unchanged.  The split kernel is the TREE form under any split count (only the key tiles that
+ * reach into [base, len) take the masked select); the combine kernel is the twin's.
+ *
+ * Rejected before any launch: everything the sink twin rejects, with the same codes and in the same order; a NULL treeMask
+ * FA_ERR_NULL_POINTER (with the other pointers); a treeMask not aligned to 8 bytes FA_ERR_MISALIGNED, directly after the sinks check;
+ * seqLenQ > FA_TREE_MAX_Q FA_ERR_BAD_SHAPE (with the other shape checks; flash_attention_tree_plan likewise).
+ * Not done here: the ragged form (a tree size per sequence); trees above 64 nodes; depth-based rotary positions in
+ * flash_attention_rope_append*, which rotates at cache positions; masks in the prefill forward and in the backward.
+ */
+#define FA_TREE_MAX_Q 64            /* draft nodes per sequence: one uint64 mask word per node */
+
+int flash_attention_tree(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                         const int32_t* kvLens, const float* kDescale, const float* vDescale, const float* sinks,
+                         const uint64_t* treeMask, void* workspace,
+                         int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead,
+                         float scale, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                         int windowSize,
+                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                         void* stream);
+
+int flash_attention_tree_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                               const int32_t* kvLens, const int32_t* blockTable,
+                               const float* kDescale, const float* vDescale, const float* sinks,
+                               const uint64_t* treeMask, void* workspace,
+                               int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                               int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                               float scale, int dtype /* of Q */, int kv_dtype, int o_dtype, int numSplits,
+                               int windowSize,
+                               const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                               void* stream);
+
+int flash_attention_tree_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenK, int dHead, int o_dtype,
+                              int numSplits, int windowSize, fa_decode_plan* plan);
+
+/*
  * flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen -- the RAGGED cache append: flash_attention_kv_append /
  * _paged with Knew / Vnew packed by token -- [totalQ, numHeadsKV, dHead] bf16 on the stride rule of flash_attention_extend_varlen's Q
  * (row t, K/V head h at t * strideS + h * strideH; strideB ignored; NULL = dense token-major) -- seqLenNew replaced by totalQ and

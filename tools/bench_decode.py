@@ -3,6 +3,7 @@
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
                                 [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks] [--rope]
+                                [--tree 8,16,64]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -106,6 +107,15 @@ Each line:
               ms       the call without sinks: [median, min, max] of its windows -- min .. max is the noise of this run
               sink_ms  the call with sinks (a [H] vector of logits around the row's LSE), likewise
               sink_ratio = sink_ms / ms (medians); splits: the plan both calls run under (profiles/sink_bench.log).
+--tree N[,N...] tree-masked verification (flash_attention_tree*) beside its causal twin: a mode of its own over the decode shapes with N draft
+              nodes per sequence in place of Sq.  One line per shape and cache form (as under --sinks), every figure per N: the twin --
+              flash_attention_sink_decode* up to 16 nodes, flash_attention_sink_extend* above, is_causal -- and the tree call share Q, the
+              cache, the lengths, the sinks and the plan (the window: the first --window value, else none), both allocate O and the
+              workspace themselves, and they are timed ALTERNATED, --repeats windows of --steps calls each, after the usual priming:
+              causal_ms  the twin: [median, min, max] of its windows -- min .. max is the noise of this run
+              tree_ms    the tree call under a heap-shaped binary-tree mask, likewise
+              tree_ratio = tree_ms / causal_ms (medians); chain_equal: one call under a chain mask is the twin's O and LSE bit for bit
+              (profiles/tree_gpu.log).
 """
 import argparse
 import json
@@ -615,6 +625,91 @@ def sinks_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def tree_main(args, fa, dev):
+    """--tree N[,N...]: flash_attention_tree on the decode shapes with N draft nodes per sequence, beside its causal twin, alternated"""
+    import torch
+    f8 = torch.float8_e4m3fn
+    nodes = [int(x) for x in args.tree.split(",") if x]
+    pages = [int(x) for x in (args.paged or "").split(",") if x]
+    W = int((args.window or "0").split(",")[0])
+    shapes = SHAPES
+    if args.shape:
+        unknown = set(args.shape) - {x[0] for x in SHAPES + EXTRA}
+        if unknown:
+            raise SystemExit(f"unknown shape(s): {sorted(unknown)}")
+        shapes = [x for x in SHAPES + EXTRA if x[0] in args.shape]
+    primed = False
+    for name, B, H, Hkv, _, Sk, d, ragged in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        lens = [1024 + (Sk - 1024) * b // (B - 1) for b in range(B)] if ragged else [Sk] * B
+        K, V = (torch.randn(B, Hkv, Sk, d, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        sinks = (torch.linspace(-2.0, 2.0, H) + torch.log(torch.tensor(float(max(lens)))) + 0.5).to(dev)
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in pages:
+            if Sk % page == 0:
+                forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        if args.kv == "fp8":
+            def quant(Tn):
+                ds = (Tn.float().abs().amax(dim=(0, 2, 3)) / 448.0).float()
+                T8 = torch.empty(Tn.shape, dtype=f8, device=dev)
+                for b in range(B):     # (a batch entry at a time: no fp32 copy of the whole cache)
+                    T8[b] = (Tn[b].float() / ds[:, None, None]).clamp(-448, 448).to(f8)
+                return T8, ds
+            (K8, kds), (V8, vds) = quant(K), quant(V)
+        for form, fp8, page in forms:
+            Kc, Vc, table = (K8, V8, None) if fp8 else (K, V, None)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                n = Sk // page
+                perm = torch.randperm(B * n, device=dev, generator=g)
+                table = perm.reshape(B, n).to(torch.int32)
+                pools = []
+                for Tn in (Kc, Vc):
+                    Tn = Tn.view(torch.uint8) if fp8 else Tn      # (pages are moved as bytes)
+                    pool = torch.empty(B * n, Hkv, page, d, device=dev, dtype=Tn.dtype)
+                    pool[perm] = Tn.view(B, Hkv, n, page, d).transpose(1, 2).reshape(B * n, Hkv, page, d)
+                    pools.append(pool.view(f8) if fp8 else pool)
+                Kc, Vc = pools
+            line = {"shape": name, "form": form, "window": W, "splits": {}, "causal_ms": {}, "tree_ms": {}, "tree_ratio": {}, "chain_equal": {}}
+            for N in nodes:
+                Q = torch.randn(B, H, N, d, device=dev, generator=g).to(torch.bfloat16)
+                plan = fa.tree_plan(B, H, Hkv, N, Sk, d, fa.FA_DTYPE_BF16, 0, window=W)
+                twin_front = getattr(fa, ("flash_attention_decode" if N <= fa.FA_DECODE_MAX_Q else "flash_attention_extend")
+                                     + ("_paged" if page else "") + ("" if N <= fa.FA_DECODE_MAX_Q else "_window"))
+                tree_front = fa.flash_attention_tree_paged if page else fa.flash_attention_tree
+                cache = [Kc, Vc] + ([table] if page else [])
+                binary = fa.tree_mask_from_parents(torch.tensor([[(i - 1) // 2 if i else -1 for i in range(N)]] * B, device=dev))
+                chain = fa.tree_mask_from_parents(torch.tensor([[i - 1 for i in range(N)]] * B, device=dev))
+                # (both fronts allocate O and the workspace themselves: the tree fronts take neither)
+                causal = lambda: twin_front(Q, *cache, lens_d, is_causal=True, window=W, sinks=sinks, **kw)
+                tree = lambda: tree_front(Q, *cache, binary, lens_d, window=W, sinks=sinks, **kw)
+                # one bit-equality check per form and node count: a chain is the twin
+                a = twin_front(Q, *cache, lens_d, is_causal=True, window=W, sinks=sinks, return_lse=True, **kw)
+                b = tree_front(Q, *cache, chain, lens_d, window=W, sinks=sinks, return_lse=True, **kw)
+                line["chain_equal"][str(N)] = bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]))
+                if not primed:   # >= 1 s of calls before the first timed window
+                    t = 0.0
+                    while t < 1000.0:
+                        t += timed(causal, 50, 0) * 50
+                    primed = True
+                a, b = [], []
+                for _ in range(args.repeats):
+                    a.append(timed(causal, args.steps, args.warmup))
+                    b.append(timed(tree, args.steps, args.warmup))
+                a, b = sorted(a), sorted(b)
+                line["splits"][str(N)] = plan["num_splits"]
+                line["causal_ms"][str(N)] = [round(x, 5) for x in (statistics.median(a), a[0], a[-1])]
+                line["tree_ms"][str(N)] = [round(x, 5) for x in (statistics.median(b), b[0], b[-1])]
+                line["tree_ratio"][str(N)] = round(statistics.median(b) / statistics.median(a), 4)
+                del Q
+            print(json.dumps(line), flush=True)
+        del K, V
+        if args.kv == "fp8":
+            del K8, V8
+        torch.cuda.empty_cache()
+
+
 def rope_main(args, fa, dev):
     import torch
     bf = torch.bfloat16
@@ -736,11 +831,14 @@ def main():
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
     ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
     ap.add_argument("--rope", action="store_true", help="time rope_cache_append* beside the unfused torch route and the plain append, alternated")
+    ap.add_argument("--tree", default=None, help="comma-separated draft-node counts: time flash_attention_tree beside its causal twin, alternated")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.tree:
+        return tree_main(args, fa, dev)
     if args.rope:
         return rope_main(args, fa, dev)
     if args.sinks:
