@@ -59,6 +59,8 @@ KEYS = {
     "sVn": ("sVnew",), "stream": ("stream",), "plan": ("plan",),
     # flash_attention_rope_append*
     "Qo": ("Qout",), "cs": ("cosSin",), "rot": ("rotDim",), "maxpos": ("maxPos",), "il": ("interleaved",), "sQo": ("sQout",),
+    # flash_attention_tree*
+    "tree": ("treeMask",),
 }
 STRIDES = ("sQ", "sK", "sV", "sO", "sKnew", "sVnew", "sQout")
 

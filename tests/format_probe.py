@@ -40,7 +40,7 @@ import torch
 import __graft_entry__ as entry
 
 fa = entry.load_package()
-import decode_window_check as dwc  # noqa: E402  (reference_window: decode_check.reference under the window's visibility)
+import kv_cache_check as kv  # noqa: E402  (reference, visible: the float64 ground truth and the rule it masks with)
 from weight_probe import paged  # noqa: E402,F401  (the seeded page scatter of the decode probes: tests/test_exact_formats.py)
 
 bf, f32, f16, u8 = torch.bfloat16, torch.float32, torch.float16, torch.uint8
@@ -254,7 +254,7 @@ def visible(p, b):
     if p["kind"] == "decode":
         L = p["lens"][b]
         vis = torch.zeros(Sq, Sk, dtype=torch.bool)
-        vis[:, :L] = dwc.visible_window(L, Sq, p["causal"], p["window"])
+        vis[:, :L] = kv.visible(L, Sq, p["causal"], p["window"])
         return vis
     k, q = torch.arange(Sk)[None, :], torch.arange(Sq)[:, None]
     return (k <= q) if p["causal"] else torch.ones(Sq, Sk, dtype=torch.bool)
@@ -269,11 +269,11 @@ def weights(p, b):
 
 
 def reference(p):
-    """(O, LSE) float64: decode through decode_check.reference (under the window: decode_window_check.reference_window, the same
-    softmax over the window's keys), prefill through the explicit softmax"""
+    """(O, LSE) float64: decode through kv_cache_check.reference (under the window: the same softmax over the window's
+    keys), prefill through the explicit softmax"""
     Q, K, V = logical(p)
     if p["kind"] == "decode":
-        return dwc.reference_window(Q, K, V, p["lens"], p["causal"], p["window"], p["scale"])
+        return kv.reference(Q, K, V, p["lens"], p["causal"], p["window"], scale=p["scale"])
     G = Q.shape[1] // K.shape[1]
     S = ((Q[0] @ K[0].repeat_interleave(G, 0).transpose(-1, -2)) * p["scale"]).masked_fill(~visible(p, 0)[None], float("-inf"))
     return (torch.softmax(S, -1) @ V[0].repeat_interleave(G, 0))[None], torch.logsumexp(S, -1)[None]

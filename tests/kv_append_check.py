@@ -1,21 +1,54 @@
-"""Reference shared by the K/V cache append tests (tests/test_kv_append_abi.py on the CPU, tests/test_kv_append.py on the GPU; no
-tests in here).  Plain torch on the CPU.
+"""Reference and scaffolding shared by the K/V cache append tests (tests/test_kv_append_abi.py on the CPU, tests/test_kv_append.py,
+test_kv_append_varlen.py and the rope append tests on the GPU; no tests in here).  Plain torch on the CPU.
 
 Writer.  `append()` is the contract of include/flash_attention.h (flash_attention_kv_append, _paged) spelled out: the position rule
-(`positions()`), the value rule (`encode()`: a bit copy for a bf16 cache, `decode_check.quantise`'s expression with a GIVEN descale
+(`positions()`), the value rule (`encode()`: a bit copy for a bf16 cache, `kv_cache_check.quantise`'s expression with a GIVEN descale
 for an fp8 one), contiguous or paged, table entries outside [0, P) skipped.  Caches are handled as integer tensors -- uint8 for
 e4m3fn bytes, int16 for bf16 patterns -- so that comparisons are of bits and NaN patterns compare like any other.
 
 Yardstick of the yardstick.  `nearest_even_code()` finds the e4m3fn code of a quotient by brute force over the table of all codes
 built from the format's definition (format_probe.TABLE): nearest value, ties to the even code, the sign kept, saturation at 448.
 tests/test_kv_append_abi.py holds `encode()` against it on every bf16 bit pattern.
+
+Scaffolding.  `sentinel()`: a cache pre-filled with a finite pattern (`SENT`), compared whole afterwards; `as_cache()`: the integer
+tensor as the call takes it; `new_rows()`: the rows to append, special values among them; `descales()`; `same()`.
 """
 import torch
 
 from format_probe import TABLE
 
 F8 = getattr(torch, "float8_e4m3fn", None)
-i16, u8 = torch.int16, torch.uint8
+bf, i16, u8 = torch.bfloat16, torch.int16, torch.uint8
+SENT = {u8: 0xA5, i16: 0x5A5A}        # (0xA5 is a finite e4m3fn code, 0x5A5A a finite bf16: never what a NaN compares as)
+
+
+def sentinel(shape, fp8, device="cpu"):
+    dt = u8 if fp8 else i16
+    return torch.full(shape, SENT[dt], dtype=dt, device=device)
+
+
+def as_cache(t):
+    """the integer tensor as the call takes it"""
+    return t.view(F8) if t.dtype == u8 else t.view(bf)
+
+
+def new_rows(shape, seed):
+    """bf16 N(0, 1) scaled so that some values saturate at descales near 1 / 64, with the special values among them"""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(shape, generator=g) * 3).to(bf)
+    flat = x.reshape(-1)
+    special = torch.tensor([float("nan"), float("inf"), -float("inf"), -0.0, 0.0, 1e-30, -1e-30, 448.0, 464.0, 3e38], dtype=bf)
+    flat[:special.numel()] = special
+    flat[-special.numel():] = special.flip(0)
+    return x
+
+
+def descales(seed, fp8, Hkv=2):
+    """(k_descale, v_descale) fp32 [Hkv] on the CPU, near 1 / 64 and near 1; (None, None) for a bf16 cache"""
+    if not fp8:
+        return None, None
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(Hkv, generator=g) * 0.05 + 0.01).float(), (torch.rand(Hkv, generator=g) * 2 + 0.5).float()
 
 
 def all_bf16_patterns():
@@ -95,3 +128,8 @@ def same_bytes(got, want):
     g, w = got.cpu(), want.cpu()
     gn, wn = (g & 0x7F) == 0x7F, (w & 0x7F) == 0x7F
     return bool(torch.equal(gn, wn)) and bool(torch.equal(g[~wn], w[~wn]))
+
+
+def same(got, want):
+    """a cache against the reference's (either may be on the device): bits, NaN bytes of an fp8 cache by class"""
+    return same_bytes(got, want) if want.dtype == u8 else torch.equal(got.cpu(), want.cpu())

@@ -11,7 +11,7 @@ in exp2 units), V comes from long_probe.v_rows.  What this family adds:
             target scores 128 nb, an anchor 128 nb - 64, every other key <= 128 nb - 256.
   ranges    row i of a sequence of `len` keys and Sq rows sees lo_i <= k < lim_i with limC_i = max(len - Sq + i + 1, 1),
             lo_i = max(limC_i - W, 0) (W = 0: 0), lim_i = limC_i (causal) or len: ranges(), which tests/test_long_cache_probe.py holds
-            to decode_window_check.visible_window (that one builds a [Sq, len] matrix: not at 2^20 keys).
+            to kv_cache_check.visible (that one builds a [Sq, len] matrix: not at 2^20 keys).
   closed    a row whose target is visible: the target weighs 1 and the k anchors 2^-64 each: l = 1 in fp32, O = V[target] BIT FOR BIT,
   forms     LSE = ln 2 * 128 nb.  A row whose target is hidden -- above lim_i, below lo_i, at or beyond len -- has the anchors for its
             best keys: O = +0 exactly, LSE = ln 2 * (128 nb - 64) + ln k, k the anchors in [lo_i, lim_i) (anchors_below()).  Every row has

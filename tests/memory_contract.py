@@ -14,15 +14,14 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 import arena as ar  # noqa: E402
-import decode_check as dc  # noqa: E402
-import extend_window_check as ewc  # noqa: E402
+import kv_cache_check as kv  # noqa: E402
 import kv_append_check as kvc  # noqa: E402
 import weight_probe as wp  # noqa: E402
 from abi_decl import c_call  # noqa: E402
 
 DEV = "cuda:0"
 bf, f32, u8, i32 = torch.bfloat16, torch.float32, torch.uint8, torch.int32
-F8 = dc.F8
+F8 = kv.F8
 CODE = {f32: fa.FA_DTYPE_F32, bf: fa.FA_DTYPE_BF16, F8: fa.FA_DTYPE_FP8_E4M3, torch.float16: fa.FA_DTYPE_F16}
 PLACEMENTS = ("aligned", "offset")          # in this order: a failure under `aligned` is a workspace or guard finding, not an address one
 
@@ -177,15 +176,15 @@ class Cache:
         K, V = randn((B, HKV, CAPACITY, d), seed), randn((B, HKV, CAPACITY, d), seed + 1)
         self.B, self.d, self.page, self.fp8, self.kd, self.vd, self.table = B, d, page, fp8, None, None, None
         if fp8:
-            (K, self.kd), (V, self.vd) = dc.quantise(K.float() * 3.0), dc.quantise(V.float() * 0.5)      # uint8; descales away from 1
-            self.refK, self.refV = dc.dequantise(K, self.kd), dc.dequantise(V, self.vd)
+            (K, self.kd), (V, self.vd) = kv.quantise(K.float() * 3.0), kv.quantise(V.float() * 0.5)      # uint8; descales away from 1
+            self.refK, self.refV = kv.dequantise(K, self.kd), kv.dequantise(V, self.vd)
         else:
             self.refK, self.refV = K.double(), V.double()
         if page:
             n = CAPACITY // page
-            table = ewc.random_table(B, n, seed + 2)
-            pools = ewc.scatter(K, table, page), ewc.scatter(V, table, page)
-            assert torch.equal(dc.gather(pools[0], table), K) and torch.equal(dc.gather(pools[1], table), V)
+            table = kv.random_table(B, n, seed + 2)
+            pools = kv.scatter(K, table, page), kv.scatter(V, table, page)
+            assert torch.equal(kv.gather(pools[0], table), K) and torch.equal(kv.gather(pools[1], table), V)
             K, V = pools
             self.table = torch.cat([table, torch.full((B, WIDE), 2 ** 31 - 1, dtype=i32)], 1) if page == 16 else table
         self.K, self.V = (t.view(F8) if fp8 else t for t in (K, V))

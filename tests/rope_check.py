@@ -17,6 +17,7 @@ differing element named.
 import torch
 
 import kv_append_check as kc
+from kv_cache_check import random_table
 
 i16, u8, bf16 = torch.int16, torch.uint8, torch.bfloat16
 
@@ -155,3 +156,33 @@ def probe_expect(x, pos, rot, interleaved):
     out[..., a] = torch.where(m == 0, x1, torch.where(m == 1, -x2, torch.where(m == 2, -x1, x2)))
     out[..., b] = torch.where(m == 0, x2, torch.where(m == 1, x1, torch.where(m == 2, -x2, -x1)))
     return out
+
+
+# ---- what the GPU tests (test_rope_append.py, test_rope_append_varlen.py) build and check alike -------------------------------------------
+QSENT = 0x4B4B                        # what Qout holds before a call: finite in bf16
+
+
+def qsent(shape, device="cpu"):
+    return torch.full(shape, QSENT, dtype=i16, device=device).view(bf16)
+
+
+def rows(shape, seed, special=False):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(shape, generator=g) * 3).to(bf16)
+    if special:       # NaN payloads, infinities, -0, tiny and huge values among them
+        flat = x.reshape(-1)
+        s = torch.tensor([0x7FC1, -0x0040 + 0x0001, 0x7F80, -0x0080, -0x8000, 0x0000, 0x0001, -0x7FFF, 0x43E0, 0x7F7F],
+                         dtype=torch.int32).to(i16).view(bf16)
+        flat[:s.numel()] = s
+        flat[-s.numel():] = s.flip(0)
+    return x
+
+
+def table_of(B, n, spare, seed):
+    """(P, block table [B, n]): a seeded permutation of the P = B * n + spare pages"""
+    return B * n + spare, random_table(B, n, seed, spare)
+
+
+def check(got, want, what):
+    for name, g, w in zip(("Qout", "Kcache", "Vcache"), got, want):
+        assert_same(f"{what}: {name}", g, w)

@@ -1,15 +1,15 @@
 """Checker shared by the attention-sink tests (tests/test_sink_abi.py, test_sink.py, test_sink_extend.py, test_sink_memory_contract.py):
 the float64 ground truth of a K/V-cache call with ``sinks``, derived from the existing references, and the data the tests build alike.
-Plain torch on the CPU; the criterion is decode_check.assert_close, unchanged.
+Plain torch on the CPU; rule, reference, criterion, the four cache forms (`Cache`) and the fronts (`attend`) are kv_cache_check's.
 
 Reference.  A sink is one more key of score ``sinks[h]`` (natural log, not scaled) and value 0 in the softmax of every row of query head
-h.  So with (O, LSE) the reference WITHOUT sinks -- decode_check.reference, or decode_window_check.reference_window under a window, or
-extend_window_check.per_sequence_reference_window for the ragged call, all imported --
+h.  So with (O, LSE) the reference WITHOUT sinks -- kv_cache_check.reference, or reference_ragged for the ragged call --
 
     LSE' = logaddexp(LSE, sink_h)        O' = O * exp(LSE - LSE')
 
-(`apply_sinks`).  `brute_force` is the same thing the long way round -- an explicit softmax in float64 over the visible keys and one
-extra column of score sink_h whose value row is 0 -- and test_sink_abi.py holds the two against each other.
+(`apply_sinks`: what kv_cache_check.reference does with its ``sinks`` argument).  `brute_force` is the same thing the long way round --
+an explicit softmax in float64 over the visible keys (`scores`: kv_cache_check.visible, never its reference) and one extra column of
+score sink_h whose value row is 0 -- and test_sink_abi.py holds the two against each other.
 
 Sink vector.  `SINKS8` is the vector of the parity cases at H = 8.  `sinks_for(H)` cycles it for H > 8.  For H < 8 it takes every
 (8 / H)-th element from index 1 on (H = 2: 0 and 5.5; H = 4: 0, 3, 5.5, 8), not the first H: the first two, (-inf, 0), would
@@ -20,17 +20,17 @@ nothing, which `assert_sinks_matter` refuses.  With 0 and 5.5 one head's sink is
 `assert_sinks_matter`: on the reference, at least ONE THIRD of the (sequence, head, row) triples of a case have a sink weight
 exp(sink_h - LSE') in [0.05, 0.95].  A case whose sinks change nothing, or swamp everything, tests nothing.
 """
+import itertools
 import math
 
 import torch
 
-from decode_check import reference
-from decode_window_check import reference_window, visible_window
-from extend_window_check import cu_of, packed, per_sequence_reference_window
+from kv_cache_check import (DEV, Cache, assert_close, attend, cu_of, fa, first_visible, i32, lse_ratio, poisoned_ff, ratios, reference,
+                            reference_ragged, same_bits, visible)
 
 NEG_INF = float("-inf")
 SINKS8 = (NEG_INF, 0.0, 1.5, 3.0, 4.5, 5.5, 6.5, 8.0)
-B, HKV, CAP = 2, 2, 384                      # every case: two sequences, two K/V heads, three 128-key tiles of capacity
+B, HKV, CAP = Cache.B, Cache.HKV, Cache.ROWS  # every case: two sequences, two K/V heads, three 128-key tiles of capacity
 WINDOWS = (0, 7, 130)
 
 
@@ -72,20 +72,11 @@ def assert_sinks_matter(lse2, sinks, ragged=False, owned=None, what=""):
 
 
 def reference_sinks(Q, K, V, lens, causal, W, sinks, scale=None):
-    """the uniform calls' reference with sinks: decode_check.reference (W = 0) or reference_window, then apply_sinks.  Returns
-    (O' [B, H, Sq, d], LSE' [B, H, Sq], O, LSE) -- the last two without sinks"""
-    O, lse = reference(Q, K, V, lens, causal, scale) if W <= 0 else reference_window(Q, K, V, lens, causal, W, scale)
+    """the uniform calls' reference with sinks: kv_cache_check.reference, then apply_sinks.  Returns (O' [B, H, Sq, d],
+    LSE' [B, H, Sq], O, LSE) -- the last two without sinks"""
+    O, lse = reference(Q, K, V, lens, causal, W, scale=scale)
     O2, lse2 = apply_sinks(O, lse, sinks)
     return O2, lse2, O, lse
-
-
-def reference_sinks_ragged(Q, K, V, sq, lens, causal, W, sinks, scale=None):
-    """the ragged call's: per_sequence_reference_window packed by token, then apply_sinks.  Q [T, H, d]; returns (O' [T, H, d],
-    LSE' [H, T], owned [T])"""
-    T, H, d = Q.shape
-    O, lse, owned = packed(per_sequence_reference_window(Q, K, V, sq, lens, causal, W, scale), sq, T, H, d)
-    O2, lse2 = apply_sinks(O, lse, sinks, ragged=True)
-    return O2, lse2, owned
 
 
 def scores(Q, K, L, causal, W, scale=None):
@@ -93,7 +84,7 @@ def scores(Q, K, L, causal, W, scale=None):
     H, Sq, d = Q.shape
     G = H // K.shape[0]
     S = (Q.double() @ K[:, :L].double().repeat_interleave(G, 0).transpose(-1, -2)) * (scale or 1.0 / d ** 0.5)
-    return S.masked_fill(~visible_window(L, Sq, causal, W)[None], NEG_INF)
+    return S.masked_fill(~visible(L, Sq, causal, W)[None], NEG_INF)
 
 
 def brute_force(Q, K, V, lens, causal, W, sinks, scale=None):
@@ -119,89 +110,19 @@ def data(d, G, Sq, seed):
 
 
 def excess(O, lse, refO, refL):
-    """(worst O error / tolerance, worst LSE error / tolerance) under decode_check.assert_close's bounds: > 1 is a refusal"""
-    err, tol = (O.double() - refO).abs(), 1e-3 + 1e-3 * refO.abs()
-    lerr, ltol = (lse.double() - refL).abs(), 2e-4 + 2e-6 * refL.abs()
-    return (err / tol).max().item(), (lerr / ltol).max().item()
+    """(worst O error / tolerance, worst LSE error / tolerance) under kv_cache_check.assert_close's bounds: > 1 is a refusal"""
+    r, lr = ratios(O, lse, refO, refL)
+    return r.max().item(), lr.max().item()
 
 
 LN2 = math.log(2.0)
 
 
 # ---- what the GPU tests (test_sink.py, test_sink_extend.py) build and run alike ---------------------------------------------------
-import itertools  # noqa: E402
-
-import decode_check as dc  # noqa: E402
-import extend_window_check as ewc  # noqa: E402
-from decode_window_check import first_visible  # noqa: E402
-
-DEV = dc.DEV
 FORMS = ((None, False), (16, False), (None, True), (128, True))      # (page size or None, fp8): the four cache forms
 FORM_IDS = ("contig-bf16", "paged16-bf16", "contig-fp8", "paged128-fp8")
 LENS = ((1, 300), (129, 300))
 f32, bf16 = torch.float32, torch.bfloat16
-
-
-class Cache:
-    """A K/V cache [B, HKV, CAP, d] of N(0, 1) data in one of the four forms.  cK, cV: what is stored, contiguous, on the CPU (bf16, or
-    the e4m3fn bytes as uint8 with the descales kd, vd = amax / 448); refK, refV: the float64 logical cache the references read"""
-
-    def __init__(self, d, page, fp8, seed, K=None, V=None, descales=None):
-        g = torch.Generator().manual_seed(seed)
-        K = torch.randn(B, HKV, CAP, d, generator=g).to(bf16) if K is None else K
-        V = torch.randn(B, HKV, CAP, d, generator=g).to(bf16) if V is None else V
-        self.d, self.page, self.fp8, self.kd, self.vd = d, page, fp8, None, None
-        if fp8:
-            if descales is None:
-                (self.cK, self.kd), (self.cV, self.vd) = dc.quantise(K.float()), dc.quantise(V.float())
-            else:       # values that are e4m3fn numbers as they stand
-                self.kd, self.vd = descales
-                self.cK, self.cV = K.float().to(dc.F8).view(torch.uint8), V.float().to(dc.F8).view(torch.uint8)
-            self.refK, self.refV = dc.dequantise(self.cK, self.kd), dc.dequantise(self.cV, self.vd)
-        else:
-            self.cK, self.cV, self.refK, self.refV = K, V, K.double(), V.double()
-        self.table = ewc.random_table(B, CAP // page, seed + 2) if page else None
-
-    def device(self, cK=None, cV=None, contiguous=False):
-        """the device tensors the fronts take, of the stored bytes (or of cK, cV in their place: a poisoned copy): K, V -- the cache,
-        or its pools under the table -- table, and the descales as keywords.  contiguous: the contiguous form of the same bytes"""
-        out = dict(table=None, ds={})
-        kv = [self.cK if cK is None else cK, self.cV if cV is None else cV]
-        if self.page and not contiguous:
-            flat = kv
-            kv = [ewc.scatter(t, self.table, self.page) for t in flat]
-            assert all(same_bits(dc.gather(p, self.table), t) for p, t in zip(kv, flat))      # (bits: a poisoned copy holds NaNs)
-            out["table"] = self.table.to(DEV)
-        out["K"], out["V"] = ((t.view(dc.F8) if self.fp8 else t).to(DEV) for t in kv)
-        if self.fp8:
-            out["ds"] = dict(k_descale=self.kd.to(DEV), v_descale=self.vd.to(DEV))
-        return out
-
-
-def poisoned(stored, lens, firsts):
-    """a copy of a stored contiguous cache with 0xFF bytes (NaN in bf16 and in e4m3fn) at and beyond every sequence's length and below
-    its first visible key"""
-    out = stored.clone()
-    raw = out.view(torch.uint8)
-    for b, (L, first) in enumerate(zip(lens, firsts)):
-        raw[b, :, L:] = 0xFF
-        raw[b, :, :first] = 0xFF
-    return out
-
-
-def attend(family, c, Q, lens, cu=None, **kw):
-    """(O, LSE) of one call through the Python fronts: family "decode", "extend" (the _window fronts: window None / 0 is the plain call)
-    or "varlen" (Q packed by token, cu the offsets); c: Cache.device()"""
-    fa = dc.fa
-    paged = c["table"] is not None
-    name = {"decode": "flash_attention_decode", "extend": "flash_attention_extend", "varlen": "flash_attention_extend"}[family] \
-        + ("_paged" if paged else "") + ("_varlen" if family == "varlen" else "") + ("" if family == "decode" else "_window")
-    args = [Q, c["K"], c["V"]] + ([c["table"]] if paged else []) + ([cu] if family == "varlen" else [])
-    return getattr(fa, name)(*args, lens, return_lse=True, **c["ds"], **kw)
-
-
-def i32(v):
-    return torch.tensor(list(v), dtype=torch.int32).to(DEV)
 
 
 def queries(family, d, G, rows, seed):
@@ -214,21 +135,17 @@ def queries(family, d, G, rows, seed):
 def reference_of(family, cache, Q, rows, lens, causal, W, sinks):
     """(O', LSE', owned or None) of a case: uniform or ragged"""
     if family == "varlen":
-        return reference_sinks_ragged(Q, cache.refK, cache.refV, rows, lens, causal, W, sinks)
+        return reference_ragged(Q, cache.refK, cache.refV, rows, lens, causal, W, sinks)
     O2, lse2, _, _ = reference_sinks(Q, cache.refK, cache.refV, lens, causal, W, sinks)
     return O2, lse2, None
 
 
 def close(O, lse, refO, refL, owned, what):
-    """decode_check.assert_close on the rows a sequence owns (all of them in a uniform call)"""
+    """kv_cache_check.assert_close on the rows a sequence owns (all of them in a uniform call)"""
     if owned is None:
-        dc.assert_close(O, lse, refO, refL, what)
+        assert_close(O, lse, refO, refL, what)
     else:
-        dc.assert_close(O.cpu()[owned], lse.cpu()[:, owned], refO[owned], refL[:, owned], what)
-
-
-def same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+        assert_close(O.cpu()[owned], lse.cpu()[:, owned], refO[owned], refL[:, owned], what)
 
 
 def run_parity(family, d, G, form, rows_list, run=True):
@@ -318,7 +235,7 @@ def run_probe(family, d, G, form, causal, rows, lens_list, splits):
                     raise AssertionError(f"{family} d{d} G{G} causal{int(causal)} lens{lens} splits{ns} {odt}: sequence {b} head {h} row {i} "
                                          f"should hold half of key {key}'s V row and holds that of key(s) {named}: {got[h, :6].tolist()}")
                 l = (lse[:, cu[b] + i] if ragged else lse[b, :, i]).double()
-                assert ((l - LN2).abs() <= 2e-4 + 2e-6 * LN2).all(), (family, lens, ns, b, i, l.tolist())
+                assert (lse_ratio(l, LN2) <= 1).all(), (family, lens, ns, b, i, l.tolist())
 
 
 def run_range(family, d, G, form, rows):
@@ -348,12 +265,12 @@ def run_range(family, d, G, form, rows):
                 lo, ll = lo[owned], ll[:, owned]
             if value == 1e4:
                 assert not lo.any(), f"{what}: O is not 0"
-                assert ((ll.double() - 1e4).abs() <= 2e-4 + 2e-6 * 1e4).all(), f"{what}: LSE is not the sink"
+                assert (lse_ratio(ll, 1e4) <= 1).all(), f"{what}: LSE is not the sink"
             if value == -1e4:
                 po, pl = plain[0].cpu(), plain[1].cpu()
                 if owned is not None:
                     po, pl = po[owned], pl[:, owned]
-                dc.assert_close(lo, ll, po.double(), pl.double(), what + " against the call without sinks")
+                assert_close(lo, ll, po.double(), pl.double(), what + " against the call without sinks")
 
 
 def run_paged_equal(family, d, rows, page, fp8, seed):
@@ -381,7 +298,7 @@ def run_poison(family, d, rows, form, seed):
         firsts = [first_visible(L, sq, W) for L, sq in zip(lens, rows if family == "varlen" else (rows,) * B)]
         assert max(firsts) > 128
         clean = cache.device()
-        dirty = cache.device(poisoned(cache.cK, lens, firsts), poisoned(cache.cV, lens, firsts))
+        dirty = cache.device(poisoned_ff(cache.cK, lens, firsts), poisoned_ff(cache.cV, lens, firsts))
         for causal, ns in itertools.product((False, True), (1, 3)):
             kw = dict(is_causal=causal, window=W, num_splits=ns, sinks=sinks, out_dtype=f32)
             a, b = attend(family, clean, Q, i32(lens), cu, **kw), attend(family, dirty, Q, i32(lens), cu, **kw)
@@ -407,7 +324,7 @@ def run_graph(step, lens, start, Sq, sinks, reference, O):
         now = lens.tolist()
         assert now == [s + (r + 1) * Sq for s in start]
         refO, refL = reference(now, vec)
-        dc.assert_close(O, lse, refO, refL, f"replay {r}")
+        assert_close(O, lse, refO, refL, f"replay {r}")
         seen.append(O.clone())
     assert not torch.equal(seen[0], seen[2])
 
@@ -425,7 +342,6 @@ class Recorder:
 
 def run_routing(monkeypatch, front, args, kw, sinks, plan, launch):
     """test 7: with sinks the front fetches [plan, workspace size, launch]; without them the same two and no sink entry point"""
-    fa = dc.fa
     rec = Recorder(fa.lib())
     monkeypatch.setattr(fa, "lib", lambda: rec)
     O, lse = getattr(fa, front)(*args, sinks=sinks, return_lse=True, **kw)

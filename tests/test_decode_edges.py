@@ -1,6 +1,6 @@
 """GPU tests of flash_attention_decode at its edges: lengths out of range (clamped on the device into [1, capacity]), custom scales and
 a sharp softmax, splits whose partial log-sum-exps differ by hundreds, |V| = 1e30, and the largest head extent the ABI accepts
-(one K/V head just under 2^31 bytes).  Reference, mask and the element-wise check are those of tests/decode_check.py."""
+(one K/V head just under 2^31 bytes).  Reference, mask and the element-wise check are those of tests/kv_cache_check.py."""
 import pytest
 
 import __graft_entry__ as entry
@@ -8,38 +8,10 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import CAP, DEV, TILE, assert_close, randn, reference, visible  # noqa: E402
+from kv_cache_check import CAP, DEV, SCALES, TILE, assert_close, assert_close_with_score_noise, randn, reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-
-
-def scores_max(Q, K, lens, causal, scale):
-    """largest |scale * score| over the visible (row, key) pairs"""
-    B, H, Sq, d = Q.shape
-    G = H // K.shape[1]
-    worst = 0.0
-    for b in range(B):
-        L = K.shape[2] if lens is None else int(lens[b])
-        S = (Q[b].double() @ K[b, :, :L].double().repeat_interleave(G, 0).transpose(-1, -2)) * scale
-        worst = max(worst, S.abs().masked_fill(~visible(L, Sq, causal)[None], 0.0).max().item())
-    return worst
-
-
-def assert_close_with_score_noise(O, lse, Q, K, V, lens, causal, scale, what):
-    """the stated 1e-3 + 1e-3 |ref| plus the fp32 score noise through exp(), 8 max(smax, 4) 2^-23 ref_abs (ref_abs: the reference on
-    |V|); the LSE within 1e-5 + 16 max(smax, 4) 2^-23 + 2^-22 |LSE| -- the fp32 terms of tests/fuzz_gpu.py"""
-    refO, refL = reference(Q, K, V, lens, causal, scale)
-    ref_abs, _ = reference(Q, K, V.abs(), lens, causal, scale)
-    smax = max(scores_max(Q, K, lens, causal, scale), 4.0)
-    O, lse = O.double().cpu(), lse.double().cpu()
-    assert torch.isfinite(O).all() and torch.isfinite(lse).all(), what
-    err, tol = (O - refO).abs(), 1e-3 + 1e-3 * refO.abs() + 8 * smax * 2.0 ** -23 * ref_abs
-    lerr, ltol = (lse - refL).abs(), 1e-5 + 16 * smax * 2.0 ** -23 + 2.0 ** -22 * refL.abs()
-    print(f"{what}: smax {smax:.1f}, LSE up to {refL.abs().max().item():.1f}, worst O error / tolerance {(err / tol).max().item():.3f}, "
-          f"worst LSE error / tolerance {(lerr / ltol).max().item():.3f}")
-    assert (err <= tol).all(), f"{what}: {int((err > tol).sum())} elements of O out, worst ratio {(err / tol).max().item():.3f}"
-    assert (lerr <= ltol).all(), f"{what}: LSE worst ratio {(lerr / ltol).max().item():.3f}"
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -60,10 +32,6 @@ def test_lengths_out_of_range_are_clamped_on_the_device(d, causal):
         torch.cuda.synchronize()
         assert torch.equal(O, Oc) and torch.equal(lse, lsec), splits
         assert_close(O, lse, refO, refL, f"clamped lengths, d {d} causal {causal} splits {splits}")
-
-
-SCALES = {"small": lambda d: (0.02, 1.0), "large": lambda d: (3.0 / d ** 0.5, 1.0), "one": lambda d: (1.0, d ** -0.25),
-          "boost3": lambda d: (1.0 / d ** 0.5, 3.0), "boost12": lambda d: (1.0 / d ** 0.5, 12.0)}
 
 
 @pytest.mark.parametrize("kind", list(SCALES))

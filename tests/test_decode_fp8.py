@@ -17,7 +17,7 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import CAP, DEV, F8, assert_close, dequantise, gather, max_pages_of, paged_layout, quantise, randn, reference  # noqa: E402
+from kv_cache_check import CAP, DEV, F8, assert_close, dequantise, gather, max_pages_of, paged_layout, quantise, randn, reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = torch.float32

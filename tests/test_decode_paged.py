@@ -14,7 +14,7 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import CAP, DEV, assert_close, gather, max_pages_of, paged_layout, randn, reference  # noqa: E402
+from kv_cache_check import CAP, DEV, assert_close, gather, max_pages_of, paged_layout, randn, reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16

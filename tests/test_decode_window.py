@@ -1,7 +1,7 @@
 """GPU tests of sliding-window decode (flash_attention_decode / flash_attention_decode_paged with window=W; the C entry points
 flash_attention_decode_window and flash_attention_decode_paged_window) over all four cache forms: contiguous / paged x bf16 / fp8.
 
-Criterion: decode_check.assert_close against the float64 explicit softmax over the keys decode_window_check.visible_window lets each
+Criterion: kv_cache_check.assert_close against the float64 explicit softmax over the keys kv_cache_check.visible lets each
 row see -- every element of the fp32 O within 1e-3 + 1e-3 |ref|, the LSE within 2e-4 + 2e-6 |ref|.  Capacity 640 = five 128-key
 tiles, one sequence per length, lengths placed so that `first` (row 0's left edge: the lowest key any row sees) falls on, one before
 and one after a tile start.  Beside parity: bitwise identities (no window, a window no shorter than the capacity, paged against
@@ -16,8 +16,8 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import DEV, F8, assert_close, dequantise, gather, quantise, randn  # noqa: E402
-from decode_window_check import first_visible, reference_window  # noqa: E402
+from kv_cache_check import (DEV, F8, assert_close, dequantise, first_visible, gather, i32 as dev_lens, poisoned_nan_inf, quantise,  # noqa: E402
+                            randn, random_table, reference, scatter)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -25,7 +25,7 @@ CAPACITY, TILE = 640, 128
 H, HKV = 8, 2
 WINDOWS = (1, 2, 15, 16, 17, 127, 128, 129, 300, 640)
 SPLITS = (0, 1, 2, 3, 5, 8)          # 0: the library's choice; 8: more than any window here has tiles, so some splits are empty
-NAN, INF = float("nan"), float("inf")
+NAN = float("nan")
 
 
 def lengths(W, Sq):
@@ -62,10 +62,6 @@ def queries(B, Sq, d):
     return randn((B, H, Sq, d), 7300 + 16 * Sq + d, BF16)
 
 
-def dev_lens(lens):
-    return torch.tensor(lens, dtype=torch.int32, device=DEV)
-
-
 def run(Q, K, V, ld, **kw):
     O, lse = fa.flash_attention_decode(Q, K, V, ld, out_dtype=torch.float32, return_lse=True, **kw)
     torch.cuda.synchronize()
@@ -92,7 +88,7 @@ def test_boundary_sweep_against_float64(d, Sq, causal):
         assert B <= BMAX
         seen |= {first_visible(L, Sq, W) for L in lens}
         Q = queries(B, Sq, d)
-        refO, refL = reference_window(Q, K[:B], V[:B], lens, causal, W)
+        refO, refL = reference(Q, K[:B], V[:B], lens, causal, W)
         Qd, ld = Q.to(DEV), dev_lens(lens)
         for splits in SPLITS:
             O, lse = run(Qd, Kd[:B], Vd[:B], ld, is_causal=causal, num_splits=splits, window=W)
@@ -139,7 +135,7 @@ def test_single_weights_on_both_sides_of_the_left_edge(d, Sq, W, L):
         V[0, :, w0 + torch.arange(d), torch.arange(d)] = 1.0
         Vd = V.to(DEV)
         for causal in (False, True):
-            refO, refL = reference_window(Q, K[:1], V, [L], causal, W)
+            refO, refL = reference(Q, K[:1], V, [L], causal, W)
             keys = torch.arange(w0, w0 + d)
             hidden = (keys < lo) | (keys >= (limc if causal else L))
             assert hidden[:d // 2].all() and not hidden[d // 2] and (refO[0, :, i, hidden] == 0).all() and (refO[0, :, i, ~hidden] > 0).all()
@@ -174,15 +170,7 @@ def test_poison_below_the_window_and_beyond_the_length_never_enters_the_result(d
         for W in POISON_W:
             lens, firsts = poison_case(W, Sq)
             B, ld = len(lens), dev_lens(lens)
-            Kp, Vp = K[:B].clone(), V[:B].clone()
-            for b, (L, f) in enumerate(zip(lens, firsts)):
-                for lo, hi in ((0, f), (L, CAPACITY)):
-                    if kv == "bf16":
-                        Kp[b, :, lo:hi:2], Kp[b, :, lo + 1:hi:2] = NAN, INF
-                        Vp[b, :, lo:hi:2], Vp[b, :, lo + 1:hi:2] = -INF, NAN
-                    else:
-                        Kp[b, :, lo:hi:2], Kp[b, :, lo + 1:hi:2] = 0x7F, 0xFF
-                        Vp[b, :, lo:hi:2], Vp[b, :, lo + 1:hi:2] = 0xFF, 0x7F
+            Kp, Vp = poisoned_nan_inf(K[:B], V[:B], lens, firsts, kv == "fp8")
             assert any(f > 0 for f in firsts)
             Qd = queries(B, Sq, d).to(DEV)
             for causal in (False, True):
@@ -195,15 +183,6 @@ def test_poison_below_the_window_and_beyond_the_length_never_enters_the_result(d
 
 
 # ---- 5. poison below the window: paged; the same bits as the contiguous path ----
-def scatter(cache_, table, page):
-    """the pool [P, Hkv, page, d] that `table` [B, n] gathers back into `cache_` [B, Hkv, n * page, d]; P = B * n + 5"""
-    B, Hkv, cap, d = cache_.shape
-    n = cap // page
-    pool = torch.zeros((B * n + 5, Hkv, page, d), dtype=cache_.dtype, device=cache_.device)
-    pool[table.long().reshape(-1)] = cache_.reshape(B, Hkv, n, page, d).permute(0, 2, 1, 3, 4).reshape(B * n, Hkv, page, d)
-    return pool
-
-
 @pytest.mark.parametrize("kv", ["bf16", "fp8"])
 @pytest.mark.parametrize("page", [16, 64, 128])
 @pytest.mark.parametrize("d", [64, 128])
@@ -221,7 +200,7 @@ def test_pages_below_the_window_are_never_read_and_neither_are_their_table_entri
         lens, firsts = poison_case(W, Sq)
         B, ld = len(lens), dev_lens(lens)
         P = B * n + 5
-        table = torch.randperm(P, generator=torch.Generator().manual_seed(7400 + page + W))[:B * n].reshape(B, n).to(torch.int32).to(DEV)
+        table = random_table(B, n, 7400 + page + W).to(DEV)
         Kp, Vp = scatter(K[:B], table, page), scatter(V[:B], table, page)
         assert torch.equal(gather(Kp, table), K[:B])
         # every page wholly below first(b): NaN contents, and an entry nobody can follow
@@ -263,10 +242,10 @@ def test_fp8_sweep_against_the_dequantised_reference(d, Sq, descales):
         B, ld = len(lens), dev_lens(lens)
         Q = queries(B, Sq, d)
         Qd = Q.to(DEV)
-        table = torch.randperm(B * n + 5, generator=torch.Generator().manual_seed(7500 + W))[:B * n].reshape(B, n).to(torch.int32).to(DEV)
+        table = random_table(B, n, 7500 + W).to(DEV)
         Kp, Vp = scatter(K8.to(DEV)[:B], table, 64).view(F8), scatter(V8.to(DEV)[:B], table, 64).view(F8)
         for causal in (False, True):
-            refO, refL = reference_window(Q, Kf[:B], Vf[:B], lens, causal, W, scale)
+            refO, refL = reference(Q, Kf[:B], Vf[:B], lens, causal, W, scale=scale)
             for splits in SPLITS:
                 kw = dict(is_causal=causal, num_splits=splits, window=W, scale=scale, **extra)
                 O, lse = run(Qd, Kd[:B], Vd[:B], ld, **kw)
@@ -288,7 +267,7 @@ def test_a_strided_cache_and_every_output_type(d):
     Kd, Vd = ks.transpose(1, 2), vs.transpose(1, 2)
     assert not Kd.is_contiguous() and Kd.shape == (B, HKV, CAPACITY, d)
     for causal in (False, True):
-        refO, refL = reference_window(Q, K[:B], V[:B], lens, causal, W)
+        refO, refL = reference(Q, K[:B], V[:B], lens, causal, W)
         for splits in (0, 1, 3):
             kw = dict(is_causal=causal, num_splits=splits, window=W)
             O, lse = run(Qd, Kd, Vd, ld, **kw)
@@ -318,7 +297,7 @@ def test_graph_replay_follows_the_lengths_as_first_crosses_a_tile_start(d, paged
     Qd, ld = Q.to(DEV), dev_lens(lens)
     if paged:
         n = CAPACITY // page
-        table = torch.randperm(B * n + 5, generator=torch.Generator().manual_seed(7600))[:B * n].reshape(B, n).to(torch.int32).to(DEV)
+        table = random_table(B, n, 7600).to(DEV)
         Kp, Vp = scatter(Kd[:B], table, page), scatter(Vd[:B], table, page)
         call = lambda **kw: fa.flash_attention_decode_paged(Qd, Kp, Vp, table, ld, is_causal=True, num_splits=splits, window=W, **kw)
     else:
@@ -341,7 +320,7 @@ def test_graph_replay_follows_the_lengths_as_first_crosses_a_tile_start(d, paged
         eager = call(out_dtype=torch.float32)
         torch.cuda.synchronize()
         assert torch.equal(O, eager), step
-        refO, _ = reference_window(Q, K[:B], V[:B], live, True, W)
+        refO, _ = reference(Q, K[:B], V[:B], live, True, W)
         assert ((O.double().cpu() - refO).abs() <= 1e-3 + 1e-3 * refO.abs()).all(), step
     assert firsts == [127, 128, 129, 130]
 

@@ -174,8 +174,7 @@ def test_the_plan_follows_the_window():
 
 def test_the_reference_mask_equals_a_brute_force_double_loop():
     torch = pytest.importorskip("torch")
-    from decode_check import visible
-    from decode_window_check import first_visible, visible_window
+    from kv_cache_check import first_visible, visible
     for L in range(1, 41):
         for Sq in range(1, 6):
             for causal in (False, True):
@@ -186,7 +185,7 @@ def test_the_reference_mask_equals_a_brute_force_double_loop():
                         lo = max(limc - W, 0)
                         for k in range(L):
                             want[i, k] = lo <= k < (limc if causal else L)
-                    got = visible_window(L, Sq, causal, W)
+                    got = visible(L, Sq, causal, W)
                     assert got.dtype == torch.bool and torch.equal(got, want), (L, Sq, causal, W)
                     assert got.any(dim=1).all(), (L, Sq, causal, W)                     # every row sees at least one key
                     assert int(got.any(dim=0).nonzero()[0]) == first_visible(L, Sq, W)  # ... and row 0's left edge is the lowest
@@ -194,7 +193,7 @@ def test_the_reference_mask_equals_a_brute_force_double_loop():
                         assert (got.sum(dim=1) <= W).all()                             # at most the last W keys
                     if W >= L:
                         assert torch.equal(got, visible(L, Sq, causal)), (L, Sq, causal, W)
-                assert torch.equal(visible_window(L, Sq, causal, 0), visible(L, Sq, causal))
+                assert torch.equal(visible(L, Sq, causal, 0), visible(L, Sq, causal))
                 assert first_visible(L, Sq, 0) == 0
 
 

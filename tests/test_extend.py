@@ -1,6 +1,6 @@
 """GPU tests of flash_attention_extend / flash_attention_extend_paged: chunked prefill against the decode K/V caches, all four forms.
 Reference, mask, criterion (1e-3 + 1e-3 |ref| on O, 2e-4 + 2e-6 |ref| on the LSE, every element) and the paged / fp8 data are those of
-tests/decode_check.py; the score-noise criterion of the scale cases is tests/test_decode_edges.py's."""
+tests/kv_cache_check.py, the score-noise criterion of the scale cases included."""
 import functools
 
 import pytest
@@ -10,8 +10,8 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import CAP, DEV, F8, assert_close, dequantise, gather, paged_layout, quantise, randn, reference  # noqa: E402
-from test_decode_edges import SCALES, assert_close_with_score_noise  # noqa: E402
+from kv_cache_check import (CAP, DEV, F8, SCALES, assert_close, assert_close_with_score_noise, dequantise, gather, i32, paged_layout,  # noqa: E402
+                            quantise, randn, reference)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -27,10 +27,6 @@ def lens_of(Sq):
 
 def dev(*ts):
     return [t.to(DEV) for t in ts]
-
-
-def i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=DEV)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,7 @@
 """GPU tests of flash_attention_extend_varlen / flash_attention_extend_paged_varlen: ragged chunked prefill against the decode K/V
 caches -- every sequence its own number of new rows, Q / O packed by token.  Reference (per sequence, as a batch of one), mask and
-criterion (1e-3 + 1e-3 |ref| on O, 2e-4 + 2e-6 |ref| on the LSE, every element) are those of tests/decode_check.py; the score-noise
-criterion of the scale cases is tests/test_decode_edges.py's.  The property most tests lean on is the seam: a sequence's bits are
+criterion (1e-3 + 1e-3 |ref| on O, 2e-4 + 2e-6 |ref| on the LSE, every element) are those of tests/kv_cache_check.py, the score-noise
+criterion of the scale cases included.  The property most tests lean on is the seam: a sequence's bits are
 those of flash_attention_extend* (and, up to 16 rows, flash_attention_decode*) on that sequence alone under the same forced splits."""
 import ctypes
 import functools
@@ -14,8 +14,8 @@ torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
 from abi_decl import c_call  # noqa: E402
-from decode_check import CAP, DEV, F8, assert_close, dequantise, gather, quantise, randn, reference  # noqa: E402
-from test_decode_edges import SCALES, assert_close_with_score_noise  # noqa: E402
+from kv_cache_check import (CAP, DEV, F8, SCALES, assert_close, assert_close_with_score_noise, cu_of, dequantise, gather, i32,  # noqa: E402
+                            quantise, randn, reference_ragged)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -29,50 +29,13 @@ PAD = 37                                        # totalQ = cu[-1] + PAD: rows no
 SENTINEL = -123456.75
 
 
-def cu_of(sq):
-    cu = [0]
-    for s in sq:
-        cu.append(cu[-1] + s)
-    return cu
-
-
-def i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=DEV)
-
-
-def per_sequence_reference(Q, K, V, sq, lens, causal, scale=None):
-    """[(refO [H, sq_b, d], refL [H, sq_b]) or None for an idle slot]: decode_check.reference on every sequence as a batch of one;
-    Q [T, H, d] packed by token, K / V [B, Hkv, cap, d]"""
-    cu, out = cu_of(sq), []
-    for b, s in enumerate(sq):
-        if s == 0:
-            out.append(None)
-            continue
-        L = min(max(int(lens[b]), 1), K.shape[2])
-        O, lse = reference(Q[cu[b]:cu[b + 1]].transpose(0, 1)[None], K[b:b + 1], V[b:b + 1], [L], causal, scale)
-        out.append((O[0], lse[0]))
-    return out
-
-
-def packed(refs, sq, T, H, d):
-    """the per-sequence references as packed (O [T, H, d], LSE [H, T], owned bool [T])"""
-    O, lse, owned = torch.zeros(T, H, d, dtype=torch.float64), torch.zeros(H, T, dtype=torch.float64), torch.zeros(T, dtype=torch.bool)
-    cu = cu_of(sq)
-    for b, r in enumerate(refs):
-        if r is not None:
-            O[cu[b]:cu[b + 1]] = r[0].transpose(0, 1)
-            lse[:, cu[b]:cu[b + 1]] = r[1]
-            owned[cu[b]:cu[b + 1]] = True
-    return O, lse, owned
-
-
 @functools.lru_cache(maxsize=None)
 def mixed_case(d, G):
     """(Q [T, H, d], K, V, packed references {causal: (O, LSE, owned)}) of the mixed batch on the CPU, computed once"""
     T, H = sum(SQ) + PAD, HKV * G
     Q = randn((T, H, d), 101 + G, BF16)
     K, V = randn((len(SQ), HKV, CAPACITY, d), 102 + d, BF16), randn((len(SQ), HKV, CAPACITY, d), 103 + d, BF16)
-    refs = {c: packed(per_sequence_reference(Q, K, V, SQ, LENS, c), SQ, T, H, d) for c in (False, True)}
+    refs = {c: reference_ragged(Q, K, V, SQ, LENS, c) for c in (False, True)}
     return Q, K, V, refs
 
 
@@ -164,7 +127,7 @@ def test_seam_every_sequence_is_extend_on_that_sequence_alone(d, page, fp8):
     G = 4
     Q, K, V, table, ds, Kc, Vc, refK, refV = forms_case(d, G, page, fp8)
     cu_l, cu, lens = cu_of(SQ), i32(cu_of(SQ)), i32(LENS)
-    refs = per_sequence_reference(Q.cpu(), refK, refV, SQ, LENS, True)
+    refO, refL, _ = reference_ragged(Q.cpu(), refK, refV, SQ, LENS, True)
     for splits in (1, 3):
         kw = dict(is_causal=True, out_dtype=torch.float32, num_splits=splits, return_lse=True, **ds)
         O, lse = call(Q, K, V, table, cu, lens, **kw)
@@ -191,7 +154,8 @@ def test_seam_every_sequence_is_extend_on_that_sequence_alone(d, page, fp8):
                     Od, ld = fa.flash_attention_decode_paged(q, K, V, table[b:b + 1], one, **kw)
                 torch.cuda.synchronize()
                 assert torch.equal(got, Od[0]) and torch.equal(gl, ld[0]), f"sequence {b} ({s} rows) differs from decode, splits {splits}"
-            assert_close(got, gl, *refs[b], f"form page {page} fp8 {fp8} d {d} sequence {b} splits {splits}")
+            assert_close(got, gl, refO[cu_l[b]:cu_l[b + 1]].transpose(0, 1), refL[:, cu_l[b]:cu_l[b + 1]],
+                         f"form page {page} fp8 {fp8} d {d} sequence {b} splits {splits}")
 
 
 @pytest.mark.parametrize("fp8,page", [(False, None), (True, 16)])
@@ -222,7 +186,7 @@ def lookup_case(sq, d=64, G=4, cap=256, seed=121, extra=0):
     B, H, T = len(sq), HKV * G, max(sum(sq), 1) + extra
     lens = [1 + (37 * b + 11) % cap for b in range(B)]
     Q, K, V = randn((T, H, d), seed, BF16), randn((B, HKV, cap, d), seed + 1, BF16), randn((B, HKV, cap, d), seed + 2, BF16)
-    ref = packed(per_sequence_reference(Q, K, V, sq, lens, True), sq, T, H, d)
+    ref = reference_ragged(Q, K, V, sq, lens, True)
     return Q.to(DEV), K.to(DEV), V.to(DEV), i32(cu_of(sq)), i32(lens), ref
 
 
@@ -411,7 +375,7 @@ def test_mixed_batch_steps_as_one_graph():
         torch.cuda.synchronize()
         assert lens.tolist() == pos
         K64, V64 = gather(dequantise(Kp.cpu(), kd.cpu()), table.cpu()), gather(dequantise(Vp.cpu(), vd.cpu()), table.cpu())
-        refO, _, owned = packed(per_sequence_reference(q, K64, V64, sq, pos, True), sq, T, H, d)
+        refO, _, owned = reference_ragged(q, K64, V64, sq, pos, True)
         O = Os.double().cpu()
         err, tol = (O - refO).abs()[owned], (1e-3 + 1e-3 * refO.abs())[owned]
         print(f"step {it}: rows {sq}, worst O error / tolerance {(err / tol).max().item():.3f}")

@@ -1,7 +1,8 @@
 """GPU tests of the ragged call with a sliding window (flash_attention_extend_varlen_window / flash_attention_extend_paged_varlen_window,
-the Python fronts and the C entry points of those names), all four cache forms.  Reference: decode_window_check.reference_window per sequence, as a batch of one; criterion: decode_check.assert_close.  The
-seam carries most of the weight: a sequence's bits are those of flash_attention_extend_window(window=W) on that sequence alone (and, up to 16
-rows, flash_attention_decode(window=W)) under the same forced splits."""
+the Python fronts and the C entry points of those names), all four cache forms.  Reference: kv_cache_check.reference_ragged (every
+sequence as a batch of one); criterion: kv_cache_check.assert_close.  The seam carries most of the weight: a sequence's bits are those
+of flash_attention_extend_window(window=W) on that sequence alone (and, up to 16 rows, flash_attention_decode(window=W)) under the same
+forced splits."""
 import functools
 
 import pytest
@@ -11,9 +12,8 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import DEV, F8, assert_close, dequantise, gather, quantise, randn  # noqa: E402
-from decode_window_check import first_visible  # noqa: E402
-from extend_window_check import cu_of, packed, per_sequence_reference_window, random_table, scatter  # noqa: E402
+from kv_cache_check import (DEV, F8, assert_close, cu_of, dequantise, first_visible, gather, i32, quantise, randn, random_table,  # noqa: E402
+                            reference_ragged, scatter)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -29,10 +29,6 @@ PAD = 23                                        # totalQ = cu[-1] + PAD: rows no
 SENTINEL = -123456.75
 
 
-def i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=DEV)
-
-
 @functools.lru_cache(maxsize=None)
 def batch(d):
     """(Q [T, H, d], K, V [B, HKV, CAPACITY, d]) of the mixed batch on the CPU"""
@@ -43,9 +39,9 @@ def batch(d):
 
 @functools.lru_cache(maxsize=None)
 def references(d, fp8, causal, W):
-    """the per-sequence float64 references of the batch against the bf16 cache or the dequantised fp8 one"""
+    """the packed float64 reference (O, LSE, owned) of the batch against the bf16 cache or the dequantised fp8 one"""
     Q, refK, refV = forms(d, None, fp8)[-3:]
-    return per_sequence_reference_window(Q, refK, refV, SQ, LENS, causal, W)
+    return reference_ragged(Q, refK, refV, SQ, LENS, causal, W)
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,7 +79,7 @@ def test_parity_mixed_batch_and_rows_no_sequence_owns(d, causal):
     T = Q.shape[0]
     cu, lens = i32(cu_of(SQ)), i32(LENS)
     for W in WINDOWS:
-        refO, refL, owned = packed(references(d, False, causal, W), SQ, T, H, d)
+        refO, refL, owned = references(d, False, causal, W)
         for splits in (0, 1, 2, 3, 5):
             O = torch.full((T, H, d), SENTINEL, dtype=torch.float32, device=DEV)
             out, lse = fa.flash_attention_extend_varlen_window(Qd, Kd, Vd, cu, lens, is_causal=causal, num_splits=splits, window=W, O=O,
@@ -106,7 +102,7 @@ def test_seam_every_sequence_is_the_windowed_extend_on_that_sequence_alone(d, pa
     Q, K, V, table, ds, Kc, Vc, _, _, _ = forms(d, page, fp8)
     cu_l, cu, lens = cu_of(SQ), i32(cu_of(SQ)), i32(LENS)
     for W in WINDOWS:
-        refs = references(d, fp8, True, W)
+        refO, refL, _ = references(d, fp8, True, W)
         for splits in (1, 3):
             kw = dict(is_causal=True, out_dtype=torch.float32, num_splits=splits, return_lse=True, window=W, **ds)
             O, lse = call(Q, K, V, table, cu, lens, **kw)
@@ -133,7 +129,8 @@ def test_seam_every_sequence_is_the_windowed_extend_on_that_sequence_alone(d, pa
                         Od, ld = fa.flash_attention_decode_paged(q, K, V, table[b:b + 1], one, **kw)
                     torch.cuda.synchronize()
                     assert torch.equal(got, Od[0]) and torch.equal(gl, ld[0]), f"sequence {b} ({s} rows) differs from decode, W {W} splits {splits}"
-                assert_close(got, gl, *refs[b], f"form page {page} fp8 {fp8} d {d} W {W} sequence {b} splits {splits}")
+                assert_close(got, gl, refO[cu_l[b]:cu_l[b + 1]].transpose(0, 1), refL[:, cu_l[b]:cu_l[b + 1]],
+                             f"form page {page} fp8 {fp8} d {d} W {W} sequence {b} splits {splits}")
 
 
 @pytest.mark.parametrize("fp8,page", [(False, None), (True, 16)])
@@ -240,7 +237,7 @@ def test_three_steps_as_one_replayed_graph_with_first_crossing_a_tile_start():
         torch.cuda.synchronize()
         assert lens.tolist() == pos
         firsts.append(first_visible(pos[0], sq[0], W))
-        refO, _, owned = packed(per_sequence_reference_window(q, Kc.cpu(), Vc.cpu(), sq, pos, True, W), sq, T, H, d)
+        refO, _, owned = reference_ragged(q, Kc.cpu(), Vc.cpu(), sq, pos, True, W)
         O = Os.double().cpu()
         err, tol = (O - refO).abs()[owned], (1e-3 + 1e-3 * refO.abs())[owned]
         print(f"step {it}: rows {sq}, worst O error / tolerance {(err / tol).max().item():.3f}")

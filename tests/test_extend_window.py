@@ -1,8 +1,8 @@
 """GPU tests of windowed chunked prefill (flash_attention_extend_window / flash_attention_extend_paged_window, the Python fronts and the
 C entry points of those names) over all four cache forms: contiguous / paged x bf16 / fp8.
 
-Criterion: decode_check.assert_close against decode_window_check.reference_window (float64 explicit softmax over the keys
-visible_window lets each row see) -- every element of the fp32 O within 1e-3 + 1e-3 |ref|, the LSE within 2e-4 + 2e-6 |ref|.
+Criterion: kv_cache_check.assert_close against kv_cache_check.reference (float64 explicit softmax over the keys
+kv_cache_check.visible lets each row see) -- every element of the fp32 O within 1e-3 + 1e-3 |ref|, the LSE within 2e-4 + 2e-6 |ref|.
 Capacity 640 = five 128-key tiles, H = 8 / Hkv = 2 plus G = 1 cases, one sequence per length.  Beside parity: the per-row-block tile
 start (single softmax weights on both sides of a row's left edge in every row block; poison below first(b) and beyond the length), the
 seams bit for bit (decode for Sq <= 16; the un-windowed call for no window and a window no shorter than the capacity; paged against
@@ -17,9 +17,9 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-from decode_check import DEV, F8, assert_close, dequantise, gather, quantise, randn  # noqa: E402
-from decode_window_check import first_visible, reference_window  # noqa: E402
-from extend_window_check import block_range, random_table, scatter  # noqa: E402
+from extend_window_check import block_range  # noqa: E402
+from kv_cache_check import (DEV, F8, assert_close, dequantise, first_visible, gather, i32 as dev_lens, poisoned_nan_inf, quantise,  # noqa: E402
+                            randn, random_table, reference, scatter)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -28,7 +28,7 @@ H, HKV = 8, 2
 SQS = (17, 40, 64, 65, 130, 200)
 WINDOWS = (1, 16, 17, 127, 128, 129, 300, 640)
 SPLITS = (0, 1, 2, 3, 5)          # 0: the library's choice; 5: more than most windows here have tiles, so some splits are empty
-NAN, INF = float("nan"), float("inf")
+NAN = float("nan")
 BMAX = 6
 
 
@@ -61,10 +61,6 @@ def queries(B, Sq, d, heads=H):
     return randn((B, heads, Sq, d), 8300 + 16 * Sq + d + heads, BF16)
 
 
-def dev_lens(lens):
-    return torch.tensor(lens, dtype=torch.int32, device=DEV)
-
-
 def run(Q, K, V, ld, **kw):
     O, lse = fa.flash_attention_extend_window(Q, K, V, ld, out_dtype=torch.float32, return_lse=True, **kw)
     torch.cuda.synchronize()
@@ -93,7 +89,7 @@ def test_parity_against_float64(d, Sq, causal):
         B = len(lens)
         assert B <= BMAX
         Q = queries(B, Sq, d)
-        refO, refL = reference_window(Q, K[:B], V[:B], lens, causal, W)
+        refO, refL = reference(Q, K[:B], V[:B], lens, causal, W)
         Qd, ld = Q.to(DEV), dev_lens(lens)
         for splits in SPLITS:
             O, lse = run(Qd, Kd[:B], Vd[:B], ld, is_causal=causal, num_splits=splits, window=W)
@@ -112,7 +108,7 @@ def test_parity_with_one_query_head_per_kv_head(d):
             Q = queries(B, Sq, d, HKV)
             Qd, ld = Q.to(DEV), dev_lens(lens)
             for causal in (False, True):
-                refO, refL = reference_window(Q, K[:B], V[:B], lens, causal, W)
+                refO, refL = reference(Q, K[:B], V[:B], lens, causal, W)
                 for splits in SPLITS:
                     O, lse = run(Qd, Kd[:B], Vd[:B], ld, is_causal=causal, num_splits=splits, window=W)
                     assert_close(O, lse, refO, refL, f"G 1 d {d} Sq {Sq} causal {causal} W {W} splits {splits}")
@@ -145,7 +141,7 @@ def test_single_weights_on_both_sides_of_the_left_edge_in_every_row_block(d, G, 
         V[0, :, w0 + torch.arange(d), torch.arange(d)] = 1.0
         Vd = V.to(DEV)
         for causal in (False, True):
-            refO, refL = reference_window(Q, K[:1], V, [L], causal, W)
+            refO, refL = reference(Q, K[:1], V, [L], causal, W)
             keys = torch.arange(w0, w0 + d)
             hidden = (keys < lo) | (keys >= (limc if causal else L))
             assert hidden[:d // 2].all() and not hidden[d // 2] and (refO[0, :, i, hidden] == 0).all() and (refO[0, :, i, ~hidden] > 0).all()
@@ -154,19 +150,6 @@ def test_single_weights_on_both_sides_of_the_left_edge_in_every_row_block(d, G, 
                 assert (O[0, :, i, hidden.to(DEV)] == 0.0).all(), (i, causal, splits)
                 assert (O[0, :, i, (~hidden).to(DEV)] > 0.0).all(), (i, causal, splits)
                 assert_close(O, lse, refO, refL, f"pairs: d {d} G {G} Sq {Sq} W {W} L {L} row {i} causal {causal} splits {splits}")
-
-
-def poisoned(K, V, lens, firsts, fp8):
-    Kp, Vp = K.clone(), V.clone()
-    for b, (L, f) in enumerate(zip(lens, firsts)):
-        for lo, hi in ((0, f), (L, CAPACITY)):
-            if fp8:
-                Kp[b, :, lo:hi:2], Kp[b, :, lo + 1:hi:2] = 0x7F, 0xFF
-                Vp[b, :, lo:hi:2], Vp[b, :, lo + 1:hi:2] = 0xFF, 0x7F
-            else:
-                Kp[b, :, lo:hi:2], Kp[b, :, lo + 1:hi:2] = NAN, INF
-                Vp[b, :, lo:hi:2], Vp[b, :, lo + 1:hi:2] = -INF, NAN
-    return Kp, Vp
 
 
 @pytest.mark.parametrize("kv", ["bf16", "fp8"])
@@ -188,7 +171,7 @@ def test_poison_below_first_and_beyond_the_length_never_enters_the_result(d, kv)
         firsts = [first_visible(L, Sq, W) for L in lens]
         assert any(f > 0 for f in firsts)
         B, ld = len(lens), dev_lens(lens)
-        Kp, Vp = poisoned(K[:B], V[:B], lens, firsts, fp8)
+        Kp, Vp = poisoned_nan_inf(K[:B], V[:B], lens, firsts, fp8)
         Qd = queries(B, Sq, d, heads).to(DEV)
         for causal in (False, True):
             for splits in (0, 1, 3, 5):
@@ -303,7 +286,7 @@ def test_fp8_against_the_dequantised_reference(d, descales):
             table = random_table(B, n, 8500 + W).to(DEV)
             Kp, Vp = scatter(K8.to(DEV)[:B], table, 64).view(F8), scatter(V8.to(DEV)[:B], table, 64).view(F8)
             for causal in (False, True):
-                refO, refL = reference_window(Q, Kf[:B], Vf[:B], lens, causal, W, scale)
+                refO, refL = reference(Q, Kf[:B], Vf[:B], lens, causal, W, scale=scale)
                 for splits in (0, 1, 3):
                     kw = dict(is_causal=causal, num_splits=splits, window=W, scale=scale, **extra)
                     got = run(Qd, Kd[:B], Vd[:B], ld, **kw)

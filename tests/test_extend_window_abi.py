@@ -2,7 +2,7 @@
 _extend_paged_varlen_window, flash_attention_extend_plan_window, flash_attention_extend_varlen_plan_window) at the C ABI and in the
 binding: the six symbols with their declared parameter lists, every refusal of the un-windowed sibling returned with the same code at
 windows 0 / 128 / 5000 (fake aligned host pointers: no GPU is touched; no call here is valid as a whole), the plan, and the Python
-model of the per-row-block tile range (extend_window_check.block_range) against a brute-force hull over visible_window."""
+model of the per-row-block tile range (extend_window_check.block_range) against a brute-force hull over kv_cache_check.visible."""
 import ctypes
 
 import pytest
@@ -171,7 +171,7 @@ def test_the_plan_follows_the_window(ragged):
 
 
 def test_the_block_range_model_is_the_hull_of_the_tiles_a_block_sees():
-    """extend_window_check.block_range against the brute-force hull over visible_window: equality for Sq > 16, decode's range for
+    """extend_window_check.block_range against the brute-force hull over kv_cache_check.visible: equality for Sq > 16, decode's range for
     Sq <= 16 (which holds the hull).  Includes the issue's example"""
     pytest.importorskip("torch")
     from extend_window_check import block_hull, block_range, decode_range, row_edges

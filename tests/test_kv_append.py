@@ -16,57 +16,15 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-import decode_window_check as dwc  # noqa: E402
 import kv_append_check as kc  # noqa: E402
-from decode_check import DEV, F8, assert_close, dequantise, gather  # noqa: E402
+from kv_append_check import SENT, as_cache, descales, new_rows, same, sentinel  # noqa: E402
+from kv_cache_check import DEV, assert_close, dequantise, gather, i32 as lens_tensor, reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf, i16, u8, i32 = torch.bfloat16, torch.int16, torch.uint8, torch.int32
 HKV = 2
-SENT = {u8: 0xA5, i16: 0x5A5A}        # (0xA5 is a finite e4m3fn code, 0x5A5A a finite bf16: never what a NaN compares as)
-
-
-def sentinel(shape, fp8, device="cpu"):
-    dt = u8 if fp8 else i16
-    return torch.full(shape, SENT[dt], dtype=dt, device=device)
-
-
-def as_cache(t):
-    """the integer tensor as the call takes it"""
-    return t.view(F8) if t.dtype == u8 else t.view(bf)
-
-
-def new_rows(shape, seed):
-    """bf16 N(0, 1) scaled so that some values saturate at descales near 1 / 64, with the special values among them"""
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(shape, generator=g) * 3).to(bf)
-    flat = x.reshape(-1)
-    special = torch.tensor([float("nan"), float("inf"), -float("inf"), -0.0, 0.0, 1e-30, -1e-30, 448.0, 464.0, 3e38], dtype=bf)
-    flat[:special.numel()] = special
-    flat[-special.numel():] = special.flip(0)
-    return x
-
-
-def descales(seed, fp8):
-    if not fp8:
-        return None, None
-    g = torch.Generator().manual_seed(seed)
-    kd, vd = (torch.rand(HKV, generator=g) * 0.05 + 0.01).float(), (torch.rand(HKV, generator=g) * 2 + 0.5).float()
-    return kd, vd
-
-
-def same(got, want):
-    """device cache against the reference's: bits, NaN bytes of an fp8 cache by class"""
-    got = got.cpu()
-    return kc.same_bytes(got, want) if want.dtype == u8 else torch.equal(got, want)
-
-
 def dev(t):
     return None if t is None else t.to(DEV)
-
-
-def lens_tensor(lens):
-    return None if lens is None else torch.tensor(lens, dtype=i32, device=DEV)
 
 
 # ---- 1. every bf16 value ----
@@ -319,7 +277,7 @@ def test_decode_step_in_one_graph(fp8, Sq, d, window):
         # ... and the float64 reference on the values the cache holds
         Kg, Vg = gather(refK, table), gather(refV, table)
         Kf, Vf = (dequantise(Kg, kd), dequantise(Vg, vd)) if fp8 else (Kg.view(bf), Vg.view(bf))
-        refO, refL = dwc.reference_window(Q, Kf, Vf, now, True, window)
+        refO, refL = reference(Q, Kf, Vf, now, True, window)
         assert_close(O, lse, refO, refL, f"decode step {t} fp8 {fp8} Sq {Sq} d {d} window {window} lengths {now}")
     assert now[0] > 128 >= start[0] and now[1] > 16 >= start[1]          # the steps crossed the tile and a page boundary
 

@@ -13,56 +13,22 @@ torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
 import kv_append_check as kc  # noqa: E402
-from decode_check import DEV, F8  # noqa: E402
+from kv_append_check import SENT, as_cache, new_rows, same  # noqa: E402
+from kv_cache_check import DEV, cu_of, i32 as t32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf, i16, u8, i32 = torch.bfloat16, torch.int16, torch.uint8, torch.int32
 HKV = 2
-SENT = {u8: 0xA5, i16: 0x5A5A}        # (a finite e4m3fn code, a finite bf16: never what a NaN compares as)
 PAD = 9                               # tokens beyond cu[-1]: not read
 
 
 def sentinel(shape, fp8):
-    dt = u8 if fp8 else i16
-    return torch.full(shape, SENT[dt], dtype=dt, device=DEV)
-
-
-def as_cache(t):
-    return t.view(F8) if t.dtype == u8 else t.view(bf)
-
-
-def new_rows(shape, seed):
-    """bf16 N(0, 1) x 3 with the special values among them (some saturate at descales near 1 / 64)"""
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(shape, generator=g) * 3).to(bf)
-    flat = x.reshape(-1)
-    special = torch.tensor([float("nan"), float("inf"), -float("inf"), -0.0, 0.0, 1e-30, -1e-30, 448.0, 464.0, 3e38], dtype=bf)
-    flat[:special.numel()] = special
-    flat[-special.numel():] = special.flip(0)
-    return x
+    return kc.sentinel(shape, fp8, DEV)
 
 
 def descales(seed, fp8):
-    if not fp8:
-        return {}
-    g = torch.Generator().manual_seed(seed)
-    return dict(k_descale=(torch.rand(HKV, generator=g) * 0.05 + 0.01).float().to(DEV), v_descale=(torch.rand(HKV, generator=g) * 2 + 0.5).float().to(DEV))
-
-
-def same(got, want):
-    """bits; NaN bytes of an fp8 cache by class"""
-    return kc.same_bytes(got, want) if want.dtype == u8 else torch.equal(got.cpu(), want.cpu())
-
-
-def cu_of(sq):
-    cu = [0]
-    for s in sq:
-        cu.append(cu[-1] + s)
-    return cu
-
-
-def t32(x):
-    return torch.tensor(x, dtype=i32, device=DEV)
+    kd, vd = kc.descales(seed, fp8)
+    return dict(k_descale=kd.to(DEV), v_descale=vd.to(DEV)) if fp8 else {}
 
 
 def both_ways(sq, lens, cap, d, fp8, page, seed, table=None, strided=False):

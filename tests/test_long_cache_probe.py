@@ -1,6 +1,6 @@
 """CPU proof of the long-cache instrument (tests/long_cache_probe.py) on a few thousand keys whose codes, through `base`, are the 24-bit
-ones of a long cache: (a) ranges() is decode_window_check.visible_window, (b) the closed forms equal the suite's float64 references
-(decode_window_check.reference_window, extend_window_check.per_sequence_reference_window) to 1e-12 -- decode, chunked prefill, ragged,
+ones of a long cache: (a) ranges() is kv_cache_check.visible, (b) the closed forms equal the suite's float64 references
+(kv_cache_check.reference, reference_ragged) to 1e-12 -- decode, chunked prefill, ragged,
 W = 0 / 100 / 4096, len < Sq, empty sequences, all four cache forms --, (c) the fp32 emulation of csrc/decode_bf16.hip.h returns the
 expected bits under 1, 3 and 64 splits and stays within 0.7 of the LSE bound, (d) every wrong kernel of long_cache_probe.MUTANTS is refused
 on a named row, (e) for every case tests/test_long_cache.py runs on the GPU both sides of every split boundary of every row block are
@@ -16,8 +16,8 @@ import __graft_entry__ as entry
 
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
-import decode_window_check as dwc  # noqa: E402
 import extend_window_check as ewc  # noqa: E402
+import kv_cache_check as kv  # noqa: E402
 import long_cache_probe as cp  # noqa: E402
 
 BASE = 2 ** 24 - 8192
@@ -88,7 +88,7 @@ def test_ranges_are_the_visible_windows(causal, W):
         lo, lim = cp.ranges(L, Sq, causal, W)
         elo, ehi = ewc.row_edges(L, Sq, causal, W)
         assert lo.tolist() == elo and (lim - 1).tolist() == ehi, (L, Sq)
-        assert int(dwc.visible_window(L, Sq, causal, W).sum()) == int((lim - lo).sum())
+        assert int(kv.visible(L, Sq, causal, W).sum()) == int((lim - lo).sum())
     x = np.arange(0, 700)
     for a in (64, 16):
         assert (cp.anchors_below(x, a) == np.cumsum(np.concatenate([[0], cp.is_anchor(x, a)[:-1]]))).all()
@@ -103,10 +103,11 @@ def test_closed_forms_are_the_float64_truth(name):
         exp = cp.expected(spec, q, torch.float32)
         if spec.kind == "varlen":
             sq = [s for s, _ in spec.seqs]
-            refs = ewc.per_sequence_reference_window(q["Q"].float(), K, V, sq, [L for _, L in spec.seqs], spec.causal, spec.W, scale)
+            O, L, owned = kv.reference_ragged(q["Q"].float(), K, V, sq, [L for _, L in spec.seqs], spec.causal, spec.W, scale=scale)
+            refs = [(O[a:b].transpose(0, 1), L[:, a:b]) if owned[a:b].any() else None for a, b in zip(kv.cu_of(sq), kv.cu_of(sq)[1:])]
             assert [r is None for r in refs] == [e is None for e in exp]
         else:
-            O, L = dwc.reference_window(q["Q"].float(), K, V, [L for _, L in spec.seqs], spec.causal, spec.W, scale)
+            O, L = kv.reference(q["Q"].float(), K, V, [L for _, L in spec.seqs], spec.causal, spec.W, scale=scale)
             refs = list(zip(O, L))
         hidden = 0
         for e, r in zip(exp, refs):

@@ -11,7 +11,7 @@ arena must be untouched outside the outputs, and the inputs unchanged.  Two plac
 512: a difference can only come from the workspace contents or a store out of bounds) and `offset` (tensors at 16 mod 256, side inputs
 at 4 mod 16: a difference that shows only here is an address formed wrongly).  The route is asserted through plan_ex / the decode
 plans, and each arena result is also held to the suite's float64 references with their own bounds (weight_probe.forward_truth,
-decode_check.assert_close, grad_check.assert_grads, kv_append_check.append): no new tolerance."""
+kv_cache_check.assert_close, grad_check.assert_grads, kv_append_check.append): no new tolerance."""
 import functools
 import math
 
@@ -23,9 +23,7 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 import arena as ar  # noqa: E402
-import decode_check as dc  # noqa: E402
-import decode_window_check as dwc  # noqa: E402
-import extend_window_check as ewc  # noqa: E402
+import kv_cache_check as kv  # noqa: E402
 import grad_check as gc  # noqa: E402
 import memory_contract as mc  # noqa: E402
 import weight_probe as wp  # noqa: E402
@@ -194,8 +192,8 @@ def cache_of(B, d, page, fp8):
 
 
 def judge_uniform(cache, Q, causal, W):
-    refO, refL = dwc.reference_window(Q, cache.refK, cache.refV, LENS, causal, W)
-    return lambda v, what: dc.assert_close(v["O"], v["lse"], refO, refL, what)
+    refO, refL = kv.reference(Q, cache.refK, cache.refV, LENS, causal, W)
+    return lambda v, what: kv.assert_close(v["O"], v["lse"], refO, refL, what)
 
 
 def rounded_once(plain32):
@@ -230,18 +228,17 @@ def test_split_kv_ragged(d, page, fp8):
     """rows (5, 0, 130, 17) and 23 rows behind them that no sequence owns: those must come back as the 0xFF they went in as"""
     B, H = len(RAGGED_ROWS), mc.HKV * mc.G
     cache = cache_of(B, d, page, fp8)
-    cu = ewc.cu_of(RAGGED_ROWS)
+    cu = kv.cu_of(RAGGED_ROWS)
     T = cu[-1] + UNOWNED
     Q = mc.randn((T, H, d), 700 + d)
     for W in WINDOWS:
         causal = W == 0
-        refs = ewc.per_sequence_reference_window(Q, cache.refK, cache.refV, RAGGED_ROWS, RAGGED_LENS, causal, W)
-        refO, refL, owned = ewc.packed(refs, RAGGED_ROWS, T, H, d)
+        refO, refL, owned = kv.reference_ragged(Q, cache.refK, cache.refV, RAGGED_ROWS, RAGGED_LENS, causal, W)
         assert int(owned.sum()) == cu[-1] and not bool(owned[cu[-1]:].any())
 
         def judge(v, what):
             O, lse = v["O"].cpu(), v["lse"].cpu()
-            dc.assert_close(O[owned], lse[:, owned], refO[owned], refL[:, owned], what)
+            kv.assert_close(O[owned], lse[:, owned], refO[owned], refL[:, owned], what)
             assert bool((O[~owned].view(torch.int32) == -1).all()) and bool((lse[:, ~owned].view(torch.int32) == -1).all()), \
                 f"{what}: a row that no sequence owns was written"
 
@@ -269,7 +266,7 @@ def test_cache_append(ragged, page, fp8):
     d, B = 128 if fp8 else 64, 4
     base = cache_of(B, d, page, fp8)
     if ragged:
-        cu, lens = ewc.cu_of(RAGGED_ROWS), RAGGED_LENS
+        cu, lens = kv.cu_of(RAGGED_ROWS), RAGGED_LENS
         Knew, Vnew = mc.randn((cu[-1] + UNOWNED, mc.HKV, d), 801), mc.randn((cu[-1] + UNOWNED, mc.HKV, d), 802)
     else:
         cu, lens = None, APPEND_LENS
@@ -293,7 +290,7 @@ def test_one_workspace_serves_several_calls():
     next one finds.  Every result is bit for bit its own fresh-workspace result"""
     d, H = 128, mc.HKV * mc.G
     c3, c4 = cache_of(3, d, 16, True), cache_of(4, d, None, False)
-    cu = ewc.cu_of(RAGGED_ROWS)
+    cu = kv.cu_of(RAGGED_ROWS)
     Q, K, V, dO = backward_inputs(1, 4, 2, 100, 300, d, 901)
     calls = {
         "decode": mc.split_kv_call("decode", c3, mc.randn((3, H, 5, d), 911), LENS, True, 3, 0),

@@ -3,7 +3,7 @@ bf16 and fp8 caches.  One sequence per length {1, Sq, 127, 128, 129, 640, capaci
 window of its own: over the end of the length -- which holds the bottom-right diagonal of every packed row -- and over every tile seam
 below it, which are the split boundaries of every split count run (1, 3, 64 and the planned one; wp.decode_seams asserts it from
 decode_plan) and, for pages of 16 and 128 keys, page seams.  Every element of O is one weight, held to the bf16 line of the fuzz sweep's
-bound against decode_check.reference; keys past the length and pairs under the mask must read exactly 0.0.  One long case: 70 000 keys
+bound against kv_cache_check.reference; keys past the length and pairs under the mask must read exactly 0.0.  One long case: 70 000 keys
 x 2 rows, windows over the last split boundary and the end.  CPU proof of the instrument: tests/test_weight_probe.py."""
 import functools
 

@@ -4,7 +4,7 @@ cache append with the rotary embedding of K and of the step's Q fused in.
 Everything is a comparison of BITS with tests/rope_check.py, the header's contract in torch on the CPU (held against exact rational
 arithmetic and against nine wrong implementations in tests/test_rope_check.py): Qout, the K cache and the V cache as integers, NaN
 codes by class, no tolerance -- but in the end-to-end steps, whose O and LSE are held bit for bit against the same attention call on
-the reference's tensors and, by decode_check.assert_close, against float64 attention on them.  Caches and Qout are pre-filled with a
+the reference's tensors and, by kv_cache_check.assert_close, against float64 attention on them.  Caches and Qout are pre-filled with a
 sentinel and compared WHOLE, padding and spare pages included, so what must not be written is checked with what must.  The calls go
 through the C ABI by name (tests/rope_call.py); the attention calls of the end-to-end steps through the binding."""
 import pytest
@@ -14,60 +14,17 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 
-import decode_window_check as dwc  # noqa: E402
 import kv_append_check as kc  # noqa: E402
+from kv_append_check import SENT, as_cache, descales, sentinel  # noqa: E402
 import rope_call as call  # noqa: E402
 import rope_check as rc  # noqa: E402
-from decode_check import DEV, F8, assert_close, dequantise, gather  # noqa: E402
+from kv_cache_check import DEV, assert_close, dequantise, gather, i32 as lens_tensor, reference  # noqa: E402
+from rope_check import check, qsent, rows, table_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf, i16, u8, i32 = torch.bfloat16, torch.int16, torch.uint8, torch.int32
-SENT = {u8: 0xA5, i16: 0x5A5A}        # finite in e4m3fn and in bf16
-QSENT = 0x4B4B                        # ... and Qout's
-
-
-def sentinel(shape, fp8, device="cpu"):
-    dt = u8 if fp8 else i16
-    return torch.full(shape, SENT[dt], dtype=dt, device=device)
-
-
-def qsent(shape, device="cpu"):
-    return torch.full(shape, QSENT, dtype=i16, device=device).view(bf)
-
-
-def as_cache(t):
-    return t.view(F8) if t.dtype == u8 else t.view(bf)
-
-
-def rows(shape, seed, special=False):
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(shape, generator=g) * 3).to(bf)
-    if special:       # NaN payloads, infinities, -0, tiny and huge values among them
-        flat = x.reshape(-1)
-        s = torch.tensor([0x7FC1, -0x0040 + 0x0001, 0x7F80, -0x0080, -0x8000, 0x0000, 0x0001, -0x7FFF, 0x43E0, 0x7F7F], dtype=i32).to(i16).view(bf)
-        flat[:s.numel()] = s
-        flat[-s.numel():] = s.flip(0)
-    return x
-
-
-def descales(seed, fp8, Hkv):
-    if not fp8:
-        return None, None
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(Hkv, generator=g) * 0.05 + 0.01).float(), (torch.rand(Hkv, generator=g) * 2 + 0.5).float()
-
-
 def dev(t):
     return None if t is None else t.to(DEV)
-
-
-def lens_tensor(lens):
-    return None if lens is None else torch.tensor(lens, dtype=i32, device=DEV)
-
-
-def table_of(B, n, spare, seed):
-    P = B * n + spare
-    return P, torch.randperm(P, generator=torch.Generator().manual_seed(seed))[:B * n].reshape(B, n).to(i32)
 
 
 def run(Q, Kn, Vn, Kc, Vc, cs, lens, il, kd, vd, table=None, Qo=None):
@@ -78,11 +35,6 @@ def run(Q, Kn, Vn, Kc, Vc, cs, lens, il, kd, vd, table=None, Qo=None):
     call.launch(dev(Q), dev(Kn), dev(Vn), Qo, Kd, Vd, dev(cs), lens_tensor(lens), il, dev(kd), dev(vd), dev(table))
     torch.cuda.synchronize()
     return Qo, Kd, Vd
-
-
-def check(got, want, what):
-    for name, g, w in zip(("Qout", "Kcache", "Vcache"), got, want):
-        rc.assert_same(f"{what}: {name}", g, w)
 
 
 def lengths(Sq, cap, page):
@@ -381,7 +333,7 @@ def test_decode_step_in_one_graph(fp8, Sq, d, il):
         # ... and float64 attention on the values they hold
         Kg, Vg = gather(refK, bt), gather(refV, bt)
         Kf, Vf = (dequantise(Kg, kd), dequantise(Vg, vd)) if fp8 else (Kg.view(bf), Vg.view(bf))
-        refO, refL = dwc.reference_window(Qr, Kf, Vf, now, True, 0)
+        refO, refL = reference(Qr, Kf, Vf, now, True, 0)
         assert_close(O, lse, refO, refL, f"rope decode step {t} fp8 {fp8} Sq {Sq} d {d} lengths {now}")
     assert now[0] > 128 >= start[0] and now[1] > 16 >= start[1]          # the steps crossed the tile and a page boundary
 

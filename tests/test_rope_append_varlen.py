@@ -13,9 +13,9 @@ fa = entry.load_package()
 import kv_append_check as kc  # noqa: E402
 import rope_call as call  # noqa: E402
 import rope_check as rc  # noqa: E402
-from decode_check import DEV, F8, assert_close, dequantise, gather  # noqa: E402
-from test_extend_varlen import cu_of, packed, per_sequence_reference  # noqa: E402
-from test_rope_append import as_cache, bits, check, descales, dev, lens_tensor, qsent, rows, sentinel, table_of  # noqa: E402
+from kv_append_check import as_cache, descales, sentinel  # noqa: E402
+from kv_cache_check import DEV, assert_close, cu_of, dequantise, gather, i32 as t32, reference_ragged  # noqa: E402
+from rope_check import check, qsent, rows, table_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf, i16, u8, i32 = torch.bfloat16, torch.int16, torch.uint8, torch.int32
@@ -26,8 +26,8 @@ CAP, PAD = 192, 9
 SQ_ALL = SQ
 
 
-def t32(x):
-    return torch.tensor(x, dtype=i32, device=DEV)
+def dev(t):
+    return None if t is None else t.to(DEV)
 
 
 def caches(B, Hkv, d, fp8, page, seed):
@@ -40,7 +40,7 @@ def caches(B, Hkv, d, fp8, page, seed):
 def run(Q, Kn, Vn, Kc, Vc, cs, cu, lens, il, kd, vd, bt=None, Qo=None):
     Qo = dev(qsent(Q.shape) if Qo is None else Qo)
     Kd, Vd = dev(Kc), dev(Vc)
-    call.launch(dev(Q), dev(Kn), dev(Vn), Qo, Kd, Vd, dev(cs), lens_tensor(lens), il, dev(kd), dev(vd), dev(bt), cu=t32(cu))
+    call.launch(dev(Q), dev(Kn), dev(Vn), Qo, Kd, Vd, dev(cs), t32(lens), il, dev(kd), dev(vd), dev(bt), cu=t32(cu))
     torch.cuda.synchronize()
     return Qo, Kd, Vd
 
@@ -157,7 +157,7 @@ def test_strided_tokens_in_place_and_bad_table_entries(fp8):
     fd = dev(fused)
     Qd, Knd, Vnd = part(fd)
     Kd, Vd = dev(Kc), dev(Vc)
-    call.launch(Qd, Knd, Vnd, Qd, Kd, Vd, dev(table), lens_tensor(LENS), False, dev(kd), dev(vd), dev(bad), cu=t32(cu))
+    call.launch(Qd, Knd, Vnd, Qd, Kd, Vd, dev(table), t32(LENS), False, dev(kd), dev(vd), dev(bad), cu=t32(cu))
     torch.cuda.synchronize()
     qo, k, v = rc.rope_append_varlen(Q, Kn, Vn, Q.clone(), Kc, Vc, table, cu, LENS, False, kd, vd, bad)
     want = fused.clone()
@@ -176,7 +176,7 @@ def test_the_fronts_make_the_same_calls():
     for pg in (None, page):
         bt, Kc, Vc = caches(B, Hkv, d, True, pg, 55)
         Kd, Vd, Qo = dev(Kc), dev(Vc), dev(qsent(Q.shape))
-        kw = dict(kv_lens=lens_tensor(LENS), interleaved=True, k_descale=dev(kd), v_descale=dev(vd), Q_out=Qo)
+        kw = dict(kv_lens=t32(LENS), interleaved=True, k_descale=dev(kd), v_descale=dev(vd), Q_out=Qo)
         if pg:
             out = fa.rope_cache_append_paged_varlen(dev(Q), dev(Kn), dev(Vn), as_cache(Kd), as_cache(Vd), dev(bt), t32(cu), dev(table), **kw)
         else:
@@ -191,7 +191,7 @@ def test_mixed_batch_steps_as_one_graph():
     once at a fixed totalQ and replayed for three steps with cu_seqlens_q and the lengths changed in place.  Sequence 0 goes from a
     96-row chunk to a 40-row chunk to 1-row decode; sequence 1 decodes behind 57 cached keys and then goes idle; sequence 2 joins at
     step 1; slot 3 stays idle.  Caches and Qout against the reference; O / LSE bit for bit against the same attention call on the
-    reference's tensors, and by decode_check.assert_close against float64 attention on them"""
+    reference's tensors, and by kv_cache_check.assert_close against float64 attention on them"""
     B, Hkv, G, d, page, n, T, rot = 4, 2, 4, 128, 16, 16, 128, 64
     H, cap = Hkv * G, n * page
     steps = [[96, 1, 0, 0], [40, 1, 30, 0], [1, 0, 2, 0]]
@@ -242,6 +242,6 @@ def test_mixed_batch_steps_as_one_graph():
         owned[:c[-1]] = True
         assert torch.equal(O[owned], O2[owned]) and torch.equal(lse[:, owned], lse2[:, owned]), it
         K64, V64 = gather(dequantise(refK, kd), bt), gather(dequantise(refV, vd), bt)
-        refO, refL, own = packed(per_sequence_reference(qr, K64, V64, sq, pos, True), sq, T, H, d)
+        refO, refL, own = reference_ragged(qr, K64, V64, sq, pos, True)
         assert torch.equal(own, owned)
         assert_close(O[owned], lse[:, owned], refO[owned], refL[:, owned], f"rope ragged step {it} rows {sq} lengths {pos}")

@@ -17,7 +17,7 @@ import arena as ar  # noqa: E402
 import memory_contract as mc  # noqa: E402
 import rope_call  # noqa: E402
 import rope_check as rc  # noqa: E402
-from test_extend_varlen import cu_of  # noqa: E402
+from kv_cache_check import cu_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf, f32, i32, i16, u8 = torch.bfloat16, torch.float32, torch.int32, torch.int16, torch.uint8

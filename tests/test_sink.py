@@ -2,7 +2,7 @@
 flash_attention_sink_decode_paged).  Every case: B = 2, Hkv = 2, capacity 384 (three 128-key tiles); the reference, the sink vector and the
 runners shared with test_sink_extend.py are in sink_check.py.
 
-1. parity against the float64 reference (decode_check.assert_close, unchanged) over d, G, both masks, windows 0 / 7 / 130, splits 1 / 3 /
+1. parity against the float64 reference (kv_cache_check.assert_close, unchanged) over d, G, both masks, windows 0 / 7 / 130, splits 1 / 3 /
    the library's choice, the four cache forms, fp32 and bf16 O; Sq 1 / 5 / 16, lengths (1, 300) and (129, 300)
 2. sinks = -inf everywhere: the bits of the call without sinks
 3. the exact probe: Q = 0, sinks = 0, window = 1 -- O is exactly half of one named key's V row, LSE = ln 2
@@ -17,8 +17,10 @@ import __graft_entry__ as entry
 
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
+import kv_cache_check as kv  # noqa: E402
 import sink_check as sc  # noqa: E402
-from sink_check import DEV, FORM_IDS, FORMS  # noqa: E402
+from kv_cache_check import DEV  # noqa: E402
+from sink_check import FORM_IDS, FORMS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROWS = (1, 5, 16)
@@ -66,12 +68,12 @@ def test_graph_replays_see_the_sinks_of_the_moment(ns):
     """`kv_lens += Sq; kv_cache_append; flash_attention_decode(sinks=)` on a contiguous bf16 cache (sink_check.run_graph)"""
     d, G, Sq, W, start = 64, 4, 5, 130, (100, 290)
     H = sc.HKV * G
-    cache = sc.Cache(d, None, False, 1030)
+    cache = kv.Cache(d, None, False, 1030)
     K, V = cache.cK.to(DEV), cache.cV.to(DEV)
     Qc = sc.queries("decode", d, G, Sq, 1031)
     Q = Qc.to(DEV)
     Kn, Vn = (sc.queries("decode", d, 1, Sq, 1032 + i).to(DEV) for i in range(2))       # [B, HKV, Sq, d]: the new rows
-    lens, sinks = sc.i32(start), torch.zeros(H, dtype=torch.float32, device=DEV)
+    lens, sinks = kv.i32(start), torch.zeros(H, dtype=torch.float32, device=DEV)
     O = torch.empty((sc.B, H, Sq, d), dtype=torch.float32, device=DEV)
     ws = torch.empty(max(fa.decode_workspace_size(sc.B, H, Sq, d, ns), 16), dtype=torch.uint8, device=DEV)
 
@@ -88,9 +90,9 @@ def test_graph_replays_see_the_sinks_of_the_moment(ns):
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
 def test_a_call_with_sinks_fetches_the_plan_the_workspace_size_and_the_sink_entry_point(monkeypatch, form, window, ns):
     d, G, Sq = 64, 4, 3
-    c = sc.Cache(d, *form, 1040).device()
+    c = kv.Cache(d, *form, 1040).device()
     paged = form[0] is not None
-    args = [sc.queries("decode", d, G, Sq, 1041).to(DEV), c["K"], c["V"]] + ([c["table"]] if paged else []) + [sc.i32((200, 256))]
+    args = [sc.queries("decode", d, G, Sq, 1041).to(DEV), c["K"], c["V"]] + ([c["table"]] if paged else []) + [kv.i32((200, 256))]
     sc.run_routing(monkeypatch, "flash_attention_decode" + ("_paged" if paged else ""), args,
                    dict(c["ds"], is_causal=True, window=window, num_splits=ns), sc.sinks_for(sc.HKV * G).to(DEV),
                    "flash_attention_decode_plan_window" if window else "flash_attention_decode_plan",

@@ -260,7 +260,7 @@ def wrong_implementations(sc, torch, Q, K, V, lens, causal, W, sinks, G):
 
 
 def test_the_helper_refuses_four_wrong_implementations():
-    """Worst error / tolerance (decode_check.assert_close's: O 1e-3 + 1e-3 |ref|, LSE 2e-4 + 2e-6 |ref|) of each emulation against the
+    """Worst error / tolerance (kv_cache_check.assert_close's: O 1e-3 + 1e-3 |ref|, LSE 2e-4 + 2e-6 |ref|) of each emulation against the
     reference, the SMALLEST over the cases below (Sq 1 / 16 / 40, the three length pairs, causal and not, windows 0 / 7 / 130; the windowed ones only
     for the last) -- measured here, d = 64,
     G = 4, N(0, 1) bf16 data, scale 1/8, SINKS8:

@@ -20,10 +20,11 @@ import __graft_entry__ as entry
 
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
-import decode_check as dc  # noqa: E402
+import kv_cache_check as kv  # noqa: E402
 import sink_check as sc  # noqa: E402
 import tree_check as tc  # noqa: E402
-from sink_check import DEV, FORM_IDS, FORMS, HKV, i32, same_bits  # noqa: E402
+from kv_cache_check import DEV, Cache, i32, same_bits  # noqa: E402
+from sink_check import FORM_IDS, FORMS, HKV  # noqa: E402
 from tree_check import B, CAP, bf16, f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ def probe_cache(d, form, Sq, lens, seed):
     """a cache in `form` whose V is tree_check.probe_values (exact in e4m3fn: descales 1) and whose K is N(0, 1) -- Q = 0 makes it moot"""
     g = torch.Generator().manual_seed(seed)
     K = torch.randn(B, HKV, CAP, d, generator=g).to(bf16)
-    return sc.Cache(d, *form, seed, K=K, V=tc.probe_values(Sq, lens, d), descales=(torch.tensor([1.0, 0.5]), torch.tensor([1.0, 1.0])))
+    return Cache(d, *form, seed, K=K, V=tc.probe_values(Sq, lens, d), descales=(torch.tensor([1.0, 0.5]), torch.tensor([1.0, 1.0])))
 
 
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
@@ -88,14 +89,14 @@ def test_exact_read_back_on_a_long_cache_under_the_planned_splits(paged_fp8):
                 key = L - Sq + j
                 V[int(table[b, key // page]), :, key % page, j] = 0x38                     # 1.0 in e4m3fn
         K = torch.zeros(B * n, HKV, page, d, dtype=torch.uint8)
-        O = fa.flash_attention_tree_paged(Q, K.view(dc.F8).to(DEV), V.view(dc.F8).to(DEV), table.to(DEV), wt, i32(lens), out_dtype=f32)
+        O = fa.flash_attention_tree_paged(Q, K.view(kv.F8).to(DEV), V.view(kv.F8).to(DEV), table.to(DEV), wt, i32(lens), out_dtype=f32)
     tc.assert_read_back(O, lens, 0, words, f"long cache, {plan['num_splits']} splits")
 
 
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
 @pytest.mark.parametrize("d,G", [(64, 4), (128, 1)])
 def test_chain_and_all_ones_words_are_the_causal_twin_bit_for_bit(d, G, form):
-    cache = sc.Cache(d, *form, 1600 + d)
+    cache = Cache(d, *form, 1600 + d)
     c = cache.device()
     H = HKV * G
     sinks = sc.sinks_for(H).to(DEV)
@@ -117,7 +118,7 @@ def test_chain_and_all_ones_words_are_the_causal_twin_bit_for_bit(d, G, form):
 def test_paged_equals_contiguous_and_ignored_bits_and_null_sinks_change_nothing(d, page, fp8):
     G = 4
     H = HKV * G
-    cache = sc.Cache(d, page, fp8, 1700 + d)
+    cache = Cache(d, page, fp8, 1700 + d)
     paged, contig = cache.device(), cache.device(contiguous=True)
     sinks = sc.sinks_for(H).to(DEV)
     none = torch.full((H,), sc.NEG_INF, dtype=f32, device=DEV)
@@ -171,7 +172,7 @@ def test_invisible_siblings_do_not_leak(d, Sq, form):
                 else:
                     k[b, :, rows], v[b, :, rows] = 0.0, 0.0
             ds = (torch.tensor([1.0, 0.5]), torch.tensor([1.0, 1.0])) if fp8 else None        # (the stored values are e4m3fn numbers as they stand)
-            cache = sc.Cache(d, page, fp8, 1801, K=k.to(bf16), V=v.to(bf16), descales=ds)
+            cache = Cache(d, page, fp8, 1801, K=k.to(bf16), V=v.to(bf16), descales=ds)
             runs.append(tc.attend(cache.device(), Q, i32(lens), wt, window=W, num_splits=ns, out_dtype=f32, sinks=sc.sinks_for(HKV * G).to(DEV)))
         (Op, lp), (Oz, lz) = runs
         assert torch.isfinite(Op[:, :, watched]).all() and torch.isfinite(lp[:, :, watched]).all()
@@ -198,8 +199,8 @@ def test_one_speculative_step_end_to_end(d, Sq):
     fa.kv_cache_append(Kn.to(DEV), Vn.to(DEV), K, V, lens)
     O, lse = fa.flash_attention_tree(Qc.to(DEV), K, V, mask, lens, return_lse=True, out_dtype=f32)
     # the whole call against the rule's reference on the cache as the append left it
-    refO, refL = tc.reference_tree(Qc, K.cpu(), V.cpu(), [s + Sq for s in start], 0, [tc.words_of_parents(parents)] * B)
-    dc.assert_close(O, lse, refO, refL, "the tree call")
+    refO, refL = kv.reference(Qc, K.cpu(), V.cpu(), [s + Sq for s in start], True, 0, words=[tc.words_of_parents(parents)] * B)
+    kv.assert_close(O, lse, refO, refL, "the tree call")
     path = [Sq - 1]                                            # the last node's walk to the root, root first
     while parents[path[0]] >= 0:
         path.insert(0, parents[path[0]])
@@ -209,8 +210,8 @@ def test_one_speculative_step_end_to_end(d, Sq):
     for b, s in enumerate(start):
         Kl[b, :, s:s + len(path)], Vl[b, :, s:s + len(path)] = Kn[b][:, path], Vn[b][:, path]
     for t, node in enumerate(path):
-        wantO, wantL = dc.reference(Qc[:, :, node:node + 1], Kl, Vl, [s + t + 1 for s in start], True)
-        dc.assert_close(O[:, :, node:node + 1], lse[:, :, node:node + 1], wantO, wantL, f"accepted node {node} (depth {t})")
+        wantO, wantL = kv.reference(Qc[:, :, node:node + 1], Kl, Vl, [s + t + 1 for s in start], True)
+        kv.assert_close(O[:, :, node:node + 1], lse[:, :, node:node + 1], wantO, wantL, f"accepted node {node} (depth {t})")
     assert fa.tree_depths([parents])[0, path].tolist() == list(range(len(path)))
     # rewind and re-append the accepted rows, packed by token
     lens -= Sq
@@ -229,13 +230,13 @@ def test_one_speculative_step_end_to_end(d, Sq):
         Kl[b, :, s + len(path)], Vl[b, :, s + len(path)] = k1[b, :, 0], v1[b, :, 0]
     O1, lse1 = fa.flash_attention_decode(q1.to(DEV), K, V, lens, is_causal=True, return_lse=True, out_dtype=f32)
     assert lens.tolist() == [s + len(path) + 1 for s in start]
-    dc.assert_close(O1, lse1, *dc.reference(q1, Kl, Vl, [s + len(path) + 1 for s in start], True), "the next token")
+    kv.assert_close(O1, lse1, *kv.reference(q1, Kl, Vl, [s + len(path) + 1 for s in start], True), "the next token")
 
 
 @pytest.mark.parametrize("Sq,ns", [(5, 1), (16, 2), (33, 1), (64, 3)])
 def test_graph_replays_see_the_words_of_the_moment(Sq, ns):
     d, G, W, lens = 64, 4, 130, (Sq + 40, 300)
-    cache = sc.Cache(d, None, False, 2000)
+    cache = Cache(d, None, False, 2000)
     c = cache.device()
     sinks = sc.sinks_for(HKV * G)
     Qc = sc.queries("decode", d, G, Sq, 2001 + Sq)
@@ -253,6 +254,6 @@ def test_graph_replays_see_the_words_of_the_moment(Sq, ns):
         wt.copy_(tc.words_tensor(words).to(DEV))
         graph.replay()
         torch.cuda.synchronize()
-        dc.assert_close(O, lse, *tc.reference_tree(Qc, cache.refK, cache.refV, lens, W, words, sinks), f"replay {r} {families}")
+        kv.assert_close(O, lse, *kv.reference(Qc, cache.refK, cache.refV, lens, True, W, words=words, sinks=sinks), f"replay {r} {families}")
         seen.append(O.clone())
     assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])

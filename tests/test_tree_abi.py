@@ -22,7 +22,8 @@ import __graft_entry__ as entry
 
 fa = entry.load_package()
 
-import tree_check as tc  # noqa: E402  (registers the short key of treeMask)
+import kv_cache_check as kv  # noqa: E402
+import tree_check as tc  # noqa: E402
 from abi_decl import (BAD_DHEAD, BAD_DTYPE, BAD_SCALE, BAD_SHAPE, BAD_STRIDE, BF16, CAP, F16, F32, FP8, MISALIGNED,  # noqa: E402
                       NULL_POINTER, MetaTensor as T, aligned_host_pointer, declared_parameters, host_call, plan_call)
 
@@ -262,17 +263,17 @@ def test_chain_and_all_ones_words_are_the_causal_reference():
             plain = sc.reference_sinks(Q, K, V, lens, True, W, sinks)[2:]
             for family in tc.TWINS:
                 words = [tc.words_of(family, Sq)] * tc.B
-                O, lse = tc.reference_tree(Q, K, V, lens, W, words, sinks)
+                O, lse = kv.reference(Q, K, V, lens, True, W, words=words, sinks=sinks)
                 worst = max(worst, (O - want[0]).abs().max().item(), (lse - want[1]).abs().max().item())
-                O, lse = tc.reference_tree(Q, K, V, lens, W, words)
+                O, lse = kv.reference(Q, K, V, lens, True, W, words=words)
                 worst = max(worst, (O - plain[0]).abs().max().item(), (lse - plain[1]).abs().max().item())
             # garbage in the ignored bits -- above i, at and beyond Sq -- and a missing self bit are not read by the rule
             words, _ = tc.case_words(Sq, Sq)
             dirty = [[(w & ~(1 << i)) | (tc.FULL << (i + 1) & tc.FULL) for i, w in enumerate(row)] for row in words]
             for b in range(tc.B):
                 assert tc.effective(dirty[b], Sq) == tc.effective(words[b], Sq)
-                assert torch.equal(tc.visible_tree(lens[b], Sq, W, dirty[b]), tc.visible_tree(lens[b], Sq, W, words[b]))
-                assert bool(tc.visible_tree(lens[b], Sq, W, words[b]).any(-1).all())       # no row is empty
+                assert torch.equal(kv.visible(lens[b], Sq, True, W, dirty[b]), kv.visible(lens[b], Sq, True, W, words[b]))
+                assert bool(kv.visible(lens[b], Sq, True, W, words[b]).any(-1).all())       # no row is empty
     print(f"chain / all-ones against the causal reference: worst difference {worst:.2e}")
     assert worst < 1e-12
 
@@ -287,7 +288,6 @@ def test_the_condition_on_the_parity_cases_holds():
 
 def wrong_kernels(torch, Sq, G, W, words, lens):
     """{name: vis(b, h, L)} of five wrong ways to read the mask, each as a visibility in place of the rule's"""
-    from decode_window_check import visible_window
     flat = [w for row in words for w in row]
 
     def parts(L, row_words):
@@ -295,14 +295,14 @@ def wrong_kernels(torch, Sq, G, W, words, lens):
         k = torch.arange(L)[None, :]
         own = (base + torch.arange(Sq)).clamp(min=0)[:, None]
         w = tc.words_tensor([row_words])[0][:, None]
-        return base, k, own, w, visible_window(L, Sq, True, W)
+        return base, k, own, w, kv.visible(L, Sq, True, W)
 
     def key_index(b, h, L):                       # the bit index taken from the key, not from key - base
         base, k, own, w, causal = parts(L, words[b])
         return causal & ((k < base) | ((w >> (k & 63)) & 1).bool() | (k == own))
 
     def batch_zero(b, h, L):                      # the words of sequence 0 for every sequence
-        return tc.visible_tree(L, Sq, W, words[0])
+        return kv.visible(L, Sq, True, W, words[0])
 
     def no_self(b, h, L):                         # the self bit not forced
         base, k, own, w, causal = parts(L, words[b])
@@ -310,12 +310,12 @@ def wrong_kernels(torch, Sq, G, W, words, lens):
 
     def above(b, h, L):                           # bits above i honoured: the draft's keys cut by the word alone, not by the causal limit
         base, k, own, w, _ = parts(L, words[b])
-        reach = visible_window(L, Sq, False, W)   # (the window's left edge, no upper limit)
+        reach = kv.visible(L, Sq, False, W)   # (the window's left edge, no upper limit)
         return reach & ((k < base) | ((w >> (k - base).clamp(0, 63)) & 1).bool() | (k == own))
 
     def packed_row(b, h, L):                      # the word indexed by the packed row g * Sq + i instead of the query row
         g = h % G
-        return tc.visible_tree(L, Sq, W, [flat[(g * Sq + i) % len(flat)] for i in range(Sq)])
+        return kv.visible(L, Sq, True, W, [flat[(g * Sq + i) % len(flat)] for i in range(Sq)])
 
     return {"the bit index taken from the key": key_index, "the words of batch 0 for every sequence": batch_zero,
             "the self bit not forced": no_self, "bits above i honoured": above, "the word indexed by the packed row": packed_row}
@@ -324,7 +324,7 @@ def wrong_kernels(torch, Sq, G, W, words, lens):
 def test_the_reference_refuses_five_wrong_kernels_each_on_a_named_row():
     """d = 64, G = 4, Sq = 16, lengths (19, 136): prefixes of 3 and 120 keys; N(0, 1) bf16 data, scale 1/8, sinks of sink_check.  The
     words: sequence 0 a binary tree, sequence 1 a star, both WITHOUT their self bits and with every bit above i set -- the rule
-    ignores both, a wrong kernel need not.  Each emulation must miss decode_check.assert_close's bounds by more than 10 x on the row
+    ignores both, a wrong kernel need not.  Each emulation must miss kv_cache_check.assert_close's bounds by more than 10 x on the row
     named here (sequence, head, row), and the reference itself on the clean words must be the reference on the dirty ones."""
     torch = pytest.importorskip("torch")
     import sink_check as sc
@@ -333,15 +333,15 @@ def test_the_reference_refuses_five_wrong_kernels_each_on_a_named_row():
     sinks = sc.sinks_for(sc.HKV * G)
     clean = [tc.words_of("binary", Sq), tc.words_of("star", Sq)]
     words = [[(w & ~(1 << i)) | (tc.FULL << (i + 1) & tc.FULL) for i, w in enumerate(row)] for row in clean]
-    refO, refL = tc.reference_tree(Q, K, V, lens, W, words, sinks)
-    cleanO, cleanL = tc.reference_tree(Q, K, V, lens, W, clean, sinks)
+    refO, refL = kv.reference(Q, K, V, lens, True, W, words=words, sinks=sinks)
+    cleanO, cleanL = kv.reference(Q, K, V, lens, True, W, words=clean, sinks=sinks)
     assert torch.equal(refO, cleanO) and torch.equal(refL, cleanL)
     named = {"the bit index taken from the key": (0, 0, 9), "the words of batch 0 for every sequence": (1, 3, 7),
              "the self bit not forced": (1, 5, 4), "bits above i honoured": (0, 2, 0), "the word indexed by the packed row": (0, 1, 6)}
     kernels = wrong_kernels(torch, Sq, G, W, words, lens)
     assert sorted(kernels) == sorted(named) and len(kernels) == 5
     for name, vis in kernels.items():
-        O, lse = tc.reference_tree(Q, K, V, lens, W, words, sinks, vis=vis)
+        O, lse = kv.reference(Q, K, V, lens, True, W, words=words, sinks=sinks, vis=vis)
         off = tc.differing_rows(O, lse, refO, refL, factor=10.0)
         eo, el = sc.excess(O[off], lse[off], refO[off], refL[off])
         print(f"{name}: {int(off.sum())} of {off.numel()} rows beyond 10 x the tolerance; worst O {eo:.0f} x, LSE {el:.0f} x")

@@ -3,7 +3,7 @@ flash_attention_tree_paged): every tensor of the call carved out of one guarded 
 placements -- `aligned`, everything at 0 mod 512, and `offset`, tensors at 16 mod 256, the side inputs at 4 mod 16 and the mask words at
 8 mod 16, the least the library accepts for them -- with the workspace entering as NaNs at exactly its stated size.  The result must be
 the run on plain allocations bit for bit, the arena untouched outside O, the LSE and the workspace, and the result is also held to the
-float64 reference of tree_check.py (decode_check.assert_close, unchanged).  One split and three; a decode row count and a
+float64 reference of tree_check.py (kv_cache_check.assert_close, unchanged).  One split and three; a decode row count and a
 chunked-prefill one.  The cache, the specs and the arena are memory_contract.py's, imported."""
 import math
 
@@ -14,7 +14,7 @@ import __graft_entry__ as entry
 torch = pytest.importorskip("torch")
 fa = entry.load_package()
 import arena as ar  # noqa: E402
-import decode_check as dc  # noqa: E402
+import kv_cache_check as kv  # noqa: E402
 import memory_contract as mc  # noqa: E402
 import sink_check as sc  # noqa: E402
 import tree_check as tc  # noqa: E402
@@ -71,7 +71,7 @@ def test_tree_calls(d, rows, page, fp8):
     sinks = sc.sinks_for(H)
     words = [tc.words_of("binary", rows), tc.words_of("random", rows, 3)]
     for W, ns in ((w, n) for w in (0, 130) for n in (1, 3)):
-        refO, refL = tc.reference_tree(Q, cache.refK, cache.refV, LENS, W, words, sinks)
+        refO, refL = kv.reference(Q, cache.refK, cache.refV, LENS, True, W, words=words, sinks=sinks)
         call = tree_call(cache, Q, LENS, ns, W, sinks, words)
         assert call.ws_bytes == fa.decode_workspace_size(len(LENS), H, rows, d, ns) and (call.ws_bytes > 0) == (ns > 1)
         _, plain = run(call, None)
@@ -82,4 +82,4 @@ def test_tree_calls(d, rows, page, fp8):
             for n in call.outs:
                 assert mc.same(got[n], plain[n]), f"{call.note} [{placement}]: {n} differs from the run on plain allocations"
             arena.check()
-            dc.assert_close(got["O"], got["lse"], refO, refL, f"{call.note} [{placement}]")
+            kv.assert_close(got["O"], got["lse"], refO, refL, f"{call.note} [{placement}]")

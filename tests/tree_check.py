@@ -1,21 +1,17 @@
 """Checker shared by the tree-masked verification tests (tests/test_tree_abi.py, test_tree.py, test_tree_memory_contract.py): the mask
-families, the visibility rule of flash_attention_tree as include/flash_attention.h states it, the float64 ground truth under it and the
-calls the GPU tests make alike.  Plain torch on the CPU for everything but the calls; the criterion is decode_check.assert_close,
+families, the condition that a case's mask matters, the read-back probe and the calls the GPU tests make alike; the visibility rule of
+flash_attention_tree as include/flash_attention.h states it and the float64 ground truth under it are kv_cache_check's.  Plain torch on the CPU for everything but the calls; the criterion is kv_cache_check.assert_close,
 unchanged (1e-3 + 1e-3 |ref| on O, 2e-4 + 2e-6 |ref| on the LSE).
 
-ABI.  abi_decl.c_call refuses a call whose declared parameter has no short key, so this module registers one for ``treeMask``
-(``tree``) in abi_decl.KEYS when it is imported; abi_decl.py itself is untouched.
-
 Rule.  With len the sequence's length, base = len - Sq, lim_i = max(base + i + 1, 1) and lo_i = max(lim_i - W, 0) (W = 0: 0), row i sees
-key k iff lo_i <= k < lim_i (decode_window_check.visible_window under the causal mask) AND (k < base, or bit k - base of the row's word
-is set, or k == lim_i - 1).  `visible_tree` builds that matrix; `reference_tree` is the explicit float64 softmax over it, per query head
-(`vis`: a visibility of the caller's own per (sequence, head) -- the wrong kernels test_tree_abi.py emulates), then
-sink_check.apply_sinks.
+key k iff lo_i <= k < lim_i (the causal mask under the window) AND (k < base, or bit k - base of the row's word is set, or
+k == lim_i - 1): kv_cache_check.visible with ``words``, and kv_cache_check.reference with ``words`` is the explicit float64 softmax over
+it, then the sinks (its ``vis``: a visibility of the caller's own per (sequence, head) -- the wrong kernels test_tree_abi.py emulates).
 
-Masks.  A case's words are a list [B][Sq] of Python ints (unsigned 64-bit patterns); `words_tensor` makes the int64 tensor the call
-takes.  Families: "chain" (bits 0 .. i), "ones" (every bit), "star" (the self bit alone: every node hangs off the prefix), "binary" (the
-heap-shaped tree, parent (i - 1) // 2) and "random" (a seeded parent array, parent uniform in [-1, i)); `words_of_parents` is the
-brute-force ancestor walk.  The first two are the causal twin.
+Masks.  A case's words are a list [B][Sq] of Python ints (unsigned 64-bit patterns); kv_cache_check.words_tensor makes the int64
+tensor the call takes.  Families: "chain" (bits 0 .. i), "ones" (every bit), "star" (the self bit alone: every node hangs off the
+prefix), "binary" (the heap-shaped tree, parent (i - 1) // 2) and "random" (a seeded parent array, parent uniform in [-1, i));
+`words_of_parents` is the brute-force ancestor walk.  The first two are the causal twin.
 
 `assert_masks_matter`: a case whose mask changes nothing tests nothing.  On the reference, for every sequence of a non-chain case whose
 prefix base is in [0, 120] and that has rows i >= 2: at least HALF of the (head, row i >= 2) pairs differ from the causal reference by
@@ -26,19 +22,16 @@ import itertools
 
 import torch
 
-import abi_decl
-import decode_check as dc
+import kv_cache_check as kv
 import sink_check as sc
-from decode_window_check import visible_window
-
-abi_decl.KEYS.setdefault("tree", ("treeMask",))
+from kv_cache_check import DEV, Cache, assert_close, fa, i32, ratios, reference, visible, words_tensor
 
 FULL = (1 << 64) - 1
 FAMILIES = ("chain", "ones", "star", "binary", "random")
 TWINS = ("chain", "ones")                    # the families that are the causal mask
 B, HKV, CAP = sc.B, sc.HKV, sc.CAP
-DEV, f32, bf16 = dc.DEV, torch.float32, torch.bfloat16
-MAX_Q = dc.fa.FA_TREE_MAX_Q
+f32, bf16 = torch.float32, torch.bfloat16
+MAX_Q = fa.FA_TREE_MAX_Q
 
 
 # ---- masks ------------------------------------------------------------------------------------------------------------------------
@@ -71,53 +64,16 @@ def words_of(family, Sq, seed=0):
     return [FULL] * Sq if family == "ones" else words_of_parents(parents_of(family, Sq, seed))
 
 
-def words_tensor(words):
-    """[B][Sq] unsigned patterns -> the int64 tensor [B, Sq] (CPU) a call takes"""
-    return torch.tensor([[w - (1 << 64) if w >> 63 else w for w in row] for row in words], dtype=torch.int64)
-
-
 def effective(words, Sq):
     """what the rule reads of a sequence's words: bits 0 .. i of word i, the self bit forced"""
     return [(w & ((1 << (i + 1)) - 1)) | (1 << i) for i, w in enumerate(words[:Sq])]
 
 
-# ---- the rule and the reference -----------------------------------------------------------------------------------------------------
-def visible_tree(L, Sq, W, words):
-    """bool [Sq, L] of one sequence under the module docstring's rule; words: its Sq patterns"""
-    base = L - Sq
-    causal = visible_window(L, Sq, True, W)
-    k = torch.arange(L)[None, :]
-    own = (base + torch.arange(Sq)).clamp(min=0)[:, None]                         # lim_i - 1
-    w = words_tensor([words])[0]
-    node = (k - base).clamp(min=0, max=63)                                        # (a visible key's node is below Sq <= 64)
-    bit = ((w[:, None] >> node) & 1).bool()
-    return causal & ((k < base) | bit | (k == own))
-
-
-def reference_tree(Q, K, V, lens, W, words, sinks=None, scale=None, vis=None):
-    """float64 explicit softmax over the visible keys (CPU tensors; K, V [B, Hkv, capacity, d], an fp8 cache dequantised), then the sinks:
-    (O [B, H, Sq, d], LSE [B, H, Sq]).  vis(b, h, L) -> bool [Sq, L]: another visibility than the rule's"""
-    Bq, H, Sq, d = Q.shape
-    G = H // K.shape[1]
-    scale = scale or 1.0 / d ** 0.5
-    O, lse = torch.zeros(Bq, H, Sq, d, dtype=torch.float64), torch.zeros(Bq, H, Sq, dtype=torch.float64)
-    for b in range(Bq):
-        L = int(lens[b])
-        k, v = (t[b, :, :L].double().repeat_interleave(G, 0) for t in (K, V))
-        S = (Q[b].double() @ k.transpose(-1, -2)) * scale
-        rule = visible_tree(L, Sq, W, words[b]) if vis is None else None
-        M = torch.stack([rule if vis is None else vis(b, h, L) for h in range(H)])
-        S = S.masked_fill(~M, float("-inf"))
-        lse[b] = torch.logsumexp(S, -1)
-        O[b] = torch.softmax(S, -1) @ v
-    return sc.apply_sinks(O, lse, sinks) if sinks is not None else (O, lse)
-
-
+# ---- when a mask matters --------------------------------------------------------------------------------------------------------
 def differing_rows(O, lse, refO, refL, factor=4.0):
     """bool [B, H, Sq]: the row is off the reference by more than `factor` x the tolerance in some element of O, or in the LSE"""
-    err, tol = (O.double() - refO).abs(), 1e-3 + 1e-3 * refO.abs()
-    lerr, ltol = (lse.double() - refL).abs(), 2e-4 + 2e-6 * refL.abs()
-    return (err > factor * tol).any(-1) | (lerr > factor * ltol)
+    r, lr = ratios(O, lse, refO, refL)
+    return (r > factor).any(-1) | (lr > factor)
 
 
 def assert_masks_matter(refO, refL, causalO, causalL, lens, families, what=""):
@@ -147,8 +103,7 @@ def case_words(Sq, n, families=("star", "binary", "random")):
 
 
 def attend(c, Q, lens, words, **kw):
-    """(O, LSE) of one tree call through the Python fronts; c: sink_check.Cache.device(); words: the int64 device tensor"""
-    fa = dc.fa
+    """(O, LSE) of one tree call through the Python fronts; c: kv_cache_check.Cache.device(); words: the int64 device tensor"""
     if c["table"] is not None:
         return fa.flash_attention_tree_paged(Q, c["K"], c["V"], c["table"], words, lens, return_lse=True, **c["ds"], **kw)
     return fa.flash_attention_tree(Q, c["K"], c["V"], words, lens, return_lse=True, **c["ds"], **kw)
@@ -156,7 +111,7 @@ def attend(c, Q, lens, words, **kw):
 
 def twin(c, Q, lens, **kw):
     """the causal twin on the same tensors: flash_attention_sink_decode* up to FA_DECODE_MAX_Q rows, flash_attention_sink_extend* above"""
-    return sc.attend("decode" if Q.shape[2] <= dc.fa.FA_DECODE_MAX_Q else "extend", c, Q, lens, is_causal=True, **kw)
+    return kv.attend("decode" if Q.shape[2] <= fa.FA_DECODE_MAX_Q else "extend", c, Q, lens, is_causal=True, **kw)
 
 
 def run_parity(d, G, form, rows, run=True):
@@ -164,7 +119,7 @@ def run_parity(d, G, form, rows, run=True):
     choice; the masks rotate through star / binary / random, two different ones per case.  run = False: the references and
     assert_masks_matter alone (no GPU).  Returns the number of sequences assert_masks_matter applied to"""
     page, fp8 = form
-    cache = sc.Cache(d, page, fp8, 1400 + d + 7 * G)
+    cache = Cache(d, page, fp8, 1400 + d + 7 * G)
     c = cache.device() if run else None
     sinks = sc.sinks_for(HKV * G)
     mattered = 0
@@ -173,15 +128,15 @@ def run_parity(d, G, form, rows, run=True):
         for m, lens in enumerate(lengths(Sq)):
             words, names = case_words(Sq, n + m)
             what = f"tree d{d} G{G} Sq{Sq} lens{lens} window{W} {'/'.join(names)} {sc.FORM_IDS[sc.FORMS.index(form)]}"
-            refO, refL = reference_tree(Q, cache.refK, cache.refV, lens, W, words, sinks)
+            refO, refL = reference(Q, cache.refK, cache.refV, lens, True, W, words=words, sinks=sinks)
             chain = [words_of("chain", Sq)] * B
-            mattered += len(assert_masks_matter(refO, refL, *reference_tree(Q, cache.refK, cache.refV, lens, W, chain, sinks), lens, names, what))
+            mattered += len(assert_masks_matter(refO, refL, *reference(Q, cache.refK, cache.refV, lens, True, W, words=chain, sinks=sinks), lens, names, what))
             if not run:
                 continue
             wt = words_tensor(words).to(DEV)
             for ns in (1, 2, 3, 0):
-                O, lse = attend(c, Q.to(DEV), sc.i32(lens), wt, window=W, num_splits=ns, sinks=sinks.to(DEV), out_dtype=f32)
-                dc.assert_close(O, lse, refO, refL, f"{what} splits{ns}")
+                O, lse = attend(c, Q.to(DEV), i32(lens), wt, window=W, num_splits=ns, sinks=sinks.to(DEV), out_dtype=f32)
+                assert_close(O, lse, refO, refL, f"{what} splits{ns}")
     return mattered
 
 
@@ -198,7 +153,7 @@ def probe_values(Sq, lens, d):
 def expected_bits(Sq, L, W, words):
     """(bits float64 [Sq, Sq], n [Sq]) of one sequence: bits[i, j] = row i sees node j (0 where the node's key does not exist), n_i =
     the keys row i sees"""
-    vis = visible_tree(L, Sq, W, words)
+    vis = visible(L, Sq, True, W, words)
     bits = torch.zeros(Sq, Sq, dtype=torch.float64)
     for j in range(Sq):
         if L - Sq + j >= 0:

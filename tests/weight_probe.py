@@ -3,7 +3,7 @@ instrument on the CPU, tests/test_probe_forward.py, test_probe_decode.py and tes
 
 Every parity test compares sums over all keys, so one (query, key) pair handled wrongly disappears in the tolerance of the sum.  The
 probes choose inputs so that every output element depends on exactly ONE pair; the ordinary element-wise comparison with the existing
-float64 references (oracle.attention_numpy / lse_numpy, decode_check.reference, grad_check.reference_grads) is then a per-pair one.
+float64 references (oracle.attention_numpy / lse_numpy, kv_cache_check.reference, grad_check.reference_grads) is then a per-pair one.
 A window is d consecutive indices from w0 = seam - d/2 (it straddles its seam); every head of a call has its own window.
 
   P through V   (forward, decode)  V[w0+j, j] = 1, V = 0 elsewhere (exact in every type)       O[q, j]  = P[q, w0+j]
@@ -38,7 +38,7 @@ fa = entry.load_package()
 import oracle  # noqa: E402  (checker only)
 import forward_routes as fr  # noqa: E402
 import grad_check as gc  # noqa: E402
-import decode_check as dc  # noqa: E402  (reference, visible)
+import kv_cache_check as kv  # noqa: E402  (reference, visible)
 from fuzz_gpu import EPS_FP8  # noqa: E402
 
 bf, f32, f16 = torch.bfloat16, torch.float32, torch.float16
@@ -384,7 +384,7 @@ def build_decode_long(d=128, seed=7):
 
 
 def decode_truth(p, causal):
-    refO, refL = dc.reference(p["Q"], p["K"], p["V"], p["lens"], causal)
+    refO, refL = kv.reference(p["Q"], p["K"], p["V"], p["lens"], causal)
     scale = 1.0 / math.sqrt(p["d"])
     smax = max(float((p["Q"][b].double() @ p["K"][b].repeat_interleave(p["G"], 0).transpose(-1, -2)).abs().max()) for b in range(len(p["lens"]))) * scale
     noise = 8.0 * max(smax, 4.0) * 2.0 ** -23
@@ -393,7 +393,7 @@ def decode_truth(p, causal):
 
 def decode_visible(L, Sq, cap, causal):
     vis = torch.zeros(Sq, cap, dtype=torch.bool)
-    vis[:, :L] = dc.visible(L, Sq, causal)
+    vis[:, :L] = kv.visible(L, Sq, causal)
     return vis
 
 

@@ -35,7 +35,7 @@ Each line:
               --paged "paged<page>" (and "paged<page>_fp8"), behind a shuffled block table -- timed like `ms` in the same run:
               append_ms[form]       one call that appends the shape's own Sq new rows per sequence at the shape's lengths (K and V)
               torch_append_ms[form] the same result built with torch ops on the same data: positions (and pages) from kv_lens and the
-                                    table on the device, decode_check.quantise's expression with the given descales, one indexed
+                                    table on the device, kv_cache_check.quantise's expression with the given descales, one indexed
                                     write per tensor; append_matches_torch[form]: the two caches hold the same bytes
               fill_ms[form], fill_tbps[form]  one call with Sq = 4096 and kv_lens = None (the cache's last 4096 rows: a fill after a
                                     prefill); bytes read + written = B Hkv 4096 d x 2 tensors x (2 + bytes per cache element)
