@@ -5,8 +5,23 @@ ARCH     := gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -fno-slp-vectorize
 LIB      := $(PKG)/libflash_attention.so
 # the library's translation units: the C ABI + one unit per group of kernel instantiations (they compile in parallel)
-KSRC     := $(wildcard $(PKG)/csrc/*.hip)
-KOBJ     := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(KSRC))
+# The split-KV units are the rows of SPLIT_FORMS in csrc/split_forms.hip.h, which says what each one is and who launches it: one object per
+# name, all from csrc/split_unit.hip (not an object itself) with -DFA_SPLIT_UNIT=<name>.  A name here without a row does not compile;
+# a row without a name here does not link.
+SPLIT_UNITS := decode_bf16 decode_fp8 decode_paged_bf16 decode_paged_fp8 \
+               extend_bf16 extend_fp8 extend_paged_bf16 extend_paged_fp8 \
+               extend_window_bf16 extend_window_fp8 extend_window_paged_bf16 extend_window_paged_fp8 \
+               extend_varlen_bf16 extend_varlen_fp8 extend_varlen_paged_bf16 extend_varlen_paged_fp8 \
+               extend_window_varlen_bf16 extend_window_varlen_fp8 extend_window_varlen_paged_bf16 extend_window_varlen_paged_fp8 \
+               decode_sink_bf16 decode_sink_fp8 decode_sink_paged_bf16 decode_sink_paged_fp8 \
+               extend_sink_bf16 extend_sink_fp8 extend_sink_paged_bf16 extend_sink_paged_fp8 \
+               extend_sink_varlen_bf16 extend_sink_varlen_fp8 extend_sink_varlen_paged_bf16 extend_sink_varlen_paged_fp8 \
+               decode_tree_bf16 decode_tree_fp8 decode_tree_paged_bf16 decode_tree_paged_fp8 \
+               extend_tree_bf16 extend_tree_fp8 extend_tree_paged_bf16 extend_tree_paged_fp8
+SPLIT_SRC := $(PKG)/csrc/split_unit.hip
+SPLIT_OBJ := $(SPLIT_UNITS:%=build/obj/inst_%.o)
+KSRC     := $(filter-out $(SPLIT_SRC),$(wildcard $(PKG)/csrc/*.hip))
+KOBJ     := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(KSRC)) $(SPLIT_OBJ)
 KHDR     := $(wildcard $(PKG)/csrc/*.h) $(PKG)/helpers.hpp include/flash_attention.h
 
 # `all` = the product, its C++ harness and driver, the oracle, the microbenchmarks bench.py uses (about 1.5 min with -j4).
@@ -25,14 +40,15 @@ build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
-# the chunked-prefill instantiations of the split-KV kernel at d = 128 (decode_bf16.hip.h with RT = 4: four 16-row tiles per wave, launch
-# bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers
-# in the default form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way
-# (the wildcard takes the ragged instantiations, inst_extend_varlen_*.hip, with them: the same kernel with a per-sequence row count;
-# and the attention-sink ones, inst_extend_sink_*.hip: the same kernel with one more term in its epilogue.  inst_decode_sink_*.hip: RT = 1, no flag;
-# inst_extend_tree_*.hip / inst_decode_tree_*.hip, the tree-masked forms, likewise)
-EXTEND_OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(wildcard $(PKG)/csrc/inst_extend_*.hip))
-$(EXTEND_OBJ): HIPFLAGS += $(MFMA_VGPR)
+# the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
+# tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
+# form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way.  The define
+# tells the unit which way it was built, and the unit refuses to compile if that is not its row's way.  $* is the unit's name
+SPLIT_FLAGS = -DFA_SPLIT_UNIT=$* $(if $(filter extend_%,$*),$(MFMA_VGPR) -DFA_SPLIT_MFMA_VGPR)
+
+$(SPLIT_OBJ): build/obj/inst_%.o: $(SPLIT_SRC) $(KHDR)
+	@mkdir -p build/obj
+	$(HIPCC) $(HIPFLAGS) $(SPLIT_FLAGS) -c -o $@ $<
 
 build/obj/%.o: $(PKG)/csrc/%.hip $(KHDR)
 	@mkdir -p build/obj
@@ -120,14 +136,20 @@ asan: asan-host oracle
 
 # Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
-KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC))
-build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s $(patsubst build/obj/%.o,build/asm/%.s,$(EXTEND_OBJ)): HIPFLAGS += $(MFMA_VGPR)
+KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s: HIPFLAGS += $(MFMA_VGPR)
+define ASM_RECIPE
+@mkdir -p build/asm
+$(HIPCC) $(HIPFLAGS) $(1) -S --cuda-device-only -o $@.tmp $<
+grep -v __hip_cuid_ $@.tmp > $@
+@rm -f $@.tmp
+endef
+
+$(SPLIT_UNITS:%=build/asm/inst_%.s): build/asm/inst_%.s: $(SPLIT_SRC) $(KHDR)
+	$(call ASM_RECIPE,$(SPLIT_FLAGS))
 
 build/asm/%.s: $(PKG)/csrc/%.hip $(KHDR)
-	@mkdir -p build/asm
-	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -o $@.tmp $<
-	grep -v __hip_cuid_ $@.tmp > $@
-	@rm -f $@.tmp
+	$(call ASM_RECIPE)
 
 asm: $(KASM)
 

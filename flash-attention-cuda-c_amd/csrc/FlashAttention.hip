@@ -6,10 +6,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <utility>
 
 #include "../../include/flash_attention.h"
 #include "../helpers.hpp"
@@ -18,6 +20,7 @@
 #include "weights.hip.h"
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
+#include "split_forms.hip.h"
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
 
@@ -502,26 +505,13 @@ static bool cache_extent_ok(const KvCache& c, int d) {
 // rows of one head of one batch entry / page: what NULL K / V strides are dense over
 static int cache_rows(const KvCache& c) { return c.paging ? c.paging->page_size : c.capacity; }
 
-// The instantiation a call launches, of the twenty that exist without sinks: decode's four are WINDOW = true and serve window = 0 too; chunked
-// prefill with windowSize = 0 launches its WINDOW = false units.  sink (a sinks call under ONE split: the kernel that writes O applies
-// the sink): the twelve SINK forms, all WINDOW = true -- chunked prefill with windowSize = 0 then runs at window = 0, as decode does.
-// A tree call (c.tree_mask) launches one of the eight TREE forms whatever the split count and whether or not it has sinks
-static Kernel split_kernel(const SplitCall& c, bool sink) {
-    return by_bool(c.cache.paging != nullptr, [&]<bool PAGED>() {
-        return by_bool(c.cache.kv_dtype == FA_DTYPE_FP8_E4M3, [&]<bool KV8>() {
-            if (c.tree_mask)
-                return by_bool(c.form.extend, [&]<bool EXTEND>() { return split_kernel_of<EXTEND, false, true, PAGED, KV8, true, true>(c.d); });
-            if (sink)
-                return c.form.extend
-                           ? by_bool(c.form.varlen, [&]<bool VARLEN>() { return split_kernel_of<true, VARLEN, true, PAGED, KV8, true>(c.d); })
-                           : split_kernel_of<false, false, true, PAGED, KV8, true>(c.d);
-            if (!c.form.extend) return split_kernel_of<false, false, true, PAGED, KV8>(c.d);
-            return by_bool(c.form.varlen, [&]<bool VARLEN>() {
-                return by_bool(c.window > 0, [&]<bool WINDOW>() { return split_kernel_of<true, VARLEN, WINDOW, PAGED, KV8>(c.d); });
-            });
-        });
-    });
+// The forty units' launchers by row of SPLIT_FORMS (split_forms.hip.h): a unit missing from the build does not link.  Here and not in
+// the header, so that no unit sees -- and compiles -- another unit's kernels
+template <size_t... U>
+constexpr std::array<int (*)(int, unsigned, hipStream_t, const SplitArgs&), sizeof...(U)> split_launchers(std::index_sequence<U...>) {
+    return {&split_unit_launch<(SplitUnit)U>...};
 }
+constexpr auto SPLIT_LAUNCH = split_launchers(std::make_index_sequence<SPLIT_UNITS>{});
 
 // flash_attention_decode*, flash_attention_extend*: one validation and launch sequence
 static int decode_run(SplitCall c) {
@@ -552,7 +542,7 @@ static int decode_run(SplitCall c) {
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
     const int rowsK = cache_rows(c.cache);
-    SinkVarlenDecodeParams p;   // (what every form launches with is a part of it: go, below)
+    SplitArgs p;   // (every form's launcher takes the part of it that is its kernel's parameter type: split_forms.hip.h)
     p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.cache.K; p.V = (const __bf16*)c.cache.V; p.O = c.O; p.lse = c.LSE;
     p.kv_lens = c.cache.kv_lens;
     p.part_o = (float*)c.workspace;
@@ -577,28 +567,20 @@ static int decode_run(SplitCall c) {
     p.cu_q = c.cu_seqlens_q;
     p.B = c.B;
     p.sinks = c.sinks;
+    p.tree_mask = c.tree_mask;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
     // Sinks (c.sinks): the kernel that writes O applies them -- under one split the SINK split kernel; under more
     // the split kernel is the call's own without sinks (the slabs hold the keys alone) and the SINK combine adds the sink, once per row
     // Tree masks (c.tree_mask): the split kernel is the TREE form under any split count -- it takes the sinks
     // pointer, NULL or not, and reads it under one split only -- and the combine is the one the call would launch without the mask
-    const bool sink = c.sinks != nullptr, tree = c.tree_mask != nullptr;
-    const Kernel sk = split_kernel(c, sink && r.ns == 1);
-    const auto go = [&](const Kernel& k, unsigned grid, int lds, bool with_sinks, bool with_tree = false) {   // each kernel with its exact parameter type
-        if (f.varlen) return with_sinks ? launch(k, grid, 256, lds, st, p) : launch(k, grid, 256, lds, st, (VarlenDecodeParams)p);
-        TreeDecodeParams pt;
-        (DecodeParams&)pt = p;
-        pt.sinks = p.sinks;
-        pt.tree_mask = c.tree_mask;
-        if (with_tree) return launch(k, grid, 256, lds, st, pt);
-        return with_sinks ? launch(k, grid, 256, lds, st, (SinkDecodeParams)pt) : launch(k, grid, 256, lds, st, (DecodeParams)p);
-    };
-    static_assert(DecodeCfg<128>::THREADS == 256);
-    const hipError_t e = go(sk, (unsigned)r.grid, sk.lds_bytes, sink && r.ns == 1, tree);
-    if (e != hipSuccess || r.ns == 1) return (int)e;
-    const Kernel ck = f.varlen ? (sink ? extend_varlen_sink_combine_kernel_of(d) : extend_varlen_combine_kernel_of(d))
-                               : (sink ? decode_sink_combine_kernel_of(d) : decode_combine_kernel_of(d));
-    return (int)go(ck, (unsigned)rows, 0, sink);
+    const bool sink = c.sinks != nullptr;
+    const SplitKind form = split_form_of(f.extend, f.varlen, c.window > 0, pg != nullptr, c.cache.kv_dtype == FA_DTYPE_FP8_E4M3,
+                                         sink && r.ns == 1, c.tree_mask != nullptr);
+    const int unit = split_unit_of(form);
+    if (unit < 0) return FA_ERR_BAD_FLAGS;   // (no entry point builds such a call: split_forms.hip.h asserts it for varlen <= extend, no ragged tree)
+    rc = SPLIT_LAUNCH[unit](d, (unsigned)r.grid, st, p);
+    if (rc != FA_OK || r.ns == 1) return rc;
+    return combine_launch(f.varlen, sink, d, (unsigned)rows, st, p);
 }
 
 // ---- K/V cache append (kv_append.hip.h) ----

@@ -696,18 +696,7 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const typename Spli
     if (p.lse && c == 0) p.lse[row] = M + __logf(W);
 }
 
-// ---- selectors (the inst_decode_*.hip and inst_extend_*.hip units: one per cache form and call family) ----
-struct Kernel;
-// The split kernel at D = d (128, else 64) with RT = EXTEND ? ExtendCfg<D>::RT : 1 and LDS for the cache's element size.  Defined in
-// split_kv_inst.hip.h and instantiated explicitly, once each, by the units: the four decode forms (EXTEND = VARLEN = false, WINDOW = true,
-// which also serves window = 0) and all sixteen chunked-prefill forms; with SINK the twelve WINDOW = true forms of those, by the
-// inst_decode_sink_*.hip and inst_extend_sink_*.hip units; with TREE (and SINK, WINDOW; VARLEN = false) the eight of {decode, chunked
-// prefill} x the four cache forms, by the inst_decode_tree_*.hip and inst_extend_tree_*.hip units.  No other combination exists
-template <bool EXTEND, bool VARLEN, bool WINDOW, bool PAGED, bool KV8, bool SINK = false, bool TREE = false>
-Kernel split_kernel_of(int d);
-Kernel extend_varlen_combine_kernel_of(int d);
-Kernel decode_combine_kernel_of(int d);
-Kernel extend_varlen_sink_combine_kernel_of(int d);   // (the SINK combines: inst_extend_sink_varlen_bf16.hip, inst_decode_sink_bf16.hip)
-Kernel decode_sink_combine_kernel_of(int d);
+// ---- which instantiations exist, which one a call launches and how the host reaches it: split_forms.hip.h (the one table; one
+// translation unit per row, all from split_unit.hip) and, for the four combine kernels, inst_split_combine.hip ----
 
 }  // namespace fa

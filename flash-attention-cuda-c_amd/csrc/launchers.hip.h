@@ -60,8 +60,8 @@ hipError_t launch(const Kernel& k, unsigned grid, int threads, int lds_bytes, hi
 }
 
 // ---- group selectors (each defined in exactly one inst_*.hip) ----
-// (the split-KV, combine, append and backward selectors are declared beside their kernels: decode_bf16.hip.h -- one template,
-// split_kernel_of, instantiated once per inst_decode_*.hip / inst_extend_*.hip unit -- kv_append.hip.h, bwd_bf16.hip.h)
+// (the append and backward selectors are declared beside their kernels: kv_append.hip.h, bwd_bf16.hip.h; the split-KV kernel's forms and
+// its combine have launchers in place of selectors -- split_forms.hip.h: one table of the forms, one unit per row built from split_unit.hip)
 // Kernels taking (Params):
 // bf16 inputs, persistent kernel instantiated at D = 128 / 64; pad: the tensors' head dimension is smaller than D; lse: the call
 // wants the LSE (without the mask that selects the instantiation that keeps the fp32 sum of the unrounded weights: computers16.hip.h)

@@ -419,7 +419,7 @@ def plan_of(spec, ns=0, o_dtype=bf, W=None):
 
 
 def kernel_name(spec, W=None):
-    """the split_kernel_of combination a call of this spec runs, as csrc/decode_bf16.hip.h names it"""
+    """the split-KV form a call of this spec runs: the flags of its row in csrc/split_forms.hip.h, under the label profiles/long_cache_gpu.log uses"""
     W = spec.W if W is None else W
     ext = spec.kind != "decode"
     return (f"split_kernel_of<EXTEND={int(ext)}, VARLEN={int(spec.kind == 'varlen')}, WINDOW={int(bool(W) or not ext)}, PAGED={int(bool(spec.page))}, "

@@ -69,6 +69,7 @@ def run(case, spec, cache, ns_asked, o_dtype=bf, W=None):
         torch.cuda.synchronize()
         got = cp.check(f"{case}, splits {ns_asked} -> {ns}, round {n}", spec, q, exp, O, lse, ns, rpb, cache)
         total = dict(rows=total["rows"] + got["rows"], hidden=total["hidden"] + got["hidden"], worst=max(total["worst"], got["worst"]))
+    # (log labels only, as in cp.kernel_name: the names profiles/long_cache_gpu.log uses; the forms are the rows of csrc/split_forms.hip.h)
     combine = "" if ns == 1 else f" + {'extend_varlen_combine_kernel_of' if spec.kind == 'varlen' else 'decode_combine_kernel_of'}(d={spec.d})"
     keys = max(L for s, L in spec.seqs if s)
     print(f"{case}: {spec.form()}{f' W {W}' if W is not None else (f' W {spec.W}' if spec.W else '')}, {cp.kernel_name(spec, W)}{combine}, "

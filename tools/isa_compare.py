@@ -4,7 +4,8 @@ function numbers in block labels ignored) and by their resource metadata (VGPRs,
 usage: isa_compare.py old.s new.s              -- one file each
        isa_compare.py old_dir new_dir          -- every *.s in each directory
        isa_compare.py old new REGEX=REPL ...   -- rename the old side's symbols first (re.sub), for a kernel whose name changed
-Kernels are paired by symbol name; prints one line per kernel that differs or exists on one side only, then a summary line."""
+Kernels are paired by symbol name; prints one line per kernel that differs, exists on one side only or appears in two files of one side,
+then a summary line."""
 import glob
 import os
 import re
@@ -57,7 +58,10 @@ def load(path):
     files = sorted(glob.glob(os.path.join(path, "*.s"))) if os.path.isdir(path) else [path]
     out = {}
     for f in files:
-        out.update(kernels(f))
+        for k, v in kernels(f).items():
+            if k in out:   # (a kernel compiled into two units: only one copy is launched, and only one would be compared)
+                print(f"TWICE IN {path}: {k} (again in {os.path.basename(f)})")
+            out[k] = v
     return out
 
 
