@@ -110,8 +110,9 @@ SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # asan-host: the library's host code under the sanitizers, and the LADDERS -- stand-alone programs (their own main, the same flags,
 # nothing preloaded; tests/host_ladder.h is what they share), each built and run: the validation ladders and plans of the ragged entry
 # points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins,
-# of the two tree-masked ones beside their sink twins
-LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder
+# of the two tree-masked ones beside their sink twins, of the speculative step's rope_append_pos and kv_accept ones beside their rope_append
+# and kv_append twins
+LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder
 $(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip

@@ -81,6 +81,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_rope_append", "flash_attention_rope_append_paged", "flash_attention_rope_append_varlen",
            "flash_attention_rope_append_paged_varlen",
            "flash_attention_tree", "flash_attention_tree_paged", "flash_attention_tree_plan",
+           "flash_attention_rope_append_pos", "flash_attention_rope_append_paged_pos",
+           "flash_attention_kv_accept", "flash_attention_kv_accept_paged",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -109,6 +111,10 @@ _APPEND_SYMBOLS = {(False, False): "flash_attention_kv_append", (True, False): "
 # ... _ROPE_SYMBOLS[paged, ragged]: the append twin with the rotary embedding fused in
 _ROPE_SYMBOLS = {(False, False): "flash_attention_rope_append", (True, False): "flash_attention_rope_append_paged",
                  (False, True): "flash_attention_rope_append_varlen", (True, True): "flash_attention_rope_append_paged_varlen"}
+# ... the speculative step's write side: _ROPE_POS_SYMBOLS[paged], the uniform rope twin with ``posOffsets`` after ``cosSin``, and
+# _ACCEPT_SYMBOLS[paged], the in-cache acceptance of the verified path
+_ROPE_POS_SYMBOLS = {False: "flash_attention_rope_append_pos", True: "flash_attention_rope_append_paged_pos"}
+_ACCEPT_SYMBOLS = {False: "flash_attention_kv_accept", True: "flash_attention_kv_accept_paged"}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -213,6 +219,14 @@ def lib() -> ctypes.CDLL:
         for (paged, ragged), name in _ROPE_SYMBOLS.items():
             fn = getattr(L, name)
             fn.argtypes = [vp] * 7 + [vp] * ragged + [vp] + [vp] * paged + [vp, vp] + [i] * 4 + paging(paged) + [i] * 6 + [sp] * 6 + [vp]
+            fn.restype = i
+        for paged, name in _ROPE_POS_SYMBOLS.items():      # posOffsets after cosSin
+            fn = getattr(L, name)
+            fn.argtypes = [vp] * 8 + [vp] + [vp] * paged + [vp, vp] + [i] * 4 + paging(paged) + [i] * 6 + [sp] * 6 + [vp]
+            fn.restype = i
+        for paged, name in _ACCEPT_SYMBOLS.items():        # the caches, kvLens, the table (paged), acceptIdx, acceptLens
+            fn = getattr(L, name)
+            fn.argtypes = [vp] * 3 + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i] + [sp] * 2 + [vp]
             fn.restype = i
         for by_window in _PLAN_SYMBOLS.values():
             for window, name in enumerate(by_window):
@@ -888,8 +902,8 @@ def tree_mask_from_parents(parents):
 
 def tree_depths(parents):
     """Depth of every node of a draft tree (``parents`` as for ``tree_mask_from_parents``): ``torch.int32 [B, Sq]``, 0 for a root.
-    Node i's position in ITS sequence is ``base + depth`` -- what a depth-based rotary embedding needs (``rope_cache_append`` rotates
-    at cache positions ``base + i``)."""
+    Node i's position in ITS sequence is ``base + depth``: the result is what ``rope_cache_append(..., pos_offsets=)`` takes, which
+    then rotates node i at ``base + depth`` and still stores it at slot ``base + i``."""
     import torch
     p = _tree_parents(parents)
     dep = torch.zeros_like(p)
@@ -899,13 +913,96 @@ def tree_depths(parents):
     return dep.to(torch.int32)
 
 
-def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream, rope=None):
+def tree_path(parents, leaf):
+    """The accepted path of a draft tree as ``kv_cache_accept`` takes it: ``parents`` as for ``tree_mask_from_parents``, ``leaf`` an
+    integer tensor ``[B]``, the last accepted node of every sequence (clamped into the tree).  Returns ``(accept_idx, accept_lens)``,
+    int32 ``[B, Sq]`` and ``[B]`` on the device of ``parents``: the nodes from the root down to ``leaf``, the tail padded with
+    ``Sq - 1``, and their count ``depth(leaf) + 1``.  Torch ops only, a number of steps known from the shape.  A DEVICE tensor of
+    parents is taken as it is -- nothing is read back to the host, so a captured graph may contain the call; entries that are not
+    parents (>= their index, < -1) give some path inside the tree, never an index outside it.  Parents given on the host go through
+    the check of ``tree_mask_from_parents``."""
+    import torch
+    if isinstance(parents, torch.Tensor) and parents.is_cuda:
+        if parents.dim() != 2 or not 1 <= parents.shape[1] <= FA_TREE_MAX_Q or parents.dtype.is_floating_point or parents.dtype == torch.bool:
+            raise ValueError(f"parents must be integers [B, Sq] with 1 <= Sq <= {FA_TREE_MAX_Q}")
+        p = parents.long()
+    else:
+        p = _tree_parents(parents)
+    B, Sq = p.shape
+    leaf = torch.as_tensor(leaf, device=p.device)
+    if leaf.shape != (B,) or leaf.dtype.is_floating_point or leaf.dtype == torch.bool:
+        raise ValueError("leaf must be an integer tensor [B]")
+    node = leaf.long().clamp(0, Sq - 1)
+    up = torch.full((B, Sq), -1, dtype=torch.int64, device=p.device)      # up[:, k]: the k-th node from the leaf upwards, -1 past the root
+    for k in range(Sq):
+        up[:, k] = node
+        nxt = torch.gather(p, 1, node.clamp(min=0)[:, None])[:, 0].clamp(-1, Sq - 1)
+        node = torch.where(node >= 0, nxt, node)
+    n = (up >= 0).sum(dim=1)
+    at = n[:, None] - 1 - torch.arange(Sq, device=p.device)[None, :]      # root first: entry t is up[n - 1 - t]
+    idx = torch.where(at >= 0, torch.gather(up, 1, at.clamp(min=0)), torch.full_like(up, Sq - 1))
+    return idx.to(torch.int32), n.to(torch.int32)
+
+
+def _accept_front(name, K, V, block_table, accept_idx, accept_lens, kv_lens, stream):
+    """The kv_cache_accept* fronts: the cache checks of the append fronts without new rows, and the entry point of _ACCEPT_SYMBOLS"""
+    import torch
+    paged = block_table is not None
+    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K_cache, V_cache", "[B, Hkv, capacity, d]")
+    if not (getattr(K, "is_cuda", False) and getattr(V, "is_cuda", False) and getattr(accept_idx, "is_cuda", False)
+            and getattr(accept_lens, "is_cuda", False) and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    if K.dim() != 4 or K.shape != V.shape or K.dtype != V.dtype or K.device != V.device:
+        raise ValueError(f"{kv} must be {layout} of one dtype on one device")
+    if K.dtype != torch.bfloat16 and (f8 is None or K.dtype != f8):
+        raise TypeError(f"{kv} must be bfloat16 or float8_e4m3fn")
+    if accept_idx.dtype != torch.int32 or accept_idx.dim() != 2 or not accept_idx.is_contiguous() or accept_idx.device != K.device:
+        raise ValueError("accept_idx must be a dense int32 device tensor [B, Sq] on the device of the caches")
+    B, Sq = accept_idx.shape
+    if not paged and K.shape[0] != B:
+        raise ValueError(f"{kv} {layout}: the batch of accept_idx")
+    if accept_lens.dtype != torch.int32 or accept_lens.shape != (B,) or not accept_lens.is_contiguous() or accept_lens.device != K.device:
+        raise ValueError("accept_lens must be a dense int32 device tensor [B] on the device of the caches")
+    capacity, tables, geometry = _cache_geometry(K, block_table, B)
+    if Sq < 1 or Sq > FA_TREE_MAX_Q or Sq > capacity:
+        raise ValueError(f"Sq = {Sq} draft nodes: must be 1 .. min(FA_TREE_MAX_Q, the capacity) ({min(FA_TREE_MAX_Q, capacity)})")
+    _check_kv_lens(kv_lens, B)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(K.device):
+        st = [_strides(K), _strides(V)]
+        rc = getattr(lib(), _ACCEPT_SYMBOLS[paged])(
+            K.data_ptr(), V.data_ptr(), ptr(kv_lens), *map(ptr, tables), accept_idx.data_ptr(), accept_lens.data_ptr(), B, K.shape[1], Sq,
+            *geometry, K.shape[3], _dtype_code(K.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+    _check(rc)
+
+
+def kv_cache_accept(K_cache, V_cache, accept_idx, accept_lens, kv_lens=None, stream=None):
+    """IN-CACHE ACCEPTANCE of a speculative step, in place; returns None.  The draft's Sq nodes lie at the cache positions
+    ``base + 0 .. base + Sq - 1`` (``kv_lens`` still counts them: ``base = min(kv_lens[b], capacity) - Sq``); per sequence, for
+    ``t = 0 .. n - 1`` in ascending order, K and V of every head at ``base + accept_idx[b, t]`` are copied to ``base + t``
+    (``n = clamp(accept_lens[b], 0, Sq)``, indices clamped into the draft) -- a copy of bits, bf16 or float8_e4m3fn.  For the path
+    of a topologically ordered tree (``tree_path``) row t becomes the draft's row ``accept_idx[b, t]``; with
+    ``rope_cache_append(..., pos_offsets=tree_depths(parents))`` the cache then holds what a linear ``rope_cache_append`` of the
+    accepted tokens writes, byte for byte.  Nothing else is written, ``kv_lens`` included: follow with
+    ``kv_lens -= Sq - accept_lens``.  ``accept_idx`` int32 ``[B, Sq]``, ``accept_lens`` int32 ``[B]``, device tensors read by the
+    kernel: no synchronisation, one graph for the whole step.  1 <= Sq <= FA_TREE_MAX_Q.  No CPU fallback."""
+    _accept_front("kv_cache_accept", K_cache, V_cache, None, accept_idx, accept_lens, kv_lens, stream)
+
+
+def kv_cache_accept_paged(K_pool, V_pool, block_table, accept_idx, accept_lens, kv_lens=None, stream=None):
+    """``kv_cache_accept`` in the PAGED caches of ``kv_cache_append_paged``.  A move whose source or destination page entry is
+    outside [0, P) is skipped, never clamped."""
+    _accept_front("kv_cache_accept_paged", K_pool, V_pool, block_table, accept_idx, accept_lens, kv_lens, stream)
+
+
+def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, k_descale, v_descale, stream, rope=None, pos_offsets=None):
     """The kv_cache_append* and rope_cache_append* fronts (``name``: the front's, in the error texts): a ``block_table`` makes the call
     paged (K, V are then the pools) and ``cu_seqlens_q`` ragged (the new rows are then packed by token: Sq is the bound on the packed
     rows, not capped at the capacity, and the batch is cu_seqlens_q's).  The tensor checks of the decode fronts (``_decode_inputs``,
     the new rows in the place of Q), the bounds of Sq, and the entry point of _APPEND_SYMBOLS.  ``rope`` = (Q, Q_out, cos_sin,
     interleaved) makes it the fused call: Q, Q_out and the table are checked as well, the entry point is _ROPE_SYMBOLS' and the
-    rotated queries are returned (ragged: ``[T, H, d]``)."""
+    rotated queries are returned (ragged: ``[T, H, d]``).  ``pos_offsets`` (uniform fused calls only) makes it _ROPE_POS_SYMBOLS'."""
     import torch
     paged, ragged = block_table is not None, cu_seqlens_q is not None
     Q, Q_out, cos_sin, interleaved = rope or (None,) * 4
@@ -952,6 +1049,10 @@ def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, 
         raise ValueError(f"cos_sin [max_pos, rot_dim]: rot_dim a multiple of 16 in 16 .. d, max_pos at least the capacity ({capacity})")
     if Q_out is not None and (not getattr(Q_out, "is_cuda", False) or Q_out.shape != Q.shape or Q_out.dtype != Q.dtype or Q_out.device != Q.device):
         raise ValueError("Q_out must be a device tensor shaped like Q, of its dtype, on its device")
+    po = pos_offsets
+    if po is not None and (not getattr(po, "is_cuda", False) or po.dtype != torch.int32 or tuple(po.shape) != (B, Sq) or not po.is_contiguous()
+                           or po.device != Q.device):
+        raise ValueError("pos_offsets must be a dense int32 device tensor [B, Sq] on the device of Q")
     with torch.cuda.device(Q.device):
         if Q_out is None:
             s = stream if stream is not None else torch.cuda.current_stream()
@@ -959,9 +1060,10 @@ def _append_front(name, K_new, V_new, K, V, block_table, cu_seqlens_q, kv_lens, 
                 Q_out = torch.empty((Sq, Q.shape[1], d), dtype=Q.dtype, device=Q.device).unsqueeze(0).transpose(1, 2) if ragged \
                     else torch.empty(Q.shape, dtype=Q.dtype, device=Q.device)
         st = [_strides(x) for x in (Q, K_new, V_new, Q_out, K, V)]
-        rc = getattr(lib(), _ROPE_SYMBOLS[paged, ragged])(
+        symbol = _ROPE_SYMBOLS[paged, ragged] if po is None else _ROPE_POS_SYMBOLS[paged]
+        rc = getattr(lib(), symbol)(
             Q.data_ptr(), K_new.data_ptr(), V_new.data_ptr(), Q_out.data_ptr(), K.data_ptr(), V.data_ptr(), t.data_ptr(),
-            *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Q.shape[1], Hkv,
+            *(() if po is None else (po.data_ptr(),)), *((ptr(cu_seqlens_q),) if ragged else ()), ptr(kv_lens), *map(ptr, tables), ptr(k_descale), ptr(v_descale), B, Q.shape[1], Hkv,
             Sq, *geometry, d, rot_dim, max_pos, int(bool(interleaved)), _dtype_code(K_new.dtype), _dtype_code(K.dtype),
             *[ctypes.byref(x) for x in st], _stream_ptr(stream))
     _check(rc)
@@ -1032,7 +1134,7 @@ def rope_table(max_pos, rot_dim, base=10000.0, device=None):
 
 
 def rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens=None, interleaved=False, k_descale=None, v_descale=None,
-                      Q_out=None, stream=None):
+                      Q_out=None, stream=None, pos_offsets=None):
     """``kv_cache_append`` with the rotary embedding fused in: ONE launch rotates the new K rows at their cache positions and stores
     them into ``K_cache`` (bf16 or float8_e4m3fn), appends ``V_new`` exactly as ``kv_cache_append`` does, and rotates the step's query
     rows ``Q`` (bf16 ``[B, H, Sq, d]``, Hkv dividing H; strided views accepted) at the same positions.  Returns the rotated queries:
@@ -1046,17 +1148,23 @@ def rope_cache_append(Q, K_new, V_new, K_cache, V_cache, cos_sin, kv_lens=None, 
     position ``flash_attention_decode`` / ``flash_attention_extend`` give it, and every Q row is written.  Values:
     ``y1 = fma(x1, c, -(x2 s))``, ``y2 = fma(x2, c, x1 s)`` in fp32, rounded once to bf16; K then goes through ``kv_cache_append``'s
     value rule, so the caches equal ``kv_cache_append`` of the bf16 rotation of K, byte for byte.  A decode step is ``kv_lens += Sq;
-    Qr = rope_cache_append(...); flash_attention_decode(Qr, ...)``, one graph.  No CPU fallback."""
+    Qr = rope_cache_append(...); flash_attention_decode(Qr, ...)``, one graph.  No CPU fallback.
+
+    ``pos_offsets``: None, or an int32 device tensor ``[B, Sq]`` read by the kernel: row i (Q and K) is then rotated at
+    ``max(first + clamp(pos_offsets[b, i], 0, Sq - 1), 0)``, ``first = clamp(kv_lens[b], 1, capacity) - Sq``, in place of
+    ``first + i``; the row's SLOT, V and everything else are unchanged, and ``pos_offsets[b, i] = i`` is the call without it.  For a
+    draft tree pass ``tree_depths(parents)``: a speculative step is ``kv_lens += Sq; Qr = rope_cache_append(..., pos_offsets=depths);
+    flash_attention_tree(Qr, ...); (sampling); kv_cache_accept(..., *tree_path(parents, leaf)); kv_lens -= Sq - accept_lens``."""
     return _append_front("rope_cache_append", K_new, V_new, K_cache, V_cache, None, None, kv_lens, k_descale, v_descale, stream,
-                         rope=(Q, Q_out, cos_sin, interleaved))
+                         rope=(Q, Q_out, cos_sin, interleaved), pos_offsets=pos_offsets)
 
 
 def rope_cache_append_paged(Q, K_new, V_new, K_pool, V_pool, block_table, cos_sin, kv_lens=None, interleaved=False, k_descale=None,
-                            v_descale=None, Q_out=None, stream=None):
+                            v_descale=None, Q_out=None, stream=None, pos_offsets=None):
     """``rope_cache_append`` into the PAGED caches of ``kv_cache_append_paged`` (max_pos at least ``max_pages * page``).  A table
-    entry outside [0, P) skips the K and V rows of its page; their Q rows are still written."""
+    entry outside [0, P) skips the K and V rows of its page; their Q rows are still written.  ``pos_offsets`` as there."""
     return _append_front("rope_cache_append_paged", K_new, V_new, K_pool, V_pool, block_table, None, kv_lens, k_descale, v_descale, stream,
-                         rope=(Q, Q_out, cos_sin, interleaved))
+                         rope=(Q, Q_out, cos_sin, interleaved), pos_offsets=pos_offsets)
 
 
 def rope_cache_append_varlen(Q, K_new, V_new, K_cache, V_cache, cu_seqlens_q, cos_sin, kv_lens=None, interleaved=False, k_descale=None,

@@ -21,6 +21,7 @@
 #include "bwd_bf16.hip.h"
 #include "decode_bf16.hip.h"
 #include "split_forms.hip.h"
+#include "kv_accept.hip.h"
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
 
@@ -399,13 +400,24 @@ struct AppendCall {
 };
 
 // What flash_attention_rope_append* adds to the append call of the same form: the query rows in and out, the cos / sin table and the
-// pair style
+// pair style.  pos_offsets: NULL, or the [B, Sq] row offsets of the _pos entry points (the last member: every other
+// entry point's initialiser leaves it NULL); with_pos says which, so that a _pos call with a NULL array is refused
 struct RopeCall {
     const void* Q;
     void* Qout;
     const float* cos_sin;
     int H, rot_dim, max_pos, interleaved;
     const fa_strides *sQ, *sQout;
+    bool with_pos;
+    const int32_t* pos_offsets;
+};
+
+// A call of the acceptance kernel (kv_accept.hip.h): the accepted path of a draft of Sq nodes moved to the front of the draft's slots
+struct AcceptCall {
+    KvCache cache;                 // k_descale / v_descale NULL: the move is a bit copy
+    const int32_t *accept_idx, *accept_lens;
+    int B, Hkv, Sq, d;
+    void* stream;
 };
 
 struct DecodeRoute {
@@ -601,11 +613,12 @@ static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
     const DecodePaging* pg = c.cache.paging;
     const int B = c.B, Hkv = c.Hkv, Sq = c.Sq, d = c.d, kv_dtype = c.cache.kv_dtype;
     if (!c.Knew || !c.Vnew || !c.cache.K || !c.cache.V || (pg && !pg->table) || (c.varlen && !c.cu_seqlens_q)) return FA_ERR_NULL_POINTER;
-    if (rope && (!rope->Q || !rope->Qout || !rope->cos_sin)) return FA_ERR_NULL_POINTER;
+    if (rope && (!rope->Q || !rope->Qout || !rope->cos_sin || (rope->with_pos && !rope->pos_offsets))) return FA_ERR_NULL_POINTER;
     if (!aligned16(c.Knew) || !aligned16(c.Vnew) || !aligned16(c.cache.K) || !aligned16(c.cache.V)) return FA_ERR_MISALIGNED;
     if (rope && (!aligned16(rope->Q) || !aligned16(rope->Qout) || !aligned16(rope->cos_sin))) return FA_ERR_MISALIGNED;
     int rc = cache_check_arrays(c.cache, c.cu_seqlens_q);
     if (rc != FA_OK) return rc;
+    if (rope && misaligned4(rope->pos_offsets)) return FA_ERR_MISALIGNED;
     if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
     const int Sk = c.cache.capacity;
     if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
@@ -673,6 +686,12 @@ static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
             const RopeAppendVarlenParams rv{r, c.cu_seqlens_q, B, rope_token_blocks};
             return (int)launch(rope_append_varlen_kernel_of(d, kv8, pg != nullptr), rope_grid, KvAppendCfg::THREADS, 0, st, rv);
         }
+        if (rope->with_pos) {   // (no ragged _pos entry point: c.varlen is false)
+            RopePosParams rp;
+            static_cast<RopeAppendParams&>(rp) = r;
+            rp.pos_offsets = rope->pos_offsets;
+            return (int)launch(rope_append_pos_kernel_of(d, kv8, pg != nullptr), rope_grid, KvAppendCfg::THREADS, 0, st, rp);
+        }
         return (int)launch(rope_append_kernel_of(d, kv8, pg != nullptr), rope_grid, KvAppendCfg::THREADS, 0, st, r);
     }
     if (c.varlen) {
@@ -682,6 +701,48 @@ static int kv_append_run(AppendCall c, const RopeCall* rope = nullptr) {
     }
     const Kernel k = kv_append_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
     return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, st, p);
+}
+
+// ---- in-cache acceptance (kv_accept.hip.h) ----
+// flash_attention_kv_accept*: the append's ladder without the new rows -- pointers, alignment, cache_check_arrays with the two index
+// arrays beside it, cache_capacity, shape (the draft capped at FA_TREE_MAX_Q and at the capacity), kv_dtype, dHead, cache strides,
+// extent, grid: a cache the append accepts, accept accepts.  One wave per (sequence, K or V, 64 consecutive (K/V head, 16-byte chunk)
+// pairs), four waves per workgroup.
+static int kv_accept_run(AcceptCall c) {
+    const DecodePaging* pg = c.cache.paging;
+    const int B = c.B, Hkv = c.Hkv, Sq = c.Sq, d = c.d, kv_dtype = c.cache.kv_dtype;
+    if (!c.cache.K || !c.cache.V || (pg && !pg->table) || !c.accept_idx || !c.accept_lens) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.cache.K) || !aligned16(c.cache.V)) return FA_ERR_MISALIGNED;
+    int rc = cache_check_arrays(c.cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if (misaligned4(c.accept_idx) || misaligned4(c.accept_lens)) return FA_ERR_MISALIGNED;
+    if ((rc = cache_capacity(c.cache)) != FA_OK) return rc;
+    const int Sk = c.cache.capacity;
+    if (B <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || d <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || Sq > Sk || Sq > FA_TREE_MAX_Q || (int64_t)B * Hkv > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (kv_dtype != FA_DTYPE_BF16 && kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (d != 64 && d != 128) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (!cache_strides_ok(c.cache, d)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(c.cache, d)) return FA_ERR_BAD_SHAPE;
+    const int chunks = d * elem_size(kv_dtype) / 16;                       // 16-byte chunks per row
+    const int head_groups = (int)(((int64_t)Hkv * chunks + 63) / 64);
+    const int64_t grid = ((int64_t)B * head_groups * 2 + KvAcceptCfg::WAVES - 1) / KvAcceptCfg::WAVES;
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    const int rowsK = cache_rows(c.cache);
+    KvAcceptParams p;
+    p.K = const_cast<void*>(c.cache.K); p.V = const_cast<void*>(c.cache.V);   // (the entry points take them writable)
+    p.kv_lens = c.cache.kv_lens;
+    p.block_table = pg ? pg->table : nullptr;
+    p.accept_idx = c.accept_idx; p.accept_lens = c.accept_lens;
+    resolve_strides(c.cache.sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+    resolve_strides(c.cache.sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.B = B; p.Hkv = Hkv; p.Sq = Sq; p.cap = Sk; p.head_groups = head_groups;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    const Kernel k = kv_accept_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
+    return (int)launch(k, (unsigned)grid, KvAcceptCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
 }
 }  // namespace fa
 
@@ -1335,6 +1396,56 @@ int flash_attention_rope_append_paged_varlen(const void* Q, const void* Knew, co
                              &rope);
 }
 
+// ---- the speculative step's write side: the rope twins with posOffsets after cosSin; in-cache acceptance ----
+int flash_attention_rope_append_pos(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V, const float* cosSin,
+                                    const int32_t* posOffsets, const int32_t* kvLens, const float* kDescale, const float* vDescale,
+                                    int batchSize, int numHeads, int numHeadsKV, int seqLenNew, int seqLenK, int dHead, int rotDim,
+                                    int maxPos, int interleaved, int dtype, int kv_dtype, const fa_strides* sQ, const fa_strides* sKnew,
+                                    const fa_strides* sVnew, const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV,
+                                    void* stream) {
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout, true, posOffsets};
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
+}
+
+int flash_attention_rope_append_paged_pos(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                          const float* cosSin, const int32_t* posOffsets, const int32_t* kvLens,
+                                          const int32_t* blockTable, const float* kDescale, const float* vDescale, int batchSize,
+                                          int numHeads, int numHeadsKV, int seqLenNew, int numPages, int pageSize, int maxPagesPerSeq,
+                                          int64_t tableStride, int dHead, int rotDim, int maxPos, int interleaved, int dtype,
+                                          int kv_dtype, const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
+                                          const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    const fa::RopeCall rope{Q, Qout, cosSin, numHeads, rotDim, maxPos, interleaved, sQ, sQout, true, posOffsets};
+    return fa::kv_append_run({.varlen = false, .Knew = Knew, .Vnew = Vnew,
+                              .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale,
+                                        .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenNew, .d = dHead, .dtype = dtype, .sKnew = sKnew,
+                              .sVnew = sVnew, .stream = stream},
+                             &rope);
+}
+
+int flash_attention_kv_accept(void* K, void* V, const int32_t* kvLens, const int32_t* acceptIdx, const int32_t* acceptLens,
+                              int batchSize, int numHeadsKV, int seqLenDraft, int seqLenK, int dHead, int kv_dtype, const fa_strides* sK,
+                              const fa_strides* sV, void* stream) {
+    return fa::kv_accept_run({.cache = {.K = K, .V = V, .kv_lens = kvLens, .kv_dtype = kv_dtype, .capacity = seqLenK, .sK = sK, .sV = sV},
+                              .accept_idx = acceptIdx, .accept_lens = acceptLens, .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenDraft,
+                              .d = dHead, .stream = stream});
+}
+
+int flash_attention_kv_accept_paged(void* Kpool, void* Vpool, const int32_t* kvLens, const int32_t* blockTable, const int32_t* acceptIdx,
+                                    const int32_t* acceptLens, int batchSize, int numHeadsKV, int seqLenDraft, int numPages,
+                                    int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, int kv_dtype, const fa_strides* sK,
+                                    const fa_strides* sV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::kv_accept_run({.cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .kv_dtype = kv_dtype, .sK = sK, .sV = sV, .paging = &pg},
+                              .accept_idx = acceptIdx, .accept_lens = acceptLens, .B = batchSize, .Hkv = numHeadsKV, .Sq = seqLenDraft,
+                              .d = dHead, .stream = stream});
+}
 
 // ---- tree-masked verification: the sinks entry points of decode with the mask words, is_causal set ----
 // the call family of a draft of seqLenQ nodes: decode's up to FA_DECODE_MAX_Q, chunked prefill's above (any d but 64 / 128 is refused later)

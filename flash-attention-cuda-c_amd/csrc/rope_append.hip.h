@@ -28,9 +28,16 @@
 //     not the Q rows.
 //   * RAGGED kernel: kv_append_varlen_kernel's: token-major, D / 16 lanes per token, a binary search in cu_q, per-lane position and
 //     page entry; a token no sequence owns is neither read nor written.
+//   * POSITION OFFSETS (POS; flash_attention_rope_append_pos, _paged_pos): the uniform kernel with the table row of
+//     new row i taken from pos_offsets[b, i] instead of i -- max(first + clamp(pos_offsets[b, i], 0, Sq - 1), 0), for Q and for K: a
+//     draft tree's node rotates at base + its depth.  The row's SLOT, its V and everything else are the twin's; the offset i is the twin.
+//     A lane loads the offsets of the rows it owns (4 bytes each, only where the Q row exists) before their table rows; the clamp keeps
+//     the table row below Lq, so a stale offset gives a wrong angle, never an address outside the table.
 //   * Every address is 64-bit arithmetic on element strides.  No LDS, no scratch, no atomics; every store is a vector store of 16
 //     bytes (8 into an fp8 cache).
 #pragma once
+
+#include <type_traits>
 
 #include "kv_append.hip.h"
 
@@ -46,6 +53,11 @@ struct RopeAppendParams {
     int rot;                      // rotDim: a multiple of 16 in [16, D]
     int interleaved;              // 0: pairs (j, j + rot / 2); 1: pairs (2j, 2j + 1)
     int head_slices, heads_per_slice;   // ceil(Hkv / heads_per_slice) slices of consecutive K/V heads
+};
+
+// the POS kernel's: a type of its own, so that RopeAppendParams keeps its size and layout
+struct RopePosParams : RopeAppendParams {
+    const int32_t* pos_offsets;   // [B][Sq] (device memory)
 };
 
 struct RopeAppendVarlenParams {
@@ -168,8 +180,8 @@ __device__ __forceinline__ void rope_heads(const RopeAppendParams& r, int slice,
     }
 }
 
-template <int D, bool KV8, bool PAGED>
-__global__ __launch_bounds__(256) void rope_append_kernel(const RopeAppendParams r) {
+template <int D, bool KV8, bool PAGED, bool POS = false>
+__global__ __launch_bounds__(256) void rope_append_kernel(const std::conditional_t<POS, RopePosParams, RopeAppendParams> r) {
     using C = KvAppendCfg;             // WROWS, BLOCK: of VIRTUAL positions here
     const KvAppendParams& p = r.a;
     constexpr int LPR = D / 16;          // lanes per row
@@ -217,6 +229,11 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RopeAppendParams
         q_ok[j] = v >= first && v < lq;
         kv_ok[j] = kv_wave && q_ok[j];
         pq[j] = max(v, 0);
+        if constexpr (POS) {                               // the row's offset in place of its index v - first
+            int off = 0;
+            if (q_ok[j]) off = r.pos_offsets[(int64_t)b * p.Sq + (v - first)];
+            pq[j] = max(first + min(max(off, 0), p.Sq - 1), 0);
+        }
     }
     const int64_t i0 = vw + lr - first;                    // the index of the lane's first row among the new rows
     rope_heads<D, KV8, NR, RPI>(r, slice, q_ok, kv_ok, pq, (int64_t)b * p.knB + i0 * p.knS, (int64_t)b * p.vnB + i0 * p.vnS,
@@ -273,6 +290,7 @@ __global__ __launch_bounds__(256) void rope_append_varlen_kernel(const RopeAppen
 
 // the instantiation for (d, fp8 cache, paged): inst_rope_append.hip
 Kernel rope_append_kernel_of(int d, bool kv8, bool paged);
+Kernel rope_append_pos_kernel_of(int d, bool kv8, bool paged);
 Kernel rope_append_varlen_kernel_of(int d, bool kv8, bool paged);
 
 }  // namespace fa

@@ -970,8 +970,9 @@ int flash_attention_sink_extend_paged_varlen(const void* Q, const void* Kpool, c
  * Rejected before any launch: everything the sink twin rejects, with the same codes and in the same order; a NULL treeMask
  * FA_ERR_NULL_POINTER (with the other pointers); a treeMask not aligned to 8 bytes FA_ERR_MISALIGNED, directly after the sinks check;
  * seqLenQ > FA_TREE_MAX_Q FA_ERR_BAD_SHAPE (with the other shape checks; flash_attention_tree_plan likewise).
- * Not done here: the ragged form (a tree size per sequence); trees above 64 nodes; depth-based rotary positions in
- * flash_attention_rope_append*, which rotates at cache positions; masks in the prefill forward and in the backward.
+ * Not done here: the ragged form (a tree size per sequence); trees above 64 nodes; masks in the prefill forward and in the backward.
+ * (Rotary positions by tree depth and the acceptance of the verified path: flash_attention_rope_append_pos and
+ * flash_attention_kv_accept, below.)
  */
 #define FA_TREE_MAX_Q 64            /* draft nodes per sequence: one uint64 mask word per node */
 
@@ -1071,8 +1072,8 @@ int flash_attention_kv_append_paged_varlen(const void* Knew, const void* Vnew, v
  * twin's shape checks); then, after the dHead check, rotDim not a multiple of 16 or outside [16, dHead] FA_ERR_BAD_SHAPE, maxPos
  * below the capacity FA_ERR_BAD_SHAPE, interleaved neither 0 nor 1 FA_ERR_BAD_FLAGS; a stride of Q or Qout that is not a multiple of
  * 16 bytes, or a row stride below dHead, FA_ERR_BAD_STRIDE (after the twin's strides).  The grid limit is the twin's.
- * Not done here: explicit position ids or offsets, sines computed on the device, fp8 or fp32 new rows, per-token descales, writing
- * kvLens, rotary embedding in flash_attention() or the backward, dHead other than 64 / 128.
+ * Not done here: absolute position ids (per-row offsets: flash_attention_rope_append_pos, below), sines computed on the device, fp8 or
+ * fp32 new rows, per-token descales, writing kvLens, rotary embedding in flash_attention() or the backward, dHead other than 64 / 128.
  */
 int flash_attention_rope_append(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V,
                                 const float* cosSin, const int32_t* kvLens, const float* kDescale, const float* vDescale,
@@ -1107,6 +1108,85 @@ int flash_attention_rope_append_paged_varlen(const void* Q, const void* Knew, co
                                              int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
                                              const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
                                              const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream);
+
+/*
+ * flash_attention_rope_append_pos, flash_attention_rope_append_paged_pos -- the fused rotary append with PER-ROW POSITION OFFSETS: each
+ * is flash_attention_rope_append / _paged with one argument more, directly after cosSin:
+ *   posOffsets [batchSize, seqLenNew] int32 (device memory), dense, base aligned to 4 bytes: entry (b, i) is posOffsets[b * seqLenNew + i].
+ *            Read BY THE KERNEL, like kvLens: no host synchronisation, and a replayed graph sees the values of the moment.
+ * With first = clamp(kvLens[b], 1, capacity) - seqLenNew as in the twin, row i is rotated -- Q and K alike -- at table row
+ *     max(first + off, 0),   off = clamp(posOffsets[b, i], 0, seqLenNew - 1)
+ * in place of the twin's max(first + i, 0).  The row is below clamp(kvLens[b], 1, capacity) <= capacity <= maxPos: a stale offset gives
+ * a wrong angle, never an address outside the table.  SLOTS DO NOT MOVE: K and V row i go to cache position L - seqLenNew + i under
+ * the twin's rule exactly (written iff that is >= 0; a table entry outside [0, numPages) skips K / V and not Q), V and the columns
+ * >= rotDim keep the twin's bits, and the values follow the twin's rule to the bit.  posOffsets[b, i] = i IS the twin, byte for byte.
+ * The use: a draft tree for flash_attention_tree*, node i at depth t of its sequence, is rotated at base + t (siblings share a
+ * position) while it is stored at slot base + i: posOffsets = the nodes' depths.
+ * Rejected before any launch: everything the twin rejects, with the same codes and in the same order; a NULL posOffsets
+ * FA_ERR_NULL_POINTER (with the other pointers); a posOffsets not aligned to 4 bytes FA_ERR_MISALIGNED (with the other 4-byte arrays).
+ * Not done here: the ragged (_varlen) forms (there is no ragged tree call), absolute position ids, writing kvLens, drafts above
+ * FA_TREE_MAX_Q in the calls that consume the result (this call itself takes any seqLenNew the twin takes).
+ */
+int flash_attention_rope_append_pos(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* K, void* V,
+                                    const float* cosSin, const int32_t* posOffsets, const int32_t* kvLens,
+                                    const float* kDescale, const float* vDescale,
+                                    int batchSize, int numHeads, int numHeadsKV, int seqLenNew, int seqLenK, int dHead,
+                                    int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
+                                    const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew, const fa_strides* sQout,
+                                    const fa_strides* sK, const fa_strides* sV, void* stream);
+
+int flash_attention_rope_append_paged_pos(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                          const float* cosSin, const int32_t* posOffsets, const int32_t* kvLens,
+                                          const int32_t* blockTable, const float* kDescale, const float* vDescale,
+                                          int batchSize, int numHeads, int numHeadsKV, int seqLenNew,
+                                          int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead,
+                                          int rotDim, int maxPos, int interleaved, int dtype, int kv_dtype,
+                                          const fa_strides* sQ, const fa_strides* sKnew, const fa_strides* sVnew,
+                                          const fa_strides* sQout, const fa_strides* sK, const fa_strides* sV, void* stream);
+
+/*
+ * flash_attention_kv_accept, flash_attention_kv_accept_paged -- IN-CACHE ACCEPTANCE of a speculative step.  The draft's seqLenDraft
+ * nodes lie at the cache positions base + 0 .. base + seqLenDraft - 1 (appended, counted by kvLens, verified by flash_attention_tree*);
+ * the call moves the accepted root-to-leaf path to base + 0 .. base + n - 1, where a linear append of the accepted tokens would have
+ * put it.  The argument lists are flash_attention_kv_append / _paged without Knew, Vnew, their strides, the descales and dtype, with
+ * seqLenNew named seqLenDraft, and with two arrays after kvLens (paged: after blockTable):
+ *   acceptIdx  [batchSize, seqLenDraft] int32, acceptLens [batchSize] int32: device memory, dense, bases aligned to 4 bytes, read BY
+ *            THE KERNEL (no host synchronisation; a replayed graph sees the values of the moment)
+ *   seqLenDraft  1 <= seqLenDraft <= FA_TREE_MAX_Q, and at most the capacity
+ * Per sequence b: L = min(kvLens[b], capacity) (NULL kvLens: the capacity) still counts the draft; L <= 0: nothing happens.
+ * base = L - seqLenDraft, n = clamp(acceptLens[b], 0, seqLenDraft), j_t = clamp(acceptIdx[b, t], 0, seqLenDraft - 1).  For
+ * t = 0 .. n - 1, IN ASCENDING ORDER OF t for every byte column, K and V of every K/V head at position base + j_t are copied to
+ * position base + t: a copy of bits, 2 dHead or dHead bytes per row by kv_dtype -- nothing is rotated or quantised again.  A move whose
+ * source or destination position is negative is skipped; a move whose source or destination page entry is outside [0, numPages) is
+ * skipped, never clamped; the move j_t == t writes nothing.  No other byte of the caches or pools is written, and kvLens is not
+ * written: the caller follows with kv_lens -= seqLenDraft - accept_lens, after which the positions from base + n on are garbage beyond
+ * the length, which every read call tolerates.  For a path of a topologically ordered tree (j_t strictly increasing, hence j_t >= t)
+ * the result is exactly "row t := the draft's row j_t": no source is overwritten before it is read.  For any other index list the
+ * result is the sequential rule above: well defined, memory safe and of no use.  (Paged: two positions of one sequence that the table
+ * maps to the same page are one row of memory; the result there is unspecified, and memory safe.)
+ * With flash_attention_rope_append_pos (posOffsets = the depths) the path's t-th node was rotated at base + t, so after the call the
+ * cache holds below base + n what flash_attention_rope_append of the accepted tokens, appended linearly, writes: byte for byte, bf16 and
+ * e4m3fn.  The whole step is one graph: kv_lens += Sq; rope_append_pos; tree; (sampling -> acceptIdx, acceptLens); kv_accept;
+ * kv_lens -= Sq - n.
+ * Conventions: the append's -- validated before the launch; no allocation, no synchronisation, nothing printed; one launch moves K and
+ * V, with 16-byte vector stores only.  Rejected before any launch, in the append's order: NULL caches, table, acceptIdx or acceptLens
+ * FA_ERR_NULL_POINTER; a cache base not aligned to 16 bytes, or kvLens, the table, acceptIdx or acceptLens not aligned to 4,
+ * FA_ERR_MISALIGNED; the append's paging and shape checks, with seqLenDraft outside [1, FA_TREE_MAX_Q] or above the capacity,
+ * FA_ERR_BAD_SHAPE; then kv_dtype FA_ERR_UNSUPPORTED_DTYPE, dHead FA_ERR_UNSUPPORTED_DHEAD, the cache strides FA_ERR_BAD_STRIDE, the
+ * extent and the grid FA_ERR_BAD_SHAPE.  A cache the append accepts, accept accepts.
+ * Not done here: a ragged form (a draft size per sequence), writing kvLens, drafts above FA_TREE_MAX_Q, freeing the pages the rewind
+ * leaves empty (the engine's).
+ */
+int flash_attention_kv_accept(void* K, void* V, const int32_t* kvLens, const int32_t* acceptIdx, const int32_t* acceptLens,
+                              int batchSize, int numHeadsKV, int seqLenDraft, int seqLenK, int dHead,
+                              int kv_dtype /* FA_DTYPE_BF16 | FA_DTYPE_FP8_E4M3 */,
+                              const fa_strides* sK, const fa_strides* sV, void* stream);
+
+int flash_attention_kv_accept_paged(void* Kpool, void* Vpool, const int32_t* kvLens, const int32_t* blockTable,
+                                    const int32_t* acceptIdx, const int32_t* acceptLens,
+                                    int batchSize, int numHeadsKV, int seqLenDraft,
+                                    int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, int kv_dtype,
+                                    const fa_strides* sK, const fa_strides* sV, void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);

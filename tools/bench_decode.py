@@ -116,6 +116,20 @@ Each line:
               tree_ms    the tree call under a heap-shaped binary-tree mask, likewise
               tree_ratio = tree_ms / causal_ms (medians); chain_equal: one call under a chain mask is the twin's O and LSE bit for bit
               (profiles/tree_gpu.log).
+--accept        with --tree N[,N...]: the WRITE side of a speculative step, a mode of its own over the decode shapes
+              with N draft nodes per sequence.  One line per shape and cache form (as under --sinks: --kv fp8, --paged), every figure
+              per N, [median, min, max] over --repeats ALTERNATED windows of --steps calls.  The draft is a heap-shaped binary tree, the
+              accepted path its last leaf's (depth + 1 nodes); the caches hold the appended draft.
+              accept_ms    kv_cache_accept* of that path: one launch, indices and count read on the device
+              reappend_ms  the route without it, its device side only: an index gather of the accepted rows out of K_new / V_new and
+                           kv_cache_append_varlen* (with --rope: of Q too, and rope_cache_append_varlen*) at the rewound lengths.  The
+                           path's length is taken from the host here and nothing is read back, which flatters this route: an engine
+                           learns the path on the host, a synchronisation per step
+              accept_ratio = accept_ms / reappend_ms (medians); accept_equals_reappend: the two routes leave the same bytes in the
+                           whole cache (with --rope: the draft appended with pos_offsets = the depths)
+              rope_append_ms, rope_pos_ms  rope_cache_append* of the N rows without and with pos_offsets = the tree's depths, alternated
+              rope_pos_ratio = rope_pos_ms / rope_append_ms (medians); twin_span = max / min of rope_append_ms's own windows: the
+                           ratio to hold it against (profiles/spec_step_gpu.log).
 """
 import argparse
 import json
@@ -710,6 +724,105 @@ def tree_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def accept_main(args, fa, dev):
+    """--accept --tree N[,N...]: kv_cache_accept* beside the gather-and-re-append route, rope_cache_append*(pos_offsets=) beside its twin"""
+    import torch
+    bf, f8 = torch.bfloat16, torch.float8_e4m3fn
+    nodes = [int(x) for x in args.tree.split(",") if x]
+    pages = [int(x) for x in (args.paged or "").split(",") if x]
+    shapes = [x for x in SHAPES + EXTRA if x[0] in args.shape] if args.shape else SHAPES
+    stats = lambda v: [round(x, 5) for x in (statistics.median(v), min(v), max(v))]
+    primed = False
+    for name, B, H, Hkv, _, Sk, d, ragged in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        lens = [1024 + (Sk - 1024) * b // (B - 1) for b in range(B)] if ragged else [Sk] * B
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)                 # the draft counted
+        table_cs = fa.rope_table(Sk, d, device=dev)
+        kds, vds = (torch.rand(Hkv, device=dev, generator=g) * 0.05 + 0.01 for _ in range(2))
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in pages:
+            if Sk % page == 0:
+                forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        for form, fp8, page in forms:
+            cdt = f8 if fp8 else bf
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                n_pages = Sk // page
+                table = torch.randperm(B * n_pages, device=dev, generator=g).reshape(B, n_pages).to(torch.int32)
+                shape = (B * n_pages, Hkv, page, d)
+            else:
+                table, shape = None, (B, Hkv, Sk, d)
+            tables = [table] if page else []
+            Kc, Vc = (torch.zeros(shape, device=dev, dtype=torch.uint8 if fp8 else bf).view(cdt) for _ in range(2))
+            p = "_paged" if page else ""
+            rope_front, accept_front = getattr(fa, "rope_cache_append" + p), getattr(fa, "kv_cache_accept" + p)
+            append_front, append_varlen = getattr(fa, "kv_cache_append" + p), getattr(fa, "kv_cache_append" + p + "_varlen")
+            rope_varlen = getattr(fa, "rope_cache_append" + p + "_varlen")
+            line = {"shape": name, "form": form, "rope": bool(args.rope), "path": {}, "accept_ms": {}, "reappend_ms": {}, "accept_ratio": {},
+                    "accept_equals_reappend": {}, "rope_append_ms": {}, "rope_pos_ms": {}, "rope_pos_ratio": {}, "twin_span": {}}
+            for N in nodes:
+                parents = torch.tensor([[(i - 1) // 2 if i else -1 for i in range(N)]] * B, device=dev)
+                depths = fa.tree_depths(parents)
+                idx, nacc = fa.tree_path(parents, torch.full((B,), N - 1, device=dev))
+                n = int(nacc[0])                                                   # (known from the tree's shape: read once, outside every timed call)
+                Q = torch.randn(B, H, N, d, device=dev, generator=g).to(bf)
+                Kn, Vn = (torch.randn(B, Hkv, N, d, device=dev, generator=g).to(bf) for _ in range(2))
+                Qo = torch.empty_like(Q)
+                # the draft in the caches, as the step leaves it before the acceptance
+                if args.rope:
+                    rope_front(Q, Kn, Vn, Kc, Vc, *tables, table_cs, lens_d, Q_out=Qo, pos_offsets=depths, **kw)
+                else:
+                    append_front(Kn, Vn, Kc, Vc, *tables, lens_d, **kw)
+                after = lens_d - (N - nacc)                                        # the rewound lengths
+                cu = (torch.arange(B + 1, device=dev) * n).to(torch.int32)
+                take = idx[:, :n].long()                                           # [B, n]
+
+                def packed(x):      # the accepted rows of [B, heads, N, d], packed by token: [B n, heads, d]
+                    return torch.gather(x.transpose(1, 2), 1, take[:, :, None, None].expand(B, n, x.shape[1], d)).reshape(B * n, x.shape[1], d)
+
+                Qa = torch.empty(B * n, H, d, device=dev, dtype=bf)
+
+                def accept(K=Kc, V=Vc):
+                    accept_front(K, V, *tables, idx, nacc, lens_d)
+
+                def reappend(K=Kc, V=Vc):
+                    if args.rope:
+                        rope_varlen(packed(Q), packed(Kn), packed(Vn), K, V, *tables, cu, table_cs, after, Q_out=Qa, **kw)
+                    else:
+                        append_varlen(packed(Kn), packed(Vn), K, V, *tables, cu, after, **kw)
+
+                copies = [(Kc.clone(), Vc.clone()) for _ in range(2)]
+                accept(*copies[0])
+                reappend(*copies[1])
+                same = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(*copies))
+                moved = not torch.equal(copies[0][0].view(torch.uint8), Kc.view(torch.uint8))
+                line["accept_equals_reappend"][str(N)] = bool(same and (moved or n == N))
+                del copies
+                twin = lambda: rope_front(Q, Kn, Vn, Kc, Vc, *tables, table_cs, lens_d, Q_out=Qo, **kw)
+                pos = lambda: rope_front(Q, Kn, Vn, Kc, Vc, *tables, table_cs, lens_d, Q_out=Qo, pos_offsets=depths, **kw)
+                if not primed:   # >= 1 s of calls before the first timed window
+                    t = 0.0
+                    while t < 1000.0:
+                        t += timed(twin, 50, 0) * 50
+                    primed = True
+                t = {"accept": [], "reappend": [], "twin": [], "pos": []}
+                for _ in range(args.repeats):      # alternated: one window of each
+                    t["twin"].append(timed(twin, args.steps, args.warmup))
+                    t["pos"].append(timed(pos, args.steps, args.warmup))
+                    t["accept"].append(timed(accept, args.steps, args.warmup))
+                    t["reappend"].append(timed(reappend, args.steps, args.warmup))
+                line["path"][str(N)] = n
+                line["accept_ms"][str(N)], line["reappend_ms"][str(N)] = stats(t["accept"]), stats(t["reappend"])
+                line["accept_ratio"][str(N)] = round(statistics.median(t["accept"]) / statistics.median(t["reappend"]), 4)
+                line["rope_append_ms"][str(N)], line["rope_pos_ms"][str(N)] = stats(t["twin"]), stats(t["pos"])
+                line["rope_pos_ratio"][str(N)] = round(statistics.median(t["pos"]) / statistics.median(t["twin"]), 4)
+                line["twin_span"][str(N)] = round(max(t["twin"]) / min(t["twin"]), 4)
+                del Q, Kn, Vn, Qo, Qa
+            print(json.dumps(line), flush=True)
+            del Kc, Vc
+            torch.cuda.empty_cache()
+
+
 def rope_main(args, fa, dev):
     import torch
     bf = torch.bfloat16
@@ -832,11 +945,16 @@ def main():
     ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
     ap.add_argument("--rope", action="store_true", help="time rope_cache_append* beside the unfused torch route and the plain append, alternated")
     ap.add_argument("--tree", default=None, help="comma-separated draft-node counts: time flash_attention_tree beside its causal twin, alternated")
+    ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.accept:
+        if not args.tree:
+            ap.error("--accept takes the draft sizes from --tree N[,N...]")
+        return accept_main(args, fa, dev)
     if args.tree:
         return tree_main(args, fa, dev)
     if args.rope:
