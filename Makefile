@@ -17,7 +17,8 @@ SPLIT_UNITS := decode_bf16 decode_fp8 decode_paged_bf16 decode_paged_fp8 \
                extend_sink_bf16 extend_sink_fp8 extend_sink_paged_bf16 extend_sink_paged_fp8 \
                extend_sink_varlen_bf16 extend_sink_varlen_fp8 extend_sink_varlen_paged_bf16 extend_sink_varlen_paged_fp8 \
                decode_tree_bf16 decode_tree_fp8 decode_tree_paged_bf16 decode_tree_paged_fp8 \
-               extend_tree_bf16 extend_tree_fp8 extend_tree_paged_bf16 extend_tree_paged_fp8
+               extend_tree_bf16 extend_tree_fp8 extend_tree_paged_bf16 extend_tree_paged_fp8 \
+               shared_bf16 shared_fp8 shared_paged_bf16 shared_paged_fp8
 SPLIT_SRC := $(PKG)/csrc/split_unit.hip
 SPLIT_OBJ := $(SPLIT_UNITS:%=build/obj/inst_%.o)
 KSRC     := $(filter-out $(SPLIT_SRC),$(wildcard $(PKG)/csrc/*.hip))
@@ -40,11 +41,11 @@ build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
-# the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
+# the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS, and the shared_* ones, which are built at the same RT; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
 # tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
 # form, 81 in VGPR form and faster on every measured shape; its d = 64 instantiations use none either way.  The define
 # tells the unit which way it was built, and the unit refuses to compile if that is not its row's way.  $* is the unit's name
-SPLIT_FLAGS = -DFA_SPLIT_UNIT=$* $(if $(filter extend_%,$*),$(MFMA_VGPR) -DFA_SPLIT_MFMA_VGPR)
+SPLIT_FLAGS = -DFA_SPLIT_UNIT=$* $(if $(filter extend_% shared_%,$*),$(MFMA_VGPR) -DFA_SPLIT_MFMA_VGPR)
 
 $(SPLIT_OBJ): build/obj/inst_%.o: $(SPLIT_SRC) $(KHDR)
 	@mkdir -p build/obj
@@ -111,8 +112,8 @@ SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # nothing preloaded; tests/host_ladder.h is what they share), each built and run: the validation ladders and plans of the ragged entry
 # points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins,
 # of the two tree-masked ones beside their sink twins, of the speculative step's rope_append_pos and kv_accept ones beside their rope_append
-# and kv_append twins
-LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder
+# and kv_append twins, of the two shared-prefix decode ones and their plan beside flash_attention_decode_window / _paged_window
+LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder host_cascade_ladder
 $(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip

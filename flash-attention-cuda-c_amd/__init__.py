@@ -34,6 +34,9 @@ entry points for that path:
 * ``flash_attention_tree(Q, K, V, tree_mask, kv_lens)`` / ``flash_attention_tree_paged(Q, K_pool, V_pool, block_table, tree_mask,
   kv_lens)`` -- tree-masked verification of a speculative draft: up to 64 draft nodes per sequence, already appended, each row seeing
   the cached prefix and the nodes its 64-bit mask word names (``tree_mask_from_parents``, ``tree_depths``, ``tree_plan``).
+* ``flash_attention_cascade_decode(Q, K_shared, V_shared, K, V, shared_len, kv_lens)`` / ``flash_attention_cascade_decode_paged(Q,
+  K_pool, V_pool, shared_table, block_table, shared_len, kv_lens)`` -- shared-prefix (cascade) decode: one prefix every sequence of the
+  batch sees in full, read once per row block of the whole batch, then each sequence's own suffix (``cascade_plan``).
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -83,6 +86,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_tree", "flash_attention_tree_paged", "flash_attention_tree_plan",
            "flash_attention_rope_append_pos", "flash_attention_rope_append_paged_pos",
            "flash_attention_kv_accept", "flash_attention_kv_accept_paged",
+           "flash_attention_cascade_decode", "flash_attention_cascade_decode_paged", "flash_attention_cascade_plan",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -115,6 +119,9 @@ _ROPE_SYMBOLS = {(False, False): "flash_attention_rope_append", (True, False): "
 # _ACCEPT_SYMBOLS[paged], the in-cache acceptance of the verified path
 _ROPE_POS_SYMBOLS = {False: "flash_attention_rope_append_pos", True: "flash_attention_rope_append_paged_pos"}
 _ACCEPT_SYMBOLS = {False: "flash_attention_kv_accept", True: "flash_attention_kv_accept_paged"}
+# ... shared-prefix decode: _CASCADE_SYMBOLS[paged], the ``_window`` entry point of decode with the shared cache, sharedLen, the shared
+# table and sinks in, two split counts, and no window
+_CASCADE_SYMBOLS = {False: "flash_attention_cascade_decode", True: "flash_attention_cascade_decode_paged"}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -137,6 +144,10 @@ class FaLaunchPlanEx(ctypes.Structure):
 class FaDecodePlan(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int) for k in ("num_splits", "row_blocks", "rows_per_block", "kv_block_rows", "threads", "grid",
                                             "lds_bytes", "combine_grid", "combine_threads")]
+
+
+class FaCascadePlan(ctypes.Structure):
+    _fields_ = [("shared", FaDecodePlan), ("unique", FaDecodePlan), ("num_splits", ctypes.c_int)]
 
 
 class FlashAttentionError(RuntimeError):
@@ -228,6 +239,14 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, name)
             fn.argtypes = [vp] * 3 + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i] + [sp] * 2 + [vp]
             fn.restype = i
+        # the cascade pair: Q, the shared K / V and the K / V of the suffixes (paged: the two pools), O, LSE, sharedLen, kvLens, the two
+        # tables (paged), the descales, sinks, the workspace; seqLenShared before seqLenK (paged: maxSharedPages before maxPagesPerSeq);
+        # two split counts; the shared tensors' strides before K's (paged: the pools' only)
+        L.flash_attention_cascade_decode.argtypes = [vp] * 13 + [i] * 7 + [f, b] + [i] * 5 + [sp] * 6 + [vp]
+        L.flash_attention_cascade_decode_paged.argtypes = [vp] * 13 + [i] * 8 + [ctypes.c_int64, i, f, b] + [i] * 5 + [sp] * 4 + [vp]
+        L.flash_attention_cascade_decode.restype = L.flash_attention_cascade_decode_paged.restype = i
+        L.flash_attention_cascade_plan.argtypes = [i] * 10 + [ctypes.POINTER(FaCascadePlan)]
+        L.flash_attention_cascade_plan.restype = i
         for by_window in _PLAN_SYMBOLS.values():
             for window, name in enumerate(by_window):
                 fn = getattr(L, name)
@@ -872,6 +891,122 @@ def flash_attention_tree_paged(Q, K_pool, V_pool, block_table, tree_mask, kv_len
     ``flash_attention_decode_paged``): the result is that call's on a contiguous copy of the same pages, bit for bit."""
     return _split_front("tree", Q, K_pool, V_pool, block_table, None, kv_lens, scale, True, out_dtype, num_splits, return_lse, None, None,
                         stream, k_descale, v_descale, window, sinks, tree_mask)
+
+
+def _cascade_splits(num_splits):
+    """``num_splits`` of the cascade fronts as the C ABI's pair: ``(shared, unique)``, 0 = the library's choice"""
+    try:
+        ns_s, ns_u = (int(n) for n in num_splits)
+    except (TypeError, ValueError):
+        raise ValueError("num_splits must be a pair (shared, unique); 0 = the library's choice") from None
+    return ns_s, ns_u
+
+
+def cascade_plan(B, H, Hkv, Sq, Ls, Sk, d, o_dtype=FA_DTYPE_BF16, num_splits=(0, 0)):
+    """What a flash_attention_cascade_decode call launches (fa_cascade_plan as a dict): ``shared`` and ``unique`` are the plans of the two
+    split launches (``Ls``, ``Sk``: the capacities of the shared part and of the suffixes), ``num_splits`` their sum -- what
+    ``decode_workspace_size(B, H, Sq, d, num_splits)`` is asked with.  ``num_splits``: the pair (shared, unique), 0 = the library's choice."""
+    p = FaCascadePlan()
+    ns_s, ns_u = _cascade_splits(num_splits)
+    _check(lib().flash_attention_cascade_plan(B, H, Hkv, Sq, Ls, Sk, d, o_dtype, ns_s, ns_u, ctypes.byref(p)))
+    return {"shared": _plan_dict(p.shared), "unique": _plan_dict(p.unique), "num_splits": p.num_splits}
+
+
+def _cascade_front(Q, K_shared, V_shared, K, V, shared_table, block_table, shared_len, kv_lens, scale, is_causal, out_dtype, num_splits,
+                   return_lse, O, workspace, stream, k_descale, v_descale, sinks):
+    """Both cascade fronts: the checks of the decode fronts on the suffix caches, the same on the shared ones, the plan and the
+    workspace as ``_split_front`` allocates it, then the entry point of _CASCADE_SYMBOLS."""
+    import torch
+    paged = block_table is not None
+    name = _CASCADE_SYMBOLS[paged]
+    kv, layout = ("K_pool, V_pool", "[P, Hkv, page, d]") if paged else ("K, V", "[B, Hkv, capacity, d]")
+    fp8 = _decode_inputs(name, kv, layout, Q, K, V, k_descale, v_descale, table=block_table)
+    B, H, Sq, d = Q.shape
+    Hkv = K.shape[1]
+    if paged:
+        t = shared_table
+        if not getattr(t, "is_cuda", False) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < 1 or not t.is_contiguous() \
+                or t.device != Q.device:
+            raise ValueError("shared_table must be a dense int32 device tensor [max_shared_pages] on the device of Q")
+        shared_capacity, shared_geometry = t.shape[0] * K.shape[2], (t.shape[0],)
+    else:
+        if not (getattr(K_shared, "is_cuda", False) and getattr(V_shared, "is_cuda", False)):
+            raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+        if K_shared.dim() != 3 or K_shared.shape != V_shared.shape or K_shared.shape[0] != Hkv or K_shared.shape[2] != d \
+                or K_shared.shape[1] < 1:
+            raise ValueError("K_shared, V_shared must be [Hkv, shared capacity, d] with the Hkv and d of K, V")
+        if not (K_shared.dtype == V_shared.dtype == K.dtype):
+            raise TypeError("K_shared, V_shared, K, V must share a dtype")
+        shared_capacity, shared_geometry = K_shared.shape[1], (K_shared.shape[1],)
+    capacity, tables, geometry = _cache_geometry(K, block_table, B)
+    if shared_len is not None and (not getattr(shared_len, "is_cuda", False) or shared_len.dtype != torch.int32 or shared_len.shape != (1,)
+                                   or shared_len.device != Q.device):
+        raise ValueError("shared_len must be an int32 device tensor [1] on the device of Q")
+    if sinks is not None and (getattr(sinks, "dtype", None) != torch.float32 or not sinks.is_cuda or sinks.device != Q.device
+                              or tuple(sinks.shape) != (H,) or not sinks.is_contiguous()):
+        raise ValueError("sinks must be a dense fp32 tensor [H] on the device of Q")
+    _check_kv_lens(kv_lens, B)
+    if scale is None:
+        scale = 1.0 / float(d) ** 0.5
+    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
+    ns_s, ns_u = _cascade_splits(num_splits)
+    p = FaCascadePlan()
+    _check(lib().flash_attention_cascade_plan(B, H, Hkv, Sq, shared_capacity, capacity, d, odt, ns_s, ns_u, ctypes.byref(p)))
+    need = decode_workspace_size(B, H, Sq, d, p.num_splits)
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.empty((B, H, Sq, d), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif O.shape != Q.shape or not O.is_cuda:
+                raise ValueError("O must be a device tensor shaped like Q")
+            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            if workspace is None:
+                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+        if not workspace.is_cuda or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        caches = (K, V) if paged else (K_shared, V_shared, K, V)
+        st = [_strides(t.unsqueeze(0)) if t.dim() == 3 else _strides(t) for t in (Q, *caches, O)]
+        rc = getattr(lib(), name)(Q.data_ptr(), *(t.data_ptr() for t in caches), O.data_ptr(), ptr(lse), ptr(shared_len), ptr(kv_lens),
+                                  *((shared_table.data_ptr(), block_table.data_ptr()) if paged else ()), ptr(k_descale), ptr(v_descale),
+                                  ptr(sinks), workspace.data_ptr(), B, H, Hkv, Sq,
+                                  *((geometry[0], geometry[1], *shared_geometry, *geometry[2:]) if paged else (*shared_geometry, *geometry)),
+                                  d, float(scale), bool(is_causal), _dtype_code(Q.dtype), _dtype_code(K.dtype), _dtype_code(O.dtype),
+                                  p.shared.num_splits, p.unique.num_splits, *[ctypes.byref(x) for x in st], _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
+
+
+def flash_attention_cascade_decode(Q, K_shared, V_shared, K, V, shared_len=None, kv_lens=None, scale=None, is_causal=False,
+                                   out_dtype=None, num_splits=(0, 0), return_lse=False, O=None, workspace=None, stream=None,
+                                   k_descale=None, v_descale=None, sinks=None):
+    """SHARED-PREFIX (cascade) decode: the logical cache of sequence b is ``[K_shared[:, :ls] ; K[b, :, :kv_lens[b]]]`` -- one prefix
+    ``[Hkv, shared capacity, d]`` that every sequence sees in full, read once per row block of the whole batch, then the sequence's own
+    suffix ``[B, Hkv, capacity, d]``.  Q ``[B, H, Sq, d]``, 1 <= Sq <= FA_DECODE_MAX_Q, is the last Sq rows of that logical sequence.
+
+    ``shared_len``: int32 device tensor ``[1]``, the valid shared keys, clamped into [1, shared capacity] on the device (None = the
+    capacity); ``kv_lens`` as in ``flash_attention_decode``, of the suffixes.  There is no mask on the shared part; of its suffix a row
+    sees what ``flash_attention_decode`` shows it on the suffix alone (``is_causal``: bottom-right, at least key 0), so whenever
+    ``kv_lens[b] >= Sq`` the result is ``flash_attention_decode(is_causal=...)`` on the concatenated cache.  The LSE covers both parts.
+    fp8 caches (all four tensors ``torch.float8_e4m3fn`` under a bf16 Q) take ONE ``k_descale`` / ``v_descale`` pair for both parts;
+    ``sinks`` as in ``flash_attention_decode``.  ``num_splits``: the pair (shared, unique), 0 = the library's choice (``cascade_plan``);
+    unique >= 2 when forced.  ``workspace``: ``decode_workspace_size(B, H, Sq, d, cascade_plan(...)["num_splits"])`` bytes, always
+    needed, allocated on the call's stream when not given.  Three launches, asynchronous, graph-capturable.  No window.  No CPU fallback."""
+    return _cascade_front(Q, K_shared, V_shared, K, V, None, None, shared_len, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse,
+                          O, workspace, stream, k_descale, v_descale, sinks)
+
+
+def flash_attention_cascade_decode_paged(Q, K_pool, V_pool, shared_table, block_table, shared_len=None, kv_lens=None, scale=None,
+                                         is_causal=False, out_dtype=None, num_splits=(0, 0), return_lse=False, O=None, workspace=None,
+                                         stream=None, k_descale=None, v_descale=None, sinks=None):
+    """``flash_attention_cascade_decode`` against PAGED caches: one pool pair ``[P, Hkv, page, d]`` serves both parts.
+    ``shared_table``: int32 device tensor ``[max_shared_pages]``, the shared part's pages in order; ``block_table`` ``[B, max_pages]``
+    holds the SUFFIX pages (an engine passes its table offset by the shared pages; the tail of a prompt that does not fill a page lives
+    in the suffix).  ``shared_len`` is clamped into [1, max_shared_pages * page].  Entries are read and clamped by the kernel as in
+    ``flash_attention_decode_paged``; the result is the contiguous call's on gathered copies under the same ``num_splits``, bit for bit."""
+    return _cascade_front(Q, None, None, K_pool, V_pool, shared_table, block_table, shared_len, kv_lens, scale, is_causal, out_dtype,
+                          num_splits, return_lse, O, workspace, stream, k_descale, v_descale, sinks)
 
 
 def _tree_parents(parents):

@@ -517,7 +517,7 @@ static bool cache_extent_ok(const KvCache& c, int d) {
 // rows of one head of one batch entry / page: what NULL K / V strides are dense over
 static int cache_rows(const KvCache& c) { return c.paging ? c.paging->page_size : c.capacity; }
 
-// The forty units' launchers by row of SPLIT_FORMS (split_forms.hip.h): a unit missing from the build does not link.  Here and not in
+// The forty-four units' launchers by row of SPLIT_FORMS (split_forms.hip.h): a unit missing from the build does not link.  Here and not in
 // the header, so that no unit sees -- and compiles -- another unit's kernels
 template <size_t... U>
 constexpr std::array<int (*)(int, unsigned, hipStream_t, const SplitArgs&), sizeof...(U)> split_launchers(std::index_sequence<U...>) {
@@ -593,6 +593,142 @@ static int decode_run(SplitCall c) {
     rc = SPLIT_LAUNCH[unit](d, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
     return combine_launch(f.varlen, sink, d, (unsigned)rows, st, p);
+}
+
+// ---- shared-prefix (cascade) decode: flash_attention_cascade_decode*  ----
+// A decode call (`u`: the sequences' own suffixes, its cache, lengths, mask and forced split count) and the ONE cache every sequence
+// sees in full before its own.  shared.kv_lens is sharedLen (one entry), shared.paging the one-row table; the descales are u.cache's.
+struct CascadeCall {
+    SplitCall u;
+    KvCache shared;
+    int num_splits_shared;
+};
+
+// The split counts, from shapes only.  Shared part: extend's rule and constants with units = Hkv * ceil(B G Sq / rows per block) and
+// the tiles of the shared capacity; unique part: decode's rule, clamped into [2, 32] (decode's kernel writes slabs under more than
+// one split only); the shared count is then capped at what is left of FA_DECODE_MAX_SPLITS.  A forced count is taken as given, and a
+// chosen one makes room for it.  NOT measured: tools/bench_decode.py --cascade --splits shows what the rule costs
+struct CascadeRoute {
+    int ns_s, ns_u, row_blocks_s;
+    int64_t grid_s;
+    DecodeRoute unique;
+};
+constexpr int CASCADE_MAX_UNIQUE_SPLITS = 32;
+
+static CascadeRoute cascade_route(const CascadeCall& c) {
+    const SplitForm f = extend_form(c.u.d);
+    CascadeRoute r{};
+    const int64_t rows = (int64_t)c.u.B * (c.u.H / c.u.Hkv) * c.u.Sq;   // packed rows per K/V head, across the batch
+    r.row_blocks_s = (int)std::min<int64_t>((rows + f.rows_per_block - 1) / f.rows_per_block, INT32_MAX);
+    const int64_t units = (int64_t)c.u.Hkv * r.row_blocks_s;
+    SplitCall u = c.u;
+    if (u.num_splits == 0) {
+        u.num_splits = std::clamp(decode_route(u).ns, 2, std::min(CASCADE_MAX_UNIQUE_SPLITS, FA_DECODE_MAX_SPLITS - c.num_splits_shared));
+    }
+    r.unique = decode_route(u);
+    r.ns_u = r.unique.ns;
+    if (c.num_splits_shared > 0) r.ns_s = c.num_splits_shared;
+    else {
+        constexpr int TILE = DecodeCfg<128>::TILE;
+        const int tiles = (c.shared.capacity + TILE - 1) / TILE;
+        const int64_t want = ((int64_t)f.wgs_per_cu * device_cus() + units - 1) / units;
+        r.ns_s = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)tiles / f.min_tiles, (int64_t)FA_DECODE_MAX_SPLITS - r.ns_u}));
+    }
+    r.grid_s = units * r.ns_s;
+    return r;
+}
+
+// the shape of a cascade call or plan: decode's refusals at decode's places, the shared part's among the shape's
+static int cascade_check_shape(const CascadeCall& c) {
+    const int Ls = c.shared.capacity, ns_s = c.num_splits_shared, ns_u = c.u.num_splits;
+    if (Ls <= 0 || Ls > (1 << 24)) return FA_ERR_BAD_SHAPE;
+    // (a count left to the library is at least 1 for the shared part and 2 for the unique one: a forced one must leave that room)
+    if (ns_s < 0 || ns_u < 0 || ns_u == 1 || (int64_t)std::max(ns_s, 1) + std::max(ns_u, 2) > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
+    const int rc = decode_check_shape(c.u);
+    if (rc != FA_OK) return rc;
+    const CascadeRoute r = cascade_route(c);
+    const int64_t rows = (int64_t)c.u.B * c.u.H * c.u.Sq;
+    if (r.row_blocks_s == INT32_MAX || r.grid_s >= FA_DECODE_MAX_WORKGROUPS || r.unique.grid >= FA_DECODE_MAX_WORKGROUPS
+        || rows >= FA_DECODE_MAX_WORKGROUPS)
+        return FA_ERR_BAD_SHAPE;
+    return FA_OK;
+}
+
+// flash_attention_cascade_decode*: one validation, in decode_run's order with the shared cache beside the sequences' own, and three
+// launches on the stream -- the SHARED unit into slabs [0, ns_s), decode's own unit on the suffixes into slabs [ns_s, ns_s + ns_u), the
+// combine over all of them.  No host synchronisation: graph-capturable
+static int cascade_run(CascadeCall c) {
+    SplitCall& u = c.u;
+    const DecodePaging *pg = u.cache.paging, *spg = c.shared.paging;
+    const int B = u.B, H = u.H, Hkv = u.Hkv, Sq = u.Sq, d = u.d;
+    if (!u.Q || !c.shared.K || !c.shared.V || !u.cache.K || !u.cache.V || !u.O || (spg && !spg->table) || (pg && !pg->table))
+        return FA_ERR_NULL_POINTER;
+    if (!aligned16(u.Q) || !aligned16(c.shared.K) || !aligned16(c.shared.V) || !aligned16(u.cache.K) || !aligned16(u.cache.V) || !aligned16(u.O)
+        || !aligned16(u.LSE) || !aligned16(u.workspace))
+        return FA_ERR_MISALIGNED;
+    int rc = cache_check_arrays(c.shared, nullptr);
+    if (rc != FA_OK || (rc = cache_check_arrays(u.cache, nullptr)) != FA_OK) return rc;
+    if (misaligned4(u.sinks)) return FA_ERR_MISALIGNED;
+    if ((rc = cache_capacity(c.shared)) != FA_OK || (rc = cache_capacity(u.cache)) != FA_OK) return rc;
+    if ((rc = cascade_check_shape(c)) != FA_OK) return rc;
+    if (u.cache.kv_dtype != FA_DTYPE_BF16 && u.cache.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!std::isfinite(u.scale) || !(u.scale > 0.f)) return FA_ERR_BAD_SCALE;
+    if (!strides_ok(u.sQ, 2, d) || !cache_strides_ok(c.shared, d) || !cache_strides_ok(u.cache, d) || !strides_ok(u.sO, elem_size(u.o_dtype), d))
+        return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(c.shared, d) || !cache_extent_ok(u.cache, d)) return FA_ERR_BAD_SHAPE;
+    if (!u.workspace) return FA_ERR_NULL_POINTER;   // (both kernels write slabs, whatever the counts)
+    const CascadeRoute r = cascade_route(c);
+    const int ns = r.ns_s + r.ns_u;
+    const int64_t rows = (int64_t)B * H * Sq;
+
+    const bool kv8 = u.cache.kv_dtype == FA_DTYPE_FP8_E4M3;
+    SplitArgs p{};
+    p.Q = (const __bf16*)u.Q; p.O = u.O; p.lse = u.LSE;
+    float* const part_o = (float*)u.workspace;
+    float* const part_lse = (float*)((char*)u.workspace + round16((size_t)rows * ns * d * sizeof(float)));
+    resolve_strides(u.sQ, H, Sq, d, p.qB, p.qH, p.qS);
+    resolve_strides(u.sO, H, Sq, d, p.oB, p.oH, p.oS);
+    p.H = H; p.Hkv = Hkv; p.G = H / Hkv; p.Sq = Sq; p.B = B;
+    p.rows = (int)rows;
+    p.o_dtype = u.o_dtype;
+    p.scale_log2 = u.scale * 1.4426950408889634f;
+    p.k_descale = u.cache.k_descale;
+    p.v_descale = u.cache.v_descale;
+    p.sinks = u.sinks;
+    // the cache a launch reads: its tensors and strides, its lengths, its capacity and its table
+    auto of_cache = [&](const KvCache& kc, const DecodePaging* g) {
+        const int rowsK = cache_rows(kc);
+        p.K = (const __bf16*)kc.K; p.V = (const __bf16*)kc.V;
+        p.kv_lens = kc.kv_lens;
+        p.Sk = kc.capacity;
+        resolve_strides(kc.sK, Hkv, rowsK, d, p.kB, p.kH, p.kS);
+        resolve_strides(kc.sV, Hkv, rowsK, d, p.vB, p.vH, p.vS);
+        p.block_table = g ? g->table : nullptr;
+        p.table_stride = g ? g->table_stride : 0;
+        p.num_pages = g ? g->num_pages : 0;
+        p.page_shift = g ? __builtin_ctz((unsigned)g->page_size) : 0;
+    };
+    hipStream_t st = reinterpret_cast<hipStream_t>(u.stream);
+    // 1. the prefix, once per row block of the whole batch
+    of_cache(c.shared, spg);
+    p.part_o = part_o; p.part_lse = part_lse;
+    p.row_blocks = r.row_blocks_s; p.ns = r.ns_s;
+    p.causal = 0; p.window = 0;
+    int unit = split_unit_of(split_form_of(false, false, false, spg != nullptr, kv8, false, false, true));
+    if (unit < 0) return FA_ERR_BAD_FLAGS;
+    if ((rc = SPLIT_LAUNCH[unit](d, (unsigned)r.grid_s, st, p)) != FA_OK) return rc;
+    // 2. the suffixes: decode's own unit under ns_u >= 2 splits, its slabs behind the prefix's
+    of_cache(u.cache, pg);
+    p.part_o = part_o + (int64_t)r.ns_s * rows * d; p.part_lse = part_lse + (int64_t)r.ns_s * rows;
+    p.row_blocks = r.unique.row_blocks; p.ns = r.ns_u;
+    p.causal = u.is_causal;
+    unit = split_unit_of(split_form_of(false, false, false, pg != nullptr, kv8, false, false));
+    if (unit < 0) return FA_ERR_BAD_FLAGS;
+    if ((rc = SPLIT_LAUNCH[unit](d, (unsigned)r.unique.grid, st, p)) != FA_OK) return rc;
+    // 3. the one combine over both parts' slabs; the sinks join here, once per row
+    p.part_o = part_o; p.part_lse = part_lse;
+    p.ns = ns;
+    return combine_launch(false, u.sinks != nullptr, d, (unsigned)rows, st, p);
 }
 
 // ---- K/V cache append (kv_append.hip.h) ----
@@ -1490,6 +1626,71 @@ int flash_attention_tree_paged(const void* Q, const void* Kpool, const void* Vpo
                            .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead,
                            .scale = scale, .is_causal = true, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits,
                            .window = windowSize, .sQ = sQ, .sO = sO, .stream = stream, .sinks = sinks, .tree_mask = treeMask});
+}
+
+// ---- shared-prefix (cascade) decode ----
+int flash_attention_cascade_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenShared, int seqLenK, int dHead,
+                                 int o_dtype, int numSplitsShared, int numSplitsUnique, fa_cascade_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const CascadeCall c{.u = {.form = decode_form(), .cache = {.capacity = seqLenK}, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV,
+                              .Sq = seqLenQ, .d = dHead, .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplitsUnique},
+                        .shared = {.capacity = seqLenShared}, .num_splits_shared = numSplitsShared};
+    int rc = cascade_check_shape(c);
+    if (rc != FA_OK) return rc;
+    const CascadeRoute r = cascade_route(c);
+    if ((rc = flash_attention_decode_plan(batchSize, numHeads, numHeadsKV, seqLenQ, seqLenK, dHead, o_dtype, r.ns_u, &plan->unique)) != FA_OK)
+        return rc;
+    const SplitForm f = extend_form(dHead);
+    plan->shared = plan->unique;   // (the tile, the threads, the LDS and the combine are the same)
+    plan->shared.num_splits = r.ns_s;
+    plan->shared.row_blocks = r.row_blocks_s;
+    plan->shared.rows_per_block = f.rows_per_block;
+    plan->shared.grid = (int)r.grid_s;
+    plan->num_splits = r.ns_s + r.ns_u;
+    return FA_OK;
+}
+
+int flash_attention_cascade_decode(const void* Q, const void* Kshared, const void* Vshared, const void* K, const void* V, void* O,
+                                   float* LSE, const int32_t* sharedLen, const int32_t* kvLens, const float* kDescale,
+                                   const float* vDescale, const float* sinks, void* workspace, int batchSize, int numHeads,
+                                   int numHeadsKV, int seqLenQ, int seqLenShared, int seqLenK, int dHead, float scale, bool is_causal,
+                                   int dtype, int kv_dtype, int o_dtype, int numSplitsShared, int numSplitsUnique, const fa_strides* sQ,
+                                   const fa_strides* sKshared, const fa_strides* sVshared, const fa_strides* sK, const fa_strides* sV,
+                                   const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::cascade_run(
+        {.u = {.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+               .cache = {.K = K, .V = V, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                         .capacity = seqLenK, .sK = sK, .sV = sV},
+               .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead, .scale = scale,
+               .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplitsUnique, .sQ = sQ, .sO = sO,
+               .stream = stream, .sinks = sinks},
+         .shared = {.K = Kshared, .V = Vshared, .kv_lens = sharedLen, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                    .capacity = seqLenShared, .sK = sKshared, .sV = sVshared},
+         .num_splits_shared = numSplitsShared});
+}
+
+int flash_attention_cascade_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE, const int32_t* sharedLen,
+                                         const int32_t* kvLens, const int32_t* sharedTable, const int32_t* blockTable,
+                                         const float* kDescale, const float* vDescale, const float* sinks, void* workspace, int batchSize,
+                                         int numHeads, int numHeadsKV, int seqLenQ, int numPages, int pageSize, int maxSharedPages,
+                                         int maxPagesPerSeq, int64_t tableStride, int dHead, float scale, bool is_causal, int dtype,
+                                         int kv_dtype, int o_dtype, int numSplitsShared, int numSplitsUnique, const fa_strides* sQ,
+                                         const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream) {
+    if (!window_descales_ok(kv_dtype, kDescale, vDescale)) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    const fa::DecodePaging spg{sharedTable, maxSharedPages, numPages, pageSize, maxSharedPages};   // one row
+    return fa::cascade_run(
+        {.u = {.form = fa::decode_form(), .Q = Q, .O = O, .LSE = LSE,
+               .cache = {.K = Kpool, .V = Vpool, .kv_lens = kvLens, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                         .sK = sK, .sV = sV, .paging = &pg},
+               .workspace = workspace, .B = batchSize, .H = numHeads, .Hkv = numHeadsKV, .Sq = seqLenQ, .d = dHead, .scale = scale,
+               .is_causal = is_causal, .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplitsUnique, .sQ = sQ, .sO = sO,
+               .stream = stream, .sinks = sinks},
+         .shared = {.K = Kpool, .V = Vpool, .kv_lens = sharedLen, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
+                    .sK = sK, .sV = sV, .paging = &spg},
+         .num_splits_shared = numSplitsShared});
 }
 
 const char* flash_attention_error_string(int code) {

@@ -101,6 +101,15 @@
 //     true, VARLEN = false with a parameter type of their own (TreeDecodeParams); their epilogue reads sinks where the SINK form
 //     does -- under ns = 1, a NULL pointer there being -inf -- and under more splits the slabs hold the keys alone and the combine
 //     kernels, sink or not, are launched unchanged.  With TREE = false every term folds away.
+//   * SHARED (flash_attention_cascade_decode*): the cache is ONE prefix that every sequence of the batch sees in
+//     full, so the unit is (K/V head, row block, split) with no batch index and the packed rows of a K/V head run ACROSS the batch:
+//     packed row = (b G + g) Sq + i, B G Sq of them, and a row block of 16 RT rows holds rows of several sequences -- a K/V tile of the
+//     prefix is fetched once for all of them.  K and V are head kvh of the one shared cache (paged: the pool through the one-row
+//     table), len is the shared length (kv_lens[0] clamped into [1, Sk]), and every row has lo = 0, span = len: no mask, p.causal is
+//     not read.  The epilogue writes slabs under every split count, ns = 1 included, at decode's slab row (b H + h) Sq + i, and never
+//     O: the sequences' own suffixes are decode's kernel into further slabs and the one combine merges both.  The loop body, the
+//     fetch, the fp8 path and the four-wave merge are the same text.  The form is RT = ExtendCfg<D>::RT, WINDOW = VARLEN = SINK = TREE =
+//     false, with a parameter type of its own (SharedDecodeParams: the struct + B).  With SHARED = false every term folds away.
 #pragma once
 
 #include "../../include/flash_attention.h"
@@ -155,9 +164,18 @@ struct SinkVarlenDecodeParams : VarlenDecodeParams {
 struct TreeDecodeParams : SinkDecodeParams {
     const uint64_t* tree_mask;    // [B][Sq] (device memory): bit j of word (b, i) set = query row i sees draft node j = key len - Sq + j
 };
-template <bool VARLEN, bool SINK = false, bool TREE = false>
+// The shared-prefix (SHARED) kernels' argument (flash_attention_cascade_decode*), again a type of its own: K / V,
+// kv_lens (one entry), Sk and the table describe the ONE shared cache; row_blocks counts the blocks of the B * G * Sq packed rows
+struct SharedDecodeParams : DecodeParams {
+    int B;
+};
+template <bool VARLEN, bool SINK = false, bool TREE = false, bool SHARED = false>
 struct SplitParamsOf {
     using type = DecodeParams;
+};
+template <>
+struct SplitParamsOf<false, false, false, true> {
+    using type = SharedDecodeParams;
 };
 template <>
 struct SplitParamsOf<false, true, true> {
@@ -261,10 +279,13 @@ __device__ __forceinline__ bool varlen_unit_of(const VarlenDecodeParams& p, int 
 // ragged chunked prefill: those with VARLEN.  SINK (WINDOW = true only; launched with ns = 1 only -- under more splits the sink is the
 // combine's): the epilogue adds the row's head's sink, a key with value 0, to (M, L) before it normalises; the loop is the same text.
 // TREE (SINK = true, VARLEN = false only; launched under any ns): the masked select in the tiles that reach into the draft's keys.
-template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false, bool SINK = false, bool TREE = false>
-__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN, SINK, TREE>::type p) {
+// SHARED (RT = ExtendCfg<D>::RT, every other flag false; launched under any ns): one cache for the whole batch, packed rows across it,
+// slabs only.
+template <int D, int RT, bool PAGED, bool KV8, bool WINDOW, bool VARLEN = false, bool SINK = false, bool TREE = false, bool SHARED = false>
+__global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const typename SplitParamsOf<VARLEN, SINK, TREE, SHARED>::type p) {
     static_assert(!SINK || WINDOW, "the SINK forms are WINDOW = true: a sinks call without a window runs them at window = 0");
     static_assert(!TREE || (SINK && !VARLEN), "the TREE forms are WINDOW = true, SINK = true, VARLEN = false");
+    static_assert(!SHARED || !(WINDOW || VARLEN || SINK || TREE), "the SHARED forms are WINDOW = VARLEN = SINK = TREE = false");
     constexpr int ES = KV8 ? 1 : 2;   // bytes per K/V element
     using KV = __attribute__((may_alias)) typename std::conditional<KV8, uint8_t, __bf16>::type;
     using C = DecodeCfg<D, ES>;
@@ -285,7 +306,8 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
     }
     const int rb = VARLEN ? vu.rb : u % p.row_blocks; u /= p.row_blocks;
     const int kvh = VARLEN ? u : u % p.Hkv;
-    const int b = VARLEN ? vu.b : u / p.Hkv;
+    // SHARED: (K/V head, row block, split) -- there is one cache, entry 0 of kv_lens and row 0 of the table; the batch index is a row's
+    const int b = VARLEN ? vu.b : SHARED ? 0 : u / p.Hkv;
 
     int len = p.Sk;
     if (p.kv_lens) len = min(max(p.kv_lens[b], 1), p.Sk);
@@ -298,9 +320,12 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
     // largest query row of the block is the last one -- unless the block reaches into the next head, then it holds a row Sq - 1.
     // RT = 1: the host caps Sq at FA_DECODE_MAX_Q = 16, so a 16-row block always holds a row with lim = len (its last row is the last
     // of all, or it holds the last query row of a head): limb = len without the arithmetic
-    const int nrows = p.G * Sq, pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
+    // SHARED: the packed rows are those of the whole batch, (b G + g) Sq + i, and every row sees the whole prefix
+    int nrows = p.G * Sq;
+    if constexpr (SHARED) nrows *= p.B;
+    const int pr0 = rb * RPB, prl = min(pr0 + RPB, nrows) - 1;
     const int gl = prl / Sq, qmax = pr0 / Sq != gl ? Sq - 1 : prl - gl * Sq;
-    const int limb = RT > 1 && p.causal ? max(len - Sq + qmax + 1, 1) : len;
+    const int limb = !SHARED && RT > 1 && p.causal ? max(len - Sq + qmax + 1, 1) : len;
     // the lowest key a row of THIS BLOCK sees: the lower bound of its smallest query row -- row 0 if the block reaches into the next
     // head, else its first row's.  RT = 1, no window, or Sq <= FA_DECODE_MAX_Q (the decode seam: the range stays decode's): `first`
     int firstb = first;
@@ -326,13 +351,19 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
     for (int rt = 0; rt < RT; ++rt) {
         const int pr = pr0 + rt * C::ROWS + r;
         const bool row_ok = pr < nrows;
-        const int g = row_ok ? pr / Sq : 0, qi = row_ok ? pr - g * Sq : 0;
+        int g = row_ok ? pr / Sq : 0;
+        const int qi = row_ok ? pr - g * Sq : 0;
+        int qb = b;   // the sequence of the row.  SHARED: g is b G + g so far
+        if constexpr (SHARED) {
+            qb = g / p.G;
+            g -= qb * p.G;
+        }
         const int h = kvh * p.G + g;
         const int limc = max(len - Sq + qi + 1, 1);
-        const int lim = p.causal ? limc : len;
+        const int lim = !SHARED && p.causal ? limc : len;
         lo[rt] = WINDOW && p.window > 0 ? max(limc - p.window, 0) : 0;
         span[rt] = (unsigned)(lim - lo[rt]);
-        const __bf16* q = p.Q + (VARLEN ? 0 : b * p.qB) + h * p.qH + (q0 + qi) * p.qS + (KV8 ? 16 : 8) * h4;
+        const __bf16* q = p.Q + (VARLEN ? 0 : qb * p.qB) + h * p.qH + (q0 + qi) * p.qS + (KV8 ? 16 : 8) * h4;
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
             const u32x4 z = {0u, 0u, 0u, 0u};
@@ -600,7 +631,13 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
         }
         const int opr = pr0 + rt * C::ROWS + orow;
         if (opr < nrows) {   // (no early exit: the barriers of the tiles to come are the whole workgroup's)
-            const int og = opr / Sq, oi = opr - og * Sq, oh = kvh * p.G + og;
+            int og = opr / Sq, ob = b;
+            const int oi = opr - og * Sq;
+            if constexpr (SHARED) {   // (og is b G + g so far)
+                ob = og / p.G;
+                og -= ob * p.G;
+            }
+            const int oh = kvh * p.G + og;
             float inv = M != NEG_INF ? 1.0f / L : 0.f;                                         // empty split: O = 0
             if constexpr (KV8) inv *= p.v_descale ? p.v_descale[kvh] : 1.f;                    // V = V8 * v_descale: once, on the normalised sum
             float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;         // ... LSE = -inf
@@ -623,9 +660,9 @@ __global__ __launch_bounds__(256, RT <= 2 ? 2 : 1) void split_kv_kernel(const ty
                     }
                 }
             }
-            const int64_t row = VARLEN ? (int64_t)oh * p.Sq + q0 + oi : ((int64_t)b * p.H + oh) * Sq + oi;
-            if (p.ns == 1) {
-                const int64_t base = (VARLEN ? 0 : b * p.oB) + oh * p.oH + (q0 + oi) * p.oS + d0;
+            const int64_t row = VARLEN ? (int64_t)oh * p.Sq + q0 + oi : ((int64_t)ob * p.H + oh) * Sq + oi;
+            if (!SHARED && p.ns == 1) {   // (SHARED: slabs under every split count, never O)
+                const int64_t base = (VARLEN ? 0 : ob * p.oB) + oh * p.oH + (q0 + oi) * p.oS + d0;
 #pragma unroll
                 for (int j = 0; j < DPT; ++j) store_out(p.O, p.o_dtype, base + j, acc[j] * inv);
                 if (p.lse && (tid & 15) == 0) p.lse[row] = lse;

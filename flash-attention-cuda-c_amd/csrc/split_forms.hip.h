@@ -1,9 +1,10 @@
 // split_forms.hip.h -- THE list of the split-KV kernel's instantiations (decode_bf16.hip.h: split_kv_kernel): which combinations of its
 // template flags exist, which of them a call launches, and how the host reaches each.  One row of SPLIT_FORMS is one translation unit of
-// libflash_attention.so: split_unit.hip compiled with -DFA_SPLIT_UNIT=<the row's name> (the Makefile's SPLIT_UNITS names the same forty;
+// libflash_attention.so: split_unit.hip compiled with -DFA_SPLIT_UNIT=<the row's name> (the Makefile's SPLIT_UNITS names the same forty-four;
 // a name missing there is a link error, one missing here a compile error), holding that form's kernels at D = 64 / 128 and their
 // launcher.  FlashAttention.hip (decode_run) fills a SplitArgs, asks split_form_of for the form and calls its SPLIT_LAUNCH[split_unit_of(form)];
-// under more than one split, combine_launch (inst_split_combine.hip) after it.  DESIGN.md section 32.
+// under more than one split, combine_launch (inst_split_combine.hip) after it; cascade_run there launches a shared_* unit, a decode_* unit
+// and the combine.  DESIGN.md sections 32 and 34.
 #pragma once
 
 #include "decode_bf16.hip.h"
@@ -11,9 +12,10 @@
 
 namespace fa {
 
-// The template flags of one form; RT follows from extend (ExtendCfg<D>::RT, else 1), the parameter type from SplitParamsOf<varlen, sink, tree>
+// The template flags of one form; RT follows from extend (ExtendCfg<D>::RT, else 1), the parameter type from
+// SplitParamsOf<varlen, sink, tree, shared>
 struct SplitKind {
-    bool extend, varlen, window, paged, kv8, sink, tree;
+    bool extend, varlen, window, paged, kv8, sink, tree, shared;
     constexpr bool operator==(const SplitKind&) const = default;
 };
 
@@ -29,6 +31,7 @@ enum class SplitUnit : int {
     extend_sink_varlen_bf16, extend_sink_varlen_fp8, extend_sink_varlen_paged_bf16, extend_sink_varlen_paged_fp8,
     decode_tree_bf16, decode_tree_fp8, decode_tree_paged_bf16, decode_tree_paged_fp8,
     extend_tree_bf16, extend_tree_fp8, extend_tree_paged_bf16, extend_tree_paged_fp8,
+    shared_bf16, shared_fp8, shared_paged_bf16, shared_paged_fp8,
 };
 
 // One row per enumerator, in the enumeration's order: {bf16, fp8} x {contiguous, paged} of each family.  No other combination exists.
@@ -65,15 +68,22 @@ inline constexpr SplitKind SPLIT_FORMS[] = {
     {.extend = true, .window = true, .sink = true, .tree = true}, {.extend = true, .window = true, .kv8 = true, .sink = true, .tree = true},
     {.extend = true, .window = true, .paged = true, .sink = true, .tree = true},
     {.extend = true, .window = true, .paged = true, .kv8 = true, .sink = true, .tree = true},
+    // shared_*: the shared-prefix launch of flash_attention_cascade_decode[_paged]: the chunked-prefill row block (extend = true: RT > 1 and
+    // the VGPR-form flag) with the packed rows across the batch and every other flag false
+    {.extend = true, .shared = true}, {.extend = true, .kv8 = true, .shared = true},
+    {.extend = true, .paged = true, .shared = true}, {.extend = true, .paged = true, .kv8 = true, .shared = true},
 };
 // clang-format on
 constexpr int SPLIT_UNITS = sizeof(SPLIT_FORMS) / sizeof(SPLIT_FORMS[0]);
-static_assert(SPLIT_UNITS == (int)SplitUnit::extend_tree_paged_fp8 + 1, "one row per enumerator");
+static_assert(SPLIT_UNITS == (int)SplitUnit::shared_paged_fp8 + 1, "one row per enumerator");
 
 // The form a call launches.  windowed: windowSize > 0; sink_in_split: the call has sinks and runs under ONE split (under more the split
 // kernel is the call's own without sinks -- the slabs hold the keys alone -- and the SINK combine adds the sink); tree: the call has a
-// tree mask, and launches a TREE form (which takes the sinks pointer, NULL or not) whatever the split count
-constexpr SplitKind split_form_of(bool extend, bool varlen, bool windowed, bool paged, bool kv8, bool sink_in_split, bool tree) {
+// tree mask, and launches a TREE form (which takes the sinks pointer, NULL or not) whatever the split count; shared: the shared-prefix
+// launch of a cascade call, which is none of the others (its sinks are the combine's, under any split count)
+constexpr SplitKind split_form_of(bool extend, bool varlen, bool windowed, bool paged, bool kv8, bool sink_in_split, bool tree,
+                                  bool shared = false) {
+    if (shared) return {.extend = true, .paged = paged, .kv8 = kv8, .shared = true};
     const bool sink = sink_in_split || tree;
     return {extend, varlen, !extend || windowed || sink, paged, kv8, sink, tree};
 }
@@ -85,16 +95,20 @@ constexpr int split_unit_of(const SplitKind& k) {
     return -1;
 }
 
-// Checked at every build, over everything a call can ask for (varlen only with extend; a tree call is never ragged): the number of
-// calls whose form has no row or is not what the call asked for, and the number of rows no call selects
+// Checked at every build, over everything a call can ask for (varlen only with extend; a tree call is never ragged; a shared launch is
+// only ever contiguous or paged, bf16 or fp8): the number of calls whose form has no row or is not what the call asked for, and the
+// number of rows no call selects
 constexpr int split_calls_without_row() {
     int bad = 0;
-    for (int i = 0; i < 128; ++i) {
+    for (int i = 0; i < 256; ++i) {
         const bool extend = i & 1, varlen = i & 2, windowed = i & 4, paged = i & 8, kv8 = i & 16, sink_in_split = i & 32, tree = i & 64;
-        if ((varlen && !extend) || (tree && varlen)) continue;
-        const SplitKind k = split_form_of(extend, varlen, windowed, paged, kv8, sink_in_split, tree);
-        const bool passed = k.extend == extend && k.varlen == varlen && k.paged == paged && k.kv8 == kv8 && k.tree == tree;
-        bad += !(split_unit_of(k) >= 0 && passed && k.sink == (sink_in_split || tree) && k.window == (!extend || windowed || k.sink));
+        const bool shared = i & 128;
+        if ((varlen && !extend) || (tree && varlen) || (shared && (extend || varlen || windowed || sink_in_split || tree))) continue;
+        const SplitKind k = split_form_of(extend, varlen, windowed, paged, kv8, sink_in_split, tree, shared);
+        const bool passed = k.extend == (extend || shared) && k.varlen == varlen && k.paged == paged && k.kv8 == kv8 && k.tree == tree
+                            && k.shared == shared;
+        bad += !(split_unit_of(k) >= 0 && passed && k.sink == (sink_in_split || tree)
+                 && k.window == (!shared && (!extend || windowed || k.sink)));
     }
     return bad;
 }
@@ -102,8 +116,9 @@ constexpr int split_rows_without_call() {
     int dead = 0;
     for (int u = 0; u < SPLIT_UNITS; ++u) {   // (a row is selected by the call that asks for exactly it, or by none; a second copy of a row never is)
         const SplitKind& k = SPLIT_FORMS[u];
-        dead += !(k.varlen <= k.extend && !(k.tree && k.varlen)
-                  && split_unit_of(split_form_of(k.extend, k.varlen, k.window, k.paged, k.kv8, k.sink && !k.tree, k.tree)) == u);
+        dead += !(k.varlen <= k.extend && !(k.tree && k.varlen) && !(k.shared && (k.varlen || k.window || k.sink || k.tree))
+                  && split_unit_of(split_form_of(k.extend && !k.shared, k.varlen, k.window, k.paged, k.kv8, k.sink && !k.tree, k.tree,
+                                                 k.shared)) == u);
     }
     return dead;
 }
@@ -117,7 +132,7 @@ struct SplitArgs : SinkVarlenDecodeParams {
 
 // Unit U's launcher: SPLIT_FORMS[U]'s kernel at D = d (128, else 64) with that form's exact parameter type.  Declared only: each unit
 // (split_unit.hip) defines the one specialisation that is its own, so no translation unit can instantiate another unit's kernels, and
-// FlashAttention.hip alone takes the forty addresses (SPLIT_LAUNCH there)
+// FlashAttention.hip alone takes the forty-four addresses (SPLIT_LAUNCH there)
 template <SplitUnit U>
 int split_unit_launch(int d, unsigned grid, hipStream_t st, const SplitArgs& a);
 
@@ -127,6 +142,7 @@ P split_params(const SplitArgs& a) {
     P p;
     static_cast<DecodeParams&>(p) = a;
     if constexpr (requires { p.cu_q; }) { p.cu_q = a.cu_q; p.B = a.B; }
+    else if constexpr (requires { p.B; }) p.B = a.B;
     if constexpr (requires { p.sinks; }) p.sinks = a.sinks;
     if constexpr (requires { p.tree_mask; }) p.tree_mask = a.tree_mask;
     return p;

@@ -1000,6 +1000,78 @@ int flash_attention_tree_plan(int batchSize, int numHeads, int numHeadsKV, int s
                               int numSplits, int windowSize, fa_decode_plan* plan);
 
 /*
+ * flash_attention_cascade_decode, flash_attention_cascade_decode_paged -- SHARED-PREFIX (cascade) decode: the sequences of the batch share
+ * one prefix (a system prompt, n samples of one prompt, beams, best-of-n candidates), and the call reads that prefix ONCE per row block
+ * of the whole batch instead of once per sequence.  The logical cache of sequence b is [ shared[0 : ls) ; unique_b[0 : len_b) ]:
+ *   Kshared, Vshared  [numHeadsKV, seqLenShared, dHead], the cache's type; strides sKshared / sVshared (strideB is not read).  Paged: one
+ *            pool serves both parts; sharedTable is int32[maxSharedPages] (device memory), the shared part's pages in order, and
+ *            blockTable holds the SUFFIX pages (an engine passes its table offset by the shared pages: the shared part is whole pages,
+ *            the tail of a prompt that does not fill a page lives in the suffix).  Entries are read and clamped by the kernel as in
+ *            flash_attention_decode_paged: only those of pages that hold a key below the length, each into [0, numPages)
+ *   sharedLen  int32[1] (device memory): ls = sharedLen[0] clamped into [1, seqLenShared] (paged: maxSharedPages * pageSize) on the
+ *            device; NULL = the capacity.  Read by the kernel like kvLens: a replayed graph sees the value of the moment
+ *   K, V, kvLens, blockTable  the sequences' own suffixes, as in flash_attention_decode*: len_b = kvLens[b] clamped into [1, seqLenK]
+ *   mask     the seqLenQ (1 .. FA_DECODE_MAX_Q) query rows are the last rows of the logical sequence.  Every row sees ALL ls shared
+ *            keys -- there is no mask on the shared part -- and of its own suffix what flash_attention_decode shows it on that suffix
+ *            alone: the bottom-right is_causal rule, "at least key 0" included.  So whenever len_b >= seqLenQ the result is
+ *            flash_attention_decode with is_causal on the concatenated cache of length ls + len_b.  The LSE is over all visible keys
+ *            of both parts.  Keys at and beyond ls in the shared cache, keys beyond len_b in the suffixes and pages not read may hold
+ *            anything
+ *   kv_dtype FA_DTYPE_BF16, or FA_DTYPE_FP8_E4M3 with kDescale / vDescale [numHeadsKV] (NULL = 1): ONE pair for both parts.  A
+ *            non-NULL descale with a bf16 cache is FA_ERR_UNSUPPORTED_DTYPE
+ *   sinks    NULL, or [numHeads] fp32 attention sinks; they join once per row, as in flash_attention_sink_decode
+ *   numSplitsShared, numSplitsUnique  0 = the library chooses, from shapes only (shared: flash_attention_extend's rule with
+ *            numHeadsKV * ceil(batchSize * G * seqLenQ / rows_per_block) units and the tiles of seqLenShared; unique:
+ *            flash_attention_decode's, clamped into [2, 32]; the shared count is then capped at FA_DECODE_MAX_SPLITS - unique).  Forced
+ *            values are taken as given: numSplitsUnique >= 2 (the suffix kernel writes partial results under more than one split only)
+ *            and the sum at most FA_DECODE_MAX_SPLITS
+ *   plan     flash_attention_cascade_plan (seqLenShared, seqLenK: the capacities): `shared` and `unique` describe the two split
+ *            launches (shared.grid = numHeadsKV * row_blocks * num_splits, no batch factor), num_splits is their sum
+ *   workspace  flash_attention_decode_workspace_size(batchSize, numHeads, seqLenQ, dHead, plan.num_splits) bytes, ALWAYS required
+ * Three launches on the stream, no host synchronisation, graph-capturable: the shared-prefix form of the split-KV kernel (packed rows
+ * (b * G + g) * seqLenQ + i across the batch, rows_per_block of them per workgroup) into partial results [0, ns_s); decode's own kernel
+ * on the suffixes into [ns_s, ns_s + ns_u); the combine kernel of flash_attention_decode over all of them, in a fixed order: the same
+ * bits run to run.  The paged call is the contiguous call on gathered copies under the same split counts, bit for bit.
+ *
+ * Rejected before any launch: everything flash_attention_decode_window / _paged_window of the same kv_dtype rejects, with the same
+ * codes and in the same order, the new arguments at their kind's place: NULL Kshared / Vshared / sharedTable FA_ERR_NULL_POINTER with
+ * the other pointers and a NULL workspace where decode asks for its own; sharedLen or sinks not 4-byte aligned FA_ERR_MISALIGNED with
+ * the other arrays; seqLenShared <= 0 or > 2^24, maxSharedPages <= 0, numSplitsUnique == 1, a negative count, a sum above
+ * FA_DECODE_MAX_SPLITS (a count left to the library needs room for 1 shared and 2 unique) or a shared grid at or above
+ * FA_DECODE_MAX_WORKGROUPS FA_ERR_BAD_SHAPE; the strides and extents of the shared tensors are checked as those of K / V.
+ * Not done here: several prefix groups in one call and multi-level cascades (call once per group), windows, tree masks,
+ * seqLenQ > FA_DECODE_MAX_Q, a ragged form, a stand-alone merge of (O, LSE) pairs.
+ */
+typedef struct fa_cascade_plan {
+    fa_decode_plan shared;   /* the shared-prefix launch */
+    fa_decode_plan unique;   /* decode's launch on the suffixes */
+    int num_splits;          /* shared.num_splits + unique.num_splits: what the workspace and the combine are sized by */
+} fa_cascade_plan;
+
+int flash_attention_cascade_plan(int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenShared, int seqLenK, int dHead,
+                                 int o_dtype, int numSplitsShared, int numSplitsUnique, fa_cascade_plan* plan);
+
+int flash_attention_cascade_decode(const void* Q, const void* Kshared, const void* Vshared, const void* K, const void* V, void* O,
+                                   float* LSE, const int32_t* sharedLen, const int32_t* kvLens,
+                                   const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                   int batchSize, int numHeads, int numHeadsKV, int seqLenQ, int seqLenShared, int seqLenK, int dHead,
+                                   float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype,
+                                   int numSplitsShared, int numSplitsUnique,
+                                   const fa_strides* sQ, const fa_strides* sKshared, const fa_strides* sVshared,
+                                   const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, void* stream);
+
+int flash_attention_cascade_decode_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* LSE,
+                                         const int32_t* sharedLen, const int32_t* kvLens,
+                                         const int32_t* sharedTable, const int32_t* blockTable,
+                                         const float* kDescale, const float* vDescale, const float* sinks, void* workspace,
+                                         int batchSize, int numHeads, int numHeadsKV, int seqLenQ,
+                                         int numPages, int pageSize, int maxSharedPages, int maxPagesPerSeq, int64_t tableStride,
+                                         int dHead, float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype,
+                                         int numSplitsShared, int numSplitsUnique,
+                                         const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                         void* stream);
+
+/*
  * flash_attention_kv_append_varlen, flash_attention_kv_append_paged_varlen -- the RAGGED cache append: flash_attention_kv_append /
  * _paged with Knew / Vnew packed by token -- [totalQ, numHeadsKV, dHead] bf16 on the stride rule of flash_attention_extend_varlen's Q
  * (row t, K/V head h at t * strideS + h * strideH; strideB ignored; NULL = dense token-major) -- seqLenNew replaced by totalQ and

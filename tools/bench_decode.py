@@ -130,6 +130,18 @@ Each line:
               rope_append_ms, rope_pos_ms  rope_cache_append* of the N rows without and with pos_offsets = the tree's depths, alternated
               rope_pos_ratio = rope_pos_ms / rope_append_ms (medians); twin_span = max / min of rope_append_ms's own windows: the
                            ratio to hold it against (profiles/spec_step_gpu.log).
+--cascade       shared-prefix decode (flash_attention_cascade_decode*) beside flash_attention_decode* on the same logical
+              problem: a mode of its own over CASCADE_SHAPES (B sequences, a shared prefix of Ls keys, suffixes of Lu keys each).  One
+              line per shape and cache form ("bf16", with --kv fp8 "fp8", with --paged "paged<page>" and "paged<page>_fp8").  Contiguous: the
+              decode call reads caches [B, Hkv, Ls + Lu, d] that each hold a copy of the prefix; paged: the decode call's block table names
+              the shared pages in every row, the cascade call gets the same pool with shared_table and the suffix columns of that table.
+              The two calls share Q, the lengths, is_causal and the output type, each has its O and workspace, and they are timed
+              ALTERNATED, --repeats windows of --steps calls each, after the usual priming:
+              decode_ms   flash_attention_decode* under its own plan: [median, min, max] of its windows
+              cascade_ms  flash_attention_cascade_decode* under the plan in "splits" = [shared, unique], likewise
+              ratio = decode_ms / cascade_ms (medians); rows_ratio: the K/V rows per K/V head the two read by their grids, B (Ls + Lu) over
+              ceil(B G Sq / rows_per_block) Ls + B Lu; max_diff: the largest |O_cascade - O_decode| of one call each (bf16 outputs).
+              With --splits s:u[,s:u...]: the forced sweep, one line per (shape, form, pair) (profiles/cascade_gpu.log).
 """
 import argparse
 import json
@@ -639,6 +651,103 @@ def sinks_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+CASCADE_SHAPES = [  # name, B, H, Hkv, Sq, Ls, Lu, d
+    ("cascade_b8", 8, 32, 8, 1, 8192, 256, 128),
+    ("cascade_b32", 32, 32, 8, 1, 8192, 256, 128),
+    ("cascade_b32_spec4", 32, 32, 8, 4, 8192, 256, 128),
+    ("cascade_b2_short", 2, 32, 8, 1, 128, 256, 128),      # sharing cannot pay: two sequences, one tile of prefix
+]
+
+
+def cascade_main(args, fa, dev):
+    """--cascade: flash_attention_cascade_decode* beside flash_attention_decode* on the same logical problem, alternated"""
+    import torch
+    f8 = torch.float8_e4m3fn
+    pages = [int(x) for x in (args.paged or "").split(",") if x]
+    sweep = [tuple(int(n) for n in pair.split(":")) for pair in (args.splits or "").split(",") if pair] or [(0, 0)]
+    shapes = CASCADE_SHAPES
+    if args.shape:
+        unknown = set(args.shape) - {x[0] for x in CASCADE_SHAPES}
+        if unknown:
+            raise SystemExit(f"unknown --cascade shape(s): {sorted(unknown)}")
+        shapes = [x for x in CASCADE_SHAPES if x[0] in args.shape]
+    primed = False
+    for name, B, H, Hkv, Sq, Ls, Lu, d in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        rnd = lambda *shape: torch.randn(*shape, device=dev, generator=g).to(torch.bfloat16)
+        Q, Ks, Vs, Ku, Vu = rnd(B, H, Sq, d), rnd(Hkv, Ls, d), rnd(Hkv, Ls, d), rnd(B, Hkv, Lu, d), rnd(B, Hkv, Lu, d)
+        lens_u = torch.full((B,), Lu, dtype=torch.int32, device=dev)
+        lens_all = torch.full((B,), Ls + Lu, dtype=torch.int32, device=dev)
+        sl = torch.tensor([Ls], dtype=torch.int32, device=dev)
+        Od, Oc = (torch.empty(B, H, Sq, d, device=dev, dtype=torch.bfloat16) for _ in range(2))
+        forms = [("bf16", False, 0)] + ([("fp8", True, 0)] if args.kv == "fp8" else [])
+        for page in pages:
+            if Ls % page == 0 and Lu % page == 0:
+                forms += [(f"paged{page}", False, page)] + ([(f"paged{page}_fp8", True, page)] if args.kv == "fp8" else [])
+        kw = {}
+        if args.kv == "fp8":      # one descale pair per K/V head for both parts
+            kds, vds = ((torch.maximum(s.float().abs().amax(dim=(1, 2)), u.float().abs().amax(dim=(0, 2, 3))) / 448.0).float()
+                        for s, u in ((Ks, Ku), (Vs, Vu)))
+            q8 = lambda t, ds, dim: (t.float() / ds.view([-1 if i == dim else 1 for i in range(t.dim())])).clamp(-448, 448).to(f8)
+            Ks8, Vs8, Ku8, Vu8 = q8(Ks, kds, 0), q8(Vs, vds, 0), q8(Ku, kds, 1), q8(Vu, vds, 1)
+        rpb = fa.cascade_plan(B, H, Hkv, Sq, Ls, Lu, d)["shared"]["rows_per_block"]
+        rows_ratio = round(B * (Ls + Lu) / (-(-B * (H // Hkv) * Sq // rpb) * Ls + B * Lu), 3)
+        for form, fp8, page in forms:
+            s_k, s_v, u_k, u_v = (Ks8, Vs8, Ku8, Vu8) if fp8 else (Ks, Vs, Ku, Vu)
+            kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+            if page:
+                ns_p, nu_p = Ls // page, Lu // page
+                perm = torch.randperm(ns_p + B * nu_p, device=dev, generator=g)
+                shared_table = perm[:ns_p].to(torch.int32).contiguous()
+                suffix_table = perm[ns_p:].reshape(B, nu_p).to(torch.int32)
+                full_table = torch.cat([shared_table[None].expand(B, -1), suffix_table], 1).contiguous()
+                pools = []
+                for s_t, u_t in ((s_k, u_k), (s_v, u_v)):
+                    s_t, u_t = (t.view(torch.uint8) if fp8 else t for t in (s_t, u_t))      # (pages are moved as bytes)
+                    pool = torch.empty(ns_p + B * nu_p, Hkv, page, d, device=dev, dtype=s_t.dtype)
+                    pool[perm[:ns_p]] = s_t.view(Hkv, ns_p, page, d).transpose(0, 1)
+                    pool[perm[ns_p:]] = u_t.view(B, Hkv, nu_p, page, d).transpose(1, 2).reshape(B * nu_p, Hkv, page, d)
+                    pools.append(pool.view(f8) if fp8 else pool)
+                decode_head, decode_front = [Q, pools[0], pools[1], full_table, lens_all], fa.flash_attention_decode_paged
+                cascade_head = [Q, pools[0], pools[1], shared_table, full_table[:, ns_p:], sl, lens_u]
+                cascade_front = fa.flash_attention_cascade_decode_paged
+            else:
+                cat = lambda s_t, u_t: torch.cat([s_t[None].expand(B, -1, -1, -1).view(torch.uint8 if fp8 else s_t.dtype),
+                                                  u_t.view(torch.uint8 if fp8 else u_t.dtype)], 2).contiguous()
+                Kd, Vd = cat(s_k, u_k), cat(s_v, u_v)
+                if fp8:
+                    Kd, Vd = Kd.view(f8), Vd.view(f8)
+                decode_head, decode_front = [Q, Kd, Vd, lens_all], fa.flash_attention_decode
+                cascade_head, cascade_front = [Q, s_k, s_v, u_k, u_v, sl, lens_u], fa.flash_attention_cascade_decode
+            dplan = fa.decode_plan(B, H, Hkv, Sq, Ls + Lu, d, fa.FA_DTYPE_BF16, 0)
+            dws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, d, dplan["num_splits"]), 16), dtype=torch.uint8, device=dev)
+            decode = lambda: decode_front(*decode_head, is_causal=True, O=Od, workspace=dws, **kw)
+            for pair in sweep:
+                cplan = fa.cascade_plan(B, H, Hkv, Sq, Ls, Lu, d, fa.FA_DTYPE_BF16, pair)
+                cws = torch.empty(fa.decode_workspace_size(B, H, Sq, d, cplan["num_splits"]), dtype=torch.uint8, device=dev)
+                cascade = lambda: cascade_front(*cascade_head, is_causal=True, O=Oc, workspace=cws, num_splits=pair, **kw)
+                if not primed:   # >= 1 s of calls before the first timed window
+                    t = 0.0
+                    while t < 1000.0:
+                        t += timed(decode, 50, 0) * 50
+                    primed = True
+                a, b = [], []
+                for _ in range(args.repeats):
+                    a.append(timed(decode, args.steps, args.warmup))
+                    b.append(timed(cascade, args.steps, args.warmup))
+                a, b = sorted(a), sorted(b)
+                print(json.dumps({"shape": name, "form": form, "B": B, "Sq": Sq, "Ls": Ls, "Lu": Lu,
+                                  "decode_splits": dplan["num_splits"], "splits": [cplan["shared"]["num_splits"], cplan["unique"]["num_splits"]],
+                                  "forced": pair != (0, 0),
+                                  "decode_ms": [round(x, 5) for x in (statistics.median(a), a[0], a[-1])],
+                                  "cascade_ms": [round(x, 5) for x in (statistics.median(b), b[0], b[-1])],
+                                  "ratio": round(statistics.median(a) / statistics.median(b), 4), "rows_ratio": rows_ratio,
+                                  "max_diff": round((Oc.float() - Od.float()).abs().max().item(), 5)}), flush=True)
+            del decode_head, cascade_head
+        del Q, Ks, Vs, Ku, Vu
+        torch.cuda.empty_cache()
+
+
 def tree_main(args, fa, dev):
     """--tree N[,N...]: flash_attention_tree on the decode shapes with N draft nodes per sequence, beside its causal twin, alternated"""
     import torch
@@ -945,12 +1054,15 @@ def main():
     ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
     ap.add_argument("--rope", action="store_true", help="time rope_cache_append* beside the unfused torch route and the plain append, alternated")
     ap.add_argument("--tree", default=None, help="comma-separated draft-node counts: time flash_attention_tree beside its causal twin, alternated")
+    ap.add_argument("--cascade", action="store_true", help="time flash_attention_cascade_decode* beside flash_attention_decode* on a shared prefix, alternated; --splits s:u,...")
     ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
     dev = torch.device("cuda:0")
+    if args.cascade:
+        return cascade_main(args, fa, dev)
     if args.accept:
         if not args.tree:
             ap.error("--accept takes the draft sizes from --tree N[,N...]")
