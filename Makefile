@@ -40,6 +40,8 @@ MFMA_VGPR := -mllvm -amdgpu-mfma-vgpr-form=1
 build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 # the backward kernel (bwd_bf16.hip.h) likewise: dV^T / dK^T of 64 keys take 256 registers; in the default form hipcc spills ~280 to scratch at D = 128
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
+# the MLA decode kernel (mla_decode.hip.h) likewise: 128 accumulator registers of O^T that the VALU rescales at every key tile
+build/obj/inst_mla_decode.o: HIPFLAGS += $(MFMA_VGPR)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS, and the shared_* ones, which are built at the same RT; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
 # tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
@@ -112,8 +114,9 @@ SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # nothing preloaded; tests/host_ladder.h is what they share), each built and run: the validation ladders and plans of the ragged entry
 # points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins,
 # of the two tree-masked ones beside their sink twins, of the speculative step's rope_append_pos and kv_accept ones beside their rope_append
-# and kv_append twins, of the two shared-prefix decode ones and their plan beside flash_attention_decode_window / _paged_window
-LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder host_cascade_ladder
+# and kv_append twins, of the two shared-prefix decode ones and their plan beside flash_attention_decode_window / _paged_window, of the two MLA decode ones and
+# their plan beside flash_attention_decode / _paged
+LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder host_cascade_ladder host_mla_ladder
 $(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip
@@ -139,7 +142,7 @@ asan: asan-host oracle
 # Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
-build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s: HIPFLAGS += $(MFMA_VGPR)
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s: HIPFLAGS += $(MFMA_VGPR)
 define ASM_RECIPE
 @mkdir -p build/asm
 $(HIPCC) $(HIPFLAGS) $(1) -S --cuda-device-only -o $@.tmp $<

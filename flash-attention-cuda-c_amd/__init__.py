@@ -87,6 +87,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_rope_append_pos", "flash_attention_rope_append_paged_pos",
            "flash_attention_kv_accept", "flash_attention_kv_accept_paged",
            "flash_attention_cascade_decode", "flash_attention_cascade_decode_paged", "flash_attention_cascade_plan",
+           "flash_attention_mla_decode", "flash_attention_mla_decode_paged", "flash_attention_mla_decode_plan",
+           "flash_attention_mla_decode_workspace_size",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -247,6 +249,16 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_cascade_decode.restype = L.flash_attention_cascade_decode_paged.restype = i
         L.flash_attention_cascade_plan.argtypes = [i] * 10 + [ctypes.POINTER(FaCascadePlan)]
         L.flash_attention_cascade_plan.restype = i
+        # the MLA pair: Q, the latent cache (paged: the pool), O, LSE, kvLens, the table (paged), the workspace; no K/V head count;
+        # dLatent, dRope where dHead stands; three strides
+        for paged in (False, True):
+            fn = getattr(L, "flash_attention_mla_decode_paged" if paged else "flash_attention_mla_decode")
+            fn.argtypes = [vp] * 5 + [vp] * paged + [vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i] + [sp] * 3 + [vp]
+            fn.restype = i
+        L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_mla_decode_plan.restype = i
+        L.flash_attention_mla_decode_workspace_size.argtypes = [i, i, i, i, i]
+        L.flash_attention_mla_decode_workspace_size.restype = ctypes.c_size_t
         for by_window in _PLAN_SYMBOLS.values():
             for window, name in enumerate(by_window):
                 fn = getattr(L, name)
@@ -1007,6 +1019,90 @@ def flash_attention_cascade_decode_paged(Q, K_pool, V_pool, shared_table, block_
     ``flash_attention_decode_paged``; the result is the contiguous call's on gathered copies under the same ``num_splits``, bit for bit."""
     return _cascade_front(Q, None, None, K_pool, V_pool, shared_table, block_table, shared_len, kv_lens, scale, is_causal, out_dtype,
                           num_splits, return_lse, O, workspace, stream, k_descale, v_descale, sinks)
+
+
+# ---- MLA decode (DESIGN.md section 35): one latent cache read as K (576 columns) and as V (the first 512) ----
+MLA_D_LATENT, MLA_D_ROPE = 512, 64
+_MLA_SYMBOLS = {False: "flash_attention_mla_decode", True: "flash_attention_mla_decode_paged"}
+
+
+def mla_decode_plan(B, H, Sq, Sk, o_dtype=FA_DTYPE_BF16, num_splits=0):
+    """What a flash_attention_mla_decode call launches (fa_decode_plan as a dict; ``Sk`` the capacity): row blocks of 64 packed rows
+    ``h * Sq + i``, ``grid = B * row_blocks * num_splits``; ``num_splits`` 0 = the library's choice (a rule that is not measured).
+    The workspace is ``decode_workspace_size(B, H, Sq, 512, num_splits)``."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_mla_decode_plan(B, H, Sq, Sk, MLA_D_LATENT, MLA_D_ROPE, o_dtype, num_splits, ctypes.byref(p)))
+    return _plan_dict(p)
+
+
+def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream):
+    """Both MLA fronts: the checks of the tensors (with the decode fronts' helpers for the table, the lengths and the workspace), the plan
+    and the workspace for the capacity, then the entry point of _MLA_SYMBOLS."""
+    import torch
+    paged = block_table is not None
+    name = _MLA_SYMBOLS[paged]
+    if not (Q.is_cuda and KV.is_cuda and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    D = MLA_D_LATENT + MLA_D_ROPE
+    if Q.dim() != 4 or KV.dim() != 3 or (not paged and Q.shape[0] != KV.shape[0]) or Q.shape[3] != D or KV.shape[2] != D:
+        raise ValueError(f"Q must be [B, H, Sq, {D}] and {'KV_pool [P, page' if paged else 'KV [B, capacity'}, {D}]")
+    if Q.dtype != KV.dtype:
+        raise TypeError("Q, KV must share a dtype")
+    if KV.stride(2) != 1:
+        raise ValueError("last dimension must be contiguous")
+    B, H, Sq, _ = Q.shape
+    # the cache as the [*, 1, rows, 576] tensor the decode helpers describe: one K/V "head"
+    capacity, tables, geometry = _cache_geometry(KV.unsqueeze(1), block_table, B)
+    _check_kv_lens(kv_lens, B)
+    if scale is None:
+        scale = float(D) ** -0.5
+    odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
+    ns = mla_decode_plan(B, H, Sq, capacity, odt, num_splits)["num_splits"]
+    need = decode_workspace_size(B, H, Sq, MLA_D_LATENT, ns)
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.empty((B, H, Sq, MLA_D_LATENT), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif tuple(O.shape) != (B, H, Sq, MLA_D_LATENT) or not O.is_cuda:
+                raise ValueError(f"O must be a device tensor [B, H, Sq, {MLA_D_LATENT}]")
+            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+            if workspace is None and need:
+                workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+        if need and (not workspace.is_cuda or workspace.numel() * workspace.element_size() < need):
+            raise ValueError(f"workspace must be a device tensor of at least {need} bytes")
+        sQ, sO = _strides(Q), _strides(O)
+        sKV = FaStrides(KV.stride(0), 0, KV.stride(1))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = getattr(lib(), name)(Q.data_ptr(), KV.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables),
+                                  workspace.data_ptr() if need else None, B, H, Sq, *geometry, MLA_D_LATENT, MLA_D_ROPE, float(scale),
+                                  bool(is_causal), _dtype_code(Q.dtype), _dtype_code(O.dtype), ns,
+                                  ctypes.byref(sQ), ctypes.byref(sKV), ctypes.byref(sO), _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
+
+
+def flash_attention_mla_decode(Q, KV, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
+                               O=None, workspace=None, stream=None):
+    """Decode for multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2) in its absorbed form: Q ``[B, H, Sq, 576]`` (bf16; the
+    absorbed ``q_nope @ W_UK`` in columns [0, 512), the rotated ``q_rope`` in [512, 576)), 1 <= Sq <= FA_DECODE_MAX_Q, against ONE
+    latent cache ``KV [B, capacity, 576]`` shared by all heads: ``O = softmax(scale * Q KV^T) KV[:, :512]``, ``[B, H, Sq, 512]``.
+
+    ``scale``: None = ``576 ** -0.5`` (FlashMLA's default, the full width of the score); a model passes its own softmax scale,
+    ``mscale ** 2 / sqrt(192)`` -- the absorption does not change it.  ``kv_lens``, ``is_causal`` (bottom-right aligned),
+    ``num_splits`` (0 = ``mla_decode_plan``'s choice), ``workspace`` (``decode_workspace_size(B, H, Sq, 512, ns)`` bytes), ``O``,
+    ``return_lse`` and ``stream`` as for ``flash_attention_decode``; strided views are accepted (last dimension contiguous).
+    The cache row is fetched once per 64 packed rows and serves both products.  No CPU fallback."""
+    return _mla_front(Q, KV, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream)
+
+
+def flash_attention_mla_decode_paged(Q, KV_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
+                                     return_lse=False, O=None, workspace=None, stream=None):
+    """``flash_attention_mla_decode`` against a PAGED latent cache: ``KV_pool [P, page, 576]`` (page a power of two >= 16) and
+    ``block_table`` int32 ``[B, max_pages]`` as in ``flash_attention_decode_paged``: entries and lengths are read and clamped by the
+    kernel, pages no visible key lies in are not read.  ``scale`` None = ``576 ** -0.5``.  The result is the contiguous call's on a
+    gathered copy under the same ``num_splits``, bit for bit."""
+    return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream)
 
 
 def _tree_parents(parents):

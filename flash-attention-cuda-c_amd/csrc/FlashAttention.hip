@@ -24,6 +24,7 @@
 #include "kv_accept.hip.h"
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
+#include "mla_decode.hip.h"
 
 namespace fa {
 
@@ -880,6 +881,108 @@ static int kv_accept_run(AcceptCall c) {
     const Kernel k = kv_accept_kernel_of(d, kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
     return (int)launch(k, (unsigned)grid, KvAcceptCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
 }
+
+// ---- MLA decode: flash_attention_mla_decode* (mla_decode.hip.h) ----
+// One latent cache [B, Sk, 576] (paged: [numPages, pageSize, 576]) read as K (all 576 columns) and as V (the first 512); one K/V "head"
+// for all H query heads.  A kernel of its own around decode's pieces: DecodeParams, the slab workspace, the combine at D = 512, the
+// cache checks.  The split rule is decode_route's formula with units = B * row blocks of 64 packed rows, one workgroup per CU and
+// EXTEND_MIN_TILES, the tiles counted in the kernel's own key tile (MlaCfg::KT).  NOT measured: the constants are chunked prefill's (the
+// other one-workgroup-per-CU form), and the forced sweep of tools/bench_decode.py --mla --splits (profiles/mla_decode_gpu.log,
+// DESIGN.md section 35) shows what the rule costs.
+struct MlaCall {
+    const void* Q;
+    const void* KV;
+    void* O;
+    float* LSE;
+    const int32_t* kv_lens;
+    void* workspace;
+    int B, H, Sq, capacity, d_latent, d_rope;
+    float scale;
+    bool is_causal;
+    int dtype, o_dtype, num_splits;
+    const fa_strides *sQ, *sKV, *sO;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+static DecodeRoute mla_route(const MlaCall& c) {
+    DecodeRoute r{};
+    const int64_t rows = (int64_t)c.H * c.Sq;
+    r.row_blocks = (int)std::min<int64_t>((rows + MlaCfg::ROWS - 1) / MlaCfg::ROWS, INT32_MAX);
+    r.tiles = (c.capacity + MlaCfg::KT - 1) / MlaCfg::KT;
+    const int64_t units = (int64_t)c.B * r.row_blocks;
+    if (c.num_splits > 0) r.ns = c.num_splits;
+    else {
+        const int64_t want = ((int64_t)device_cus() + units - 1) / units;   // (wgs_per_cu = 1)
+        r.ns = (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)r.tiles / EXTEND_MIN_TILES, (int64_t)FA_DECODE_MAX_SPLITS}));
+    }
+    r.grid = units * r.ns;
+    return r;
+}
+
+// the shape of a call or a plan, in decode_check_shape's order
+static int mla_check_shape(const MlaCall& c) {
+    const int B = c.B, H = c.H, Sq = c.Sq, Sk = c.capacity;
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || c.d_latent <= 0 || c.d_rope <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.num_splits < 0 || c.num_splits > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_output_dtype(c.o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.d_latent != MlaCfg::DL || c.d_rope != MlaCfg::DR) return FA_ERR_UNSUPPORTED_DHEAD;
+    const DecodeRoute r = mla_route(c);
+    if (r.grid > INT32_MAX || r.row_blocks == INT32_MAX) return FA_ERR_BAD_SHAPE;
+    const int64_t rows = (int64_t)B * H * Sq;
+    if (r.grid >= FA_DECODE_MAX_WORKGROUPS || (r.ns > 1 && rows >= FA_DECODE_MAX_WORKGROUPS)) return FA_ERR_BAD_SHAPE;
+    return FA_OK;
+}
+
+// one validation, in decode_run's order, and the launches: the MLA kernel and, under more than one split, the combine at D = 512
+static int mla_run(MlaCall c) {
+    const DecodePaging* pg = c.paging;
+    constexpr int D = MlaCfg::D, DL = MlaCfg::DL;
+    if (!c.Q || !c.KV || !c.O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Q) || !aligned16(c.KV) || !aligned16(c.O) || !aligned16(c.LSE) || !aligned16(c.workspace)) return FA_ERR_MISALIGNED;
+    fa_strides tKV{};   // the cache's strides without the head stride, which no MLA call reads
+    if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
+    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .kv_dtype = FA_DTYPE_BF16, .capacity = c.capacity,
+                  .sK = c.sKV ? &tKV : nullptr, .sV = c.sKV ? &tKV : nullptr, .paging = pg};
+    int rc = cache_check_arrays(cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    c.capacity = cache.capacity;
+    if ((rc = mla_check_shape(c)) != FA_OK) return rc;
+    if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
+    if (!strides_ok(c.sQ, 2, D) || !cache_strides_ok(cache, D) || !strides_ok(c.sO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;
+    const DecodeRoute r = mla_route(c);
+    if (r.ns > 1 && !c.workspace) return FA_ERR_NULL_POINTER;
+    const int64_t rows = (int64_t)c.B * c.H * c.Sq;
+    if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    DecodeParams p{};
+    p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.KV; p.V = (const __bf16*)c.KV; p.O = c.O; p.lse = c.LSE;
+    p.kv_lens = c.kv_lens;
+    p.part_o = (float*)c.workspace;
+    p.part_lse = r.ns > 1 ? (float*)((char*)c.workspace + round16((size_t)rows * r.ns * DL * sizeof(float))) : nullptr;
+    resolve_strides(c.sQ, c.H, c.Sq, D, p.qB, p.qH, p.qS);
+    resolve_strides(cache.sK, 1, cache_rows(cache), D, p.kB, p.kH, p.kS);
+    p.vB = p.kB; p.vH = p.kH; p.vS = p.kS;
+    resolve_strides(c.sO, c.H, c.Sq, DL, p.oB, p.oH, p.oS);
+    p.H = c.H; p.Hkv = 1; p.G = c.H; p.Sq = c.Sq; p.Sk = cache.capacity;
+    p.row_blocks = r.row_blocks; p.ns = r.ns;
+    p.rows = (int)rows;
+    p.o_dtype = c.o_dtype;
+    p.causal = c.is_causal;
+    p.scale_log2 = c.scale * 1.4426950408889634f;
+    p.block_table = pg ? pg->table : nullptr;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    rc = mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
+    if (rc != FA_OK || r.ns == 1) return rc;
+    return mla_combine_launch((unsigned)rows, st, p);
+}
 }  // namespace fa
 
 extern "C" {
@@ -1691,6 +1794,51 @@ int flash_attention_cascade_decode_paged(const void* Q, const void* Kpool, const
          .shared = {.K = Kpool, .V = Vpool, .kv_lens = sharedLen, .k_descale = kDescale, .v_descale = vDescale, .kv_dtype = kv_dtype,
                     .sK = sK, .sV = sV, .paging = &spg},
          .num_splits_shared = numSplitsShared});
+}
+
+// ---- MLA decode ----
+int flash_attention_mla_decode_plan(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope, int o_dtype,
+                                    int numSplits, fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const MlaCall c{.B = batchSize, .H = numHeads, .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope,
+                    .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits};
+    const int rc = mla_check_shape(c);
+    if (rc != FA_OK) return rc;
+    const DecodeRoute r = mla_route(c);
+    plan->num_splits = r.ns;
+    plan->row_blocks = r.row_blocks;
+    plan->rows_per_block = MlaCfg::ROWS;
+    plan->kv_block_rows = MlaCfg::KT;
+    plan->threads = MlaCfg::THREADS;
+    plan->grid = (int)r.grid;
+    plan->lds_bytes = MlaCfg::LDS_BYTES;
+    plan->combine_grid = r.ns > 1 ? (int)((int64_t)batchSize * numHeads * seqLenQ) : 0;   // one workgroup per (batch, head, query row)
+    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    return FA_OK;
+}
+
+size_t flash_attention_mla_decode_workspace_size(int batchSize, int numHeads, int seqLenQ, int dLatent, int numSplits) {
+    return flash_attention_decode_workspace_size(batchSize, numHeads, seqLenQ, dLatent, numSplits);
+}
+
+int flash_attention_mla_decode(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, void* workspace, int batchSize,
+                               int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope, float scale, bool is_causal, int dtype,
+                               int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream});
+}
+
+int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                     const int32_t* blockTable, void* workspace, int batchSize, int numHeads, int seqLenQ, int numPages,
+                                     int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope, float scale,
+                                     bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sKV,
+                                     const fa_strides* sO, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream});
 }
 
 const char* flash_attention_error_string(int code) {

@@ -1260,6 +1260,58 @@ int flash_attention_kv_accept_paged(void* Kpool, void* Vpool, const int32_t* kvL
                                     int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dHead, int kv_dtype,
                                     const fa_strides* sK, const fa_strides* sV, void* stream);
 
+/*
+ * flash_attention_mla_decode -- decode for multi-head latent attention (MLA: DeepSeek-V2 / V3 / R1, Kimi-K2) in its ABSORBED form: every
+ * query head attends ONE shared cache row per token, dLatent = 512 latent columns followed by dRope = 64 rotary columns.  The score
+ * uses all 576 columns, the value is the first 512 columns of the same row:
+ *     O = softmax(scale * Q KV^T) * KV[:, :512]
+ * The cache is fetched once per 64 packed (head, query row) rows and serves both products.
+ *   Q        [batchSize, numHeads, seqLenQ, 576] bf16: the absorbed q_nope * W_UK in columns [0, 512), the rotated q_rope in [512, 576)
+ *   KV       [batchSize, seqLenK, 576] bf16, seqLenK the CAPACITY.  sKV: strideB the batch stride, strideS the row stride; strideH is
+ *            not read.  NULL = dense
+ *   O        [batchSize, numHeads, seqLenQ, 512] in o_dtype;  LSE optional fp32 [batchSize, numHeads, seqLenQ], natural log
+ *   scale    the caller's: a model passes mscale^2 / sqrt(192), its softmax scale before the absorption.  Finite and positive
+ *   dLatent, dRope  only (512, 64); anything else FA_ERR_UNSUPPORTED_DHEAD
+ * Everything else is flash_attention_decode's contract, word for word: 1 <= seqLenQ <= FA_DECODE_MAX_Q; kvLens (DEVICE int32, 4-byte
+ * aligned, optional) is read by the kernel and clamped into [1, capacity], NULL = the capacity; is_causal is bottom-right aligned (row i
+ * sees k <= len - seqLenQ + i, and at least key 0); rows at and beyond the length may hold NaN or inf; numSplits 0 = chosen on the host
+ * from shapes only, 1 .. FA_DECODE_MAX_SPLITS forced; the workspace (flash_attention_mla_decode_workspace_size bytes, 16-byte aligned,
+ * contents undefined before and after) may be NULL only under one split; slabs are combined in a fixed order, so results are the same
+ * bits run to run; BF16 and F16 outputs are the F32 result rounded once; scores and softmax are fp32 and the weights enter the P.V
+ * product as a bf16 hi + lo pair, so 1e-3 + 1e-3 |ref| holds for caches of a handful of keys.  Arguments are validated before any
+ * launch, in flash_attention_decode's order and with its codes; the call allocates nothing, never synchronises the host, prints
+ * nothing and can be captured into a graph.
+ *
+ * flash_attention_mla_decode_paged -- the same against a pool of pages: KVpool [numPages, pageSize, 576] bf16 (sKV: strideB the PAGE
+ * stride, strideS the row stride), blockTable / tableStride / numPages / pageSize / maxPagesPerSeq as in flash_attention_decode_paged:
+ * pages are a power of two >= 16, the pool may exceed 2^32 bytes, table entries are read and clamped by the kernel, pages no visible
+ * key lies in are not read and their entries may hold anything.  Equal, bit for bit, to the contiguous call on a gathered copy with
+ * the same split count.
+ *
+ * flash_attention_mla_decode_plan -- fa_decode_plan of such a call: rows_per_block = 64, row_blocks = ceil(numHeads * seqLenQ / 64),
+ * grid = batchSize * row_blocks * num_splits, kv_block_rows / lds_bytes / threads of the MLA kernel.  The split rule (enough units for
+ * one workgroup per CU, no split shorter than two key tiles of the capacity) is NOT measured.  The grid and row limits of
+ * FA_DECODE_MAX_WORKGROUPS apply.  flash_attention_mla_decode_workspace_size = flash_attention_decode_workspace_size at dHead = 512.
+ *
+ * Not done: fp8 latent caches, a latent-cache append, windows, sinks, tree masks, ragged calls and chunked prefill, cascade, other
+ * latent widths, a 128-row block that reads the cache once at numHeads = 128, a single-weights flag.
+ */
+int    flash_attention_mla_decode_plan(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                       int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
+size_t flash_attention_mla_decode_workspace_size(int batchSize, int numHeads, int seqLenQ, int dLatent, int numSplits /* as planned */);
+
+int flash_attention_mla_decode(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, void* workspace,
+                               int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                               float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                               const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                     const int32_t* blockTable, void* workspace,
+                                     int batchSize, int numHeads, int seqLenQ,
+                                     int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                     int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                                     const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
 
