@@ -42,6 +42,10 @@ build/obj/inst_bf16_pair_d128.o: HIPFLAGS += $(MFMA_VGPR)
 build/obj/inst_bwd_bf16.o: HIPFLAGS += $(MFMA_VGPR)
 # the MLA decode kernel (mla_decode.hip.h) likewise: 128 accumulator registers of O^T that the VALU rescales at every key tile
 build/obj/inst_mla_decode.o: HIPFLAGS += $(MFMA_VGPR)
+# the MLA prefill kernel (fwd_mla.hip.h) likewise: 128 accumulator registers of O^T per wave, rescaled at every key tile, beside 96 of
+# Q^T and 64 of scores; and no packed fp32 arithmetic in its softmax (the flag after it)
+NO_PK_F32 := -Xclang -target-feature -Xclang -packed-fp32-ops
+build/obj/inst_bf16_mla.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS, and the shared_* ones, which are built at the same RT; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
 # tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
@@ -115,8 +119,9 @@ SANFLAGS  := -fsanitize=address,undefined -fno-omit-frame-pointer -g
 # points, of the six attention-sink entry points beside their _window twins, of the four rope_append ones beside their kv_append twins,
 # of the two tree-masked ones beside their sink twins, of the speculative step's rope_append_pos and kv_accept ones beside their rope_append
 # and kv_append twins, of the two shared-prefix decode ones and their plan beside flash_attention_decode_window / _paged_window, of the two MLA decode ones and
-# their plan beside flash_attention_decode / _paged
-LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder host_cascade_ladder host_mla_ladder
+# their plan beside flash_attention_decode / _paged, of the MLA prefill one and its plan beside flash_attention_ex
+LADDERS := host_ladder host_sink_ladder host_rope_ladder host_tree_ladder host_spec_ladder host_cascade_ladder host_mla_ladder \
+           host_mla_prefill_ladder
 $(ASAN_DIR)/libflash_attention.so: $(LIB)
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(SANFLAGS) -fno-gpu-sanitize -shared-libsan -c -o $(ASAN_DIR)/FlashAttention.o $(PKG)/csrc/FlashAttention.hip
@@ -143,6 +148,7 @@ asan: asan-host oracle
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
 build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s: HIPFLAGS += $(MFMA_VGPR)
+build/asm/inst_bf16_mla.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 define ASM_RECIPE
 @mkdir -p build/asm
 $(HIPCC) $(HIPFLAGS) $(1) -S --cuda-device-only -o $@.tmp $<

@@ -89,6 +89,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_cascade_decode", "flash_attention_cascade_decode_paged", "flash_attention_cascade_plan",
            "flash_attention_mla_decode", "flash_attention_mla_decode_paged", "flash_attention_mla_decode_plan",
            "flash_attention_mla_decode_workspace_size",
+           "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -259,6 +260,11 @@ def lib() -> ctypes.CDLL:
         L.flash_attention_mla_decode_plan.restype = i
         L.flash_attention_mla_decode_workspace_size.argtypes = [i, i, i, i, i]
         L.flash_attention_mla_decode_workspace_size.restype = ctypes.c_size_t
+        # MLA prefill: flash_attention_ex's signature with (dQK, dV) where dHead stands and no input dtype
+        L.flash_attention_mla_prefill.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, f, b, i, sp, sp, sp, sp, ctypes.c_uint, vp]
+        L.flash_attention_mla_prefill.restype = i
+        L.flash_attention_mla_prefill_plan.argtypes = [i, i, i, i, i, i, b, i, ctypes.c_uint, ctypes.POINTER(FaLaunchPlan)]
+        L.flash_attention_mla_prefill_plan.restype = i
         for by_window in _PLAN_SYMBOLS.values():
             for window, name in enumerate(by_window):
                 fn = getattr(L, name)
@@ -1103,6 +1109,61 @@ def flash_attention_mla_decode_paged(Q, KV_pool, block_table, kv_lens=None, scal
     kernel, pages no visible key lies in are not read.  ``scale`` None = ``576 ** -0.5``.  The result is the contiguous call's on a
     gathered copy under the same ``num_splits``, bit for bit."""
     return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream)
+
+
+def mla_prefill_plan(B, H, Sq, Sk, is_causal=False, o_dtype=FA_DTYPE_BF16, flags=0, d_qk=192, d_v=128):
+    """The launch a flash_attention_mla_prefill() call makes (kernel_id 4)."""
+    p = FaLaunchPlan()
+    _check(lib().flash_attention_mla_prefill_plan(B, H, Sq, Sk, d_qk, d_v, bool(is_causal), o_dtype, flags, ctypes.byref(p)))
+    return {k: getattr(p, k) for k, _ in FaLaunchPlan._fields_}
+
+
+def flash_attention_mla_prefill(Q, K, V, O=None, scale=None, is_causal=False, out_dtype=None, return_lse=False, weights_dtype=None,
+                                stream=None):
+    """MLA prefill: O = softmax(scale * Q K^T [+ causal mask]) V with bf16 Q [B, H, Sq, 192], K [B, H, Sk, 192], V [B, H, Sk, 128].
+
+    The up-projected form of multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2): 128 "nope" + 64 rotary score columns, 128
+    value columns; O is [B, H, Sq, 128].  ``scale`` defaults to ``192 ** -0.5`` (a model with YaRN passes its own).  The mask is
+    flash_attention's: key k is hidden from row q when ``k > q``.  Any last-dimension-contiguous views are taken as they are (the
+    ``[B, S, H * d]`` model layout through ``.view(B, S, H, d).transpose(1, 2)``).  ``weights_dtype``: None = the rows that see fewer
+    than FA_EARLY_KEYS keys get their softmax weights as a bf16 hi + lo pair, the rest single bf16; ``torch.bfloat16`` =
+    FA_FLAG_BF16_WEIGHTS, single bf16 on every row; ``torch.float16`` is refused (there is no fp16 form).  Returns O, or ``(O, LSE)``
+    with ``return_lse=True``.  Asynchronous on ``stream`` (default: torch's current stream).
+    """
+    import torch
+    if not (Q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError("flash_attention_mla_prefill needs device tensors (no CPU fallback)")
+    if Q.dim() != 4 or K.dim() != 4 or V.dim() != 4 or Q.shape[:2] != K.shape[:2] or K.shape[:3] != V.shape[:3] \
+            or Q.shape[3] != K.shape[3]:
+        raise ValueError("Q must be [B, H, Sq, 192], K [B, H, Sk, 192] and V [B, H, Sk, 128]")
+    if not (Q.dtype == K.dtype == V.dtype == torch.bfloat16):
+        raise TypeError("Q, K, V must be bfloat16")
+    B, H, Sq, d_qk = Q.shape
+    Sk, d_v = V.shape[2:4]
+    if scale is None:
+        scale = float(d_qk) ** -0.5
+    if O is None:
+        O = torch.empty((B, H, Sq, d_v), dtype=out_dtype or torch.bfloat16, device=Q.device)
+    elif tuple(O.shape) != (B, H, Sq, d_v) or not O.is_cuda:
+        raise ValueError("O must be a device tensor of shape [B, H, Sq, 128]")
+    flags = 0
+    if weights_dtype is not None:
+        if weights_dtype == torch.bfloat16:
+            flags = FA_FLAG_BF16_WEIGHTS
+        elif weights_dtype == torch.float16:
+            flags = FA_FLAG_F16_WEIGHTS   # (the library refuses it: FA_ERR_BAD_FLAGS)
+        else:
+            raise TypeError("weights_dtype must be torch.bfloat16 or None")
+    if any(t.stride(3) != 1 for t in (Q, K, V, O)):
+        raise ValueError("the last dimension of Q, K, V and O must be contiguous")
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=Q.device) if return_lse else None
+    refs = [ctypes.byref(_strides(t)) for t in (Q, K, V, O)]
+    with torch.cuda.device(Q.device):
+        rc = lib().flash_attention_mla_prefill(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(),
+                                               lse.data_ptr() if lse is not None else None, B, H, Sq, Sk, d_qk, d_v, float(scale),
+                                               bool(is_causal), _dtype_code(O.dtype), *refs, flags, _stream_ptr(stream))
+    _check(rc)
+    return (O, lse) if return_lse else O
 
 
 def _tree_parents(parents):

@@ -25,6 +25,7 @@
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
 #include "mla_decode.hip.h"
+#include "fwd_mla.hip.h"
 
 namespace fa {
 
@@ -983,6 +984,91 @@ static int mla_run(MlaCall c) {
     if (rc != FA_OK || r.ns == 1) return rc;
     return mla_combine_launch((unsigned)rows, st, p);
 }
+
+// ---- MLA prefill (fwd_mla.hip.h): bf16 Q, K [.., 192] and V, O [.., 128] ----
+struct MlaPrefillCall {
+    const void *Q, *K, *V;
+    void* O;
+    float* LSE;
+    int B, H, Sq, Sk, d_qk, d_v;
+    float scale;
+    bool is_causal;
+    int o_dtype;
+    const fa_strides *sQ, *sK, *sV, *sO;
+    unsigned flags;
+    void* stream;
+};
+
+// The launch decision: ONE kernel over all 256-row query blocks of every head, one workgroup per unit.  hp: the leading query blocks
+// of every head whose FIRST row can see fewer than FA_EARLY_KEYS keys -- all when seqLenK is below it; under the mask the blocks with
+// 256 qb + 1 < FA_EARLY_KEYS -- take the bf16 hi + lo weight pair (more rows than the rule names where a block straddles it, never
+// fewer); none with FA_FLAG_BF16_WEIGHTS.
+struct MlaPrefillRoute {
+    int nQ, hp;
+    int64_t units, cpx;
+    int grid;
+};
+static MlaPrefillRoute mla_prefill_route(int B, int H, int Sq, int Sk, bool causal, unsigned flags) {
+    using C = MlaPrefillCfg;
+    MlaPrefillRoute r{};
+    r.nQ = getNumCta(Sq, C::ROWS);
+    r.hp = (flags & FA_FLAG_BF16_WEIGHTS) ? 0
+           : Sk < FA_EARLY_KEYS           ? r.nQ
+           : causal                       ? std::min(r.nQ, (FA_EARLY_KEYS - 1 + C::ROWS - 1) / C::ROWS)
+                                          : 0;
+    r.units = (int64_t)B * H * r.nQ;
+    r.cpx = (r.units + 7) / 8;
+    r.grid = (int)(8 * r.cpx);
+    return r;
+}
+
+// What the call and its plan check alike, in flash_attention_cross's order: shapes, the output type, the widths, the flags
+static int mla_prefill_check_shape(int B, int H, int Sq, int Sk, int d_qk, int d_v, int o_dtype, unsigned flags, bool scale_ok) {
+    if (B <= 0 || H <= 0 || Sq <= 0 || d_qk <= 0 || d_v <= 0) return FA_ERR_BAD_SHAPE;
+    if ((int64_t)B * H > INT32_MAX / 2 || Sq > (1 << 24)) return FA_ERR_BAD_SHAPE;
+    if (!scale_ok) return FA_ERR_BAD_SCALE;
+    if (!is_output_dtype(o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (d_qk != MlaPrefillCfg::DQK || d_v != MlaPrefillCfg::DV) return FA_ERR_UNSUPPORTED_DHEAD;
+    // (there is no fp16 form: the early rows' precision comes from the bf16 pair)
+    if (flags & ~(unsigned)FA_FLAG_BF16_WEIGHTS) return FA_ERR_BAD_FLAGS;
+    if (Sk <= 0 || Sk > (1 << 24)) return FA_ERR_BAD_SHAPE;
+    return FA_OK;
+}
+
+static int mla_prefill_run(const MlaPrefillCall& c) {
+    using C = MlaPrefillCfg;
+    if (!c.Q || !c.K || !c.V || !c.O) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Q) || !aligned16(c.K) || !aligned16(c.V) || !aligned16(c.O)) return FA_ERR_MISALIGNED;
+    int rc = mla_prefill_check_shape(c.B, c.H, c.Sq, c.Sk, c.d_qk, c.d_v, c.o_dtype, c.flags, std::isfinite(c.scale));
+    if (rc != FA_OK) return rc;
+    if (c.LSE && !aligned16(c.LSE)) return FA_ERR_MISALIGNED;
+    const int osz = elem_size(c.o_dtype);
+    if (!strides_ok(c.sQ, 2, C::DQK) || !strides_ok(c.sK, 2, C::DQK) || !strides_ok(c.sV, 2, C::DV) || !strides_ok(c.sO, osz, C::DV))
+        return FA_ERR_BAD_STRIDE;
+    // one head's K / V extent, with the slack of the last tile's rows, stays below the descriptors' 2^31 bytes
+    const int64_t rows = (int64_t)c.Sk + KV_EXTENT_SLACK;
+    if (!kv_extent_ok(rows, c.sK ? c.sK->strideS : C::DQK, 2) || !kv_extent_ok(rows, c.sV ? c.sV->strideS : C::DV, 2)) return FA_ERR_BAD_SHAPE;
+    const MlaPrefillRoute r = mla_prefill_route(c.B, c.H, c.Sq, c.Sk, c.is_causal, c.flags);
+    if (r.units > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;   // unit indices are 32-bit
+    Params p;
+    p.Q = c.Q; p.K = c.K; p.V = c.V; p.O = c.O; p.lse = c.LSE;
+    resolve_strides(c.sQ, c.H, c.Sq, C::DQK, p.qB, p.qH, p.qS);
+    resolve_strides(c.sK, c.H, c.Sk, C::DQK, p.kB, p.kH, p.kS);
+    resolve_strides(c.sV, c.H, c.Sk, C::DV, p.vB, p.vH, p.vS);
+    resolve_strides(c.sO, c.H, c.Sq, C::DV, p.oB, p.oH, p.oS);
+    p.B = c.B; p.H = c.H; p.S = c.Sq; p.Sk = c.Sk; p.d = C::DQK;
+    p.scale = c.scale;
+    p.scale_log2 = c.scale * 1.4426950408889634f;
+    p.dbg = nullptr;
+    p.qb0 = 0;
+    p.nQ = r.nQ;
+    p.units = (int)r.units;
+    p.cpx = (int)r.cpx;
+    p.jpx = r.grid / 8;
+    p.hp = r.hp;
+    return (int)launch(mla_prefill_kernel(c.is_causal, c.o_dtype), (unsigned)r.grid, C::THREADS, C::LDS_BYTES,
+                       reinterpret_cast<hipStream_t>(c.stream), p);
+}
 }  // namespace fa
 
 extern "C" {
@@ -1839,6 +1925,27 @@ int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O,
     return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
                         .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
                         .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream});
+}
+
+// ---- MLA prefill ----
+int flash_attention_mla_prefill_plan(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dQK, int dV, bool is_causal, int o_dtype,
+                                     unsigned flags, fa_launch_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    const int rc = mla_prefill_check_shape(batchSize, numHeads, seqLenQ, seqLenK, dQK, dV, o_dtype, flags, true);
+    if (rc != FA_OK) return rc;
+    const MlaPrefillRoute r = mla_prefill_route(batchSize, numHeads, seqLenQ, seqLenK, is_causal, flags);
+    if (r.units > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    *plan = fa_launch_plan{MlaPrefillCfg::ROWS, MlaPrefillCfg::KT, MlaPrefillCfg::THREADS, r.grid, MlaPrefillCfg::LDS_BYTES, 4};
+    return FA_OK;
+}
+
+int flash_attention_mla_prefill(const void* Q, const void* K, const void* V, void* O, float* LSE, int batchSize, int numHeads, int seqLenQ,
+                                int seqLenK, int dQK, int dV, float scale, bool is_causal, int o_dtype, const fa_strides* sQ,
+                                const fa_strides* sK, const fa_strides* sV, const fa_strides* sO, unsigned flags, void* stream) {
+    return fa::mla_prefill_run({.Q = Q, .K = K, .V = V, .O = O, .LSE = LSE, .B = batchSize, .H = numHeads, .Sq = seqLenQ, .Sk = seqLenK,
+                                .d_qk = dQK, .d_v = dV, .scale = scale, .is_causal = is_causal, .o_dtype = o_dtype, .sQ = sQ, .sK = sK,
+                                .sV = sV, .sO = sO, .flags = flags, .stream = stream});
 }
 
 const char* flash_attention_error_string(int code) {

@@ -81,5 +81,8 @@ Kernel f32_d64_kernel(bool causal, bool pad, int o_dtype);
 // workgroups per CU, paired; else one per CU (inst_bf16_pair_d64.hip, inst_bf16_pair_d128.hip)
 Kernel bf16_pair_d64_kernel(bool causal, int o_dtype);
 Kernel bf16_pair_d128_kernel(bool causal, int o_dtype);
+// Kernel taking (Params): bf16 inputs with 192 score and 128 value columns, 256-row units, one per workgroup of four waves; the units
+// of the first Params::hp query blocks of every head run with bf16 hi + lo weights, the rest with single bf16 (inst_bf16_mla.hip)
+Kernel mla_prefill_kernel(bool causal, int o_dtype);
 
 }  // namespace fa

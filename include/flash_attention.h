@@ -274,7 +274,8 @@ typedef struct fa_launch_plan {
     int threads;         /* threads per workgroup                  (tests/main.cu:52)  */
     int grid;            /* number of workgroups                   (helpers.hpp:33-36) */
     int lds_bytes;       /* dynamic LDS per workgroup              (tests/main.cu:55)  */
-    int kernel_id;       /* which internal kernel: 0 generic fp32 VALU, 1 bf16 MFMA, 2 fp8 MFMA, 3 exact-fp32 MFMA */
+    int kernel_id;       /* which internal kernel: 0 generic fp32 VALU, 1 bf16 MFMA, 2 fp8 MFMA, 3 exact-fp32 MFMA,
+                            4 the MLA prefill kernel (flash_attention_mla_prefill_plan) */
 } fa_launch_plan;
 
 int flash_attention_plan(int batchSize, int numHeads, int seqLen, int dHead, bool is_causal,
@@ -1311,6 +1312,35 @@ int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O,
                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
                                      int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
                                      const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+/*
+ * flash_attention_mla_prefill -- the forward pass of multi-head latent attention in its UP-PROJECTED (prefill) form: ordinary multi-head
+ * attention whose score and value widths differ,
+ *     O = softmax(scale Q K^T [+ mask]) V,   Q [B, H, Sq, 192], K [B, H, Sk, 192], V [B, H, Sk, 128], O [B, H, Sq, 128]
+ * (192 = 128 "nope" + 64 rotary columns, concatenated by the caller).  bf16 Q, K, V; O in fp32, bf16 or fp16; LSE fp32 [B, H, Sq] or
+ * NULL, natural log, as in flash_attention_lse.  The contract is flash_attention_cross's: is_causal hides key k from row q when k > q on
+ * absolute indices (the prompt from position 0 when seqLenQ = seqLenK; a chunk behind a cached context is a non-causal call on the
+ * context and a causal call on the chunk, merged by the caller through the two LSEs); strides in elements, last dimension contiguous,
+ * NULL = dense (sV and sO describe 128-wide rows); validation before any launch, in flash_attention_cross's order and codes: NULL
+ * pointers, alignment, shapes, scale, o_dtype, the widths -- only (dQK, dV) = (192, 128), anything else FA_ERR_UNSUPPORTED_DHEAD --
+ * flags, seqLenK, the LSE's alignment, strides, one head's K / V extent below 2^31 bytes.  No allocation, no workspace, no
+ * synchronisation; graph-capturable; any seqLenQ, seqLenK >= 1.
+ * Softmax weights: the rows that can see fewer than FA_EARLY_KEYS keys (and the other rows of their 256-row block) are fed to the P.V
+ * product as a bf16 hi + lo pair, every other row as single bf16; flags = FA_FLAG_BF16_WEIGHTS: single bf16 on every row;
+ * FA_FLAG_F16_WEIGHTS: FA_ERR_BAD_FLAGS (there is no fp16 form).  The normaliser and the LSE are the fp32 sum of the unrounded weights.
+ * flash_attention_mla_prefill_plan -- the launch of such a call: q_block_rows = 256, kv_block_rows = 64, threads = 256, one workgroup
+ * per (batch, head, query block) rounded up to a multiple of 8, lds_bytes = 92160, kernel_id = 4.
+ * Not done: a backward pass, grouped K/V heads, a separate rope tensor (K must be concatenated), a bottom-right mask, an fp8 form, an
+ * LSE merge call.
+ */
+int flash_attention_mla_prefill_plan(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dQK, int dV,
+                                     bool is_causal, int o_dtype, unsigned flags, fa_launch_plan* plan);
+
+int flash_attention_mla_prefill(const void* Q, const void* K, const void* V, void* O, float* LSE,
+                                int batchSize, int numHeads, int seqLenQ, int seqLenK, int dQK, int dV,
+                                float scale, bool is_causal, int o_dtype,
+                                const fa_strides* sQ, const fa_strides* sK, const fa_strides* sV, const fa_strides* sO,
+                                unsigned flags, void* stream);
 
 /* Human-readable text for a return code of the functions above (static storage). */
 const char* flash_attention_error_string(int code);
