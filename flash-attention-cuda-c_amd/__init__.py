@@ -89,6 +89,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_cascade_decode", "flash_attention_cascade_decode_paged", "flash_attention_cascade_plan",
            "flash_attention_mla_decode", "flash_attention_mla_decode_paged", "flash_attention_mla_decode_plan",
            "flash_attention_mla_decode_workspace_size",
+           "flash_attention_mla_decode_fp8", "flash_attention_mla_decode_paged_fp8",
+           "flash_attention_mla_append", "flash_attention_mla_append_paged",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
@@ -125,6 +127,11 @@ _ACCEPT_SYMBOLS = {False: "flash_attention_kv_accept", True: "flash_attention_kv
 # ... shared-prefix decode: _CASCADE_SYMBOLS[paged], the ``_window`` entry point of decode with the shared cache, sharedLen, the shared
 # table and sinks in, two split counts, and no window
 _CASCADE_SYMBOLS = {False: "flash_attention_cascade_decode", True: "flash_attention_cascade_decode_paged"}
+# ... MLA decode: _MLA_SYMBOLS[paged], and _MLA_FP8_SYMBOLS[paged]: the ``_fp8`` twin with ``kvDescale`` and ``kv_dtype``; the
+# latent-cache append: _MLA_APPEND_SYMBOLS[paged]
+_MLA_SYMBOLS = {False: "flash_attention_mla_decode", True: "flash_attention_mla_decode_paged"}
+_MLA_FP8_SYMBOLS = {False: "flash_attention_mla_decode_fp8", True: "flash_attention_mla_decode_paged_fp8"}
+_MLA_APPEND_SYMBOLS = {False: "flash_attention_mla_append", True: "flash_attention_mla_append_paged"}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -253,8 +260,16 @@ def lib() -> ctypes.CDLL:
         # the MLA pair: Q, the latent cache (paged: the pool), O, LSE, kvLens, the table (paged), the workspace; no K/V head count;
         # dLatent, dRope where dHead stands; three strides
         for paged in (False, True):
-            fn = getattr(L, "flash_attention_mla_decode_paged" if paged else "flash_attention_mla_decode")
+            fn = getattr(L, _MLA_SYMBOLS[paged])
             fn.argtypes = [vp] * 5 + [vp] * paged + [vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i] + [sp] * 3 + [vp]
+            fn.restype = i
+            # ... the fp8 twins: kvDescale before the workspace, kv_dtype after dtype
+            fn = getattr(L, _MLA_FP8_SYMBOLS[paged])
+            fn.argtypes = [vp] * 5 + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i, i] + [sp] * 3 + [vp]
+            fn.restype = i
+            # ... the latent-cache append: the two new tensors, the cache, kvLens, the table (paged), kvDescale
+            fn = getattr(L, _MLA_APPEND_SYMBOLS[paged])
+            fn.argtypes = [vp] * 4 + [vp] * paged + [vp] + [i] * 2 + paging(paged) + [i] * 4 + [sp] * 3 + [vp]
             fn.restype = i
         L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_mla_decode_plan.restype = i
@@ -1029,7 +1044,6 @@ def flash_attention_cascade_decode_paged(Q, K_pool, V_pool, shared_table, block_
 
 # ---- MLA decode: one latent cache read as K (576 columns) and as V (the first 512) ----
 MLA_D_LATENT, MLA_D_ROPE = 512, 64
-_MLA_SYMBOLS = {False: "flash_attention_mla_decode", True: "flash_attention_mla_decode_paged"}
 
 
 def mla_decode_plan(B, H, Sq, Sk, o_dtype=FA_DTYPE_BF16, num_splits=0):
@@ -1041,19 +1055,35 @@ def mla_decode_plan(B, H, Sq, Sk, o_dtype=FA_DTYPE_BF16, num_splits=0):
     return _plan_dict(p)
 
 
-def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream):
+def _mla_descale(kv_descale, fp8, device):
+    """the check both MLA fronts and both append fronts make of ``kv_descale``: one fp32 on the device, and only with an fp8 cache"""
+    import torch
+    t = kv_descale
+    if t is None:
+        return
+    if not fp8:
+        raise ValueError("kv_descale belongs to an fp8 (float8_e4m3fn) latent cache under bf16 rows")
+    if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != device or tuple(t.shape) not in ((1,), ()):
+        raise ValueError("kv_descale must be an fp32 tensor of one element on the device of the cache")
+
+
+def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale=None):
     """Both MLA fronts: the checks of the tensors (with the decode fronts' helpers for the table, the lengths and the workspace), the plan
-    and the workspace for the capacity, then the entry point of _MLA_SYMBOLS."""
+    and the workspace for the capacity, then the entry point of _MLA_SYMBOLS -- or, for a float8_e4m3fn cache under a bf16 Q, of
+    _MLA_FP8_SYMBOLS, which takes ``kv_descale`` and the cache's dtype code."""
     import torch
     paged = block_table is not None
-    name = _MLA_SYMBOLS[paged]
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    fp8 = f8 is not None and getattr(KV, "dtype", None) == f8 and Q.dtype == torch.bfloat16
+    name = (_MLA_FP8_SYMBOLS if fp8 else _MLA_SYMBOLS)[paged]
     if not (Q.is_cuda and KV.is_cuda and (not paged or block_table.is_cuda)):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
     D = MLA_D_LATENT + MLA_D_ROPE
     if Q.dim() != 4 or KV.dim() != 3 or (not paged and Q.shape[0] != KV.shape[0]) or Q.shape[3] != D or KV.shape[2] != D:
         raise ValueError(f"Q must be [B, H, Sq, {D}] and {'KV_pool [P, page' if paged else 'KV [B, capacity'}, {D}]")
-    if Q.dtype != KV.dtype:
+    if not fp8 and Q.dtype != KV.dtype:
         raise TypeError("Q, KV must share a dtype")
+    _mla_descale(kv_descale, fp8, Q.device)
     if KV.stride(2) != 1:
         raise ValueError("last dimension must be contiguous")
     B, H, Sq, _ = Q.shape
@@ -1081,15 +1111,16 @@ def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_spl
         sKV = FaStrides(KV.stride(0), 0, KV.stride(1))
         ptr = lambda t: t.data_ptr() if t is not None else None
         rc = getattr(lib(), name)(Q.data_ptr(), KV.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables),
-                                  workspace.data_ptr() if need else None, B, H, Sq, *geometry, MLA_D_LATENT, MLA_D_ROPE, float(scale),
-                                  bool(is_causal), _dtype_code(Q.dtype), _dtype_code(O.dtype), ns,
+                                  *((ptr(kv_descale),) if fp8 else ()), workspace.data_ptr() if need else None, B, H, Sq, *geometry,
+                                  MLA_D_LATENT, MLA_D_ROPE, float(scale), bool(is_causal), _dtype_code(Q.dtype),
+                                  *((_dtype_code(KV.dtype),) if fp8 else ()), _dtype_code(O.dtype), ns,
                                   ctypes.byref(sQ), ctypes.byref(sKV), ctypes.byref(sO), _stream_ptr(s))
     _check(rc)
     return (O, lse) if return_lse else O
 
 
 def flash_attention_mla_decode(Q, KV, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0, return_lse=False,
-                               O=None, workspace=None, stream=None):
+                               O=None, workspace=None, stream=None, kv_descale=None):
     """Decode for multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2) in its absorbed form: Q ``[B, H, Sq, 576]`` (bf16; the
     absorbed ``q_nope @ W_UK`` in columns [0, 512), the rotated ``q_rope`` in [512, 576)), 1 <= Sq <= FA_DECODE_MAX_Q, against ONE
     latent cache ``KV [B, capacity, 576]`` shared by all heads: ``O = softmax(scale * Q KV^T) KV[:, :512]``, ``[B, H, Sq, 512]``.
@@ -1098,17 +1129,81 @@ def flash_attention_mla_decode(Q, KV, kv_lens=None, scale=None, is_causal=False,
     ``mscale ** 2 / sqrt(192)`` -- the absorption does not change it.  ``kv_lens``, ``is_causal`` (bottom-right aligned),
     ``num_splits`` (0 = ``mla_decode_plan``'s choice), ``workspace`` (``decode_workspace_size(B, H, Sq, 512, ns)`` bytes), ``O``,
     ``return_lse`` and ``stream`` as for ``flash_attention_decode``; strided views are accepted (last dimension contiguous).
-    The cache row is fetched once per 64 packed rows and serves both products.  No CPU fallback."""
-    return _mla_front(Q, KV, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream)
+    The cache row is fetched once per 64 packed rows and serves both products.
+
+    fp8 cache: ``KV`` of ``torch.float8_e4m3fn`` under a bf16 Q, with ``kv_descale``, an fp32 device tensor of ONE element (None =
+    1) read by the kernel: the logical cache is ``KV.float() * kv_descale``, in the score and in the value columns alike -- half the
+    bytes per token.  The cache ``mla_cache_append`` writes.  No CPU fallback."""
+    return _mla_front(Q, KV, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale)
 
 
 def flash_attention_mla_decode_paged(Q, KV_pool, block_table, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
-                                     return_lse=False, O=None, workspace=None, stream=None):
+                                     return_lse=False, O=None, workspace=None, stream=None, kv_descale=None):
     """``flash_attention_mla_decode`` against a PAGED latent cache: ``KV_pool [P, page, 576]`` (page a power of two >= 16) and
     ``block_table`` int32 ``[B, max_pages]`` as in ``flash_attention_decode_paged``: entries and lengths are read and clamped by the
     kernel, pages no visible key lies in are not read.  ``scale`` None = ``576 ** -0.5``.  The result is the contiguous call's on a
-    gathered copy under the same ``num_splits``, bit for bit."""
-    return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream)
+    gathered copy under the same ``num_splits``, bit for bit.  A ``torch.float8_e4m3fn`` pool with ``kv_descale`` as for
+    ``flash_attention_mla_decode``."""
+    return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                      kv_descale)
+
+
+def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, stream):
+    """Both mla_cache_append fronts: the tensor checks, the bounds of Sq, and the entry point of _MLA_APPEND_SYMBOLS"""
+    import torch
+    paged = block_table is not None
+    layout = "KV_pool [P, page, 576]" if paged else "KV_cache [B, capacity, 576]"
+    if not (getattr(c_kv, "is_cuda", False) and getattr(k_pe, "is_cuda", False) and getattr(KV, "is_cuda", False)
+            and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    D = MLA_D_LATENT + MLA_D_ROPE
+    if c_kv.dim() != 3 or k_pe.dim() != 3 or KV.dim() != 3 or c_kv.shape[2] != MLA_D_LATENT or k_pe.shape[2] != MLA_D_ROPE \
+            or c_kv.shape[:2] != k_pe.shape[:2] or KV.shape[2] != D or (not paged and KV.shape[0] != c_kv.shape[0]):
+        raise ValueError(f"c_kv must be [B, Sq, {MLA_D_LATENT}], k_pe [B, Sq, {MLA_D_ROPE}] and {layout}")
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    fp8 = f8 is not None and KV.dtype == f8
+    if c_kv.dtype != torch.bfloat16 or k_pe.dtype != torch.bfloat16 or not (fp8 or KV.dtype == torch.bfloat16):
+        raise TypeError(f"c_kv, k_pe must be bfloat16 and {layout.split()[0]} bfloat16 or float8_e4m3fn")
+    if c_kv.device != KV.device or k_pe.device != KV.device:
+        raise ValueError("c_kv, k_pe and the cache must be on one device")
+    _mla_descale(kv_descale, fp8, KV.device)
+    if c_kv.stride(2) != 1 or k_pe.stride(2) != 1 or KV.stride(2) != 1:
+        raise ValueError("last dimension must be contiguous")
+    B, Sq, _ = c_kv.shape
+    capacity, tables, geometry = _cache_geometry(KV.unsqueeze(1), block_table, B)
+    if Sq < 1 or Sq > capacity:
+        raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
+    _check_kv_lens(kv_lens, B)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(KV.device):
+        st = [FaStrides(t.stride(0), 0, t.stride(1)) for t in (c_kv, k_pe, KV)]
+        rc = getattr(lib(), _MLA_APPEND_SYMBOLS[paged])(
+            c_kv.data_ptr(), k_pe.data_ptr(), KV.data_ptr(), ptr(kv_lens), *map(ptr, tables), ptr(kv_descale), B, Sq, *geometry,
+            MLA_D_LATENT, MLA_D_ROPE, _dtype_code(c_kv.dtype), _dtype_code(KV.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+    _check(rc)
+
+
+def mla_cache_append(c_kv, k_pe, KV_cache, kv_lens=None, kv_descale=None, stream=None):
+    """Write the new tokens of every sequence into the MLA latent cache ``flash_attention_mla_decode`` reads, in place.  Returns None.
+
+    ``c_kv`` bf16 ``[B, Sq, 512]`` (the compressed latent) and ``k_pe`` bf16 ``[B, Sq, 64]`` (the key's rotary part, already
+    rotated) become columns [0, 512) and [512, 576) of one cache row; strided views are accepted (last dimension contiguous), so
+    two slices of one projection pass without a copy.  ``KV_cache``: ``[B, capacity, 576]``, bf16 (a copy of bits) or
+    ``torch.float8_e4m3fn`` with ``kv_descale`` (an fp32 device tensor of ONE element, None = 1): the stored byte is the e4m3fn code
+    of ``clamp(x.float() / kv_descale, -448, 448)``, rounded to nearest even once; NaN stores a NaN code.  1 <= Sq <= capacity.
+
+    Positions as for ``kv_cache_append``: ``kv_lens[b]`` already counts the new rows, row i goes to ``min(kv_lens[b], capacity)
+    - Sq + i`` when that is >= 0, and ``kv_lens[b] <= 0`` writes nothing.  A decode step is ``kv_lens += Sq; mla_cache_append(...);
+    flash_attention_mla_decode(..., is_causal=True)``: lengths and the descale are read by the kernels, so the step is one graph.
+    Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
+    _mla_append_front("mla_cache_append", c_kv, k_pe, KV_cache, None, kv_lens, kv_descale, stream)
+
+
+def mla_cache_append_paged(c_kv, k_pe, KV_pool, block_table, kv_lens=None, kv_descale=None, stream=None):
+    """``mla_cache_append`` into a PAGED latent cache: ``KV_pool [P, page, 576]`` and ``block_table`` int32 ``[B, max_pages]`` as in
+    ``flash_attention_mla_decode_paged``.  Only the entries of pages that receive a row are read; an entry outside [0, P) is NOT
+    clamped: the rows that would go to that page are skipped and nothing else is touched.  Returns None."""
+    _mla_append_front("mla_cache_append_paged", c_kv, k_pe, KV_pool, block_table, kv_lens, kv_descale, stream)
 
 
 def mla_prefill_plan(B, H, Sq, Sk, is_causal=False, o_dtype=FA_DTYPE_BF16, flags=0, d_qk=192, d_v=128):

@@ -25,6 +25,7 @@
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
 #include "mla_decode.hip.h"
+#include "mla_append.hip.h"
 #include "fwd_mla.hip.h"
 
 namespace fa {
@@ -904,6 +905,8 @@ struct MlaCall {
     const fa_strides *sQ, *sKV, *sO;
     const DecodePaging* paging;
     void* stream;
+    int kv_dtype;                  // the cache's element type: FA_DTYPE_BF16, or FA_DTYPE_FP8_E4M3 (the _fp8 entry points)
+    const float* kv_descale;       // fp8: optional, ONE fp32 (device memory) for the whole cache; NULL = 1
 };
 
 static DecodeRoute mla_route(const MlaCall& c) {
@@ -945,13 +948,15 @@ static int mla_run(MlaCall c) {
     if (!aligned16(c.Q) || !aligned16(c.KV) || !aligned16(c.O) || !aligned16(c.LSE) || !aligned16(c.workspace)) return FA_ERR_MISALIGNED;
     fa_strides tKV{};   // the cache's strides without the head stride, which no MLA call reads
     if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
-    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .kv_dtype = FA_DTYPE_BF16, .capacity = c.capacity,
+    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .k_descale = c.kv_descale, .v_descale = c.kv_descale,
+                  .kv_dtype = c.kv_dtype, .capacity = c.capacity,
                   .sK = c.sKV ? &tKV : nullptr, .sV = c.sKV ? &tKV : nullptr, .paging = pg};
     int rc = cache_check_arrays(cache, nullptr);
     if (rc != FA_OK) return rc;
     if ((rc = cache_capacity(cache)) != FA_OK) return rc;
     c.capacity = cache.capacity;
     if ((rc = mla_check_shape(c)) != FA_OK) return rc;
+    if (c.kv_dtype != FA_DTYPE_BF16 && c.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
     if (!strides_ok(c.sQ, 2, D) || !cache_strides_ok(cache, D) || !strides_ok(c.sO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
     if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;
@@ -979,10 +984,73 @@ static int mla_run(MlaCall c) {
     p.table_stride = pg ? pg->table_stride : 0;
     p.num_pages = pg ? pg->num_pages : 0;
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.k_descale = p.v_descale = c.kv_descale;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
-    rc = mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
+    rc = c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_decode_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
+                                         : mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
     return mla_combine_launch((unsigned)rows, st, p);
+}
+
+// ---- the MLA latent-cache append: flash_attention_mla_append* (mla_append.hip.h) ----
+// kv_append_run's ladder on one cache tensor with the two widths (dLatent, dRope) at the place of dHead and no K/V head count.  One
+// workgroup per (sequence, block of 64 key positions)
+struct MlaAppendCall {
+    const void *Cnew, *Rnew;
+    void* KV;
+    const int32_t* kv_lens;
+    const float* kv_descale;
+    int B, Sq, capacity, d_latent, d_rope, dtype, kv_dtype;
+    const fa_strides *sC, *sR, *sKV;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+static int mla_append_run(const MlaAppendCall& c) {
+    using C = MlaAppendCfg;
+    constexpr int D = C::DL + C::DR;
+    const DecodePaging* pg = c.paging;
+    if (!c.Cnew || !c.Rnew || !c.KV || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Cnew) || !aligned16(c.Rnew) || !aligned16(c.KV)) return FA_ERR_MISALIGNED;
+    // strideH is read of none of the three tensors
+    fa_strides tC{}, tR{}, tKV{};
+    if (c.sC) tC = fa_strides{c.sC->strideB, 0, c.sC->strideS};
+    if (c.sR) tR = fa_strides{c.sR->strideB, 0, c.sR->strideS};
+    if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
+    const fa_strides *sC = c.sC ? &tC : nullptr, *sR = c.sR ? &tR : nullptr, *sKV = c.sKV ? &tKV : nullptr;
+    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .k_descale = c.kv_descale, .v_descale = c.kv_descale,
+                  .kv_dtype = c.kv_dtype, .capacity = c.capacity, .sK = sKV, .sV = sKV, .paging = pg};
+    int rc = cache_check_arrays(cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    const int B = c.B, Sq = c.Sq, Sk = cache.capacity;
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || c.d_latent <= 0 || c.d_rope <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || Sq > Sk || B > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.kv_dtype != FA_DTYPE_BF16 && c.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.kv_dtype == FA_DTYPE_BF16 && c.kv_descale) return FA_ERR_UNSUPPORTED_DTYPE;   // a bf16 cache is a bit copy
+    if (c.d_latent != C::DL || c.d_rope != C::DR) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (!strides_ok(sC, 2, C::DL) || !strides_ok(sR, 2, C::DR) || !cache_strides_ok(cache, D)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;   // what is written can be read
+    const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
+    const int64_t grid = (int64_t)B * row_blocks;
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    MlaAppendParams p;
+    int64_t unused;
+    p.Cnew = (const __bf16*)c.Cnew; p.Rnew = (const __bf16*)c.Rnew; p.KV = c.KV;
+    p.kv_lens = c.kv_lens;
+    p.block_table = pg ? pg->table : nullptr;
+    p.descale = c.kv_descale;
+    resolve_strides(sC, 1, Sq, C::DL, p.cB, unused, p.cS);
+    resolve_strides(sR, 1, Sq, C::DR, p.rB, unused, p.rS);
+    resolve_strides(sKV, 1, cache_rows(cache), D, p.kvB, unused, p.kvS);
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    const Kernel k = mla_append_kernel_of(c.kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
+    return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
 }
 
 // ---- MLA prefill (fwd_mla.hip.h): bf16 Q, K [.., 192] and V, O [.., 128] ----
@@ -1888,7 +1956,7 @@ int flash_attention_mla_decode_plan(int batchSize, int numHeads, int seqLenQ, in
     using namespace fa;
     if (!plan) return FA_ERR_NULL_POINTER;
     const MlaCall c{.B = batchSize, .H = numHeads, .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope,
-                    .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits};
+                    .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits, .kv_dtype = FA_DTYPE_BF16};
     const int rc = mla_check_shape(c);
     if (rc != FA_OK) return rc;
     const DecodeRoute r = mla_route(c);
@@ -1913,7 +1981,8 @@ int flash_attention_mla_decode(const void* Q, const void* KV, void* O, float* LS
                                int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream) {
     return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
                         .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
-                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream});
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream,
+                        .kv_dtype = FA_DTYPE_BF16});
 }
 
 int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
@@ -1924,7 +1993,51 @@ int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O,
     const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
     return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
                         .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
-                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream});
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
+                        .kv_dtype = FA_DTYPE_BF16});
+}
+
+// ---- MLA decode against an fp8 latent cache, and the latent-cache append ----
+int flash_attention_mla_decode_fp8(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, const float* kvDescale,
+                                   void* workspace, int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                   float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ,
+                                   const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream,
+                        .kv_dtype = kv_dtype, .kv_descale = kvDescale});
+}
+
+int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                         const int32_t* blockTable, const float* kvDescale, void* workspace, int batchSize, int numHeads,
+                                         int seqLenQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent,
+                                         int dRope, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, int numSplits,
+                                         const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
+                        .kv_dtype = kv_dtype, .kv_descale = kvDescale});
+}
+
+int flash_attention_mla_append(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, const float* kvDescale, int batchSize,
+                               int seqLenNew, int seqLenK, int dLatent, int dRope, int dtype, int kv_dtype, const fa_strides* sC,
+                               const fa_strides* sR, const fa_strides* sKV, void* stream) {
+    return fa::mla_append_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KV, .kv_lens = kvLens, .kv_descale = kvDescale, .B = batchSize,
+                               .Sq = seqLenNew, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .dtype = dtype,
+                               .kv_dtype = kv_dtype, .sC = sC, .sR = sR, .sKV = sKV, .stream = stream});
+}
+
+int flash_attention_mla_append_paged(const void* Cnew, const void* Rnew, void* KVpool, const int32_t* kvLens, const int32_t* blockTable,
+                                     const float* kvDescale, int batchSize, int seqLenNew, int numPages, int pageSize, int maxPagesPerSeq,
+                                     int64_t tableStride, int dLatent, int dRope, int dtype, int kv_dtype, const fa_strides* sC,
+                                     const fa_strides* sR, const fa_strides* sKV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_append_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KVpool, .kv_lens = kvLens, .kv_descale = kvDescale, .B = batchSize,
+                               .Sq = seqLenNew, .d_latent = dLatent, .d_rope = dRope, .dtype = dtype, .kv_dtype = kv_dtype, .sC = sC,
+                               .sR = sR, .sKV = sKV, .paging = &pg, .stream = stream});
 }
 
 // ---- MLA prefill ----

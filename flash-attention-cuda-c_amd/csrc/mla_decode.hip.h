@@ -33,6 +33,8 @@
 // The parameters are a DecodeParams filled as decode_run fills one (K = the latent cache, V not read, Hkv = 1, G = H, kH not read).
 #pragma once
 
+#include <type_traits>
+
 #include "decode_bf16.hip.h"
 #include "launchers.hip.h"
 
@@ -61,11 +63,22 @@ struct MlaCfg {
 
 // the two launchers of inst_mla_decode.hip: the split kernel (contiguous or paged) and decode_combine_kernel<512>
 int mla_decode_launch(bool paged, unsigned grid, hipStream_t st, const DecodeParams& p);
+int mla_decode_fp8_launch(bool paged, unsigned grid, hipStream_t st, const DecodeParams& p);   // inst_mla_decode_fp8.hip: the KV8 form
 int mla_combine_launch(unsigned rows, hipStream_t st, const DecodeParams& p);
 
-template <bool PAGED>
+// KV8 (flash_attention_mla_decode_fp8 / _paged_fp8): the cache holds e4m3fn bytes, rows of 576 bytes, under ONE
+// fp32 descale (p.k_descale, NULL = 1).  Only the stream from memory changes: a row is 72 chunks of 8 bytes as a bf16 row is 72 chunks of
+// 16, so the lane map of the fetch is the bf16 form's with 8-byte loads, and fp8x8_to_bf16x8 -- exact -- makes of each the 16 bytes the
+// bf16 form writes to the same place of the image.  From the image on nothing differs; the descale multiplies the score scale before the
+// loop and the normaliser after it.
+template <bool PAGED, bool KV8 = false>
 __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p) {
     using C = MlaCfg;
+    constexpr int ES = KV8 ? 1 : 2;                           // bytes per cache element
+    constexpr int CB = 8 * ES;                                // bytes of a fetched chunk: 8 elements
+    typedef std::conditional_t<KV8, u32x2, u32x4> chunk_t;
+    typedef std::conditional_t<KV8, uint8_t, __bf16> elem_t;
+    const elem_t* const Kp = reinterpret_cast<const elem_t*>(p.K);
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const lds_ptr smem = (lds_ptr)smem_raw;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -109,18 +122,18 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
     // the fetch: waves 0, 1 take the tile's first 16-key group, waves 2, 3 its second; load n of a wave is the 16-byte chunk
     // (64 (NLD (wave & 1) + n) + lane) of the group's 16 x CPR chunks, row-major
     const int grp = wv >> 1;
-    const int ksb = (int)(p.kS * 2);
+    const int ksb = (int)(p.kS * ES);
     int goff[C::NLD], loff[C::NLD];
 #pragma unroll
     for (int n = 0; n < C::NLD; ++n) {
         const int idx = 64 * (C::NLD * (wave & 1) + n) + lane;
         const int row = idx / C::CPR, ch = idx - row * C::CPR;
-        goff[n] = row * ksb + ch * 16;
+        goff[n] = row * ksb + ch * CB;
         loff[n] = (16 * grp + row) * C::LROW + ch * 16;
     }
     // contiguous: one descriptor over the VISIBLE rows of this sequence -- rows >= len read as 0
-    const char* Kb = (const char*)(p.K + (PAGED ? 0 : b * p.kB));
-    const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kb, 0, (len - 1) * ksb + C::ROWB, 0x00020000);
+    const char* Kb = (const char*)(Kp + (PAGED ? 0 : b * p.kB));
+    const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kb, 0, (len - 1) * ksb + C::D * ES, 0x00020000);
     // paged: this sequence's row of the table, the last page that holds a visible key, the entry of the wave's group of a tile
     const int32_t* tb = p.block_table + (PAGED ? b * p.table_stride : 0);
     const int last_page = PAGED ? (len - 1) >> p.page_shift : 0;
@@ -128,27 +141,31 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
         const int key = t * C::KT + 16 * grp;
         return tb[min(key >> p.page_shift, last_page)];
     };
-    u32x4 kn[C::NLD];
+    chunk_t kn[C::NLD];
+    auto load_chunk = [](__amdgpu_buffer_rsrc_t rsrc, int off) {
+        if constexpr (KV8) return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
+        else return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+    };
     auto load_tile = [&](int t, int entry) {
         if constexpr (!PAGED) {
             const int base = (t * C::KT + 16 * grp) * ksb;
 #pragma unroll
             for (int n = 0; n < C::NLD; ++n)
-                kn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, base + goff[n], 0, 0));
+                kn[n] = load_chunk(krsrc, base + goff[n]);
         } else {
             // the group's descriptor: at its first row, holding its rows below len (none: zero bytes, everything reads as 0)
             const int key = t * C::KT + 16 * grp;
             const int page = min(max(entry, 0), p.num_pages - 1);
-            const __bf16* base = p.K + page * p.kB + (key & ((1 << p.page_shift) - 1)) * p.kS;
+            const elem_t* base = Kp + page * p.kB + (key & ((1 << p.page_shift) - 1)) * p.kS;
             const int rows = min(len - key, 16);
-            const int bytes = rows > 0 ? (rows - 1) * ksb + C::ROWB : 0;
+            const int bytes = rows > 0 ? (rows - 1) * ksb + C::D * ES : 0;
             const uint64_t a = (uint64_t)base;
             const uint64_t au = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
             const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc((void*)au, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 #pragma unroll
             for (int n = 0; n < C::NLD; ++n)
-                kn[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(gr, goff[n], 0, 0));
+                kn[n] = load_chunk(gr, goff[n]);
         }
     };
 
@@ -163,6 +180,10 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
     FA_LDS float* ll = reinterpret_cast<FA_LDS float*>(smem + C::L_OFF);
 
     const float NEG_INF = -__builtin_inff();
+    // KV8: the logical cache is KV8 * ds -- in the scores (here) and in the values (the normaliser, below)
+    float ds = 1.f;
+    if constexpr (KV8) ds = p.k_descale ? p.k_descale[0] : 1.f;
+    const float sl2_ds = p.scale_log2 * ds;
     float m = NEG_INF, l = 0.f;   // of this lane's row: running max (log2 domain, shared by the row's four lanes), this lane's share of the sum
     f32x4 o[4][C::DG];            // O^T: column 128 wave + 16 dg + 4 h4 + reg, packed row 16 rt + r
 #pragma unroll
@@ -184,7 +205,10 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
         // wave left before the first barrier of tile t - 1)
         const lds_ptr img = smem + ((t - t0) & 1) * C::IMG;
 #pragma unroll
-        for (int n = 0; n < C::NLD; ++n) lds_write_b128(img, loff[n], kn[n]);
+        for (int n = 0; n < C::NLD; ++n) {
+            if constexpr (KV8) lds_write_b128(img, loff[n], fp8x8_to_bf16x8(kn[n][0], kn[n][1]));
+            else lds_write_b128(img, loff[n], kn[n]);
+        }
         __syncthreads();
         if (t + 1 < t1) {   // (uniform) the next tile, in flight under both products; paged: its entry arrived a tile ago
             load_tile(t + 1, e_next);
@@ -204,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
             float mx = NEG_INF;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                x[j] = kb + 16 * (j >> 2) + (j & 3) < lim ? s[j >> 2][j & 3] * p.scale_log2 : NEG_INF;
+                x[j] = kb + 16 * (j >> 2) + (j & 3) < lim ? s[j >> 2][j & 3] * (KV8 ? sl2_ds : p.scale_log2) : NEG_INF;
                 mx = fmaxf(mx, x[j]);
             }
             mx = max_all_quarters(mx);
@@ -279,7 +303,8 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(const DecodeParams p
         if (rt < nrt && opr < nrows) {
             const float M = al[rt * 16 + r], L = ll[rt * 16 + r];
             const int oh = opr / Sq, oi = opr - oh * Sq;
-            const float inv = M != NEG_INF ? 1.0f / L : 0.f;                                      // empty split: O = 0
+            float inv = M != NEG_INF ? 1.0f / L : 0.f;                                            // empty split: O = 0
+            if constexpr (KV8) inv *= ds;                                                         // (the slabs are normalised: both branches)
             const float lse = M != NEG_INF ? (M + __log2f(L)) * 0.6931471805599453f : NEG_INF;    // ... LSE = -inf
             const int64_t row = ((int64_t)b * p.H + oh) * Sq + oi;
             const int col = wave * 128 + 4 * h4;

@@ -1294,8 +1294,22 @@ int flash_attention_kv_accept_paged(void* Kpool, void* Vpool, const int32_t* kvL
  * one workgroup per CU, no split shorter than two key tiles of the capacity) is NOT measured.  The grid and row limits of
  * FA_DECODE_MAX_WORKGROUPS apply.  flash_attention_mla_decode_workspace_size = flash_attention_decode_workspace_size at dHead = 512.
  *
- * Not done: fp8 latent caches, a latent-cache append, windows, sinks, tree masks, ragged calls and chunked prefill, cascade, other
- * latent widths, a 128-row block that reads the cache once at numHeads = 128, a single-weights flag.
+ * flash_attention_mla_decode_fp8, flash_attention_mla_decode_paged_fp8 -- the two calls against an FP8 latent cache (DESIGN.md section
+ * 37): KV / KVpool hold one-byte OCP e4m3fn elements (kv_dtype = FA_DTYPE_FP8_E4M3, anything else FA_ERR_UNSUPPORTED_DTYPE; dtype, Q's
+ * type, stays FA_DTYPE_BF16) in rows of 576 bytes; sKV counts in elements, which are bytes: every stride a multiple of 16
+ * (FA_ERR_BAD_STRIDE), strideH not read; the extent limits count one byte per element.  kvDescale: a DEVICE pointer to ONE fp32, 4-byte
+ * aligned (FA_ERR_MISALIGNED), NULL = 1.0, read by the kernel -- a replayed graph sees the value of the moment.  The logical cache is
+ * KV8 * kvDescale[0], in the score columns and in the value columns alike:
+ *     O = softmax(scale * Q (d KV8)^T) * d KV8[:, :512],   the LSE over the logical scores
+ * A descale that is not finite and positive gives unspecified numbers, never a bad address.  Everything else -- the shapes, the
+ * clamps, the mask, the splits, the workspace, the plan (flash_attention_mla_decode_plan / _workspace_size describe these calls
+ * unchanged: the plan does not depend on the cache's type), the order and the codes of the refusals -- is the bf16 call's.  Bytes at
+ * and beyond the length may be any pattern, 0x7F / 0xFF included; below the length a NaN byte is data.  e4m3fn -> bf16 is exact and
+ * happens in registers on the way to LDS; from there on the arithmetic is the bf16 call's, so under a power-of-two descale the result
+ * equals, bit for bit, the bf16 call on the dequantised cache with the same split count; and paged equals contiguous on a gathered copy.
+ *
+ * Not done: windows, sinks, tree masks, ragged calls and chunked prefill, cascade, other latent widths, per-block scales or a mixed
+ * fp8-latent / bf16-rope row, a 128-row block that reads the cache once at numHeads = 128, a single-weights flag.
  */
 int    flash_attention_mla_decode_plan(int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
                                        int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
@@ -1312,6 +1326,52 @@ int flash_attention_mla_decode_paged(const void* Q, const void* KVpool, void* O,
                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
                                      int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
                                      const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_decode_fp8(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, const float* kvDescale,
+                                   void* workspace,
+                                   int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                   float scale, bool is_causal, int dtype, int kv_dtype /* FA_DTYPE_FP8_E4M3 */, int o_dtype, int numSplits,
+                                   const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                         const int32_t* blockTable, const float* kvDescale, void* workspace,
+                                         int batchSize, int numHeads, int seqLenQ,
+                                         int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                         int dLatent, int dRope, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype,
+                                         int numSplits,
+                                         const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+/*
+ * flash_attention_mla_append, flash_attention_mla_append_paged -- the WRITE side of the MLA latent cache: the new
+ * tokens of every sequence become rows of the cache that flash_attention_mla_decode* reads.
+ *   Cnew     [batchSize, seqLenNew, 512] bf16: the compressed latent;  Rnew [batchSize, seqLenNew, 64] bf16: the key's rotary part,
+ *            ALREADY rotated by the caller.  They go into row p as columns [0, 512) and [512, 576).  sC / sR: strideB and strideS in
+ *            elements (strideH is not read), NULL = dense; the last dimension is contiguous, so two slices of one projection pass
+ *            without a copy
+ *   KV / KVpool  [batchSize, seqLenK, 576], seqLenK the CAPACITY, or a pool [numPages, pageSize, 576] behind blockTable; bf16 (kv_dtype
+ *            = FA_DTYPE_BF16; kvDescale must be NULL) or e4m3fn bytes (FA_DTYPE_FP8_E4M3; sKV in bytes) under kvDescale, ONE fp32 in
+ *            device memory, NULL = 1.0
+ *   dLatent, dRope  only (512, 64); anything else FA_ERR_UNSUPPORTED_DHEAD.  1 <= seqLenNew <= capacity, not capped at FA_DECODE_MAX_Q
+ * The rules are flash_attention_kv_append's, word for word: L = min(kvLens[b], capacity) ALREADY counts the new rows, row i goes to
+ * position L - seqLenNew + i when that is >= 0, L <= 0 writes nothing; only the entries of pages that receive a row are read, an entry
+ * outside [0, numPages) is skipped and never clamped; bf16 is a copy of bits; fp8 is the e4m3fn code of clamp(fp32(x) / descale, -448,
+ * 448), the correctly rounded quotient rounded to nearest even once, the sign of zero kept, +-inf stored as +-448 and NaN as a NaN
+ * code; nothing else in the cache changes; lengths, the descale and the table are read by the kernel, so `kv_lens += Sq; mla_append;
+ * mla_decode` is one graph.  Validated before the launch in flash_attention_kv_append's order and with its codes, the two widths at
+ * the place of dHead; no allocation, no synchronisation, no atomics: every cache byte has one writer.
+ * Not done: a rotation fused into the append, fp8 new rows, a ragged form.
+ */
+int flash_attention_mla_append(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, const float* kvDescale,
+                               int batchSize, int seqLenNew, int seqLenK, int dLatent, int dRope,
+                               int dtype /* of Cnew, Rnew: FA_DTYPE_BF16 */, int kv_dtype /* FA_DTYPE_BF16 | FA_DTYPE_FP8_E4M3 */,
+                               const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream);
+
+int flash_attention_mla_append_paged(const void* Cnew, const void* Rnew, void* KVpool, const int32_t* kvLens, const int32_t* blockTable,
+                                     const float* kvDescale,
+                                     int batchSize, int seqLenNew,
+                                     int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope,
+                                     int dtype, int kv_dtype,
+                                     const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream);
 
 /*
  * flash_attention_mla_prefill -- the forward pass of multi-head latent attention in its UP-PROJECTED (prefill) form: ordinary multi-head

@@ -157,6 +157,14 @@ Each line:
               With --paged a,b: paged_ms[page] / paged_ratio[page], the same data in pages behind a shuffled table.  With --splits
               a,b,c: the forced sweep, one line per (shape, split count) with mla_ms only; --no-cross: no torch route
               (profiles/mla_decode_gpu.log).
+              With --kv fp8 (profiles/mla_fp8_gpu.log): the same cache quantised to e4m3fn under one descale
+              (amax / 448), its call in the same windows, alternated with the bf16 call, which stays the yardstick:
+              fp8_ms      one flash_attention_mla_decode call on the fp8 cache: [median, min, max];  fp8_ratio = fp8_ms / mla_ms (medians)
+              fp8_kv_tbps the fp8 cache's bytes, counted once at one byte per element (B L 576), / fp8_ms
+              spread      (max - min) / median of the mla_ms windows: the run's own window-to-window spread
+              paged_fp8_ms[page] with --paged.  With --append: one decode step's new token (Sq = 1) written into the fp8 cache at
+              position L - 1, append_ms (mla_cache_append) beside torch_append_ms, the torch route that produces the same bytes
+              (cat, divide, clamp, convert, indexed copy), alternated; append_same_bytes says that it did.
 """
 import argparse
 import json
@@ -823,12 +831,19 @@ def mla_main(args, fa, dev):
                 w = sorted(timed(lambda: mla(ns), args.steps, args.warmup) for _ in range(args.repeats))
                 print(json.dumps(dict(base, splits=ns, forced=True, mla_ms=[round(x, 5) for x in (statistics.median(w), w[0], w[-1])])), flush=True)
             continue
-        a, b = [], []
+        fp8 = args.kv == "fp8"
+        if fp8:      # the same cache as e4m3fn bytes under one descale; the bf16 call above stays the yardstick
+            ds = (KV.float().abs().amax() / 448.0).reshape(1)
+            KV8 = (KV.float() / ds).clamp(-448, 448).to(torch.float8_e4m3fn)
+            mla8 = lambda: fa.flash_attention_mla_decode(Q, KV8, lens, O=O, workspace=ws, kv_descale=ds)
+        a, b, c = [], [], []
         for _ in range(args.repeats):
             a.append(timed(mla, args.steps, args.warmup))
+            if fp8:
+                c.append(timed(mla8, args.steps, args.warmup))
             if beside_torch:
                 b.append(timed(torch_ops, args.steps, args.warmup))
-        a, b = sorted(a), sorted(b)
+        a, b, c = sorted(a), sorted(b), sorted(c)
         ms = statistics.median(a)
         out = dict(base, splits=plan["num_splits"], grid=plan["grid"], mla_ms=[round(x, 5) for x in (ms, a[0], a[-1])],
                    kv_tbps=round(kv_bytes / ms / 1e9, 3), tflops=round(2 * (D + DL) * B * H * Sq * L / ms / 1e9, 1),
@@ -837,6 +852,11 @@ def mla_main(args, fa, dev):
         if beside_torch:
             out.update(torch_ms=[round(x, 5) for x in (statistics.median(b), b[0], b[-1])], speedup=round(statistics.median(b) / ms, 3),
                        max_diff_vs_torch=round((mla().float() - torch_ops().float()).abs().max().item(), 5))
+        if fp8:
+            ms8 = statistics.median(c)
+            out.update(fp8_ms=[round(x, 5) for x in (ms8, c[0], c[-1])], fp8_ratio=round(ms8 / ms, 4),
+                       fp8_kv_tbps=round(B * L * D / ms8 / 1e9, 3), spread=round((a[-1] - a[0]) / ms, 4),
+                       max_diff_fp8_vs_bf16=round((mla8().float() - mla().float()).abs().max().item(), 5))
         for page in pages:
             if L % page:
                 continue
@@ -846,10 +866,45 @@ def mla_main(args, fa, dev):
             pool[perm] = KV.view(B * n, page, D)
             table = perm.view(B, n).to(torch.int32)
             paged = lambda: fa.flash_attention_mla_decode_paged(Q, pool, table, lens, O=O, workspace=ws)
-            w = sorted(timed(paged, args.steps, args.warmup) for _ in range(args.repeats))
+            w, w8 = [], []
+            if fp8:
+                pool8 = torch.empty(B * n, page, D, device=dev, dtype=torch.uint8)
+                pool8[perm] = KV8.view(torch.uint8).view(B * n, page, D)
+                pool8 = pool8.view(torch.float8_e4m3fn)
+                paged8 = lambda: fa.flash_attention_mla_decode_paged(Q, pool8, table, lens, O=O, workspace=ws, kv_descale=ds)
+            for _ in range(args.repeats):
+                w.append(timed(paged, args.steps, args.warmup))
+                if fp8:
+                    w8.append(timed(paged8, args.steps, args.warmup))
+            w, w8 = sorted(w), sorted(w8)
             out.setdefault("paged_ms", {})[page] = [round(x, 5) for x in (statistics.median(w), w[0], w[-1])]
             out.setdefault("paged_ratio", {})[page] = round(statistics.median(w) / ms, 4)
+            if fp8:
+                out.setdefault("paged_fp8_ms", {})[page] = [round(x, 5) for x in (statistics.median(w8), w8[0], w8[-1])]
+                del pool8
             del pool, table
+        if fp8 and args.append:      # one decode step's token into the fp8 cache, beside the torch route to the same bytes
+            c_kv = torch.randn(B, 1, DL, device=dev, generator=g).to(torch.bfloat16)
+            k_pe = torch.randn(B, 1, D - DL, device=dev, generator=g).to(torch.bfloat16)
+            mine, theirs = KV8.clone(), KV8.clone()
+            rows, at = torch.arange(B, device=dev), (lens - 1).long()
+            append = lambda: fa.mla_cache_append(c_kv, k_pe, mine, lens, kv_descale=ds)
+
+            def torch_append():
+                row = (torch.cat([c_kv, k_pe], -1).float() / ds).clamp(-448, 448).to(torch.float8_e4m3fn)
+                theirs.view(torch.uint8)[rows, at] = row.view(torch.uint8)[:, 0]
+
+            x, y = [], []
+            for _ in range(args.repeats):
+                x.append(timed(append, args.steps, args.warmup))
+                y.append(timed(torch_append, args.steps, args.warmup))
+            x, y = sorted(x), sorted(y)
+            out.update(append_ms=[round(v, 5) for v in (statistics.median(x), x[0], x[-1])],
+                       torch_append_ms=[round(v, 5) for v in (statistics.median(y), y[0], y[-1])],
+                       append_same_bytes=bool(torch.equal(mine.view(torch.uint8), theirs.view(torch.uint8))))
+            del mine, theirs
+        if fp8:
+            del KV8
         print(json.dumps(out), flush=True)
         del Q, KV, O, ws, q2, kt, v
         torch.cuda.empty_cache()
