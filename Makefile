@@ -50,6 +50,9 @@ build/obj/inst_bf16_mla.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 # latent-cache append (mla_append.hip.h) without it too
 build/obj/inst_mla_decode_fp8.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 build/obj/inst_mla_append.o: HIPFLAGS += $(NO_PK_F32)
+# the sparse MLA decode kernel (mla_sparse.hip.h): the dense kernel's accumulators; each unit under the flags of its dense twin
+build/obj/inst_mla_sparse.o: HIPFLAGS += $(MFMA_VGPR)
+build/obj/inst_mla_sparse_fp8.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS, and the shared_* ones, which are built at the same RT; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
 # tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
@@ -151,8 +154,8 @@ asan: asan-host oracle
 # Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
-build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s: HIPFLAGS += $(MFMA_VGPR)
-build/asm/inst_bf16_mla.s build/asm/inst_mla_decode_fp8.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s build/asm/inst_mla_sparse.s: HIPFLAGS += $(MFMA_VGPR)
+build/asm/inst_bf16_mla.s build/asm/inst_mla_decode_fp8.s build/asm/inst_mla_sparse_fp8.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 build/asm/inst_mla_append.s: HIPFLAGS += $(NO_PK_F32)
 define ASM_RECIPE
 @mkdir -p build/asm

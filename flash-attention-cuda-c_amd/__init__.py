@@ -91,6 +91,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_mla_decode_workspace_size",
            "flash_attention_mla_decode_fp8", "flash_attention_mla_decode_paged_fp8",
            "flash_attention_mla_append", "flash_attention_mla_append_paged",
+           "flash_attention_mla_sparse_decode", "flash_attention_mla_sparse_decode_paged", "flash_attention_mla_sparse_decode_fp8",
+           "flash_attention_mla_sparse_decode_paged_fp8", "flash_attention_mla_sparse_plan",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
@@ -132,6 +134,10 @@ _CASCADE_SYMBOLS = {False: "flash_attention_cascade_decode", True: "flash_attent
 _MLA_SYMBOLS = {False: "flash_attention_mla_decode", True: "flash_attention_mla_decode_paged"}
 _MLA_FP8_SYMBOLS = {False: "flash_attention_mla_decode_fp8", True: "flash_attention_mla_decode_paged_fp8"}
 _MLA_APPEND_SYMBOLS = {False: "flash_attention_mla_append", True: "flash_attention_mla_append_paged"}
+# ... sparse MLA decode: _MLA_SPARSE_SYMBOLS[fp8 cache][paged], the dense entry point with ``indices, topk, indexStrideB, indexStrideQ``
+# after ``kvLens``
+_MLA_SPARSE_SYMBOLS = {False: {False: "flash_attention_mla_sparse_decode", True: "flash_attention_mla_sparse_decode_paged"},
+                       True: {False: "flash_attention_mla_sparse_decode_fp8", True: "flash_attention_mla_sparse_decode_paged_fp8"}}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -267,12 +273,23 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, _MLA_FP8_SYMBOLS[paged])
             fn.argtypes = [vp] * 5 + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i, i] + [sp] * 3 + [vp]
             fn.restype = i
+            # ... the sparse calls: the index list, topk and its two strides after kvLens
+            i64 = ctypes.c_int64
+            fn = getattr(L, _MLA_SPARSE_SYMBOLS[False][paged])
+            fn.argtypes = [vp] * 5 + [vp, i, i64, i64] + [vp] * paged + [vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i] + [sp] * 3 + [vp]
+            fn.restype = i
+            fn = getattr(L, _MLA_SPARSE_SYMBOLS[True][paged])
+            fn.argtypes = [vp] * 5 + [vp, i, i64, i64] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i, i] \
+                + [sp] * 3 + [vp]
+            fn.restype = i
             # ... the latent-cache append: the two new tensors, the cache, kvLens, the table (paged), kvDescale
             fn = getattr(L, _MLA_APPEND_SYMBOLS[paged])
             fn.argtypes = [vp] * 4 + [vp] * paged + [vp] + [i] * 2 + paging(paged) + [i] * 4 + [sp] * 3 + [vp]
             fn.restype = i
         L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_mla_decode_plan.restype = i
+        L.flash_attention_mla_sparse_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_mla_sparse_plan.restype = i
         L.flash_attention_mla_decode_workspace_size.argtypes = [i, i, i, i, i]
         L.flash_attention_mla_decode_workspace_size.restype = ctypes.c_size_t
         # MLA prefill: flash_attention_ex's signature with (dQK, dV) where dHead stands and no input dtype
@@ -1055,6 +1072,16 @@ def mla_decode_plan(B, H, Sq, Sk, o_dtype=FA_DTYPE_BF16, num_splits=0):
     return _plan_dict(p)
 
 
+def mla_sparse_plan(B, H, Sq, topk, o_dtype=FA_DTYPE_BF16, num_splits=0):
+    """What a flash_attention_mla_sparse_decode call launches (fa_decode_plan as a dict): a unit is (sequence, query row, block of 64
+    heads), ``row_blocks = ceil(H / 64)``, ``grid = B * Sq * row_blocks * num_splits``, and the splits divide the ``ceil(topk / 32)``
+    tiles of the slot range; ``num_splits`` 0 = the library's choice (the dense rule, not measured for gathered tiles).  The capacity
+    does not enter.  The workspace is ``decode_workspace_size(B, H, Sq, 512, num_splits)``."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_mla_sparse_plan(B, H, Sq, topk, MLA_D_LATENT, MLA_D_ROPE, o_dtype, num_splits, ctypes.byref(p)))
+    return _plan_dict(p)
+
+
 def _mla_descale(kv_descale, fp8, device):
     """the check both MLA fronts and both append fronts make of ``kv_descale``: one fp32 on the device, and only with an fp8 cache"""
     import torch
@@ -1067,16 +1094,19 @@ def _mla_descale(kv_descale, fp8, device):
         raise ValueError("kv_descale must be an fp32 tensor of one element on the device of the cache")
 
 
-def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale=None):
+def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale=None,
+               indices=None):
     """Both MLA fronts: the checks of the tensors (with the decode fronts' helpers for the table, the lengths and the workspace), the plan
     and the workspace for the capacity, then the entry point of _MLA_SYMBOLS -- or, for a float8_e4m3fn cache under a bf16 Q, of
-    _MLA_FP8_SYMBOLS, which takes ``kv_descale`` and the cache's dtype code."""
+    _MLA_FP8_SYMBOLS, which takes ``kv_descale`` and the cache's dtype code.  With ``indices`` (the sparse fronts): the entry point of
+    _MLA_SPARSE_SYMBOLS, the plan for topk, and the index list with its two strides after the lengths."""
     import torch
     paged = block_table is not None
+    sparse = indices is not None
     f8 = getattr(torch, "float8_e4m3fn", None)
     fp8 = f8 is not None and getattr(KV, "dtype", None) == f8 and Q.dtype == torch.bfloat16
-    name = (_MLA_FP8_SYMBOLS if fp8 else _MLA_SYMBOLS)[paged]
-    if not (Q.is_cuda and KV.is_cuda and (not paged or block_table.is_cuda)):
+    name = _MLA_SPARSE_SYMBOLS[fp8][paged] if sparse else (_MLA_FP8_SYMBOLS if fp8 else _MLA_SYMBOLS)[paged]
+    if not (Q.is_cuda and KV.is_cuda and (not paged or block_table.is_cuda) and (not sparse or indices.is_cuda)):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
     D = MLA_D_LATENT + MLA_D_ROPE
     if Q.dim() != 4 or KV.dim() != 3 or (not paged and Q.shape[0] != KV.shape[0]) or Q.shape[3] != D or KV.shape[2] != D:
@@ -1087,13 +1117,25 @@ def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_spl
     if KV.stride(2) != 1:
         raise ValueError("last dimension must be contiguous")
     B, H, Sq, _ = Q.shape
+    if sparse:
+        if indices.dtype != torch.int32 or indices.device != Q.device or indices.dim() != 3 or tuple(indices.shape[:2]) != (B, Sq):
+            raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
+        if indices.shape[2] < 1 or indices.stride(2) != 1:
+            raise ValueError("indices needs topk >= 1 and a contiguous last dimension")
     # the cache as the [*, 1, rows, 576] tensor the decode helpers describe: one K/V "head"
     capacity, tables, geometry = _cache_geometry(KV.unsqueeze(1), block_table, B)
     _check_kv_lens(kv_lens, B)
     if scale is None:
         scale = float(D) ** -0.5
     odt = _dtype_code(out_dtype or (O.dtype if O is not None else _default_out_dtype(Q.dtype)))
-    ns = mla_decode_plan(B, H, Sq, capacity, odt, num_splits)["num_splits"]
+    if sparse:
+        ns = mla_sparse_plan(B, H, Sq, indices.shape[2], odt, num_splits)["num_splits"]
+        # (a stride of a dimension of size 1 may be anything: the kernel multiplies it by 0)
+        index_args = (indices.data_ptr(), indices.shape[2], indices.stride(0) if B > 1 else 0,
+                      indices.stride(1) if Sq > 1 else indices.shape[2])
+    else:
+        ns = mla_decode_plan(B, H, Sq, capacity, odt, num_splits)["num_splits"]
+        index_args = ()
     need = decode_workspace_size(B, H, Sq, MLA_D_LATENT, ns)
     with torch.cuda.device(Q.device):
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -1110,7 +1152,7 @@ def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_spl
         sQ, sO = _strides(Q), _strides(O)
         sKV = FaStrides(KV.stride(0), 0, KV.stride(1))
         ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = getattr(lib(), name)(Q.data_ptr(), KV.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *map(ptr, tables),
+        rc = getattr(lib(), name)(Q.data_ptr(), KV.data_ptr(), O.data_ptr(), ptr(lse), ptr(kv_lens), *index_args, *map(ptr, tables),
                                   *((ptr(kv_descale),) if fp8 else ()), workspace.data_ptr() if need else None, B, H, Sq, *geometry,
                                   MLA_D_LATENT, MLA_D_ROPE, float(scale), bool(is_causal), _dtype_code(Q.dtype),
                                   *((_dtype_code(KV.dtype),) if fp8 else ()), _dtype_code(O.dtype), ns,
@@ -1146,6 +1188,36 @@ def flash_attention_mla_decode_paged(Q, KV_pool, block_table, kv_lens=None, scal
     ``flash_attention_mla_decode``."""
     return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
                       kv_descale)
+
+
+def flash_attention_mla_sparse_decode(Q, KV, indices, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
+                                      return_lse=False, O=None, workspace=None, stream=None, kv_descale=None):
+    """SPARSE MLA decode (DeepSeek-V3.2's sparse attention after its indexer): ``flash_attention_mla_decode`` in which query row
+    ``(b, i)`` attends the cache rows ``indices[b, i, :]`` names -- int32 ``[B, Sq, topk]`` on the device, shared by all H heads, last
+    dimension contiguous -- and not the rows ``0 .. len``.  Slot t is a key iff ``0 <= indices[b, i, t] < lim``, ``lim = len_b`` or, under
+    ``is_causal``, ``max(len_b - Sq + i + 1, 1)``; any other slot (-1 padding, a position at or beyond the length or behind the mask)
+    is skipped and its cache row is never read.  A position in two slots counts twice; order does not matter.  A row without any key
+    gives ``O = 0`` and ``LSE = -inf``.  The cache is not copied: the kernel gathers the rows itself, and reads indices and lengths on
+    the device, so a captured call sees the values of the replay.
+
+    Every keyword as for ``flash_attention_mla_decode``: ``scale`` None = ``576 ** -0.5``; ``num_splits`` 0 = ``mla_sparse_plan``'s
+    choice; ``workspace`` ``decode_workspace_size(B, H, Sq, 512, ns)`` bytes; a ``torch.float8_e4m3fn`` cache with ``kv_descale``.  With
+    ``indices[b, i] = arange(capacity)`` and every length the capacity the result is the dense call's, bit for bit.  No CPU fallback."""
+    if indices is None:
+        raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
+    return _mla_front(Q, KV, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale, indices)
+
+
+def flash_attention_mla_sparse_decode_paged(Q, KV_pool, block_table, indices, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                                            num_splits=0, return_lse=False, O=None, workspace=None, stream=None, kv_descale=None):
+    """``flash_attention_mla_sparse_decode`` against a PAGED latent cache, ``KV_pool [P, page, 576]`` and ``block_table`` as in
+    ``flash_attention_mla_decode_paged``.  ``indices`` hold LOGICAL positions of the sequence: the kernel reads
+    ``block_table[b, p // page]`` itself, clamps the entry into [0, P), and reads no entry for a slot that is not a key.  The result is
+    the contiguous call's on a gathered copy under the same ``num_splits``, bit for bit."""
+    if indices is None:
+        raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
+    return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
+                      kv_descale, indices)
 
 
 def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, stream):

@@ -25,6 +25,7 @@
 #include "kv_append.hip.h"
 #include "rope_append.hip.h"
 #include "mla_decode.hip.h"
+#include "mla_sparse.hip.h"
 #include "mla_append.hip.h"
 #include "fwd_mla.hip.h"
 
@@ -907,14 +908,24 @@ struct MlaCall {
     void* stream;
     int kv_dtype;                  // the cache's element type: FA_DTYPE_BF16, or FA_DTYPE_FP8_E4M3 (the _fp8 entry points)
     const float* kv_descale;       // fp8: optional, ONE fp32 (device memory) for the whole cache; NULL = 1
+    // the sparse calls (flash_attention_mla_sparse_decode*; mla_sparse.hip.h): every query row (b, i) attends the
+    // positions indices[b, i, 0 .. topk) names
+    bool sparse;
+    const int32_t* indices;        // [B, Sq, topk] (device memory)
+    int topk;
+    int64_t index_stride_b, index_stride_q;
 };
 
+// The sparse calls route by the same formula over their own units and tiles: a unit is (sequence, query row, block of 64 HEADS) -- rows
+// that share a tile share an index list -- and the tiles are those of the topk slots, not of the capacity.  The constants are
+// inherited with the formula and NOT measured for a gathered tile: the forced sweep of tools/bench_decode.py --mla --sparse --splits
+// (profiles/mla_sparse_gpu.log) shows what the rule costs.
 static DecodeRoute mla_route(const MlaCall& c) {
     DecodeRoute r{};
-    const int64_t rows = (int64_t)c.H * c.Sq;
+    const int64_t rows = c.sparse ? (int64_t)c.H : (int64_t)c.H * c.Sq;
     r.row_blocks = (int)std::min<int64_t>((rows + MlaCfg::ROWS - 1) / MlaCfg::ROWS, INT32_MAX);
-    r.tiles = (c.capacity + MlaCfg::KT - 1) / MlaCfg::KT;
-    const int64_t units = (int64_t)c.B * r.row_blocks;
+    r.tiles = ((c.sparse ? c.topk : c.capacity) + MlaCfg::KT - 1) / MlaCfg::KT;
+    const int64_t units = (int64_t)c.B * r.row_blocks * (c.sparse ? c.Sq : 1);
     if (c.num_splits > 0) r.ns = c.num_splits;
     else {
         const int64_t want = ((int64_t)device_cus() + units - 1) / units;   // (wgs_per_cu = 1)
@@ -924,12 +935,15 @@ static DecodeRoute mla_route(const MlaCall& c) {
     return r;
 }
 
+constexpr int MLA_SPARSE_MAX_TOPK = 1 << 20;
+
 // the shape of a call or a plan, in decode_check_shape's order
 static int mla_check_shape(const MlaCall& c) {
     const int B = c.B, H = c.H, Sq = c.Sq, Sk = c.capacity;
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || c.d_latent <= 0 || c.d_rope <= 0) return FA_ERR_BAD_SHAPE;
     if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
     if (c.num_splits < 0 || c.num_splits > FA_DECODE_MAX_SPLITS) return FA_ERR_BAD_SHAPE;
+    if (c.sparse && (c.topk < 1 || c.topk > MLA_SPARSE_MAX_TOPK)) return FA_ERR_BAD_SHAPE;
     if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!is_output_dtype(c.o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
     if (c.d_latent != MlaCfg::DL || c.d_rope != MlaCfg::DR) return FA_ERR_UNSUPPORTED_DHEAD;
@@ -940,11 +954,13 @@ static int mla_check_shape(const MlaCall& c) {
     return FA_OK;
 }
 
-// one validation, in decode_run's order, and the launches: the MLA kernel and, under more than one split, the combine at D = 512
+// one validation, in decode_run's order, and the launches: the MLA kernel and, under more than one split, the combine at D = 512.
+// The sparse calls add four refusals at their places: NULL indices with the pointers, their alignment after the other arrays', topk
+// with the shapes, the index row stride with the strides
 static int mla_run(MlaCall c) {
     const DecodePaging* pg = c.paging;
     constexpr int D = MlaCfg::D, DL = MlaCfg::DL;
-    if (!c.Q || !c.KV || !c.O || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!c.Q || !c.KV || !c.O || (pg && !pg->table) || (c.sparse && !c.indices)) return FA_ERR_NULL_POINTER;
     if (!aligned16(c.Q) || !aligned16(c.KV) || !aligned16(c.O) || !aligned16(c.LSE) || !aligned16(c.workspace)) return FA_ERR_MISALIGNED;
     fa_strides tKV{};   // the cache's strides without the head stride, which no MLA call reads
     if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
@@ -953,19 +969,21 @@ static int mla_run(MlaCall c) {
                   .sK = c.sKV ? &tKV : nullptr, .sV = c.sKV ? &tKV : nullptr, .paging = pg};
     int rc = cache_check_arrays(cache, nullptr);
     if (rc != FA_OK) return rc;
+    if (c.sparse && misaligned4(c.indices)) return FA_ERR_MISALIGNED;
     if ((rc = cache_capacity(cache)) != FA_OK) return rc;
     c.capacity = cache.capacity;
     if ((rc = mla_check_shape(c)) != FA_OK) return rc;
     if (c.kv_dtype != FA_DTYPE_BF16 && c.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
     if (!strides_ok(c.sQ, 2, D) || !cache_strides_ok(cache, D) || !strides_ok(c.sO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
+    if (c.sparse && (c.index_stride_q < c.topk || c.index_stride_b < 0)) return FA_ERR_BAD_STRIDE;
     if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;
     const DecodeRoute r = mla_route(c);
     if (r.ns > 1 && !c.workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)c.B * c.H * c.Sq;
     if (rows > INT32_MAX) return FA_ERR_BAD_SHAPE;
 
-    DecodeParams p{};
+    MlaSparseParams p{};   // (the dense kernels take its DecodeParams)
     p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.KV; p.V = (const __bf16*)c.KV; p.O = c.O; p.lse = c.LSE;
     p.kv_lens = c.kv_lens;
     p.part_o = (float*)c.workspace;
@@ -986,6 +1004,14 @@ static int mla_run(MlaCall c) {
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
     p.k_descale = p.v_descale = c.kv_descale;
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    if (c.sparse) {
+        p.indices = c.indices; p.topk = c.topk;
+        p.isB = c.index_stride_b; p.isQ = c.index_stride_q;
+        rc = c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_sparse_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
+                                             : mla_sparse_launch(pg != nullptr, (unsigned)r.grid, st, p);
+        if (rc != FA_OK || r.ns == 1) return rc;
+        return mla_sparse_combine_launch((unsigned)rows, st, p);   // (a row may have no key in any split)
+    }
     rc = c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_decode_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
                                          : mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
@@ -2021,6 +2047,83 @@ int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void
                         .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
                         .kv_dtype = kv_dtype, .kv_descale = kvDescale});
 }
+
+// ---- sparse MLA decode ----
+int flash_attention_mla_sparse_plan(int batchSize, int numHeads, int seqLenQ, int topk, int dLatent, int dRope, int o_dtype, int numSplits,
+                                    fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    // (the capacity does not enter the launch: any valid one stands for it in the shape check)
+    const MlaCall c{.B = batchSize, .H = numHeads, .Sq = seqLenQ, .capacity = 1, .d_latent = dLatent, .d_rope = dRope,
+                    .dtype = FA_DTYPE_BF16, .o_dtype = o_dtype, .num_splits = numSplits, .kv_dtype = FA_DTYPE_BF16, .sparse = true,
+                    .topk = topk};
+    const int rc = mla_check_shape(c);
+    if (rc != FA_OK) return rc;
+    const DecodeRoute r = mla_route(c);
+    plan->num_splits = r.ns;
+    plan->row_blocks = r.row_blocks;
+    plan->rows_per_block = MlaCfg::ROWS;
+    plan->kv_block_rows = MlaCfg::KT;
+    plan->threads = MlaCfg::THREADS;
+    plan->grid = (int)r.grid;
+    plan->lds_bytes = MlaCfg::LDS_BYTES;
+    plan->combine_grid = r.ns > 1 ? (int)((int64_t)batchSize * numHeads * seqLenQ) : 0;   // one workgroup per (batch, head, query row)
+    plan->combine_threads = r.ns > 1 ? 256 : 0;
+    return FA_OK;
+}
+
+// the four calls: the dense ones with the index list after kvLens
+#define FA_SPARSE_ARGS const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ
+#define FA_SPARSE_FIELDS .sparse = true, .indices = indices, .topk = topk, .index_stride_b = indexStrideB, .index_stride_q = indexStrideQ
+
+int flash_attention_mla_sparse_decode(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, FA_SPARSE_ARGS,
+                                      void* workspace, int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                      float scale, bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ,
+                                      const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream,
+                        .kv_dtype = FA_DTYPE_BF16, FA_SPARSE_FIELDS});
+}
+
+int flash_attention_mla_sparse_decode_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens, FA_SPARSE_ARGS,
+                                            const int32_t* blockTable, void* workspace, int batchSize, int numHeads, int seqLenQ,
+                                            int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope,
+                                            float scale, bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ,
+                                            const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
+                        .kv_dtype = FA_DTYPE_BF16, FA_SPARSE_FIELDS});
+}
+
+int flash_attention_mla_sparse_decode_fp8(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, FA_SPARSE_ARGS,
+                                          const float* kvDescale, void* workspace, int batchSize, int numHeads, int seqLenQ, int seqLenK,
+                                          int dLatent, int dRope, float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype,
+                                          int numSplits, const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream,
+                        .kv_dtype = kv_dtype, .kv_descale = kvDescale, FA_SPARSE_FIELDS});
+}
+
+int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                                FA_SPARSE_ARGS, const int32_t* blockTable, const float* kvDescale, void* workspace,
+                                                int batchSize, int numHeads, int seqLenQ, int numPages, int pageSize, int maxPagesPerSeq,
+                                                int64_t tableStride, int dLatent, int dRope, float scale, bool is_causal, int dtype,
+                                                int kv_dtype, int o_dtype, int numSplits, const fa_strides* sQ, const fa_strides* sKV,
+                                                const fa_strides* sO, void* stream) {
+    if (kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
+                        .kv_dtype = kv_dtype, .kv_descale = kvDescale, FA_SPARSE_FIELDS});
+}
+#undef FA_SPARSE_ARGS
+#undef FA_SPARSE_FIELDS
 
 int flash_attention_mla_append(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, const float* kvDescale, int batchSize,
                                int seqLenNew, int seqLenK, int dLatent, int dRope, int dtype, int kv_dtype, const fa_strides* sC,

@@ -1342,6 +1342,73 @@ int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void
                                          const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
 
 /*
+ * flash_attention_mla_sparse_decode, _paged, _fp8, _paged_fp8 -- SPARSE MLA decode (DeepSeek-V3.2's sparse
+ * attention after its indexer): the four flash_attention_mla_decode* calls in which every query row (b, i) attends the cache rows a
+ * device-side index list names, not the rows 0 .. len.  The signatures are the dense ones with four arguments after kvLens:
+ *   indices        DEVICE int32 [batchSize, seqLenQ, topk], 4-byte aligned (FA_ERR_MISALIGNED), NULL = FA_ERR_NULL_POINTER; all numHeads
+ *                  heads of a query row share its list
+ *   topk           1 .. 2^20 slots per row (FA_ERR_BAD_SHAPE)
+ *   indexStrideB, indexStrideQ   element strides of indices for b and i, the last dimension contiguous: indexStrideQ >= topk and
+ *                  indexStrideB >= 0 (FA_ERR_BAD_STRIDE)
+ * Slot t of row (b, i) names the LOGICAL position p = indices[b, i, t] of sequence b.  It is a key iff 0 <= p < lim, lim = len_b or,
+ * under is_causal, max(len_b - seqLenQ + i + 1, 1); len_b is kvLens[b] read and clamped into [1, capacity] by the kernel, as in the
+ * dense call.  Any other slot -- -1 padding, a position at or beyond the length, a position the mask hides -- is not a key: its cache
+ * row is never read, and in the paged form neither is its table entry.  A position in two slots is two keys.  Order does not matter.
+ *     O[b, h, i] = softmax over the row's keys of (scale * q . KV[p, :576]) * KV[p, :512],   and the LSE over the same scores
+ * A row without any key gives O = 0 and LSE = -inf, under one split and under many.  Paged: p is logical; the kernel reads
+ * blockTable[b, p / pageSize] itself and clamps the entry into [0, numPages).  fp8: the cache form and the one descale of
+ * flash_attention_mla_decode_fp8.  The cache is not copied: the kernel gathers the 32 rows of a tile by their own 64-bit addresses.
+ * Everything else is the dense call's contract, word for word, the order and the codes of the refusals included (the four new ones
+ * stand with their kind: the pointer with the pointers, the alignment after the other arrays', topk with the shapes, the stride
+ * with the strides): no allocation, no synchronisation, capturable -- indices, lengths and the table are read by the kernel, so a
+ * replayed graph sees the values of the moment; numSplits 0 or forced; a NULL workspace only under one split; slabs combined in a fixed
+ * order; hi + lo bf16 weights.  With indices[b, i, :] = 0 .. topk - 1 and topk = capacity = every length the result equals the dense
+ * call's bit for bit under the same split count.
+ *
+ * flash_attention_mla_sparse_plan -- fa_decode_plan of such a call: a unit is (sequence, query row, block of 64 heads), so
+ * rows_per_block = 64, row_blocks = ceil(numHeads / 64), grid = batchSize * seqLenQ * row_blocks * num_splits; the splits divide the
+ * ceil(topk / 32) tiles of the slot range, by the dense rule and its constants (NOT measured for gathered tiles).  The capacity does
+ * not enter.  The workspace of a call is flash_attention_mla_decode_workspace_size(batchSize, numHeads, seqLenQ, 512, num_splits)
+ * with THIS plan's num_splits.
+ *
+ * Not done: seqLenQ above FA_DECODE_MAX_Q (sparse prefill), per-128-column fp8 scales, windows, sinks and tree masks on the sparse
+ * call, a 128-head block, the indexer.
+ */
+int flash_attention_mla_sparse_plan(int batchSize, int numHeads, int seqLenQ, int topk, int dLatent, int dRope,
+                                    int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
+
+int flash_attention_mla_sparse_decode(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens,
+                                      const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ, void* workspace,
+                                      int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                      float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                                      const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_sparse_decode_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                            const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,
+                                            const int32_t* blockTable, void* workspace,
+                                            int batchSize, int numHeads, int seqLenQ,
+                                            int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                            int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                                            const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_sparse_decode_fp8(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens,
+                                          const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,
+                                          const float* kvDescale, void* workspace,
+                                          int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                          float scale, bool is_causal, int dtype, int kv_dtype /* FA_DTYPE_FP8_E4M3 */, int o_dtype,
+                                          int numSplits,
+                                          const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                                const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,
+                                                const int32_t* blockTable, const float* kvDescale, void* workspace,
+                                                int batchSize, int numHeads, int seqLenQ,
+                                                int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                                int dLatent, int dRope, float scale, bool is_causal, int dtype, int kv_dtype,
+                                                int o_dtype, int numSplits,
+                                                const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+/*
  * flash_attention_mla_append, flash_attention_mla_append_paged -- the WRITE side of the MLA latent cache: the new
  * tokens of every sequence become rows of the cache that flash_attention_mla_decode* reads.
  *   Cnew     [batchSize, seqLenNew, 512] bf16: the compressed latent;  Rnew [batchSize, seqLenNew, 64] bf16: the key's rotary part,

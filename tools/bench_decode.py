@@ -3,7 +3,7 @@
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
                                 [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks] [--rope]
-                                [--tree 8,16,64] [--mla]
+                                [--tree 8,16,64] [--mla [--sparse 2048]]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -165,6 +165,18 @@ Each line:
               paged_fp8_ms[page] with --paged.  With --append: one decode step's new token (Sq = 1) written into the fp8 cache at
               position L - 1, append_ms (mla_cache_append) beside torch_append_ms, the torch route that produces the same bytes
               (cat, divide, clamp, convert, indexed copy), alternated; append_same_bytes says that it did.
+              With --sparse TOPK (profiles/mla_sparse_gpu.log): flash_attention_mla_sparse_decode* on the H 16 / 128
+              shapes with TOPK distinct random positions of [0, L) per query row (int32, unsorted), beside three routes, all ALTERNATED in
+              the same windows:
+              sparse_ms       one flash_attention_mla_sparse_decode call (O and the workspace given): [median, min, max]
+              gathered_ms     today's route as a whole: torch.index_select of the rows into [B, TOPK, 576], then
+                              flash_attention_mla_decode on the copy;  vs_gathered = gathered_ms / sparse_ms (medians)
+              dense_ms        flash_attention_mla_decode over the full cache (it computes another result: what sparsity saves)
+              dense_topk_ms   the dense call on a contiguous cache of length TOPK: the price of the gather itself, no bar on it
+              spread          (max - min) / median of the sparse_ms windows;  beats_gathered: sparse max < gathered min
+              max_diff_vs_gathered   the largest difference of one result each (bf16 outputs; the same keys in the same order)
+              --kv fp8: sparse_fp8_ms, the same lists on the quantised cache; --paged a,b: sparse_paged_ms[page] (and
+              sparse_paged_fp8_ms[page]); --splits a,b,c: the forced sweep of the sparse call, one line per (shape, split count).
 """
 import argparse
 import json
@@ -786,9 +798,94 @@ MLA_SHAPES = [  # name, B, H, Sq, L, beside torch: the latent cache is [B, L, 57
 MLA_HBM_TBPS, MLA_MFMA_CYCLES, MLA_LOADED_GHZ, MLA_CUS = 6.3, 16, 1.9, 256
 
 
+def mla_sparse_main(args, fa, dev):
+    """--mla --sparse TOPK: flash_attention_mla_sparse_decode* beside gather + dense, dense, and dense at length TOPK, alternated"""
+    import torch
+    topk = args.sparse
+    pages = [int(x) for x in (args.paged or "").split(",") if x]
+    sweep = [int(n) for n in (args.splits or "").split(",") if n]
+    shapes = [x for x in MLA_SHAPES if x[5] and (not args.shape or x[0] in args.shape)]
+    DL, D = fa.MLA_D_LATENT, fa.MLA_D_LATENT + fa.MLA_D_ROPE
+    stats = lambda w: [round(x, 5) for x in (statistics.median(w), min(w), max(w))]
+    primed = False
+    for name, B, H, Sq, L, _ in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        Q = torch.randn(B, H, Sq, D, device=dev, generator=g).to(torch.bfloat16)
+        KV = torch.randn(B, L, D, device=dev, generator=g).to(torch.bfloat16)
+        lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+        # TOPK distinct positions per query row, unsorted: the first TOPK of a random order of [0, L)
+        idx = torch.rand(B, Sq, L, device=dev, generator=g).argsort(-1)[..., :topk].to(torch.int32).contiguous()
+        flat = (idx[:, 0].long() + torch.arange(B, device=dev)[:, None] * L).reshape(-1)      # rows of KV.view(B L, 576); Sq = 1
+        O = torch.empty(B, H, Sq, DL, device=dev, dtype=torch.bfloat16)
+        plans = [fa.mla_sparse_plan(B, H, Sq, topk), fa.mla_decode_plan(B, H, Sq, L), fa.mla_decode_plan(B, H, Sq, topk)]
+        ws = torch.empty(max(fa.decode_workspace_size(B, H, Sq, DL, max([p["num_splits"] for p in plans] + sweep)), 16), dtype=torch.uint8,
+                         device=dev)
+        short = KV[:, :topk].contiguous()
+        gathered = lambda: fa.flash_attention_mla_decode(Q, torch.index_select(KV.view(B * L, D), 0, flat).view(B, topk, D), None, O=O,
+                                                         workspace=ws)
+        routes = {"sparse_ms": lambda ns=0: fa.flash_attention_mla_sparse_decode(Q, KV, idx, lens, O=O, workspace=ws, num_splits=ns),
+                  "gathered_ms": gathered,
+                  "dense_ms": lambda: fa.flash_attention_mla_decode(Q, KV, lens, O=O, workspace=ws),
+                  "dense_topk_ms": lambda: fa.flash_attention_mla_decode(Q, short, None, O=O, workspace=ws)}
+        if args.kv == "fp8":
+            ds = (KV.float().abs().amax() / 448.0).reshape(1)
+            KV8 = (KV.float() / ds).clamp(-448, 448).to(torch.float8_e4m3fn)
+            routes["sparse_fp8_ms"] = lambda: fa.flash_attention_mla_sparse_decode(Q, KV8, idx, lens, O=O, workspace=ws, kv_descale=ds)
+        for page in pages:
+            if L % page:
+                continue
+            n = L // page
+            perm = torch.randperm(B * n, device=dev, generator=g)
+            pool = torch.empty(B * n, page, D, device=dev, dtype=torch.bfloat16)
+            pool[perm] = KV.view(B * n, page, D)
+            table = perm.view(B, n).to(torch.int32)
+            routes[f"sparse_paged_ms.{page}"] = lambda pool=pool, table=table: fa.flash_attention_mla_sparse_decode_paged(
+                Q, pool, table, idx, lens, O=O, workspace=ws)
+            if args.kv == "fp8":
+                pool8 = torch.empty(B * n, page, D, device=dev, dtype=torch.uint8)
+                pool8[perm] = KV8.view(torch.uint8).view(B * n, page, D)
+                routes[f"sparse_paged_fp8_ms.{page}"] = lambda pool8=pool8.view(torch.float8_e4m3fn), table=table: \
+                    fa.flash_attention_mla_sparse_decode_paged(Q, pool8, table, idx, lens, O=O, workspace=ws, kv_descale=ds)
+        if not primed:   # >= 1 s of calls before the first timed window
+            t = 0.0
+            while t < 1000.0:
+                t += timed(routes["sparse_ms"], 50, 0) * 50
+            primed = True
+        sel_bytes = B * Sq * topk * D * 2
+        base = {"shape": name, "B": B, "H": H, "Sq": Sq, "L": L, "topk": topk, "selected_MB": round(sel_bytes / 1e6, 1)}
+        if sweep:
+            for ns in sweep:
+                w = [timed(lambda: routes["sparse_ms"](ns), args.steps, args.warmup) for _ in range(args.repeats)]
+                print(json.dumps(dict(base, splits=ns, forced=True, sparse_ms=stats(w))), flush=True)
+            continue
+        w = {k: [] for k in routes}
+        for _ in range(args.repeats):
+            for k, fn in routes.items():
+                w[k].append(timed(fn, args.steps, args.warmup))
+        out = dict(base, splits=plans[0]["num_splits"], grid=plans[0]["grid"])
+        for k, v in w.items():
+            key, _, page = k.partition(".")
+            if page:
+                out.setdefault(key, {})[int(page)] = stats(v)
+            else:
+                out[key] = stats(v)
+        ms = statistics.median(w["sparse_ms"])
+        a = routes["sparse_ms"]().float().clone()
+        out.update(selected_tbps=round(sel_bytes / ms / 1e9, 3), vs_gathered=round(statistics.median(w["gathered_ms"]) / ms, 3),
+                   vs_dense=round(statistics.median(w["dense_ms"]) / ms, 3), vs_dense_topk=round(statistics.median(w["dense_topk_ms"]) / ms, 3),
+                   spread=round((max(w["sparse_ms"]) - min(w["sparse_ms"])) / ms, 4),
+                   beats_gathered=bool(max(w["sparse_ms"]) < min(w["gathered_ms"])),
+                   max_diff_vs_gathered=round((a - gathered().float()).abs().max().item(), 5))
+        print(json.dumps(out), flush=True)
+        del routes, Q, KV, O, ws, idx, short, w
+        torch.cuda.empty_cache()
+
+
 def mla_main(args, fa, dev):
     """--mla: flash_attention_mla_decode* beside the same problem from torch ops, alternated"""
     import torch
+    if args.sparse:
+        return mla_sparse_main(args, fa, dev)
     pages = [int(x) for x in (args.paged or "").split(",") if x]
     sweep = [int(n) for n in (args.splits or "").split(",") if n]
     shapes = MLA_SHAPES
@@ -1218,6 +1315,7 @@ def main():
     ap.add_argument("--tree", default=None, help="comma-separated draft-node counts: time flash_attention_tree beside its causal twin, alternated")
     ap.add_argument("--cascade", action="store_true", help="time flash_attention_cascade_decode* beside flash_attention_decode* on a shared prefix, alternated; --splits s:u,...")
     ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
+    ap.add_argument("--sparse", type=int, default=0, help="with --mla: time flash_attention_mla_sparse_decode* at this topk beside gather + dense, alternated")
     ap.add_argument("--mla", action="store_true", help="time flash_attention_mla_decode* beside the same problem from torch ops, alternated; --paged, --splits")
     args = ap.parse_args()
     import torch
