@@ -93,6 +93,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_mla_append", "flash_attention_mla_append_paged",
            "flash_attention_mla_sparse_decode", "flash_attention_mla_sparse_decode_paged", "flash_attention_mla_sparse_decode_fp8",
            "flash_attention_mla_sparse_decode_paged_fp8", "flash_attention_mla_sparse_plan",
+           "flash_attention_mla_index_topk", "flash_attention_mla_index_topk_paged",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
@@ -138,6 +139,8 @@ _MLA_APPEND_SYMBOLS = {False: "flash_attention_mla_append", True: "flash_attenti
 # after ``kvLens``
 _MLA_SPARSE_SYMBOLS = {False: {False: "flash_attention_mla_sparse_decode", True: "flash_attention_mla_sparse_decode_paged"},
                        True: {False: "flash_attention_mla_sparse_decode_fp8", True: "flash_attention_mla_sparse_decode_paged_fp8"}}
+# ... the MLA indexer: _MLA_INDEX_SYMBOLS[paged]
+_MLA_INDEX_SYMBOLS = {False: "flash_attention_mla_index_topk", True: "flash_attention_mla_index_topk_paged"}
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -285,6 +288,11 @@ def lib() -> ctypes.CDLL:
             # ... the latent-cache append: the two new tensors, the cache, kvLens, the table (paged), kvDescale
             fn = getattr(L, _MLA_APPEND_SYMBOLS[paged])
             fn.argtypes = [vp] * 4 + [vp] * paged + [vp] + [i] * 2 + paging(paged) + [i] * 4 + [sp] * 3 + [vp]
+            fn.restype = i
+            # ... the indexer: Qidx, W, the index cache and its scales, kvLens, the table (paged), logits, indices; topk and the three
+            # strides; the shape with (numIndexHeads, dIndex) after the cache geometry
+            fn = getattr(L, _MLA_INDEX_SYMBOLS[paged])
+            fn.argtypes = [vp] * 5 + [vp] * paged + [vp, vp, i, i64, i64, i64, i, i] + paging(paged) + [i, i, b, vp]
             fn.restype = i
         L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_mla_decode_plan.restype = i
@@ -1218,6 +1226,86 @@ def flash_attention_mla_sparse_decode_paged(Q, KV_pool, block_table, indices, kv
         raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
     return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream,
                       kv_descale, indices)
+
+
+# ---- the MLA sparse-attention indexer: fp8 index logits and the top-k positions of every query row ----
+MLA_INDEX_HEADS, MLA_INDEX_D = 64, 128
+
+
+def _mla_index_front(Qidx, W, K, k_scale, block_table, topk, kv_lens, is_causal, logits, indices, return_logits, stream):
+    """Both indexer fronts: the checks of the tensors (the decode fronts' helpers for the table and the lengths), the two outputs
+    allocated unless given, then the entry point of _MLA_INDEX_SYMBOLS."""
+    import torch
+    paged = block_table is not None
+    name = _MLA_INDEX_SYMBOLS[paged]
+    if not (Qidx.is_cuda and W.is_cuda and K.is_cuda and k_scale.is_cuda and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    f8 = (getattr(torch, "float8_e4m3fn", None), torch.uint8)
+    if Qidx.dtype not in f8 or K.dtype not in f8:
+        raise TypeError("Qidx and the index cache must be float8_e4m3fn (or its bytes as uint8)")
+    HD = (MLA_INDEX_HEADS, MLA_INDEX_D)
+    if Qidx.dim() != 4 or tuple(Qidx.shape[2:]) != HD or K.dim() != 3 or K.shape[2] != HD[1] or (not paged and Qidx.shape[0] != K.shape[0]):
+        raise ValueError(f"Qidx must be [B, Sq, {HD[0]}, {HD[1]}] and {'K_pool [P, page' if paged else 'Kidx [B, capacity'}, {HD[1]}]")
+    B, Sq = Qidx.shape[:2]
+    if W.dtype != torch.float32 or tuple(W.shape) != (B, Sq, HD[0]) or W.device != Qidx.device:
+        raise ValueError(f"W must be an fp32 tensor [B, Sq, {HD[0]}] on the device of Qidx")
+    if k_scale.dtype != torch.float32 or tuple(k_scale.shape) != tuple(K.shape[:2]) or k_scale.device != Qidx.device:
+        raise ValueError(f"k_scale must be an fp32 tensor {'[P, page]' if paged else '[B, capacity]'} on the device of Qidx")
+    if not (Qidx.is_contiguous() and W.is_contiguous() and K.is_contiguous() and k_scale.is_contiguous()):
+        raise ValueError("Qidx, W, the index cache and its scales must be dense")
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
+        raise ValueError("topk must be an int >= 1")
+    capacity, tables, geometry = _cache_geometry(K.unsqueeze(1), block_table, B)
+    _check_kv_lens(kv_lens, B)
+    with torch.cuda.device(Qidx.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if logits is None:
+                logits = torch.empty((B, Sq, capacity), dtype=torch.float32, device=Qidx.device)
+            elif logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 3 or tuple(logits.shape[:2]) != (B, Sq) \
+                    or logits.shape[2] < capacity or not logits.is_contiguous():
+                raise ValueError("logits must be a dense fp32 device tensor [B, Sq, >= capacity]")
+            if indices is None:
+                indices = torch.empty((B, Sq, topk), dtype=torch.int32, device=Qidx.device)
+            elif indices.dtype != torch.int32 or not indices.is_cuda or tuple(indices.shape) != (B, Sq, topk) or indices.stride(2) != 1:
+                raise ValueError("indices must be an int32 device tensor [B, Sq, topk] with a contiguous last dimension")
+        # (a stride of a dimension of size 1 may be anything: the kernel multiplies it by 0)
+        rc = getattr(lib(), name)(Qidx.data_ptr(), W.data_ptr(), K.data_ptr(), k_scale.data_ptr(),
+                                  kv_lens.data_ptr() if kv_lens is not None else None, *(t.data_ptr() for t in tables),
+                                  logits.data_ptr(), indices.data_ptr(), topk, logits.shape[2], indices.stride(0) if B > 1 else 0,
+                                  indices.stride(1) if Sq > 1 else topk, B, Sq, *geometry, HD[0], HD[1], bool(is_causal), _stream_ptr(s))
+    _check(rc)
+    return (indices, logits) if return_logits else indices
+
+
+def mla_index_topk(Qidx, W, Kidx, k_scale, topk, kv_lens=None, is_causal=False, logits=None, indices=None, return_logits=False,
+                   stream=None):
+    """The INDEXER of sparse MLA decode (DeepSeek-V3.2's lightning indexer in its fp8 form): the ``indices`` that
+    ``flash_attention_mla_sparse_decode`` takes, computed on the device from the index cache.
+
+    ``Qidx [B, Sq, 64, 128]`` and ``Kidx [B, capacity, 128]`` are ``torch.float8_e4m3fn`` (or their bytes as uint8), ``W [B, Sq, 64]``
+    fp32 (the caller folds Q's scale, the softmax scale and ``64 ** -0.5`` into it; it may be negative), ``k_scale [B, capacity]`` fp32,
+    one per token; all dense.  ``logit[b, i, k] = k_scale[b, k] * sum_h W[b, i, h] * relu(Qidx[b, i, h] . Kidx[b, k])`` for the
+    positions the sparse call's rule shows row ``(b, i)``: ``k < lim``, ``lim = len_b`` (``kv_lens`` read and clamped into
+    ``[1, capacity]`` on the device; None = the capacity) or, under ``is_causal``, ``max(len_b - Sq + i + 1, 1)``.
+
+    Returns ``indices``, int32 ``[B, Sq, topk]``: per row the ``min(topk, lim)`` positions with the largest logits, ties to the lower
+    position, in ascending order, then ``-1`` -- one fully determined tensor, the same bits run to run.  ``return_logits=True``:
+    ``(indices, logits)``, ``logits`` fp32 ``[B, Sq, capacity]`` with the elements at or beyond ``lim`` unspecified.  ``logits`` and
+    ``indices`` may be given (``logits [B, Sq, >= capacity]``, dense); otherwise they are allocated.  1 <= Sq <= FA_DECODE_MAX_Q,
+    1 <= topk <= 2 ** 20.  Capturable; no CPU fallback."""
+    return _mla_index_front(Qidx, W, Kidx, k_scale, None, topk, kv_lens, is_causal, logits, indices, return_logits, stream)
+
+
+def mla_index_topk_paged(Qidx, W, K_pool, k_scale_pool, block_table, topk, kv_lens=None, is_causal=False, logits=None, indices=None,
+                         return_logits=False, stream=None):
+    """``mla_index_topk`` against a PAGED index cache: ``K_pool [P, page, 128]`` (page a power of two >= 16), ``k_scale_pool [P, page]``
+    and ``block_table`` int32 ``[B, max_pages]`` as in ``flash_attention_mla_decode_paged``; entries and lengths are read and clamped by
+    the kernel, and pages without a visible key are not read, nor are their table entries.  The result is the contiguous call's on a
+    gathered copy, bit for bit."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    return _mla_index_front(Qidx, W, K_pool, k_scale_pool, block_table, topk, kv_lens, is_causal, logits, indices, return_logits, stream)
 
 
 def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, stream):

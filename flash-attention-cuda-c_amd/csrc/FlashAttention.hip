@@ -26,6 +26,7 @@
 #include "rope_append.hip.h"
 #include "mla_decode.hip.h"
 #include "mla_sparse.hip.h"
+#include "mla_index.hip.h"
 #include "mla_append.hip.h"
 #include "fwd_mla.hip.h"
 
@@ -1016,6 +1017,62 @@ static int mla_run(MlaCall c) {
                                          : mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
     return mla_combine_launch((unsigned)rows, st, p);
+}
+
+// ---- the MLA sparse-attention indexer: flash_attention_mla_index_topk* (mla_index.hip.h) ----
+// fp8 index logits of 64 index heads x 128 columns against the index cache, then the top-k positions of every query row: the producer of
+// the `indices` the sparse calls above consume, under their visibility rule.  Two launches chained on the stream; nothing is allocated.
+struct MlaIndexCall {
+    const void* Q;
+    const float* W;
+    const void* K;
+    const float* k_scale;
+    const int32_t* kv_lens;
+    float* logits;
+    int32_t* indices;
+    int topk;
+    int64_t logit_stride, index_stride_b, index_stride_q;
+    int B, Sq, capacity, heads, d;
+    bool is_causal;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+// mla_run's order: the pointers, the tensors' 16-byte alignment, the arrays' 4-byte alignment, the paging geometry, the shape (topk with
+// it), the widths, the strides, the grid
+static int mla_index_run(MlaIndexCall c) {
+    using C = MlaIndexCfg;
+    const DecodePaging* pg = c.paging;
+    if (!c.Q || !c.W || !c.K || !c.k_scale || !c.logits || !c.indices || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Q) || !aligned16(c.K) || !aligned16(c.logits)) return FA_ERR_MISALIGNED;
+    KvCache cache{.K = c.K, .V = c.K, .kv_lens = c.kv_lens, .kv_dtype = FA_DTYPE_FP8_E4M3, .capacity = c.capacity, .paging = pg};
+    int rc = cache_check_arrays(cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if (misaligned4(c.W) || misaligned4(c.k_scale) || misaligned4(c.indices)) return FA_ERR_MISALIGNED;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    const int B = c.B, Sq = c.Sq, Sk = cache.capacity;
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || c.heads <= 0 || c.d <= 0) return FA_ERR_BAD_SHAPE;
+    // (one launch holds fewer than 2^32 threads: the top-k's 1024-thread workgroup per row here, the logits' grid below)
+    if (Sq > FA_DECODE_MAX_Q || Sk > (1 << 24) || (int64_t)B * Sq >= (1 << 22)) return FA_ERR_BAD_SHAPE;
+    if (c.topk < 1 || c.topk > MLA_SPARSE_MAX_TOPK) return FA_ERR_BAD_SHAPE;
+    if (c.heads != C::HEADS || c.d != C::D) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (c.logit_stride < Sk || c.index_stride_q < c.topk || c.index_stride_b < 0) return FA_ERR_BAD_STRIDE;
+    const int key_blocks = (Sk + C::KB - 1) / C::KB;
+    if ((int64_t)B * key_blocks >= FA_DECODE_MAX_WORKGROUPS) return FA_ERR_BAD_SHAPE;
+
+    MlaIndexParams p{};
+    p.Q = (const uint8_t*)c.Q; p.W = c.W; p.K = (const uint8_t*)c.K; p.k_scale = c.k_scale;
+    p.kv_lens = c.kv_lens;
+    p.block_table = pg ? pg->table : nullptr;
+    p.logits = c.logits; p.indices = c.indices;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.ls = c.logit_stride; p.isB = c.index_stride_b; p.isQ = c.index_stride_q;
+    p.Sq = Sq; p.cap = Sk; p.topk = c.topk;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.causal = c.is_causal;
+    p.key_blocks = key_blocks;
+    return mla_index_launch(pg != nullptr, (unsigned)(B * key_blocks), (unsigned)(B * Sq), reinterpret_cast<hipStream_t>(c.stream), p);
 }
 
 // ---- the MLA latent-cache append: flash_attention_mla_append* (mla_append.hip.h) ----
@@ -2124,6 +2181,29 @@ int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpoo
 }
 #undef FA_SPARSE_ARGS
 #undef FA_SPARSE_FIELDS
+
+// ---- the MLA sparse-attention indexer ----
+int flash_attention_mla_index_topk(const void* Qidx, const float* W, const void* Kidx, const float* kScale, const int32_t* kvLens,
+                                   float* logits, int32_t* indices, int topk, int64_t logitStride, int64_t indexStrideB,
+                                   int64_t indexStrideQ, int batchSize, int seqLenQ, int seqLenK, int numIndexHeads, int dIndex,
+                                   bool is_causal, void* stream) {
+    return fa::mla_index_run({.Q = Qidx, .W = W, .K = Kidx, .k_scale = kScale, .kv_lens = kvLens, .logits = logits, .indices = indices,
+                              .topk = topk, .logit_stride = logitStride, .index_stride_b = indexStrideB, .index_stride_q = indexStrideQ,
+                              .B = batchSize, .Sq = seqLenQ, .capacity = seqLenK, .heads = numIndexHeads, .d = dIndex,
+                              .is_causal = is_causal, .stream = stream});
+}
+
+int flash_attention_mla_index_topk_paged(const void* Qidx, const float* W, const void* Kpool, const float* kScalePool,
+                                         const int32_t* kvLens, const int32_t* blockTable, float* logits, int32_t* indices, int topk,
+                                         int64_t logitStride, int64_t indexStrideB, int64_t indexStrideQ, int batchSize, int seqLenQ,
+                                         int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int numIndexHeads,
+                                         int dIndex, bool is_causal, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_index_run({.Q = Qidx, .W = W, .K = Kpool, .k_scale = kScalePool, .kv_lens = kvLens, .logits = logits,
+                              .indices = indices, .topk = topk, .logit_stride = logitStride, .index_stride_b = indexStrideB,
+                              .index_stride_q = indexStrideQ, .B = batchSize, .Sq = seqLenQ, .heads = numIndexHeads, .d = dIndex,
+                              .is_causal = is_causal, .paging = &pg, .stream = stream});
+}
 
 int flash_attention_mla_append(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, const float* kvDescale, int batchSize,
                                int seqLenNew, int seqLenK, int dLatent, int dRope, int dtype, int kv_dtype, const fa_strides* sC,

@@ -1372,7 +1372,7 @@ int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void
  * with THIS plan's num_splits.
  *
  * Not done: seqLenQ above FA_DECODE_MAX_Q (sparse prefill), per-128-column fp8 scales, windows, sinks and tree masks on the sparse
- * call, a 128-head block, the indexer.
+ * call, a 128-head block.
  */
 int flash_attention_mla_sparse_plan(int batchSize, int numHeads, int seqLenQ, int topk, int dLatent, int dRope,
                                     int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
@@ -1407,6 +1407,55 @@ int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpoo
                                                 int dLatent, int dRope, float scale, bool is_causal, int dtype, int kv_dtype,
                                                 int o_dtype, int numSplits,
                                                 const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+/*
+ * flash_attention_mla_index_topk, flash_attention_mla_index_topk_paged -- the INDEXER of sparse MLA decode (DESIGN.md section 39;
+ * DeepSeek-V3.2's "lightning indexer" in the model's own fp8 form): the producer of the `indices` flash_attention_mla_sparse_decode*
+ * takes.  Per sequence b, query row i and cache position k
+ *     logit[b, i, k] = kScale[b, k] * sum_{h < 64} W[b, i, h] * max(0, sum_{d < 128} Qidx[b, i, h, d] * Kidx[b, k, d])
+ *   Qidx     [batchSize, seqLenQ, 64, 128] e4m3fn bytes, dense, 16-byte aligned
+ *   W        [batchSize, seqLenQ, 64] fp32, dense, 4-byte aligned: the caller folds Q's scale, the softmax scale and 64^-0.5 into
+ *            it; it may be negative
+ *   Kidx     [batchSize, seqLenK, 128] e4m3fn bytes, dense, 16-byte aligned; kScale [batchSize, seqLenK] fp32, one per token
+ *   paged    Kpool [numPages, pageSize, 128] and kScalePool [numPages, pageSize] behind blockTable, with pageSize, maxPagesPerSeq and
+ *            tableStride as in flash_attention_mla_decode_paged: pages a power of two >= 16, the capacity maxPagesPerSeq * pageSize,
+ *            entries read and clamped into [0, numPages) by the kernel, page bases 64-bit (a pool may exceed 2^32 bytes)
+ *   numIndexHeads, dIndex   only (64, 128); anything else FA_ERR_UNSUPPORTED_DHEAD
+ *   1 <= seqLenQ <= FA_DECODE_MAX_Q, 1 <= topk <= 2^20, capacity <= 2^24, batchSize * seqLenQ < 2^22 (FA_ERR_BAD_SHAPE)
+ * Visible positions are the sparse call's, so the output feeds it unchanged: len_b = kvLens[b] read and clamped into [1, capacity] by
+ * the kernels (NULL = the capacity); lim_i = len_b or, under is_causal, max(len_b - seqLenQ + i + 1, 1).
+ * Both outputs are the caller's; nothing is allocated:
+ *   logits   fp32 [batchSize, seqLenQ, logitStride], logitStride >= capacity (FA_ERR_BAD_STRIDE), 16-byte aligned base.  Element
+ *            (b, i, k), k < lim_i, is the logit above with -0 stored as +0; elements at or beyond lim_i are unspecified (not written).
+ *            A documented output, and the input of the selection.
+ *   indices  int32 [batchSize, seqLenQ, topk], element strides indexStrideB >= 0 and indexStrideQ >= topk (FA_ERR_BAD_STRIDE),
+ *            4-byte aligned.  Row (b, i) holds the n = min(topk, lim_i) positions k < lim_i with the largest logits, ties to the lower
+ *            position, written in ASCENDING order, then topk - n entries of -1: one fully determined tensor given the logits, the
+ *            same bits run to run.  A NaN logit below the limit is data: its rank is unspecified, and the row still holds exactly n
+ *            distinct in-range positions.
+ * Conventions of the MLA decode calls: validated before any launch in their order and with their codes -- NULL Qidx, W, Kidx, kScale,
+ * logits, indices or (paged) blockTable FA_ERR_NULL_POINTER; then Qidx, Kidx, logits 16-byte aligned; then kvLens, blockTable, W, kScale,
+ * indices 4-byte aligned (FA_ERR_MISALIGNED); the paging geometry; the shape with topk; the widths; the strides.  No host
+ * synchronisation, no global atomics, capturable: lengths and the table are read on the device, so a replayed graph sees the values of
+ * the moment.  Rows and pages at or beyond every length may hold any byte and any scale (NaN included) and are not read; the table
+ * entries of unread pages may hold anything.  Two launches chained on the stream: the logits (a workgroup per 256 keys of a sequence;
+ * the index cache is read once whatever seqLenQ is) and a radix select per (b, i) row.
+ *
+ * Not done: the write side of the index cache (quantising append, Hadamard rotation), bf16 index tensors, other head counts,
+ * seqLenQ above FA_DECODE_MAX_Q (the prefill indexer), a ragged form, a plan call, strided inputs, a first histogram fused into the
+ * logits kernel.
+ */
+int flash_attention_mla_index_topk(const void* Qidx, const float* W, const void* Kidx, const float* kScale, const int32_t* kvLens,
+                                   float* logits, int32_t* indices, int topk, int64_t logitStride, int64_t indexStrideB,
+                                   int64_t indexStrideQ, int batchSize, int seqLenQ, int seqLenK, int numIndexHeads, int dIndex,
+                                   bool is_causal, void* stream);
+
+int flash_attention_mla_index_topk_paged(const void* Qidx, const float* W, const void* Kpool, const float* kScalePool,
+                                         const int32_t* kvLens, const int32_t* blockTable, float* logits, int32_t* indices, int topk,
+                                         int64_t logitStride, int64_t indexStrideB, int64_t indexStrideQ,
+                                         int batchSize, int seqLenQ,
+                                         int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                         int numIndexHeads, int dIndex, bool is_causal, void* stream);
 
 /*
  * flash_attention_mla_append, flash_attention_mla_append_paged -- the WRITE side of the MLA latent cache: the new

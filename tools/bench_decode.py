@@ -3,7 +3,7 @@
 
   python3 tools/bench_decode.py [--steps N] [--warmup W] [--repeats R] [--shape NAME ...] [--splits 1,2,4,...] [--no-cross]
                                 [--paged 16,128,256] [--kv fp8] [--window 128,4096] [--append] [--extend | --varlen] [--sinks] [--rope]
-                                [--tree 8,16,64] [--mla [--sparse 2048]]
+                                [--tree 8,16,64] [--mla [--sparse 2048 | --index 2048]]
 
 Shapes (bf16 in / bf16 out, d = 128 unless named, Sq new rows against a cache of capacity Sk):
   single_32k B1 H32 Hkv8 Sq1 Sk32768      single_128k B1 H32 Hkv8 Sq1 Sk131072    batch8_8k B8 H32 Hkv8 Sq1 Sk8192
@@ -177,6 +177,15 @@ Each line:
               max_diff_vs_gathered   the largest difference of one result each (bf16 outputs; the same keys in the same order)
               --kv fp8: sparse_fp8_ms, the same lists on the quantised cache; --paged a,b: sparse_paged_ms[page] (and
               sparse_paged_fp8_ms[page]); --splits a,b,c: the forced sweep of the sparse call, one line per (shape, split count).
+              With --index TOPK (profiles/mla_index_gpu.log): the indexer, mla_index_topk, on the (B, L) of the
+              sparse shapes (H does not enter: 64 index heads x 128 columns, Sq = 1, every sequence full), beside the torch route to the
+              same indices, ALTERNATED in the same windows:
+              index_ms        one mla_index_topk call (logits and indices given): [median, min, max]
+              torch_index_ms  bf16 matmul of the dequantised tensors, relu, the weighted sum over heads, the scales, torch.topk, sort
+              logits_ms       the call with topk = L: the logits kernel and a selection that only writes 0 .. L - 1
+              topk_ms         index_ms - logits_ms (medians): what the radix select adds
+              kv_tbps         the index cache's bytes (B L 132) / logits_ms;  spread = (max - min) / median of the index_ms windows
+              beats_torch     index max < torch min;  same_indices: both routes picked the same positions for one result each
 """
 import argparse
 import json
@@ -881,11 +890,68 @@ def mla_sparse_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def mla_index_main(args, fa, dev):
+    """--mla --index TOPK: mla_index_topk beside the torch route to the same indices, alternated"""
+    import torch
+    topk = args.index
+    seen, shapes = set(), []
+    for name, B, _, Sq, L, beside in MLA_SHAPES:      # the sparse shapes' distinct (B, L): H does not enter
+        if beside and (B, L) not in seen and (not args.shape or name in args.shape):
+            seen.add((B, L))
+            shapes.append((name.split("_", 1)[1], B, Sq, L))
+    stats = lambda w: [round(x, 5) for x in (statistics.median(w), min(w), max(w))]
+    primed = False
+    for name, B, Sq, L in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        Q8 = torch.randn(B, Sq, 64, 128, device=dev, generator=g).to(torch.float8_e4m3fn)
+        K8 = torch.randn(B, L, 128, device=dev, generator=g).to(torch.float8_e4m3fn)
+        W = torch.randn(B, Sq, 64, device=dev, generator=g) * 0.125
+        ks = torch.rand(B, L, device=dev, generator=g) + 0.5
+        lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+        logits = torch.empty(B, Sq, L, device=dev)
+        idx, idx_all = (torch.empty(B, Sq, n, dtype=torch.int32, device=dev) for n in (topk, L))
+        Qb, Kb, Wb = Q8.to(torch.bfloat16).view(B, Sq * 64, 128), K8.to(torch.bfloat16).transpose(1, 2), W.to(torch.bfloat16)
+
+        def torch_route():
+            s = torch.relu_(torch.matmul(Qb, Kb)).view(B, Sq, 64, L)
+            lg = torch.einsum("bihk,bih->bik", s, Wb).float() * ks[:, None]
+            return torch.topk(lg, topk, dim=-1).indices.sort(-1).values
+
+        routes = {"index_ms": lambda: fa.mla_index_topk(Q8, W, K8, ks, topk, lens, logits=logits, indices=idx),
+                  "torch_index_ms": torch_route,
+                  "logits_ms": lambda: fa.mla_index_topk(Q8, W, K8, ks, L, lens, logits=logits, indices=idx_all)}
+        if not primed:   # >= 1 s of calls before the first timed window
+            t = 0.0
+            while t < 1000.0:
+                t += timed(routes["index_ms"], 50, 0) * 50
+            primed = True
+        w = {k: [] for k in routes}
+        for _ in range(args.repeats):
+            for k, fn in routes.items():
+                w[k].append(timed(fn, args.steps, args.warmup))
+        ms, lms = statistics.median(w["index_ms"]), statistics.median(w["logits_ms"])
+        # the torch route rounds to bf16, so its order may differ near ties: compare against the selection of the call's own logits
+        mine = routes["index_ms"]().long()
+        own = torch.topk(logits, topk, dim=-1).indices.sort(-1).values
+        out = {"shape": name, "B": B, "Sq": Sq, "L": L, "topk": topk, **{k: stats(v) for k, v in w.items()},
+               "topk_ms": round(ms - lms, 5), "kv_tbps": round(B * L * 132 / lms / 1e9, 3),
+               "vs_torch": round(statistics.median(w["torch_index_ms"]) / ms, 3),
+               "spread": round((max(w["index_ms"]) - min(w["index_ms"])) / ms, 4),
+               "beats_torch": bool(max(w["index_ms"]) < min(w["torch_index_ms"])),
+               "same_indices": bool(torch.equal(mine, own)),
+               "overlap_with_torch": round((mine[..., None] == torch_route()[..., None, :]).any(-1).float().mean().item(), 4)}
+        print(json.dumps(out), flush=True)
+        del routes, Q8, K8, Qb, Kb, logits, idx, idx_all, w
+        torch.cuda.empty_cache()
+
+
 def mla_main(args, fa, dev):
     """--mla: flash_attention_mla_decode* beside the same problem from torch ops, alternated"""
     import torch
     if args.sparse:
         return mla_sparse_main(args, fa, dev)
+    if args.index:
+        return mla_index_main(args, fa, dev)
     pages = [int(x) for x in (args.paged or "").split(",") if x]
     sweep = [int(n) for n in (args.splits or "").split(",") if n]
     shapes = MLA_SHAPES
@@ -1316,6 +1382,7 @@ def main():
     ap.add_argument("--cascade", action="store_true", help="time flash_attention_cascade_decode* beside flash_attention_decode* on a shared prefix, alternated; --splits s:u,...")
     ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
     ap.add_argument("--sparse", type=int, default=0, help="with --mla: time flash_attention_mla_sparse_decode* at this topk beside gather + dense, alternated")
+    ap.add_argument("--index", type=int, default=0, help="with --mla: time mla_index_topk at this topk beside the torch route to the same indices, alternated")
     ap.add_argument("--mla", action="store_true", help="time flash_attention_mla_decode* beside the same problem from torch ops, alternated; --paged, --splits")
     args = ap.parse_args()
     import torch
