@@ -55,6 +55,8 @@ build/obj/inst_mla_sparse.o: HIPFLAGS += $(MFMA_VGPR)
 build/obj/inst_mla_sparse_fp8.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 # the MLA indexer (mla_index.hip.h): no packed fp32 arithmetic in its ReLU / weight / head-sum epilogue
 build/obj/inst_mla_index.o: HIPFLAGS += $(NO_PK_F32)
+# the MLA index-cache append (mla_index_append.hip.h): its rotation, transform and scales are pinned to the bit in plain fp32
+build/obj/inst_mla_index_append.o: HIPFLAGS += $(NO_PK_F32)
 tests/fa_tune tests/fa_tune_c128 tests/fa_tune_seam tests/fa_tune_tail: HIPFLAGS += $(MFMA_VGPR)
 # the chunked-prefill units of the split-KV kernel (the extend_* names of SPLIT_UNITS, and the shared_* ones, which are built at the same RT; decode_bf16.hip.h with RT = 4 at d = 128: four 16-row
 # tiles per wave, launch bounds 256, 1; the decode units, RT = 1, are built without the flag): 206 accumulation registers in the default
@@ -158,7 +160,7 @@ asan: asan-host oracle
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
 build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s build/asm/inst_mla_sparse.s: HIPFLAGS += $(MFMA_VGPR)
 build/asm/inst_bf16_mla.s build/asm/inst_mla_decode_fp8.s build/asm/inst_mla_sparse_fp8.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
-build/asm/inst_mla_append.s build/asm/inst_mla_index.s: HIPFLAGS += $(NO_PK_F32)
+build/asm/inst_mla_append.s build/asm/inst_mla_index.s build/asm/inst_mla_index_append.s: HIPFLAGS += $(NO_PK_F32)
 define ASM_RECIPE
 @mkdir -p build/asm
 $(HIPCC) $(HIPFLAGS) $(1) -S --cuda-device-only -o $@.tmp $<

@@ -37,6 +37,9 @@ entry points for that path:
 * ``flash_attention_cascade_decode(Q, K_shared, V_shared, K, V, shared_len, kv_lens)`` / ``flash_attention_cascade_decode_paged(Q,
   K_pool, V_pool, shared_table, block_table, shared_len, kv_lens)`` -- shared-prefix (cascade) decode: one prefix every sequence of the
   batch sees in full, read once per row block of the whole batch, then each sequence's own suffix (``cascade_plan``).
+* ``mla_index_append(k_new, Kidx, k_scale, kv_lens, q=, w=)`` / ``mla_index_append_paged(..., block_table, ...)`` -- the write side
+  of the MLA indexer's cache: rotary, a 128-point Hadamard transform, one scale per row and the e4m3fn codes, for the step's index
+  keys (into the cache) and queries (into the ``Qidx`` / ``W`` that ``mla_index_topk`` takes), one launch.
 * ``multi_head_attention(Q, K, V, num_heads)`` -- the reference's Python oracle API
   (``check.py:4-25``): ``(B, S, d_model)`` tensors; the ``(B,S,H,d_k) -> (B,H,S,d_k)`` transposes of
   ``check.py:14-16,24`` are done by strides inside the kernel, not by copies.
@@ -49,6 +52,7 @@ the package is loaded through ``__graft_entry__.load_package()`` under the modul
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +98,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_mla_sparse_decode", "flash_attention_mla_sparse_decode_paged", "flash_attention_mla_sparse_decode_fp8",
            "flash_attention_mla_sparse_decode_paged_fp8", "flash_attention_mla_sparse_plan",
            "flash_attention_mla_index_topk", "flash_attention_mla_index_topk_paged",
+           "flash_attention_mla_index_append", "flash_attention_mla_index_append_paged",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
@@ -141,6 +146,9 @@ _MLA_SPARSE_SYMBOLS = {False: {False: "flash_attention_mla_sparse_decode", True:
                        True: {False: "flash_attention_mla_sparse_decode_fp8", True: "flash_attention_mla_sparse_decode_paged_fp8"}}
 # ... the MLA indexer: _MLA_INDEX_SYMBOLS[paged]
 _MLA_INDEX_SYMBOLS = {False: "flash_attention_mla_index_topk", True: "flash_attention_mla_index_topk_paged"}
+# ... and the write side of its cache: _MLA_INDEX_APPEND_SYMBOLS[paged]
+_MLA_INDEX_APPEND_SYMBOLS = {False: "flash_attention_mla_index_append", True: "flash_attention_mla_index_append_paged"}
+FA_INDEX_SCALE_F32, FA_INDEX_SCALE_POW2 = 0, 1     # scaleFmt: the row's scale as computed, or rounded up to a power of two (ue8m0)
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
                  ("extend", True): ("flash_attention_extend_varlen_plan", "flash_attention_extend_varlen_plan_window")}
@@ -293,6 +301,11 @@ def lib() -> ctypes.CDLL:
             # strides; the shape with (numIndexHeads, dIndex) after the cache geometry
             fn = getattr(L, _MLA_INDEX_SYMBOLS[paged])
             fn.argtypes = [vp] * 5 + [vp] * paged + [vp, vp, i, i64, i64, i64, i, i] + paging(paged) + [i, i, b, vp]
+            fn.restype = i
+            # ... the index-cache append: Knew, the cache and its scales, Qraw, Wraw, Qidx, W, cosSin, kvLens, the table (paged); the
+            # shape; rotDim, maxPos, interleaved, scaleFmt, wScale; two strides
+            fn = getattr(L, _MLA_INDEX_APPEND_SYMBOLS[paged])
+            fn.argtypes = [vp] * 9 + [vp] * paged + [i, i] + paging(paged) + [i] * 6 + [f, sp, sp, vp]
             fn.restype = i
         L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_mla_decode_plan.restype = i
@@ -1364,6 +1377,114 @@ def mla_cache_append_paged(c_kv, k_pe, KV_pool, block_table, kv_lens=None, kv_de
     ``flash_attention_mla_decode_paged``.  Only the entries of pages that receive a row are read; an entry outside [0, P) is NOT
     clamped: the rows that would go to that page are skipped and nothing else is touched.  Returns None."""
     _mla_append_front("mla_cache_append_paged", c_kv, k_pe, KV_pool, block_table, kv_lens, kv_descale, stream)
+
+
+def _mla_index_append_front(name, k_new, K, k_scale, block_table, kv_lens, q, w, cos_sin, interleaved, scale_fmt, w_scale, Qidx, W, stream):
+    """Both mla_index_append fronts: the tensor checks, the bounds of Sq, Qidx and W allocated unless given, and the entry point of
+    _MLA_INDEX_APPEND_SYMBOLS"""
+    import torch
+    paged = block_table is not None
+    layout = "K_pool [P, page, 128]" if paged else "Kidx [B, capacity, 128]"
+    if not (getattr(k_new, "is_cuda", False) and getattr(K, "is_cuda", False) and getattr(k_scale, "is_cuda", False)
+            and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    H, D = MLA_INDEX_HEADS, MLA_INDEX_D
+    if k_new.dim() != 3 or K.dim() != 3 or k_new.shape[2] != D or K.shape[2] != D or (not paged and K.shape[0] != k_new.shape[0]):
+        raise ValueError(f"k_new must be [B, Sq, {D}] and {layout}")
+    f8 = (getattr(torch, "float8_e4m3fn", None), torch.uint8)
+    if k_new.dtype != torch.bfloat16 or K.dtype not in f8:
+        raise TypeError(f"k_new must be bfloat16 and {layout.split()[0]} float8_e4m3fn (or its bytes as uint8)")
+    if k_scale.dtype != torch.float32 or tuple(k_scale.shape) != tuple(K.shape[:2]) or k_scale.device != K.device:
+        raise ValueError(f"k_scale must be an fp32 tensor {'[P, page]' if paged else '[B, capacity]'} on the device of the cache")
+    if k_new.device != K.device:
+        raise ValueError("k_new and the cache must be on one device")
+    if not (K.is_contiguous() and k_scale.is_contiguous()) or k_new.stride(2) != 1:
+        raise ValueError("the index cache and its scales must be dense, and the last dimension of k_new contiguous")
+    B, Sq, _ = k_new.shape
+    capacity, tables, geometry = _cache_geometry(K.unsqueeze(1), block_table, B)
+    if Sq < 1 or Sq > capacity:
+        raise ValueError(f"Sq = {Sq} new rows: must be 1 .. the capacity ({capacity})")
+    _check_kv_lens(kv_lens, B)
+    if (q is None) != (w is None) or (q is None and (Qidx is not None or W is not None)):
+        raise ValueError("q and w go together, and Qidx / W only with them")
+    if q is not None:
+        if not (getattr(q, "is_cuda", False) and getattr(w, "is_cuda", False)):
+            raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+        if q.dtype != torch.bfloat16 or tuple(q.shape) != (B, Sq, H, D) or q.stride(3) != 1 or q.device != K.device:
+            raise ValueError(f"q must be a bfloat16 tensor [B, Sq, {H}, {D}] on the device of the cache, its last dimension contiguous")
+        if w.dtype != torch.float32 or tuple(w.shape) != (B, Sq, H) or not w.is_contiguous() or w.device != K.device:
+            raise ValueError(f"w must be a dense fp32 tensor [B, Sq, {H}] on the device of the cache")
+    if scale_fmt not in ("f32", "pow2"):
+        raise ValueError('scale_fmt must be "f32" or "pow2"')
+    w_scale = float(w_scale)
+    if not math.isfinite(w_scale):
+        raise ValueError("w_scale must be finite")
+    max_pos = rot_dim = 0
+    if cos_sin is not None:
+        t = cos_sin
+        if getattr(t, "dtype", None) != torch.float32 or not t.is_cuda or t.device != K.device or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError("cos_sin must be a dense fp32 tensor [max_pos, rot_dim] on the device of the cache")
+        max_pos, rot_dim = t.shape
+        if rot_dim % 16 or not 16 <= rot_dim <= D or max_pos < capacity:
+            raise ValueError(f"cos_sin [max_pos, rot_dim]: rot_dim a multiple of 16 in 16 .. {D}, max_pos at least the capacity ({capacity})")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(K.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if q is not None:
+            with torch.cuda.stream(s):
+                if Qidx is None:
+                    Qidx = torch.empty((B, Sq, H, D), dtype=f8[0] or torch.uint8, device=K.device)
+                elif not getattr(Qidx, "is_cuda", False) or Qidx.dtype not in f8 or tuple(Qidx.shape) != (B, Sq, H, D) \
+                        or not Qidx.is_contiguous() or Qidx.device != K.device:
+                    raise ValueError(f"Qidx must be a dense float8_e4m3fn device tensor [B, Sq, {H}, {D}]")
+                if W is None:
+                    W = torch.empty((B, Sq, H), dtype=torch.float32, device=K.device)
+                elif not getattr(W, "is_cuda", False) or W.dtype != torch.float32 or tuple(W.shape) != (B, Sq, H) or not W.is_contiguous() \
+                        or W.device != K.device:
+                    raise ValueError(f"W must be a dense fp32 device tensor [B, Sq, {H}]")
+        sk = FaStrides(k_new.stride(0), 0, k_new.stride(1))
+        sq = FaStrides(q.stride(0), q.stride(2), q.stride(1)) if q is not None else None
+        rc = getattr(lib(), _MLA_INDEX_APPEND_SYMBOLS[paged])(
+            k_new.data_ptr(), K.data_ptr(), k_scale.data_ptr(), ptr(q), ptr(w), ptr(Qidx), ptr(W), ptr(cos_sin), ptr(kv_lens),
+            *map(ptr, tables), B, Sq, *geometry, H, D, rot_dim, max_pos, int(bool(interleaved)),
+            FA_INDEX_SCALE_POW2 if scale_fmt == "pow2" else FA_INDEX_SCALE_F32, w_scale, ctypes.byref(sk),
+            ctypes.byref(sq) if sq is not None else None, _stream_ptr(s))
+    _check(rc)
+    return (Qidx, W) if q is not None else None
+
+
+def mla_index_append(k_new, Kidx, k_scale, kv_lens=None, q=None, w=None, cos_sin=None, interleaved=False, scale_fmt="pow2", w_scale=1.0,
+                     Qidx=None, W=None, stream=None):
+    """The WRITE side of the index cache ``mla_index_topk`` reads (DeepSeek-V3.2's indexer): one launch rotates, Hadamard-transforms
+    and quantises the step's raw bf16 index projections.
+
+    ``k_new`` bf16 ``[B, Sq, 128]`` (a strided slice of a fused projection is accepted) becomes rows of ``Kidx [B, capacity, 128]``
+    (``torch.float8_e4m3fn`` or its bytes) and one fp32 scale each in ``k_scale [B, capacity]``, in place.  Positions as for
+    ``mla_cache_append``: ``kv_lens[b]`` already counts the new rows, row i goes to ``min(kv_lens[b], capacity) - Sq + i`` when that is
+    >= 0, and ``kv_lens[b] <= 0`` writes nothing.  With ``q`` bf16 ``[B, Sq, 64, 128]`` (strided views accepted) and ``w`` fp32
+    ``[B, Sq, 64]`` the same is done to the index queries: returns ``(Qidx, W)``, the indexer's dense inputs, ``W = (w * q_scale) *
+    w_scale`` with ``w_scale`` the model's ``softmax_scale * 64 ** -0.5``; every query row is written, rotated at
+    ``max(clamp(kv_lens[b], 1, capacity) - Sq + i, 0)``.  Without ``q``: the K side alone (a cache fill), returns None.
+
+    Per row of 128: the rotary embedding of ``rope_cache_append`` under ``cos_sin`` (``rope_table``; None = the rows are already
+    rotated) and ``interleaved``, rounded to bf16; a 128-point Walsh-Hadamard transform in fp32 times ``2 ** -3.5``, rounded to bf16;
+    ``scale = max(amax, 1e-4) / 448`` as computed (``scale_fmt="f32"``) or rounded up to a power of two (``"pow2"``, the model's
+    ue8m0 form); the e4m3fn codes of the row over its scale.  Pinned to the bit: include/flash_attention.h.  Lengths and the table are
+    read by the kernel, so ``kv_lens += Sq; mla_index_append; mla_index_topk; flash_attention_mla_sparse_decode`` is one graph.
+    Asynchronous on ``stream`` (default: torch's current stream).  No CPU fallback."""
+    return _mla_index_append_front("mla_index_append", k_new, Kidx, k_scale, None, kv_lens, q, w, cos_sin, interleaved, scale_fmt, w_scale,
+                                   Qidx, W, stream)
+
+
+def mla_index_append_paged(k_new, K_pool, k_scale_pool, block_table, kv_lens=None, q=None, w=None, cos_sin=None, interleaved=False,
+                           scale_fmt="pow2", w_scale=1.0, Qidx=None, W=None, stream=None):
+    """``mla_index_append`` into a PAGED index cache: ``K_pool [P, page, 128]``, ``k_scale_pool [P, page]`` and ``block_table`` int32
+    ``[B, max_pages]`` as in ``mla_index_topk_paged``.  Only the entries of pages that receive a row are read; an entry outside [0, P)
+    is NOT clamped: the rows that would go to that page are skipped and nothing else is touched (the query rows are still written)."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages] with a contiguous last dimension")
+    return _mla_index_append_front("mla_index_append_paged", k_new, K_pool, k_scale_pool, block_table, kv_lens, q, w, cos_sin, interleaved,
+                                   scale_fmt, w_scale, Qidx, W, stream)
 
 
 def mla_prefill_plan(B, H, Sq, Sk, is_causal=False, o_dtype=FA_DTYPE_BF16, flags=0, d_qk=192, d_v=128):

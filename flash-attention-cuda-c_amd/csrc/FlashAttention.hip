@@ -28,6 +28,7 @@
 #include "mla_sparse.hip.h"
 #include "mla_index.hip.h"
 #include "mla_append.hip.h"
+#include "mla_index_append.hip.h"
 #include "fwd_mla.hip.h"
 
 namespace fa {
@@ -1136,6 +1137,76 @@ static int mla_append_run(const MlaAppendCall& c) {
     return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
 }
 
+// ---- the MLA index-cache append: flash_attention_mla_index_append* (mla_index_append.hip.h) ----
+// mla_append_run's ladder on the index cache (dense rows of 128 bytes and their fp32 scales, as mla_index_run reads them), with the
+// optional Q side and rope_append's table rules.  One launch: a workgroup per (sequence, block of 64 key positions), then one per query row
+struct MlaIndexAppendCall {
+    const void* Knew;
+    void* K;
+    float* k_scale;
+    const void* Qraw;
+    const float* Wraw;
+    void* Qidx;
+    float* W;
+    const float* cos_sin;
+    const int32_t* kv_lens;
+    int B, Sq, capacity, heads, d, rot_dim, max_pos, interleaved, scale_fmt;
+    float w_scale;
+    const fa_strides *sKnew, *sQraw;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+static int mla_index_append_run(const MlaIndexAppendCall& c) {
+    using C = MlaIndexAppendCfg;
+    const DecodePaging* pg = c.paging;
+    if (!c.Knew || !c.K || !c.k_scale || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    const bool q_side = c.Qraw != nullptr;
+    if ((c.Wraw != nullptr) != q_side || (c.Qidx != nullptr) != q_side || (c.W != nullptr) != q_side) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Knew) || !aligned16(c.K) || !aligned16(c.Qraw) || !aligned16(c.Qidx) || !aligned16(c.cos_sin)) return FA_ERR_MISALIGNED;
+    KvCache cache{.K = c.K, .V = c.K, .kv_lens = c.kv_lens, .kv_dtype = FA_DTYPE_FP8_E4M3, .capacity = c.capacity, .paging = pg};
+    int rc = cache_check_arrays(cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if (misaligned4(c.k_scale) || misaligned4(c.Wraw) || misaligned4(c.W)) return FA_ERR_MISALIGNED;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    const int B = c.B, Sq = c.Sq, Sk = cache.capacity;
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || c.heads <= 0 || c.d <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || Sq > Sk || B > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.heads != C::HEADS || c.d != C::D) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (c.cos_sin) {
+        if (c.rot_dim < 16 || c.rot_dim > C::D || c.rot_dim % 16) return FA_ERR_BAD_SHAPE;
+        if (c.max_pos < Sk) return FA_ERR_BAD_SHAPE;   // every position the kernel can form lies in the table
+    }
+    if (c.interleaved != 0 && c.interleaved != 1) return FA_ERR_BAD_FLAGS;
+    if (c.scale_fmt != FA_INDEX_SCALE_F32 && c.scale_fmt != FA_INDEX_SCALE_POW2) return FA_ERR_BAD_FLAGS;
+    if (!std::isfinite(c.w_scale)) return FA_ERR_BAD_SCALE;
+    fa_strides tK{};                                   // strideH of Knew is not read
+    if (c.sKnew) tK = fa_strides{c.sKnew->strideB, 0, c.sKnew->strideS};
+    if (!strides_ok(c.sKnew ? &tK : nullptr, 2, C::D) || !strides_ok(q_side ? c.sQraw : nullptr, 2, C::D)) return FA_ERR_BAD_STRIDE;
+    const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
+    const int64_t k_blocks = (int64_t)B * row_blocks, grid = k_blocks + (q_side ? (int64_t)B * Sq : 0);
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    MlaIndexAppendParams p{};
+    p.Knew = (const __bf16*)c.Knew; p.K = (uint8_t*)c.K; p.k_scale = c.k_scale;
+    p.Qraw = (const __bf16*)c.Qraw; p.Wraw = c.Wraw; p.Qidx = (uint8_t*)c.Qidx; p.W = c.W;
+    p.cos_sin = c.cos_sin; p.kv_lens = c.kv_lens;
+    p.block_table = pg ? pg->table : nullptr;
+    p.knB = c.sKnew ? tK.strideB : (int64_t)Sq * C::D;
+    p.knS = c.sKnew ? tK.strideS : C::D;
+    p.qB = c.sQraw ? c.sQraw->strideB : (int64_t)Sq * C::HEADS * C::D;   // dense Qraw is [B, Sq, 64, 128]
+    p.qH = c.sQraw ? c.sQraw->strideH : C::D;
+    p.qS = c.sQraw ? c.sQraw->strideS : C::HEADS * C::D;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.w_scale = c.w_scale;
+    p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks; p.k_blocks = (int)k_blocks;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.rot = c.cos_sin ? c.rot_dim : 0; p.interleaved = c.interleaved; p.pow2 = c.scale_fmt == FA_INDEX_SCALE_POW2;
+    const Kernel k = mla_index_append_kernel_of(pg != nullptr);
+    return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
+}
+
 // ---- MLA prefill (fwd_mla.hip.h): bf16 Q, K [.., 192] and V, O [.., 128] ----
 struct MlaPrefillCall {
     const void *Q, *K, *V;
@@ -2221,6 +2292,29 @@ int flash_attention_mla_append_paged(const void* Cnew, const void* Rnew, void* K
     return fa::mla_append_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KVpool, .kv_lens = kvLens, .kv_descale = kvDescale, .B = batchSize,
                                .Sq = seqLenNew, .d_latent = dLatent, .d_rope = dRope, .dtype = dtype, .kv_dtype = kv_dtype, .sC = sC,
                                .sR = sR, .sKV = sKV, .paging = &pg, .stream = stream});
+}
+
+// ---- the MLA index-cache append ----
+int flash_attention_mla_index_append(const void* Knew, void* Kidx, float* kScale, const void* Qraw, const float* Wraw, void* Qidx, float* W,
+                                     const float* cosSin, const int32_t* kvLens, int batchSize, int seqLenNew, int seqLenK,
+                                     int numIndexHeads, int dIndex, int rotDim, int maxPos, int interleaved, int scaleFmt, float wScale,
+                                     const fa_strides* sKnew, const fa_strides* sQraw, void* stream) {
+    return fa::mla_index_append_run({.Knew = Knew, .K = Kidx, .k_scale = kScale, .Qraw = Qraw, .Wraw = Wraw, .Qidx = Qidx, .W = W,
+                                     .cos_sin = cosSin, .kv_lens = kvLens, .B = batchSize, .Sq = seqLenNew, .capacity = seqLenK,
+                                     .heads = numIndexHeads, .d = dIndex, .rot_dim = rotDim, .max_pos = maxPos, .interleaved = interleaved,
+                                     .scale_fmt = scaleFmt, .w_scale = wScale, .sKnew = sKnew, .sQraw = sQraw, .stream = stream});
+}
+
+int flash_attention_mla_index_append_paged(const void* Knew, void* Kpool, float* kScalePool, const void* Qraw, const float* Wraw,
+                                           void* Qidx, float* W, const float* cosSin, const int32_t* kvLens, const int32_t* blockTable,
+                                           int batchSize, int seqLenNew, int numPages, int pageSize, int maxPagesPerSeq,
+                                           int64_t tableStride, int numIndexHeads, int dIndex, int rotDim, int maxPos, int interleaved,
+                                           int scaleFmt, float wScale, const fa_strides* sKnew, const fa_strides* sQraw, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_index_append_run({.Knew = Knew, .K = Kpool, .k_scale = kScalePool, .Qraw = Qraw, .Wraw = Wraw, .Qidx = Qidx, .W = W,
+                                     .cos_sin = cosSin, .kv_lens = kvLens, .B = batchSize, .Sq = seqLenNew, .heads = numIndexHeads,
+                                     .d = dIndex, .rot_dim = rotDim, .max_pos = maxPos, .interleaved = interleaved, .scale_fmt = scaleFmt,
+                                     .w_scale = wScale, .sKnew = sKnew, .sQraw = sQraw, .paging = &pg, .stream = stream});
 }
 
 // ---- MLA prefill ----

@@ -1441,7 +1441,7 @@ int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpoo
  * entries of unread pages may hold anything.  Two launches chained on the stream: the logits (a workgroup per 256 keys of a sequence;
  * the index cache is read once whatever seqLenQ is) and a radix select per (b, i) row.
  *
- * Not done: the write side of the index cache (quantising append, Hadamard rotation), bf16 index tensors, other head counts,
+ * (The write side of the index cache: flash_attention_mla_index_append, below.)  Not done: bf16 index tensors, other head counts,
  * seqLenQ above FA_DECODE_MAX_Q (the prefill indexer), a ragged form, a plan call, strided inputs, a first histogram fused into the
  * logits kernel.
  */
@@ -1488,6 +1488,69 @@ int flash_attention_mla_append_paged(const void* Cnew, const void* Rnew, void* K
                                      int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope,
                                      int dtype, int kv_dtype,
                                      const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream);
+
+/*
+ * flash_attention_mla_index_append, flash_attention_mla_index_append_paged -- the WRITE side of the MLA index cache (DESIGN.md section
+ * 40): one launch turns the step's raw bf16 index projections into what flash_attention_mla_index_topk* reads.
+ *   Knew     bf16 [batchSize, seqLenNew, 128], 16-byte aligned; sKnew: strideB / strideS in elements (strideH is not read), the last
+ *            dimension contiguous, NULL = dense: a slice of a fused projection passes without a copy
+ *   Kidx / Kpool, kScale / kScalePool   the indexer's own layouts, written in place: [batchSize, seqLenK, 128] e4m3fn bytes (seqLenK
+ *            the CAPACITY) and fp32 [batchSize, seqLenK], or the pools [numPages, pageSize, 128] and [numPages, pageSize] behind
+ *            blockTable / tableStride; pages, capacity and 64-bit page bases as there
+ *   kvLens   DEVICE int32 [batchSize], read by the kernel; it ALREADY counts the new rows; NULL = the capacity
+ *   Qraw, Wraw, Qidx, W   the optional Q side, all four NULL (the K side alone: a cache fill) or all four non-NULL, any mixture
+ *            FA_ERR_NULL_POINTER.  Qraw bf16 [batchSize, seqLenNew, 64, 128] (sQraw: strideB, strideH, strideS in elements, NULL =
+ *            dense); Wraw fp32 [batchSize, seqLenNew, 64], dense; Qidx e4m3fn [batchSize, seqLenNew, 64, 128] and W fp32 [batchSize,
+ *            seqLenNew, 64], the indexer's dense inputs, written whole: W[b, i, h] = (Wraw[b, i, h] * qscale[b, i, h]) * wScale, two
+ *            fp32 products, qscale the scale of the query row's head h
+ *   wScale   host float, finite (FA_ERR_BAD_SCALE): the model's softmax_scale * 64^-0.5
+ *   cosSin, rotDim, maxPos, interleaved   flash_attention_rope_append's table and rules: fp32 [maxPos, rotDim], cos then sin, rotDim a
+ *            multiple of 16 in [16, 128], maxPos >= the capacity.  cosSin = NULL: no rotation (the rows are already rotated); rotDim
+ *            and maxPos are then not read
+ *   scaleFmt FA_INDEX_SCALE_F32 or FA_INDEX_SCALE_POW2 (the model's ue8m0 form); anything else FA_ERR_BAD_FLAGS
+ *   numIndexHeads, dIndex   only (64, 128); anything else FA_ERR_UNSUPPORTED_DHEAD
+ * Positions.  K rows: flash_attention_mla_append's rule, word for word -- L = min(kvLens[b], capacity), row i goes to p = L - seqLenNew
+ * + i iff p >= 0, L <= 0 writes nothing; paged: only the entries of pages that receive a row are read, an entry outside [0, numPages)
+ * skips its rows and is never clamped; 1 <= seqLenNew <= capacity, not capped at FA_DECODE_MAX_Q.  A K row is rotated at p.  Q rows:
+ * flash_attention_rope_append's rule -- every row is written, rotated at max(clamp(kvLens[b], 1, capacity) - seqLenNew + i, 0).
+ * Values, pinned to the bit, per row of 128 (each stage of the model's pipeline returns a bf16 tensor):
+ *   1. x = the bf16 values as fp32;
+ *   2. with cosSin: the columns < rotDim rotated by flash_attention_rope_append's formula, y1 = fmaf(x1, c, -(x2 s)), y2 = fmaf(x2, c,
+ *      x1 s), rounded once to bf16; the columns >= rotDim untouched;
+ *   3. an in-place Walsh-Hadamard transform in fp32, Sylvester order: seven stages of element strides 1, 2, 4, ..., 64 in that order,
+ *      each butterfly (a, b) = (t[j], t[j + stride]) -> (a + b, a - b), one fp32 add and one fp32 subtract, nothing fused;
+ *   4. r = bf16(fl32(t * c0)), c0 the fp32 nearest to 2^-3.5, rounded to nearest even;
+ *   5. amax = max(max_j |r_j|, 1e-4f);
+ *   6. s0 = fl32(amax * c1), c1 the fp32 nearest to 1 / 448; the scale s = s0 (FA_INDEX_SCALE_F32) or 2^(E + (M != 0)), E and M the
+ *      unbiased exponent and the mantissa field of s0 (FA_INDEX_SCALE_POW2: the least power of two >= s0);
+ *   7. the codes: flash_attention_kv_append's arithmetic on r under the descale s -- the correctly rounded fp32 quotient, saturated
+ *      at +-448, rounded to nearest even once to e4m3fn, the sign of zero kept;
+ *   8. K: the 128 bytes to the row, s to its kScale slot;  Q: the bytes to Qidx[b, i, h], W as above.
+ * A NaN or an infinity in a row leaves that row's bytes and scale unspecified, never a bad address; other rows are unaffected.
+ * Validated before the launch in flash_attention_mla_append's order and with its codes, the new checks with their kind: the pointers;
+ * Knew, Kidx, Qraw, Qidx, cosSin 16-byte aligned; kvLens, blockTable, kScale, Wraw, W 4-byte aligned (FA_ERR_MISALIGNED); the paging
+ * geometry; the shapes; the widths; rotDim and maxPos (FA_ERR_BAD_SHAPE), interleaved and scaleFmt (FA_ERR_BAD_FLAGS), wScale; the
+ * strides; the grid.  No allocation, no host synchronisation, no atomics: every output byte has one writer.  Capturable: lengths and
+ * the table are read on the device, so `kv_lens += Sq; mla_index_append; mla_index_topk; mla_sparse_decode` is one graph.
+ * Not done: the k_norm LayerNorm in front, a ragged form, bf16 index caches, other head counts or widths, per-row position offsets.
+ */
+enum fa_index_scale_fmt {
+    FA_INDEX_SCALE_F32 = 0,
+    FA_INDEX_SCALE_POW2 = 1
+};
+
+int flash_attention_mla_index_append(const void* Knew, void* Kidx, float* kScale, const void* Qraw, const float* Wraw, void* Qidx,
+                                     float* W, const float* cosSin, const int32_t* kvLens,
+                                     int batchSize, int seqLenNew, int seqLenK, int numIndexHeads, int dIndex,
+                                     int rotDim, int maxPos, int interleaved, int scaleFmt, float wScale,
+                                     const fa_strides* sKnew, const fa_strides* sQraw, void* stream);
+
+int flash_attention_mla_index_append_paged(const void* Knew, void* Kpool, float* kScalePool, const void* Qraw, const float* Wraw,
+                                           void* Qidx, float* W, const float* cosSin, const int32_t* kvLens, const int32_t* blockTable,
+                                           int batchSize, int seqLenNew,
+                                           int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                           int numIndexHeads, int dIndex, int rotDim, int maxPos, int interleaved, int scaleFmt,
+                                           float wScale, const fa_strides* sKnew, const fa_strides* sQraw, void* stream);
 
 /*
  * flash_attention_mla_prefill -- the forward pass of multi-head latent attention in its UP-PROJECTED (prefill) form: ordinary multi-head

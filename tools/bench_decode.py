@@ -945,9 +945,100 @@ def mla_index_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+def mla_index_append_main(args, fa, dev):
+    """--mla --index-append: mla_index_append* beside the torch route to the same cache (rotary, a bf16 matmul with the Sylvester matrix,
+    amax, scale, cast, scatter through the table), alternated: the indexer's three (B, L) at Sq = 1 with the Q side, and one 4096-row fill
+    (the K side alone), each into a contiguous and a page-64 index cache"""
+    import torch
+    bf, f8, PAGE, ROT = torch.bfloat16, torch.float8_e4m3fn, 64, 64
+    seen, shapes = set(), []
+    for name, B, _, Sq, L, beside in MLA_SHAPES:      # the sparse shapes' distinct (B, L)
+        if beside and (B, L) not in seen:
+            seen.add((B, L))
+            shapes.append((name.split("_", 1)[1], B, Sq, L, L, True))
+    shapes.append(("fill4096", 1, 4096, 4096, 32768, False))
+    if args.shape:
+        shapes = [x for x in shapes if x[0] in args.shape]
+    j = torch.arange(128, device=dev)
+    parity = sum(((j[:, None] & j[None, :]) >> bit) & 1 for bit in range(7)) & 1
+    Hm = (1.0 - 2.0 * parity).to(bf)                  # the 128 x 128 Sylvester matrix
+    w_scale = 128 ** -0.5 * 64 ** -0.5
+    stats = lambda w: [round(x, 5) for x in (statistics.median(w), min(w), max(w))]
+    primed = False
+    for name, B, Sq, L, cap, with_q in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        kn = torch.randn(B, Sq, 128, device=dev, generator=g).to(bf)
+        qn = torch.randn(B, Sq, 64, 128, device=dev, generator=g).to(bf) if with_q else None
+        wn = torch.randn(B, Sq, 64, device=dev, generator=g) if with_q else None
+        lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+        cs = fa.rope_table(cap, ROT, device=dev)
+        pos = lens[:, None].long() - Sq + torch.arange(Sq, device=dev)[None]               # [B, Sq]: every row is written
+        bidx = torch.arange(B, device=dev)[:, None]
+        for page in (0, PAGE):
+            if page:
+                table = torch.randperm(B * (cap // page), device=dev, generator=g).to(torch.int32).view(B, cap // page)
+                shape = (B * (cap // page), page)
+                where = (table.long().gather(1, pos // page), pos % page)
+            else:
+                table, shape, where = None, (B, cap), (bidx, pos)
+            caches = [(torch.zeros(shape + (128,), dtype=torch.uint8, device=dev), torch.zeros(shape, device=dev)) for _ in range(2)]
+            Qidx, W = torch.empty(B, Sq, 64, 128, dtype=f8, device=dev), torch.empty(B, Sq, 64, device=dev)
+            tQ, tW = torch.empty_like(Qidx), torch.empty_like(W)
+
+            def quantise(x, p):                       # x bf16 [.., 128] rotated at p (broadcast over x's leading dimensions)
+                t = cs[p]
+                c, s = t[..., :ROT // 2], t[..., ROT // 2:]
+                x1, x2 = x[..., :ROT // 2].float(), x[..., ROT // 2:ROT].float()
+                xr = torch.cat([(x1 * c - x2 * s).to(bf), (x2 * c + x1 * s).to(bf), x[..., ROT:]], -1)
+                r = torch.matmul(xr, Hm) * 2.0 ** -3.5
+                sc = torch.exp2(torch.ceil(torch.log2(r.abs().amax(-1).float().clamp_(min=1e-4) * (1.0 / 448.0))))
+                return (r.float() / sc[..., None]).clamp_(-448.0, 448.0).to(f8), sc
+
+            def torch_route(cache=caches[1]):
+                codes, sc = quantise(kn, pos)
+                cache[0][where], cache[1][where] = codes.view(torch.uint8), sc
+                if with_q:
+                    codes, sc = quantise(qn, pos[:, :, None])
+                    tQ.copy_(codes)
+                    torch.mul(wn * sc, w_scale, out=tW)
+
+            kw = dict(q=qn, w=wn, Qidx=Qidx, W=W, w_scale=w_scale) if with_q else {}
+            if page:
+                mine = lambda c=caches[0]: fa.mla_index_append_paged(kn, c[0].view(f8), c[1], table, lens, cos_sin=cs, **kw)
+            else:
+                mine = lambda c=caches[0]: fa.mla_index_append(kn, c[0].view(f8), c[1], lens, cos_sin=cs, **kw)
+            routes = {"index_append_ms": mine, "torch_index_append_ms": torch_route}
+            if not primed:   # >= 1 s of calls before the first timed window
+                t = 0.0
+                while t < 1000.0:
+                    t += timed(mine, 200, 0) * 200
+                primed = True
+            w = {k: [] for k in routes}
+            for _ in range(args.repeats):
+                for k, fn in routes.items():
+                    w[k].append(timed(fn, args.steps, args.warmup))
+            ms = statistics.median(w["index_append_ms"])
+            torch.cuda.synchronize()
+            # the torch route's matmul sums in another order and its rotation is not fused: most bytes agree, not all
+            same = (caches[0][0][where] == caches[1][0][where]).float().mean().item()      # (the rows written)
+            wrote = B * Sq * (65 if with_q else 1) * (256 + 132)      # per row: 256 bytes read, 128 codes and one fp32 written
+            out = {"shape": name, "B": B, "Sq": Sq, "L": L, "page": page, "q_side": with_q, **{k: stats(v) for k, v in w.items()},
+                   "vs_torch": round(statistics.median(w["torch_index_append_ms"]) / ms, 3),
+                   "spread": round((max(w["index_append_ms"]) - min(w["index_append_ms"])) / ms, 4),
+                   "beats_torch": bool(max(w["index_append_ms"]) < min(w["torch_index_append_ms"])),
+                   "gbps": round(wrote / ms / 1e6, 2), "cache_bytes_equal_to_torch": round(same, 5),
+                   "scales_equal_to_torch": round((caches[0][1][where] == caches[1][1][where]).float().mean().item(), 5)}
+            print(json.dumps(out), flush=True)
+            del routes, caches, Qidx, W, tQ, tW, w
+        del kn, qn, wn, cs
+        torch.cuda.empty_cache()
+
+
 def mla_main(args, fa, dev):
     """--mla: flash_attention_mla_decode* beside the same problem from torch ops, alternated"""
     import torch
+    if args.index_append:
+        return mla_index_append_main(args, fa, dev)
     if args.sparse:
         return mla_sparse_main(args, fa, dev)
     if args.index:
@@ -1383,6 +1474,7 @@ def main():
     ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
     ap.add_argument("--sparse", type=int, default=0, help="with --mla: time flash_attention_mla_sparse_decode* at this topk beside gather + dense, alternated")
     ap.add_argument("--index", type=int, default=0, help="with --mla: time mla_index_topk at this topk beside the torch route to the same indices, alternated")
+    ap.add_argument("--index-append", action="store_true", help="with --mla: time mla_index_append* beside the torch route to the same index cache, alternated")
     ap.add_argument("--mla", action="store_true", help="time flash_attention_mla_decode* beside the same problem from torch ops, alternated; --paged, --splits")
     args = ap.parse_args()
     import torch
