@@ -99,6 +99,8 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_mla_sparse_decode_paged_fp8", "flash_attention_mla_sparse_plan",
            "flash_attention_mla_index_topk", "flash_attention_mla_index_topk_paged",
            "flash_attention_mla_index_append", "flash_attention_mla_index_append_paged",
+           "flash_attention_mla_sparse_decode_packed", "flash_attention_mla_sparse_decode_paged_packed",
+           "flash_attention_mla_append_packed", "flash_attention_mla_append_paged_packed",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
@@ -148,6 +150,12 @@ _MLA_SPARSE_SYMBOLS = {False: {False: "flash_attention_mla_sparse_decode", True:
 _MLA_INDEX_SYMBOLS = {False: "flash_attention_mla_index_topk", True: "flash_attention_mla_index_topk_paged"}
 # ... and the write side of its cache: _MLA_INDEX_APPEND_SYMBOLS[paged]
 _MLA_INDEX_APPEND_SYMBOLS = {False: "flash_attention_mla_index_append", True: "flash_attention_mla_index_append_paged"}
+# ... the packed latent row (656 bytes: 512 e4m3fn codes, four fp32 scales, 64 bf16 rotary columns): the sparse read and the append,
+# _MLA_PACKED_SYMBOLS[paged] and _MLA_APPEND_PACKED_SYMBOLS[paged] -- the ``_fp8`` sparse signature without ``kvDescale`` and ``kv_dtype``,
+# the append's with ``scaleFmt`` in their place
+_MLA_PACKED_SYMBOLS = {False: "flash_attention_mla_sparse_decode_packed", True: "flash_attention_mla_sparse_decode_paged_packed"}
+_MLA_APPEND_PACKED_SYMBOLS = {False: "flash_attention_mla_append_packed", True: "flash_attention_mla_append_paged_packed"}
+MLA_PACKED_ROW_BYTES = 656
 FA_INDEX_SCALE_F32, FA_INDEX_SCALE_POW2 = 0, 1     # scaleFmt: the row's scale as computed, or rounded up to a power of two (ue8m0)
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
@@ -292,6 +300,13 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, _MLA_SPARSE_SYMBOLS[True][paged])
             fn.argtypes = [vp] * 5 + [vp, i, i64, i64] + [vp] * paged + [vp, vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i, i] \
                 + [sp] * 3 + [vp]
+            fn.restype = i
+            # ... on the packed row: the bf16 sparse signature; its append: scaleFmt where kvDescale stands, no kv_dtype
+            fn = getattr(L, _MLA_PACKED_SYMBOLS[paged])
+            fn.argtypes = list(getattr(L, _MLA_SPARSE_SYMBOLS[False][paged]).argtypes)
+            fn.restype = i
+            fn = getattr(L, _MLA_APPEND_PACKED_SYMBOLS[paged])
+            fn.argtypes = [vp] * 4 + [vp] * paged + [i] + [i] * 2 + paging(paged) + [i] * 3 + [sp] * 3 + [vp]
             fn.restype = i
             # ... the latent-cache append: the two new tensors, the cache, kvLens, the table (paged), kvDescale
             fn = getattr(L, _MLA_APPEND_SYMBOLS[paged])
@@ -1116,23 +1131,29 @@ def _mla_descale(kv_descale, fp8, device):
 
 
 def _mla_front(Q, KV, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, kv_descale=None,
-               indices=None):
+               indices=None, packed=False):
     """Both MLA fronts: the checks of the tensors (with the decode fronts' helpers for the table, the lengths and the workspace), the plan
     and the workspace for the capacity, then the entry point of _MLA_SYMBOLS -- or, for a float8_e4m3fn cache under a bf16 Q, of
     _MLA_FP8_SYMBOLS, which takes ``kv_descale`` and the cache's dtype code.  With ``indices`` (the sparse fronts): the entry point of
-    _MLA_SPARSE_SYMBOLS, the plan for topk, and the index list with its two strides after the lengths."""
+    _MLA_SPARSE_SYMBOLS, the plan for topk, and the index list with its two strides after the lengths.  ``packed`` (the sparse fronts on
+    the packed row): the entry point of _MLA_PACKED_SYMBOLS on a uint8 cache of 656-byte rows, its strides in bytes."""
     import torch
     paged = block_table is not None
     sparse = indices is not None
     f8 = getattr(torch, "float8_e4m3fn", None)
-    fp8 = f8 is not None and getattr(KV, "dtype", None) == f8 and Q.dtype == torch.bfloat16
+    fp8 = not packed and f8 is not None and getattr(KV, "dtype", None) == f8 and Q.dtype == torch.bfloat16
     name = _MLA_SPARSE_SYMBOLS[fp8][paged] if sparse else (_MLA_FP8_SYMBOLS if fp8 else _MLA_SYMBOLS)[paged]
+    if packed:
+        name = _MLA_PACKED_SYMBOLS[paged]
     if not (Q.is_cuda and KV.is_cuda and (not paged or block_table.is_cuda) and (not sparse or indices.is_cuda)):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
     D = MLA_D_LATENT + MLA_D_ROPE
-    if Q.dim() != 4 or KV.dim() != 3 or (not paged and Q.shape[0] != KV.shape[0]) or Q.shape[3] != D or KV.shape[2] != D:
-        raise ValueError(f"Q must be [B, H, Sq, {D}] and {'KV_pool [P, page' if paged else 'KV [B, capacity'}, {D}]")
-    if not fp8 and Q.dtype != KV.dtype:
+    KD = MLA_PACKED_ROW_BYTES if packed else D
+    if Q.dim() != 4 or KV.dim() != 3 or (not paged and Q.shape[0] != KV.shape[0]) or Q.shape[3] != D or KV.shape[2] != KD:
+        raise ValueError(f"Q must be [B, H, Sq, {D}] and {'KV_pool [P, page' if paged else 'KV [B, capacity'}, {KD}]")
+    if packed and (Q.dtype != torch.bfloat16 or KV.dtype != torch.uint8):
+        raise TypeError(f"a packed latent cache is torch.uint8 rows of {KD} bytes under a bfloat16 Q")
+    if not fp8 and not packed and Q.dtype != KV.dtype:
         raise TypeError("Q, KV must share a dtype")
     _mla_descale(kv_descale, fp8, Q.device)
     if KV.stride(2) != 1:
@@ -1241,6 +1262,31 @@ def flash_attention_mla_sparse_decode_paged(Q, KV_pool, block_table, indices, kv
                       kv_descale, indices)
 
 
+def flash_attention_mla_sparse_decode_packed(Q, KV, indices, kv_lens=None, scale=None, is_causal=False, out_dtype=None, num_splits=0,
+                                             return_lse=False, O=None, workspace=None, stream=None):
+    """``flash_attention_mla_sparse_decode`` on the PACKED latent row, the mixed fp8 row DeepSeek-V3.2 is served
+    with: ``KV`` is ``torch.uint8 [B, capacity, 656]`` (last dimension contiguous, row stride a multiple of 16 bytes), a row being 512
+    e4m3fn codes, four fp32 scales -- scale j for the latent columns ``[128 j, 128 j + 128)`` -- and the 64 rotary columns as bf16.
+    The logical cache is ``(codes.view(float8_e4m3fn).float() * scales.repeat_interleave(128, -1)).bfloat16()`` beside the rope bytes
+    viewed as bf16, and the result is the bf16 sparse call's on that cache, bit for bit, under the same ``num_splits``: the kernel
+    applies the scales on the way into its LDS image.  Every keyword and every rule as for ``flash_attention_mla_sparse_decode``;
+    there is no ``kv_descale``.  The cache ``mla_cache_append_packed`` writes.  No CPU fallback."""
+    if indices is None:
+        raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
+    return _mla_front(Q, KV, None, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, None, indices,
+                      packed=True)
+
+
+def flash_attention_mla_sparse_decode_paged_packed(Q, KV_pool, block_table, indices, kv_lens=None, scale=None, is_causal=False,
+                                                   out_dtype=None, num_splits=0, return_lse=False, O=None, workspace=None, stream=None):
+    """``flash_attention_mla_sparse_decode_packed`` against a PAGED packed cache: ``KV_pool`` ``torch.uint8 [P, page, 656]`` and
+    ``block_table`` as in ``flash_attention_mla_sparse_decode_paged``."""
+    if indices is None:
+        raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
+    return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, None,
+                      indices, packed=True)
+
+
 # ---- the MLA sparse-attention indexer (DESIGN.md section 39): fp8 index logits and the top-k positions of every query row ----
 MLA_INDEX_HEADS, MLA_INDEX_D = 64, 128
 
@@ -1321,21 +1367,27 @@ def mla_index_topk_paged(Qidx, W, K_pool, k_scale_pool, block_table, topk, kv_le
     return _mla_index_front(Qidx, W, K_pool, k_scale_pool, block_table, topk, kv_lens, is_causal, logits, indices, return_logits, stream)
 
 
-def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, stream):
-    """Both mla_cache_append fronts: the tensor checks, the bounds of Sq, and the entry point of _MLA_APPEND_SYMBOLS"""
+def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, stream, scale_fmt=None):
+    """Both mla_cache_append fronts: the tensor checks, the bounds of Sq, and the entry point of _MLA_APPEND_SYMBOLS.  With ``scale_fmt``
+    (the packed fronts): a uint8 cache of 656-byte rows and the entry point of _MLA_APPEND_PACKED_SYMBOLS"""
     import torch
     paged = block_table is not None
-    layout = "KV_pool [P, page, 576]" if paged else "KV_cache [B, capacity, 576]"
+    packed = scale_fmt is not None
+    if packed and scale_fmt not in ("f32", "pow2"):
+        raise ValueError("scale_fmt must be 'f32' or 'pow2'")
+    KD = MLA_PACKED_ROW_BYTES if packed else MLA_D_LATENT + MLA_D_ROPE
+    layout = f"KV_pool [P, page, {KD}]" if paged else f"KV_cache [B, capacity, {KD}]"
     if not (getattr(c_kv, "is_cuda", False) and getattr(k_pe, "is_cuda", False) and getattr(KV, "is_cuda", False)
             and (not paged or block_table.is_cuda)):
         raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
-    D = MLA_D_LATENT + MLA_D_ROPE
     if c_kv.dim() != 3 or k_pe.dim() != 3 or KV.dim() != 3 or c_kv.shape[2] != MLA_D_LATENT or k_pe.shape[2] != MLA_D_ROPE \
-            or c_kv.shape[:2] != k_pe.shape[:2] or KV.shape[2] != D or (not paged and KV.shape[0] != c_kv.shape[0]):
+            or c_kv.shape[:2] != k_pe.shape[:2] or KV.shape[2] != KD or (not paged and KV.shape[0] != c_kv.shape[0]):
         raise ValueError(f"c_kv must be [B, Sq, {MLA_D_LATENT}], k_pe [B, Sq, {MLA_D_ROPE}] and {layout}")
     f8 = getattr(torch, "float8_e4m3fn", None)
-    fp8 = f8 is not None and KV.dtype == f8
-    if c_kv.dtype != torch.bfloat16 or k_pe.dtype != torch.bfloat16 or not (fp8 or KV.dtype == torch.bfloat16):
+    fp8 = not packed and f8 is not None and KV.dtype == f8
+    if packed and (c_kv.dtype != torch.bfloat16 or k_pe.dtype != torch.bfloat16 or KV.dtype != torch.uint8):
+        raise TypeError(f"c_kv, k_pe must be bfloat16 and {layout.split()[0]} uint8 (packed rows of {KD} bytes)")
+    if not packed and (c_kv.dtype != torch.bfloat16 or k_pe.dtype != torch.bfloat16 or not (fp8 or KV.dtype == torch.bfloat16)):
         raise TypeError(f"c_kv, k_pe must be bfloat16 and {layout.split()[0]} bfloat16 or float8_e4m3fn")
     if c_kv.device != KV.device or k_pe.device != KV.device:
         raise ValueError("c_kv, k_pe and the cache must be on one device")
@@ -1350,9 +1402,11 @@ def _mla_append_front(name, c_kv, k_pe, KV, block_table, kv_lens, kv_descale, st
     ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(KV.device):
         st = [FaStrides(t.stride(0), 0, t.stride(1)) for t in (c_kv, k_pe, KV)]
-        rc = getattr(lib(), _MLA_APPEND_SYMBOLS[paged])(
-            c_kv.data_ptr(), k_pe.data_ptr(), KV.data_ptr(), ptr(kv_lens), *map(ptr, tables), ptr(kv_descale), B, Sq, *geometry,
-            MLA_D_LATENT, MLA_D_ROPE, _dtype_code(c_kv.dtype), _dtype_code(KV.dtype), *[ctypes.byref(x) for x in st], _stream_ptr(stream))
+        fmt = (FA_INDEX_SCALE_POW2 if scale_fmt == "pow2" else FA_INDEX_SCALE_F32) if packed else ptr(kv_descale)
+        rc = getattr(lib(), (_MLA_APPEND_PACKED_SYMBOLS if packed else _MLA_APPEND_SYMBOLS)[paged])(
+            c_kv.data_ptr(), k_pe.data_ptr(), KV.data_ptr(), ptr(kv_lens), *map(ptr, tables), fmt, B, Sq, *geometry,
+            MLA_D_LATENT, MLA_D_ROPE, _dtype_code(c_kv.dtype), *(() if packed else (_dtype_code(KV.dtype),)),
+            *[ctypes.byref(x) for x in st], _stream_ptr(stream))
     _check(rc)
 
 
@@ -1377,6 +1431,22 @@ def mla_cache_append_paged(c_kv, k_pe, KV_pool, block_table, kv_lens=None, kv_de
     ``flash_attention_mla_decode_paged``.  Only the entries of pages that receive a row are read; an entry outside [0, P) is NOT
     clamped: the rows that would go to that page are skipped and nothing else is touched.  Returns None."""
     _mla_append_front("mla_cache_append_paged", c_kv, k_pe, KV_pool, block_table, kv_lens, kv_descale, stream)
+
+
+def mla_cache_append_packed(c_kv, k_pe, KV_cache, kv_lens=None, scale_fmt="f32", stream=None):
+    """``mla_cache_append`` into the PACKED latent cache ``flash_attention_mla_sparse_decode_packed`` reads: ``KV_cache`` is
+    ``torch.uint8 [B, capacity, 656]``.  Per block of 128 latent columns of a new row: ``amax = max(max |x|, 1e-4)``, the scale
+    ``s = amax * fl32(1 / 448)`` (``scale_fmt="f32"``) or the least power of two above it (``"pow2"``), the codes
+    ``clamp(x / s, -448, 448)`` rounded to e4m3fn once, ``s`` to the block's fp32 slot; ``k_pe`` is copied as bf16.  Positions,
+    ``kv_lens`` and ``stream`` as for ``mla_cache_append``: the step ``kv_lens += Sq; mla_cache_append_packed(...);
+    flash_attention_mla_sparse_decode_packed(...)`` is one graph.  Returns None.  No CPU fallback."""
+    _mla_append_front("mla_cache_append_packed", c_kv, k_pe, KV_cache, None, kv_lens, None, stream, scale_fmt=str(scale_fmt))
+
+
+def mla_cache_append_paged_packed(c_kv, k_pe, KV_pool, block_table, kv_lens=None, scale_fmt="f32", stream=None):
+    """``mla_cache_append_packed`` into a PAGED packed cache, ``KV_pool`` ``torch.uint8 [P, page, 656]`` behind ``block_table`` as in
+    ``mla_cache_append_paged``: an entry outside [0, P) skips its rows and nothing else is touched.  Returns None."""
+    _mla_append_front("mla_cache_append_paged_packed", c_kv, k_pe, KV_pool, block_table, kv_lens, None, stream, scale_fmt=str(scale_fmt))
 
 
 def _mla_index_append_front(name, k_new, K, k_scale, block_table, kv_lens, q, w, cos_sin, interleaved, scale_fmt, w_scale, Qidx, W, stream):

@@ -28,6 +28,7 @@
 #include "mla_sparse.hip.h"
 #include "mla_index.hip.h"
 #include "mla_append.hip.h"
+#include "mla_append_packed.hip.h"
 #include "mla_index_append.hip.h"
 #include "fwd_mla.hip.h"
 
@@ -916,7 +917,11 @@ struct MlaCall {
     const int32_t* indices;        // [B, Sq, topk] (device memory)
     int topk;
     int64_t index_stride_b, index_stride_q;
+    // the cache's row: MLA_ROW_PLAIN, 576 elements of kv_dtype, or MLA_ROW_PACKED (the _packed entry points),
+    // MlaPackedRow's 656 bytes -- kv_dtype is then FA_DTYPE_FP8_E4M3 (strides in bytes) and the call sparse
+    int layout;
 };
+enum { MLA_ROW_PLAIN = 0, MLA_ROW_PACKED = 1 };
 
 // The sparse calls route by the same formula over their own units and tiles: a unit is (sequence, query row, block of 64 HEADS) -- rows
 // that share a tile share an index list -- and the tiles are those of the topk slots, not of the capacity.  The constants are
@@ -959,9 +964,12 @@ static int mla_check_shape(const MlaCall& c) {
 // one validation, in decode_run's order, and the launches: the MLA kernel and, under more than one split, the combine at D = 512.
 // The sparse calls add four refusals at their places: NULL indices with the pointers, their alignment after the other arrays', topk
 // with the shapes, the index row stride with the strides
+// A packed cache (MLA_ROW_PACKED) differs in the width of its row alone: 656 bytes where the others have 576 elements
 static int mla_run(MlaCall c) {
     const DecodePaging* pg = c.paging;
     constexpr int D = MlaCfg::D, DL = MlaCfg::DL;
+    const bool packed = c.layout == MLA_ROW_PACKED;
+    const int KD = packed ? MlaPackedRow::BYTES : D;   // the cache row in elements of kv_dtype
     if (!c.Q || !c.KV || !c.O || (pg && !pg->table) || (c.sparse && !c.indices)) return FA_ERR_NULL_POINTER;
     if (!aligned16(c.Q) || !aligned16(c.KV) || !aligned16(c.O) || !aligned16(c.LSE) || !aligned16(c.workspace)) return FA_ERR_MISALIGNED;
     fa_strides tKV{};   // the cache's strides without the head stride, which no MLA call reads
@@ -977,9 +985,9 @@ static int mla_run(MlaCall c) {
     if ((rc = mla_check_shape(c)) != FA_OK) return rc;
     if (c.kv_dtype != FA_DTYPE_BF16 && c.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
     if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;   // (exp2 with the positive scale folded in)
-    if (!strides_ok(c.sQ, 2, D) || !cache_strides_ok(cache, D) || !strides_ok(c.sO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
+    if (!strides_ok(c.sQ, 2, D) || !cache_strides_ok(cache, KD) || !strides_ok(c.sO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
     if (c.sparse && (c.index_stride_q < c.topk || c.index_stride_b < 0)) return FA_ERR_BAD_STRIDE;
-    if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;
+    if (!cache_extent_ok(cache, KD)) return FA_ERR_BAD_SHAPE;
     const DecodeRoute r = mla_route(c);
     if (r.ns > 1 && !c.workspace) return FA_ERR_NULL_POINTER;
     const int64_t rows = (int64_t)c.B * c.H * c.Sq;
@@ -991,7 +999,7 @@ static int mla_run(MlaCall c) {
     p.part_o = (float*)c.workspace;
     p.part_lse = r.ns > 1 ? (float*)((char*)c.workspace + round16((size_t)rows * r.ns * DL * sizeof(float))) : nullptr;
     resolve_strides(c.sQ, c.H, c.Sq, D, p.qB, p.qH, p.qS);
-    resolve_strides(cache.sK, 1, cache_rows(cache), D, p.kB, p.kH, p.kS);
+    resolve_strides(cache.sK, 1, cache_rows(cache), KD, p.kB, p.kH, p.kS);
     p.vB = p.kB; p.vH = p.kH; p.vS = p.kS;
     resolve_strides(c.sO, c.H, c.Sq, DL, p.oB, p.oH, p.oS);
     p.H = c.H; p.Hkv = 1; p.G = c.H; p.Sq = c.Sq; p.Sk = cache.capacity;
@@ -1009,11 +1017,13 @@ static int mla_run(MlaCall c) {
     if (c.sparse) {
         p.indices = c.indices; p.topk = c.topk;
         p.isB = c.index_stride_b; p.isQ = c.index_stride_q;
-        rc = c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_sparse_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
-                                             : mla_sparse_launch(pg != nullptr, (unsigned)r.grid, st, p);
+        rc = packed                            ? mla_sparse_packed_launch(pg != nullptr, (unsigned)r.grid, st, p)
+             : c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_sparse_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
+                                               : mla_sparse_launch(pg != nullptr, (unsigned)r.grid, st, p);
         if (rc != FA_OK || r.ns == 1) return rc;
         return mla_sparse_combine_launch((unsigned)rows, st, p);   // (a row may have no key in any split)
     }
+    if (packed) return FA_ERR_UNSUPPORTED_DTYPE;   // (no entry point: dense decode on the packed row is not done)
     rc = c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_decode_fp8_launch(pg != nullptr, (unsigned)r.grid, st, p)
                                          : mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
@@ -1135,6 +1145,64 @@ static int mla_append_run(const MlaAppendCall& c) {
     p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
     const Kernel k = mla_append_kernel_of(c.kv_dtype == FA_DTYPE_FP8_E4M3, pg != nullptr);
     return (int)launch(k, (unsigned)grid, KvAppendCfg::THREADS, 0, reinterpret_cast<hipStream_t>(c.stream), p);
+}
+
+// ---- the packed-row append: flash_attention_mla_append_packed* (mla_append_packed.hip.h) ----
+// mla_append_run's ladder on rows of MlaPackedRow::BYTES bytes (sKV in bytes), scaleFmt -- mla_index_append_run's, FA_ERR_BAD_FLAGS --
+// where kv_dtype and the descale's checks stand
+struct MlaAppendPackedCall {
+    const void *Cnew, *Rnew;
+    void* KV;
+    const int32_t* kv_lens;
+    int B, Sq, capacity, d_latent, d_rope, dtype, scale_fmt;
+    const fa_strides *sC, *sR, *sKV;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+static int mla_append_packed_run(const MlaAppendPackedCall& c) {
+    using C = MlaAppendCfg;
+    constexpr int KD = MlaPackedRow::BYTES;
+    const DecodePaging* pg = c.paging;
+    if (!c.Cnew || !c.Rnew || !c.KV || (pg && !pg->table)) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Cnew) || !aligned16(c.Rnew) || !aligned16(c.KV)) return FA_ERR_MISALIGNED;
+    fa_strides tC{}, tR{}, tKV{};   // strideH is read of none of the three tensors
+    if (c.sC) tC = fa_strides{c.sC->strideB, 0, c.sC->strideS};
+    if (c.sR) tR = fa_strides{c.sR->strideB, 0, c.sR->strideS};
+    if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
+    const fa_strides *sC = c.sC ? &tC : nullptr, *sR = c.sR ? &tR : nullptr, *sKV = c.sKV ? &tKV : nullptr;
+    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .kv_dtype = FA_DTYPE_FP8_E4M3, .capacity = c.capacity, .sK = sKV, .sV = sKV,
+                  .paging = pg};
+    int rc = cache_check_arrays(cache, nullptr);
+    if (rc != FA_OK) return rc;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    const int B = c.B, Sq = c.Sq, Sk = cache.capacity;
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || c.d_latent <= 0 || c.d_rope <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || Sq > Sk || B > INT32_MAX / 2) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.scale_fmt != FA_INDEX_SCALE_F32 && c.scale_fmt != FA_INDEX_SCALE_POW2) return FA_ERR_BAD_FLAGS;
+    if (c.d_latent != C::DL || c.d_rope != C::DR) return FA_ERR_UNSUPPORTED_DHEAD;
+    if (!strides_ok(sC, 2, C::DL) || !strides_ok(sR, 2, C::DR) || !cache_strides_ok(cache, KD)) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(cache, KD)) return FA_ERR_BAD_SHAPE;   // what is written can be read
+    const int row_blocks = (Sq + KvAppendCfg::BLOCK - 1) / KvAppendCfg::BLOCK + 1;   // blocks are aligned in key positions
+    const int64_t grid = (int64_t)B * row_blocks;
+    if (grid > INT32_MAX) return FA_ERR_BAD_SHAPE;
+
+    MlaAppendPackedParams p{};
+    int64_t unused;
+    p.Cnew = (const __bf16*)c.Cnew; p.Rnew = (const __bf16*)c.Rnew; p.KV = c.KV;
+    p.kv_lens = c.kv_lens;
+    p.block_table = pg ? pg->table : nullptr;
+    resolve_strides(sC, 1, Sq, C::DL, p.cB, unused, p.cS);
+    resolve_strides(sR, 1, Sq, C::DR, p.rB, unused, p.rS);
+    resolve_strides(sKV, 1, cache_rows(cache), KD, p.kvB, unused, p.kvS);
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.Sq = Sq; p.cap = Sk; p.row_blocks = row_blocks;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.pow2 = c.scale_fmt == FA_INDEX_SCALE_POW2;
+    return (int)launch(mla_append_packed_kernel_of(pg != nullptr), (unsigned)grid, KvAppendCfg::THREADS, 0,
+                       reinterpret_cast<hipStream_t>(c.stream), p);
 }
 
 // ---- the MLA index-cache append: flash_attention_mla_index_append* (mla_index_append.hip.h) ----
@@ -2250,6 +2318,30 @@ int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpoo
                         .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
                         .kv_dtype = kv_dtype, .kv_descale = kvDescale, FA_SPARSE_FIELDS});
 }
+
+// ... on the packed row: the _fp8 signatures without kvDescale and kv_dtype
+int flash_attention_mla_sparse_decode_packed(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens, FA_SPARSE_ARGS,
+                                             void* workspace, int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                             float scale, bool is_causal, int dtype, int o_dtype, int numSplits, const fa_strides* sQ,
+                                             const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    return fa::mla_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal,
+                        .dtype = dtype, .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream,
+                        .kv_dtype = FA_DTYPE_FP8_E4M3, FA_SPARSE_FIELDS, .layout = fa::MLA_ROW_PACKED});
+}
+
+int flash_attention_mla_sparse_decode_paged_packed(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                                   FA_SPARSE_ARGS, const int32_t* blockTable, void* workspace, int batchSize, int numHeads,
+                                                   int seqLenQ, int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                                   int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype,
+                                                   int numSplits, const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO,
+                                                   void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .kv_lens = kvLens, .workspace = workspace, .B = batchSize, .H = numHeads,
+                        .Sq = seqLenQ, .d_latent = dLatent, .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype,
+                        .o_dtype = o_dtype, .num_splits = numSplits, .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream,
+                        .kv_dtype = FA_DTYPE_FP8_E4M3, FA_SPARSE_FIELDS, .layout = fa::MLA_ROW_PACKED});
+}
 #undef FA_SPARSE_ARGS
 #undef FA_SPARSE_FIELDS
 
@@ -2292,6 +2384,25 @@ int flash_attention_mla_append_paged(const void* Cnew, const void* Rnew, void* K
     return fa::mla_append_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KVpool, .kv_lens = kvLens, .kv_descale = kvDescale, .B = batchSize,
                                .Sq = seqLenNew, .d_latent = dLatent, .d_rope = dRope, .dtype = dtype, .kv_dtype = kv_dtype, .sC = sC,
                                .sR = sR, .sKV = sKV, .paging = &pg, .stream = stream});
+}
+
+// ---- the packed-row latent-cache append ----
+int flash_attention_mla_append_packed(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, int scaleFmt, int batchSize,
+                                      int seqLenNew, int seqLenK, int dLatent, int dRope, int dtype, const fa_strides* sC,
+                                      const fa_strides* sR, const fa_strides* sKV, void* stream) {
+    return fa::mla_append_packed_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KV, .kv_lens = kvLens, .B = batchSize, .Sq = seqLenNew,
+                                      .capacity = seqLenK, .d_latent = dLatent, .d_rope = dRope, .dtype = dtype, .scale_fmt = scaleFmt,
+                                      .sC = sC, .sR = sR, .sKV = sKV, .stream = stream});
+}
+
+int flash_attention_mla_append_paged_packed(const void* Cnew, const void* Rnew, void* KVpool, const int32_t* kvLens,
+                                            const int32_t* blockTable, int scaleFmt, int batchSize, int seqLenNew, int numPages,
+                                            int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope, int dtype,
+                                            const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_append_packed_run({.Cnew = Cnew, .Rnew = Rnew, .KV = KVpool, .kv_lens = kvLens, .B = batchSize, .Sq = seqLenNew,
+                                      .d_latent = dLatent, .d_rope = dRope, .dtype = dtype, .scale_fmt = scaleFmt, .sC = sC, .sR = sR,
+                                      .sKV = sKV, .paging = &pg, .stream = stream});
 }
 
 // ---- the MLA index-cache append ----

@@ -61,6 +61,14 @@ struct MlaCfg {
     static_assert(IMG % 16 == 0 && LROW % 16 == 0, "16-byte aligned rows");
 };
 
+// The PACKED latent row (include/flash_attention.h): 512 e4m3fn codes, four fp32 scales -- scale j for the columns
+// [128 j, 128 j + 128) -- and the 64 rotary columns as bf16.  Byte offsets within the row
+struct MlaPackedRow {
+    static constexpr int CODES = 0, SCALES = MlaCfg::DL, ROPE = SCALES + 16, BYTES = ROPE + 2 * MlaCfg::DR;
+    static constexpr int BLOCK = 128;                         // columns under one scale
+    static_assert(BYTES == 656 && BYTES % 16 == 0, "41 chunks of 16 bytes");
+};
+
 // the two launchers of inst_mla_decode.hip: the split kernel (contiguous or paged) and decode_combine_kernel<512>
 int mla_decode_launch(bool paged, unsigned grid, hipStream_t st, const DecodeParams& p);
 int mla_decode_fp8_launch(bool paged, unsigned grid, hipStream_t st, const DecodeParams& p);   // inst_mla_decode_fp8.hip: the KV8 form

@@ -1553,6 +1553,67 @@ int flash_attention_mla_index_append_paged(const void* Knew, void* Kpool, float*
                                            float wScale, const fa_strides* sKnew, const fa_strides* sQraw, void* stream);
 
 /*
+ * THE PACKED LATENT ROW -- the mixed fp8 row the serving engines store for DeepSeek-V3.2: 656 bytes per token,
+ *     bytes [0, 512)     the 512 latent ("nope") columns as OCP e4m3fn codes
+ *     bytes [512, 528)   four fp32 scales, scale j for the columns [128 j, 128 j + 128)
+ *     bytes [528, 656)   the 64 rotary columns as bf16, not quantised
+ * The LOGICAL cache value is a bf16 number: column c < 512 is bf16_rne(fl32(float(code[c]) * scale[c / 128])) -- one fp32 product, then
+ * one round-to-nearest-even to bf16; columns 512 .. 575 are the stored bf16, bit for bit.
+ * KV is uint8 [batchSize, seqLenK, 656] or a pool [numPages, pageSize, 656]; sKV strides are in BYTES, the row stride >= 656 and a
+ * multiple of 16 (FA_ERR_BAD_STRIDE), the base 16-byte aligned.
+ *
+ * flash_attention_mla_sparse_decode_packed, _paged_packed -- the READ: flash_attention_mla_sparse_decode_fp8 / _paged_fp8 without kvDescale
+ * and kv_dtype, on the logical cache above.  Everything else is the sparse call's contract, word for word: a slot is a key iff
+ * 0 <= p < lim; slots that are not keys are never fetched, nor their table entries (their rows may hold any byte, NaN scales
+ * included); duplicates count twice; a row without a key gives O = 0 and LSE = -inf; lengths, indices and the table are read on the
+ * device; numSplits 0 or forced; the plan and the workspace of flash_attention_mla_sparse_plan; validation in the same order with the
+ * same codes; no allocation, capturable.  The result equals flash_attention_mla_sparse_decode on the dequantised bf16 cache bit for
+ * bit under the same split count: the scales are applied on the way into the kernel's LDS image, not folded into the score scale.
+ *
+ * flash_attention_mla_append_packed, _paged_packed -- the WRITE: flash_attention_mla_append / _paged with int scaleFmt in place of
+ * kvDescale and kv_dtype (FA_INDEX_SCALE_F32 or FA_INDEX_SCALE_POW2; anything else FA_ERR_BAD_FLAGS, checked where kv_dtype is).
+ * Positions are flash_attention_mla_append's, word for word: L = min(kvLens[b], capacity) ALREADY counts the new rows, row i goes to
+ * p = L - seqLenNew + i iff p >= 0, L <= 0 writes nothing; only the table entries of pages that receive a row are read; an entry
+ * outside [0, numPages) skips its rows and is never clamped; 1 <= seqLenNew <= capacity.  Values, per block j of 128 latent columns of
+ * a new row, are flash_attention_mla_index_append's steps 5 - 7 on the bf16 inputs:
+ *   amax = max(max |x|, 1e-4f);  s0 = fl32(amax * c1), c1 the fp32 nearest to 1 / 448;  s = s0 (FA_INDEX_SCALE_F32) or the least power
+ *   of two >= s0 (FA_INDEX_SCALE_POW2);  the codes: flash_attention_kv_append's arithmetic under the descale s -- the correctly rounded
+ *   fp32 quotient, saturated at +-448, rounded once to nearest even, the sign of zero kept;  s goes to the block's scale slot;  the
+ *   rotary columns are a bit copy.
+ * A NaN or an infinity in a block leaves that block's 128 codes and its scale unspecified, never a bad address; nothing else is
+ * affected.  No allocation, no synchronisation, no atomics: every cache byte has one writer, and `kv_lens += Sq; mla_index_append;
+ * mla_append_packed; mla_index_topk; mla_sparse_decode_packed` is one graph.
+ * Not done: dense MLA decode on the packed row, ragged forms, a 128-head block.
+ */
+int flash_attention_mla_sparse_decode_packed(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens,
+                                             const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,
+                                             void* workspace,
+                                             int batchSize, int numHeads, int seqLenQ, int seqLenK, int dLatent, int dRope,
+                                             float scale, bool is_causal, int dtype, int o_dtype, int numSplits,
+                                             const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_sparse_decode_paged_packed(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* kvLens,
+                                                   const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,
+                                                   const int32_t* blockTable, void* workspace,
+                                                   int batchSize, int numHeads, int seqLenQ,
+                                                   int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                                   int dLatent, int dRope, float scale, bool is_causal, int dtype, int o_dtype,
+                                                   int numSplits,
+                                                   const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_append_packed(const void* Cnew, const void* Rnew, void* KV, const int32_t* kvLens, int scaleFmt,
+                                      int batchSize, int seqLenNew, int seqLenK, int dLatent, int dRope,
+                                      int dtype /* of Cnew, Rnew: FA_DTYPE_BF16 */,
+                                      const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream);
+
+int flash_attention_mla_append_paged_packed(const void* Cnew, const void* Rnew, void* KVpool, const int32_t* kvLens,
+                                            const int32_t* blockTable, int scaleFmt,
+                                            int batchSize, int seqLenNew,
+                                            int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope,
+                                            int dtype,
+                                            const fa_strides* sC, const fa_strides* sR, const fa_strides* sKV, void* stream);
+
+/*
  * flash_attention_mla_prefill -- the forward pass of multi-head latent attention in its UP-PROJECTED (prefill) form: ordinary multi-head
  * attention whose score and value widths differ,
  *     O = softmax(scale Q K^T [+ mask]) V,   Q [B, H, Sq, 192], K [B, H, Sk, 192], V [B, H, Sk, 128], O [B, H, Sq, 128]

@@ -177,6 +177,11 @@ Each line:
               max_diff_vs_gathered   the largest difference of one result each (bf16 outputs; the same keys in the same order)
               --kv fp8: sparse_fp8_ms, the same lists on the quantised cache; --paged a,b: sparse_paged_ms[page] (and
               sparse_paged_fp8_ms[page]); --splits a,b,c: the forced sweep of the sparse call, one line per (shape, split count).
+              --kv packed (profiles/mla_packed_gpu.log): sparse_fp8_ms as above and, in the same windows,
+              packed_ms       flash_attention_mla_sparse_decode_packed on the same cache as 656-byte rows (per-block scales amax / 448)
+              packed_ratio = packed_ms / sparse_ms (medians);  packed_within_spread: packed_ms <= sparse_ms (1 + spread), the bar
+              paged_packed_ms[page] with --paged;  with --append: append_packed_ms, one mla_cache_append_packed of a new token per
+              sequence at L - 1, beside torch_append_packed_ms, the torch ops that write the same bytes (append_packed_same_bytes)
               With --index TOPK (profiles/mla_index_gpu.log): the indexer, mla_index_topk, on the (B, L) of the
               sparse shapes (H does not enter: 64 index heads x 128 columns, Sq = 1, every sequence full), beside the torch route to the
               same indices, ALTERNATED in the same windows:
@@ -807,6 +812,15 @@ MLA_SHAPES = [  # name, B, H, Sq, L, beside torch: the latent cache is [B, L, 57
 MLA_HBM_TBPS, MLA_MFMA_CYCLES, MLA_LOADED_GHZ, MLA_CUS = 6.3, 16, 1.9, 256
 
 
+def pack_rows(torch, c, r):
+    """bf16 c [.., 512] and r [.., 64] as packed latent rows, uint8 [.., 656]: per block of 128 columns the scale
+    max(amax, 1e-4) / 448 as fp32, the quotient clamped to +-448 as e4m3fn codes; r's bytes.  The torch route to mla_cache_append_packed"""
+    x = c.float().unflatten(-1, (4, 128))
+    s = x.abs().amax(-1).clamp_(min=1e-4) * (1.0 / 448.0)
+    codes = (x / s[..., None]).clamp_(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).flatten(-2)
+    return torch.cat([codes, s.view(torch.uint8), r.contiguous().view(torch.uint8)], -1)
+
+
 def mla_sparse_main(args, fa, dev):
     """--mla --sparse TOPK: flash_attention_mla_sparse_decode* beside gather + dense, dense, and dense at length TOPK, alternated"""
     import torch
@@ -836,10 +850,22 @@ def mla_sparse_main(args, fa, dev):
                   "gathered_ms": gathered,
                   "dense_ms": lambda: fa.flash_attention_mla_decode(Q, KV, lens, O=O, workspace=ws),
                   "dense_topk_ms": lambda: fa.flash_attention_mla_decode(Q, short, None, O=O, workspace=ws)}
-        if args.kv == "fp8":
+        packed = args.kv == "packed"      # the 656-byte row's call beside the bf16 and the one-descale fp8 calls
+        if args.kv == "fp8" or packed:
             ds = (KV.float().abs().amax() / 448.0).reshape(1)
             KV8 = (KV.float() / ds).clamp(-448, 448).to(torch.float8_e4m3fn)
             routes["sparse_fp8_ms"] = lambda: fa.flash_attention_mla_sparse_decode(Q, KV8, idx, lens, O=O, workspace=ws, kv_descale=ds)
+        if packed:
+            KVP = pack_rows(torch, KV[..., :DL], KV[..., DL:])
+            routes["packed_ms"] = lambda: fa.flash_attention_mla_sparse_decode_packed(Q, KVP, idx, lens, O=O, workspace=ws)
+        for page in pages if packed else ():
+            if L % page == 0:
+                n = L // page
+                perm = torch.randperm(B * n, device=dev, generator=g)
+                poolp = torch.empty(B * n, page, KVP.shape[-1], device=dev, dtype=torch.uint8)
+                poolp[perm] = KVP.view(B * n, page, -1)
+                routes[f"paged_packed_ms.{page}"] = lambda poolp=poolp, table=perm.view(B, n).to(torch.int32): \
+                    fa.flash_attention_mla_sparse_decode_paged_packed(Q, poolp, table, idx, lens, O=O, workspace=ws)
         for page in pages:
             if L % page:
                 continue
@@ -885,6 +911,27 @@ def mla_sparse_main(args, fa, dev):
                    spread=round((max(w["sparse_ms"]) - min(w["sparse_ms"])) / ms, 4),
                    beats_gathered=bool(max(w["sparse_ms"]) < min(w["gathered_ms"])),
                    max_diff_vs_gathered=round((a - gathered().float()).abs().max().item(), 5))
+        if packed:      # the bar: packed_ms <= sparse_ms (1 + spread), medians, the bf16 call of the same windows the yardstick
+            pms = statistics.median(w["packed_ms"])
+            out.update(packed_ratio=round(pms / ms, 4), packed_within_spread=bool(pms <= ms * (1 + out["spread"])),
+                       packed_selected_tbps=round(B * Sq * topk * KVP.shape[-1] / pms / 1e9, 3),
+                       max_diff_packed_vs_bf16=round((a - routes["packed_ms"]().float()).abs().max().item(), 5))
+        if packed and args.append:      # one decode step's token (Sq = 1) into the packed cache at L - 1, beside torch to the same bytes
+            c_kv = torch.randn(B, 1, DL, device=dev, generator=g).to(torch.bfloat16)
+            k_pe = torch.randn(B, 1, D - DL, device=dev, generator=g).to(torch.bfloat16)
+            mine, theirs = KVP.clone(), KVP.clone()
+            rows, at = torch.arange(B, device=dev), (lens - 1).long()
+
+            def torch_append():
+                theirs[rows, at] = pack_rows(torch, c_kv, k_pe)[:, 0]
+
+            x = {"append_packed_ms": lambda: fa.mla_cache_append_packed(c_kv, k_pe, mine, lens), "torch_append_packed_ms": torch_append}
+            wa = {k: [] for k in x}
+            for _ in range(args.repeats):
+                for k, fn in x.items():
+                    wa[k].append(timed(fn, args.steps, args.warmup))
+            out.update({k: stats(v) for k, v in wa.items()}, append_packed_same_bytes=bool(torch.equal(mine, theirs)))
+            del mine, theirs
         print(json.dumps(out), flush=True)
         del routes, Q, KV, O, ws, idx, short, w
         torch.cuda.empty_cache()
@@ -1466,7 +1513,8 @@ def main():
     ap.add_argument("--append", action="store_true", help="add append_ms / torch_append_ms / fill_ms / fill_tbps per cache form to every shape's line")
     ap.add_argument("--extend", action="store_true", help="time flash_attention_extend on its own shapes, beside the decode-slice and prefill-pair routes")
     ap.add_argument("--varlen", action="store_true", help="time flash_attention_extend_varlen on mixed batches, beside the grouped calls of today")
-    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line")
+    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8", "packed"],
+                    help="fp8: add fp8_ms / fp8_kv_tbps (and paged_fp8_ms) to every shape's line; packed: with --mla --sparse, the 656-byte row")
     ap.add_argument("--sinks", action="store_true", help="time every shape with and without sinks=, alternated: ms, sink_ms, sink_ratio")
     ap.add_argument("--rope", action="store_true", help="time rope_cache_append* beside the unfused torch route and the plain append, alternated")
     ap.add_argument("--tree", default=None, help="comma-separated draft-node counts: time flash_attention_tree beside its causal twin, alternated")
@@ -1477,6 +1525,8 @@ def main():
     ap.add_argument("--index-append", action="store_true", help="with --mla: time mla_index_append* beside the torch route to the same index cache, alternated")
     ap.add_argument("--mla", action="store_true", help="time flash_attention_mla_decode* beside the same problem from torch ops, alternated; --paged, --splits")
     args = ap.parse_args()
+    if args.kv == "packed" and not (args.mla and args.sparse):
+        ap.error("--kv packed: only the sparse MLA call reads the packed row (--mla --sparse TOPK)")
     import torch
     import __graft_entry__ as entry
     fa = entry.load_package()
