@@ -53,6 +53,10 @@ build/obj/inst_mla_append.o: HIPFLAGS += $(NO_PK_F32)
 # the sparse MLA decode kernel (mla_sparse.hip.h): the dense kernel's accumulators; each unit under the flags of its dense twin
 build/obj/inst_mla_sparse.o: HIPFLAGS += $(MFMA_VGPR)
 build/obj/inst_mla_sparse_fp8.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
+# the sparse MLA prefill kernel (mla_sparse_prefill.hip.h): 128 accumulator registers per wave in eight waves; each unit under the flags
+# of its sparse decode twin
+build/obj/inst_mla_sparse_prefill.o: HIPFLAGS += $(MFMA_VGPR)
+build/obj/inst_mla_sparse_prefill_fp8.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 # its packed-row form (656-byte rows: fp8 codes, per-128-column scales, bf16 rotary columns): built as the fp8 unit; the packed-row
 # append (mla_append_packed.hip.h) pins its scales to the bit in plain fp32
 build/obj/inst_mla_sparse_packed.o: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
@@ -162,8 +166,8 @@ asan: asan-host oracle
 # Device assembly of every library unit, under the flags of its object.  Only the __hip_cuid_ lines differ between two compiles of one
 # source, so they are dropped: a source-level change that is meant to be free can be proved so by comparing build/asm before and after.
 KASM     := $(patsubst $(PKG)/csrc/%.hip,build/asm/%.s,$(KSRC)) $(SPLIT_UNITS:%=build/asm/inst_%.s)
-build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s build/asm/inst_mla_sparse.s: HIPFLAGS += $(MFMA_VGPR)
-build/asm/inst_bf16_mla.s build/asm/inst_mla_decode_fp8.s build/asm/inst_mla_sparse_fp8.s build/asm/inst_mla_sparse_packed.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
+build/asm/inst_bf16_pair_d128.s build/asm/inst_bwd_bf16.s build/asm/inst_mla_decode.s build/asm/inst_mla_sparse.s build/asm/inst_mla_sparse_prefill.s: HIPFLAGS += $(MFMA_VGPR)
+build/asm/inst_bf16_mla.s build/asm/inst_mla_decode_fp8.s build/asm/inst_mla_sparse_fp8.s build/asm/inst_mla_sparse_packed.s build/asm/inst_mla_sparse_prefill_fp8.s: HIPFLAGS += $(MFMA_VGPR) $(NO_PK_F32)
 build/asm/inst_mla_append.s build/asm/inst_mla_index.s build/asm/inst_mla_index_append.s build/asm/inst_mla_append_packed.s: HIPFLAGS += $(NO_PK_F32)
 define ASM_RECIPE
 @mkdir -p build/asm

@@ -102,6 +102,7 @@ EXPORTS = ("flash_attention", "flash_attention_strided", "flash_attention_lse", 
            "flash_attention_mla_sparse_decode_packed", "flash_attention_mla_sparse_decode_paged_packed",
            "flash_attention_mla_append_packed", "flash_attention_mla_append_paged_packed",
            "flash_attention_mla_prefill", "flash_attention_mla_prefill_plan",
+           "flash_attention_mla_sparse_prefill", "flash_attention_mla_sparse_prefill_paged", "flash_attention_mla_sparse_prefill_plan",
            "flash_attention_error_string", "flash_attention_version")
 
 # The C entry point of a K/V-cache call: _SPLIT_SYMBOLS[family, paged, ragged][window > 0][fp8 cache].  Decode has a bf16-only entry
@@ -156,6 +157,8 @@ _MLA_INDEX_APPEND_SYMBOLS = {False: "flash_attention_mla_index_append", True: "f
 _MLA_PACKED_SYMBOLS = {False: "flash_attention_mla_sparse_decode_packed", True: "flash_attention_mla_sparse_decode_paged_packed"}
 _MLA_APPEND_PACKED_SYMBOLS = {False: "flash_attention_mla_append_packed", True: "flash_attention_mla_append_paged_packed"}
 MLA_PACKED_ROW_BYTES = 656
+# ... sparse MLA prefill: _MLA_SPARSE_PREFILL_SYMBOLS[paged], ragged and token-major, both cache types through ``kv_dtype``
+_MLA_SPARSE_PREFILL_SYMBOLS = {False: "flash_attention_mla_sparse_prefill", True: "flash_attention_mla_sparse_prefill_paged"}
 FA_INDEX_SCALE_F32, FA_INDEX_SCALE_POW2 = 0, 1     # scaleFmt: the row's scale as computed, or rounded up to a power of two (ue8m0)
 _PLAN_SYMBOLS = {("decode", False): ("flash_attention_decode_plan", "flash_attention_decode_plan_window"),
                  ("extend", False): ("flash_attention_extend_plan", "flash_attention_extend_plan_window"),
@@ -322,6 +325,13 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, _MLA_INDEX_APPEND_SYMBOLS[paged])
             fn.argtypes = [vp] * 9 + [vp] * paged + [i, i] + paging(paged) + [i] * 6 + [f, sp, sp, vp]
             fn.restype = i
+            # ... sparse prefill: Q, KV, O, LSE, cuSeqlensQ, kvLens, indices with topk and its token stride, the table (paged),
+            # kvDescale; the shape with totalQ where seqLenQ stands; both dtypes; no workspace, no split count
+            fn = getattr(L, _MLA_SPARSE_PREFILL_SYMBOLS[paged])
+            fn.argtypes = [vp] * 6 + [vp, i, i64] + [vp] * paged + [vp] + [i] * 3 + paging(paged) + [i, i, f, b, i, i, i] + [sp] * 3 + [vp]
+            fn.restype = i
+        L.flash_attention_mla_sparse_prefill_plan.argtypes = [i] * 7 + [ctypes.POINTER(FaDecodePlan)]
+        L.flash_attention_mla_sparse_prefill_plan.restype = i
         L.flash_attention_mla_decode_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
         L.flash_attention_mla_decode_plan.restype = i
         L.flash_attention_mla_sparse_plan.argtypes = [i] * 8 + [ctypes.POINTER(FaDecodePlan)]
@@ -1285,6 +1295,98 @@ def flash_attention_mla_sparse_decode_paged_packed(Q, KV_pool, block_table, indi
         raise ValueError("indices must be an int32 tensor [B, Sq, topk] on the device of Q")
     return _mla_front(Q, KV_pool, block_table, kv_lens, scale, is_causal, out_dtype, num_splits, return_lse, O, workspace, stream, None,
                       indices, packed=True)
+
+
+# ---- sparse MLA prefill: the sparse rule on ragged token-major tensors, a unit per (token, 128 heads) ----
+def mla_sparse_prefill_plan(B, H, total_q, topk, o_dtype=FA_DTYPE_BF16):
+    """What a flash_attention_mla_sparse_prefill call launches (fa_decode_plan as a dict): a unit is (token, block of 128 heads),
+    ``rows_per_block = 128``, ``row_blocks = ceil(H / 128)``, ``num_splits = 1``, ``grid = total_q * row_blocks``, 512 threads, no
+    combine.  There is no workspace."""
+    p = FaDecodePlan()
+    _check(lib().flash_attention_mla_sparse_prefill_plan(B, H, total_q, topk, MLA_D_LATENT, MLA_D_ROPE, o_dtype, ctypes.byref(p)))
+    return _plan_dict(p)
+
+
+def _mla_sparse_prefill_front(Q, KV, block_table, indices, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, return_lse, O, stream,
+                              kv_descale):
+    """Both sparse prefill fronts: the checks of the token-major tensors, then -- with _mla_front's helpers for the table, the lengths
+    and the descale -- the entry point of _MLA_SPARSE_PREFILL_SYMBOLS.  An O or LSE allocated here is zero-filled: tokens no sequence
+    owns are not written."""
+    import torch
+    paged = block_table is not None
+    name = _MLA_SPARSE_PREFILL_SYMBOLS[paged]
+    if indices is None or cu_seqlens_q is None:
+        raise ValueError("indices [T, topk] and cu_seqlens_q [B + 1] are required int32 device tensors")
+    if not (Q.is_cuda and KV.is_cuda and indices.is_cuda and (not paged or block_table.is_cuda)):
+        raise RuntimeError(f"{name} needs device tensors (no CPU fallback)")
+    D = MLA_D_LATENT + MLA_D_ROPE
+    if Q.dim() != 3 or KV.dim() != 3 or Q.shape[2] != D or KV.shape[2] != D:
+        raise ValueError(f"Q must be packed by token, [T, H, {D}], and {'KV_pool [P, page' if paged else 'KV [B, capacity'}, {D}]")
+    B = _cu_seqlens(cu_seqlens_q, Q)
+    if not paged and KV.shape[0] != B:
+        raise ValueError("KV [B, capacity, 576] must hold one cache per sequence of cu_seqlens_q")
+    f8 = getattr(torch, "float8_e4m3fn", None)
+    fp8 = f8 is not None and KV.dtype == f8 and Q.dtype == torch.bfloat16
+    if not fp8 and Q.dtype != KV.dtype:
+        raise TypeError("Q, KV must share a dtype")
+    _mla_descale(kv_descale, fp8, Q.device)
+    if Q.stride(2) != 1 or KV.stride(2) != 1:
+        raise ValueError("last dimension must be contiguous")
+    T, H, _ = Q.shape
+    if indices.dtype != torch.int32 or indices.device != Q.device or indices.dim() != 2 or indices.shape[0] != T \
+            or indices.shape[1] < 1 or indices.stride(1) != 1:
+        raise ValueError("indices must be an int32 tensor [T, topk >= 1] on the device of Q with a contiguous last dimension")
+    capacity, tables, geometry = _cache_geometry(KV.unsqueeze(1), block_table, B)
+    _check_kv_lens(kv_lens, B)
+    if scale is None:
+        scale = float(D) ** -0.5
+    with torch.cuda.device(Q.device):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if O is None:
+                O = torch.zeros((T, H, MLA_D_LATENT), dtype=out_dtype or _default_out_dtype(Q.dtype), device=Q.device)
+            elif tuple(O.shape) != (T, H, MLA_D_LATENT) or not O.is_cuda or O.stride(2) != 1:
+                raise ValueError(f"O must be a device tensor [T, H, {MLA_D_LATENT}] with a contiguous last dimension")
+            lse = torch.zeros((H, T), dtype=torch.float32, device=Q.device) if return_lse else None
+        sQ, sO = FaStrides(0, Q.stride(1), Q.stride(0)), FaStrides(0, O.stride(1), O.stride(0))
+        sKV = FaStrides(KV.stride(0), 0, KV.stride(1))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = getattr(lib(), name)(Q.data_ptr(), KV.data_ptr(), O.data_ptr(), ptr(lse), cu_seqlens_q.data_ptr(), ptr(kv_lens),
+                                  indices.data_ptr(), indices.shape[1], indices.stride(0) if T > 1 else indices.shape[1],
+                                  *map(ptr, tables), ptr(kv_descale), B, H, T, *geometry, MLA_D_LATENT, MLA_D_ROPE, float(scale),
+                                  bool(is_causal), _dtype_code(Q.dtype), _dtype_code(KV.dtype), _dtype_code(O.dtype),
+                                  ctypes.byref(sQ), ctypes.byref(sKV), ctypes.byref(sO), _stream_ptr(s))
+    _check(rc)
+    return (O, lse) if return_lse else O
+
+
+def flash_attention_mla_sparse_prefill(Q, KV, indices, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False, out_dtype=None,
+                                       return_lse=False, O=None, stream=None, kv_descale=None):
+    """SPARSE MLA PREFILL: ``flash_attention_mla_sparse_decode``'s rule on a RAGGED token-major batch -- a prompt, a chunk of a
+    chunked prefill, a mixed continuous-batching step -- with any number of tokens per sequence.  ``Q [T, H, 576]`` bf16 packed by
+    token, ``KV [B, capacity, 576]`` (bf16, or ``torch.float8_e4m3fn`` with ``kv_descale``), ``indices`` int32 ``[T, topk]`` (one list
+    per token, shared by its heads), ``cu_seqlens_q`` int32 ``[B + 1]`` as in ``flash_attention_extend_varlen``: sequence b owns the
+    tokens ``[cu[b], cu[b + 1])``, T is a bound, and tokens no sequence owns are neither read nor written (an O or LSE allocated here
+    holds zeros there).  Token j of sequence b sees slot t iff ``0 <= indices[tok, t] < lim``, ``lim = len_b`` or, under
+    ``is_causal``, ``max(len_b - sq_b + j + 1, 1)`` with ``kv_lens[b]`` already counting the new rows; a position in two slots counts
+    twice; a token without a key gives ``O = 0``, ``LSE = -inf``.  Returns ``O [T, H, 512]`` (and the LSE ``[H, T]``).
+
+    One launch, no workspace, nothing allocated by the library: a workgroup of eight waves serves (token, 128 heads), so a gathered row
+    is fetched once per 128 heads.  A token's result equals ``flash_attention_mla_sparse_decode`` on that token alone under one split,
+    bit for bit.  ``scale`` None = ``576 ** -0.5``.  Indices, lengths and ``cu_seqlens_q`` are read on the device: a captured call
+    sees the values of the replay.  No CPU fallback."""
+    return _mla_sparse_prefill_front(Q, KV, None, indices, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, return_lse, O, stream,
+                                     kv_descale)
+
+
+def flash_attention_mla_sparse_prefill_paged(Q, KV_pool, block_table, indices, cu_seqlens_q, kv_lens=None, scale=None, is_causal=False,
+                                             out_dtype=None, return_lse=False, O=None, stream=None, kv_descale=None):
+    """``flash_attention_mla_sparse_prefill`` against a PAGED latent cache, ``KV_pool [P, page, 576]`` and ``block_table`` int32
+    ``[B, max_pages]`` as in ``flash_attention_mla_sparse_decode_paged``: ``indices`` hold logical positions, the kernel reads and clamps
+    the table entries itself and reads none for a slot that is not a key.  The result is the contiguous call's on a gathered copy, bit
+    for bit."""
+    return _mla_sparse_prefill_front(Q, KV_pool, block_table, indices, cu_seqlens_q, kv_lens, scale, is_causal, out_dtype, return_lse, O,
+                                     stream, kv_descale)
 
 
 # ---- the MLA sparse-attention indexer (DESIGN.md section 39): fp8 index logits and the top-k positions of every query row ----

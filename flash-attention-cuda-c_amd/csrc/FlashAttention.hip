@@ -26,6 +26,7 @@
 #include "rope_append.hip.h"
 #include "mla_decode.hip.h"
 #include "mla_sparse.hip.h"
+#include "mla_sparse_prefill.hip.h"
 #include "mla_index.hip.h"
 #include "mla_append.hip.h"
 #include "mla_append_packed.hip.h"
@@ -1028,6 +1029,95 @@ static int mla_run(MlaCall c) {
                                          : mla_decode_launch(pg != nullptr, (unsigned)r.grid, st, p);
     if (rc != FA_OK || r.ns == 1) return rc;
     return mla_combine_launch((unsigned)rows, st, p);
+}
+
+// ---- sparse MLA prefill: flash_attention_mla_sparse_prefill* (mla_sparse_prefill.hip.h) ----
+// The sparse call on RAGGED token-major tensors: totalQ bounds the packed tokens, cu_seqlens_q (device memory) says which sequence owns
+// which, every token has its own index list.  A unit is (token, block of 128 heads) and walks all its slot tiles: one launch, no
+// split, no workspace
+struct MlaSparsePrefillCall {
+    const void* Q;
+    const void* KV;
+    void* O;
+    float* LSE;
+    const int32_t *cu_seqlens_q, *kv_lens, *indices;
+    int topk;
+    int64_t index_stride_q;
+    const float* kv_descale;
+    int B, H, total_q, capacity, d_latent, d_rope;
+    float scale;
+    bool is_causal;
+    int dtype, kv_dtype, o_dtype;
+    const fa_strides *sQ, *sKV, *sO;
+    const DecodePaging* paging;
+    void* stream;
+};
+
+// the shape of a call or a plan, in mla_check_shape's order; totalQ stands where seqLenQ stands, uncapped
+static int mla_sparse_prefill_check_shape(const MlaSparsePrefillCall& c, int64_t& grid) {
+    const int B = c.B, H = c.H, T = c.total_q, Sk = c.capacity;
+    if (B <= 0 || H <= 0 || T <= 0 || Sk <= 0 || c.d_latent <= 0 || c.d_rope <= 0) return FA_ERR_BAD_SHAPE;
+    if (Sk > (1 << 24) || (int64_t)B * H > INT32_MAX / 2 || (int64_t)H * T > INT32_MAX) return FA_ERR_BAD_SHAPE;
+    if (B > FA_VARLEN_MAX_BATCH) return FA_ERR_BAD_SHAPE;
+    if (c.topk < 1 || c.topk > MLA_SPARSE_MAX_TOPK) return FA_ERR_BAD_SHAPE;
+    if (c.dtype != FA_DTYPE_BF16) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (!is_output_dtype(c.o_dtype)) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.d_latent != MlaCfg::DL || c.d_rope != MlaCfg::DR) return FA_ERR_UNSUPPORTED_DHEAD;
+    grid = (int64_t)T * ((H + MlaSparsePrefillCfg::ROWS - 1) / MlaSparsePrefillCfg::ROWS);
+    if (grid >= FA_DECODE_MAX_WORKGROUPS) return FA_ERR_BAD_SHAPE;
+    return FA_OK;
+}
+
+// mla_run's ladder in its order with its codes; cuSeqlensQ stands with the pointers and with the arrays' 4-byte alignment, totalQ with
+// the shapes, indexStrideQ with the strides.  One launch
+static int mla_sparse_prefill_run(MlaSparsePrefillCall c) {
+    const DecodePaging* pg = c.paging;
+    constexpr int D = MlaCfg::D, DL = MlaCfg::DL;
+    if (!c.Q || !c.KV || !c.O || (pg && !pg->table) || !c.indices || !c.cu_seqlens_q) return FA_ERR_NULL_POINTER;
+    if (!aligned16(c.Q) || !aligned16(c.KV) || !aligned16(c.O) || !aligned16(c.LSE)) return FA_ERR_MISALIGNED;
+    fa_strides tKV{};   // the cache's strides without the head stride, which no MLA call reads
+    if (c.sKV) tKV = fa_strides{c.sKV->strideB, 0, c.sKV->strideS};
+    KvCache cache{.K = c.KV, .V = c.KV, .kv_lens = c.kv_lens, .k_descale = c.kv_descale, .v_descale = c.kv_descale,
+                  .kv_dtype = c.kv_dtype, .capacity = c.capacity,
+                  .sK = c.sKV ? &tKV : nullptr, .sV = c.sKV ? &tKV : nullptr, .paging = pg};
+    int rc = cache_check_arrays(cache, c.cu_seqlens_q);
+    if (rc != FA_OK) return rc;
+    if (misaligned4(c.indices)) return FA_ERR_MISALIGNED;
+    if ((rc = cache_capacity(cache)) != FA_OK) return rc;
+    c.capacity = cache.capacity;
+    int64_t grid = 0;
+    if ((rc = mla_sparse_prefill_check_shape(c, grid)) != FA_OK) return rc;
+    if (c.kv_dtype != FA_DTYPE_BF16 && c.kv_dtype != FA_DTYPE_FP8_E4M3) return FA_ERR_UNSUPPORTED_DTYPE;
+    if (c.kv_dtype == FA_DTYPE_BF16 && c.kv_descale) return FA_ERR_UNSUPPORTED_DTYPE;   // (the descale belongs to an fp8 cache)
+    if (!std::isfinite(c.scale) || !(c.scale > 0.f)) return FA_ERR_BAD_SCALE;
+    const fa_strides tQ = token_strides(c.sQ, c.H, D), tO = token_strides(c.sO, c.H, DL);
+    if (!strides_ok(&tQ, 2, D) || !cache_strides_ok(cache, D) || !strides_ok(&tO, elem_size(c.o_dtype), DL)) return FA_ERR_BAD_STRIDE;
+    if (c.index_stride_q < c.topk) return FA_ERR_BAD_STRIDE;
+    if (!cache_extent_ok(cache, D)) return FA_ERR_BAD_SHAPE;
+
+    MlaSparsePrefillParams p{};
+    p.Q = (const __bf16*)c.Q; p.K = (const __bf16*)c.KV; p.V = (const __bf16*)c.KV; p.O = c.O; p.lse = c.LSE;
+    p.kv_lens = c.kv_lens;
+    p.qB = 0; p.qH = tQ.strideH; p.qS = tQ.strideS;
+    resolve_strides(cache.sK, 1, cache_rows(cache), D, p.kB, p.kH, p.kS);
+    p.vB = p.kB; p.vH = p.kH; p.vS = p.kS;
+    p.oB = 0; p.oH = tO.strideH; p.oS = tO.strideS;
+    p.H = c.H; p.Hkv = 1; p.G = c.H; p.Sq = c.total_q; p.Sk = cache.capacity;
+    p.row_blocks = (c.H + MlaSparsePrefillCfg::ROWS - 1) / MlaSparsePrefillCfg::ROWS; p.ns = 1;
+    p.rows = (int)((int64_t)c.H * c.total_q);
+    p.o_dtype = c.o_dtype;
+    p.causal = c.is_causal;
+    p.scale_log2 = c.scale * 1.4426950408889634f;
+    p.block_table = pg ? pg->table : nullptr;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.num_pages = pg ? pg->num_pages : 0;
+    p.page_shift = pg ? __builtin_ctz((unsigned)pg->page_size) : 0;
+    p.k_descale = p.v_descale = c.kv_descale;
+    p.indices = c.indices; p.topk = c.topk; p.isB = 0; p.isQ = c.index_stride_q;
+    p.cu_q = c.cu_seqlens_q; p.B = c.B;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    return c.kv_dtype == FA_DTYPE_FP8_E4M3 ? mla_sparse_prefill_fp8_launch(pg != nullptr, (unsigned)grid, st, p)
+                                           : mla_sparse_prefill_launch(pg != nullptr, (unsigned)grid, st, p);
 }
 
 // ---- the MLA sparse-attention indexer: flash_attention_mla_index_topk* (mla_index.hip.h) ----
@@ -2344,6 +2434,55 @@ int flash_attention_mla_sparse_decode_paged_packed(const void* Q, const void* KV
 }
 #undef FA_SPARSE_ARGS
 #undef FA_SPARSE_FIELDS
+
+// ---- sparse MLA prefill ----
+int flash_attention_mla_sparse_prefill_plan(int batchSize, int numHeads, int totalQ, int topk, int dLatent, int dRope, int o_dtype,
+                                            fa_decode_plan* plan) {
+    using namespace fa;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    // (the capacity does not enter the launch: any valid one stands for it in the shape check)
+    const MlaSparsePrefillCall c{.topk = topk, .B = batchSize, .H = numHeads, .total_q = totalQ, .capacity = 1, .d_latent = dLatent,
+                                 .d_rope = dRope, .dtype = FA_DTYPE_BF16, .kv_dtype = FA_DTYPE_BF16, .o_dtype = o_dtype};
+    int64_t grid = 0;
+    const int rc = mla_sparse_prefill_check_shape(c, grid);
+    if (rc != FA_OK) return rc;
+    plan->num_splits = 1;
+    plan->row_blocks = (numHeads + MlaSparsePrefillCfg::ROWS - 1) / MlaSparsePrefillCfg::ROWS;
+    plan->rows_per_block = MlaSparsePrefillCfg::ROWS;
+    plan->kv_block_rows = MlaCfg::KT;
+    plan->threads = MlaSparsePrefillCfg::THREADS;
+    plan->grid = (int)grid;
+    plan->lds_bytes = MlaSparsePrefillCfg::LDS_BYTES;
+    plan->combine_grid = 0;
+    plan->combine_threads = 0;
+    return FA_OK;
+}
+
+int flash_attention_mla_sparse_prefill(const void* Q, const void* KV, void* O, float* LSE, const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                       const int32_t* indices, int topk, int64_t indexStrideQ, const float* kvDescale, int batchSize,
+                                       int numHeads, int totalQ, int seqLenK, int dLatent, int dRope, float scale, bool is_causal, int dtype,
+                                       int kv_dtype, int o_dtype, const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO,
+                                       void* stream) {
+    return fa::mla_sparse_prefill_run({.Q = Q, .KV = KV, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ, .kv_lens = kvLens,
+                                       .indices = indices, .topk = topk, .index_stride_q = indexStrideQ, .kv_descale = kvDescale,
+                                       .B = batchSize, .H = numHeads, .total_q = totalQ, .capacity = seqLenK, .d_latent = dLatent,
+                                       .d_rope = dRope, .scale = scale, .is_causal = is_causal, .dtype = dtype, .kv_dtype = kv_dtype,
+                                       .o_dtype = o_dtype, .sQ = sQ, .sKV = sKV, .sO = sO, .stream = stream});
+}
+
+int flash_attention_mla_sparse_prefill_paged(const void* Q, const void* KVpool, void* O, float* LSE, const int32_t* cuSeqlensQ,
+                                             const int32_t* kvLens, const int32_t* indices, int topk, int64_t indexStrideQ,
+                                             const int32_t* blockTable, const float* kvDescale, int batchSize, int numHeads, int totalQ,
+                                             int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride, int dLatent, int dRope,
+                                             float scale, bool is_causal, int dtype, int kv_dtype, int o_dtype, const fa_strides* sQ,
+                                             const fa_strides* sKV, const fa_strides* sO, void* stream) {
+    const fa::DecodePaging pg{blockTable, tableStride, numPages, pageSize, maxPagesPerSeq};
+    return fa::mla_sparse_prefill_run({.Q = Q, .KV = KVpool, .O = O, .LSE = LSE, .cu_seqlens_q = cuSeqlensQ, .kv_lens = kvLens,
+                                       .indices = indices, .topk = topk, .index_stride_q = indexStrideQ, .kv_descale = kvDescale,
+                                       .B = batchSize, .H = numHeads, .total_q = totalQ, .d_latent = dLatent, .d_rope = dRope,
+                                       .scale = scale, .is_causal = is_causal, .dtype = dtype, .kv_dtype = kv_dtype, .o_dtype = o_dtype,
+                                       .sQ = sQ, .sKV = sKV, .sO = sO, .paging = &pg, .stream = stream});
+}
 
 // ---- the MLA sparse-attention indexer ----
 int flash_attention_mla_index_topk(const void* Qidx, const float* W, const void* Kidx, const float* kScale, const int32_t* kvLens,

@@ -1371,8 +1371,8 @@ int flash_attention_mla_decode_paged_fp8(const void* Q, const void* KVpool, void
  * not enter.  The workspace of a call is flash_attention_mla_decode_workspace_size(batchSize, numHeads, seqLenQ, 512, num_splits)
  * with THIS plan's num_splits.
  *
- * Not done: seqLenQ above FA_DECODE_MAX_Q (sparse prefill), per-128-column fp8 scales, windows, sinks and tree masks on the sparse
- * call, a 128-head block.
+ * Not done: per-128-column fp8 scales here (the packed calls, below), windows, sinks and tree masks on the sparse call.  seqLenQ above
+ * FA_DECODE_MAX_Q and a 128-head block are flash_attention_mla_sparse_prefill's (below).
  */
 int flash_attention_mla_sparse_plan(int batchSize, int numHeads, int seqLenQ, int topk, int dLatent, int dRope,
                                     int o_dtype, int numSplits /* 0 = the library chooses */, fa_decode_plan* plan);
@@ -1407,6 +1407,60 @@ int flash_attention_mla_sparse_decode_paged_fp8(const void* Q, const void* KVpoo
                                                 int dLatent, int dRope, float scale, bool is_causal, int dtype, int kv_dtype,
                                                 int o_dtype, int numSplits,
                                                 const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+/*
+ * flash_attention_mla_sparse_prefill, _paged -- SPARSE MLA PREFILL: flash_attention_mla_sparse_decode's rule for a
+ * RAGGED, token-major batch with any number of query tokens per sequence -- a prompt, a chunk of a chunked prefill, a mixed
+ * continuous-batching step -- on the conventions of flash_attention_extend_varlen.  Both calls serve bf16 and e4m3fn caches through
+ * kv_dtype (FA_DTYPE_BF16, or FA_DTYPE_FP8_E4M3 with kvDescale, the ONE fp32 descale of flash_attention_mla_decode_fp8; kvDescale must
+ * be NULL with a bf16 cache, FA_ERR_UNSUPPORTED_DTYPE).
+ *   Q            bf16, PACKED BY TOKEN [totalQ, numHeads, 576]: token t, head h at t * strideS + h * strideH (strideB is ignored)
+ *   O            [totalQ, numHeads, 512] in o_dtype (F32, BF16, F16) on token strides; LSE optional dense fp32 [numHeads, totalQ],
+ *                row h * totalQ + t
+ *   KV           the latent cache [batchSize, capacity, 576]; paged: the pool [numPages, pageSize, 576] behind blockTable, with the
+ *                geometry arguments of flash_attention_mla_sparse_decode_paged
+ *   totalQ       a HOST-side BOUND on the packed tokens, >= 1, not capped.  cuSeqlensQ: DEVICE int32 [batchSize + 1], 4-byte aligned,
+ *                required, read and clamped by the kernel as in flash_attention_extend_varlen: sequence b owns the tokens [q0, q1),
+ *                sq_b = q1 - q0 (0 is legal: an idle slot).  Tokens no sequence owns -- [cuSeqlensQ[batchSize], totalQ) among them --
+ *                are not read and not written: not O, not the LSE.  batchSize <= FA_VARLEN_MAX_BATCH
+ *   indices      DEVICE int32 [totalQ, topk], token stride indexStrideQ >= topk elements: one list per token, shared by its heads
+ *   rule         token j of sequence b, len_b = clamp(kvLens[b], 1, capacity): slot t is a key iff 0 <= indices[tok, t] < lim, lim = len_b
+ *                or, under is_causal, max(len_b - sq_b + j + 1, 1).  Any other slot is not a key: its row is never read, paged neither
+ *                is its table entry.  A position in two slots is two keys.  A token without a key: O = 0, LSE = -inf.  kvLens[b]
+ *                ALREADY counts the new rows, as in flash_attention_extend_varlen
+ *   seam         a token's O and LSE are, BIT FOR BIT, flash_attention_mla_sparse_decode*'s of the same cache form for that token alone
+ *                (batchSize = 1, seqLenQ = 1, numSplits = 1, not causal, kvLens = the token's lim); paged equals contiguous on a
+ *                gathered copy
+ * No workspace argument, no allocation, no host synchronisation, graph-capturable: indices, lengths, cuSeqlensQ and the table are read
+ * on the device.  One launch: a unit is (token, block of 128 heads) -- a gathered row is fetched once per 128 heads -- and walks all
+ * ceil(topk / 32) slot tiles itself; no split, no combine.
+ * flash_attention_mla_sparse_prefill_plan -- fa_decode_plan of such a call: rows_per_block = 128, row_blocks = ceil(numHeads / 128),
+ * num_splits = 1, grid = totalQ * row_blocks (below FA_DECODE_MAX_WORKGROUPS, else FA_ERR_BAD_SHAPE), threads = 512, no combine; the
+ * workspace size is 0.
+ * Rejected before the launch, in flash_attention_mla_sparse_decode's order with its codes; the new arguments stand with their kind: a
+ * NULL cuSeqlensQ with the pointers, its 4-byte alignment with the arrays', totalQ < 1, batchSize > FA_VARLEN_MAX_BATCH, numHeads *
+ * totalQ > INT32_MAX and the grid with the shapes, indexStrideQ < topk with the strides.
+ * Not done: the packed 656-byte row, windows, sinks, the prefill indexer (flash_attention_mla_index_topk above FA_DECODE_MAX_Q rows).
+ */
+int flash_attention_mla_sparse_prefill_plan(int batchSize, int numHeads, int totalQ, int topk, int dLatent, int dRope, int o_dtype,
+                                            fa_decode_plan* plan);
+
+int flash_attention_mla_sparse_prefill(const void* Q, const void* KV, void* O, float* LSE,
+                                       const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                       const int32_t* indices, int topk, int64_t indexStrideQ, const float* kvDescale,
+                                       int batchSize, int numHeads, int totalQ, int seqLenK, int dLatent, int dRope,
+                                       float scale, bool is_causal, int dtype /* of Q */, int kv_dtype, int o_dtype,
+                                       const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
+
+int flash_attention_mla_sparse_prefill_paged(const void* Q, const void* KVpool, void* O, float* LSE,
+                                             const int32_t* cuSeqlensQ, const int32_t* kvLens,
+                                             const int32_t* indices, int topk, int64_t indexStrideQ,
+                                             const int32_t* blockTable, const float* kvDescale,
+                                             int batchSize, int numHeads, int totalQ,
+                                             int numPages, int pageSize, int maxPagesPerSeq, int64_t tableStride,
+                                             int dLatent, int dRope, float scale, bool is_causal, int dtype /* of Q */, int kv_dtype,
+                                             int o_dtype,
+                                             const fa_strides* sQ, const fa_strides* sKV, const fa_strides* sO, void* stream);
 
 /*
  * flash_attention_mla_index_topk, flash_attention_mla_index_topk_paged -- the INDEXER of sparse MLA decode (DESIGN.md section 39;
@@ -1583,7 +1637,7 @@ int flash_attention_mla_index_append_paged(const void* Knew, void* Kpool, float*
  * A NaN or an infinity in a block leaves that block's 128 codes and its scale unspecified, never a bad address; nothing else is
  * affected.  No allocation, no synchronisation, no atomics: every cache byte has one writer, and `kv_lens += Sq; mla_index_append;
  * mla_append_packed; mla_index_topk; mla_sparse_decode_packed` is one graph.
- * Not done: dense MLA decode on the packed row, ragged forms, a 128-head block.
+ * Not done: dense MLA decode on the packed row, ragged forms and a 128-head block on the packed row.
  */
 int flash_attention_mla_sparse_decode_packed(const void* Q, const void* KV, void* O, float* LSE, const int32_t* kvLens,
                                              const int32_t* indices, int topk, int64_t indexStrideB, int64_t indexStrideQ,

@@ -1081,9 +1081,85 @@ def mla_index_append_main(args, fa, dev):
         torch.cuda.empty_cache()
 
 
+# --mla --sparse-prefill: name, [(new tokens, cache rows) per sequence]
+MLA_SPARSE_PREFILL_SHAPES = [
+    ("prompt4096_8k", [(4096, 8192)]),
+    ("batch8_chunk512_4k", [(512, 4096)] * 8),
+    ("mixed_64dec_chunk1024", [(1, 4096)] * 64 + [(1024, 4096)]),
+]
+
+
+def mla_sparse_prefill_main(args, fa, dev):
+    """--mla --sparse-prefill TOPK: flash_attention_mla_sparse_prefill beside today's route, flash_attention_mla_sparse_decode in slices
+    of FA_DECODE_MAX_Q rows under the planned split count (every host call of the route included), alternated in one process; the
+    median of --repeats windows and the run's own spread.  Distinct random positions below every token's limit: the worst case for
+    locality.  max_diff_vs_sliced compares against the sliced route under ONE forced split, where the keys and their order are the same"""
+    import torch
+    topk, MQ = args.sparse_prefill, fa.FA_DECODE_MAX_Q
+    g = torch.Generator(device=dev).manual_seed(11)
+    for name, seqs in MLA_SPARSE_PREFILL_SHAPES:
+        if args.shape and name not in args.shape:
+            continue
+        for H in (16, 128):
+            B, cap = len(seqs), max(c for _, c in seqs)
+            rows = [n for n, _ in seqs]
+            cu = [0]
+            for n in rows:
+                cu.append(cu[-1] + n)
+            T = cu[-1]
+            Q = torch.randn((T, H, 576), device=dev, generator=g).to(torch.bfloat16)
+            KV = torch.randn((B, cap, 576), device=dev, generator=g).to(torch.bfloat16)
+            lens = torch.tensor([c for _, c in seqs], dtype=torch.int32, device=dev)
+            cud = torch.tensor(cu, dtype=torch.int32, device=dev)
+            lim = torch.cat([torch.arange(c - n + 1, c + 1, device=dev) for n, c in seqs])                  # causal: the token's limit
+            key = torch.rand((T, cap), device=dev, generator=g).masked_fill(torch.arange(cap, device=dev)[None] >= lim[:, None], 2.0)
+            idx = key.argsort(1)[:, :topk].to(torch.int32).contiguous()
+            del key
+            O = torch.zeros((T, H, 512), dtype=torch.bfloat16, device=dev)
+            prefill = lambda out=O: fa.flash_attention_mla_sparse_prefill(Q, KV, idx, cud, lens, is_causal=True, O=out)
+            # today's route: sequences with the same row count share a call; a chunk goes in slices of MQ rows
+            slices = []
+            for n in sorted(set(rows)):
+                bs = [b for b in range(B) if rows[b] == n]
+                assert bs == list(range(bs[0], bs[-1] + 1))
+                t0 = cu[bs[0]]
+                view = lambda t, w: t[t0:t0 + len(bs) * n].view(len(bs), n, *t.shape[1:])
+                for s0 in range(0, n, MQ):
+                    m = min(MQ, n - s0)
+                    slices.append((view(Q, 576)[:, s0:s0 + m].transpose(1, 2), KV[bs[0]:bs[-1] + 1], view(idx, topk)[:, s0:s0 + m],
+                                   (lens[bs[0]:bs[-1] + 1] - n + s0 + m).contiguous(), (bs[0], n, s0, m, len(bs))))
+            def sliced(out, ns, ws):
+                for q, kv, ix, ln, (b0, n, s0, m, nb) in slices:
+                    o = out[cu[b0]:cu[b0] + nb * n].view(nb, n, H, 512)[:, s0:s0 + m].transpose(1, 2)
+                    fa.flash_attention_mla_sparse_decode(q, kv, ix, ln, is_causal=True, num_splits=ns, O=o, workspace=ws)
+            need = max(fa.decode_workspace_size(nb, H, m, 512, fa.mla_sparse_plan(nb, H, m, topk, fa.FA_DTYPE_BF16, 0)["num_splits"])
+                       for *_, (b0, n, s0, m, nb) in slices)
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            planned = sorted({fa.mla_sparse_plan(nb, H, m, topk, fa.FA_DTYPE_BF16, 0)["num_splits"] for *_, (b0, n, s0, m, nb) in slices})
+            O1 = torch.zeros_like(O)
+            prefill()
+            sliced(O1, 1, ws)
+            torch.cuda.synchronize()
+            diff = (O.float() - O1.float()).abs().max().item()
+            a, b = [], []
+            for _ in range(args.repeats):
+                a.append(timed(prefill, args.steps, 1))
+                b.append(timed(lambda: sliced(O1, 0, ws), args.steps, 1))
+            med = lambda v: sorted(v)[len(v) // 2]
+            pm, sm = med(a), med(b)
+            spread = max((max(a) - min(a)) / pm, (max(b) - min(b)) / sm)
+            flop = 2.0 * T * H * topk * (576 + 512)
+            print(json.dumps({"bench": "mla_sparse_prefill", "shape": name, "H": H, "tokens": T, "batch": B, "topk": topk,
+                              "prefill_ms": round(pm, 4), "tflops": round(flop / pm / 1e9, 1), "sliced_decode_ms": round(sm, 4),
+                              "sliced_calls": len(slices), "sliced_planned_splits": planned, "ratio": round(sm / pm, 3),
+                              "spread": round(spread, 4), "max_diff_vs_sliced": diff}), flush=True)
+
+
 def mla_main(args, fa, dev):
     """--mla: flash_attention_mla_decode* beside the same problem from torch ops, alternated"""
     import torch
+    if args.sparse_prefill:
+        return mla_sparse_prefill_main(args, fa, dev)
     if args.index_append:
         return mla_index_append_main(args, fa, dev)
     if args.sparse:
@@ -1521,6 +1597,7 @@ def main():
     ap.add_argument("--cascade", action="store_true", help="time flash_attention_cascade_decode* beside flash_attention_decode* on a shared prefix, alternated; --splits s:u,...")
     ap.add_argument("--accept", action="store_true", help="with --tree N: time kv_cache_accept* beside gather + re-append, and rope_cache_append*(pos_offsets=) beside its twin")
     ap.add_argument("--sparse", type=int, default=0, help="with --mla: time flash_attention_mla_sparse_decode* at this topk beside gather + dense, alternated")
+    ap.add_argument("--sparse-prefill", type=int, default=0, help="with --mla: time flash_attention_mla_sparse_prefill at this topk beside the sparse decode call in 16-row slices, alternated")
     ap.add_argument("--index", type=int, default=0, help="with --mla: time mla_index_topk at this topk beside the torch route to the same indices, alternated")
     ap.add_argument("--index-append", action="store_true", help="with --mla: time mla_index_append* beside the torch route to the same index cache, alternated")
     ap.add_argument("--mla", action="store_true", help="time flash_attention_mla_decode* beside the same problem from torch ops, alternated; --paged, --splits")
